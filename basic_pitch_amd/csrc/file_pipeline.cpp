@@ -544,6 +544,32 @@ void set_report(bp_file_report* r, int status, const std::string& msg) {
   std::snprintf(r->message, sizeof r->message, "%s", msg.c_str());
 }
 
+// A report's message field holds 239 characters.  A message that names two paths keeps its wording whatever their
+// length: a path that does not fit is shortened to "..." + its last characters (the file name stays), so that the reason
+// ("same file stem", "already exists") is never cut off.
+constexpr size_t kMessageChars = sizeof(bp_file_report::message) - 1;
+
+std::string path_tail(const std::string& p, size_t n) {
+  if (p.size() <= n) return p;
+  return n <= 3 ? p.substr(p.size() - n) : "..." + p.substr(p.size() - (n - 3));
+}
+
+std::string two_path_message(const std::string& t0, const std::string& p0, const std::string& t1, const std::string& p1,
+                             const std::string& t2) {
+  const size_t fixed = t0.size() + t1.size() + t2.size();
+  if (fixed + p0.size() + p1.size() <= kMessageChars) return t0 + p0 + t1 + p1 + t2;
+  const size_t room = kMessageChars > fixed ? kMessageChars - fixed : 0;
+  size_t n0 = room / 2, n1 = room - n0;  // a path shorter than its half leaves the rest to the other
+  if (p0.size() < n0) {
+    n1 += n0 - p0.size();
+    n0 = p0.size();
+  } else if (p1.size() < n1) {
+    n0 += n1 - p1.size();
+    n1 = p1.size();
+  }
+  return t0 + path_tail(p0, n0) + t1 + path_tail(p1, n1) + t2;
+}
+
 }  // namespace
 
 extern "C" {
@@ -690,7 +716,7 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
       if (seen.count(stem)) {
         dup[(size_t)i] = 1;
         set_report(&reports[i], BP_ERR_INVALID_ARG,
-                   std::string("the outputs of ") + paths[i] + " would overwrite those of " + paths[seen[stem]] + " (same file stem)");
+                   two_path_message("the outputs of ", paths[i], " would overwrite those of ", paths[seen[stem]], " (same file stem)"));
         reports[i].n_note_events = 0, reports[i].n_frames = 0;
         reports[i].ms_read = reports[i].ms_lane_wait = reports[i].ms_device = reports[i].ms_notes = reports[i].ms_write = 0.0f;
       } else {
@@ -743,7 +769,8 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
       const std::string base = std::string(out_dir) + "/" + stem_of(path) + "_basic_pitch.";
       // refuse before doing the work, like build_output_path
       if ((prm.save_midi && stat((base + "mid").c_str(), &st) == 0) || (prm.save_notes && stat((base + "csv").c_str(), &st) == 0)) {
-        set_report(rep, BP_ERR_INVALID_ARG, base + "* already exists and would be overwritten. Skipping output files for " + path + ".");
+        set_report(rep, BP_ERR_INVALID_ARG,
+                   two_path_message("", base + "*", " already exists and would be overwritten. Skipping output files for ", path, "."));
         continue;
       }
       size_t n_bytes = 0;

@@ -11,7 +11,17 @@ resident in HBM (BASELINE.json configs[1]: "Batch=256 synthetic 2 s @ 22.05 kHz 
 units: file/window sharding, no collective on the data path — SURVEY.md §8e), so scaling is weak
 and `value` = windows processed by all ranks / max-over-ranks time.
 
-Extra objects on the JSON line:
+A plain run does what `value` needs and no more: set-up, the sustained pre-pass `value` is measured behind (see
+`sustained` below), W warm-up steps, the K timed steps, the outputs of the last timed step when `--dump-outputs DIR` is
+given, and the JSON line.  `--full` adds everything else the line has carried: `value_cold`, the per-stage table and the
+rooflines, the exact-f32 A/B rate, two lanes, the other BASELINE.json configs, the batch-1 host seam and the CPU baseline.
+
+  --dump-outputs DIR  note.npy, onset.npy, contour.npy (float32): the three posteriorgrams of the last timed step for a
+                      fixed, seeded sample of the batch's windows (the same windows for all three, at most 60 MB in all; at
+                      batch 256, 198 of the 256 windows).  The input batch comes from a seeded generator: the same arguments
+                      give the same inputs in every run.
+
+Extra objects on the JSON line (--full):
   roofline      dominant kernel (contour_conv1_march_kernel: Conv2D 8->8 3x39, 65 % of the path's FLOPs): algorithmic FLOP
                 per launch / mean launch duration measured with HIP events on the kernel's stream over the
                 timed steps, against the dense f16 MFMA peak (2.5 PFLOP/s; the kernel spends three f16 MFMAs per
@@ -72,6 +82,23 @@ def pmc_traffic(kernel_key: str, batch: int):
         if kernel_key in k:
             return v["hbm_read_bytes"] + v["hbm_write_bytes"]
     return None
+
+
+DUMP_BUDGET_BYTES = 60_000_000  # --dump-outputs: all three arrays together
+DUMP_SEED = 0
+
+
+def dump_outputs(torch, out: dict, directory: str) -> None:
+    """The posteriorgrams of the last timed step as DIR/<name>.npy (float32).  A batch larger than the budget is
+    sampled: the same fixed, seeded, sorted choice of windows for every array, so two builds compare window by window."""
+    os.makedirs(directory, exist_ok=True)
+    n = next(iter(out.values())).shape[0]
+    per_window = sum(t[0].numel() * 4 for t in out.values())
+    k = min(n, DUMP_BUDGET_BYTES // per_window)
+    idx = np.arange(n) if k == n else np.sort(np.random.default_rng(DUMP_SEED).choice(n, size=k, replace=False))
+    for name, t in out.items():
+        sel = torch.as_tensor(idx, device=t.device)
+        np.save(os.path.join(directory, name + ".npy"), t.index_select(0, sel).float().cpu().numpy())
 
 
 def cpu_baseline(seconds_budget: float = 12.0) -> dict:
@@ -527,7 +554,15 @@ def main() -> None:
                          "has no collective, so the control path runs on CPU tensors over gloo by default")
     ap.add_argument("--bf16-weights", action="store_true",
                     help="BASELINE.json configs[3]: bf16 CNN weights + fp32 CQT (use with --batch 1024); not the headline line")
+    ap.add_argument("--full", action="store_true",
+                    help="windows workload: besides `value`, everything else the line reports (value_cold, stage table and "
+                         "rooflines, exact-f32 rate, two lanes, other configs, batch-1 host seam, CPU baseline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="windows workload: write the last timed step's posteriorgrams (a fixed, seeded sample of the "
+                         "batch's windows, float32) as DIR/{note,onset,contour}.npy")
     args = ap.parse_args()
+    if args.dump_outputs and args.workload != "windows":
+        raise SystemExit("--dump-outputs writes the windows workload's posteriorgrams: use it with --workload windows")
 
     if args.workload == "files" and args.native and args.lanes > 4:
         # the HIP runtime maps a process's streams onto FOUR hardware queues by default; kernels of lanes that share a queue
@@ -617,7 +652,8 @@ def main() -> None:
     }
     # The timed steps carry HIP events around the dominant kernel only (roofline.achieved is measured live there); the
     # full per-stage table costs 16 event records = ~25 us (2.6 %) per step and comes from a second, untimed pass.
-    # The exact-f32 A/B path has no dominant-only mode: it is timed with the full set.
+    # The exact-f32 A/B path has no dominant-only mode: it is timed with the full set.  A plain run keeps the same events,
+    # so that its timed steps are the ones --full times.
     model = Model(device=local_rank, max_windows=B, stage_timing=args.exact_f32, time_dominant=not args.exact_f32,
                   exact_f32_mfma=args.exact_f32, bf16_weights=args.bf16_weights, ext_cqt_44k=args.ext_cqt_44k)
 
@@ -632,8 +668,8 @@ def main() -> None:
     extras = {}
     # `value_cold`: the contract's W warm-up + K timed steps started on an idle GPU, as rounds 1 - 4 measured `value` — run
     # FIRST, on a handle of its own, so that both protocols are on every line and a round-to-round difference can be told
-    # from a protocol difference.  `value` itself is measured behind the sustained pass since round 5.
-    if not args.exact_f32 and args.sustained_s > 0:
+    # from a protocol difference.  `value` itself is measured behind the sustained pass since round 5.  --full only.
+    if args.full and not args.exact_f32 and args.sustained_s > 0:
         cold_model = Model(device=local_rank, max_windows=B, bf16_weights=args.bf16_weights, ext_cqt_44k=args.ext_cqt_44k)
         for _ in range(args.warmup):
             cold_model._predict_device(audio, out=out, sync=False)
@@ -690,7 +726,7 @@ def main() -> None:
         step()
     torch.cuda.synchronize()
     if args.warmup:
-        model.stage_ms()  # reset the per-stage accumulation
+        model.stage_ms()  # reset the per-stage accumulation (and the dominant-event sampling: the timed steps are --full's)
 
     if world > 1:
         dist.barrier()
@@ -702,10 +738,12 @@ def main() -> None:
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
-    stage = model.stage_ms()  # mean per-launch ms over the timed steps (HIP events on the kernels' stream)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(torch, out, args.dump_outputs)  # before anything below writes `out` again
+    stage = model.stage_ms() if args.full else None  # mean per-launch ms over the timed steps (HIP events on the kernels' stream)
     if sus_model is not None:
         sus_model.close()  # after the timed steps: freeing a gigabyte of device buffers idles the GPU for milliseconds
-    if not args.exact_f32 and rank == 0:
+    if args.full and not args.exact_f32 and rank == 0:
         # untimed second pass with events around every stage (same inputs, same kernels); the dominant kernel's entry
         # stays the one measured inside the timed region
         dom = {k: v for k, v in stage.items() if v > 0.0}
@@ -730,7 +768,8 @@ def main() -> None:
     ok = bool(torch.isfinite(out["note"]).all() and torch.isfinite(out["onset"]).all() and torch.isfinite(out["contour"]).all())
 
     # (2) rank 0 only, the exact-f32 A/B path's rate on the same batch.
-    if not args.exact_f32 and not args.no_exact_f32 and rank == 0 and not (args.bf16_weights or args.ext_cqt_44k):
+    if (args.full and not args.exact_f32 and not args.no_exact_f32 and rank == 0
+            and not (args.bf16_weights or args.ext_cqt_44k)):
         ex_model = Model(device=local_rank, max_windows=B, exact_f32_mfma=True)
         for _ in range(2):
             ex_model._predict_device(audio, out=out, sync=False)
@@ -741,7 +780,7 @@ def main() -> None:
         torch.cuda.synchronize()
         extras["exact_f32_windows_per_s"] = B * 8 / (time.perf_counter() - t0)
         ex_model.close()
-    if (not args.exact_f32 and not args.no_config_extras and rank == 0 and world == 1
+    if (args.full and not args.exact_f32 and not args.no_config_extras and rank == 0 and world == 1
             and not (args.bf16_weights or args.ext_cqt_44k)):
         # beside the headline: two handles on two streams taking alternate batches — what a service with two lanes gets
         # (the kernels of one batch run under the launch gaps and tails of the other's; per-kernel times are no longer
@@ -770,44 +809,6 @@ def main() -> None:
     if rank == 0:
         total_windows = B * args.steps * world
         value = total_windows / elapsed
-        if args.exact_f32:
-            c1_ms = stage["contour1"]
-            c1_flop = C1_FLOP_PER_WINDOW
-            c1_kernel = "contour1_kernel (Conv2D 8->8 3x39 + norm/BN/stack; exact-f32 MFMA 32x32x2)"
-            c1_peak = F32_MFMA_PEAK_TFLOPS
-            c1_exec = 355 * 504 * (2 * 32 * 32 * 2) * B / (c1_ms * 1e-3) / 1e12
-            c1_bytes = None
-            c1_key = None
-        else:
-            c1_ms = stage["contour_conv1"]
-            folded = stage.get("contour_conv1_edge", 0.0) > 0.0
-            mf = (2 / 3 if args.bf16_weights else 1)
-            if folded and os.environ.get("BP_CONV1") != "rounds":
-                c1_flop = C1_FLOP_PER_WINDOW * F1_SHARE
-                c1_kernel = ("contour_conv1_march_kernel (interior 56/66 of harmonic stack + Conv2D 8->8 3x39 + ReLU with the 8 "
-                             "shifted channels folded into one 176-tap kernel; wave-private vertical march on f16 MFMA 16x16x32: "
-                             "hi/lo-split weights resident in registers, each z fragment read once from LDS for all three frame "
-                             "taps, fp32 accumulate; algorithmic FLOPs = the reference's 8-channel products it replaces)")
-                c1_exec = M1_EXECUTED_FLOP_PER_WINDOW * mf * B / (c1_ms * 1e-3) / 1e12
-                c1_bytes = F1_BYTES_PER_WINDOW * B
-                c1_key = "contour_conv1_march_kernel"
-            elif folded:
-                c1_flop = C1_FLOP_PER_WINDOW * F1_SHARE
-                c1_kernel = ("contour_conv1_folded_kernel (interior 56/66 of harmonic stack + Conv2D 8->8 3x39 + ReLU with the 8 "
-                             "shifted channels folded into one 176-tap kernel; f16 MFMA 32x32x16 on hi/lo-split operands from "
-                             "LDS, fp32 accumulate; algorithmic FLOPs = the reference's 8-channel products it replaces)")
-                c1_exec = F1_EXECUTED_FLOP_PER_WINDOW * mf * B / (c1_ms * 1e-3) / 1e12
-                c1_bytes = F1_BYTES_PER_WINDOW * B
-                c1_key = "contour_conv1_folded_kernel"
-            else:
-                c1_flop = C1_FLOP_PER_WINDOW
-                c1_kernel = ("contour_conv1_kernel<FullGeo> (harmonic stack + Conv2D 8->8 3x39 + ReLU; f16 MFMA 32x32x16 on "
-                             "hi/lo-split operands from LDS, fp32 accumulate, no K split)")
-                c1_exec = D1_EXECUTED_FLOP_PER_WINDOW * mf * B / (c1_ms * 1e-3) / 1e12
-                c1_bytes = D1_BYTES_PER_WINDOW * B
-                c1_key = "contour_conv1_kernel"
-            c1_peak = F16_MFMA_PEAK_TFLOPS
-        achieved = c1_flop * B / (c1_ms * 1e-3) / 1e12
         line = {
             "metric": "audio windows/sec (2 s @ 44.1 kHz) end-to-end CQT+CNN" if args.ext_cqt_44k
             else "audio windows/sec (2 s @ 22.05 kHz) end-to-end CQT+CNN",
@@ -837,72 +838,114 @@ def main() -> None:
                 **({"share_gpu": "all ranks on device 0 (functional check of the N > 1 path, not a scaling number)"}
                    if args.share_gpu else {}),
             },
-            "roofline": {
-                "kernel": c1_kernel,
-                "bound": "mfma",
-                "achieved": achieved,
-                "peak": c1_peak,
-                "unit": "TFLOP/s",
-                "frac": achieved / c1_peak,
-                "traffic": pmc_traffic(c1_key, B) if c1_key else None,
-                "traffic_unit": "bytes per launch (PMC, profiles/%s_pmc.md)" % PMC_PROFILE,
-                # the kernel's own ratio above is ~1; the STEP moves far more than the path's algorithmic I/O (c1 round trip,
-                # pyramid planes, lp): that ratio belongs on the line too
-                "step_traffic": pmc_step_traffic(B) if c1_key else None,
-                # what THIS kernel reads and writes by construction (zp in, the materialised 8-channel c1 out): an
-                # implementation choice, not the algorithm's I/O ...
-                "kernel_io_bytes_per_launch": c1_bytes,
-                # ... which for the whole contour branch (conv1 + conv2; c1 never needs to exist) is the 172 x 309 fp32 CQT
-                # in and the 172 x 264 fp32 contour map out
-                "branch_algorithmic_bytes_per_launch": (172 * 309 * 4 + 172 * 264 * 4) * B,
-                "executed_mfma_tflops": c1_exec,  # incl. the 3-product split and Toeplitz padding
-                "executed_frac": c1_exec / c1_peak,
-                "launch_ms": c1_ms,
-                "algorithmic_flop_per_launch": c1_flop * B,
-            },
-            "path_roofline": {
-                "flop_frac_f16_peak": FLOP_PER_WINDOW * value / world / (F16_MFMA_PEAK_TFLOPS * 1e12),
-                "hbm_frac_algorithmic": BYTES_PER_WINDOW * value / world / (HBM_PEAK_GBS * 1e9),
-            },
-            "stage_ms": stage,
-            "stage_ms_note": "per-stage HIP-event means from a second untimed pass (16 event records per step cost ~2.6 %); "
-                             "the dominant kernel's entry is the one measured inside the timed steps"
-                             + ("" if stage_all_pass is None or c1_key is None else
-                                f" (second pass: {stage_all_pass.get('contour_conv1', stage_all_pass.get('contour', 0.0)):.4f} ms)"),
             "outputs_finite": ok,
         }
-        if not args.ext_cqt_44k:
-            # the CQT stage (a7-a9: pyramid + filterbank + NormalizedLog; since round 3 the filterbank
-            # launch also normalises, BatchNorms and splits the windows it owns — `zpack` is a stage of its own only when a
-            # launch has fewer windows than CUs) against both of its rooflines; algorithmic 79,425,024 FLOP and 387,968 B
-            # (audio in + 172x309 fp32 out) per window
-            cqt_ms = stage["pyramid"] + stage["filterbank"] + stage.get("zpack", 0.0)
-            cqt_rate = B / (cqt_ms * 1e-3)
-            # ceilings per window: HBM 387,968 B at 8 TB/s; split-f16 MFMA = 3 products x the dense matrices the two
-            # kernels execute (decimators 22.4 MFLOP, filterbank 57.1 MFLOP clipped to the kernels' support) at the
-            # 2.5 PFLOP/s f16 peak.  The matrix ceiling is the lower (binding) one.
-            cqt_mfma_flop = 3 * (22_361_088 + 57_063_936)
-            line["cqt_stage"] = {
-                "ms": cqt_ms,
-                "includes": "pyramid (planes) + filterbank + normalise / BatchNorm / split (zpack, fused into the filterbank "
-                            "launch at this batch)",
-                "windows_per_s": cqt_rate,
-                "hbm_fraction": 387_968 * cqt_rate / (HBM_PEAK_GBS * 1e9),
-                "mfma_split_f16_fraction": cqt_mfma_flop * cqt_rate / (F16_MFMA_PEAK_TFLOPS * 1e12),
-                "binding": "split-f16 MFMA (3 products per multiply): its ceiling, 10.5 M windows/s, lies below the HBM "
-                           "ceiling of 20.6 M windows/s",
-                "algorithmic_bytes_per_window": 387_968,
-                "algorithmic_flop_per_window": 79_425_024,
-            }
+        if args.full:
+            # the per-stage table and the rooflines: the dominant kernel's events of the timed steps + the second pass
+            if args.exact_f32:
+                c1_ms = stage["contour1"]
+                c1_flop = C1_FLOP_PER_WINDOW
+                c1_kernel = "contour1_kernel (Conv2D 8->8 3x39 + norm/BN/stack; exact-f32 MFMA 32x32x2)"
+                c1_peak = F32_MFMA_PEAK_TFLOPS
+                c1_exec = 355 * 504 * (2 * 32 * 32 * 2) * B / (c1_ms * 1e-3) / 1e12
+                c1_bytes = None
+                c1_key = None
+            else:
+                c1_ms = stage["contour_conv1"]
+                folded = stage.get("contour_conv1_edge", 0.0) > 0.0
+                mf = (2 / 3 if args.bf16_weights else 1)
+                if folded and os.environ.get("BP_CONV1") != "rounds":
+                    c1_flop = C1_FLOP_PER_WINDOW * F1_SHARE
+                    c1_kernel = ("contour_conv1_march_kernel (interior 56/66 of harmonic stack + Conv2D 8->8 3x39 + ReLU with the 8 "
+                                 "shifted channels folded into one 176-tap kernel; wave-private vertical march on f16 MFMA 16x16x32: "
+                                 "hi/lo-split weights resident in registers, each z fragment read once from LDS for all three frame "
+                                 "taps, fp32 accumulate; algorithmic FLOPs = the reference's 8-channel products it replaces)")
+                    c1_exec = M1_EXECUTED_FLOP_PER_WINDOW * mf * B / (c1_ms * 1e-3) / 1e12
+                    c1_bytes = F1_BYTES_PER_WINDOW * B
+                    c1_key = "contour_conv1_march_kernel"
+                elif folded:
+                    c1_flop = C1_FLOP_PER_WINDOW * F1_SHARE
+                    c1_kernel = ("contour_conv1_folded_kernel (interior 56/66 of harmonic stack + Conv2D 8->8 3x39 + ReLU with the 8 "
+                                 "shifted channels folded into one 176-tap kernel; f16 MFMA 32x32x16 on hi/lo-split operands from "
+                                 "LDS, fp32 accumulate; algorithmic FLOPs = the reference's 8-channel products it replaces)")
+                    c1_exec = F1_EXECUTED_FLOP_PER_WINDOW * mf * B / (c1_ms * 1e-3) / 1e12
+                    c1_bytes = F1_BYTES_PER_WINDOW * B
+                    c1_key = "contour_conv1_folded_kernel"
+                else:
+                    c1_flop = C1_FLOP_PER_WINDOW
+                    c1_kernel = ("contour_conv1_kernel<FullGeo> (harmonic stack + Conv2D 8->8 3x39 + ReLU; f16 MFMA 32x32x16 on "
+                                 "hi/lo-split operands from LDS, fp32 accumulate, no K split)")
+                    c1_exec = D1_EXECUTED_FLOP_PER_WINDOW * mf * B / (c1_ms * 1e-3) / 1e12
+                    c1_bytes = D1_BYTES_PER_WINDOW * B
+                    c1_key = "contour_conv1_kernel"
+                c1_peak = F16_MFMA_PEAK_TFLOPS
+            achieved = c1_flop * B / (c1_ms * 1e-3) / 1e12
+            line.update({
+                "roofline": {
+                    "kernel": c1_kernel,
+                    "bound": "mfma",
+                    "achieved": achieved,
+                    "peak": c1_peak,
+                    "unit": "TFLOP/s",
+                    "frac": achieved / c1_peak,
+                    "traffic": pmc_traffic(c1_key, B) if c1_key else None,
+                    "traffic_unit": "bytes per launch (PMC, profiles/%s_pmc.md)" % PMC_PROFILE,
+                    # the kernel's own ratio above is ~1; the STEP moves far more than the path's algorithmic I/O (c1 round trip,
+                    # pyramid planes, lp): that ratio belongs on the line too
+                    "step_traffic": pmc_step_traffic(B) if c1_key else None,
+                    # what THIS kernel reads and writes by construction (zp in, the materialised 8-channel c1 out): an
+                    # implementation choice, not the algorithm's I/O ...
+                    "kernel_io_bytes_per_launch": c1_bytes,
+                    # ... which for the whole contour branch (conv1 + conv2; c1 never needs to exist) is the 172 x 309 fp32 CQT
+                    # in and the 172 x 264 fp32 contour map out
+                    "branch_algorithmic_bytes_per_launch": (172 * 309 * 4 + 172 * 264 * 4) * B,
+                    "executed_mfma_tflops": c1_exec,  # incl. the 3-product split and Toeplitz padding
+                    "executed_frac": c1_exec / c1_peak,
+                    "launch_ms": c1_ms,
+                    "algorithmic_flop_per_launch": c1_flop * B,
+                },
+                "path_roofline": {
+                    "flop_frac_f16_peak": FLOP_PER_WINDOW * value / world / (F16_MFMA_PEAK_TFLOPS * 1e12),
+                    "hbm_frac_algorithmic": BYTES_PER_WINDOW * value / world / (HBM_PEAK_GBS * 1e9),
+                },
+                "stage_ms": stage,
+                "stage_ms_note": "per-stage HIP-event means from a second untimed pass (16 event records per step cost ~2.6 %); "
+                                 "the dominant kernel's entry is the one measured inside the timed steps"
+                                 + ("" if stage_all_pass is None or c1_key is None else
+                                    f" (second pass: {stage_all_pass.get('contour_conv1', stage_all_pass.get('contour', 0.0)):.4f} ms)"),
+            })
+            if not args.ext_cqt_44k:
+                # the CQT stage (a7-a9: pyramid + filterbank + NormalizedLog; since round 3 the filterbank
+                # launch also normalises, BatchNorms and splits the windows it owns — `zpack` is a stage of its own only when a
+                # launch has fewer windows than CUs) against both of its rooflines; algorithmic 79,425,024 FLOP and 387,968 B
+                # (audio in + 172x309 fp32 out) per window
+                cqt_ms = stage["pyramid"] + stage["filterbank"] + stage.get("zpack", 0.0)
+                cqt_rate = B / (cqt_ms * 1e-3)
+                # ceilings per window: HBM 387,968 B at 8 TB/s; split-f16 MFMA = 3 products x the dense matrices the two
+                # kernels execute (decimators 22.4 MFLOP, filterbank 57.1 MFLOP clipped to the kernels' support) at the
+                # 2.5 PFLOP/s f16 peak.  The matrix ceiling is the lower (binding) one.
+                cqt_mfma_flop = 3 * (22_361_088 + 57_063_936)
+                line["cqt_stage"] = {
+                    "ms": cqt_ms,
+                    "includes": "pyramid (planes) + filterbank + normalise / BatchNorm / split (zpack, fused into the filterbank "
+                                "launch at this batch)",
+                    "windows_per_s": cqt_rate,
+                    "hbm_fraction": 387_968 * cqt_rate / (HBM_PEAK_GBS * 1e9),
+                    "mfma_split_f16_fraction": cqt_mfma_flop * cqt_rate / (F16_MFMA_PEAK_TFLOPS * 1e12),
+                    "binding": "split-f16 MFMA (3 products per multiply): its ceiling, 10.5 M windows/s, lies below the HBM "
+                               "ceiling of 20.6 M windows/s",
+                    "algorithmic_bytes_per_window": 387_968,
+                    "algorithmic_flop_per_window": 79_425_024,
+                }
         line.update(extras)
-        if (not args.no_config_extras and not args.exact_f32
+        if (args.full and not args.no_config_extras and not args.exact_f32
                 and not (args.bf16_weights or args.ext_cqt_44k) and B == BATCH):
             model.close()
             del audio, out
             torch.cuda.empty_cache()
             line["configs"] = config_extras(torch, local_rank)
             line["seam_b1_host"] = seam_b1_host()
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline()  # rank 0's host cores, after the timed region, for any N
         print(json.dumps(line), flush=True)
     if world > 1:

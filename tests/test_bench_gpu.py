@@ -30,7 +30,7 @@ def _json_lines(text):
 
 def test_bench_two_ranks_share_one_gpu():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--steps", "3", "--warmup", "1",
-           "--no-cpu-baseline", "--no-exact-f32", "--no-fp8-extra", "--sustained-s", "0"]
+           "--no-cpu-baseline", "--no-exact-f32", "--no-fp8-extra", "--sustained-s", "0", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-4000:]
     lines = _json_lines(res.stdout)
@@ -45,7 +45,7 @@ def test_bench_two_ranks_share_one_gpu():
 
 def test_bench_single_rank_line_has_the_contract_keys():
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "1", "--no-cpu-baseline",
-           "--sustained-s", "0"]
+           "--sustained-s", "0", "--full"]
     res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     assert res.returncode == 0, res.stderr[-4000:]
     (line,) = _json_lines(res.stdout)
@@ -67,6 +67,43 @@ def test_bench_single_rank_line_has_the_contract_keys():
     assert line["seam_b1_host"]["windows_per_s"] > 0 and line["seam_b1_host"]["ms_per_call"] > 0
     st = r["step_traffic"]
     assert st is None or (st["ratio"] > 1.0 and st["bytes_per_step"] > st["algorithmic_bytes_per_step"])
+
+
+def test_bench_plain_run_is_the_headline_alone_and_dumps_its_outputs(tmp_path):
+    """A plain run (no --full) times the K steps it is given and reports the headline alone; --dump-outputs writes the
+    last timed step's posteriorgrams (a seeded sample of the batch, float32, at most 64 MB), and the same arguments give
+    bit-identical files in a second run (the same seeded inputs through a deterministic path)."""
+    import numpy as np
+
+    lines, dumps = [], []
+    for run in ("a", "b"):
+        cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "8", "--warmup", "2",
+               "--sustained-s", "0.5", "--dump-outputs", str(tmp_path / run)]
+        res = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
+        assert res.returncode == 0, res.stderr[-4000:]
+        (line,) = _json_lines(res.stdout)
+        lines.append(line)
+        dumps.append({k: np.load(str(tmp_path / run / f"{k}.npy")) for k in ("note", "onset", "contour")})
+    line = lines[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in line, k
+    assert line["steps"] == 8 and line["warmup"] == 2 and line["unit"] == "windows/s" and line["higher_is_better"] is True
+    assert abs(line["value"] - 256 * 8 / (line["ms_per_step"] * 8e-3)) <= 1e-6 * line["value"]
+    # --steps sets the timed steps: the timed loop's time per step agrees with the one of the sustained pass (the same
+    # step, timed in a loop of its own); a loop of another length divided by 8 would be off by that ratio
+    sus = line["sustained"]
+    assert sus["steps"] >= 8 and 0.5 < line["ms_per_step"] / sus["ms_per_step"] < 2.0, (line["ms_per_step"], sus)
+    for k in ("value_cold", "roofline", "stage_ms", "exact_f32_windows_per_s", "two_lanes", "configs", "seam_b1_host",
+              "cpu_baseline"):
+        assert k not in line, k  # --full only
+    a, b = dumps
+    assert sum(os.path.getsize(str(tmp_path / "a" / f"{k}.npy")) for k in a) <= 64_000_000
+    n = a["note"].shape[0]
+    assert 0 < n <= 256 and a["note"].shape == a["onset"].shape == (n, 172, 88) and a["contour"].shape == (n, 172, 264)
+    for k in a:
+        assert a[k].dtype == np.float32 and np.isfinite(a[k]).all(), k
+        assert a[k].min() >= 0.0 and a[k].max() <= 1.0 and a[k].max() > a[k].min(), k  # sigmoid posteriorgrams
+        assert np.array_equal(a[k], b[k]), k
 
 
 def test_library_then_torch_share_one_hip_runtime():

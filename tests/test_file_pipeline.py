@@ -199,6 +199,36 @@ def test_transcribe_files_equals_predict_and_save(tmp_path):
 
 
 @pytest.mark.gpu
+def test_transcribe_files_reports_keep_their_reason_with_long_paths(tmp_path):
+    """A report's message is a fixed-size field (239 characters).  With paths longer than that the messages keep their
+    wording and their reason ("same file stem", "already exists": what sharding.py maps to IOError); the paths in them are
+    shortened to their last characters.  test_transcribe_files_equals_predict_and_save met this under a long TMPDIR."""
+    from basic_pitch_amd import Model, transcribe_files
+
+    deep = tmp_path / ("d" * 120) / ("e" * 120)
+    (deep / "sub").mkdir(parents=True)
+    t = np.arange(22050) / 22050.0
+    for p in (deep / "a.wav", deep / "sub" / "a.wav"):
+        with wave.open(str(p), "wb") as w:
+            w.setnchannels(1), w.setsampwidth(2), w.setframerate(22050)
+            w.writeframes((0.3 * np.sin(2 * np.pi * 330.0 * t) * 32767).astype("<i2").tobytes())
+    out = tmp_path / ("o" * 200)
+    out.mkdir()
+    model = Model(max_windows=16)
+    rep = transcribe_files([deep / "a.wav", deep / "sub" / "a.wav"], out, models=[model])
+    assert rep[0]["status"] == 0 and rep[1]["status"] != 0, rep
+    m = rep[1]["message"]
+    assert len(m) <= 239 and m.startswith("the outputs of ...") and " would overwrite those of ..." in m, m
+    assert m.endswith("e" * 40 + "/a.wav (same file stem)") and ("e" * 40 + "/sub/a.wav would overwrite") in m, m
+    again = transcribe_files([deep / "a.wav"], out, models=[model])
+    m = again[0]["message"]
+    assert again[0]["status"] != 0 and len(m) <= 239 and m.startswith("..."), again
+    assert ("o" * 40 + "/a_basic_pitch.* already exists and would be overwritten. Skipping output files for ...") in m, m
+    assert m.endswith("e" * 40 + "/a.wav."), m
+    model.close()
+
+
+@pytest.mark.gpu
 def test_sharded_batch_job_through_the_native_pipeline(tmp_path):
     """predict_and_save_sharded(native=True): two worker processes on the one GPU, each running its LPT shard through
     bp_transcribe_files; same bytes as the single-process Python job, reports in input order."""
