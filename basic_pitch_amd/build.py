@@ -18,6 +18,7 @@ HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd.h")
 
 SOURCES = [
     "bp_api.hip",
+    "track_api.hip",
     "cqt_pyramid.hip",
     "cqt_filterbank.hip",
     "cqt_planes.hip",
@@ -60,7 +61,7 @@ def _stale(ab: bool = False) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = _sources(ab) + [os.path.join(CSRC, "bp_common.h"), HEADER]
+    deps = _sources(ab) + [os.path.join(CSRC, "bp_common.h"), os.path.join(CSRC, "bp_context.h"), HEADER]
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
@@ -102,7 +103,7 @@ def build_library(force: bool = False, verbose: bool = False, ab: bool = False) 
     hipcc = find_hipcc()
     obj_dir = os.path.join(LIB_DIR, "obj_ab" if ab else "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    headers = [os.path.join(CSRC, "bp_common.h"), HEADER]
+    headers = [os.path.join(CSRC, "bp_common.h"), os.path.join(CSRC, "bp_context.h"), HEADER]
     t_hdr = max(os.path.getmtime(h) for h in headers if os.path.exists(h))
     flags = FLAGS + (["-DBP_AB_KERNELS"] if ab else [])
 

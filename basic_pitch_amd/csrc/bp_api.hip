@@ -4,31 +4,16 @@
 // Replaces, for the hot path only, what the reference delegates to TensorFlow / onnxruntime /
 // TFLite / CoreML behind basic_pitch/inference.py:71-182 (Model) and the window loop of
 // run_inference (inference.py:282-315).
-#include "../../include/basic_pitch_amd.h"
-
 #include <cmath>
-#include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <ctime>
-#include <string>
-#include <vector>
 
-#include "bp_common.h"
+#include "bp_context.h"
 
 namespace bp {
 // kernels (one translation unit each)
 void launch_pyramid(const float* audio, float* pyr, const float* lowpass, int n_windows, hipStream_t s);
-void launch_window_track(const float* samples, int64_t n_samples, int64_t first_window, int n_windows,
-                         float* audio, int win_len, int hop, int lead, hipStream_t stream);
-void launch_window_tracks(const TrackSegs& ts, int n_slots, float* audio, int win_len, int hop, int lead,
-                          hipStream_t stream);
-void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
-                          hipStream_t stream);
-void launch_unwrap3(const float* note, const float* onset, const float* contour, int64_t first_window, int n_windows,
-                    int64_t total_rows, float* o_note, float* o_onset, float* o_contour, hipStream_t stream);
-void launch_unwrap(const float* win_out, int n_freq, int64_t first_window, int n_windows,
-                   int64_t total_rows, float* out, hipStream_t s);
 size_t filterbank_scratch_floats(int n_windows);
 void launch_filterbank(const float* audio, const float* pyr, const float* bfrag, const float* sqrt_len,
                        float* lp, int* mm, float* scratch, int n_windows, LogConsts kc, int n_cu,
@@ -65,11 +50,6 @@ bool launch_filterbank_planes(const uint16_t* pl, const float* audio, int64_t au
 void filterbank_planes_bin_consts(const float* sqrt_len, int n_bins, LogConsts kc, float* out);
 void launch_zpack(const float* lp, const int* mm, uint32_t* zp, int n_windows, LogConsts kc, int n_bins,
                   hipStream_t s);
-ResamplePlan make_resample_plan(int source_rate, int target_rate, std::vector<double>& taps);
-void launch_downmix(const float* pcm, int64_t n_frames, int channels, float* mono, hipStream_t stream);
-void launch_downmix_raw(const void* raw, int format, int64_t n_frames, int channels, float* mono, hipStream_t stream);
-void launch_resample(const float* x, int64_t n_in, const double* taps, const ResamplePlan& pl, float* y,
-                     int64_t n_out, int mode, hipStream_t stream);
 #ifdef BP_AB_KERNELS  // conv_contour_direct.hip: the exact 8-channel and the round-2 folded conv1 (A/B builds only)
 void launch_contour_conv1_exact(const uint32_t* zp, const void* wlds, const float* bias, float* c1, int n_windows,
                                 int n_cu, bool weights_have_lo, hipStream_t stream);
@@ -102,42 +82,12 @@ void launch_contour_conv2(const float* c1, const float* w2, float bias, float* c
 #endif
 void launch_contour_conv2_proj(const float* c1, const void* wfrag, float bias, float* contour, int n_windows, int n_cu,
                                bool weights_have_lo, hipStream_t stream);
-// flac_device.hip
-struct FdStream {
-  int channels, bits, min_block, max_block;
-  int64_t total;
-  uint32_t audio_start, nbytes;
-};
-struct FlacDeviceBuffers {
-  uint8_t* file = nullptr;
-  size_t file_cap = 0;
-  void* cands = nullptr;
-  uint32_t* counts = nullptr;
-  size_t cands_cap = 0, counts_cap = 0;
-  void* packed = nullptr;
-  uint32_t* offs = nullptr;
-  size_t packed_cap = 0, offs_cap = 0;
-  void* frames = nullptr;
-  int32_t* scratch = nullptr;
-  size_t frames_cap = 0, scratch_cap = 0;
-  int* meta = nullptr;
-  uint16_t* crc_tab = nullptr;
-};
-int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream);
-void flac_device_free(FlacDeviceBuffers& b);
 #ifdef BP_AB_KERNELS  // note_march.hip: the 32x32x16 form of the note march (A/B builds only)
 void launch_note_march(const float* contour, const void* wfrag, const float* wf32, float* note, int n_windows,
                        bool weights_have_lo, hipStream_t stream);
 #endif
 void launch_note_march16(const float* contour, const void* wfrag, const float* wf32, float* note, int n_windows, int n_cu,
                          bool weights_have_lo, hipStream_t stream);
-void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,
-                            double onset_thresh, const void* tab, const double* gauss, void* stats, uint8_t* bits,
-                            int8_t* bend, hipStream_t s);
-void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, const void* bits, void* bits_dst,
-                        int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
-                        void* stats_dst, hipStream_t s);
-void launch_note_stats_init(void* stats, hipStream_t s);
 #ifdef BP_AB_KERNELS
 void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* wmx,
                          float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
@@ -280,99 +230,8 @@ bool expect(const Blob& b, const char* name, std::initializer_list<uint32_t> sha
 
 }  // namespace
 
-struct bp_context {
-  int device = 0;
-  unsigned flags = 0;
-  int n_cu = 256;
-  char arch[32] = {0};
-  hipStream_t own_stream = nullptr, stream = nullptr;
-  hipEvent_t done = nullptr;  // BP_FLAG_BLOCKING_WAIT: the event a waiting host thread sleeps on
-  int64_t cap = 0;
-  int64_t workspace_bytes = 0;
-  std::string err;
+namespace bp {
 
-  // window geometry: the reference's 22.05 kHz model, or the extended 44.1 kHz range (BP_FLAG_EXT_CQT_44K)
-  bool ext = false;
-  int win_len = kAudioN, hop = BP_HOP_SIZE, lead = BP_OVERLAP_LEN / 2, n_bins = kBins, rate = BP_AUDIO_SAMPLE_RATE;
-  int64_t pyr_stride = kPyrStride;
-
-  LogConsts kc{};
-  float b_contour2 = 0, b_note2 = 0, b_onset2 = 0;
-  // device constants
-  float *d_lowpass = nullptr, *d_sqrt_len = nullptr, *d_fb_bfrag = nullptr;
-  float* d_pl_bin_k = nullptr;  // cqt_planes.hip filterbank: per-bin eps / s^2, s = sqrt(len) 2^-12
-  // fused branches (conv_branch.hip): f16 hi/lo A fragments (raw bytes) + {bias1[32], extra[9], bias2}
-  float *d_note_wfrag = nullptr, *d_note_w16 = nullptr, *d_note_wf32 = nullptr, *d_onset_wfrag = nullptr, *d_onset_wf32 = nullptr,
-        *d_onset_wmx = nullptr, *d_onset_w16 = nullptr;
-  float* zp = nullptr;  // uint32 [cap][kZRowsP][kZRow] pre-split z, zero padded (bp_common.h)
-  // contour branch, two-kernel form (conv_contour_direct.hip): LDS weight image, bias[8], conv2 taps [5][5][8]
-  float *d_d1_wlds = nullptr, *d_d1_wfold = nullptr, *d_d1_wmarch = nullptr, *d_d1_wrim = nullptr, *d_d1_wrimm = nullptr, *d_d1_bias = nullptr,
-        *d_d2_w = nullptr, *d_d2_wproj = nullptr;
-  bool rim_exact = false, fold_mx = false;
-  int resample_mode = 0;  // BP_RESAMPLE=plain|tiled: 1 | 2 (A/B runs of the resampling kernels)
-  int contour_parts = 0;  // BP_CONTOUR_PARTS (0: automatic)
-  float* d_d1_wfold_mx = nullptr;
-  float* c1s = nullptr;  // [cap][172][kC1Row][8] relu(conv1); pad bins zeroed once at allocation
-  // cqt_planes.hip: decimator / filterbank fragments (raw bytes of f16 hi / lo), the planes of a chunk [cap][2][stride] f16
-  float *d_pl_tfrag = nullptr, *d_pl_bfrag = nullptr, *planes = nullptr;
-  float *d_c1_bfrag = nullptr, *d_c1_bias = nullptr, *d_o1_bfrag = nullptr, *d_o1_bias = nullptr;
-  float *d_n1_bfrag = nullptr, *d_n1_bias = nullptr, *d_w_contour2 = nullptr, *d_w_note2 = nullptr,
-        *d_w_onset2 = nullptr;
-  // workspace (per chunk of `cap` windows)
-  float *audio = nullptr, *pyr = nullptr, *lp = nullptr, *c1 = nullptr, *contour = nullptr, *n1 = nullptr,
-        *note = nullptr, *o1 = nullptr, *onset = nullptr;
-  int* mm = nullptr;
-  float* fb_scratch = nullptr;  // filterbank partial extrema (grow-only; >= cap windows)
-  int64_t fb_scratch_windows = 0;
-  // track path staging (grow-only)
-  float* track = nullptr;
-  int64_t track_cap = 0;
-  // audio ingest (audio_ingest.hip): staging for PCM / mono / 22.05 kHz signal (grow-only), cached filter
-  float *pcm_dev = nullptr, *mono_dev = nullptr, *res_dev = nullptr;
-  int64_t pcm_cap = 0, mono_cap = 0, res_cap = 0;
-  double* taps_dev = nullptr;
-  int taps_rate = 0;
-  ResamplePlan plan{};
-  float* track_out = nullptr;  // [T, 88+88+264] staging when outputs are host pointers
-  int64_t track_out_cap = 0;
-  int64_t maps_rows = 0;       // rows of the maps a *_candidates call left in track_out (bp_track_maps); 0: none
-  // device-side note candidates (note_device.hip): bitmap [T][11] + bend map [T][88] (bytes), stats, the bend tables
-  float* nd_buf = nullptr;
-  int64_t nd_cap = 0;          // floats
-  float* nd_tables = nullptr;  // [88] int4 windows, [51] double Gaussian, then the stats record
-  FlacDeviceBuffers fd;            // flac_device.hip: the file's bytes, the frame lists, the scratch rows
-  int* fd_status_host = nullptr;   // page-locked: the device decoder's error bits of the last call
-  float* nd_stats_host = nullptr;  // page-locked copy of the stats record
-  void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
-  bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
-
-  // stage timing: a ring of event sets, one per chunk, averaged by bp_get_stage_ms
-  static constexpr int kTimedRing = 128;
-  static constexpr int kDomEvery = 4;
-  static constexpr int kMaxMarks = 32;  // a stage may be launched in parts (the contour branch): its intervals are summed
-  hipEvent_t ev[kTimedRing][kMaxMarks + 1] = {};
-  // per ring slot (the mark sequence depends on the chunk: zpack only below half a window per CU, contour parts):
-  // stage id of the interval between ev[c][i] and ev[c][i+1]; -1: not a stage (skipped)
-  int seq[kTimedRing][kMaxMarks] = {};
-  int n_seq[kTimedRing] = {};
-  bool ev_valid = false;
-  int64_t timed_chunks = 0;  // chunks recorded since the last bp_get_stage_ms
-  int64_t dom_chunks = 0;    // chunks seen in BP_FLAG_TIME_DOMINANT mode (every kDomEvery-th is recorded)
-};
-
-#define BP_HIP(call)                                                                       \
-  do {                                                                                     \
-    hipError_t e_ = (call);                                                                \
-    if (e_ != hipSuccess) {                                                                \
-      char buf_[512];                                                                      \
-      std::snprintf(buf_, sizeof buf_, "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), \
-                    __FILE__, __LINE__);                                                   \
-      h->err = buf_;                                                                       \
-      return (e_ == hipErrorOutOfMemory) ? BP_ERR_OUT_OF_MEMORY : BP_ERR_HIP;              \
-    }                                                                                      \
-  } while (0)
-
-namespace {
 
 int upload(bp_handle h, const std::vector<float>& host, float** dev) {
   BP_HIP(hipMalloc(dev, host.size() * sizeof(float)));
@@ -386,6 +245,10 @@ int alloc(bp_handle h, float** p, int64_t floats) {
   h->workspace_bytes += floats * sizeof(float);
   return BP_OK;
 }
+
+}  // namespace bp
+
+namespace {
 
 // ---- operand packing -----------------------------------------------------------------------
 // Filterbank B fragments [4 roles][55 steps][64 lanes] (cqt_filterbank.hip roles; 16x16x4: lane ->
@@ -1009,6 +872,10 @@ static void launch_rim(bp_handle h, const uint32_t* zp, float* c1, int n, bool w
     launch_contour_conv1_rim_march(zp, h->d_d1_wrimm, h->d_d1_bias, c1, n, h->n_cu, wlo, s);
 }
 
+}  // namespace
+
+namespace bp {
+
 // One chunk (n <= cap) of windows already resident at `audio_dev`; outputs to device pointers.
 int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float* onset_dev,
               float* contour_dev) {
@@ -1139,7 +1006,40 @@ int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float
   return BP_OK;
 }
 
-}  // namespace
+
+int grow(bp_handle h, float** buf, int64_t* cap, int64_t need) {
+  if (need <= *cap) return BP_OK;
+  // hipFree waits for the whole device, so work of an earlier call that still reads the old buffer has finished
+  if (*buf) BP_HIP(hipFree(*buf));
+  *buf = nullptr;
+  *cap = 0;
+  BP_HIP(hipMalloc(buf, (size_t)(need > 0 ? need : 1) * 4));
+  *cap = need;
+  return BP_OK;
+}
+
+// end of a host-blocking call: spin on the stream (lowest latency) or, with BP_FLAG_BLOCKING_WAIT, give the core to another
+// worker thread while the device works.  hipEventSynchronize on a hipEventBlockingSync event does not do that here: measured
+// on the MI355X box its user time equals its wall time (tools/experiments/host_cpu.py — the runtime polls the signal), so
+// the wait is a query after 20, 40, then every 80 us with the thread asleep in between (a call of a few ms ends ~0.1 ms late).
+int wait_stream(bp_handle h) {
+  if (h->done) {
+    BP_HIP(hipEventRecord(h->done, h->stream));
+    for (long ns = 20000;;) {
+      const hipError_t e = hipEventQuery(h->done);
+      if (e == hipSuccess) break;
+      if (e != hipErrorNotReady) BP_HIP(e);
+      const timespec ts{0, ns};
+      nanosleep(&ts, nullptr);
+      if (ns < 80000) ns *= 2;
+    }
+  } else {
+    BP_HIP(hipStreamSynchronize(h->stream));
+  }
+  return BP_OK;
+}
+
+}  // namespace bp
 
 extern "C" {
 
@@ -1578,676 +1478,6 @@ int bp_infer(bp_handle h, const float* audio, int64_t n_windows, float* note, fl
   return BP_OK;
 }
 
-// the same counts for a handle's geometry (hop 36164 / lead-in 3840 at 22.05 kHz, doubled for the extended range)
-static int64_t h_track_n_windows(bp_handle h, int64_t n_samples) {
-  if (n_samples <= 0) return 0;
-  return (n_samples + h->lead + h->hop - 1) / h->hop;
-}
-static int64_t h_track_n_frames(bp_handle h, int64_t n_samples) {
-  if (n_samples <= 0) return 0;
-  const double n_expected_windows = (double)n_samples / (double)h->hop;
-  const int64_t rows = (int64_t)(n_expected_windows * (double)BP_FRAMES_PER_WINDOW);
-  const int64_t avail = h_track_n_windows(h, n_samples) * BP_FRAMES_PER_WINDOW;
-  return rows < avail ? rows : avail;
-}
-
-int64_t bp_handle_track_n_windows(bp_handle h, int64_t n_samples) { return h ? h_track_n_windows(h, n_samples) : 0; }
-int64_t bp_handle_track_n_frames(bp_handle h, int64_t n_samples) { return h ? h_track_n_frames(h, n_samples) : 0; }
-int64_t bp_handle_window_samples(bp_handle h) { return h ? h->win_len : 0; }
-int bp_handle_sample_rate(bp_handle h) { return h ? h->rate : 0; }
-int64_t bp_handle_resampled_length(bp_handle h, int64_t n_frames, int sample_rate) {
-  if (!h || n_frames <= 0 || sample_rate <= 0) return 0;
-  return (n_frames * (int64_t)h->rate + sample_rate - 1) / sample_rate;
-}
-
-int64_t bp_track_n_windows(int64_t n_samples) {
-  if (n_samples <= 0) return 0;
-  return (n_samples + BP_OVERLAP_LEN / 2 + BP_HOP_SIZE - 1) / BP_HOP_SIZE;
-}
-
-int64_t bp_track_n_frames(int64_t n_samples) {
-  if (n_samples <= 0) return 0;
-  // int(n_samples / hop_size * 142) evaluated like the reference: float64 division, then product
-  const double n_expected_windows = (double)n_samples / (double)BP_HOP_SIZE;
-  int64_t rows = (int64_t)(n_expected_windows * (double)BP_FRAMES_PER_WINDOW);
-  const int64_t avail = bp_track_n_windows(n_samples) * BP_FRAMES_PER_WINDOW;
-  return rows < avail ? rows : avail;
-}
-
-// windows of a device-resident 22.05 kHz signal -> un-overlapped posteriorgrams (host or device outputs)
-// end of a host-blocking call: spin on the stream (lowest latency) or, with BP_FLAG_BLOCKING_WAIT, give the core to another
-// worker thread while the device works.  hipEventSynchronize on a hipEventBlockingSync event does not do that here: measured
-// on the MI355X box its user time equals its wall time (tools/experiments/host_cpu.py — the runtime polls the signal), so
-// the wait is a query every 20..160 us with the thread asleep in between (a call of a few ms ends ~0.1 ms late).
-static int wait_stream(bp_handle h) {
-  if (h->done) {
-    BP_HIP(hipEventRecord(h->done, h->stream));
-    for (long ns = 20000;;) {
-      const hipError_t e = hipEventQuery(h->done);
-      if (e == hipSuccess) break;
-      if (e != hipErrorNotReady) BP_HIP(e);
-      const timespec ts{0, ns};
-      nanosleep(&ts, nullptr);
-      if (ns < 80000) ns *= 2;
-    }
-  } else {
-    BP_HIP(hipStreamSynchronize(h->stream));
-  }
-  return BP_OK;
-}
-
-// out_kind kTrackOutInternal: the un-overlapped maps stay in h->track_out ([T][88] note, [T][88] onset, [T][264] contour) and
-// the call returns with the work queued on the handle's stream (the caller goes on with device work on them)
-constexpr int kTrackOutInternal = 100;
-static int track_core(bp_handle h, const float* d_samples, int64_t n_samples, float* note, float* onset,
-                      float* contour, int out_kind) {
-  hipStream_t s = h->stream;
-  const int64_t n_win = h_track_n_windows(h, n_samples);
-  const int64_t T = h_track_n_frames(h, n_samples);
-  float *d_note = note, *d_onset = onset, *d_contour = contour;
-  h->maps_rows = 0;
-  if (out_kind == BP_MEM_HOST || out_kind == kTrackOutInternal) {
-    const int64_t need = T * (88 + 88 + 264);
-    if (need > h->track_out_cap) {
-      if (h->track_out) BP_HIP(hipFree(h->track_out));
-      h->track_out = nullptr;
-      h->track_out_cap = 0;
-      BP_HIP(hipMalloc(&h->track_out, (size_t)(need > 0 ? need : 1) * 4));
-      h->track_out_cap = need;
-    }
-    d_note = h->track_out;
-    d_onset = d_note + T * 88;
-    d_contour = d_onset + T * 88;
-  }
-  for (int64_t w0 = 0; w0 < n_win; w0 += h->cap) {
-    const int n = (int)((n_win - w0) < h->cap ? (n_win - w0) : h->cap);
-    launch_window_track(d_samples, n_samples, w0, n, h->audio, h->win_len, h->hop, h->lead, s);
-    int rc = run_chunk(h, h->audio, n, h->note, h->onset, h->contour);
-    if (rc) return rc;
-    if (T > 0) launch_unwrap3(h->note, h->onset, h->contour, w0, n, T, d_note, d_onset, d_contour, s);
-  }
-  BP_HIP(hipGetLastError());
-  if (out_kind == kTrackOutInternal) {
-    h->maps_rows = T;
-    return BP_OK;
-  }
-  if (out_kind == BP_MEM_HOST && T > 0) {
-    BP_HIP(hipMemcpyAsync(note, d_note, (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
-    BP_HIP(hipMemcpyAsync(onset, d_onset, (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
-    BP_HIP(hipMemcpyAsync(contour, d_contour, (size_t)T * 264 * 4, hipMemcpyDeviceToHost, s));
-  }
-  return wait_stream(h);
-}
-
-static int grow(bp_handle h, float** buf, int64_t* cap, int64_t need) {
-  if (need <= *cap) return BP_OK;
-  // hipFree waits for the whole device, so work of an earlier call that still reads the old buffer has finished
-  if (*buf) BP_HIP(hipFree(*buf));
-  *buf = nullptr;
-  *cap = 0;
-  BP_HIP(hipMalloc(buf, (size_t)(need > 0 ? need : 1) * 4));
-  *cap = need;
-  return BP_OK;
-}
-
-int bp_infer_track(bp_handle h, const float* samples, int64_t n_samples, float* note, float* onset,
-                   float* contour, int mem_kind) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  if (n_samples < 0 || (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE)) {
-    h->err = "bp_infer_track: bad argument";
-    return BP_ERR_INVALID_ARG;
-  }
-  const int64_t n_win = h_track_n_windows(h, n_samples);
-  const int64_t T = h_track_n_frames(h, n_samples);
-  if (n_win == 0) return BP_OK;
-  if (!samples || (T > 0 && (!note || !onset || !contour))) {
-    h->err = "bp_infer_track: null pointer";
-    return BP_ERR_INVALID_ARG;
-  }
-  BP_HIP(hipSetDevice(h->device));
-  const float* d_samples = samples;
-  if (mem_kind == BP_MEM_HOST) {
-    int rc = grow(h, &h->track, &h->track_cap, n_samples);
-    if (rc) return rc;
-    BP_HIP(hipMemcpyAsync(h->track, samples, (size_t)n_samples * 4, hipMemcpyHostToDevice, h->stream));
-    d_samples = h->track;
-  }
-  return track_core(h, d_samples, n_samples, note, onset, contour, mem_kind);
-}
-
-int bp_infer_tracks(bp_handle h, int64_t n_tracks, const float* const* samples, const int64_t* n_samples,
-                    float* const* note, float* const* onset, float* const* contour, int mem_kind) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  if (n_tracks < 0 || (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE) ||
-      (n_tracks > 0 && (!samples || !n_samples || !note || !onset || !contour))) {
-    h->err = "bp_infer_tracks: bad argument";
-    return BP_ERR_INVALID_ARG;
-  }
-  int64_t total_samples = 0, total_rows = 0;
-  for (int64_t t = 0; t < n_tracks; ++t) {
-    if (n_samples[t] < 0 || (n_samples[t] > 0 && !samples[t])) {
-      h->err = "bp_infer_tracks: negative length or null samples";
-      return BP_ERR_INVALID_ARG;
-    }
-    const int64_t T = h_track_n_frames(h, n_samples[t]);
-    if (T > 0 && (!note[t] || !onset[t] || !contour[t])) {
-      h->err = "bp_infer_tracks: null output pointer";
-      return BP_ERR_INVALID_ARG;
-    }
-    total_samples += n_samples[t];
-    total_rows += T;
-  }
-  if (total_samples == 0) return BP_OK;
-  BP_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  // device views of every track's input and outputs
-  std::vector<const float*> d_in(n_tracks);
-  std::vector<float*> d_note(n_tracks), d_onset(n_tracks), d_contour(n_tracks);
-  if (mem_kind == BP_MEM_HOST) {
-    int rc = grow(h, &h->track, &h->track_cap, total_samples);
-    if (rc) return rc;
-    rc = grow(h, &h->track_out, &h->track_out_cap, total_rows * (88 + 88 + 264));
-    if (rc) return rc;
-    int64_t so = 0, ro = 0;
-    for (int64_t t = 0; t < n_tracks; ++t) {
-      const int64_t T = h_track_n_frames(h, n_samples[t]);
-      if (n_samples[t] > 0)
-        BP_HIP(hipMemcpyAsync(h->track + so, samples[t], (size_t)n_samples[t] * 4, hipMemcpyHostToDevice, s));
-      d_in[t] = h->track + so;
-      d_note[t] = h->track_out + ro * 440;
-      d_onset[t] = d_note[t] + T * 88;
-      d_contour[t] = d_onset[t] + T * 88;
-      so += n_samples[t];
-      ro += T;
-    }
-  } else {
-    for (int64_t t = 0; t < n_tracks; ++t) {
-      d_in[t] = samples[t];
-      d_note[t] = note[t];
-      d_onset[t] = onset[t];
-      d_contour[t] = contour[t];
-    }
-  }
-  // the windows of consecutive tracks are packed into full chunks; the pieces of a chunk are windowed by ONE launch and
-  // un-overlapped by one launch (bp_common.h TrackSegs; more than kMaxTrackSegs pieces per chunk: several launches)
-  std::vector<TrackSeg> segs;
-  int cur = 0;
-  auto for_groups = [&](auto&& fn) {
-    for (size_t g0 = 0; g0 < segs.size(); g0 += kMaxTrackSegs) {
-      TrackSegs ts{};
-      ts.n = (int)std::min<size_t>(kMaxTrackSegs, segs.size() - g0);
-      for (int k = 0; k < ts.n; ++k) ts.seg[k] = segs[g0 + k];
-      const int first = ts.seg[0].at, slots = ts.seg[ts.n - 1].at + ts.seg[ts.n - 1].n_windows - first;
-      for (int k = 0; k < ts.n; ++k) ts.seg[k].at -= first;  // slots relative to the group's first window
-      fn(ts, first, slots);
-    }
-  };
-  auto flush = [&]() -> int {
-    if (cur == 0) return BP_OK;
-    for_groups([&](const TrackSegs& ts, int first, int slots) {
-      launch_window_tracks(ts, slots, h->audio + (int64_t)first * h->win_len, h->win_len, h->hop, h->lead, s);
-    });
-    int rc = run_chunk(h, h->audio, cur, h->note, h->onset, h->contour);
-    if (rc) return rc;
-    for_groups([&](const TrackSegs& ts, int first, int slots) {
-      launch_unwrap_tracks(ts, slots, h->note + (int64_t)first * kPlaneN, h->onset + (int64_t)first * kPlaneN,
-                           h->contour + (int64_t)first * kPlaneC, s);
-    });
-    segs.clear();
-    cur = 0;
-    return BP_OK;
-  };
-  for (int64_t t = 0; t < n_tracks; ++t) {
-    const int64_t n_win = h_track_n_windows(h, n_samples[t]);
-    const int64_t T = h_track_n_frames(h, n_samples[t]);
-    for (int64_t w0 = 0; w0 < n_win;) {
-      const int64_t room = h->cap - cur;
-      const int n = (int)((n_win - w0) < room ? (n_win - w0) : room);
-      segs.push_back(TrackSeg{d_in[t], {d_note[t], d_onset[t], d_contour[t]}, n_samples[t], w0, T, n, cur});
-      cur += n;
-      w0 += n;
-      if (cur == h->cap) {
-        int rc = flush();
-        if (rc) return rc;
-      }
-    }
-  }
-  {
-    int rc = flush();
-    if (rc) return rc;
-  }
-  BP_HIP(hipGetLastError());
-  if (mem_kind == BP_MEM_HOST) {
-    for (int64_t t = 0; t < n_tracks; ++t) {
-      const int64_t T = h_track_n_frames(h, n_samples[t]);
-      if (T <= 0) continue;
-      BP_HIP(hipMemcpyAsync(note[t], d_note[t], (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
-      BP_HIP(hipMemcpyAsync(onset[t], d_onset[t], (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
-      BP_HIP(hipMemcpyAsync(contour[t], d_contour[t], (size_t)T * 264 * 4, hipMemcpyDeviceToHost, s));
-    }
-  }
-  return wait_stream(h);
-}
-
-int64_t bp_resampled_length(int64_t n_frames, int sample_rate) {
-  if (n_frames <= 0 || sample_rate <= 0) return 0;
-  return (n_frames * (int64_t)BP_AUDIO_SAMPLE_RATE + sample_rate - 1) / sample_rate;
-}
-
-// downmix + resample into h->res_dev (or straight through when already mono 22.05 kHz on the device);
-// *out = device pointer of the 22.05 kHz signal, *n_out = its length
-static int pcm_width(int format) {
-  switch (format) {
-    case BP_PCM_F32: return 4;
-    case BP_PCM_S16: return 2;
-    case BP_PCM_S24: return 3;
-    case BP_PCM_S32: return 4;
-    case BP_PCM_U8: return 1;
-    case BP_PCM_F64: return 8;
-    default: return 0;
-  }
-}
-
-static int ingest(bp_handle h, const void* pcm, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind,
-                  const float** out, int64_t* n_out) {
-  const int width = pcm_width(format);
-  if (n_frames < 0 || channels < 1 || channels > 64 || sample_rate < 1000 || sample_rate > 768000 || width == 0 ||
-      (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE) || (n_frames > 0 && !pcm)) {
-    h->err = "audio ingest: bad argument (n_frames, channels, sample_rate, format, mem_kind or null pcm)";
-    return BP_ERR_INVALID_ARG;
-  }
-  BP_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  *n_out = bp_handle_resampled_length(h, n_frames, sample_rate);
-  *out = nullptr;
-  if (n_frames == 0) return BP_OK;
-  const void* d_pcm = pcm;
-  if (mem_kind == BP_MEM_HOST) {
-    const int64_t bytes = n_frames * channels * width;
-    int rc = grow(h, &h->pcm_dev, &h->pcm_cap, (bytes + 3) / 4);
-    if (rc) return rc;
-    BP_HIP(hipMemcpyAsync(h->pcm_dev, pcm, (size_t)bytes, hipMemcpyHostToDevice, s));
-    d_pcm = h->pcm_dev;
-  }
-  const float* d_mono = static_cast<const float*>(d_pcm);
-  if (channels > 1 || format != BP_PCM_F32) {
-    int rc = grow(h, &h->mono_dev, &h->mono_cap, n_frames);
-    if (rc) return rc;
-    if (format == BP_PCM_F32)
-      launch_downmix(static_cast<const float*>(d_pcm), n_frames, channels, h->mono_dev, s);
-    else
-      launch_downmix_raw(d_pcm, format, n_frames, channels, h->mono_dev, s);
-    d_mono = h->mono_dev;
-  }
-  if (sample_rate == h->rate) {
-    *out = d_mono;
-    return BP_OK;
-  }
-  if (h->taps_rate != sample_rate) {
-    std::vector<double> taps;
-    ResamplePlan pl = make_resample_plan(sample_rate, h->rate, taps);
-    pl.rev_off = 0;
-    if (!pl.direct && pl.up == 1 && pl.down == 2) {
-      // the 2 : 1 kernel walks the taps backwards, a block of 32 per scalar load: a reversed copy behind the table, padded
-      // with zeros to whole blocks (a zero tap adds x * 0 = 0 to a float64 sum)
-      const size_t M = taps.size(), base = (M + 31) / 32 * 32, padded = (M + 31) / 32 * 32;
-      taps.resize(base + padded, 0.0);
-      for (size_t i = 0; i < M; ++i) taps[base + i] = taps[M - 1 - i];
-      pl.rev_off = (int64_t)base;
-    }
-    if (h->taps_dev) BP_HIP(hipFree(h->taps_dev));
-    h->taps_dev = nullptr;
-    h->taps_rate = 0;
-    BP_HIP(hipMalloc(&h->taps_dev, taps.size() * sizeof(double)));
-    BP_HIP(hipMemcpy(h->taps_dev, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->plan = pl;
-    h->taps_rate = sample_rate;
-  }
-  int rc = grow(h, &h->res_dev, &h->res_cap, *n_out);
-  if (rc) return rc;
-  launch_resample(d_mono, n_frames, h->taps_dev, h->plan, h->res_dev, *n_out, h->resample_mode, s);
-  BP_HIP(hipGetLastError());
-  *out = h->res_dev;
-  return BP_OK;
-}
-
-int bp_resample(bp_handle h, const float* pcm, int64_t n_frames, int channels, int sample_rate, float* out22k,
-                int mem_kind) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  const float* d = nullptr;
-  int64_t n_out = 0;
-  int rc = ingest(h, pcm, BP_PCM_F32, n_frames, channels, sample_rate, mem_kind, &d, &n_out);
-  if (rc) return rc;
-  if (n_out == 0) return BP_OK;
-  if (!out22k) {
-    h->err = "bp_resample: out22k is NULL";
-    return BP_ERR_INVALID_ARG;
-  }
-  BP_HIP(hipMemcpyAsync(out22k, d, (size_t)n_out * 4,
-                        mem_kind == BP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
-  BP_HIP(hipStreamSynchronize(h->stream));
-  return BP_OK;
-}
-
-int bp_infer_pcm_raw(bp_handle h, const void* pcm, int format, int64_t n_frames, int channels, int sample_rate, float* note,
-                     float* onset, float* contour, int mem_kind) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  const float* d = nullptr;
-  int64_t n = 0;
-  int rc = ingest(h, pcm, format, n_frames, channels, sample_rate, mem_kind, &d, &n);
-  if (rc) return rc;
-  if (h_track_n_windows(h, n) == 0) return BP_OK;
-  if (h_track_n_frames(h, n) > 0 && (!note || !onset || !contour)) {
-    h->err = "bp_infer_pcm: null output pointer";
-    return BP_ERR_INVALID_ARG;
-  }
-  return track_core(h, d, n, note, onset, contour, mem_kind);
-}
-
-int bp_infer_pcm(bp_handle h, const float* pcm, int64_t n_frames, int channels, int sample_rate, float* note,
-                 float* onset, float* contour, int mem_kind) {
-  return bp_infer_pcm_raw(h, pcm, BP_PCM_F32, n_frames, channels, sample_rate, note, onset, contour, mem_kind);
-}
-
-// ---- device-side note candidates (note_device.hip): what note decoding needs of a track's posteriorgrams
-extern "C" void bp_internal_bend_tables(int32_t* tab, double* gauss);
-extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);
-
-// d_note / d_onset / d_contour: device maps of T frames (note / onset are modified when the parameters set a frequency
-// range, like constrain_frequency does).  Outputs: host buffers.
-static int candidates_core(bp_handle h, float* d_note, float* d_onset, const float* d_contour, int64_t T,
-                           const bp_note_params* prm, float* note_out, uint8_t* cand_out, int8_t* bend_out, int* status) {
-  hipStream_t s = h->stream;
-  *status = 0;
-  if (T <= 0) return wait_stream(h);
-  constexpr size_t kTabBytes = 88 * 16, kGaussBytes = 51 * 8, kStatsBytes = 16;
-  if (!h->nd_tables) {
-    std::vector<float> raw((kTabBytes + kGaussBytes + kStatsBytes) / 4, 0.f);
-    bp_internal_bend_tables(reinterpret_cast<int32_t*>(raw.data()), reinterpret_cast<double*>(raw.data() + kTabBytes / 4));
-    int rc = upload(h, raw, &h->nd_tables);
-    if (rc) return rc;
-    BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->nd_stats_host), kStatsBytes, hipHostMallocPortable));
-    BP_HIP(hipHostGetDevicePointer(&h->nd_stats_host_dev, h->nd_stats_host, 0));
-  }
-  const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bend_bytes = T * 88;  // multiples of 4
-  int rc = grow(h, &h->nd_buf, &h->nd_cap, (((bits_bytes + 15) & ~(int64_t)15) + bend_bytes + 3) / 4);
-  if (rc) return rc;
-  uint8_t* d_bits = reinterpret_cast<uint8_t*>(h->nd_buf);
-  int8_t* d_bend = reinterpret_cast<int8_t*>(d_bits + ((bits_bytes + 15) & ~(int64_t)15));
-  char* tables = reinterpret_cast<char*>(h->nd_tables);
-  void* d_stats = tables + kTabBytes + kGaussBytes;
-  int lo = 0, hi = 88;
-  bp_internal_freq_limits(prm, &lo, &hi);
-  const bool want_bends = prm->include_pitch_bends != 0 && bend_out != nullptr;
-  if (!h->nd_stats_ready) launch_note_stats_init(d_stats, s);
-  h->nd_stats_ready = false;
-  launch_note_candidates(d_note, d_onset, d_contour, T, lo, hi, prm->infer_onsets != 0, prm->onset_threshold, tables,
-                         reinterpret_cast<const double*>(tables + kTabBytes), d_stats, d_bits, want_bends ? d_bend : nullptr, s);
-  BP_HIP(hipGetLastError());
-  // The results go home.  Into page-locked buffers (bp_host_alloc) a kernel of this stream writes them over PCIe itself:
-  // the copy engine serialises the copies of all lanes in both directions (measured: a lane's 27 MB of posteriorgrams
-  // going out kept the next file's samples from coming in), and it is busy with the inbound samples.  Pageable
-  // destinations take ordinary copies.
-  // (the attributes describe the START of a buffer only — a pointer into a page-locked block that ends before
-  // `bytes` would send the kernel's writes past the registration.  The whole extent must lie inside the allocation the
-  // pointer belongs to: hipMemGetAddressRange gives its base and size for the device view of a page-locked block; where that
-  // cannot be established the copies take over.)
-  auto device_view = [](void* p, size_t bytes) -> void* {
-    if (!p) return nullptr;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    if (at.type != hipMemoryTypeHost || !at.devicePointer) return nullptr;
-    hipDeviceptr_t base = nullptr;
-    size_t size = 0;
-    if (hipMemGetAddressRange(&base, &size, at.devicePointer) != hipSuccess) {
-      (void)hipGetLastError();
-      return nullptr;
-    }
-    const uintptr_t b0 = reinterpret_cast<uintptr_t>(base), q = reinterpret_cast<uintptr_t>(at.devicePointer);
-    return (q >= b0 && q + bytes <= b0 + size) ? at.devicePointer : nullptr;
-  };
-  bool exported_by_kernel = false;
-  void *v_note = device_view(note_out, (size_t)T * 88 * 4), *v_bits = device_view(cand_out, (size_t)bits_bytes),
-       *v_bend = want_bends ? device_view(bend_out, (size_t)bend_bytes) : nullptr;
-  const bool aligned = !((reinterpret_cast<uintptr_t>(v_note) | reinterpret_cast<uintptr_t>(v_bits) | reinterpret_cast<uintptr_t>(v_bend)) & 3);
-  if (v_note && v_bits && (v_bend || !want_bends) && aligned) {
-    // ... the stats record with them; the same kernel leaves the device record initialised for the next track
-    launch_note_export(d_note, v_note, T * 88 * 4, d_bits, v_bits, bits_bytes, d_bend, v_bend, bend_bytes, d_stats,
-                       h->nd_stats_host_dev, s);
-    BP_HIP(hipGetLastError());
-    exported_by_kernel = true;
-  } else {
-    BP_HIP(hipMemcpyAsync(h->nd_stats_host, d_stats, kStatsBytes, hipMemcpyDeviceToHost, s));
-    BP_HIP(hipMemcpyAsync(note_out, d_note, (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
-    BP_HIP(hipMemcpyAsync(cand_out, d_bits, (size_t)bits_bytes, hipMemcpyDeviceToHost, s));
-    if (want_bends) BP_HIP(hipMemcpyAsync(bend_out, d_bend, (size_t)bend_bytes, hipMemcpyDeviceToHost, s));
-  }
-  rc = wait_stream(h);
-  if (rc) return rc;
-  if (exported_by_kernel) h->nd_stats_ready = true;  // only now: the export kernel, which re-initialises the record, has run
-  const int nan_flag = reinterpret_cast<const int*>(h->nd_stats_host)[1];
-  // numpy's rules for NaN cells, and an onset threshold <= 0 (every cell that is not a peak qualifies), need the maps
-  // themselves: the host decoder takes over (bp_infer_* + bp_notes_decode)
-  if (nan_flag || !(prm->onset_threshold > 0.0)) *status = 1;
-  return BP_OK;
-}
-
-int bp_note_candidates(bp_handle h, const float* note, const float* onset, const float* contour, int64_t n_frames,
-                       const bp_note_params* params, int mem_kind, float* note_out, uint8_t* cand_bits, int8_t* bend_map,
-                       int* status) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  if (!params || !status || n_frames < 0 || (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE) ||
-      (n_frames > 0 && (!note || !onset || !contour || !note_out || !cand_bits))) {
-    h->err = "bp_note_candidates: null pointer, negative frame count or bad mem_kind";
-    return BP_ERR_INVALID_ARG;
-  }
-  BP_HIP(hipSetDevice(h->device));
-  const int64_t T = n_frames;
-  // a private copy on the device: the frequency limits are applied in place
-  int rc = grow(h, &h->track_out, &h->track_out_cap, T * (88 + 88 + 264));
-  if (rc) return rc;
-  float *d_note = h->track_out, *d_onset = d_note + T * 88, *d_contour = d_onset + T * 88;
-  const hipMemcpyKind kind = mem_kind == BP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice;
-  if (T > 0) {
-    BP_HIP(hipMemcpyAsync(d_note, note, (size_t)T * 88 * 4, kind, h->stream));
-    BP_HIP(hipMemcpyAsync(d_onset, onset, (size_t)T * 88 * 4, kind, h->stream));
-    BP_HIP(hipMemcpyAsync(d_contour, contour, (size_t)T * 264 * 4, kind, h->stream));
-  }
-  return candidates_core(h, d_note, d_onset, d_contour, T, params, note_out, cand_bits, bend_map, status);
-}
-
-int bp_infer_pcm_raw_candidates(bp_handle h, const void* pcm, int format, int64_t n_frames, int channels, int sample_rate,
-                                const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map,
-                                int* status) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  if (!params || !status) {
-    h->err = "bp_infer_pcm_raw_candidates: null params / status";
-    return BP_ERR_INVALID_ARG;
-  }
-  const float* d = nullptr;
-  int64_t n = 0;
-  int rc = ingest(h, pcm, format, n_frames, channels, sample_rate, BP_MEM_HOST, &d, &n);
-  if (rc) return rc;
-  *status = 0;
-  const int64_t T = h_track_n_frames(h, n);
-  if (h_track_n_windows(h, n) == 0 || T == 0) return wait_stream(h);
-  if (!note_out || !cand_bits) {
-    h->err = "bp_infer_pcm_raw_candidates: null output pointer";
-    return BP_ERR_INVALID_ARG;
-  }
-  rc = track_core(h, d, n, nullptr, nullptr, nullptr, kTrackOutInternal);
-  if (rc) return rc;
-  float *d_note = h->track_out, *d_onset = d_note + T * 88, *d_contour = d_onset + T * 88;
-  return candidates_core(h, d_note, d_onset, d_contour, T, params, note_out, cand_bits, bend_map, status);
-}
-
-int bp_track_maps(bp_handle h, int64_t n_frames, float* note, float* onset, float* contour, int mem_kind) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  if (n_frames <= 0 || n_frames != h->maps_rows || !note || !onset || !contour ||
-      (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE)) {
-    h->err = "bp_track_maps: no maps of that many rows are left on the device (call it right after a *_candidates call of "
-             "this handle, with that call's row count) or a null / unknown destination";
-    return BP_ERR_INVALID_ARG;
-  }
-  BP_HIP(hipSetDevice(h->device));
-  const int64_t T = n_frames;
-  const float *d_note = h->track_out, *d_onset = d_note + T * 88, *d_contour = d_onset + T * 88;
-  const hipMemcpyKind kind = mem_kind == BP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-  BP_HIP(hipMemcpyAsync(note, d_note, (size_t)T * 88 * 4, kind, h->stream));
-  BP_HIP(hipMemcpyAsync(onset, d_onset, (size_t)T * 88 * 4, kind, h->stream));
-  BP_HIP(hipMemcpyAsync(contour, d_contour, (size_t)T * 264 * 4, kind, h->stream));
-  return wait_stream(h);
-}
-
-// ---- FLAC decoded on the device (flac_device.hip) ---------------------------------------------------------------------------
-// The file's bytes to the device, the three decode launches queued on the handle's stream, the error bits on their way to a
-// page-locked word; *fmt / *lay describe the PCM now (being) written to h->pcm_dev.
-static int flac_to_device_pcm(bp_handle h, const void* file, size_t nbytes, bp_flac_stream_layout* lay, int* fmt) {
-  if (!file || nbytes < 42) {
-    h->err = "FLAC on the device: null or too short";
-    return BP_ERR_INVALID_ARG;
-  }
-  if (bp_flac_layout(file, nbytes, lay) != BP_OK) {
-    h->err = std::string("FLAC on the device: ") + bp_audio_last_error();
-    return BP_ERR_BAD_AUDIO;
-  }
-  if (lay->n_frames <= 0 || lay->min_block < 16 || lay->max_block < lay->min_block || lay->bits_per_sample > 24 ||
-      lay->bits_per_sample < 4 || lay->channels > 8 || nbytes >= ((size_t)1 << 31) ||
-      lay->n_frames * lay->channels >= ((int64_t)1 << 33)) {
-    h->err = "FLAC on the device: a stream the device decoder leaves to the host (no sample count / block sizes in STREAMINFO, "
-             "more than 24 bits or 8 channels, or 2 GB and more)";
-    return BP_ERR_UNSUPPORTED;
-  }
-  BP_HIP(hipSetDevice(h->device));
-  hipStream_t s = h->stream;
-  if (!h->fd_status_host) BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fd_status_host), 2 * sizeof(int), hipHostMallocPortable));
-  if (nbytes + 64 > h->fd.file_cap) {
-    if (h->fd.file) BP_HIP(hipFree(h->fd.file));
-    h->fd.file = nullptr, h->fd.file_cap = 0;
-    const size_t cap = nbytes + nbytes / 4 + 4096;
-    BP_HIP(hipMalloc(&h->fd.file, cap));
-    h->fd.file_cap = cap;
-  }
-  BP_HIP(hipMemcpyAsync(h->fd.file, file, nbytes, hipMemcpyHostToDevice, s));
-  BP_HIP(hipMemsetAsync(h->fd.file + nbytes, 0, 64, s));
-  const int wide = lay->bits_per_sample > 16;
-  *fmt = wide ? BP_PCM_S32 : BP_PCM_S16;
-  const int64_t bytes = lay->n_frames * lay->channels * (wide ? 4 : 2);
-  int rc = grow(h, &h->pcm_dev, &h->pcm_cap, (bytes + 3) / 4);
-  if (rc) return rc;
-  FdStream st{lay->channels, lay->bits_per_sample, lay->min_block, lay->max_block, lay->n_frames, (uint32_t)lay->audio_start,
-              (uint32_t)nbytes};
-  if (flac_device_decode(h->fd, st, h->pcm_dev, s) != 0) {
-    h->err = "FLAC on the device: allocation or launch failed";
-    (void)hipGetLastError();
-    return BP_ERR_HIP;
-  }
-  BP_HIP(hipMemcpyAsync(h->fd_status_host, h->fd.meta, 2 * sizeof(int), hipMemcpyDeviceToHost, s));
-  return BP_OK;
-}
-
-// after the stream has been waited for: what the decode kernels reported
-static int flac_device_verdict(bp_handle h) {
-  const int st = h->fd_status_host ? h->fd_status_host[0] : 0;
-  if (st == 0) return BP_OK;
-  h->err = std::string("FLAC on the device: the stream could not be decoded (") + ((st & 2) ? "frame chain " : "") +
-           ((st & 4) ? "CRC-16 " : "") + ((st & 8) ? "reserved value / overrun " : "") + ((st & 16) ? "candidate overflow " : "") +
-           "); the host decoder (bp_flac_decode) reports the cause";
-  return BP_ERR_BAD_AUDIO;
-}
-
-int bp_flac_decode_device(bp_handle h, const void* file, size_t nbytes, int32_t* pcm, int64_t capacity_frames, int64_t* n_frames) {
-  if (!h || !n_frames) return BP_ERR_INVALID_ARG;
-  bp_flac_stream_layout lay;
-  int fmt = 0;
-  int rc = flac_to_device_pcm(h, file, nbytes, &lay, &fmt);
-  if (rc) return rc;
-  rc = wait_stream(h);
-  if (rc) return rc;
-  rc = flac_device_verdict(h);
-  if (rc) return rc;
-  *n_frames = lay.n_frames;
-  if (!pcm) return BP_OK;
-  if (capacity_frames < lay.n_frames) {
-    h->err = "bp_flac_decode_device: the output buffer is too small";
-    return BP_ERR_INVALID_ARG;
-  }
-  const int64_t n = lay.n_frames * lay.channels;
-  if (fmt == BP_PCM_S32) {
-    BP_HIP(hipMemcpy(pcm, h->pcm_dev, (size_t)n * 4, hipMemcpyDeviceToHost));
-    const int sh = 32 - lay.bits_per_sample;
-    for (int64_t i = 0; i < n; ++i) pcm[i] >>= sh;  // left-justified on the device
-  } else {
-    std::vector<int16_t> tmp((size_t)n);
-    BP_HIP(hipMemcpy(tmp.data(), h->pcm_dev, (size_t)n * 2, hipMemcpyDeviceToHost));
-    const int sh = 16 - lay.bits_per_sample;
-    for (int64_t i = 0; i < n; ++i) pcm[i] = (int32_t)tmp[(size_t)i] >> sh;
-  }
-  return BP_OK;
-}
-
-int bp_infer_flac(bp_handle h, const void* file, size_t nbytes, float* note, float* onset, float* contour, int mem_kind) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  bp_flac_stream_layout lay;
-  int fmt = 0;
-  int rc = flac_to_device_pcm(h, file, nbytes, &lay, &fmt);
-  if (rc) return rc;
-  const float* d = nullptr;
-  int64_t n = 0;
-  rc = ingest(h, h->pcm_dev, fmt, lay.n_frames, lay.channels, lay.sample_rate, BP_MEM_DEVICE, &d, &n);
-  if (rc) return rc;
-  if (h_track_n_windows(h, n) == 0) {
-    rc = wait_stream(h);
-    return rc ? rc : flac_device_verdict(h);
-  }
-  if (h_track_n_frames(h, n) > 0 && (!note || !onset || !contour)) {
-    h->err = "bp_infer_flac: null output pointer";
-    return BP_ERR_INVALID_ARG;
-  }
-  rc = track_core(h, d, n, note, onset, contour, mem_kind);
-  if (rc) return rc;
-  if (mem_kind != BP_MEM_HOST) {
-    rc = wait_stream(h);
-    if (rc) return rc;
-  }
-  return flac_device_verdict(h);
-}
-
-int bp_infer_flac_candidates(bp_handle h, const void* file, size_t nbytes, const bp_note_params* params, float* note_out,
-                             uint8_t* cand_bits, int8_t* bend_map, int* status) {
-  if (!h) return BP_ERR_INVALID_ARG;
-  if (!params || !status) {
-    h->err = "bp_infer_flac_candidates: null params / status";
-    return BP_ERR_INVALID_ARG;
-  }
-  bp_flac_stream_layout lay;
-  int fmt = 0;
-  int rc = flac_to_device_pcm(h, file, nbytes, &lay, &fmt);
-  if (rc) return rc;
-  const float* d = nullptr;
-  int64_t n = 0;
-  rc = ingest(h, h->pcm_dev, fmt, lay.n_frames, lay.channels, lay.sample_rate, BP_MEM_DEVICE, &d, &n);
-  if (rc) return rc;
-  *status = 0;
-  const int64_t T = h_track_n_frames(h, n);
-  if (h_track_n_windows(h, n) == 0 || T == 0) {
-    rc = wait_stream(h);
-    return rc ? rc : flac_device_verdict(h);
-  }
-  if (!note_out || !cand_bits) {
-    h->err = "bp_infer_flac_candidates: null output pointer";
-    return BP_ERR_INVALID_ARG;
-  }
-  rc = track_core(h, d, n, nullptr, nullptr, nullptr, kTrackOutInternal);
-  if (rc) return rc;
-  float *d_note = h->track_out, *d_onset = d_note + T * 88, *d_contour = d_onset + T * 88;
-  rc = candidates_core(h, d_note, d_onset, d_contour, T, params, note_out, cand_bits, bend_map, status);
-  if (rc) return rc;
-  return flac_device_verdict(h);
-}
 
 void* bp_host_alloc(size_t bytes) {
   void* p = nullptr;

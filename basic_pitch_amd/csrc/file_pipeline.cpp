@@ -32,6 +32,8 @@
 
 #include "../../include/basic_pitch_amd.h"
 
+extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);  // flac_decode.cpp
+
 namespace {
 
 thread_local std::string g_file_error;
@@ -812,11 +814,10 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
         channels = w.channels, sr = w.sample_rate, n_frames = w.n_frames, pcm = w.pcm, format = wav_pcm_format(w);
       } else if (n_bytes >= 4 && (std::memcmp(fb, "fLaC", 4) == 0 || std::memcmp(fb, "ID3", 3) == 0)) {
         // FLAC: the file's BYTES go to the device and are decoded there (flac_device.hip) — no core-time per sample here,
-        // half the PCIe bytes of the PCM — unless the stream is one the device decoder leaves to the host (no sample count
-        // or block sizes in STREAMINFO, more than 24 bits / 8 channels) or params.host_flac asks for the host decoder
+        // half the PCIe bytes of the PCM — unless the stream is one the device decoder leaves to the host (flac_decode.cpp
+        // bp_internal_flac_device_supported) or params.host_flac asks for the host decoder
         bp_flac_stream_layout lay;
-        if (!prm.host_flac && bp_flac_layout(fb, n_bytes, &lay) == BP_OK && lay.n_frames > 0 && lay.min_block >= 16 &&
-            lay.max_block >= lay.min_block && lay.bits_per_sample <= 24 && lay.bits_per_sample >= 4 && lay.channels <= 8) {
+        if (!prm.host_flac && bp_flac_layout(fb, n_bytes, &lay) == BP_OK && bp_internal_flac_device_supported(&lay, n_bytes)) {
           flac_on_device = true;
           channels = lay.channels, sr = lay.sample_rate, n_frames = lay.n_frames;
         } else if (!host_flac_decode()) {

@@ -620,4 +620,13 @@ int bp_flac_layout(const void* file, size_t nbytes, bp_flac_stream_layout* out) 
 
 const char* bp_audio_last_error(void) { return g_err.c_str(); }
 
+// Library-internal (not in the public header): whether the device decoder (flac_device.hip) takes a stream — a sample count
+// and block sizes in STREAMINFO, 4 to 24 bits, at most 8 channels, less than 2 GB of file and 2^33 samples.  The device entry
+// points (bp_infer_flac*) and the file job's choice of decoder (file_pipeline.cpp) both ask here.
+int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes) {
+  return lay->n_frames > 0 && lay->min_block >= 16 && lay->max_block >= lay->min_block && lay->bits_per_sample <= 24 &&
+         lay->bits_per_sample >= 4 && lay->channels <= 8 && nbytes < ((size_t)1 << 31) &&
+         lay->n_frames * lay->channels < ((int64_t)1 << 33);
+}
+
 }  // extern "C"

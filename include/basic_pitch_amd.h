@@ -400,8 +400,10 @@ int bp_infer_flac_candidates(bp_handle h, const void* file, size_t nbytes, const
                              uint8_t* cand_bits, int8_t* bend_map, int* status);
 /* The three posteriorgrams the LAST bp_infer_*_candidates call of this handle left on the device, n_frames rows each
  * ([n][88], [n][88], [n][264]; host or device destinations): what that call's *status == 1 asks for (a NaN in the maps: the
- * host decoder needs the maps themselves, bp_notes_decode) without running the track again.  BP_ERR_INVALID_ARG when
- * n_frames is not the row count of that call or another call has used the handle's track buffer since. */
+ * host decoder needs the maps themselves, bp_notes_decode) without running the track again.  Note and onset come with the
+ * call's frequency limits already applied (minimum / maximum frequency: the cells outside are zero), as its note_out does.
+ * BP_ERR_INVALID_ARG when n_frames is not the row count of that call or another call has used the handle's track buffer
+ * since (a track call of this handle with host output maps, bp_note_candidates, another *_candidates call). */
 int bp_track_maps(bp_handle h, int64_t n_frames, float* note, float* onset, float* contour, int mem_kind);
 /* The sequential half (host): output_to_notes_polyphonic from the candidates (note_creation.py:404-509), pitch bends read
  * from bend_map, frame times as bp_notes_decode.  `note` is only read. */

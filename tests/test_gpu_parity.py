@@ -646,6 +646,17 @@ def test_new_entry_points_reject_bad_arguments():
     assert lib.bp_infer_pcm(h, buf.ctypes.data, 10, 1, 44100, None, None, None, 7) == _native.BP_ERR_INVALID_ARG  # mem_kind
     assert b"ingest" in lib.bp_last_error(h)
     assert m.predict_tracks([np.zeros(0, np.float32)])[0]["note"].shape == (0, 88)
+    # bp_infer_flac checks its outputs before it queues anything: the refused call leaves the handle as a fresh one
+    with open(os.path.join(GOLDEN, "vocadito_10_excerpt.flac"), "rb") as f:
+        flac = f.read()
+    assert lib.bp_infer_flac(h, flac, len(flac), None, None, None, _native.BP_MEM_HOST) == _native.BP_ERR_INVALID_ARG
+    got = m.predict_flac(flac)
+    fresh = Model(max_windows=4)
+    want = fresh.predict_flac(flac)
+    fresh.close()
+    assert got["note"].shape[0] > 0
+    for k in want:
+        assert np.array_equal(got[k], want[k]), k
     m.close()
 
 
@@ -1317,4 +1328,19 @@ def test_track_maps_gives_the_nan_fallback_its_maps_without_a_second_pass():
     m.predict_pcm_raw(pcm, _native.BP_PCM_F32, n, 1, 22050)  # the track buffer is used by another call: nothing to hand over
     assert m._lib.bp_track_maps(m._handle, T, got["note"].ctypes.data, got["onset"].ctypes.data, got["contour"].ctypes.data,
                                 _native.BP_MEM_HOST) == -1
+
+    def candidates_then(other):  # a status-1 candidates call, then another call that uses the track buffer
+        st = C.c_int(0)
+        assert m._lib.bp_infer_pcm_raw_candidates(m._handle, pcm.ctypes.data, _native.BP_PCM_F32, n, 1, 22050, C.byref(prm),
+                                                  note.ctypes.data, bits.ctypes.data, bend.ctypes.data, C.byref(st)) == 0
+        assert st.value == 1
+        other()
+        return m._lib.bp_track_maps(m._handle, T, got["note"].ctypes.data, got["onset"].ctypes.data, got["contour"].ctypes.data,
+                                    _native.BP_MEM_HOST)
+
+    assert candidates_then(lambda: m.predict_tracks([pcm[:, 0]])) == -1  # bp_infer_tracks, host memory
+    maps = {k: np.ascontiguousarray(want[k]) for k in ("note", "onset", "contour")}
+    assert candidates_then(lambda: m._lib.bp_note_candidates(
+        m._handle, maps["note"].ctypes.data, maps["onset"].ctypes.data, maps["contour"].ctypes.data, T, C.byref(prm),
+        _native.BP_MEM_HOST, note.ctypes.data, bits.ctypes.data, bend.ctypes.data, C.byref(C.c_int(0)))) == -1
     m.close()

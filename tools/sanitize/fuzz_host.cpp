@@ -16,6 +16,9 @@ int64_t bp_handle_resampled_length(bp_handle, int64_t, int) { return 0; }
 int bp_handle_sample_rate(bp_handle) { return 22050; }
 int bp_infer_pcm_raw_candidates(bp_handle, const void*, int, int64_t, int, int, const bp_note_params*, float*, uint8_t*, int8_t*,
                                 int*) { return -1; }
+int bp_infer_flac(bp_handle, const void*, size_t, float*, float*, float*, int) { return -1; }
+int bp_infer_flac_candidates(bp_handle, const void*, size_t, const bp_note_params*, float*, uint8_t*, int8_t*, int*) { return -1; }
+int bp_track_maps(bp_handle, int64_t, float*, float*, float*, int) { return -1; }
 }
 static uint64_t s = 88172645463325252ull;
 static uint32_t rnd() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (uint32_t)(s >> 11); }
