@@ -19,6 +19,7 @@ HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd.h")
 SOURCES = [
     "bp_api.hip",
     "track_api.hip",
+    "weight_pack.hip",
     "cqt_pyramid.hip",
     "cqt_filterbank.hip",
     "cqt_planes.hip",
@@ -43,12 +44,14 @@ SOURCES = [
 # (`build_library(ab=True)` -> lib/libbasicpitch_amd_ab.so, every source with -DBP_AB_KERNELS, which also turns the BP_*
 # environment switches on: csrc/bp_common.h ab_env).  The product library carries neither.
 AB_SOURCES = [
-    "conv_contour_direct.hip",  # exact 8-channel conv1 (BP_RIM=exact, BP_CONV1=full), round-2 folded conv1 (BP_CONV1=rounds)
+    "conv_contour_direct.hip",  # round-2 folded conv1 of the interior bins (BP_CONV1=rounds)
     "onset_march.hip",          # onset march on 32x32x16 (BP_ONSET=march32)
     "note_march.hip",           # note march on 32x32x16 (BP_NOTE=march32)
     "conv_contour_fold_mx.hip", # contour conv1 of the fp8-corrections mode (BP_FLAG_FP8_CORRECTIONS: A/B library only since round 6)
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
+# every header a source includes: editing one rebuilds all objects
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:
@@ -61,7 +64,7 @@ def _stale(ab: bool = False) -> bool:
     if not os.path.exists(lib):
         return True
     t = os.path.getmtime(lib)
-    deps = _sources(ab) + [os.path.join(CSRC, "bp_common.h"), os.path.join(CSRC, "bp_context.h"), HEADER]
+    deps = _sources(ab) + HEADERS
     return any(os.path.getmtime(d) > t for d in deps if os.path.exists(d))
 
 
@@ -103,8 +106,7 @@ def build_library(force: bool = False, verbose: bool = False, ab: bool = False) 
     hipcc = find_hipcc()
     obj_dir = os.path.join(LIB_DIR, "obj_ab" if ab else "obj")
     os.makedirs(obj_dir, exist_ok=True)
-    headers = [os.path.join(CSRC, "bp_common.h"), os.path.join(CSRC, "bp_context.h"), HEADER]
-    t_hdr = max(os.path.getmtime(h) for h in headers if os.path.exists(h))
+    t_hdr = max(os.path.getmtime(h) for h in HEADERS if os.path.exists(h))
     flags = FLAGS + (["-DBP_AB_KERNELS"] if ab else [])
 
     def compile_one(src: str) -> str:
@@ -129,7 +131,8 @@ def build_library(force: bool = False, verbose: bool = False, ab: bool = False) 
             os.remove(os.path.join(obj_dir, stale))
     with ThreadPoolExecutor(max_workers=min(8, os.cpu_count() or 1)) as pool:
         objs = list(pool.map(compile_one, sources))
-    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", lib_path + ".tmp"] + objs
+    # -z defs: a declared function that nothing defines fails here, not at the dlopen
+    cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-Wl,-z,defs", "-o", lib_path + ".tmp"] + objs
     res = subprocess.run(cmd, capture_output=True, text=True)
     if res.returncode != 0:
         raise RuntimeError("hipcc link failed:\n" + res.stdout + res.stderr)

@@ -21,7 +21,7 @@
 #include <vector>
 
 #include "../../include/basic_pitch_amd.h"
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -1,5 +1,5 @@
-// Private to csrc: the handle (struct bp_context) and what bp_api.hip and track_api.hip share of it — the kernel launches
-// both call, the HIP error macro and the workspace / chunk / wait helpers (defined in bp_api.hip).
+// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip and weight_pack.hip share of it — the
+// HIP error macro and the workspace / chunk / wait helpers (defined in bp_api.hip).
 #pragma once
 #include "../../include/basic_pitch_amd.h"
 
@@ -7,55 +7,7 @@
 #include <string>
 #include <vector>
 
-#include "bp_common.h"
-
-namespace bp {
-// kernels the track entry points launch (one translation unit each)
-void launch_window_track(const float* samples, int64_t n_samples, int64_t first_window, int n_windows,
-                         float* audio, int win_len, int hop, int lead, hipStream_t stream);
-void launch_window_tracks(const TrackSegs& ts, int n_slots, float* audio, int win_len, int hop, int lead,
-                          hipStream_t stream);
-void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
-                          hipStream_t stream);
-void launch_unwrap3(const float* note, const float* onset, const float* contour, int64_t first_window, int n_windows,
-                    int64_t total_rows, float* o_note, float* o_onset, float* o_contour, hipStream_t stream);
-ResamplePlan make_resample_plan(int source_rate, int target_rate, std::vector<double>& taps);
-void launch_downmix(const float* pcm, int64_t n_frames, int channels, float* mono, hipStream_t stream);
-void launch_downmix_raw(const void* raw, int format, int64_t n_frames, int channels, float* mono, hipStream_t stream);
-void launch_resample(const float* x, int64_t n_in, const double* taps, const ResamplePlan& pl, float* y,
-                     int64_t n_out, int mode, hipStream_t stream);
-// flac_device.hip
-struct FdStream {
-  int channels, bits, min_block, max_block;
-  int64_t total;
-  uint32_t audio_start, nbytes;
-};
-struct FlacDeviceBuffers {
-  uint8_t* file = nullptr;
-  size_t file_cap = 0;
-  void* cands = nullptr;
-  uint32_t* counts = nullptr;
-  size_t cands_cap = 0, counts_cap = 0;
-  void* packed = nullptr;
-  uint32_t* offs = nullptr;
-  size_t packed_cap = 0, offs_cap = 0;
-  void* frames = nullptr;
-  int32_t* scratch = nullptr;
-  size_t frames_cap = 0, scratch_cap = 0;
-  int* meta = nullptr;
-  uint16_t* crc_tab = nullptr;
-};
-int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream);
-void flac_device_free(FlacDeviceBuffers& b);
-// note_device.hip
-void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,
-                            double onset_thresh, const void* tab, const double* gauss, void* stats, uint8_t* bits,
-                            int8_t* bend, hipStream_t s);
-void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, const void* bits, void* bits_dst,
-                        int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
-                        void* stats_dst, hipStream_t s);
-void launch_note_stats_init(void* stats, hipStream_t s);
-}  // namespace bp
+#include "bp_kernels.h"
 
 struct bp_context {
   int device = 0;
@@ -82,12 +34,11 @@ struct bp_context {
   float *d_note_wfrag = nullptr, *d_note_w16 = nullptr, *d_note_wf32 = nullptr, *d_onset_wfrag = nullptr, *d_onset_wf32 = nullptr,
         *d_onset_wmx = nullptr, *d_onset_w16 = nullptr;
   float* zp = nullptr;  // uint32 [cap][kZRowsP][kZRow] pre-split z, zero padded (bp_common.h)
-  // contour branch, two-kernel form (conv_contour_direct.hip): LDS weight image, bias[8], conv2 taps [5][5][8]
-  float *d_d1_wlds = nullptr, *d_d1_wfold = nullptr, *d_d1_wmarch = nullptr, *d_d1_wrim = nullptr, *d_d1_wrimm = nullptr, *d_d1_bias = nullptr,
+  // contour branch: conv1 A fragments (interior march, round-2 folded, rim GEMM, rim march), bias[8], conv2 taps [5][5][8]
+  float *d_d1_wfold = nullptr, *d_d1_wmarch = nullptr, *d_d1_wrim = nullptr, *d_d1_wrimm = nullptr, *d_d1_bias = nullptr,
         *d_d2_w = nullptr, *d_d2_wproj = nullptr;
-  bool rim_exact = false, fold_mx = false;
+  bool fold_mx = false;
   int resample_mode = 0;  // BP_RESAMPLE=plain|tiled: 1 | 2 (A/B runs of the resampling kernels)
-  int contour_parts = 0;  // BP_CONTOUR_PARTS (0: automatic)
   float* d_d1_wfold_mx = nullptr;
   float* c1s = nullptr;  // [cap][172][kC1Row][8] relu(conv1); pad bins zeroed once at allocation
   // cqt_planes.hip: decimator / filterbank fragments (raw bytes of f16 hi / lo), the planes of a chunk [cap][2][stride] f16
@@ -126,9 +77,9 @@ struct bp_context {
   // stage timing: a ring of event sets, one per chunk, averaged by bp_get_stage_ms
   static constexpr int kTimedRing = 128;
   static constexpr int kDomEvery = 4;
-  static constexpr int kMaxMarks = 32;  // a stage may be launched in parts (the contour branch): its intervals are summed
+  static constexpr int kMaxMarks = 32;  // intervals per chunk (bp_get_stage_ms sums those of a stage)
   hipEvent_t ev[kTimedRing][kMaxMarks + 1] = {};
-  // per ring slot (the mark sequence depends on the chunk: zpack only below half a window per CU, contour parts):
+  // per ring slot (the mark sequence depends on the chunk: zpack only below half a window per CU):
   // stage id of the interval between ev[c][i] and ev[c][i+1]; -1: not a stage (skipped)
   int seq[kTimedRing][kMaxMarks] = {};
   int n_seq[kTimedRing] = {};
@@ -150,7 +101,7 @@ struct bp_context {
   } while (0)
 
 namespace bp {
-int upload(bp_handle h, const std::vector<float>& host, float** dev);
+int upload(bp_handle h, const void* host, size_t bytes, float** dev);
 int alloc(bp_handle h, float** p, int64_t floats);
 int grow(bp_handle h, float** buf, int64_t* cap, int64_t need);
 int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float* onset_dev, float* contour_dev);

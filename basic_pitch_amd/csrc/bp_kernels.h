@@ -1,0 +1,142 @@
+// Private to csrc: the host functions each kernel file exports to the rest of the library, and the FLAC decoder's host
+// structs.  Every file that defines one of these includes this header, so the compiler checks each definition against
+// its declaration.  Declarations under BP_AB_KERNELS exist only in the A/B library (build.py AB_SOURCES).
+#pragma once
+#include <vector>
+
+#include "bp_common.h"
+
+namespace bp {
+
+// cqt_pyramid.hip
+void launch_pyramid(const float* audio, float* pyr, const float* lowpass, int n_windows, hipStream_t s);
+void launch_window_track(const float* samples, int64_t n_samples, int64_t first_window, int n_windows,
+                         float* audio, int win_len, int hop, int lead, hipStream_t stream);
+void launch_window_tracks(const TrackSegs& ts, int n_slots, float* audio, int win_len, int hop, int lead,
+                          hipStream_t stream);
+void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
+                          hipStream_t stream);
+void launch_unwrap3(const float* note, const float* onset, const float* contour, int64_t first_window, int n_windows,
+                    int64_t total_rows, float* o_note, float* o_onset, float* o_contour, hipStream_t stream);
+
+// cqt_filterbank.hip: the exact-f32 filterbank (BP_FLAG_F32_MFMA)
+size_t filterbank_scratch_floats(int n_windows);
+void launch_filterbank(const float* audio, const float* pyr, const float* bfrag, const float* sqrt_len,
+                       float* lp, int* mm, float* scratch, int n_windows, LogConsts kc, int n_cu,
+                       hipStream_t s);
+void launch_mm_reduce(const float* scratch, int* mm, int n_windows, int n_partials, hipStream_t stream);
+
+// cqt_planes.hip: the pyramid as pre-split, reflect-padded f16 planes; operands straight from HBM / L2
+int64_t planes_elements_per_window(bool ext);
+void launch_planes_split(const float* src, int64_t src_stride, int level, uint16_t* pl, int n_windows, bool ext,
+                         hipStream_t stream);
+void launch_planes_unsplit(const uint16_t* pl, int level, float* dst, int64_t dst_stride, int n_windows, bool ext,
+                           hipStream_t stream);
+void launch_planes_edge_rows(const float* audio, int64_t audio_stride, uint16_t* pl, int n_windows, bool ext,
+                             hipStream_t stream);
+void launch_pyramid_planes(const float* audio, int64_t audio_stride, uint16_t* pl, const void* tfrag, int n_windows,
+                           int n_cu, bool ext, hipStream_t stream);
+int filterbank_planes_partials(bool ext);
+bool launch_filterbank_planes(const uint16_t* pl, const float* audio, int64_t audio_stride, const void* bfrag,
+                              const float* bin_consts, float* lp, float* scratch,
+                              uint32_t* zp, int n_windows, LogConsts kc, int n_cu, bool ext, hipStream_t stream);
+void filterbank_planes_bin_consts(const float* sqrt_len, int n_bins, LogConsts kc, float* out);
+
+// conv_contour1.hip, conv_stride3.hip, conv_heads.hip: the exact-f32 layers (BP_FLAG_F32_MFMA)
+void launch_contour1(const float* lp, const int* mm, const float* bfrag, const float* bias, float* c1,
+                     int n_windows, LogConsts kc, int n_cu, hipStream_t s);
+void launch_onset1(const float* lp, const int* mm, const float* bfrag, const float* bias, float* o1,
+                   int n_windows, LogConsts kc, int n_cu, hipStream_t s);
+void launch_note1(const float* contour, const float* bfrag, const float* bias, float* n1, int n_windows,
+                  int n_cu, hipStream_t s);
+void launch_contour2(const float* c1, const float* wgt, float bias, float* contour, int n_windows,
+                     hipStream_t s);
+void launch_note2(const float* n1, const float* wgt, float bias, float* note, int n_windows,
+                  hipStream_t s);
+void launch_onset2(const float* note, const float* o1, const float* wgt, float bias, float* onset,
+                   int n_windows, hipStream_t s);
+
+// conv_branch.hip: z pack
+void launch_zpack(const float* lp, const int* mm, uint32_t* zp, int n_windows, LogConsts kc, int n_bins,
+                  hipStream_t s);
+void launch_zpack_partials(const float* lp, const float* scratch, int n_partials, uint32_t* zp, int n_windows,
+                           LogConsts kc, int n_bins, hipStream_t stream);
+
+// contour conv1: conv_contour_march.hip (interior), conv_contour_rim_march.hip and conv_contour_rim.hip (rim)
+bool contour_conv1_use_march();
+void launch_contour_conv1_march(const uint32_t* zp, const void* wfrag, const float* bias, float* c1, int n_windows, int n_cu,
+                                bool weights_have_lo, hipStream_t stream);
+void launch_contour_conv1_rim(const uint32_t* zp, const void* afrag, const float* bias, float* c1, int n_windows, int n_cu,
+                              bool weights_have_lo, bool ext, hipStream_t stream);
+void launch_contour_conv1_rim_march(const uint32_t* zp, const void* afrag, const float* bias, float* c1, int n_windows, int n_cu,
+                                    bool weights_have_lo, hipStream_t stream);
+// conv_contour2.hip
+void launch_contour_conv2_proj(const float* c1, const void* wfrag, float bias, float* contour, int n_windows, int n_cu,
+                               bool weights_have_lo, hipStream_t stream);
+// note_march16.hip, onset_march16.hip
+void launch_note_march16(const float* contour, const void* wfrag, const float* wf32, float* note, int n_windows, int n_cu,
+                         bool weights_have_lo, hipStream_t stream);
+void launch_onset_march16(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, float* onset,
+                          int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
+
+#ifdef BP_AB_KERNELS
+// conv_contour_direct.hip: the round-2 folded conv1 (BP_CONV1=rounds)
+void launch_contour_conv1_folded(const uint32_t* zp, const void* wfold, const float* bias, float* c1, int n_windows,
+                                 int n_cu, bool weights_have_lo, hipStream_t stream);
+// conv_contour_fold_mx.hip: the fp8-correction mode's contour conv1
+void launch_contour_conv1_fold_mx(const uint32_t* zp, const void* a16, const void* amx, const void* ascale,
+                                  const float* bias, float* c1, int n_windows, int n_cu, hipStream_t stream);
+// conv_contour2.hip: the round-2 vector kernel (BP_CONV2=valu)
+void launch_contour_conv2(const float* c1, const float* w2, float bias, float* contour, int n_windows, int n_cu,
+                          hipStream_t stream);
+// note_march.hip, onset_march.hip: the 32x32x16 forms of the marches (BP_NOTE=march32, BP_ONSET=march32)
+void launch_note_march(const float* contour, const void* wfrag, const float* wf32, float* note, int n_windows,
+                       bool weights_have_lo, hipStream_t stream);
+void launch_onset_march(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, float* onset,
+                        int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
+// conv_branch.hip: the workgroup onset kernel (BP_ONSET=ring, and the fp8-correction mode)
+void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* wmx,
+                         float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
+#endif
+
+// audio_ingest.hip
+ResamplePlan make_resample_plan(int source_rate, int target_rate, std::vector<double>& taps);
+void launch_downmix(const float* pcm, int64_t n_frames, int channels, float* mono, hipStream_t stream);
+void launch_downmix_raw(const void* raw, int format, int64_t n_frames, int channels, float* mono, hipStream_t stream);
+void launch_resample(const float* x, int64_t n_in, const double* taps, const ResamplePlan& pl, float* y,
+                     int64_t n_out, int mode, hipStream_t stream);
+
+// flac_device.hip
+struct FdStream {
+  int channels, bits, min_block, max_block;
+  int64_t total;       // samples per channel
+  uint32_t audio_start, nbytes;
+};
+struct FlacDeviceBuffers {
+  uint8_t* file = nullptr;      // the file's bytes + 64 zero bytes
+  size_t file_cap = 0;
+  void* cands = nullptr;        // FdCand [chunks][kFdChunkCands]
+  uint32_t* counts = nullptr;
+  size_t cands_cap = 0, counts_cap = 0;
+  void* packed = nullptr;       // FdCand, in file order
+  uint32_t* offs = nullptr;
+  size_t packed_cap = 0, offs_cap = 0;
+  void* frames = nullptr;       // FdFrame
+  int32_t* scratch = nullptr;
+  size_t frames_cap = 0, scratch_cap = 0;
+  int* meta = nullptr;          // [0] status, [1] n_frames
+  uint16_t* crc_tab = nullptr;
+};
+int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream);
+void flac_device_free(FlacDeviceBuffers& b);
+
+// note_device.hip
+void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,
+                            double onset_thresh, const void* tab, const double* gauss, void* stats, uint8_t* bits,
+                            int8_t* bend, hipStream_t s);
+void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, const void* bits, void* bits_dst,
+                        int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
+                        void* stats_dst, hipStream_t s);
+void launch_note_stats_init(void* stats, hipStream_t s);
+
+}  // namespace bp

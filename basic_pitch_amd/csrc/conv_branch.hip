@@ -34,10 +34,9 @@
 // Roofline: bound = f16 MFMA issue.  Algorithmic work per window: note 47.5 + 20.3 MFLOP, onset
 // 193.7 + 9.0 MFLOP.  HBM bytes per window: note 181,632 read + 60,544
 // written; onset 214,656 (zp) + 60,544 (note) read + 60,544 written.
-#include <stdio.h>
 #include <stdlib.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 
@@ -61,7 +60,6 @@ struct BranchParams {
   const float* note;   // onset only: note posteriorgram [n][172][88]
   float* out;          // [n][172][88]
   int n_windows;
-  unsigned long long* prof;  // tools only: per-phase reference-clock totals of block 0 (null in production)
   const uint4* wmx;    // MX kernels: [kMxSteps][64 lanes][2] x 16 bytes of fp8 conv1 corrections, then [64] E8M0 scales
 };
 
@@ -249,17 +247,9 @@ __device__ __forceinline__ void raw_convert(int row_first, const uint4* raw_, ui
 // WLO = false: conv1 weights without a lo part (BP_FLAG_BF16_WEIGHTS): 2 MFMAs per k-step
 // MX = true (onset, WLO): conv1's two correction products on the block-scaled fp8 instruction, everything in ONE
 // accumulator: per tile 13 f16 + 7 fp8 matrix instructions (864 pipe cycles) instead of 39 f16 ones (1248)
-template <class Br, bool WLO, bool PROF = false, bool MX = false>
+template <class Br, bool WLO, bool MX = false>
 __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParams p) {
   static_assert(!MX || (Br::kOnset && WLO), "the fp8-correction variant exists for the onset branch");
-  unsigned long long acc_t[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long t_prev = PROF ? __builtin_readcyclecounter() : 0;
-#define BR_STAMP(k)                                                \
-  if (PROF) {                                                      \
-    const unsigned long long t_now = __builtin_readcyclecounter(); \
-    acc_t[k] += t_now - t_prev;                                    \
-    t_prev = t_now;                                                \
-  }
   constexpr int KS1 = Br::KS1, KH2 = Br::KH2, PH1 = Br::PH1, PH2 = Br::PH2;
   __shared__ __attribute__((aligned(16))) uint4 img_hi[Br::RING * Br::SLOTS];
   __shared__ __attribute__((aligned(16))) uint4 img_lo[Br::RING * Br::SLOTS];
@@ -348,7 +338,6 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
 
     for (int ph = 0; ph < n_phase; ++ph) {
       const int r0 = T0 - PH2 + kBrRows * ph;  // first conv1 row of this phase
-      BR_STAMP(0);
       // the next phase's source rows start their way into LDS now (raw was consumed before the last barrier)
       if (ph + 1 < n_phase) raw_dma_issue<Br>(p, b, r0 + kBrRows + PH1, raw, wave, lane);
       float note_cur[kBrTilesPerRow];
@@ -534,11 +523,9 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
           }
         }
       }
-      BR_STAMP(1);
       if (ph + 1 < n_phase) fetch_notes(r0 + kBrRows);
       __builtin_amdgcn_s_waitcnt(0x0F70);  // vmcnt(0): this wave's share of the DMA (and the note values) has landed
       lds_barrier();
-      BR_STAMP(2);
 
       // ---- output rows r0-PH2 .. r0-PH2+3 (one per wave), then the next 4 image rows
       {
@@ -558,18 +545,10 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
           }
         }
       }
-      BR_STAMP(3);
       if (ph + 1 < n_phase) raw_convert<Br, MX>(r0 + kBrRows + PH1, raw, img_hi, img_lo, threadIdx.x);
-      BR_STAMP(4);
       lds_barrier();
-      BR_STAMP(5);
     }
   }
-  if (PROF && blockIdx.x == 0 && lane == 0) {
-#pragma unroll
-    for (int k = 0; k < 6; ++k) p.prof[wave * 6 + k] = acc_t[k];
-  }
-#undef BR_STAMP
 }
 #endif  // BP_AB_KERNELS
 
@@ -648,34 +627,9 @@ template <class Br>
 static void launch_branch(const BranchParams& p, int n_cu, bool weights_have_lo, hipStream_t stream) {
   const int items = p.n_windows * Br::CHUNKS;
   const int grid = items < Br::WGS * n_cu ? items : Br::WGS * n_cu;
-#ifdef BP_AB_KERNELS  // tools only (A/B builds): phase profile of block 0 to stderr
-  static const bool prof = ab_env("BP_BRANCH_PROF") != nullptr;
-  if (prof) {
-    BranchParams q = p;
-    unsigned long long hbuf[24];
-    int resident = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, branch_kernel<Br, true>, kBrThreads, 0);
-    fprintf(stderr, "brprof %s: %d workgroups resident per CU\n", Br::kOnset ? "onset" : "note", resident);
-    if (hipMalloc(&q.prof, sizeof hbuf) != hipSuccess) return;
-    (void)hipMemsetAsync(q.prof, 0, sizeof hbuf, stream);
-    if (p.wmx)
-      hipLaunchKernelGGL((branch_kernel<Br, true, true, true>), dim3(grid), dim3(kBrThreads), 0, stream, q);
-    else
-      hipLaunchKernelGGL((branch_kernel<Br, true, true>), dim3(grid), dim3(kBrThreads), 0, stream, q);
-    (void)hipMemcpyAsync(hbuf, q.prof, sizeof hbuf, hipMemcpyDeviceToHost, stream);
-    (void)hipStreamSynchronize(stream);
-    (void)hipFree(q.prof);
-    for (int w = 0; w < 4; ++w) {
-      fprintf(stderr, "brprof %s wave %d:", Br::kOnset ? "onset" : "note", w);
-      for (int k = 0; k < 6; ++k) fprintf(stderr, " %llu", hbuf[w * 6 + k]);
-      fprintf(stderr, "\n");
-    }
-    return;
-  }
-#endif
   if constexpr (Br::kOnset) {
     if (weights_have_lo && p.wmx) {
-      hipLaunchKernelGGL((branch_kernel<Br, true, false, true>), dim3(grid), dim3(kBrThreads), 0, stream, p);
+      hipLaunchKernelGGL((branch_kernel<Br, true, true>), dim3(grid), dim3(kBrThreads), 0, stream, p);
       return;
     }
   }
@@ -688,8 +642,7 @@ static void launch_branch(const BranchParams& p, int n_cu, bool weights_have_lo,
 // wmx: the fp8 correction fragments (pack_onset_mx) or null for the three-product f16 kernel
 void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* wmx,
                          float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
-  BranchParams p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows, nullptr,
-                 static_cast<const uint4*>(wmx)};
+  BranchParams p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows, static_cast<const uint4*>(wmx)};
   launch_branch<OnsetBr>(p, n_cu, weights_have_lo, stream);
 }
 #endif  // BP_AB_KERNELS

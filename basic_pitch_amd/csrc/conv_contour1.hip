@@ -25,7 +25,7 @@
 // Roofline (this kernel): bound = f32 MFMA (157.3 TFLOP/s).  Algorithmic work 8*8*3*39*172*264*2 =
 // 680,030,208 FLOP / window (executed on MFMA: 732 MFLOP incl. Toeplitz padding).  Algorithmic
 // bytes: 212,592 read (lp) + 1,453,056 written (c1).
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

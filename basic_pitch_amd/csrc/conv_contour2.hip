@@ -7,7 +7,7 @@
 // the HBM rate nor at the vector rate) stays in the A/B library behind BP_CONV2=valu.
 #include <stdlib.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -30,7 +30,7 @@
 #include <stdlib.h>
 #include <string.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

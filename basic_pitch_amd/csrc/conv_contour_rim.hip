@@ -28,7 +28,7 @@
 // Roofline: f16 MFMA issue.  Algorithmic work 103 MFLOP per window (the reference's 8-channel products for 40 of 264
 // bins); executed 4860 x 3 MFMAs; bytes per window: 2 x 172 x 576 B of zp read, 220 KB of c1 written, 1.6 MB of A
 // fragments from L2.
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

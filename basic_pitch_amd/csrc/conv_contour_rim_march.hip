@@ -25,7 +25,7 @@
 // bytes per window: 2 x 11 x 18 x 576 B of zp read (through L2), 220 KB of c1 written; A: 573 KB per WORKGROUP lifetime.
 #include <stdio.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -14,7 +14,7 @@
 //     2*KW*4 FMAs (>= 10 FMA per LDS read: above the 8:1 VALU:LDS issue ratio of a CU);
 //   * weights are wave-uniform -> scalar loads, used as SGPR operands of v_fma_f32.
 // Roofline: f32 VALU; algorithmic work 18.2 / 20.3 / 9.0 MFLOP per window.
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -18,7 +18,7 @@
 //
 // Roofline: bound = f32 MFMA.  Algorithmic work 193.7 MFLOP (onset) + 47.5 MFLOP (note) per window;
 // bytes: 212,592 (lp) resp. 181,632 (contour) read, 1,937,408 written each.
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -24,7 +24,7 @@
 // Roofline (this kernel): bound = f32 MFMA; algorithmic work 9 * 172 * 72 * 256 MAC = 57.06 MFLOP
 // per window (dense; 34.8 MFLOP on non-zero taps), algorithmic bytes 175,376 (audio) + 174,764
 // (pyramid) read + 212,592 written.
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -29,7 +29,7 @@
 #include <cstring>
 #include <type_traits>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

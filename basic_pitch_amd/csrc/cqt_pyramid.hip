@@ -12,7 +12,7 @@
 // staged once in LDS and every thread produces two adjacent outputs from 65 ds_read_b128, so the
 // kernel is VALU-issue bound, not LDS- or HBM-bound.  Algorithmic bytes per window: 175,376 B read
 // (level 0) + 174,764 B of pyramid written.
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -34,7 +34,7 @@
 #include <stdint.h>
 #include <stdio.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 
@@ -63,12 +63,6 @@ struct FdFrame {
   uint32_t blocksize, hdr_bytes;
   int64_t first_sample;
   uint32_t ch_code, pad;
-};
-
-struct FdStream {
-  int channels, bits, min_block, max_block;
-  int64_t total;       // samples per channel
-  uint32_t audio_start, nbytes;
 };
 
 __device__ __forceinline__ uint8_t fd_crc8(const uint8_t* d, int n) {
@@ -973,22 +967,6 @@ __global__ __launch_bounds__(256) void flac_finalize_kernel(FdDecodeParams p) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-struct FlacDeviceBuffers {  // (the same layout is declared in bp_api.hip)
-  uint8_t* file = nullptr;      // the file's bytes + 64 zero bytes
-  size_t file_cap = 0;
-  void* cands = nullptr;        // FdCand [chunks][kFdChunkCands]
-  uint32_t* counts = nullptr;
-  size_t cands_cap = 0, counts_cap = 0;
-  void* packed = nullptr;       // FdCand, in file order
-  uint32_t* offs = nullptr;
-  size_t packed_cap = 0, offs_cap = 0;
-  void* frames = nullptr;       // FdFrame
-  int32_t* scratch = nullptr;
-  size_t frames_cap = 0, scratch_cap = 0;
-  int* meta = nullptr;          // [0] status, [1] n_frames
-  uint16_t* crc_tab = nullptr;
-};
-
 static int fd_grow(void** p, size_t* cap, size_t want, size_t elem) {
   if (want <= *cap) return 0;
   if (*p) (void)hipFree(*p);

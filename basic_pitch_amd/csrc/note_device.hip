@@ -16,7 +16,7 @@
 // The arithmetic is the host decoder's, operation for operation (float64 differences and quotient, IEEE division; float64
 // products for the bend's argmax with the host's Gaussian table): the same bits, the same events —
 // tests/test_gpu_parity.py::test_device_note_candidates_give_the_host_decoders_events.
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -21,10 +21,9 @@
 //     out[t] = (((((q0 + q1) + q2) + q3) + q4) + q5) + q6 + bias — the old kernel's summation order.
 // Roofline: f16 MFMA issue; 18 MFMAs (12 conv1 + 6 projection) per 30 output pixels; HBM 182 KB read (+28 % chunk
 // halo) and 61 KB written per window.
-#include <stdio.h>
 #include <stdlib.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 
@@ -255,12 +254,6 @@ void launch_note_march(const float* contour, const void* wfrag, const float* wf3
   NoteMarchParams p{static_cast<const uint4*>(wfrag), wf32, contour, note, n_windows * chunks * kNmStrips, chunks};
   if (p.n_tasks <= 0) return;
   const int grid = (p.n_tasks + kNmWaves - 1) / kNmWaves;
-  static const bool prof = ab_env("BP_BRANCH_PROF") != nullptr;
-  if (prof) {  // tools only
-    int resident = 0;
-    (void)hipOccupancyMaxActiveBlocksPerMultiprocessor(&resident, note_march_kernel<true>, 64 * kNmWaves, 0);
-    fprintf(stderr, "brprof note_march: %d workgroups resident per CU, grid %d\n", resident, grid);
-  }
   if (weights_have_lo)
     hipLaunchKernelGGL(note_march_kernel<true>, dim3(grid), dim3(64 * kNmWaves), 0, stream, p);
   else

@@ -35,7 +35,7 @@
 #include <stdio.h>
 #include <stdlib.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

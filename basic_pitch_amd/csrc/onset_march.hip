@@ -25,7 +25,7 @@
 // Roofline: f16 MFMA issue; 45 MFMAs (39 conv1 + 6 projection) per 30 output pixels; + 9 % rows of chunk halo.
 #include <stdlib.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -31,7 +31,7 @@
 // Roofline: f16 MFMA issue; 90 16x16x32 per 30 output pixels; + 9 % rows of chunk halo.
 #include <stdlib.h>
 
-#include "bp_common.h"
+#include "bp_kernels.h"
 
 namespace bp {
 

@@ -237,7 +237,7 @@ int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params
   if (!h->nd_tables) {
     std::vector<float> raw((kTabBytes + kGaussBytes + kStatsBytes) / 4, 0.f);
     bp_internal_bend_tables(reinterpret_cast<int32_t*>(raw.data()), reinterpret_cast<double*>(raw.data() + kTabBytes / 4));
-    int rc = upload(h, raw, &h->nd_tables);
+    int rc = upload(h, raw.data(), raw.size() * sizeof(float), &h->nd_tables);
     if (rc) return rc;
     BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->nd_stats_host), kStatsBytes, hipHostMallocPortable));
     BP_HIP(hipHostGetDevicePointer(&h->nd_stats_host_dev, h->nd_stats_host, 0));

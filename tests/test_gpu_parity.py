@@ -854,7 +854,7 @@ def _ab_env(**switches):
     only exist in the A/B library (build.py: build_library(ab=True), -DBP_AB_KERNELS), which is built here if the tree
     does not hold a current one; with no switches, the product library."""
     e = dict(os.environ)
-    for k in ("BASIC_PITCH_AMD_LIB", "BP_ONSET", "BP_NOTE", "BP_CONV1", "BP_CONV2", "BP_RIM", "BP_RESAMPLE", "BP_CONTOUR_PARTS"):
+    for k in ("BASIC_PITCH_AMD_LIB", "BP_ONSET", "BP_NOTE", "BP_CONV1", "BP_CONV2", "BP_RIM", "BP_RESAMPLE"):
         e.pop(k, None)
     if switches:
         from basic_pitch_amd import build as B
