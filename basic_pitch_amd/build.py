@@ -47,7 +47,6 @@ AB_SOURCES = [
     "conv_contour_direct.hip",  # round-2 folded conv1 of the interior bins (BP_CONV1=rounds)
     "onset_march.hip",          # onset march on 32x32x16 (BP_ONSET=march32)
     "note_march.hip",           # note march on 32x32x16 (BP_NOTE=march32)
-    "conv_contour_fold_mx.hip", # contour conv1 of the fp8-corrections mode (BP_FLAG_FP8_CORRECTIONS: A/B library only since round 6)
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects

@@ -13,28 +13,25 @@
 #include "weight_pack.h"
 
 namespace bp {
-// the onset branch: the wave-private march on 16x16x32.  A/B builds only: the workgroup kernel for the fp8-correction
-// mode (it carries the block-scaled products), BP_ONSET=march32 selects the 32x32x16 form of the march, BP_ONSET=ring the
-// workgroup kernel without fp8.
-static void launch_onset(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* wmx,
-                         const void* w16, float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
-  int kind = 0;
+// the onset branch: the wave-private march on 16x16x32.  A/B builds only: BP_ONSET=march32 selects the 32x32x16 form of
+// the march, BP_ONSET=ring the workgroup kernel.
+static void launch_onset(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* w16,
+                         float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
 #ifdef BP_AB_KERNELS
-  static const int env_kind = [] {
+  static const int kind = [] {
     const char* e = ab_env("BP_ONSET");
     return e && std::strcmp(e, "ring") == 0 ? 2 : (e && std::strcmp(e, "march32") == 0 ? 1 : 0);
   }();
-  kind = env_kind;
-  if (kind == 1 && !wmx) {
+  if (kind == 1) {
     launch_onset_march(zp, note, wfrag, wf32, onset, n_windows, n_cu, weights_have_lo, stream);
     return;
   }
-  if (wmx || kind == 2) {
-    launch_onset_branch(zp, note, wfrag, wf32, wmx, onset, n_windows, n_cu, weights_have_lo, stream);
+  if (kind == 2) {
+    launch_onset_branch(zp, note, wfrag, wf32, onset, n_windows, n_cu, weights_have_lo, stream);
     return;
   }
 #endif
-  (void)wfrag, (void)wmx, (void)kind;
+  (void)wfrag;
   launch_onset_march16(zp, note, w16, wf32, onset, n_windows, n_cu, weights_have_lo, stream);
 }
 // contour conv2: the tap projection on the matrix cores (round 6).  A/B builds only: BP_CONV2=valu selects the round-2 kernel.
@@ -95,7 +92,7 @@ namespace {
 thread_local std::string g_create_error;
 
 int free_all(bp_handle h) {
-  float* ptrs[] = {h->d_pl_tfrag, h->d_pl_bfrag, h->d_pl_bin_k, h->planes, h->d_note_wfrag, h->d_note_w16, h->d_note_wf32, h->d_onset_wfrag, h->d_onset_wf32, h->d_onset_wmx, h->d_onset_w16, h->zp, h->c1s, h->d_d1_wfold, h->d_d1_wmarch, h->d_d1_wrim, h->d_d1_wrimm, h->d_d1_wfold_mx, h->d_d1_bias, h->d_d2_w, h->d_d2_wproj, h->d_lowpass, h->d_sqrt_len, h->d_fb_bfrag, h->d_c1_bfrag, h->d_c1_bias, h->d_o1_bfrag,
+  float* ptrs[] = {h->d_pl_tfrag, h->d_pl_bfrag, h->d_pl_bin_k, h->planes, h->d_note_wfrag, h->d_note_w16, h->d_note_wf32, h->d_onset_wfrag, h->d_onset_wf32, h->d_onset_w16, h->zp, h->c1s, h->d_d1_wfold, h->d_d1_wmarch, h->d_d1_wrim, h->d_d1_wrimm, h->d_d1_bias, h->d_d2_w, h->d_d2_wproj, h->d_lowpass, h->d_sqrt_len, h->d_fb_bfrag, h->d_c1_bfrag, h->d_c1_bias, h->d_o1_bfrag,
                    h->d_o1_bias, h->d_n1_bfrag, h->d_n1_bias, h->d_w_contour2, h->d_w_note2, h->d_w_onset2,
                    h->audio, h->pyr, h->lp, h->c1, h->contour, h->n1, h->note, h->o1, h->onset, h->track,
                    h->track_out, h->nd_buf, h->nd_tables, h->fb_scratch, h->pcm_dev, h->mono_dev, h->res_dev, reinterpret_cast<float*>(h->taps_dev)};
@@ -136,16 +133,9 @@ static void launch_rim(bp_handle h, const uint32_t* zp, float* c1, int n, bool w
     launch_contour_conv1_rim_march(zp, h->d_d1_wrimm, h->d_d1_bias, c1, n, h->n_cu, wlo, s);
 }
 
-// The interior of contour conv1: the vertical march.  A/B library only: the fp8-correction kernel (BP_FLAG_FP8_CORRECTIONS)
-// and, on BP_CONV1=rounds, the round-2 folded kernel.
+// The interior of contour conv1: the vertical march.  A/B library only: the round-2 folded kernel on BP_CONV1=rounds.
 static void launch_conv1_interior(bp_handle h, const uint32_t* zp, float* c1, int n, bool wlo, hipStream_t s) {
 #ifdef BP_AB_KERNELS
-  if (h->fold_mx && wlo) {
-    const char* base = reinterpret_cast<const char*>(h->d_d1_wfold_mx);
-    launch_contour_conv1_fold_mx(zp, base, base + 36 * 64 * 16, base + 36 * 64 * 16 + 18 * 64 * 32, h->d_d1_bias, c1, n,
-                                 h->n_cu, s);
-    return;
-  }
   if (!contour_conv1_use_march()) {
     launch_contour_conv1_folded(zp, h->d_d1_wfold, h->d_d1_bias, c1, n, h->n_cu, wlo, s);
     return;
@@ -251,8 +241,7 @@ int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float
     BP_MARK(BP_STAGE_CONTOUR_CONV2);
     launch_note(contour_dev, h->d_note_wfrag, h->d_note_w16, h->d_note_wf32, note_dev, n, h->n_cu, wlo, s);
     BP_MARK(BP_STAGE_NOTE);
-    launch_onset(zp, note_dev, h->d_onset_wfrag, h->d_onset_wf32, h->d_onset_wmx, h->d_onset_w16, onset_dev,
-                 n, h->n_cu, wlo, s);
+    launch_onset(zp, note_dev, h->d_onset_wfrag, h->d_onset_wf32, h->d_onset_w16, onset_dev, n, h->n_cu, wlo, s);
     BP_MARK(BP_STAGE_ONSET);
   }
 #undef BP_MARK
@@ -378,7 +367,6 @@ int bp_create(const void* weights, size_t nbytes, int device_ordinal, unsigned f
   h->b_contour2 = pw.b_contour2;
   h->b_note2 = pw.b_note2;
   h->b_onset2 = pw.b_onset2;
-  h->fold_mx = pw.fold_mx;
   if (const char* es = ab_env("BP_RESAMPLE"))  // A/B runs: the resampler's simpler kernels (bit-identical results)
     h->resample_mode = std::strcmp(es, "plain") == 0 ? 1 : std::strcmp(es, "tiled") == 0 ? 2 : 0;
 
@@ -685,7 +673,7 @@ int bp_run_stage(bp_handle h, int stage, const bp_stage_buffers* bf, int64_t n_w
       break;
     case BP_STAGE_ONSET:
       if ((ok = need(bf->zp) && need(bf->note) && need(bf->onset)))
-        launch_onset(bf->zp, bf->note, h->d_onset_wfrag, h->d_onset_wf32, h->d_onset_wmx, h->d_onset_w16, bf->onset, n, h->n_cu, wlo, s);
+        launch_onset(bf->zp, bf->note, h->d_onset_wfrag, h->d_onset_wf32, h->d_onset_w16, bf->onset, n, h->n_cu, wlo, s);
       break;
     default:
       h->err = "bp_run_stage: unknown stage";

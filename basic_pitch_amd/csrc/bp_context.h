@@ -32,14 +32,12 @@ struct bp_context {
   float* d_pl_bin_k = nullptr;  // cqt_planes.hip filterbank: per-bin eps / s^2, s = sqrt(len) 2^-12
   // fused branches (conv_branch.hip): f16 hi/lo A fragments (raw bytes) + {bias1[32], extra[9], bias2}
   float *d_note_wfrag = nullptr, *d_note_w16 = nullptr, *d_note_wf32 = nullptr, *d_onset_wfrag = nullptr, *d_onset_wf32 = nullptr,
-        *d_onset_wmx = nullptr, *d_onset_w16 = nullptr;
+        *d_onset_w16 = nullptr;
   float* zp = nullptr;  // uint32 [cap][kZRowsP][kZRow] pre-split z, zero padded (bp_common.h)
   // contour branch: conv1 A fragments (interior march, round-2 folded, rim GEMM, rim march), bias[8], conv2 taps [5][5][8]
   float *d_d1_wfold = nullptr, *d_d1_wmarch = nullptr, *d_d1_wrim = nullptr, *d_d1_wrimm = nullptr, *d_d1_bias = nullptr,
         *d_d2_w = nullptr, *d_d2_wproj = nullptr;
-  bool fold_mx = false;
   int resample_mode = 0;  // BP_RESAMPLE=plain|tiled: 1 | 2 (A/B runs of the resampling kernels)
-  float* d_d1_wfold_mx = nullptr;
   float* c1s = nullptr;  // [cap][172][kC1Row][8] relu(conv1); pad bins zeroed once at allocation
   // cqt_planes.hip: decimator / filterbank fragments (raw bytes of f16 hi / lo), the planes of a chunk [cap][2][stride] f16
   float *d_pl_tfrag = nullptr, *d_pl_bfrag = nullptr, *planes = nullptr;

@@ -83,9 +83,6 @@ void launch_onset_march16(const uint32_t* zp, const float* note, const void* wfr
 // conv_contour_direct.hip: the round-2 folded conv1 (BP_CONV1=rounds)
 void launch_contour_conv1_folded(const uint32_t* zp, const void* wfold, const float* bias, float* c1, int n_windows,
                                  int n_cu, bool weights_have_lo, hipStream_t stream);
-// conv_contour_fold_mx.hip: the fp8-correction mode's contour conv1
-void launch_contour_conv1_fold_mx(const uint32_t* zp, const void* a16, const void* amx, const void* ascale,
-                                  const float* bias, float* c1, int n_windows, int n_cu, hipStream_t stream);
 // conv_contour2.hip: the round-2 vector kernel (BP_CONV2=valu)
 void launch_contour_conv2(const float* c1, const float* w2, float bias, float* contour, int n_windows, int n_cu,
                           hipStream_t stream);
@@ -94,9 +91,9 @@ void launch_note_march(const float* contour, const void* wfrag, const float* wf3
                        bool weights_have_lo, hipStream_t stream);
 void launch_onset_march(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, float* onset,
                         int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
-// conv_branch.hip: the workgroup onset kernel (BP_ONSET=ring, and the fp8-correction mode)
-void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* wmx,
-                         float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
+// conv_branch.hip: the workgroup onset kernel (BP_ONSET=ring)
+void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, float* onset,
+                         int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
 #endif
 
 // audio_ingest.hip

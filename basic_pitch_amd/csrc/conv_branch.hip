@@ -1,7 +1,7 @@
-// Fused onset branch, workgroup form — the kernel of the fp8-correction mode (BP_FLAG_FP8_CORRECTIONS) and the A/B reference
-// of the default wave-private march (onset_march.hip, round 3; BP_ONSET=ring selects this one); also home of zpack_kernel.
+// Fused onset branch, workgroup form — the A/B reference of the wave-private marches (onset_march16.hip, the default, and
+// onset_march.hip; BP_ONSET=ring selects this one, A/B library only); also home of zpack_kernel, which the product uses.
 // (The note branch, which shared this skeleton in round 1, lives in note_march.hip since round 2; its workgroup kernel was
-// retired in round 3.)
+// retired in round 3.  The fp8-correction variant of this kernel was retired in round 6.)
 //
 //   onset branch (basic_pitch/models.py:295-318): Conv2D 8->32, 5x5, strides (1,3), "same", folded BN,
 //                ReLU on the harmonic stack (nn.py:69-88), Concatenate([note, features]) (305),
@@ -14,10 +14,9 @@
 //   1. conv1 runs as an implicit GEMM in TRANSPOSED form on v_mfma_f32_32x32x16_f16:
 //          C1[channel (32 rows)][pixel (32 cols)] = W1[channel][k] x patch[k][pixel]
 //      A = weights (resident in VGPRs for the whole kernel), B = one ds_read_b128 per lane from an LDS
-//      "image" whose 16-byte slots hold the 8 k-values a lane needs (note: 8 adjacent contour bins of one
-//      frame; onset: the 8 harmonic-stack channels of one bin).  Operands are split x = hi + lo (two
-//      f16, lo stored * 2^11 — bp_common.h), products hi*hi + (lo*hi + hi*lo) * 2^-11 accumulate in fp32:
-//      fp32-class accuracy at the f16 matrix rate.
+//      "image" whose 16-byte slots hold the 8 k-values a lane needs (the 8 harmonic-stack channels of one
+//      bin).  Operands are split x = hi + lo (two f16, lo stored * 2^11 — bp_common.h), products
+//      hi*hi + (lo*hi + hi*lo) * 2^-11 accumulate in fp32: fp32-class accuracy at the f16 matrix rate.
 //   2. The C layout of a 32x32 MFMA (col = lane & 31, row = (r&3) + 8(r>>2) + 4(lane>>5)) is, up to a
 //      permutation of K that is folded into the packed conv2 weights, exactly the B-operand layout of the
 //      next MFMA.  So bias + ReLU + hi/lo split happen in registers and feed the "tap projection"
@@ -31,9 +30,8 @@
 //      image and for Q: no halo recompute inside a chunk (two chunks per window -> 512 work items at
 //      B = 256; 2 workgroups per CU overlap one's staging with the other's MFMAs).
 //
-// Roofline: bound = f16 MFMA issue.  Algorithmic work per window: note 47.5 + 20.3 MFLOP, onset
-// 193.7 + 9.0 MFLOP.  HBM bytes per window: note 181,632 read + 60,544
-// written; onset 214,656 (zp) + 60,544 (note) read + 60,544 written.
+// Roofline: bound = f16 MFMA issue.  Algorithmic work per window: 193.7 + 9.0 MFLOP.
+// HBM bytes per window: 214,656 (zp) + 60,544 (note) read + 60,544 written.
 #include <stdlib.h>
 
 #include "bp_kernels.h"
@@ -47,7 +45,7 @@ __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
   lo = (_Float16)((v - (float)hi) * kLoScale);
 }
 
-#ifdef BP_AB_KERNELS  // the workgroup branch kernel (BP_ONSET=ring) and its fp8-correction variant (BP_FLAG_FP8_CORRECTIONS): A/B library only since round 6
+#ifdef BP_AB_KERNELS  // the workgroup branch kernel (BP_ONSET=ring): A/B library only since round 6
 constexpr int kBrThreads = 256;
 constexpr int kBrRows = 4;                               // conv1 rows per phase
 constexpr int kBrTilesPerRow = 3;                        // 32-pixel tiles, 30 inner pixels each
@@ -55,17 +53,15 @@ static_assert(kBrTilesPerRow * 30 >= kFreqN, "tiles cover a row");
 
 struct BranchParams {
   const uint4* wfrag;  // [A1 hi: KS1*64][A1 lo: KS1*64][A2 hi: 2*64][A2 lo: 2*64] x (8 x f16)
-  const float* wf32;   // bias1[32], extra[9] (onset: taps of the note channel), bias2
-  const void* src;     // note: contour f32 [n][172][264]; onset: zp u32 [n][kZRowsP][kZRow] (padded, bp_common.h)
-  const float* note;   // onset only: note posteriorgram [n][172][88]
+  const float* wf32;   // bias1[32], extra[9] (taps of the note channel), bias2
+  const void* src;     // zp u32 [n][kZRowsP][kZRow] (padded, bp_common.h)
+  const float* note;   // note posteriorgram [n][172][88]
   float* out;          // [n][172][88]
   int n_windows;
-  const uint4* wmx;    // MX kernels: [kMxSteps][64 lanes][2] x 16 bytes of fp8 conv1 corrections, then [64] E8M0 scales
 };
 
-// ---- branch descriptions ----------------------------------------------------------------------
+// ---- the onset branch's geometry ---------------------------------------------------------------
 struct OnsetBr {
-  static constexpr bool kOnset = true;
   static constexpr int KS1 = 13;            // conv1 k-steps: (tap pair of the 5x5 window) x 8 channels
   static constexpr int PH1 = 2;             // ONNX pads [2,1,2,1]
   static constexpr int ND = 6;              // tap 25 (dt = 5, dw = 0) is a zero-weight dummy
@@ -79,95 +75,67 @@ struct OnsetBr {
   static constexpr int RAW_ROW = 101;       // 16-byte units: words 20 .. 423 (bins -36 .. 263 + 101 and the tail)
   static constexpr int RAW_PAD = 0;
   static constexpr int RAW_UNITS = RAW_PAD + kBrRows * RAW_ROW;
-#ifndef BP_ONSET_CHUNKS
-#define BP_ONSET_CHUNKS 2
-#endif
-  static constexpr int CHUNKS = BP_ONSET_CHUNKS;  // time chunks per window (work items = windows x CHUNKS)
+  static constexpr int CHUNKS = 2;          // time chunks per window (work items = windows x CHUNKS)
   static constexpr int WGS = 2;
   static __device__ constexpr int d_of(int s, int h) { return (2 * s + h) / 5; }
   static __device__ constexpr int x_of(int s, int h) { return (2 * s + h) % 5; }
   static __device__ __forceinline__ int lane_slot(int wc) { return 3 * wc; }  // bin 3w+dw-1 -> slot 3w+dw
 };
 
-
-// ---- fp8 planes of the MX variant (the correction products lo_w a + hi_w lo_a of conv1 on
-// v_mfma_scale_f32_32x32x64_f8f6f4, see conv_contour_fold_mx.hip): a slot of the second image then holds
-// [fp8(a 2^6) x 8 channels | fp8(lo_a 2^6) x 8 channels] instead of 8 f16 lo parts — the same 16 bytes.
-using s16x2 = __attribute__((ext_vector_type(2))) short;
-using h16x2 = __attribute__((ext_vector_type(2))) _Float16;
-using i32x8 = __attribute__((ext_vector_type(8))) int;
-constexpr int kMxSA = 6;      // |z| <= 1.61 (BN of a [0, 1] map, checked in bp_create): a 2^6 <= 103 < 448
-constexpr int kMxSteps = 7;   // onset conv1: 28 taps (25 + 3 zero) in steps of 4 taps x 8 channels
-__device__ __forceinline__ uint32_t fp8x4_of_f16x4(uint32_t pair01, uint32_t pair23) {
-  s16x2 r = {0, 0};
-  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(r, __builtin_bit_cast(h16x2, pair01), 1.0f / (float)(1 << kMxSA), false);
-  r = __builtin_amdgcn_cvt_scalef32_pk_fp8_f16(r, __builtin_bit_cast(h16x2, pair23), 1.0f / (float)(1 << kMxSA), true);
-  return __builtin_bit_cast(uint32_t, r);
-}
-// (hi f16 x 8, lo f16 x 8) of a slot -> its fp8 form
-__device__ __forceinline__ uint4 fp8_slot(const uint4 vh, const uint4 vl) {
-  return uint4{fp8x4_of_f16x4(vh.x, vh.y), fp8x4_of_f16x4(vh.z, vh.w), fp8x4_of_f16x4(vl.x, vl.y),
-               fp8x4_of_f16x4(vl.z, vl.w)};
-}
-
 // ---- image staging: `nrows` rows starting at `row_first` (absolute frame index, may be outside the window).
 // Tasks (row, slot) are dealt round-robin to the 256 threads; a thread first ISSUES the loads of all its tasks
 // (NT x 8 in flight), then splits / packs and writes them: the global-load latency is paid once per call, not once
-// per task.  Slots that are zero for every row (onset: the two padding bins of "same") are written by init_rows.
-template <class Br, int NROWS, bool MX = false>
+// per task.  Slots that are zero for every row (the two padding bins of "same") are written by init_rows.
+template <class Br, int NROWS>
 __device__ __forceinline__ void stage_rows(const BranchParams& p, int b, int row_first,
                                            uint4* __restrict__ img_hi, uint4* __restrict__ img_lo, int tid) {
-  constexpr int PER_ROW = Br::kOnset ? kFreqC : Br::SLOTS;       // tasks per row
-  constexpr int NT = (NROWS * PER_ROW + kBrThreads - 1) / kBrThreads;
-  constexpr int ntask = NROWS * PER_ROW;
-  static_assert(Br::kOnset, "the onset branch is the only tenant");
-  {
-    // stack bin f -> slot f + 1; zp is zero outside the CQT and in its pad frames -1 / 172 (bp_common.h): only rows
-    // further outside the window need a guard
-    uint32_t u[NT][8];
-    int dst[NT];
+  constexpr int NT = (NROWS * kFreqC + kBrThreads - 1) / kBrThreads;
+  constexpr int ntask = NROWS * kFreqC;  // tasks (row, stack bin)
+  // stack bin f -> slot f + 1; zp is zero outside the CQT and in its pad frames -1 / 172 (bp_common.h): only rows
+  // further outside the window need a guard
+  uint32_t u[NT][8];
+  int dst[NT];
 #pragma unroll
-    for (int k = 0; k < NT; ++k) {
-      const int e = tid + k * kBrThreads;
-      dst[k] = -1;
-      if (e < ntask) {
-        const int rr = e / PER_ROW, f = e - rr * PER_ROW;
-        const int row = row_first + rr;
-        const bool rvalid = row >= -1 && row <= kFrames;
-        const uint32_t* src = static_cast<const uint32_t*>(p.src) + (int64_t)b * kZWin +
-                              (int64_t)((rvalid ? row : -1) + 1) * kZRow + kZPadL + f;
-        dst[k] = ((row + 64 * Br::RING) % Br::RING) * Br::SLOTS + f + 1;
+  for (int k = 0; k < NT; ++k) {
+    const int e = tid + k * kBrThreads;
+    dst[k] = -1;
+    if (e < ntask) {
+      const int rr = e / kFreqC, f = e - rr * kFreqC;
+      const int row = row_first + rr;
+      const bool rvalid = row >= -1 && row <= kFrames;
+      const uint32_t* src = static_cast<const uint32_t*>(p.src) + (int64_t)b * kZWin +
+                            (int64_t)((rvalid ? row : -1) + 1) * kZRow + kZPadL + f;
+      dst[k] = ((row + 64 * Br::RING) % Br::RING) * Br::SLOTS + f + 1;
 #pragma unroll
-        for (int c = 0; c < 8; ++c) u[k][c] = src[harm_shift(c)];  // row -1 is all zero: also serves rows < -1
-      }
+      for (int c = 0; c < 8; ++c) u[k][c] = src[harm_shift(c)];  // row -1 is all zero: also serves rows < -1
     }
+  }
 #pragma unroll
-    for (int k = 0; k < NT; ++k) {
-      if (dst[k] < 0) continue;
-      uint4 vh, vl;
-      vh.x = (u[k][0] & 0xffffu) | (u[k][1] << 16);
-      vh.y = (u[k][2] & 0xffffu) | (u[k][3] << 16);
-      vh.z = (u[k][4] & 0xffffu) | (u[k][5] << 16);
-      vh.w = (u[k][6] & 0xffffu) | (u[k][7] << 16);
-      vl.x = (u[k][0] >> 16) | (u[k][1] & 0xffff0000u);
-      vl.y = (u[k][2] >> 16) | (u[k][3] & 0xffff0000u);
-      vl.z = (u[k][4] >> 16) | (u[k][5] & 0xffff0000u);
-      vl.w = (u[k][6] >> 16) | (u[k][7] & 0xffff0000u);
-      img_hi[dst[k]] = vh;
-      img_lo[dst[k]] = MX ? fp8_slot(vh, vl) : vl;
-    }
+  for (int k = 0; k < NT; ++k) {
+    if (dst[k] < 0) continue;
+    uint4 vh, vl;
+    vh.x = (u[k][0] & 0xffffu) | (u[k][1] << 16);
+    vh.y = (u[k][2] & 0xffffu) | (u[k][3] << 16);
+    vh.z = (u[k][4] & 0xffffu) | (u[k][5] << 16);
+    vh.w = (u[k][6] & 0xffffu) | (u[k][7] << 16);
+    vl.x = (u[k][0] >> 16) | (u[k][1] & 0xffff0000u);
+    vl.y = (u[k][2] >> 16) | (u[k][3] & 0xffff0000u);
+    vl.z = (u[k][4] >> 16) | (u[k][5] & 0xffff0000u);
+    vl.w = (u[k][6] >> 16) | (u[k][7] & 0xffff0000u);
+    img_hi[dst[k]] = vh;
+    img_lo[dst[k]] = vl;
   }
 }
 
 // `NROWS` rows in pieces of Br::PIECE rows: bounds the registers a staging call holds in flight
-template <class Br, int NROWS, bool MX = false>
+template <class Br, int NROWS>
 __device__ __forceinline__ void stage_block(const BranchParams& p, int b, int row_first, uint4* __restrict__ img_hi,
                                             uint4* __restrict__ img_lo, int tid) {
   constexpr int P = Br::PIECE;
 #pragma unroll
-  for (int r = 0; r + P <= NROWS; r += P) stage_rows<Br, P, MX>(p, b, row_first + r, img_hi, img_lo, tid);
+  for (int r = 0; r + P <= NROWS; r += P) stage_rows<Br, P>(p, b, row_first + r, img_hi, img_lo, tid);
   if constexpr (NROWS % P != 0)
-    stage_rows<Br, NROWS % P, MX>(p, b, row_first + NROWS - NROWS % P, img_hi, img_lo, tid);
+    stage_rows<Br, NROWS % P>(p, b, row_first + NROWS - NROWS % P, img_hi, img_lo, tid);
 }
 
 // ---- steady-state staging: the kBrRows source rows of the NEXT phase come in by LDS-DMA (global_load_lds_dwordx4:
@@ -194,13 +162,10 @@ __device__ __forceinline__ void raw_dma_issue(const BranchParams& p, int b, int 
   // division
   static_assert(kBrRows == kBrThreads / 64, "one row per wave");
   const int row = row_first + wave;  // wave-uniform
-  const float* src;
-  if constexpr (Br::kOnset) {
-    // rows outside [-1, 172] read the all-zero pad row -1 of the padded window (bp_common.h)
-    const bool rvalid = row >= -1 && row <= kFrames;
-    src = reinterpret_cast<const float*>(static_cast<const uint32_t*>(p.src) + (int64_t)b * kZWin +
-                                         (int64_t)((rvalid ? row : -1) + 1) * kZRow + Br::RAW_W0);
-  }
+  // rows outside [-1, 172] read the all-zero pad row -1 of the padded window (bp_common.h)
+  const bool rvalid = row >= -1 && row <= kFrames;
+  const float* src = reinterpret_cast<const float*>(static_cast<const uint32_t*>(p.src) + (int64_t)b * kZWin +
+                                                    (int64_t)((rvalid ? row : -1) + 1) * kZRow + Br::RAW_W0);
   uint4* dst = raw + Br::RAW_PAD + wave * Br::RAW_ROW;
 #pragma unroll
   for (int u0 = 0; u0 < Br::RAW_ROW; u0 += 64) {
@@ -208,7 +173,7 @@ __device__ __forceinline__ void raw_dma_issue(const BranchParams& p, int b, int 
   }
 }
 
-template <class Br, bool MX = false>
+template <class Br>
 __device__ __forceinline__ void raw_convert(int row_first, const uint4* raw_, uint4* __restrict__ img_hi,
                                             uint4* __restrict__ img_lo, int tid) {
   // the DMA's LDS writes are invisible to the optimiser: read behind a memory clobber, at a laundered OFFSET (laundering the
@@ -216,40 +181,34 @@ __device__ __forceinline__ void raw_convert(int row_first, const uint4* raw_, ui
   int zoff = 0;
   asm volatile("" : "+v"(zoff)::"memory");
   const uint4* raw = raw_ + zoff;
-  constexpr int PER_ROW = Br::kOnset ? kFreqC : kFreqN;
-  constexpr int ntask = kBrRows * PER_ROW;
+  constexpr int ntask = kBrRows * kFreqC;
 #pragma unroll 1
   for (int e = tid; e < ntask; e += kBrThreads) {
-    const int rr = e / PER_ROW, f = e - rr * PER_ROW;
+    const int rr = e / kFreqC, f = e - rr * kFreqC;
     const int row = row_first + rr;
-    uint4 vh{0u, 0u, 0u, 0u}, vl{0u, 0u, 0u, 0u};
-    if constexpr (Br::kOnset) {
-      const uint32_t* words = reinterpret_cast<const uint32_t*>(raw + Br::RAW_PAD + rr * Br::RAW_ROW) +
-                              (kZPadL - Br::RAW_W0) + f;
-      uint32_t u[8];
+    const uint32_t* words = reinterpret_cast<const uint32_t*>(raw + Br::RAW_PAD + rr * Br::RAW_ROW) +
+                            (kZPadL - Br::RAW_W0) + f;
+    uint32_t u[8];
 #pragma unroll
-      for (int c = 0; c < 8; ++c) u[c] = words[harm_shift(c)];
-      vh.x = (u[0] & 0xffffu) | (u[1] << 16);
-      vh.y = (u[2] & 0xffffu) | (u[3] << 16);
-      vh.z = (u[4] & 0xffffu) | (u[5] << 16);
-      vh.w = (u[6] & 0xffffu) | (u[7] << 16);
-      vl.x = (u[0] >> 16) | (u[1] & 0xffff0000u);
-      vl.y = (u[2] >> 16) | (u[3] & 0xffff0000u);
-      vl.z = (u[4] >> 16) | (u[5] & 0xffff0000u);
-      vl.w = (u[6] >> 16) | (u[7] & 0xffff0000u);
-      const int dst = ((row + 64 * Br::RING) % Br::RING) * Br::SLOTS + f + 1;
-      img_hi[dst] = vh;
-      img_lo[dst] = MX ? fp8_slot(vh, vl) : vl;
-    }
+    for (int c = 0; c < 8; ++c) u[c] = words[harm_shift(c)];
+    uint4 vh, vl;
+    vh.x = (u[0] & 0xffffu) | (u[1] << 16);
+    vh.y = (u[2] & 0xffffu) | (u[3] << 16);
+    vh.z = (u[4] & 0xffffu) | (u[5] << 16);
+    vh.w = (u[6] & 0xffffu) | (u[7] << 16);
+    vl.x = (u[0] >> 16) | (u[1] & 0xffff0000u);
+    vl.y = (u[2] >> 16) | (u[3] & 0xffff0000u);
+    vl.z = (u[4] >> 16) | (u[5] & 0xffff0000u);
+    vl.w = (u[6] >> 16) | (u[7] & 0xffff0000u);
+    const int dst = ((row + 64 * Br::RING) % Br::RING) * Br::SLOTS + f + 1;
+    img_hi[dst] = vh;
+    img_lo[dst] = vl;
   }
 }
 
 // WLO = false: conv1 weights without a lo part (BP_FLAG_BF16_WEIGHTS): 2 MFMAs per k-step
-// MX = true (onset, WLO): conv1's two correction products on the block-scaled fp8 instruction, everything in ONE
-// accumulator: per tile 13 f16 + 7 fp8 matrix instructions (864 pipe cycles) instead of 39 f16 ones (1248)
-template <class Br, bool WLO, bool MX = false>
+template <class Br, bool WLO>
 __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParams p) {
-  static_assert(!MX || (Br::kOnset && WLO), "the fp8-correction variant exists for the onset branch");
   constexpr int KS1 = Br::KS1, KH2 = Br::KH2, PH1 = Br::PH1, PH2 = Br::PH2;
   __shared__ __attribute__((aligned(16))) uint4 img_hi[Br::RING * Br::SLOTS];
   __shared__ __attribute__((aligned(16))) uint4 img_lo[Br::RING * Br::SLOTS];
@@ -260,21 +219,11 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
   const int h = lane >> 5, li = lane & 31;
 
   // resident A operands (weights) and biases
-  uint4 a1h[KS1], a1l[MX ? 1 : KS1], a2h[2], a2l[2];
-  i32x8 amx[MX ? kMxSteps : 1];
-  int amx_scale = 127;
+  uint4 a1h[KS1], a1l[KS1], a2h[2], a2l[2];
 #pragma unroll
   for (int s = 0; s < KS1; ++s) {
     a1h[s] = p.wfrag[s * 64 + lane];
-    if (!MX) a1l[s] = p.wfrag[(KS1 + s) * 64 + lane];
-  }
-  if constexpr (MX) {
-#pragma unroll
-    for (int S = 0; S < kMxSteps; ++S) {
-      const uint4 m0 = p.wmx[(S * 64 + lane) * 2], m1 = p.wmx[(S * 64 + lane) * 2 + 1];
-      amx[S] = i32x8{(int)m0.x, (int)m0.y, (int)m0.z, (int)m0.w, (int)m1.x, (int)m1.y, (int)m1.z, (int)m1.w};
-    }
-    amx_scale = reinterpret_cast<const int*>(p.wmx + kMxSteps * 64 * 2)[lane];
+    a1l[s] = p.wfrag[(KS1 + s) * 64 + lane];
   }
 #pragma unroll
   for (int s = 0; s < 2; ++s) {
@@ -284,7 +233,7 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
   float bias1[16];
 #pragma unroll
   for (int r = 0; r < 16; ++r) bias1[r] = p.wf32[(r & 3) + 8 * (r >> 2) + 4 * h];
-  // onset: the 3x3 taps of the note channel (concat channel 0) for the frame taps this lane half owns
+  // the 3x3 taps of the note channel (concat channel 0) for the frame taps this lane half owns
   constexpr int DT0 = Br::DT0;
   float extra[DT0][3];
 #pragma unroll
@@ -292,14 +241,14 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
 #pragma unroll
     for (int dw = 0; dw < 3; ++dw) {
       const int dt = DT0 * h + i;
-      extra[i][dw] = (Br::kOnset && dt < KH2) ? p.wf32[32 + dt * 3 + dw] : 0.0f;
+      extra[i][dw] = dt < KH2 ? p.wf32[32 + dt * 3 + dw] : 0.0f;
     }
   const float bias2 = p.wf32[41];
   // every load above has landed before the loops: with loads pending from the preheader the wait-count pass puts a
   // conservative s_waitcnt vmcnt(1) in front of each tile's first MFMA, which also waits for the (untracked) LDS-DMA
   __builtin_amdgcn_s_waitcnt(0x0F70);
 
-  // slots no staging call writes (onset: the two zero bins either side of a row) are zero from here on
+  // slots no staging call writes (the two zero bins either side of a row) are zero from here on
   for (int i = threadIdx.x; i < Br::RING * Br::SLOTS; i += kBrThreads) {
     img_hi[i] = uint4{0u, 0u, 0u, 0u};
     img_lo[i] = uint4{0u, 0u, 0u, 0u};
@@ -314,23 +263,21 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
     const int n_phase = (T1 - T0 + 2 * PH2 + kBrRows - 1) / kBrRows;
 
     __syncthreads();  // previous item finished with the rings
-    stage_block<Br, Br::RING, MX>(p, b, T0 - PH2 - PH1, img_hi, img_lo, threadIdx.x);
-    // onset: the note values (concat channel 0, models.py:305) of this lane's pixels in the phase's three tiles are
+    stage_block<Br, Br::RING>(p, b, T0 - PH2 - PH1, img_hi, img_lo, threadIdx.x);
+    // the note values (concat channel 0, models.py:305) of this lane's pixels in the phase's three tiles are
     // fetched one phase ahead into registers, right in front of a vmcnt(0) wait that exists anyway: no global load is
     // left inside the tile loop (one there makes the compiler wait on vmcnt in front of every tile's MFMAs, and with
     // it on the LDS-DMA in flight).  Unconditional loads from clamped addresses, masked where they are used.
     float note_nx[kBrTilesPerRow] = {0.0f, 0.0f, 0.0f};
     auto fetch_notes = [&](int r_first) {
-      if constexpr (Br::kOnset) {
 #pragma unroll
-        for (int j = 0; j < kBrTilesPerRow; ++j) {
-          const int tile = wave + 4 * j;
-          int row = r_first + tile / kBrTilesPerRow;
-          row = row < 0 ? 0 : (row > kFrames - 1 ? kFrames - 1 : row);
-          int w = (tile % kBrTilesPerRow) * 30 - 1 + li;
-          w = w < 0 ? 0 : (w > kFreqN - 1 ? kFreqN - 1 : w);
-          note_nx[j] = p.note[((int64_t)b * kFrames + row) * kFreqN + w];
-        }
+      for (int j = 0; j < kBrTilesPerRow; ++j) {
+        const int tile = wave + 4 * j;
+        int row = r_first + tile / kBrTilesPerRow;
+        row = row < 0 ? 0 : (row > kFrames - 1 ? kFrames - 1 : row);
+        int w = (tile % kBrTilesPerRow) * 30 - 1 + li;
+        w = w < 0 ? 0 : (w > kFreqN - 1 ? kFreqN - 1 : w);
+        note_nx[j] = p.note[((int64_t)b * kFrames + row) * kFreqN + w];
       }
     };
     fetch_notes(T0 - PH2);
@@ -365,8 +312,7 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
             r = r + 1 == Br::RING ? 0 : r + 1;
           }
           const int lane_off = Br::lane_slot(wc);
-          float note_c = 0.0f;
-          if constexpr (Br::kOnset) note_c = j == 0 ? note_cur[0] : (j == 1 ? note_cur[1] : note_cur[2]);
+          const float note_c = j == 0 ? note_cur[0] : (j == 1 ? note_cur[1] : note_cur[2]);
 
           f32x16 acc, accc;  // the hi x hi chain starts from the bias
 #pragma unroll
@@ -374,89 +320,40 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
             acc[r] = bias1[r];
             accc[r] = 0.0f;
           }
+          // image fragments are read kBrPf k-steps ahead of the MFMAs that consume them (the compiler's own
+          // schedule waits for every read right after issuing it)
+          constexpr int kBrPf = KS1 < 3 ? KS1 : 3;
+          f16x8 bhf[KS1], blf[KS1];
+          auto issue = [&](int s) {
+            const int o0 = rb[Br::d_of(s, 0)] + Br::x_of(s, 0);
+            const int o1 = rb[Br::d_of(s, 1)] + Br::x_of(s, 1);
+            const int slot = lane_off + (h ? o1 : o0);
+            bhf[s] = __builtin_bit_cast(f16x8, img_hi[slot]);
+            blf[s] = __builtin_bit_cast(f16x8, img_lo[slot]);
+          };
+#pragma unroll
+          for (int s = 0; s < kBrPf; ++s) issue(s);
+          __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+          for (int s = 0; s < KS1; ++s) {
+            if (s + kBrPf < KS1) issue(s + kBrPf);
+            __builtin_amdgcn_sched_barrier(0);
+            const f16x8 ah = __builtin_bit_cast(f16x8, a1h[s]);
+            const f16x8 al = __builtin_bit_cast(f16x8, a1l[s]);
+            if (WLO) accc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bhf[s], accc, 0, 0, 0);
+            acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bhf[s], acc, 0, 0, 0);
+            accc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, blf[s], accc, 0, 0, 0);
+            __builtin_amdgcn_sched_barrier(0);
+          }
+          // ReLU, split, and the tap projection (two values per VALU operation where the packed-f32 pipe has one)
           uint32_t b2hw[8], b2lw[8];
-          if constexpr (!MX) {
-            // image fragments are read kBrPf k-steps ahead of the MFMAs that consume them (the compiler's own
-            // schedule waits for every read right after issuing it)
-            constexpr int kBrPf = KS1 < 3 ? KS1 : 3;
-            f16x8 bhf[KS1], blf[KS1];
-            auto issue = [&](int s) {
-              const int o0 = rb[Br::d_of(s, 0)] + Br::x_of(s, 0);
-              const int o1 = rb[Br::d_of(s, 1)] + Br::x_of(s, 1);
-              const int slot = lane_off + (h ? o1 : o0);
-              bhf[s] = __builtin_bit_cast(f16x8, img_hi[slot]);
-              blf[s] = __builtin_bit_cast(f16x8, img_lo[slot]);
-            };
 #pragma unroll
-            for (int s = 0; s < kBrPf; ++s) issue(s);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int s = 0; s < KS1; ++s) {
-              if (s + kBrPf < KS1) issue(s + kBrPf);
-              __builtin_amdgcn_sched_barrier(0);
-              const f16x8 ah = __builtin_bit_cast(f16x8, a1h[s]);
-              const f16x8 al = __builtin_bit_cast(f16x8, a1l[s]);
-              if (WLO) accc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bhf[s], accc, 0, 0, 0);
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bhf[s], acc, 0, 0, 0);
-              accc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, blf[s], accc, 0, 0, 0);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-            // ReLU, split, and the tap projection (two values per VALU operation where the packed-f32 pipe has one)
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              f32x2 v = __builtin_elementwise_fma(f32x2{accc[r], accc[r + 1]}, f32x2{kLoUnscale, kLoUnscale},
-                                                  f32x2{acc[r], acc[r + 1]});
-              v.x = fmaxf(v.x, 0.0f);
-              v.y = fmaxf(v.y, 0.0f);
-              split_f16x2(v, b2hw[r >> 1], b2lw[r >> 1]);
-            }
-          } else {
-            // block S = k-steps 2 S, 2 S + 1 on the f16 instruction (hi x hi) + one block-scaled fp8 instruction for the
-            // corrections of the same four taps: lane half h holds taps 4 S + h (bytes 0..15: fp8(a) | fp8(lo_a) of its 8
-            // channels) and 4 S + 2 + h (bytes 16..31) — the slots its two hi reads use.  One E8M0 scale for both
-            // correction kinds (bp_api.hip pack_onset_mx), so a 32-tap K block may mix them.  Operands one block ahead.
-            constexpr int kBlocks = kMxSteps;
-            constexpr int kPf = 1, kBuf = kPf + 1;  // two blocks ahead: 8 spills at the 256-register budget for 1-2 %
-            f16x8 bhf[kBuf][2];
-            uint4 bmf[kBuf][2];
-            // half i of block S: the f16 hi operand of k-step 2 S + i and the fp8 pair of the same slot.  A wave issues
-            // about one LDS read per 14 cycles in order with everything else, so the reads of block S + 1 go BETWEEN the
-            // (dependent) matrix instructions of block S instead of in front of them
-            auto issue = [&](int S, int i) {
-              const int buf = S % kBuf;
-              const int s = 2 * S + i < KS1 ? 2 * S + i : KS1 - 1;  // block 6 has one k-step: its second half is zero weights
-              const int o0 = rb[Br::d_of(s, 0)] + Br::x_of(s, 0);
-              const int o1 = rb[Br::d_of(s, 1)] + Br::x_of(s, 1);
-              const int slot = lane_off + (h ? o1 : o0);
-              if (2 * S + i < KS1) bhf[buf][i] = __builtin_bit_cast(f16x8, img_hi[slot]);
-              bmf[buf][i] = img_lo[slot];
-            };
-            issue(0, 0);
-            issue(0, 1);
-            __builtin_amdgcn_sched_barrier(0);
-#pragma unroll
-            for (int S = 0; S < kBlocks; ++S) {
-              const int buf = S % kBuf;
-              const bool more = S + 1 < kBlocks;
-              acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a1h[2 * S]), bhf[buf][0], acc, 0, 0, 0);
-              __builtin_amdgcn_sched_barrier(0);
-              if (more) issue(S + 1, 0);
-              __builtin_amdgcn_sched_barrier(0);
-              if (2 * S + 1 < KS1)
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a1h[2 * S + 1 < KS1 ? 2 * S + 1 : 0]),
-                                                             bhf[buf][1], acc, 0, 0, 0);
-              const i32x8 bm = {(int)bmf[buf][0].x, (int)bmf[buf][0].y, (int)bmf[buf][0].z, (int)bmf[buf][0].w,
-                                (int)bmf[buf][1].x, (int)bmf[buf][1].y, (int)bmf[buf][1].z, (int)bmf[buf][1].w};
-              acc = __builtin_amdgcn_mfma_scale_f32_32x32x64_f8f6f4(amx[S], bm, acc, 0, 0, 0, amx_scale, 0, 127 - kMxSA);
-              __builtin_amdgcn_sched_barrier(0);
-              if (more) issue(S + 1, 1);
-              __builtin_amdgcn_sched_barrier(0);
-            }
-#pragma unroll
-            for (int r = 0; r < 16; r += 2) {
-              f32x2 v{relu_f32(acc[r]), relu_f32(acc[r + 1])};
-              split_f16x2(v, b2hw[r >> 1], b2lw[r >> 1]);
-            }
+          for (int r = 0; r < 16; r += 2) {
+            f32x2 v = __builtin_elementwise_fma(f32x2{accc[r], accc[r + 1]}, f32x2{kLoUnscale, kLoUnscale},
+                                                f32x2{acc[r], acc[r + 1]});
+            v.x = fmaxf(v.x, 0.0f);
+            v.y = fmaxf(v.y, 0.0f);
+            split_f16x2(v, b2hw[r >> 1], b2lw[r >> 1]);
           }
           f16x8 b2h[2], b2l[2];
 #pragma unroll
@@ -479,7 +376,7 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
             ppc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, b2l[s], ppc, 0, 0, 0);
           }
           // The packed conv2 weights put tap (dt, dw) in C row r = 3 (dt - DT0 h) + dw of lane half h = (dt >= DT0)
-          // (bp_api.hip pack_branch), so a lane holds all three dw projections of its pixel for its frame taps, and
+          // (weight_pack.hip pack_branch), so a lane holds all three dw projections of its pixel for its frame taps, and
           //   Q[row][dt][w] = (P[dt,0][w-1] + P[dt,1][w]) + P[dt,2][w+1]
           // is two whole-wave lane shifts (DPP wave_shr / wave_shl; the tile's edge pixels li = 0, 31 are halo and take
           // garbage from the other half) - no LDS round trip.  The onset head adds the note channel of the concat.
@@ -491,12 +388,8 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
             return __builtin_bit_cast(float,
                                       __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x130, 0xf, 0xf, true));
           };
-          float n_c = 0.0f, n_l = 0.0f, n_r = 0.0f;
-          if constexpr (Br::kOnset) {
-            n_c = wvalid ? note_c : 0.0f;
-            n_l = from_left(n_c);
-            n_r = from_right(n_c);
-          }
+          const float n_c = wvalid ? note_c : 0.0f;
+          const float n_l = from_left(n_c), n_r = from_right(n_c);
           const bool store_ok = li >= 1 && li <= 30 && w < kFreqN;
 #pragma unroll
           for (int i = 0; i < DT0; ++i) {
@@ -507,7 +400,7 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
             p0 = wvalid ? p0 : 0.0f;
             p2 = wvalid ? p2 : 0.0f;
             float q = (from_left(p0) + p1) + from_right(p2);
-            if constexpr (Br::kOnset) q += (n_l * extra[i][0] + n_c * extra[i][1]) + n_r * extra[i][2];
+            q += (n_l * extra[i][0] + n_c * extra[i][1]) + n_r * extra[i][2];
             const int dt = DT0 * h + i;
             // unconditional store: lanes that must not write (halo pixels, the frame taps half 1 does not own) aim at a
             // scratch slot — an exec-mask branch per store costs more issue slots than the select
@@ -545,7 +438,7 @@ __global__ __launch_bounds__(kBrThreads, Br::WGS) void branch_kernel(BranchParam
           }
         }
       }
-      if (ph + 1 < n_phase) raw_convert<Br, MX>(r0 + kBrRows + PH1, raw, img_hi, img_lo, threadIdx.x);
+      if (ph + 1 < n_phase) raw_convert<Br>(r0 + kBrRows + PH1, raw, img_hi, img_lo, threadIdx.x);
       lds_barrier();
     }
   }
@@ -623,27 +516,15 @@ void launch_zpack_partials(const float* lp, const float* scratch, int n_partials
 }
 
 #ifdef BP_AB_KERNELS
-template <class Br>
-static void launch_branch(const BranchParams& p, int n_cu, bool weights_have_lo, hipStream_t stream) {
-  const int items = p.n_windows * Br::CHUNKS;
-  const int grid = items < Br::WGS * n_cu ? items : Br::WGS * n_cu;
-  if constexpr (Br::kOnset) {
-    if (weights_have_lo && p.wmx) {
-      hipLaunchKernelGGL((branch_kernel<Br, true, true>), dim3(grid), dim3(kBrThreads), 0, stream, p);
-      return;
-    }
-  }
+void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, float* onset,
+                         int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
+  const BranchParams p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows};
+  const int items = n_windows * OnsetBr::CHUNKS;
+  const int grid = items < OnsetBr::WGS * n_cu ? items : OnsetBr::WGS * n_cu;
   if (weights_have_lo)
-    hipLaunchKernelGGL((branch_kernel<Br, true>), dim3(grid), dim3(kBrThreads), 0, stream, p);
+    hipLaunchKernelGGL((branch_kernel<OnsetBr, true>), dim3(grid), dim3(kBrThreads), 0, stream, p);
   else
-    hipLaunchKernelGGL((branch_kernel<Br, false>), dim3(grid), dim3(kBrThreads), 0, stream, p);
-}
-
-// wmx: the fp8 correction fragments (pack_onset_mx) or null for the three-product f16 kernel
-void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, const void* wmx,
-                         float* onset, int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
-  BranchParams p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows, static_cast<const uint4*>(wmx)};
-  launch_branch<OnsetBr>(p, n_cu, weights_have_lo, stream);
+    hipLaunchKernelGGL((branch_kernel<OnsetBr, false>), dim3(grid), dim3(kBrThreads), 0, stream, p);
 }
 #endif  // BP_AB_KERNELS
 

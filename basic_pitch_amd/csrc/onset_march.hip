@@ -1,6 +1,6 @@
 // Onset branch, wave-private march on 32x32x16 (round 3; since round 4 behind BP_ONSET=march32: the default is its
-// 16x16x32 form, onset_march16.hip.  The workgroup kernel of conv_branch.hip stays for the fp8-correction mode and as the
-// A/B reference, BP_ONSET=ring).
+// 16x16x32 form, onset_march16.hip.  The workgroup kernel of conv_branch.hip stays as the A/B reference,
+// BP_ONSET=ring).
 //
 //   basic_pitch/models.py:295-318: Conv2D 8->32, 5x5, strides (1,3), "same", folded BN, ReLU on the harmonic stack
 //   (nn.py:69-88), Concatenate([note, features]) (305), Conv2D 33->1, 3x3, "same", sigmoid -> onset

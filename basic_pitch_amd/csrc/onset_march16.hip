@@ -1,5 +1,5 @@
 // Onset branch, wave-private march on v_mfma_f32_16x16x32_f16 (round 4; the default.  onset_march.hip keeps the
-// 32x32x16 form behind BP_ONSET=march32, conv_branch.hip the workgroup kernel behind BP_ONSET=ring / the fp8 mode).
+// 32x32x16 form behind BP_ONSET=march32, conv_branch.hip the workgroup kernel behind BP_ONSET=ring).
 //
 //   basic_pitch/models.py:295-318: Conv2D 8->32, 5x5, strides (1,3), "same", folded BN, ReLU on the harmonic stack
 //   (nn.py:69-88), Concatenate([note, features]) (305), Conv2D 33->1, 3x3, "same", sigmoid -> onset

@@ -13,7 +13,6 @@ namespace bp {
 struct PackedWeights {
   LogConsts kc{};
   float b_contour2 = 0, b_note2 = 0, b_onset2 = 0;
-  bool fold_mx = false;  // d_d1_wfold_mx holds the fp8-correction conv1 operands (A/B library)
   std::vector<std::pair<float* bp_context::*, std::vector<uint8_t>>> tables;
 };
 

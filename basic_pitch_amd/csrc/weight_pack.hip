@@ -1,4 +1,4 @@
-// The weights blob -> the operand tables of a handle: blob parsing, the f16 / e4m3 conversions and the packing of every
+// The weights blob -> the operand tables of a handle: blob parsing, the f16 conversions and the packing of every
 // kernel's operands, all on the host.  pack_weights is the one entry point (weight_pack.h); bp_create uploads what it
 // returns.  A .hip file because the packers use bp_common.h's __host__ __device__ tap helpers.
 #include <cmath>
@@ -499,115 +499,6 @@ void pack_contour_folded(const Tensor* w1, std::vector<uint16_t>& out) {
       }
 }
 
-// ---- block-scaled fp8 (OCP e4m3fn, as gfx950's v_mfma_scale_f32_*_f8f6f4 reads it) for correction products ----
-// encode v / 2^e to e4m3fn, round to nearest even, saturating at +-448 (no infinities in the format)
-static uint8_t f32_to_e4m3(double v) {
-  const uint8_t sign = v < 0 ? 0x80 : 0;
-  double a = std::fabs(v);
-  if (!(a > 0)) return sign;
-  if (a >= 448.0) return sign | 0x7E;
-  int ex;
-  (void)std::frexp(a, &ex);  // a = m * 2^ex, m in [0.5, 1)
-  int e = ex - 1;             // a = 1.x * 2^e
-  if (e < -6) e = -6;         // subnormal range shares the exponent of the smallest normal
-  const double q = std::nearbyint(a / std::ldexp(1.0, e - 3));  // units of 2^(e-3): 8..15 normal, 0..7 subnormal
-  int m = (int)q;
-  if (m >= 16) {
-    m = 8;
-    ++e;
-  }
-  if (e > 8) return sign | 0x7E;
-  if (m < 8) return sign | (uint8_t)m;  // subnormal (e == -6)
-  return sign | (uint8_t)(((e + 7) << 3) | (m - 8));
-}
-
-// Folded conv1 with fp8 corrections (conv_contour_fold_mx.hip, the default).  The Toeplitz-expanded folded kernel of
-// pack_contour_folded — row i = (j = i >> 3, o = i & 7), tap' = 16 e + 8 kh + el  ->  keff[o][dt][tap' - j - 1] — as
-//   a16     [36 steps][64 lanes][8] f16: the hi part;
-//   mx      [18 steps][64 lanes][32 B]: for the 16 taps tap' = 32 e + 16 kh .. + 15 of step S = 6 dt + e:
-//           bytes 0..15 fp8(lo_w) (K block 0 of the instruction), bytes 16..31 fp8(hi_w) (K block 1); lo_w = w - f16(w);
-//   scales  [64 lanes]: the E8M0 exponent of the block that lane half supplies (kh = 0: lo_w, 1: hi_w), one per row.
-void pack_contour_folded_mx(const Tensor* w1, std::vector<uint16_t>& a16, std::vector<uint8_t>& mx,
-                            std::vector<int32_t>& scales) {
-  static const int shifts[8] = {-36, 0, 36, 57, 72, 84, 93, 101};
-  std::vector<double> keff((size_t)8 * 3 * 176, 0.0);
-  for (int o = 0; o < 8; ++o)
-    for (int c = 0; c < 8; ++c)
-      for (int dt = 0; dt < 3; ++dt)
-        for (int df = 0; df < 39; ++df)
-          keff[((size_t)o * 3 + dt) * 176 + (df - 19 + shifts[c] + 55)] += (double)w1->data[((o * 8 + c) * 3 + dt) * 39 + df];
-  auto tap = [&](int i, int dt, int t) -> float {  // A[i][tap' = t] of frame dt
-    const int j = i >> 3, o = i & 7, g = t - j - 1;
-    return (g >= 0 && g < 176) ? (float)keff[((size_t)o * 3 + dt) * 176 + g] : 0.0f;
-  };
-  a16.assign((size_t)36 * 64 * 8, 0);
-  for (int dt = 0; dt < 3; ++dt)
-    for (int e = 0; e < 12; ++e)
-      for (int lane = 0; lane < 64; ++lane)
-        for (int el = 0; el < 8; ++el)
-          a16[((size_t)(dt * 12 + e) * 64 + lane) * 8 + el] = f32_to_f16(tap(lane & 31, dt, 16 * e + 8 * (lane >> 5) + el));
-  mx.assign((size_t)18 * 64 * 32, 0);
-  // ONE E8M0 scale per accumulator row and K block for all 18 steps (a register instead of 18 in the kernel): e4m3 is a
-  // floating format with 15 binades of normals, taps 2^-15 below the row maximum are noise at the corrections' scale
-  auto block_exp = [](double m) {
-    const int e2 = m > 0 ? (int)std::ceil(std::log2(m / 448.0)) : -126;
-    return e2 < -126 ? -126 : e2;
-  };
-  auto split = [&](int i, int dt, int t, double& h, double& l) {
-    const double v = (double)tap(i, dt, t);
-    h = (double)f16_to_f32(f32_to_f16((float)v)), l = v - h;
-  };
-  std::vector<int32_t> sc(64, 127);
-  for (int i = 0; i < 32; ++i) {
-    double mlo = 0, mhi = 0, h, l;
-    for (int dt = 0; dt < 3; ++dt)
-      for (int t = 0; t < 192; ++t) split(i, dt, t, h, l), mlo = std::fmax(mlo, std::fabs(l)), mhi = std::fmax(mhi, std::fabs(h));
-    const int elo = block_exp(mlo), ehi = block_exp(mhi);
-    sc[i] = 127 + elo;       // lane (i, kh = 0): K block 0 = lo_w
-    sc[32 + i] = 127 + ehi;  // lane (i, kh = 1): K block 1 = hi_w
-    for (int S = 0; S < 18; ++S)
-      for (int kh = 0; kh < 2; ++kh)
-        for (int el = 0; el < 16; ++el) {
-          split(i, S / 6, 32 * (S % 6) + 16 * kh + el, h, l);
-          uint8_t* dst = &mx[((size_t)S * 64 + 32 * kh + i) * 32];
-          dst[el] = f32_to_e4m3(std::ldexp(l, -elo));
-          dst[16 + el] = f32_to_e4m3(std::ldexp(h, -ehi));
-        }
-  }
-  scales = sc;
-}
-
-// Onset conv1 correction products on the block-scaled fp8 instruction (conv_branch.hip, MX variant):
-//   mx [7 steps][64 lanes][32 B] then [64] E8M0 scales.  Lane (i = out channel, kh) of step S: bytes 0..15 = tap
-//   4 S + kh of the 5x5 window, bytes 16..31 = tap 4 S + 2 + kh (taps >= 25: zero); per tap [fp8(lo_w) x 8 channels |
-//   fp8(hi_w) x 8 channels], meeting the image slot's [fp8(a) | fp8(lo_a)].  ONE scale per out channel for both kinds:
-//   lo_w is stored 2^11 larger than hi_w (|lo_w| <= 2^-11 |w|), lo_a arrives 2^11 larger than a, so both products carry
-//   2^(e - 17) and a 32-tap K block may mix them.
-void pack_onset_mx(const Tensor* w1, std::vector<uint8_t>& mx, std::vector<int32_t>& scales) {
-  mx.assign((size_t)7 * 64 * 32, 0);
-  scales.assign(64, 127);
-  for (int i = 0; i < 32; ++i) {
-    double mhi = 0;
-    for (int k = 0; k < 8 * 25; ++k) mhi = std::fmax(mhi, std::fabs((double)f16_to_f32(f32_to_f16(w1->data[i * 200 + k]))));
-    int e = mhi > 0 ? (int)std::ceil(std::log2(mhi / 448.0)) : -100;
-    e = e < -100 ? -100 : e;
-    // products: (A0 2^(e-11)) (a8 2^-6) and (A1 2^e) (lo8 2^-6 2^-11): scale_a = 2^(e-11), scale_b = 2^-6 (kMxSA)
-    scales[i] = scales[32 + i] = 127 + e - 11;
-    for (int S = 0; S < 7; ++S)
-      for (int kh = 0; kh < 2; ++kh)
-        for (int part = 0; part < 2; ++part) {
-          const int q = 4 * S + 2 * part + kh;
-          uint8_t* dst = &mx[((size_t)S * 64 + 32 * kh + i) * 32 + 16 * part];
-          for (int c = 0; c < 8; ++c) {
-            const double v = q < 25 ? (double)w1->data[((i * 8 + c) * 5 + q / 5) * 5 + q % 5] : 0.0;
-            const double hi = (double)f16_to_f32(f32_to_f16((float)v));
-            dst[c] = f32_to_e4m3(std::ldexp(v - hi, -(e - 11)));
-            dst[8 + c] = f32_to_e4m3(std::ldexp(hi, -e));
-          }
-        }
-  }
-}
-
 // Fused branch A fragments (conv_branch.hip): [A1 hi: KS1*64][A1 lo: KS1*64][A2 hi: 2*64][A2 lo: 2*64] x 8 f16.
 // A1 lane (i = out channel = lane & 31, h = lane >> 5), element e: conv1 weight of k = 8h + e of step s.
 // A2 lane (i = projection row, h), element e of step s2: conv2 weight of the channel that C-register
@@ -753,31 +644,12 @@ int pack_weights(const void* weights, size_t nbytes, unsigned flags, PackedWeigh
     pack_contour_rim_march(c1w, frag);
     add(out, &bp_context::d_d1_wrimm, frag);
   }
-#ifdef BP_AB_KERNELS
-  // folded conv1: all three split-precision products on f16 by default (fp32-class); BP_FLAG_FP8_CORRECTIONS opts into
-  // the block-scaled fp8 corrections (conv_contour_fold_mx.hip; ~1e-5 on the contour map), BP_CONV1=f16 then keeps this
-  // one layer on the three-product f16 kernel (A/B runs).
-  // the fp8 planes hold z 2^6 with z = bn_a x + bn_b, x in [0, 1] (NormalizedLog): they must stay below e4m3's 448
-  const bool fp8_ok = std::fmax(std::fabs(out.kc.bn_b), std::fabs(out.kc.bn_a + out.kc.bn_b)) * 64.0f <= 440.0f &&
-                      (flags & BP_FLAG_FP8_CORRECTIONS) && !(flags & BP_FLAG_F16_CORRECTIONS);
-  if (const char* ec = ab_env("BP_CONV1");
-      !(ec && std::strcmp(ec, "f16") == 0) && fp8_ok && !(flags & BP_FLAG_BF16_WEIGHTS)) {
-    std::vector<uint16_t> a16;
-    std::vector<uint8_t> mxf;
-    std::vector<int32_t> mxs;
-    pack_contour_folded_mx(c1w, a16, mxf, mxs);
-    add(out, &bp_context::d_d1_wfold_mx, a16, mxf, mxs);
-    out.fold_mx = true;
-  }
-#else
-  // the reduced-precision fp8-corrections mode left the product library in round 6 (not faster than the default any more,
-  // narrower than the config's fp32): its kernels are built into the A/B library only
+  // the reduced-precision fp8-corrections mode was retired in round 6 (not faster than the default any more, narrower
+  // than the config's fp32); BP_FLAG_F16_CORRECTIONS, the name of today's only arithmetic, wins when both are set
   if ((flags & BP_FLAG_FP8_CORRECTIONS) && !(flags & BP_FLAG_F16_CORRECTIONS)) {
-    err = "bp_create: BP_FLAG_FP8_CORRECTIONS is built into the A/B library only (basic_pitch_amd.build.build_library(ab=True), "
-          "BASIC_PITCH_AMD_LIB); the product library computes all three split-precision products on f16";
+    err = "bp_create: BP_FLAG_FP8_CORRECTIONS was retired in round 6; every split-precision product is computed on f16";
     return BP_ERR_INVALID_ARG;
   }
-#endif
   for (int br = 0; br < 2; ++br) {
     std::vector<float> f32(42, 0.f);
     const Tensor* b1 = br ? o1b : n1b;
@@ -800,15 +672,6 @@ int pack_weights(const void* weights, size_t nbytes, unsigned flags, PackedWeigh
   // the onset march on 16x16x32 (the default): its own fragment order
   pack_onset16(o1w, o2w, frag);
   add(out, &bp_context::d_onset_w16, frag);
-#ifdef BP_AB_KERNELS
-  // onset conv1: fp8 corrections under BP_FLAG_FP8_CORRECTIONS like the folded contour conv1 (BP_ONSET=f16: not this layer)
-  if (const char* eo = ab_env("BP_ONSET"); !(eo && std::strcmp(eo, "f16") == 0) && fp8_ok && !(flags & BP_FLAG_BF16_WEIGHTS)) {
-    std::vector<uint8_t> mxf;
-    std::vector<int32_t> mxs;
-    pack_onset_mx(o1w, mxf, mxs);
-    add(out, &bp_context::d_onset_wmx, mxf, mxs);
-  }
-#endif
 
   std::vector<float> c1f, o1f, n1f;
   pack_contour1(c1w, c1f);

@@ -97,7 +97,7 @@ class Model:
             flags |= _native.BP_FLAG_EXT_CQT_44K
         if f16_corrections:  # the default arithmetic since round 3 (all three split-precision products on f16): a no-op
             flags |= _native.BP_FLAG_F16_CORRECTIONS
-        if fp8_corrections:  # A/B library only since round 6 (the product library refuses the flag: ValueError)
+        if fp8_corrections:  # retired in round 6: bp_create refuses the flag (ValueError)
             flags |= _native.BP_FLAG_FP8_CORRECTIONS
         if blocking_wait:  # whole-track calls sleep on an interrupt instead of spinning (file jobs: workers share cores)
             flags |= _native.BP_FLAG_BLOCKING_WAIT

@@ -92,14 +92,10 @@ typedef enum bp_mem_kind {
                                     * wins over BP_FLAG_FP8_CORRECTIONS when both are set: the pair is accepted): every matrix product of the path
                                     * is hi hi + lo hi + hi lo on the f16 instruction with fp32 accumulation — fp32-class
                                     * results (<= 2^-22 per product), 5e-6 / 5e-7 per stage against the fp32 oracle. */
-#define BP_FLAG_FP8_CORRECTIONS 64u /* NOT IN THE PRODUCT LIBRARY since round 6: bp_create refuses it with BP_ERR_INVALID_ARG
-                                    * (unless BP_FLAG_F16_CORRECTIONS is set too, which wins).  Rounds 2 - 5: an opt-in
-                                    * reduced-precision mode — the two correction products of the folded contour conv1 and
-                                    * of the onset conv1 on the block-scaled fp8 matrix instruction, ~1e-5 / ~3e-5 on the
-                                    * contour / onset map; once the default moved to the register-resident marches it was no
-                                    * faster (345 k against 347 k windows/s, round 5).  Its kernels are compiled into the A/B
-                                    * library only (basic_pitch_amd/build.py: build_library(ab=True)), where the flag works
-                                    * as before (tests/test_gpu_parity.py::test_fp8_corrections_mode_lives_in_the_ab_library). */
+#define BP_FLAG_FP8_CORRECTIONS 64u /* RETIRED: bp_create refuses it with BP_ERR_INVALID_ARG (unless BP_FLAG_F16_CORRECTIONS
+                                    * is set too, which wins).  Rounds 2 - 5 it put the correction products of the contour
+                                    * and onset conv1 on the block-scaled fp8 matrix instruction (~1e-5 / ~3e-5 on those
+                                    * maps); round 6 removed the mode, no faster than the default and narrower than fp32. */
 #define BP_FLAG_BLOCKING_WAIT 128u /* the whole-track calls (bp_infer_track / _tracks / _pcm / _pcm_raw) wait for the device
                                     * asleep on an interrupt instead of spinning on the stream: for file jobs with more worker
                                     * threads than cores (bp_transcribe_files).  Costs tens of microseconds of wake-up

@@ -268,9 +268,13 @@ def test_no_kernel_of_the_product_library_uses_scratch():
                  "contour_conv1_rim_kernel", "contour_conv1_rim_march_kernel", "contour_conv2_proj_kernel", "note_march16_kernel", "onset_march16_kernel", "flac_decode_kernel"):
         assert must in names, must
     # kernels that left the product library (the A/B library carries them): the 32x32x16 marches, the workgroup branch
-    # kernel and the fp8-corrections mode's kernels
+    # kernel and the vector conv2; and the retired fp8-corrections mode's contour kernel, which neither library carries
     for gone in ("note_march_kernel", "branch_kernel", "contour_conv1_fold_mx_kernel", "onset_march_kernel", "contour_conv2_kernel"):
         assert gone + "<" not in names and gone + "(" not in names, gone
+    # the A/B library: the workgroup branch kernel in its two f16 forms (with / without weight lo parts), no fp8 kernel
+    ab_names = [r["name"] for r in kernel_resources(build.build_library(ab=True))]
+    assert sum("branch_kernel<" in n for n in ab_names) == 2, ab_names
+    assert not any("fold_mx" in n for n in ab_names), ab_names
     bad = [(r["name"], r["scratch"], r["vgpr_spill"], r["sgpr_spill"]) for r in rows
            if r["scratch"] or r["vgpr_spill"] or r["sgpr_spill"]]
     assert not bad, bad

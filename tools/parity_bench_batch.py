@@ -1,6 +1,6 @@
 # The benchmark's own batch against the fp64 oracle, window by window (tools/): bench.py's 256 uniform[-1, 1) windows (torch
-# generator, seed 1234, drawn on the device) + 256 normal(0, 0.01) windows through the default path, the opt-in fp8 mode and
-# the exact-f32 A/B path; the fp32 numpy/torch oracle and the C fp32 oracle beside them as two more fp32-class evaluations
+# generator, seed 1234, drawn on the device) + 256 normal(0, 0.01) windows through the default path and the exact-f32 A/B
+# path; the fp32 numpy/torch oracle and the C fp32 oracle beside them as two more fp32-class evaluations
 # of the same graph.   python tools/parity_bench_batch.py [n]  ->  markdown table on stdout
 import os, sys, time
 import numpy as np
@@ -30,8 +30,6 @@ def per_window(p, ref):
     return np.max([np.abs(p[k] - ref[k]).reshape(len(ref[k]), -1).max(1) for k in KEYS], axis=0)
 
 paths = {"default (all-f16 split)": {}, "exact-f32 A/B path": {"exact_f32_mfma": True}}
-if "_ab" in os.environ.get("BASIC_PITCH_AMD_LIB", ""):  # the fp8-corrections mode lives in the A/B library since round 6
-    paths["fp8 corrections (A/B library)"] = {"fp8_corrections": True}
 try:
     O.c_library(); have_c = True
 except OSError:

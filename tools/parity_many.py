@@ -1,5 +1,5 @@
-# Whole-path deviation from the fp64 oracle over MANY noise-like windows (tools/): BP_FLAG_FP8_CORRECTIONS (opt-in since round 3) and
-# the default (all-f16 split products), max per map.  python tools/parity_many.py [n_windows_per_family]
+# Whole-path deviation from the fp64 oracle over MANY noise-like windows (tools/): the default path (all-f16 split products),
+# max per map.  python tools/parity_many.py [n_windows_per_family]
 import os, sys, time
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -9,7 +9,7 @@ from oracle import bp_oracle as O
 from basic_pitch_amd import Model
 n = int(sys.argv[1]) if len(sys.argv) > 1 else 64
 W = O.load_weights()
-a, b = Model(max_windows=256, fp8_corrections=True), Model(max_windows=256)  # fp8 opt-in mode, default (all-f16)
+model = Model(max_windows=256)
 for kind in ("uniform", "normal"):
     x = make_windows(kind, n, 321)
     t0 = time.time()
@@ -27,10 +27,9 @@ for kind in ("uniform", "normal"):
     def per_window(p):
         return np.max([np.abs(p[k] - r64[k]).reshape(n, -1).max(1) for k in r64], axis=0)
     e32 = per_window(r32)
-    pa, pb = a.predict(x), b.predict(x)
+    p = model.predict(x)
     print(kind, n, "windows, oracle %.0f s" % (time.time() - t0))
-    for name, p in (("fp8 corrections", pa), ("f16 corrections", pb)):
-        print("   %-16s" % name, {k: "max %.2e  p99.99 %.2e" % (np.abs(p[k] - r64[k]).max(), np.quantile(np.abs(p[k] - r64[k]), 0.9999)) for k in r64})
-        e = per_window(p)
-        print("   %-16s windows within 1e-4: %d/%d, within max(1e-4, 2 x fp32 oracle): %d/%d, worst ratio to that bound %.2f; fp32 oracle itself within 1e-4: %d/%d (max %.2e)"
-              % ("", (e <= 1e-4).sum(), n, (e <= np.maximum(1e-4, 2 * e32)).sum(), n, (e / np.maximum(1e-4, 2 * e32)).max(), (e32 <= 1e-4).sum(), n, e32.max()))
+    print("   ", {k: "max %.2e  p99.99 %.2e" % (np.abs(p[k] - r64[k]).max(), np.quantile(np.abs(p[k] - r64[k]), 0.9999)) for k in r64})
+    e = per_window(p)
+    print("    windows within 1e-4: %d/%d, within max(1e-4, 2 x fp32 oracle): %d/%d, worst ratio to that bound %.2f; fp32 oracle itself within 1e-4: %d/%d (max %.2e)"
+          % ((e <= 1e-4).sum(), n, (e <= np.maximum(1e-4, 2 * e32)).sum(), n, (e / np.maximum(1e-4, 2 * e32)).max(), (e32 <= 1e-4).sum(), n, e32.max()))

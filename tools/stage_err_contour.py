@@ -1,5 +1,5 @@
 # Stage check (tools/): the contour branch kernels alone against the fp64 oracle, fed with the oracle's own z; per-bin
-# errors at the rims.  On the GPU box: python tools/stage_err_contour.py   (BP_CONV1=f16 for the all-f16 folded kernel)
+# errors at the rims.  On the GPU box: python tools/stage_err_contour.py
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

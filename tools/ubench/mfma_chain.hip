@@ -1,6 +1,7 @@
 // Micro-benchmark (tools/): how fast ONE accumulator chain of [f16 32x32x16, f16 32x32x16, fp8 32x32x64 block-scaled]
 // runs on a SIMD with 1 and 2 waves resident, operands from registers — the matrix-side bound of the folded conv1 block
-// (conv_contour_fold_mx.hip), against the same instructions on independent accumulators.
+// (conv_contour_fold_mx.hip of the fp8-corrections mode, retired in round 6), against the same instructions on
+// independent accumulators.
 #include <hip/hip_runtime.h>
 #include <stdio.h>
 #include <stdlib.h>
