@@ -339,3 +339,57 @@ def test_native_file_reader_direct_io_reads_the_same_bytes(tmp_path):
         finally:
             os.unlink(q)
     print("O_DIRECT used on", tmp_path, ":", used_any)
+
+
+def test_every_kernel_keeps_f16_and_f32_denormals():
+    """The split-f16 operands of the default path carry quiet audio in f16 subnormals: every kernel
+    of both libraries must run with FLOAT_DENORM_MODE_32 and FLOAT_DENORM_MODE_16_64 = 3 (no flushing on input or output),
+    read from COMPUTE_PGM_RSRC1 of each kernel descriptor in the built libraries.  A flag such as
+    -fgpu-flush-denormals-to-zero turns the 32-bit field to 0."""
+    import sys
+
+    from basic_pitch_amd import build
+
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    from kernel_resources import denorm_modes, kernel_resources
+
+    for ab in (False, True):
+        path = build.build_library(ab=ab)
+        modes = denorm_modes(path)
+        assert len(modes) == len(kernel_resources(path)) >= 40, (ab, len(modes))
+        flushing = {k: m for k, m in modes.items() if m != (3, 3)}
+        assert not flushing, (ab, flushing)
+
+
+def test_level_bounds_reject_a_subnormal_flush(weights):
+    """The bounds of tests/test_gpu_levels.py are tight enough to catch the regression they exist for.  On every quiet
+    window (peak <= -60 dBFS, both rates) the split representation emulated with IEEE f16 subnormals, through the fp64
+    oracle, meets the stage bounds (pyramid, magnitude, log-power) and the whole-path QUIET_GATE; with f16 subnormals
+    flushed it breaches at least one of them (measured: the pyramid bound by 13x .. 42x).  Two quiet windows cannot
+    tell the two apart and are held to that: digital silence, and 16-bit dither, whose samples (multiples of 2^-15)
+    the lo half carries exactly when hi is flushed."""
+    import level_windows as L
+
+    exact = []
+    for ext, ws in ((False, L.windows_22k()), (True, L.windows_44k())):
+        ws = [w for w in ws if w[2]]
+        x = np.stack([w for _, w, _ in ws])
+        r64 = O.forward(x.astype(np.float64), weights, np.float64, intermediates=True, ext=ext)
+        emu = {f: O.forward(L.split_emulate(x, f), weights, np.float64, intermediates=True, ext=ext) for f in (False, True)}
+        for i, (name, w, _) in enumerate(ws):
+            pk = float(np.abs(w).max())
+            assert pk <= L.db(-60) * 1.0001, name
+
+            def excess(r):
+                return (L.pyramid_excess([lv[i] for lv in r["levels"][1:]], [lv[i] for lv in r64["levels"][1:]], pk),
+                        L.mag_excess(r["mag"][i], r64["mag"][i]), L.lp_excess(r["lp"][i], r64["lp"][i], r64["mag"][i]),
+                        L.out_err({k: r[k][i] for k in ("note", "onset", "contour")},
+                                  {k: r64[k][i] for k in ("note", "onset", "contour")}) / L.QUIET_GATE)
+
+            ieee, ftz = excess(emu[False]), excess(emu[True])
+            assert max(ieee) <= 0.25, (ext, name, ieee)  # measured: <= 0.07 of QUIET_GATE, <= 0.05 of the stage bounds
+            if np.array_equal(L.split_emulate(w, True), w.astype(np.float64)):
+                exact.append(name)
+                continue
+            assert max(ftz) > 1.0, (ext, name, ftz)
+    assert sorted(exact) == sorted(["silence", "dither +-2 LSB"] * 2), exact
