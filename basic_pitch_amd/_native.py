@@ -25,6 +25,9 @@ BP_FLAG_F16_CORRECTIONS = 32
 BP_FLAG_FP8_CORRECTIONS = 64
 BP_FLAG_BLOCKING_WAIT = 128
 BP_PCM_F32, BP_PCM_S16, BP_PCM_S24, BP_PCM_S32, BP_PCM_U8, BP_PCM_F64 = range(6)
+# the WAV (format tag, bits per sample) each code stands for; a sample is bits // 8 bytes wide
+BP_PCM_WAV = {BP_PCM_U8: (1, 8), BP_PCM_S16: (1, 16), BP_PCM_S24: (1, 24), BP_PCM_S32: (1, 32), BP_PCM_F32: (3, 32),
+              BP_PCM_F64: (3, 64)}
 BP_N_STAGES = 15
 BP_Z_ROW = 448
 BP_Z_ROWS = 174

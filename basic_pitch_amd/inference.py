@@ -55,6 +55,34 @@ def _is_torch_cuda(x: Any) -> bool:
     return type(x).__module__.startswith("torch") and hasattr(x, "is_cuda") and bool(x.is_cuda)
 
 
+# the model's three posteriorgrams and their widths, in the order the native calls take their pointers
+_MAPS = (("note", N_FREQ_BINS_NOTES), ("onset", N_FREQ_BINS_NOTES), ("contour", N_FREQ_BINS_CONTOURS))
+
+# samples two neighbouring windows share / samples from one window's start to the next (inference.py:303-305)
+_OVERLAP_LEN = DEFAULT_OVERLAPPING_FRAMES * FFT_HOP
+_HOP_SIZE = AUDIO_N_SAMPLES - _OVERLAP_LEN
+
+_WAV_PCM = {wav: fmt for fmt, wav in _native.BP_PCM_WAV.items()}  # WAV (format tag, bits) -> BP_PCM_*
+
+
+def _empty_maps(lead: Tuple[int, ...], device: Any = None) -> Dict[str, Any]:
+    """Fresh C-contiguous float32 {"note","onset","contour"} of shape `lead` + (width,): numpy arrays, or torch tensors
+    on `device` when one is given."""
+    if device is None:
+        return {k: np.empty(lead + (w,), dtype=np.float32) for k, w in _MAPS}
+    import torch
+
+    return {k: torch.empty(lead + (w,), dtype=torch.float32, device=device) for k, w in _MAPS}
+
+
+def _ptr(a: Any) -> int:
+    return a.ctypes.data if isinstance(a, np.ndarray) else a.data_ptr()
+
+
+def _mem_kind(a: Any) -> int:
+    return _native.BP_MEM_HOST if isinstance(a, np.ndarray) else _native.BP_MEM_DEVICE
+
+
 class Model:
     """Drop-in for `basic_pitch.inference.Model`: load a serialized model, `predict(x) -> dict`.
 
@@ -86,21 +114,19 @@ class Model:
         self._lib = _native.load_library()
         self._handle = C.c_void_p()
         blob = _weights.load_model_blob(model_path)  # ValueError if unloadable, like inference.py:148-154
-        flags = _native.BP_FLAG_STAGE_TIMING if stage_timing else 0
-        if time_dominant:  # HIP events around the dominant kernel only (2 records per chunk instead of 16)
-            flags |= _native.BP_FLAG_TIME_DOMINANT
-        if exact_f32_mfma:  # A/B reference: contour conv1 on the exact-f32 MFMA kernel
-            flags |= _native.BP_FLAG_F32_MFMA
-        if bf16_weights:  # BASELINE.json configs[3]: conv weights rounded to bf16, 2 matrix instructions per product
-            flags |= _native.BP_FLAG_BF16_WEIGHTS
-        if ext_cqt_44k:  # BASELINE.json configs[4]: 44.1 kHz windows of 87,688 samples, 10-octave / 345-bin CQT
-            flags |= _native.BP_FLAG_EXT_CQT_44K
-        if f16_corrections:  # the default arithmetic since round 3 (all three split-precision products on f16): a no-op
-            flags |= _native.BP_FLAG_F16_CORRECTIONS
-        if fp8_corrections:  # retired in round 6: bp_create refuses the flag (ValueError)
-            flags |= _native.BP_FLAG_FP8_CORRECTIONS
-        if blocking_wait:  # whole-track calls sleep on an interrupt instead of spinning (file jobs: workers share cores)
-            flags |= _native.BP_FLAG_BLOCKING_WAIT
+        flags = 0
+        for on, bit in (
+            (stage_timing, _native.BP_FLAG_STAGE_TIMING),
+            (time_dominant, _native.BP_FLAG_TIME_DOMINANT),  # HIP events around the dominant kernel only (2 records per chunk instead of 16)
+            (exact_f32_mfma, _native.BP_FLAG_F32_MFMA),  # A/B reference: contour conv1 on the exact-f32 MFMA kernel
+            (bf16_weights, _native.BP_FLAG_BF16_WEIGHTS),  # BASELINE.json configs[3]: conv weights rounded to bf16, 2 matrix instructions per product
+            (ext_cqt_44k, _native.BP_FLAG_EXT_CQT_44K),  # BASELINE.json configs[4]: 44.1 kHz windows of 87,688 samples, 10-octave / 345-bin CQT
+            (f16_corrections, _native.BP_FLAG_F16_CORRECTIONS),  # the default arithmetic since round 3 (all three split-precision products on f16): a no-op
+            (fp8_corrections, _native.BP_FLAG_FP8_CORRECTIONS),  # retired in round 6: bp_create refuses the flag (ValueError)
+            (blocking_wait, _native.BP_FLAG_BLOCKING_WAIT),  # whole-track calls sleep on an interrupt instead of spinning (file jobs: workers share cores)
+        ):
+            if on:
+                flags |= bit
         rc = self._lib.bp_create(blob, len(blob), int(device), flags, int(max_windows), C.byref(self._handle))
         if rc != _native.BP_OK:
             self._handle = C.c_void_p()
@@ -129,6 +155,35 @@ class Model:
     def __exit__(self, *exc: Any) -> None:
         self.close()
 
+    # -- native call helpers ----------------------------------------------------------------------
+    def _track_frames(self, n: int) -> int:
+        """Rows of the un-overlapped posteriorgrams of a track of `n` samples at the model's rate."""
+        return int(self._lib.bp_handle_track_n_frames(self._handle, n))
+
+    def _pcm_frames(self, n_frames: int, sample_rate: int) -> int:
+        """The same for `n_frames` of audio at `sample_rate`, resampled to the model's rate first."""
+        return self._track_frames(int(self._lib.bp_handle_resampled_length(self._handle, int(n_frames), int(sample_rate))))
+
+    def _use_torch_stream(self, device: Any) -> None:
+        """Queue this handle's work on torch's current stream of `device`."""
+        import torch
+
+        self._lib.bp_set_stream(self._handle, C.c_void_p(torch.cuda.current_stream(device).cuda_stream))
+
+    def _infer(self, name: str, args: Tuple[Any, ...], out: Any, mem_kind: bool = True) -> None:
+        """Call the library's `name(handle, *args, note, onset, contour[, BP_MEM_*])` and raise what its status maps to.
+        `out`: the three maps, or (bp_infer_tracks) a list of them, passed as three arrays of pointers; whether they are
+        numpy arrays or torch tensors decides the pointers and the memory kind."""
+        if isinstance(out, list):
+            ptrs = [(C.c_void_p * len(out))(*[_ptr(o[k]) for o in out]) for k, _ in _MAPS]
+            first = out[0]["note"]
+        else:
+            ptrs = [_ptr(out[k]) for k, _ in _MAPS]
+            first = out["note"]
+        if mem_kind:
+            ptrs.append(_mem_kind(first))
+        _native.check(self._lib, self._handle, getattr(self._lib, name)(self._handle, *args, *ptrs), name)
+
     # -- inference --------------------------------------------------------------------------------
     def predict(self, x: Any) -> Dict[str, Any]:
         """x: float32 [n, 43844] or [n, 43844, 1] -> {"note","onset","contour"} (inference.py:156-182).
@@ -136,82 +191,65 @@ class Model:
         numpy in -> fresh, writable, C-contiguous numpy arrays out (the reference's consumer mutates
         them, note_creation.py:338-341).  torch CUDA tensor in -> torch CUDA tensors out (zero copy).
         """
-        if _is_torch_cuda(x):
-            return self._predict_device(x)
-        x = np.asarray(x)
-        if x.ndim == 3 and x.shape[2] == 1:
-            x = x[:, :, 0]
-        if x.ndim != 2 or x.shape[1] != self.audio_n_samples:
-            raise ValueError(f"expected input of shape (n, {self.audio_n_samples}[, 1]), got {x.shape}")
-        x = np.ascontiguousarray(x, dtype=np.float32)
-        n = x.shape[0]
-        out = {
-            "note": np.empty((n, ANNOT_N_FRAMES, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "onset": np.empty((n, ANNOT_N_FRAMES, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "contour": np.empty((n, ANNOT_N_FRAMES, N_FREQ_BINS_CONTOURS), dtype=np.float32),
-        }
-        if n:
-            rc = self._lib.bp_infer(
-                self._handle,
-                x.ctypes.data,
-                n,
-                out["note"].ctypes.data,
-                out["onset"].ctypes.data,
-                out["contour"].ctypes.data,
-                _native.BP_MEM_HOST,
-            )
-            _native.check(self._lib, self._handle, rc, "bp_infer")
-        return out
+        return self._predict_device(x)
 
     def _predict_device(self, x: Any, out: Optional[Dict[str, Any]] = None, sync: bool = True) -> Dict[str, Any]:
-        import torch
+        """`predict`; for a CUDA tensor `out` may name the tensors to fill, and `sync=False` returns without waiting for
+        the device."""
+        on_dev = _is_torch_cuda(x)
+        if on_dev:
+            import torch
 
-        if x.dim() == 3 and x.shape[2] == 1:
-            x = x[:, :, 0]
-        if x.dim() != 2 or x.shape[1] != self.audio_n_samples or x.dtype != torch.float32:
-            raise ValueError(f"expected float32 CUDA tensor of shape (n, {self.audio_n_samples}[, 1]), got {tuple(x.shape)}")
-        if x.device.index != self.device:
-            raise ValueError(f"input lives on cuda:{x.device.index}, model on cuda:{self.device}")
-        x = x.contiguous()
+            if x.dim() == 3 and x.shape[2] == 1:
+                x = x[:, :, 0]
+            if x.dim() != 2 or x.shape[1] != self.audio_n_samples or x.dtype != torch.float32:
+                raise ValueError(f"expected float32 CUDA tensor of shape (n, {self.audio_n_samples}[, 1]), got {tuple(x.shape)}")
+            if x.device.index != self.device:
+                raise ValueError(f"input lives on cuda:{x.device.index}, model on cuda:{self.device}")
+            x = x.contiguous()
+        else:
+            x = np.asarray(x)
+            if x.ndim == 3 and x.shape[2] == 1:
+                x = x[:, :, 0]
+            if x.ndim != 2 or x.shape[1] != self.audio_n_samples:
+                raise ValueError(f"expected input of shape (n, {self.audio_n_samples}[, 1]), got {x.shape}")
+            x = np.ascontiguousarray(x, dtype=np.float32)
         n = x.shape[0]
         if out is None:
-            out = {
-                "note": torch.empty((n, ANNOT_N_FRAMES, N_FREQ_BINS_NOTES), dtype=torch.float32, device=x.device),
-                "onset": torch.empty((n, ANNOT_N_FRAMES, N_FREQ_BINS_NOTES), dtype=torch.float32, device=x.device),
-                "contour": torch.empty((n, ANNOT_N_FRAMES, N_FREQ_BINS_CONTOURS), dtype=torch.float32, device=x.device),
-            }
-        if n:
-            self._lib.bp_set_stream(self._handle, C.c_void_p(torch.cuda.current_stream(x.device).cuda_stream))
-            rc = self._lib.bp_infer_async(
-                self._handle, x.data_ptr(), n, out["note"].data_ptr(), out["onset"].data_ptr(), out["contour"].data_ptr()
-            )
-            _native.check(self._lib, self._handle, rc, "bp_infer_async")
+            out = _empty_maps((n, ANNOT_N_FRAMES), x.device if on_dev else None)
+        if n and on_dev:
+            self._use_torch_stream(x.device)
+            self._infer("bp_infer_async", (_ptr(x), n), out, mem_kind=False)
             if sync:
                 _native.check(self._lib, self._handle, self._lib.bp_synchronize(self._handle), "bp_synchronize")
+        elif n:
+            self._infer("bp_infer", (_ptr(x), n), out)
         return out
 
     def predict_track(self, samples: np.ndarray) -> Dict[str, np.ndarray]:
         """Whole mono 22.05 kHz track -> un-overlapped posteriorgrams (inference.py:282-315 on device)."""
-        samples = np.ascontiguousarray(samples, dtype=np.float32)
-        if samples.ndim != 1:
-            raise ValueError("predict_track expects a 1-D mono signal")
-        n = samples.shape[0]
-        T = int(self._lib.bp_handle_track_n_frames(self._handle, n))
-        out = {
-            "note": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "onset": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "contour": np.empty((T, N_FREQ_BINS_CONTOURS), dtype=np.float32),
-        }
-        rc = self._lib.bp_infer_track(
-            self._handle,
-            samples.ctypes.data,
-            n,
-            out["note"].ctypes.data,
-            out["onset"].ctypes.data,
-            out["contour"].ctypes.data,
-            _native.BP_MEM_HOST,
-        )
-        _native.check(self._lib, self._handle, rc, "bp_infer_track")
+        return self._predict_track_device(samples)
+
+    def _predict_track_device(self, samples: "Any", out: Optional[Dict[str, "Any"]] = None) -> Dict[str, "Any"]:
+        """`predict_track`; a device-resident track (1-D float32 CUDA tensor) -> device posteriorgrams (zero copy), into
+        the tensors of `out` when given."""
+        on_dev = _is_torch_cuda(samples)
+        if on_dev:
+            import torch
+
+            if not (samples.dtype == torch.float32 and samples.dim() == 1):
+                raise ValueError("expected a 1-D float32 CUDA tensor")
+            samples = samples.contiguous()
+        else:
+            samples = np.ascontiguousarray(samples, dtype=np.float32)
+            if samples.ndim != 1:
+                raise ValueError("predict_track expects a 1-D mono signal")
+        n = int(samples.shape[0])
+        if out is None:
+            out = _empty_maps((self._track_frames(n),), samples.device if on_dev else None)
+        if on_dev:
+            self._use_torch_stream(samples.device)
+        self._infer("bp_infer_track", (_ptr(samples), n), out)
         return out
 
     def predict_tracks(self, tracks: "List[Any]") -> "List[Dict[str, Any]]":
@@ -227,58 +265,15 @@ class Model:
             tr = [t.contiguous() for t in tracks]
             if any(t.dtype != torch.float32 or t.dim() != 1 for t in tr):
                 raise ValueError("expected 1-D float32 CUDA tensors")
-            lens = [int(t.shape[0]) for t in tr]
-            outs = [
-                {k: torch.empty((int(self._lib.bp_handle_track_n_frames(self._handle, L)), w), dtype=torch.float32, device=tr[0].device)
-                 for k, w in (("note", N_FREQ_BINS_NOTES), ("onset", N_FREQ_BINS_NOTES), ("contour", N_FREQ_BINS_CONTOURS))}
-                for L in lens
-            ]
-            ptr = lambda a: a.data_ptr()  # noqa: E731
-            kind = _native.BP_MEM_DEVICE
-            self._lib.bp_set_stream(self._handle, C.c_void_p(torch.cuda.current_stream(tr[0].device).cuda_stream))
+            self._use_torch_stream(tr[0].device)
         else:
             tr = [np.ascontiguousarray(t, dtype=np.float32) for t in tracks]
             if any(t.ndim != 1 for t in tr):
                 raise ValueError("predict_tracks expects 1-D mono signals")
-            lens = [int(t.shape[0]) for t in tr]
-            outs = [
-                {k: np.empty((int(self._lib.bp_handle_track_n_frames(self._handle, L)), w), dtype=np.float32)
-                 for k, w in (("note", N_FREQ_BINS_NOTES), ("onset", N_FREQ_BINS_NOTES), ("contour", N_FREQ_BINS_CONTOURS))}
-                for L in lens
-            ]
-            ptr = lambda a: a.ctypes.data  # noqa: E731
-            kind = _native.BP_MEM_HOST
-        arr = lambda vals: (C.c_void_p * n)(*[C.c_void_p(v) for v in vals])  # noqa: E731
-        rc = self._lib.bp_infer_tracks(
-            self._handle, n, arr([ptr(t) for t in tr]), (C.c_int64 * n)(*lens),
-            arr([ptr(o["note"]) for o in outs]), arr([ptr(o["onset"]) for o in outs]),
-            arr([ptr(o["contour"]) for o in outs]), kind,
-        )
-        _native.check(self._lib, self._handle, rc, "bp_infer_tracks")
+        lens = [int(t.shape[0]) for t in tr]
+        outs = [_empty_maps((self._track_frames(L),), tr[0].device if on_device else None) for L in lens]
+        self._infer("bp_infer_tracks", (n, (C.c_void_p * n)(*[_ptr(t) for t in tr]), (C.c_int64 * n)(*lens)), outs)
         return outs
-
-    def _predict_track_device(self, samples: "Any", out: Optional[Dict[str, "Any"]] = None) -> Dict[str, "Any"]:
-        """Device-resident mono 22.05 kHz track (1-D float32 CUDA tensor) -> device posteriorgrams (zero copy)."""
-        import torch
-
-        if not (samples.is_cuda and samples.dtype == torch.float32 and samples.dim() == 1):
-            raise ValueError("expected a 1-D float32 CUDA tensor")
-        samples = samples.contiguous()
-        n = int(samples.shape[0])
-        T = int(self._lib.bp_handle_track_n_frames(self._handle, n))
-        if out is None:
-            out = {
-                "note": torch.empty((T, N_FREQ_BINS_NOTES), dtype=torch.float32, device=samples.device),
-                "onset": torch.empty((T, N_FREQ_BINS_NOTES), dtype=torch.float32, device=samples.device),
-                "contour": torch.empty((T, N_FREQ_BINS_CONTOURS), dtype=torch.float32, device=samples.device),
-            }
-        self._lib.bp_set_stream(self._handle, C.c_void_p(torch.cuda.current_stream(samples.device).cuda_stream))
-        rc = self._lib.bp_infer_track(
-            self._handle, samples.data_ptr(), n, out["note"].data_ptr(), out["onset"].data_ptr(),
-            out["contour"].data_ptr(), _native.BP_MEM_DEVICE,
-        )
-        _native.check(self._lib, self._handle, rc, "bp_infer_track")
-        return out
 
     @staticmethod
     def _as_pcm(pcm: np.ndarray) -> np.ndarray:
@@ -308,7 +303,7 @@ class Model:
         <= 0 — decode the maps themselves (`note_creation.model_output_to_notes`).  `prm`: `note_creation._note_params`."""
         on_dev = _is_torch_cuda(output["note"])
         maps = {}
-        for k, w in (("note", N_FREQ_BINS_NOTES), ("onset", N_FREQ_BINS_NOTES), ("contour", N_FREQ_BINS_CONTOURS)):
+        for k, w in _MAPS:
             a = output[k]
             if on_dev:
                 a = a.contiguous().float()
@@ -322,14 +317,13 @@ class Model:
         bits = np.empty((T, 12), np.uint8)
         bend = np.empty((T, N_FREQ_BINS_NOTES), np.int8) if prm.include_pitch_bends else None
         status = C.c_int(0)
-        ptr = (lambda a: a.data_ptr()) if on_dev else (lambda a: a.ctypes.data)
         if on_dev:
             import torch
 
             torch.cuda.current_stream(maps["note"].device).synchronize()
         rc = self._lib.bp_note_candidates(
-            self._handle, ptr(maps["note"]), ptr(maps["onset"]), ptr(maps["contour"]), T, C.byref(prm),
-            _native.BP_MEM_DEVICE if on_dev else _native.BP_MEM_HOST, note.ctypes.data, bits.ctypes.data,
+            self._handle, _ptr(maps["note"]), _ptr(maps["onset"]), _ptr(maps["contour"]), T, C.byref(prm),
+            _mem_kind(maps["note"]), note.ctypes.data, bits.ctypes.data,
             bend.ctypes.data if bend is not None else None, C.byref(status),
         )
         _native.check(self._lib, self._handle, rc, "bp_note_candidates")
@@ -339,18 +333,8 @@ class Model:
         """Decoded PCM at any rate / channel count -> un-overlapped posteriorgrams: downmix, resampling, windowing,
         CQT + CNN and un-overlapping all on the device (bp_infer_pcm)."""
         pcm = self._as_pcm(pcm)
-        n22 = int(self._lib.bp_handle_resampled_length(self._handle, pcm.shape[0], int(sample_rate)))
-        T = int(self._lib.bp_handle_track_n_frames(self._handle, n22))
-        out = {
-            "note": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "onset": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "contour": np.empty((T, N_FREQ_BINS_CONTOURS), dtype=np.float32),
-        }
-        rc = self._lib.bp_infer_pcm(
-            self._handle, pcm.ctypes.data, pcm.shape[0], pcm.shape[1], int(sample_rate),
-            out["note"].ctypes.data, out["onset"].ctypes.data, out["contour"].ctypes.data, _native.BP_MEM_HOST,
-        )
-        _native.check(self._lib, self._handle, rc, "bp_infer_pcm")
+        out = _empty_maps((self._pcm_frames(pcm.shape[0], sample_rate),))
+        self._infer("bp_infer_pcm", (pcm.ctypes.data, pcm.shape[0], pcm.shape[1], int(sample_rate)), out)
         return out
 
     def predict_pcm_raw(self, samples, fmt: int, n_frames: int, channels: int, sample_rate: int) -> Dict[str, np.ndarray]:
@@ -358,22 +342,14 @@ class Model:
         of n_frames * channels of them): they cross PCIe as they are — 16-bit stereo is half the bytes of its float form
         — and become float on the device, bit-identical to converting on the host first (bp_infer_pcm_raw)."""
         buf = np.frombuffer(samples, dtype=np.uint8)
-        width = {_native.BP_PCM_F32: 4, _native.BP_PCM_S16: 2, _native.BP_PCM_S24: 3, _native.BP_PCM_S32: 4,
-                 _native.BP_PCM_U8: 1, _native.BP_PCM_F64: 8}[int(fmt)]
+        width = _native.BP_PCM_WAV[int(fmt)][1] // 8
         if buf.size < int(n_frames) * int(channels) * width:
             raise ValueError("predict_pcm_raw: the buffer is shorter than n_frames * channels samples")
-        n22 = int(self._lib.bp_handle_resampled_length(self._handle, int(n_frames), int(sample_rate)))
-        T = int(self._lib.bp_handle_track_n_frames(self._handle, n22))
-        out = {
-            "note": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "onset": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "contour": np.empty((T, N_FREQ_BINS_CONTOURS), dtype=np.float32),
-        }
-        rc = self._lib.bp_infer_pcm_raw(
-            self._handle, buf.ctypes.data if buf.size else None, int(fmt), int(n_frames), int(channels), int(sample_rate),
-            out["note"].ctypes.data, out["onset"].ctypes.data, out["contour"].ctypes.data, _native.BP_MEM_HOST,
+        out = _empty_maps((self._pcm_frames(n_frames, sample_rate),))
+        self._infer(
+            "bp_infer_pcm_raw",
+            (buf.ctypes.data if buf.size else None, int(fmt), int(n_frames), int(channels), int(sample_rate)), out,
         )
-        _native.check(self._lib, self._handle, rc, "bp_infer_pcm_raw")
         return out
 
     def flac_layout(self, data: bytes) -> Dict[str, int]:
@@ -399,16 +375,8 @@ class Model:
     def predict_flac(self, data: bytes) -> Dict[str, np.ndarray]:
         """The posteriorgrams of a FLAC file's bytes: decode on the device, then what predict_pcm_raw does (bp_infer_flac)."""
         lay = self.flac_layout(data)
-        n22 = int(self._lib.bp_handle_resampled_length(self._handle, lay["n_frames"], lay["sample_rate"]))
-        T = int(self._lib.bp_handle_track_n_frames(self._handle, n22))
-        out = {
-            "note": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "onset": np.empty((T, N_FREQ_BINS_NOTES), dtype=np.float32),
-            "contour": np.empty((T, N_FREQ_BINS_CONTOURS), dtype=np.float32),
-        }
-        rc = self._lib.bp_infer_flac(self._handle, data, len(data), out["note"].ctypes.data, out["onset"].ctypes.data,
-                                     out["contour"].ctypes.data, _native.BP_MEM_HOST)
-        _native.check(self._lib, self._handle, rc, "bp_infer_flac")
+        out = _empty_maps((self._pcm_frames(lay["n_frames"], lay["sample_rate"]),))
+        self._infer("bp_infer_flac", (data, len(data)), out)
         return out
 
     # -- introspection ----------------------------------------------------------------------------
@@ -524,9 +492,10 @@ def run_inference(
     Returns {"note": (T,88), "onset": (T,88), "contour": (T,264)} float32, T = int(L/36164*142).
     """
     model = _model_from(model_or_model_path)
-    n_overlapping_frames = DEFAULT_OVERLAPPING_FRAMES
-    overlap_len = n_overlapping_frames * FFT_HOP
-    hop_size = AUDIO_N_SAMPLES - overlap_len
+
+    def host_decoded():
+        pcm, sr = _audio.read_audio(str(audio_path))
+        return model.predict_pcm(pcm, sr), pcm.shape[0], sr
 
     # decode on the host (container parsing), everything after it on the device: channel-mean downmix, resampling
     # to 22.05 kHz, the 3840-sample lead-in + windowing, CQT + CNN, un-overlapping (inference.py:239-244, 302-315)
@@ -536,10 +505,8 @@ def run_inference(
         # a WAV file's samples go to the device in the file's own format (no float copy on the host, half the PCIe bytes
         # for 16-bit audio); same posteriorgrams, bit for bit, as decoding them here
         raw, tag, bits, channels, file_sr = _audio.wav_raw(str(audio_path))
-        fmt = {(1, 8): _native.BP_PCM_U8, (1, 16): _native.BP_PCM_S16, (1, 24): _native.BP_PCM_S24,
-               (1, 32): _native.BP_PCM_S32, (3, 32): _native.BP_PCM_F32, (3, 64): _native.BP_PCM_F64}[(tag, bits)]
         n_file_frames = len(raw) // (bits // 8) // channels
-        unwrapped_output = model.predict_pcm_raw(raw, fmt, n_file_frames, channels, file_sr)
+        unwrapped_output = model.predict_pcm_raw(raw, _WAV_PCM[(tag, bits)], n_file_frames, channels, file_sr)
     elif head[:4] == b"fLaC" and hasattr(model, "predict_flac"):
         # a FLAC file's BYTES go to the device and are decoded there (csrc/flac_device.hip): half the PCIe bytes of the PCM and
         # no host core-time per sample; what the device decoder leaves to the host (or cannot follow) is decoded here as
@@ -550,16 +517,11 @@ def run_inference(
             lay = model.flac_layout(blob)
             if lay["n_frames"] <= 0:
                 raise _native.NativeLibraryError("no sample count in STREAMINFO")
-            unwrapped_output = model.predict_flac(blob)
-            n_file_frames, file_sr = lay["n_frames"], lay["sample_rate"]
+            unwrapped_output, n_file_frames, file_sr = model.predict_flac(blob), lay["n_frames"], lay["sample_rate"]
         except (ValueError, _native.NativeLibraryError):
-            pcm, file_sr = _audio.read_audio(str(audio_path))
-            n_file_frames = pcm.shape[0]
-            unwrapped_output = model.predict_pcm(pcm, file_sr)
+            unwrapped_output, n_file_frames, file_sr = host_decoded()
     else:
-        pcm, file_sr = _audio.read_audio(str(audio_path))
-        n_file_frames = pcm.shape[0]
-        unwrapped_output = model.predict_pcm(pcm, file_sr)
+        unwrapped_output, n_file_frames, file_sr = host_decoded()
     audio_original_length = int(-(-n_file_frames * AUDIO_SAMPLE_RATE // file_sr))  # librosa.resample: ceil(n * sr / file_sr)
 
     if debug_file:
@@ -567,8 +529,8 @@ def run_inference(
             json.dump(
                 {
                     "audio_original_length": audio_original_length,
-                    "hop_size_samples": hop_size,
-                    "overlap_length_samples": overlap_len,
+                    "hop_size_samples": _HOP_SIZE,
+                    "overlap_length_samples": _OVERLAP_LEN,
                     "unwrapped_output": {k: v.tolist() for k, v in unwrapped_output.items()},
                 },
                 f,
@@ -583,19 +545,16 @@ def run_inference_windowed(
 
     Used by the tests to show that the on-device track path equals the per-window path.
     """
-    n_overlapping_frames = DEFAULT_OVERLAPPING_FRAMES
-    overlap_len = n_overlapping_frames * FFT_HOP
-    hop_size = AUDIO_N_SAMPLES - overlap_len
     windows: List[np.ndarray] = []
     audio_original_length = 0
-    for audio_windowed, _, audio_original_length in get_audio_input(audio_path, overlap_len, hop_size):
+    for audio_windowed, _, audio_original_length in get_audio_input(audio_path, _OVERLAP_LEN, _HOP_SIZE):
         windows.append(audio_windowed[0])
     output: Dict[str, List[np.ndarray]] = {"note": [], "onset": [], "contour": []}
     for i in range(0, len(windows), batch):
         for k, v in model.predict(np.stack(windows[i : i + batch])).items():
             output[k].append(v)
     return {
-        k: unwrap_output(np.concatenate(output[k]), audio_original_length, n_overlapping_frames, hop_size)
+        k: unwrap_output(np.concatenate(output[k]), audio_original_length, DEFAULT_OVERLAPPING_FRAMES, _HOP_SIZE)
         for k in output
     }
 
@@ -621,28 +580,47 @@ def predict_window_range(
     verify_input_path(audio_path)
     pcm, file_sr = _audio.read_audio(str(audio_path))
     y = np.ascontiguousarray(model.resample(pcm, file_sr), dtype=np.float32)
-    n_overlapping_frames = DEFAULT_OVERLAPPING_FRAMES
-    overlap_len = n_overlapping_frames * FFT_HOP
-    hop_size = AUDIO_N_SAMPLES - overlap_len
-    n_olap = n_overlapping_frames // 2
-    padded = np.concatenate([np.zeros((overlap_len // 2,), dtype=np.float32), y])
-    n_windows = len(range(0, padded.shape[0], hop_size))
+    n_olap = DEFAULT_OVERLAPPING_FRAMES // 2
+    padded = np.concatenate([np.zeros((_OVERLAP_LEN // 2,), dtype=np.float32), y])
+    n_windows = len(range(0, padded.shape[0], _HOP_SIZE))
     w0, w1 = split_windows(n_windows, n_pieces)[piece]
-    rows: Dict[str, List[np.ndarray]] = {"note": [], "onset": [], "contour": []}
+    rows: Dict[str, List[np.ndarray]] = {k: [] for k, _ in _MAPS}
     batch = int(getattr(model, "max_windows", 256))
     for a in range(w0, w1, batch):
         b = min(w1, a + batch)
         x = np.zeros((b - a, AUDIO_N_SAMPLES), dtype=np.float32)
         for w in range(a, b):
-            seg = padded[w * hop_size : w * hop_size + AUDIO_N_SAMPLES]
+            seg = padded[w * _HOP_SIZE : w * _HOP_SIZE + AUDIO_N_SAMPLES]
             x[w - a, : len(seg)] = seg
         for k, v in model.predict(x).items():
             if k in rows:
                 v = np.asarray(v)[:, n_olap:-n_olap, :]
                 rows[k].append(v.reshape(v.shape[0] * v.shape[1], v.shape[2]))
-    width = {"note": 88, "onset": 88, "contour": 264}
-    return {"rows": {k: (np.concatenate(v) if v else np.zeros((0, width[k]), np.float32)) for k, v in rows.items()},
+    return {"rows": {k: (np.concatenate(rows[k]) if rows[k] else np.zeros((0, w), np.float32)) for k, w in _MAPS},
             "range": (w0, w1), "n_windows": n_windows, "original_length": int(y.shape[0])}
+
+
+def _min_note_len_frames(minimum_note_length: float) -> int:
+    """A note length in milliseconds as a number of model frames (inference.py:469)."""
+    return int(np.round(minimum_note_length / 1000 * (AUDIO_SAMPLE_RATE / FFT_HOP)))
+
+
+def _output_to_notes(
+    model_output: Dict[str, np.ndarray], onset_threshold: float, frame_threshold: float, minimum_note_length: float,
+    minimum_frequency: Optional[float], maximum_frequency: Optional[float], multiple_pitch_bends: bool, melodia_trick: bool,
+    midi_tempo: float,
+) -> Tuple["infer.pretty_midi.PrettyMIDI", List["infer.NoteEvent"]]:
+    """`note_creation.model_output_to_notes` from the arguments `predict` takes (inference.py:470-480): (midi_data, note_events)."""
+    return infer.model_output_to_notes(
+        model_output, onset_thresh=onset_threshold, frame_thresh=frame_threshold,
+        min_note_len=_min_note_len_frames(minimum_note_length), min_freq=minimum_frequency, max_freq=maximum_frequency,
+        multiple_pitch_bends=multiple_pitch_bends, melodia_trick=melodia_trick, midi_tempo=midi_tempo,
+    )
+
+
+def _output_stem(audio_path: Union[pathlib.Path, str]) -> str:
+    """The `<stem>` of a file's outputs `<stem>_basic_pitch.<ext>` (inference.py:395)."""
+    return os.path.splitext(os.path.basename(str(audio_path)))[0]
 
 
 def assemble_window_ranges(
@@ -668,16 +646,12 @@ def assemble_window_ranges(
         at = p["range"][1]
     if not parts or at != parts[0]["n_windows"]:
         raise ValueError("window ranges do not cover the file")
-    hop_size = AUDIO_N_SAMPLES - DEFAULT_OVERLAPPING_FRAMES * FFT_HOP
-    n_rows = int(parts[0]["original_length"] / hop_size * (AUDIO_WINDOW_LENGTH * ANNOTATIONS_FPS - DEFAULT_OVERLAPPING_FRAMES))
-    model_output = {k: np.ascontiguousarray(np.concatenate([p["rows"][k] for p in parts])[:n_rows]) for k in ("note", "onset", "contour")}
-    min_note_len = int(np.round(minimum_note_length / 1000 * (AUDIO_SAMPLE_RATE / FFT_HOP)))
-    midi_data, note_events = infer.model_output_to_notes(
-        model_output, onset_thresh=onset_threshold, frame_thresh=frame_threshold, min_note_len=min_note_len,
-        min_freq=minimum_frequency, max_freq=maximum_frequency, multiple_pitch_bends=multiple_pitch_bends,
-        melodia_trick=melodia_trick, midi_tempo=midi_tempo,
+    n_rows = int(parts[0]["original_length"] / _HOP_SIZE * (AUDIO_WINDOW_LENGTH * ANNOTATIONS_FPS - DEFAULT_OVERLAPPING_FRAMES))
+    model_output = {k: np.ascontiguousarray(np.concatenate([p["rows"][k] for p in parts])[:n_rows]) for k, _ in _MAPS}
+    return (model_output,) + _output_to_notes(
+        model_output, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency, maximum_frequency,
+        multiple_pitch_bends, melodia_trick, midi_tempo,
     )
-    return model_output, midi_data, note_events
 
 
 class OutputExtensions(enum.Enum):
@@ -703,8 +677,7 @@ def build_output_path(
     audio_path: Union[pathlib.Path, str], output_directory: Union[pathlib.Path, str], output_type: OutputExtensions
 ) -> pathlib.Path:
     """inference.py:374-406: <dir>/<stem>_basic_pitch.<ext>; IOError if it already exists."""
-    basename, _ = os.path.splitext(os.path.basename(str(audio_path)))
-    output_path = pathlib.Path(output_directory) / f"{basename}_basic_pitch.{output_type.value}"
+    output_path = pathlib.Path(output_directory) / f"{_output_stem(audio_path)}_basic_pitch.{output_type.value}"
     if output_path.exists():
         raise IOError(f"{output_path} already exists and would be overwritten. Skipping output files for {audio_path}.")
     return output_path
@@ -737,17 +710,9 @@ def predict(
 ) -> Tuple[Dict[str, np.ndarray], "infer.pretty_midi.PrettyMIDI", List["infer.NoteEvent"]]:
     """Run a single prediction (inference.py:431-506): (model_output, midi_data, note_events)."""
     model_output = run_inference(audio_path, model_or_model_path, debug_file)
-    min_note_len = int(np.round(minimum_note_length / 1000 * (AUDIO_SAMPLE_RATE / FFT_HOP)))
-    midi_data, note_events = infer.model_output_to_notes(
-        model_output,
-        onset_thresh=onset_threshold,
-        frame_thresh=frame_threshold,
-        min_note_len=min_note_len,
-        min_freq=minimum_frequency,
-        max_freq=maximum_frequency,
-        multiple_pitch_bends=multiple_pitch_bends,
-        melodia_trick=melodia_trick,
-        midi_tempo=midi_tempo,
+    midi_data, note_events = _output_to_notes(
+        model_output, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency, maximum_frequency,
+        multiple_pitch_bends, melodia_trick, midi_tempo,
     )
     if debug_file:
         with open(debug_file) as f:
@@ -756,7 +721,7 @@ def predict(
             json.dump(
                 {
                     **debug_data,
-                    "min_note_length": min_note_len,
+                    "min_note_length": _min_note_len_frames(minimum_note_length),
                     "onset_thresh": onset_threshold,
                     "frame_thresh": frame_threshold,
                     "estimated_notes": [
@@ -802,7 +767,6 @@ def predict_many(
     posteriorgrams are dropped as soon as they are written.  The GPU is kept at most two groups ahead of the decoders.
     """
     import concurrent.futures as cf
-    import os
 
     # a path loads the model like the reference does (once per thread: _model_from); a Model — or anything with its
     # resample / predict_tracks — is used
@@ -813,18 +777,12 @@ def predict_many(
     if not return_exceptions:
         for p in paths:
             verify_input_path(p)
-    min_note_len = int(np.round(minimum_note_length / 1000 * (AUDIO_SAMPLE_RATE / FFT_HOP)))
-
-    def decode(model_output: Dict[str, np.ndarray]):
-        midi_data, note_events = infer.model_output_to_notes(
-            model_output, onset_thresh=onset_threshold, frame_thresh=frame_threshold, min_note_len=min_note_len,
-            min_freq=minimum_frequency, max_freq=maximum_frequency, multiple_pitch_bends=multiple_pitch_bends,
-            melodia_trick=melodia_trick, midi_tempo=midi_tempo,
-        )
-        return model_output, midi_data, note_events
 
     def decode_and_finish(i: int, model_output: Dict[str, np.ndarray]):
-        res = decode(model_output)
+        res = (model_output,) + _output_to_notes(
+            model_output, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency, maximum_frequency,
+            multiple_pitch_bends, melodia_trick, midi_tempo,
+        )
         return res if _finish is None else _finish(i, res)
 
     def read(p: pathlib.Path):
@@ -953,12 +911,14 @@ def predict_and_save_many(
     # a duplicate whose earlier namesake FAILED (nothing was written under that stem) is an ordinary file after all
     first_of: Dict[str, int] = {}
     retry: List[int] = []
-    for i in range(len(paths)):
-        stem, _ = os.path.splitext(os.path.basename(str(paths[i])))
+    retried: set = set()  # the stems of `retry`: one retry per stem, its later namesakes stay duplicates
+    for i, p in enumerate(paths):
+        stem = _output_stem(p)
         if i not in dup:
             first_of.setdefault(stem, i)
-        elif isinstance(report[first_of.get(stem, i)], BaseException) and stem not in {os.path.splitext(os.path.basename(str(paths[k])))[0] for k in retry}:
+        elif isinstance(report[first_of.get(stem, i)], BaseException) and stem not in retried:
             retry.append(i)
+            retried.add(stem)
         else:
             report[i] = dup[i]
     for i, r in zip(retry, run(retry) if retry else []):
@@ -1023,11 +983,11 @@ def transcribe_files(
         n = len(paths)
         prm = _native.bp_transcribe_params()
         lib.bp_transcribe_params_default(C.byref(prm))
-        prm.notes.onset_threshold, prm.notes.frame_threshold = float(onset_threshold), float(frame_threshold)
-        prm.notes.min_note_len = int(np.round(minimum_note_length / 1000 * (AUDIO_SAMPLE_RATE / FFT_HOP)))
-        prm.notes.melodia_trick = int(bool(melodia_trick))
-        prm.notes.min_freq_hz = float(minimum_frequency) if minimum_frequency is not None else 0.0
-        prm.notes.max_freq_hz = float(maximum_frequency) if maximum_frequency is not None else 0.0
+        # the decoder settings of model_output_to_notes (infer_onsets, the energy tolerance and pitch bends at its defaults)
+        prm.notes = infer._note_params(
+            onset_threshold, frame_threshold, _min_note_len_frames(minimum_note_length), True, maximum_frequency,
+            minimum_frequency, melodia_trick, infer.ENERGY_TOLERANCE, True,
+        )
         prm.midi_tempo = float(midi_tempo)
         prm.multiple_pitch_bends = int(bool(multiple_pitch_bends))
         prm.save_midi, prm.save_notes, prm.threads = int(bool(save_midi)), int(bool(save_notes)), int(threads)
@@ -1055,7 +1015,7 @@ def duplicate_output_stems(paths: Sequence[Union[pathlib.Path, str]]) -> Dict[in
     seen: Dict[str, int] = {}
     dup: Dict[int, IOError] = {}
     for i, p in enumerate(paths):
-        stem, _ = os.path.splitext(os.path.basename(str(p)))
+        stem = _output_stem(p)
         if stem in seen:
             dup[i] = IOError(f"the outputs of {p} would overwrite those of {paths[seen[stem]]} (same file stem "
                              f"'{stem}'). Skipping output files for {p}.")

@@ -45,6 +45,44 @@ def sonify_midi(midi: "pretty_midi.PrettyMIDI", save_path, sr: Optional[int] = 4
     wavfile.write(save_path, sr, y)
 
 
+def _note_params(onset_thresh, frame_thresh, min_note_len, infer_onsets, max_freq, min_freq, melodia_trick, energy_tol,
+                 include_pitch_bends):
+    prm = _native.bp_note_params()
+    _native.load_library().bp_note_params_default(C.byref(prm))
+    prm.onset_threshold, prm.frame_threshold = float(onset_thresh), float(frame_thresh)
+    prm.min_note_len, prm.energy_tol = int(min_note_len), int(energy_tol)
+    prm.infer_onsets, prm.melodia_trick = int(bool(infer_onsets)), int(bool(melodia_trick))
+    prm.include_pitch_bends = int(bool(include_pitch_bends))
+    prm.min_freq_hz = float(min_freq) if min_freq is not None else 0.0
+    prm.max_freq_hz = float(max_freq) if max_freq is not None else 0.0
+    return prm
+
+
+def _grow_and_call(fn, fixed_args, T: int, what: str):
+    """Call the native decoder `fn(*fixed_args, events, cap_ev, bends, cap_b, &n_ev, &n_b)` with event / bend buffers
+    sized for T frames, again with larger ones when it reports them too small; returns (events, bends, n_events)."""
+    n_ev, n_b = C.c_int64(0), C.c_int64(0)
+    cap_ev, cap_b = max(256, T // 4), max(4096, 4 * T)
+    while True:
+        events = (_native.bp_note_event * cap_ev)()
+        bends = np.empty(cap_b, dtype=np.int32)
+        rc = fn(*fixed_args, C.addressof(events), cap_ev, bends.ctypes.data, cap_b, C.byref(n_ev), C.byref(n_b))
+        if rc == _native.BP_OK:
+            return events, bends, n_ev.value
+        if n_ev.value > cap_ev or n_b.value > cap_b:  # buffers too small: sizes were returned
+            cap_ev, cap_b = max(cap_ev, n_ev.value), max(cap_b, n_b.value)
+            continue
+        raise ValueError(f"{what}: {_native.load_library().bp_notes_last_error().decode(errors='replace')}")
+
+
+def _note_events(events, bends: np.ndarray, n: int, include_pitch_bends: bool) -> List[NoteEvent]:
+    """The first n `bp_note_event` records and the flat bend array they index -> [(start_s, end_s, pitch, amplitude, bends)]."""
+    flat = bends.tolist() if include_pitch_bends else None
+    return [(float(e.start_s), float(e.end_s), int(e.pitch_midi), np.float32(e.amplitude),
+             flat[e.bend_offset : e.bend_offset + e.n_bends] if include_pitch_bends else None)
+            for e in events[:n]]
+
+
 def _decode(
     frames: np.ndarray, onsets: np.ndarray, contours: np.ndarray, onset_thresh: float, frame_thresh: float,
     min_note_len: int, infer_onsets: bool, max_freq: Optional[float], min_freq: Optional[float],
@@ -66,46 +104,15 @@ def _decode(
     T = frames.shape[0]
     if onsets.shape[0] != T or contours.shape[0] != T:
         raise ValueError("note, onset and contour must have the same number of frames")
-    prm = _native.bp_note_params()
-    lib.bp_note_params_default(C.byref(prm))
-    prm.onset_threshold, prm.frame_threshold = float(onset_thresh), float(frame_thresh)
-    prm.min_note_len, prm.energy_tol = int(min_note_len), int(energy_tol)
-    prm.infer_onsets, prm.melodia_trick = int(bool(infer_onsets)), int(bool(melodia_trick))
-    prm.include_pitch_bends = int(bool(include_pitch_bends))
-    prm.min_freq_hz = float(min_freq) if min_freq is not None else 0.0
-    prm.max_freq_hz = float(max_freq) if max_freq is not None else 0.0
-    n_ev, n_b = C.c_int64(0), C.c_int64(0)
-    cap_ev, cap_b = max(256, T // 4), max(4096, 4 * T)
-    while True:
-        events = (_native.bp_note_event * cap_ev)()
-        bends = np.empty(cap_b, dtype=np.int32)
-        rc = lib.bp_notes_decode(
-            frames.ctypes.data, onsets.ctypes.data, contours.ctypes.data, T, C.byref(prm), C.addressof(events),
-            cap_ev, bends.ctypes.data, cap_b, C.byref(n_ev), C.byref(n_b),
-        )
-        if rc == _native.BP_OK:
-            for name, used in (("note", frames), ("onset", onsets)):
-                orig = given[name]
-                if used is not orig and isinstance(orig, np.ndarray) and orig.flags.writeable:
-                    orig[:, ~used.any(axis=0) & orig.any(axis=0)] = 0
-            return events, bends, n_ev.value
-        if n_ev.value > cap_ev or n_b.value > cap_b:  # buffers too small: sizes were returned
-            cap_ev, cap_b = max(cap_ev, n_ev.value), max(cap_b, n_b.value)
-            continue
-        raise ValueError(f"bp_notes_decode: {lib.bp_notes_last_error().decode(errors='replace')}")
-
-
-def _note_params(onset_thresh, frame_thresh, min_note_len, infer_onsets, max_freq, min_freq, melodia_trick, energy_tol,
-                 include_pitch_bends):
-    prm = _native.bp_note_params()
-    _native.load_library().bp_note_params_default(C.byref(prm))
-    prm.onset_threshold, prm.frame_threshold = float(onset_thresh), float(frame_thresh)
-    prm.min_note_len, prm.energy_tol = int(min_note_len), int(energy_tol)
-    prm.infer_onsets, prm.melodia_trick = int(bool(infer_onsets)), int(bool(melodia_trick))
-    prm.include_pitch_bends = int(bool(include_pitch_bends))
-    prm.min_freq_hz = float(min_freq) if min_freq is not None else 0.0
-    prm.max_freq_hz = float(max_freq) if max_freq is not None else 0.0
-    return prm
+    prm = _note_params(onset_thresh, frame_thresh, min_note_len, infer_onsets, max_freq, min_freq, melodia_trick,
+                       energy_tol, include_pitch_bends)
+    decoded = _grow_and_call(lib.bp_notes_decode, (frames.ctypes.data, onsets.ctypes.data, contours.ctypes.data, T, C.byref(prm)),
+                             T, "bp_notes_decode")
+    for name, used in (("note", frames), ("onset", onsets)):
+        orig = given[name]
+        if used is not orig and isinstance(orig, np.ndarray) and orig.flags.writeable:
+            orig[:, ~used.any(axis=0) & orig.any(axis=0)] = 0
+    return decoded
 
 
 def decode_candidates(note: np.ndarray, cand_bits: np.ndarray, bend_map: Optional[np.ndarray], prm) -> List[NoteEvent]:
@@ -122,24 +129,12 @@ def decode_candidates(note: np.ndarray, cand_bits: np.ndarray, bend_map: Optiona
         bend_map = np.require(bend_map, np.int8, ["C"])
         if bend_map.shape != (T, N_FREQ_BINS_NOTES):
             raise ValueError("expected bend_map (T, 88) int8")
-    n_ev, n_b = C.c_int64(0), C.c_int64(0)
-    cap_ev, cap_b = max(256, T // 4), max(4096, 4 * T)
-    while True:
-        events = (_native.bp_note_event * cap_ev)()
-        bends = np.empty(cap_b, dtype=np.int32)
-        rc = lib.bp_notes_decode_candidates(
-            note.ctypes.data, cand_bits.ctypes.data, bend_map.ctypes.data if bend_map is not None else None, T,
-            C.byref(prm), C.addressof(events), cap_ev, bends.ctypes.data, cap_b, C.byref(n_ev), C.byref(n_b),
-        )
-        if rc == _native.BP_OK:
-            with_bends = bool(prm.include_pitch_bends)
-            return [(float(e.start_s), float(e.end_s), int(e.pitch_midi), np.float32(e.amplitude),
-                     bends[e.bend_offset : e.bend_offset + e.n_bends].tolist() if with_bends else None)
-                    for e in events[: n_ev.value]]
-        if n_ev.value > cap_ev or n_b.value > cap_b:
-            cap_ev, cap_b = max(cap_ev, n_ev.value), max(cap_b, n_b.value)
-            continue
-        raise ValueError(f"bp_notes_decode_candidates: {lib.bp_notes_last_error().decode(errors='replace')}")
+    events, bends, n = _grow_and_call(
+        lib.bp_notes_decode_candidates,
+        (note.ctypes.data, cand_bits.ctypes.data, bend_map.ctypes.data if bend_map is not None else None, T, C.byref(prm)),
+        T, "bp_notes_decode_candidates",
+    )
+    return _note_events(events, bends, n, bool(prm.include_pitch_bends))
 
 
 def output_to_notes_polyphonic(
@@ -244,15 +239,5 @@ def model_output_to_notes(
     frames, onsets, contours = output["note"], output["onset"], output["contour"]
     ev, bends, n = _decode(frames, onsets, contours, onset_thresh, frame_thresh, min_note_len, infer_onsets,
                            max_freq, min_freq, melodia_trick, ENERGY_TOLERANCE, include_pitch_bends)
-    events: List[NoteEvent] = []
-    flat_bends = bends.tolist() if (include_pitch_bends and hasattr(bends, "tolist")) else None
-    for i in range(n):
-        e = ev[i]
-        if not include_pitch_bends:
-            b = None
-        elif flat_bends is not None:
-            b = flat_bends[e.bend_offset : e.bend_offset + e.n_bends]
-        else:
-            b = [int(v) for v in bends[e.bend_offset : e.bend_offset + e.n_bends]]
-        events.append((float(e.start_s), float(e.end_s), int(e.pitch_midi), np.float32(e.amplitude), b))
+    events = _note_events(ev, bends, n, include_pitch_bends)
     return note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
