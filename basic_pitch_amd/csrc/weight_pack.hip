@@ -130,7 +130,7 @@ bool pack_filterbank(const Tensor* re, const Tensor* im, std::vector<float>& out
   return true;
 }
 
-// IEEE binary16 <-> binary32 on the host (round to nearest even; inputs here are |x| < 8, no inf/nan)
+// IEEE binary16 <-> binary32 on the host (round to nearest even; overflow gives an infinity, which put_split reports)
 uint16_t f32_to_f16(float f) {
   uint32_t x;
   std::memcpy(&x, &f, 4);
@@ -178,19 +178,22 @@ float f16_to_f32(uint16_t hv) {
   return f;
 }
 
-// x = hi + lo / lo_scale: lo_scale > 1 keeps the residual inside f16's normal range (cqt_mfma.hip)
-void put_split(std::vector<uint16_t>& out, size_t hi_base, size_t lo_base, size_t idx, float v,
+// x = hi + lo / lo_scale: lo_scale > 1 keeps the residual inside f16's normal range (cqt_mfma.hip).  Returns false if
+// the hi part is not a finite f16 (|v| >= 65520, or v not finite): the caller refuses the weights.
+bool put_split(std::vector<uint16_t>& out, size_t hi_base, size_t lo_base, size_t idx, float v,
                float lo_scale = 1.0f) {
   const uint16_t hi = f32_to_f16(v);
   out[hi_base + idx] = hi;
   out[lo_base + idx] = f32_to_f16((v - f16_to_f32(hi)) * lo_scale);
+  return (hi & 0x7c00u) != 0x7c00u;
 }
 
 // The folded kernel (pack_contour_folded) for the vertical march (conv_contour_march.hip): M = 16 rows = (2-bin offset j,
 // out channel o), a position is a pair of bins, K = 6 k-steps of 32 taps per frame tap.  A fragments [3 dt][6 k-steps]
 // [hi|lo][64 lanes] x (8 x f16): lane (row i = 8 j + o = lane & 15, gq = lane >> 4), element el -> tap' = 32 s + 8 gq + el,
 // g = tap' - j - 56.
-void pack_contour_march(const Tensor* w1, std::vector<uint16_t>& out) {
+bool pack_contour_march(const Tensor* w1, std::vector<uint16_t>& out) {
+  bool ok = true;
   static const int shifts[8] = {-36, 0, 36, 57, 72, 84, 93, 101};  // nn.py:51-54 (bp_common.h harm_shift)
   std::vector<double> keff((size_t)8 * 3 * 176, 0.0);               // [o][dt][g + 55]
   for (int o = 0; o < 8; ++o)
@@ -208,9 +211,10 @@ void pack_contour_march(const Tensor* w1, std::vector<uint16_t>& out) {
         for (int el = 0; el < 8; ++el) {
           const int g = 32 * s + 8 * gq + el - j - 56;
           const float v = (g >= -55 && g <= 120) ? (float)keff[((size_t)o * 3 + dt) * 176 + g + 55] : 0.0f;
-          put_split(out, base_hi, base_lo, el, v, 2048.0f);
+          ok &= put_split(out, base_hi, base_lo, el, v, 2048.0f);
         }
       }
+  return ok;
 }
 
 // Rim of the contour conv1 as a dense GEMM (conv_contour_rim.hip): per side (low rim f in [0, 20), high rim
@@ -221,8 +225,9 @@ void pack_contour_march(const Tensor* w1, std::vector<uint16_t>& out) {
 // kh = lane >> 5), element el: j = 16 e + 8 kh + el.
 // `n_bins`: bins of the CQT (309; 345 for the extended 44.1 kHz mode, whose bins 309..344 reach the high rim); `kJ`: z bins a
 // side's window holds (144; 160 for the extended mode: the kernel's RimGeo<160>).
-void pack_contour_rim(const Tensor* w1, std::vector<uint16_t>& out, int n_bins = 309, int kJ = 144) {
+bool pack_contour_rim(const Tensor* w1, std::vector<uint16_t>& out, int n_bins = 309, int kJ = 144) {
   static const int shifts[8] = {-36, 0, 36, 57, 72, 84, 93, 101};
+  bool ok = true;
   const int kStepsDt = kJ / 16;
   out.assign((size_t)2 * 5 * 3 * kStepsDt * 2 * 64 * 8, 0);
   for (int side = 0; side < 2; ++side) {
@@ -253,18 +258,20 @@ void pack_contour_rim(const Tensor* w1, std::vector<uint16_t>& out, int n_bins =
             const size_t base_hi = ((step * 2 + 0) * 64 + lane) * 8, base_lo = ((step * 2 + 1) * 64 + lane) * 8;
             for (int el = 0; el < 8; ++el) {
               const int j = 16 * e + 8 * kh + el;
-              put_split(out, base_hi, base_lo, el, (float)k[(((size_t)fl * 8 + o) * 3 + dt) * kJ + j], 2048.0f);
+              ok &= put_split(out, base_hi, base_lo, el, (float)k[(((size_t)fl * 8 + o) * 3 + dt) * kJ + j], 2048.0f);
             }
           }
   }
+  return ok;
 }
 
 // The same dense per-side matrix for the register-resident rim kernel (conv_contour_rim_march.hip, 309-bin CQT): M blocks of
 // 16 rows = (2 bins x 8 channels), K = (dt, j) flattened = 432 -> 14 k-steps of 32 (zeros behind 432).  A fragments
 // [side][block 10][k-step 14][hi|lo][64 lanes][8]: lane (row i = lane & 15 = 8 (f % 2) + o, g = lane >> 4), element el:
 // k = 32 s + 8 g + el.
-void pack_contour_rim_march(const Tensor* w1, std::vector<uint16_t>& out) {
+bool pack_contour_rim_march(const Tensor* w1, std::vector<uint16_t>& out) {
   static const int shifts[8] = {-36, 0, 36, 57, 72, 84, 93, 101};
+  bool ok = true;
   constexpr int kJ = 144, kSteps = (3 * kJ + 31) / 32, n_bins = 309;
   out.assign((size_t)2 * 10 * kSteps * 2 * 64 * 8, 0);
   for (int side = 0; side < 2; ++side) {
@@ -294,10 +301,11 @@ void pack_contour_rim_march(const Tensor* w1, std::vector<uint16_t>& out) {
           for (int el = 0; el < 8; ++el) {
             const int kk = 32 * s + 8 * g + el;
             const float v = kk < 3 * kJ ? (float)k[(((size_t)fl * 8 + o) * 3 + kk / kJ) * kJ + kk % kJ] : 0.0f;
-            put_split(out, base_hi, base_lo, el, v, 2048.0f);
+            ok &= put_split(out, base_hi, base_lo, el, v, 2048.0f);
           }
         }
   }
+  return ok;
 }
 
 // contour conv1 Toeplitz B fragments [4 waves][126][64] (conv_contour1.hip).
@@ -343,9 +351,11 @@ void pack_note1(const Tensor* w, std::vector<float>& out) {
 // A1: lane (m = lane & 15, g = lane >> 4), element e: out channel 16 mb + m, stack channel e, tap onset16_{dt,dw}(s, g).
 // A2: row rho = lane & 15 = 4 dt + dw (dt, dw < 3), K index 8 g + e <-> conv1 channel 4 g + e (e < 4) or 16 + 4 g + e - 4:
 // the order in which conv1's C layout leaves a pixel's channels in a lane.
-void pack_onset16(const Tensor* w1, const Tensor* w2, std::vector<uint16_t>& out) {
+// Returns 0, or bit 0 / bit 1 set if a weight of w1 / w2 has no finite f16 hi part.
+int pack_onset16(const Tensor* w1, const Tensor* w2, std::vector<uint16_t>& out) {
   const size_t frag = 64 * 8, a1h = 0, a1l = 2 * kOnset16KSteps * frag, a2h = 2 * a1l, a2l = a2h + frag;
   out.assign(a2l + frag, 0);
+  int bad = 0;
   for (int s = 0; s < kOnset16KSteps; ++s)
     for (int mb = 0; mb < 2; ++mb)
       for (int lane = 0; lane < 64; ++lane)
@@ -353,7 +363,7 @@ void pack_onset16(const Tensor* w1, const Tensor* w2, std::vector<uint16_t>& out
           const int m = lane & 15, g = lane >> 4;
           const int q = onset16_dt(s, g) * 5 + onset16_dw(s, g);
           const float v = onset16_live(s, g) ? w1->data[((16 * mb + m) * 8 + e) * 25 + q] : 0.f;
-          put_split(out, a1h, a1l, ((size_t)(2 * s + mb) * 64 + lane) * 8 + e, v, 2048.0f);
+          if (!put_split(out, a1h, a1l, ((size_t)(2 * s + mb) * 64 + lane) * 8 + e, v, 2048.0f)) bad |= 1;
         }
   for (int lane = 0; lane < 64; ++lane)
     for (int e = 0; e < 8; ++e) {
@@ -361,8 +371,9 @@ void pack_onset16(const Tensor* w1, const Tensor* w2, std::vector<uint16_t>& out
       const int dt = rho >> 2, dw = rho & 3;
       const int ch = e < 4 ? 4 * g + e : 16 + 4 * g + (e - 4);
       const float v = (dt < 3 && dw < 3) ? w2->data[((1 + ch) * 3 + dt) * 3 + dw] : 0.f;  // channel 0 of the concat is the note map
-      put_split(out, a2h, a2l, (size_t)lane * 8 + e, v, 2048.0f);
+      if (!put_split(out, a2h, a2l, (size_t)lane * 8 + e, v, 2048.0f)) bad |= 2;
     }
+  return bad;
 }
 
 // conv_contour2.hip contour_conv2_proj_kernel: Conv2D 8 -> 1, 5 x 5 (models.py:254-263; w2 is OIHW (1, 8, 5, 5)) as the A operand
@@ -600,6 +611,18 @@ int pack_weights(const void* weights, size_t nbytes, unsigned flags, PackedWeigh
     };
     to_bf16(c1w), to_bf16(c2w), to_bf16(n1w), to_bf16(n2w), to_bf16(o1w), to_bf16(o2w);
   }
+  // a model is any set of finite numbers: a NaN or an infinity would reach every output of a branch unannounced (after the
+  // bf16 rounding: a finite value next to FLT_MAX rounds to an infinity)
+  for (const auto& nt : {std::make_pair("bn_affine", bn), std::make_pair("contour1_w", c1w), std::make_pair("contour1_b", c1b),
+                         std::make_pair("contour2_w", c2w), std::make_pair("contour2_b", c2b), std::make_pair("note1_w", n1w),
+                         std::make_pair("note1_b", n1b), std::make_pair("note2_w", n2w), std::make_pair("note2_b", n2b),
+                         std::make_pair("onset1_w", o1w), std::make_pair("onset1_b", o1b), std::make_pair("onset2_w", o2w),
+                         std::make_pair("onset2_b", o2b)})
+    for (uint32_t i = 0; i < nt.second->count; ++i)
+      if (!std::isfinite(nt.second->data[i])) {
+        err = std::string("bp_create: ") + nt.first + " holds a NaN or an infinity";
+        return BP_ERR_BAD_WEIGHTS;
+      }
   std::vector<float> fb;
   if (!pack_filterbank(re, im, fb, err)) return BP_ERR_UNSUPPORTED;
   const bool ext = (flags & BP_FLAG_EXT_CQT_44K) != 0;
@@ -633,16 +656,19 @@ int pack_weights(const void* weights, size_t nbytes, unsigned flags, PackedWeigh
   pack_contour_folded(c1w, frag);
   add(out, &bp_context::d_d1_wfold, frag);
 #endif
-  pack_contour_march(c1w, frag);
+  // contour1_w reaches the kernels summed over the harmonic shifts that meet in one z bin (up to 8 taps)
+  bool c1_ok = pack_contour_march(c1w, frag);
   add(out, &bp_context::d_d1_wmarch, frag);
-  if (ext)
-    pack_contour_rim(c1w, frag, kBinsExt, 160);  // the 345-bin CQT: 160 z bins per rim side (conv_contour_rim.hip RimGeo<160>)
-  else
-    pack_contour_rim(c1w, frag);
+  // ext: the 345-bin CQT, 160 z bins per rim side (conv_contour_rim.hip RimGeo<160>)
+  c1_ok &= ext ? pack_contour_rim(c1w, frag, kBinsExt, 160) : pack_contour_rim(c1w, frag);
   add(out, &bp_context::d_d1_wrim, frag);
   if (!ext) {  // the register-resident rim kernel serves the 309-bin CQT
-    pack_contour_rim_march(c1w, frag);
+    c1_ok &= pack_contour_rim_march(c1w, frag);
     add(out, &bp_context::d_d1_wrimm, frag);
+  }
+  if (!c1_ok) {
+    err = "bp_create: contour1_w, folded over the harmonic shifts, is too large for the f16 operand (|w| >= 65520)";
+    return BP_ERR_BAD_WEIGHTS;
   }
   // the reduced-precision fp8-corrections mode was retired in round 6 (not faster than the default any more, narrower
   // than the config's fp32); BP_FLAG_F16_CORRECTIONS, the name of today's only arithmetic, wins when both are set
@@ -670,7 +696,12 @@ int pack_weights(const void* weights, size_t nbytes, unsigned flags, PackedWeigh
   }
   add(out, &bp_context::d_note_w16, frag);
   // the onset march on 16x16x32 (the default): its own fragment order
-  pack_onset16(o1w, o2w, frag);
+  // (onset2_w's taps of concat channel 0, the note map, are an fp32 table: no f16 limit there)
+  if (const int bad = pack_onset16(o1w, o2w, frag)) {
+    err = std::string("bp_create: ") + ((bad & 1) ? "onset1_w" : "onset2_w") +
+          " holds a weight too large for the f16 operand (|w| >= 65520)";
+    return BP_ERR_BAD_WEIGHTS;
+  }
   add(out, &bp_context::d_onset_w16, frag);
 
   std::vector<float> c1f, o1f, n1f;

@@ -1097,7 +1097,21 @@ def test_predict_and_save_sharded_two_workers_on_one_gpu(tmp_path):
         assert open(r["outputs"]["note_events"]).read() == open(out1 / "clip_0_basic_pitch.csv").read()
 
 
-def test_onset_march_equals_workgroup_kernel(tmp_path):
+AB_WEIGHTS = pytest.mark.parametrize("model", ["shipped", "bounded"])
+
+
+def _ab_args(model, tmp_path):
+    """extra arguments of an A/B tool: none for the shipped model, `--weights` with the blob of one bounded family
+    (tests/weight_families.py: every tap far from zero, a negative bn_affine scale) otherwise"""
+    if model == "shipped":
+        return []
+    import weight_families as WF
+
+    return ["--weights", WF.blob_path(tmp_path, WF.family(WF.MODE_FAMILY))]
+
+
+@AB_WEIGHTS
+def test_onset_march_equals_workgroup_kernel(tmp_path, model):
     """The three onset kernels are the same operator in different decompositions.  The 32x32x16 march (BP_ONSET=march32,
     onset_march.hip) and the round-2 workgroup kernel (BP_ONSET=ring, conv_branch.hip) use the same k-step
     order: bit-identical maps.  The default since round 4 (onset_march16.hip, 16x16x32 with the weights in registers)
@@ -1111,7 +1125,7 @@ def test_onset_march_equals_workgroup_kernel(tmp_path):
     outs = {}
     for name, env in (("march16", {}), ("march32", {"BP_ONSET": "march32"}), ("ring", {"BP_ONSET": "ring"})):
         out = str(tmp_path / f"{name}.npy")
-        subprocess.run([sys.executable, tool, out], check=True, env=_ab_env(**env), timeout=600)
+        subprocess.run([sys.executable, tool, out] + _ab_args(model, tmp_path), check=True, env=_ab_env(**env), timeout=600)
         outs[name] = np.load(out)
     assert np.isfinite(outs["march16"]).all()
     assert np.array_equal(outs["march32"], outs["ring"])
@@ -1119,7 +1133,8 @@ def test_onset_march_equals_workgroup_kernel(tmp_path):
     assert d <= 2e-6, d
 
 
-def test_contour_march_equals_round_kernel(tmp_path):
+@AB_WEIGHTS
+def test_contour_march_equals_round_kernel(tmp_path, model):
     """The contour conv1 interior as a vertical march on 16x16x32 (conv_contour_march.hip, the default since round 4) and
     as 256-position rounds on 32x32x16 (BP_CONV1=rounds) are the same folded operator: they sum the same 528 products
     per output in another order (32 taps per matrix instruction instead of 16, frame taps interleaved row by row), so
@@ -1132,14 +1147,15 @@ def test_contour_march_equals_round_kernel(tmp_path):
     outs = {}
     for name, env in (("march", {}), ("rounds", {"BP_CONV1": "rounds"})):
         out = str(tmp_path / f"{name}.npy")
-        subprocess.run([sys.executable, tool, out], check=True, env=_ab_env(**env), timeout=600)
+        subprocess.run([sys.executable, tool, out] + _ab_args(model, tmp_path), check=True, env=_ab_env(**env), timeout=600)
         outs[name] = np.load(out)
     assert np.isfinite(outs["march"]).all()
     d = np.abs(outs["march"] - outs["rounds"]).max()
     assert d <= 2e-6, d
 
 
-def test_rim_march_equals_rim_gemm(tmp_path):
+@AB_WEIGHTS
+def test_rim_march_equals_rim_gemm(tmp_path, model):
     """The rim of contour conv1 with the weights resident in registers (conv_contour_rim_march.hip, the default for the
     309-bin CQT since round 5: 16-row blocks on 16x16x32, 14 k-steps of 32, z rows by LDS-DMA) and as the round-3 GEMM
     (conv_contour_rim.hip, BP_RIM=gemm in the A/B library: 32-row blocks on 32x32x16, 27 k-steps of 16) multiply the same
@@ -1152,7 +1168,7 @@ def test_rim_march_equals_rim_gemm(tmp_path):
     outs = {}
     for name, env in (("march", {}), ("gemm", {"BP_RIM": "gemm"})):
         out = str(tmp_path / f"{name}.npy")
-        subprocess.run([sys.executable, tool, out], check=True, env=_ab_env(**env), timeout=600)
+        subprocess.run([sys.executable, tool, out] + _ab_args(model, tmp_path), check=True, env=_ab_env(**env), timeout=600)
         outs[name] = np.load(out)
     assert np.isfinite(outs["march"]).all()
     d = np.abs(outs["march"] - outs["gemm"])
@@ -1160,7 +1176,8 @@ def test_rim_march_equals_rim_gemm(tmp_path):
     assert d[..., 24:240].max() == 0.0  # away from the rim nothing changed
 
 
-def test_conv2_projection_equals_the_vector_kernel(tmp_path):
+@AB_WEIGHTS
+def test_conv2_projection_equals_the_vector_kernel(tmp_path, model):
     """Contour conv2 as a tap projection on the matrix cores (conv_contour2.hip contour_conv2_proj_kernel, the default since
     round 6: per input pixel 25 taps x 8 channels on v_mfma_f32_32x32x8_f16 with split operands, 25 additions per output) and
     the round-2 vector kernel (200 fp32 FMAs per output, BP_CONV2=valu in the A/B library) compute the same sums in another
@@ -1173,14 +1190,15 @@ def test_conv2_projection_equals_the_vector_kernel(tmp_path):
     outs = {}
     for name, env in (("proj", {}), ("valu", {"BP_CONV2": "valu"})):
         out = str(tmp_path / f"{name}.npy")
-        subprocess.run([sys.executable, tool, out], check=True, env=_ab_env(**env), timeout=600)
+        subprocess.run([sys.executable, tool, out] + _ab_args(model, tmp_path), check=True, env=_ab_env(**env), timeout=600)
         outs[name] = np.load(out)
     assert np.isfinite(outs["proj"]).all()
     d = np.abs(outs["proj"] - outs["valu"]).max()
     assert d <= 2e-6, d
 
 
-def test_note_march16_equals_note_march32(tmp_path):
+@AB_WEIGHTS
+def test_note_march16_equals_note_march32(tmp_path, model):
     """The note branch on 16x16x32 (note_march16.hip, the default since round 6: one accumulator at scale 2^11, the
     activations' lo parts from a residual matrix instruction, conv2's vertical sum in lane) and the round-2 march on 32x32x16
     (note_march.hip, BP_NOTE=march32 in the A/B library) evaluate the same split-precision products of the same operands in
@@ -1195,7 +1213,7 @@ def test_note_march16_equals_note_march32(tmp_path):
     outs = {}
     for name, env in (("march16", {}), ("march32", {"BP_NOTE": "march32"})):
         out = str(tmp_path / f"{name}.npy")
-        subprocess.run([sys.executable, tool, out], check=True, env=_ab_env(**env), timeout=600)
+        subprocess.run([sys.executable, tool, out] + _ab_args(model, tmp_path), check=True, env=_ab_env(**env), timeout=600)
         outs[name] = np.load(out)
     assert np.isfinite(outs["march16"]).all()
     d = np.abs(outs["march16"] - outs["march32"]).max()

@@ -10,11 +10,17 @@ if sys.argv[1] == "--cmp":
     d = np.abs(a - b)
     print("max", d.max(), "n>1e-6", int((d > 1e-6).sum()), "of", d.size)
     sys.exit(0)
+# `--weights PATH` anywhere on the command line: the model the handle loads instead of the shipped one
+weights = None
+if "--weights" in sys.argv:
+    i = sys.argv.index("--weights")
+    weights = sys.argv[i + 1]
+    del sys.argv[i : i + 2]
 from stage_harness import StageRunner, zp_pack
 rng = np.random.default_rng(11)
 n = 3
 z = (rng.random((n, 172, 309), dtype=np.float32) * 2.4 - 0.8).astype(np.float32)
-r = StageRunner()
+r = StageRunner(__import__("basic_pitch_amd").Model(weights) if weights else None)
 got = r.run("contour", n, {"zp": zp_pack(z).view(np.int32)}, {"contour": ((n, 172, 264), __import__("torch").float32)})["contour"]
 np.save(sys.argv[1], got)
 print("saved", sys.argv[1], got.shape, float(got.mean()))

@@ -10,13 +10,19 @@ if sys.argv[1] == "--cmp":
     d = np.abs(a - b)
     print("max", d.max(), "n>1e-6", int((d > 1e-6).sum()), "of", d.size)
     sys.exit(0)
+# `--weights PATH` anywhere on the command line: the model the handle loads instead of the shipped one
+weights = None
+if "--weights" in sys.argv:
+    i = sys.argv.index("--weights")
+    weights = sys.argv[i + 1]
+    del sys.argv[i : i + 2]
 from stage_harness import StageRunner
 rng = np.random.default_rng(12)
 n = int(sys.argv[2]) if len(sys.argv) > 2 else 5
 # sigmoid outputs: mostly small, some ridges near 1 (and exact 0 / 1 / tiny values at the map's rim)
 c = rng.random((n, 172, 264), dtype=np.float32) ** 3
 c[0, :3] = 0.0; c[0, -2:] = 1.0; c[1, :, :3] = 1.0; c[1, :, -4:] = 1e-7
-r = StageRunner()
+r = StageRunner(__import__("basic_pitch_amd").Model(weights) if weights else None)
 got = r.run("note", n, {"contour": c}, {"note": ((n, 172, 88), __import__("torch").float32)})["note"]
 np.save(sys.argv[1], got)
 print("saved", sys.argv[1], got.shape, float(got.mean()))

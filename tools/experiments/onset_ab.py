@@ -18,6 +18,12 @@ if sys.argv[1] == "--cmp":
         print("mean |d| by frame (x1e6):", d.mean(axis=(0, 2)) * 1e6)
         print("signed mean:", float((a - b).mean()))
     sys.exit(0)
+# `--weights PATH` anywhere on the command line: the model the handle loads instead of the shipped one
+weights = None
+if "--weights" in sys.argv:
+    i = sys.argv.index("--weights")
+    weights = sys.argv[i + 1]
+    del sys.argv[i : i + 2]
 from stage_harness import StageRunner, zp_pack
 rng = np.random.default_rng(5)
 n = 3
@@ -32,7 +38,7 @@ if "zsmall" in mode:
     z *= 0.01
 if "zzero" in mode:
     z[:] = 0
-r = StageRunner()
+r = StageRunner(__import__("basic_pitch_amd").Model(weights) if weights else None)
 got = r.run("onset", n, {"zp": zp_pack(z).view(np.int32), "note": note}, {"onset": ((n, 172, 88), __import__("torch").float32)})["onset"]
 np.save(sys.argv[1], got)
 print("saved", sys.argv[1], got.shape, float(got.mean()))
