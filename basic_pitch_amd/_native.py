@@ -204,6 +204,14 @@ EXPORTED_SYMBOLS = [
     "bp_wav_info",
     "bp_wav_decode",
     "bp_files_last_error",
+    "bp_stream_open",
+    "bp_stream_push",
+    "bp_stream_finish",
+    "bp_streams_push",
+    "bp_stream_close",
+    "bp_stream_rows_bound",
+    "bp_stream_state_bytes",
+    "bp_stream_rows_after",
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -19,6 +19,7 @@ HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd.h")
 SOURCES = [
     "bp_api.hip",
     "track_api.hip",
+    "stream_api.hip",
     "weight_pack.hip",
     "cqt_pyramid.hip",
     "cqt_filterbank.hip",

@@ -350,4 +350,88 @@ void launch_resample(const float* x, int64_t n_in, const double* taps, const Res
     hipLaunchKernelGGL(resample_poly_kernel, per_output, dim3(256), 0, stream, x, n_in, taps, pl, y, n_out);
 }
 
+// ---- streaming ingest (stream_api.hip): the same two steps on a chunk of a signal that arrives in pieces ------------------
+// A frame's mono value, computed as downmix_raw_kernel computes it.
+template <int FMT>
+__device__ __forceinline__ float mono_frame(const uint8_t* __restrict__ raw, int64_t i, int channels) {
+  if (channels == 1) return pcm_sample<FMT>(raw, i);
+  float s = 0.0f;
+  for (int c = 0; c < channels; ++c) s += pcm_sample<FMT>(raw, i * channels + c);
+  return s / (float)channels;
+}
+
+// Threads [0, n_frames): frame i -> dst[(dst_pos + i) mod dst_cap] (dst_cap 0: dst[i]; n_frames <= dst_cap otherwise).
+// Threads [n_frames, n_frames + n_hist): entry t of the resampler's next input history, the last n_hist mono frames of
+// (hist_old | these frames): from the chunk where it reaches that far back, else from the old history.
+template <int FMT>
+__global__ __launch_bounds__(256) void stream_downmix_kernel(const uint8_t* __restrict__ raw, int64_t n_frames, int channels,
+                                                             float* __restrict__ dst, int dst_pos, int dst_cap,
+                                                             const float* __restrict__ hist_old,
+                                                             float* __restrict__ hist_new, int n_hist) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i < n_frames) {
+    int64_t p = dst_pos + i;
+    if (dst_cap > 0 && p >= dst_cap) p -= dst_cap;
+    dst[p] = mono_frame<FMT>(raw, i, channels);
+  } else if (i < n_frames + n_hist) {
+    const int64_t t = i - n_frames, r = n_frames - n_hist + t;  // r: the frame's index in the chunk
+    hist_new[t] = r >= 0 ? mono_frame<FMT>(raw, r, channels) : hist_old[t + n_frames];
+  }
+}
+
+// resample_poly_kernel at an ABSOLUTE output index: y[k] for k in [k0, k0 + n_k) — the same taps, the same j order, the same
+// float64 accumulator, the same clipping of the sum at n_in — of a signal whose frames [chunk_start - n_hist, chunk_start)
+// are `hist` and whose frames from chunk_start on are `chunk`.  The caller asks only for outputs whose first frame
+// ceil((k down + centre - (n_taps - 1)) / up) lies inside the history (n_hist = ceil(n_taps / up) frames suffice for every
+// output that was not complete before the chunk arrived).  Output k goes to ring[(ring_pos + k - k0) mod ring_cap].
+__global__ __launch_bounds__(256) void stream_resample_kernel(const float* __restrict__ hist, int n_hist,
+                                                              const float* __restrict__ chunk, int64_t chunk_start,
+                                                              int64_t n_in, const double* __restrict__ taps, ResamplePlan pl,
+                                                              int64_t k0, int64_t n_k, float* __restrict__ ring, int ring_pos,
+                                                              int ring_cap) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= n_k) return;
+  const int64_t k = k0 + idx;
+  const int64_t base = k * (int64_t)pl.down + pl.centre;
+  int64_t j_hi = base / pl.up;
+  if (j_hi > n_in - 1) j_hi = n_in - 1;
+  const int64_t lo_num = base - (pl.n_taps - 1);
+  int64_t j_lo = lo_num <= 0 ? 0 : (lo_num + pl.up - 1) / pl.up;
+  if (j_lo < chunk_start - n_hist) j_lo = chunk_start - n_hist;  // never taken for the outputs the caller asks for
+  double acc = 0.0;
+  for (int64_t j = j_lo; j <= j_hi; ++j) {
+    const float x = j >= chunk_start ? chunk[j - chunk_start] : hist[j - (chunk_start - n_hist)];
+    acc += (double)x * taps[base - j * pl.up];
+  }
+  int64_t p = ring_pos + idx;  // n_k <= ring_cap: one wrap at most
+  if (p >= ring_cap) p -= ring_cap;
+  ring[p] = (float)acc;
+}
+
+void launch_stream_downmix(const void* raw, int format, int64_t n_frames, int channels, float* dst, int dst_pos, int dst_cap,
+                           const float* hist_old, float* hist_new, int n_hist, hipStream_t stream) {
+  if (n_frames + n_hist <= 0) return;
+  const dim3 grid((unsigned)((n_frames + n_hist + 255) / 256));
+  const uint8_t* p = static_cast<const uint8_t*>(raw);
+#define BP_STREAM_DOWNMIX(F) \
+  hipLaunchKernelGGL(stream_downmix_kernel<F>, grid, dim3(256), 0, stream, p, n_frames, channels, dst, dst_pos, dst_cap, hist_old, hist_new, n_hist)
+  switch (format) {
+    case BP_PCM_S16: BP_STREAM_DOWNMIX(BP_PCM_S16); break;
+    case BP_PCM_S24: BP_STREAM_DOWNMIX(BP_PCM_S24); break;
+    case BP_PCM_S32: BP_STREAM_DOWNMIX(BP_PCM_S32); break;
+    case BP_PCM_U8: BP_STREAM_DOWNMIX(BP_PCM_U8); break;
+    case BP_PCM_F64: BP_STREAM_DOWNMIX(BP_PCM_F64); break;
+    default: BP_STREAM_DOWNMIX(BP_PCM_F32); break;
+  }
+#undef BP_STREAM_DOWNMIX
+}
+
+void launch_stream_resample(const float* hist, int n_hist, const float* chunk, int64_t chunk_start, int64_t n_in,
+                            const double* taps, const ResamplePlan& pl, int64_t k0, int64_t n_k, float* ring, int ring_pos,
+                            int ring_cap, hipStream_t stream) {
+  if (n_k <= 0) return;
+  hipLaunchKernelGGL(stream_resample_kernel, dim3((unsigned)((n_k + 255) / 256)), dim3(256), 0, stream, hist, n_hist, chunk,
+                     chunk_start, n_in, taps, pl, k0, n_k, ring, ring_pos, ring_cap);
+}
+
 }  // namespace bp

@@ -188,6 +188,21 @@ struct TrackSegs {
   int n;
 };
 
+// One window of a streaming step (stream_api.hip): where its samples lie in its stream's ring and where its kept frames go.
+// A step's windows come from any number of streams, so the table lives in device memory, one entry per window slot of a
+// chunk: one launch windows them all and one un-overlaps them all, whatever the number of streams.
+struct StreamSlot {
+  const float* ring;  // the stream's ring of the model-rate signal: sample p at ring[p % ring_cap]
+  float* out[3];      // the stream's note / onset / contour rows of this call (device)
+  int64_t start;      // absolute index of the window's first sample (negative inside the lead-in)
+  int64_t n_valid;    // samples the signal has: beyond them zeros (a finished stream is zero-extended)
+  int64_t out_row;    // row of out[] the window's first kept frame goes to
+  int ring_cap;       // >= the window length
+  int start_pos;      // start mod ring_cap, in [0, ring_cap)
+  int n_rows;         // kept frames to write: 142, fewer where finish trims to T rows, 0 for none
+  int reserved;
+};
+
 // order-preserving float <-> int map so per-window min/max can use integer atomics
 __device__ __forceinline__ int f2ord(float f) {
   int i = __float_as_int(f);

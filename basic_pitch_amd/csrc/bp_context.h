@@ -71,6 +71,17 @@ struct bp_context {
   float* nd_stats_host = nullptr;  // page-locked copy of the stats record
   void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
   bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
+  // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
+  // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window slots.  The
+  // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.
+  float *st_pcm = nullptr, *st_mono = nullptr, *st_out = nullptr, *st_slots = nullptr;
+  int64_t st_pcm_cap = 0, st_mono_cap = 0, st_out_cap = 0, st_slots_cap = 0;
+  struct StreamTaps {
+    int rate;
+    double* dev;
+    bp::ResamplePlan plan;
+  };
+  std::vector<StreamTaps> st_taps;
 
   // stage timing: a ring of event sets, one per chunk, averaged by bp_get_stage_ms
   static constexpr int kTimedRing = 128;
@@ -104,4 +115,8 @@ int alloc(bp_handle h, float** p, int64_t floats);
 int grow(bp_handle h, float** buf, int64_t* cap, int64_t need);
 int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float* onset_dev, float* contour_dev);
 int wait_stream(bp_handle h);
+// track_api.hip: the end of a call that has queued work, and the argument domain of raw PCM
+int finish(bp_handle h, int rc);
+int pcm_width(int format);
+int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind);
 }  // namespace bp

@@ -18,6 +18,9 @@ void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, c
                           hipStream_t stream);
 void launch_unwrap3(const float* note, const float* onset, const float* contour, int64_t first_window, int n_windows,
                     int64_t total_rows, float* o_note, float* o_onset, float* o_contour, hipStream_t stream);
+void launch_window_streams(const StreamSlot* slots, int n_slots, float* audio, int win_len, hipStream_t stream);
+void launch_unwrap_streams(const StreamSlot* slots, int n_slots, const float* note, const float* onset, const float* contour,
+                           hipStream_t stream);
 
 // cqt_filterbank.hip: the exact-f32 filterbank (BP_FLAG_F32_MFMA)
 size_t filterbank_scratch_floats(int n_windows);
@@ -102,6 +105,14 @@ void launch_downmix(const float* pcm, int64_t n_frames, int channels, float* mon
 void launch_downmix_raw(const void* raw, int format, int64_t n_frames, int channels, float* mono, hipStream_t stream);
 void launch_resample(const float* x, int64_t n_in, const double* taps, const ResamplePlan& pl, float* y,
                      int64_t n_out, int mode, hipStream_t stream);
+// streaming ingest (stream_api.hip): frames -> mono at dst[(dst_pos + i) % dst_cap] (dst_cap 0: a plain buffer) and, with
+// n_hist > 0, the last n_hist mono frames of (hist_old | these frames) -> hist_new; outputs [k0, k0 + n_k) of the signal
+// whose frames before `chunk_start` are the n_hist of `hist` and from there on `chunk` -> ring[(ring_pos + i) % ring_cap]
+void launch_stream_downmix(const void* raw, int format, int64_t n_frames, int channels, float* dst, int dst_pos, int dst_cap,
+                           const float* hist_old, float* hist_new, int n_hist, hipStream_t stream);
+void launch_stream_resample(const float* hist, int n_hist, const float* chunk, int64_t chunk_start, int64_t n_in,
+                            const double* taps, const ResamplePlan& pl, int64_t k0, int64_t n_k, float* ring, int ring_pos,
+                            int ring_cap, hipStream_t stream);
 
 // flac_device.hip
 struct FdStream {

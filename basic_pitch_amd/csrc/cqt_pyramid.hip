@@ -199,4 +199,42 @@ void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, c
   hipLaunchKernelGGL(unwrap_tracks_kernel, dim3(16, n_slots, 3), dim3(256), 0, stream, ts, note, onset, contour);
 }
 
+// ---- streaming steps (stream_api.hip): the same two kernels over windows that lie in the rings of any number of streams;
+// blockIdx.y = window slot of the chunk, its entry of the slot table says where the window is and where its rows go ----
+__global__ __launch_bounds__(256) void window_streams_kernel(const StreamSlot* __restrict__ slots, float* __restrict__ audio,
+                                                             int win_len) {
+  const StreamSlot g = slots[blockIdx.y];  // block-uniform
+  float* dst = audio + (int64_t)blockIdx.y * win_len;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < win_len; i += gridDim.x * 256) {
+    const int64_t x = g.start + i;
+    int p = g.start_pos + i;  // win_len <= ring_cap: one wrap at most
+    if (p >= g.ring_cap) p -= g.ring_cap;
+    dst[i] = (x >= 0 && x < g.n_valid) ? g.ring[p] : 0.0f;
+  }
+}
+
+void launch_window_streams(const StreamSlot* slots, int n_slots, float* audio, int win_len, hipStream_t stream) {
+  hipLaunchKernelGGL(window_streams_kernel, dim3(43, n_slots), dim3(256), 0, stream, slots, audio, win_len);
+}
+
+__global__ __launch_bounds__(256) void unwrap_streams_kernel(const StreamSlot* __restrict__ slots,
+                                                             const float* __restrict__ note,
+                                                             const float* __restrict__ onset,
+                                                             const float* __restrict__ contour) {
+  const int slot = blockIdx.y, map = blockIdx.z;
+  const StreamSlot g = slots[slot];
+  if (g.n_rows <= 0) return;
+  const int n_freq = map == 2 ? kFreqC : kFreqN;
+  const float* win_out = map == 0 ? note : (map == 1 ? onset : contour);
+  const float* src = win_out + ((int64_t)slot * kFrames + 15) * n_freq;
+  float* dst = g.out[map] + g.out_row * n_freq;
+  const int n = g.n_rows * n_freq;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dst[i] = src[i];
+}
+
+void launch_unwrap_streams(const StreamSlot* slots, int n_slots, const float* note, const float* onset, const float* contour,
+                           hipStream_t stream) {
+  hipLaunchKernelGGL(unwrap_streams_kernel, dim3(16, n_slots, 3), dim3(256), 0, stream, slots, note, onset, contour);
+}
+
 }  // namespace bp

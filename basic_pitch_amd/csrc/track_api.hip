@@ -16,6 +16,34 @@ extern "C" void bp_internal_bend_tables(int32_t* tab, double* gauss);
 extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
+// ---- what the streaming sessions (stream_api.hip) share with this file (declared in bp_context.h)
+namespace bp {
+
+// The end of a call that has queued work: the wait, or on the first error the drained stream (its own status ignored), so
+// that no copy from or into a caller's buffer is still in flight when the call returns.
+int finish(bp_handle h, int rc) {
+  if (rc == BP_OK) rc = wait_stream(h);
+  if (rc != BP_OK) (void)hipStreamSynchronize(h->stream);
+  return rc;
+}
+
+int pcm_width(int format) {
+  static const int width[] = {4, 2, 3, 4, 1, 8};  // BP_PCM_F32, S16, S24, S32, U8, F64
+  return format >= BP_PCM_F32 && format <= BP_PCM_F64 ? width[format] : 0;
+}
+
+// pcm_given: false for a null pcm pointer (the FLAC path's device buffer counts as given)
+int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind) {
+  if (n_frames < 0 || channels < 1 || channels > 64 || sample_rate < 1000 || sample_rate > 768000 || pcm_width(format) == 0 ||
+      (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE) || (n_frames > 0 && !pcm_given)) {
+    h->err = "audio ingest: bad argument (n_frames, channels, sample_rate, format, mem_kind or null pcm)";
+    return BP_ERR_INVALID_ARG;
+  }
+  return BP_OK;
+}
+
+}  // namespace bp
+
 namespace {
 
 // ---- geometry: windows and frames of a 22.05 kHz signal for a hop / lead-in (the reference's 36164 / 3840, or a handle's:
@@ -74,30 +102,7 @@ int stage_samples(bp_handle h, int64_t n_tracks, const float* const* samples, co
   return BP_OK;
 }
 
-// The end of a call that has queued work: the wait, or on the first error the drained stream (its own status ignored), so
-// that no copy from or into a caller's buffer is still in flight when the call returns.
-int finish(bp_handle h, int rc) {
-  if (rc == BP_OK) rc = wait_stream(h);
-  if (rc != BP_OK) (void)hipStreamSynchronize(h->stream);
-  return rc;
-}
-
 // ---- audio ingest: downmix + resample into h->res_dev (or straight through when already mono 22.05 kHz on the device)
-int pcm_width(int format) {
-  static const int width[] = {4, 2, 3, 4, 1, 8};  // BP_PCM_F32, S16, S24, S32, U8, F64
-  return format >= BP_PCM_F32 && format <= BP_PCM_F64 ? width[format] : 0;
-}
-
-// pcm_given: false for a null pcm pointer (the FLAC path's device buffer counts as given)
-int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind) {
-  if (n_frames < 0 || channels < 1 || channels > 64 || sample_rate < 1000 || sample_rate > 768000 || pcm_width(format) == 0 ||
-      (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE) || (n_frames > 0 && !pcm_given)) {
-    h->err = "audio ingest: bad argument (n_frames, channels, sample_rate, format, mem_kind or null pcm)";
-    return BP_ERR_INVALID_ARG;
-  }
-  return BP_OK;
-}
-
 // n_frames > 0, the arguments checked; *out = device pointer of the 22.05 kHz signal (bp_handle_resampled_length samples)
 int queue_ingest(bp_handle h, const void* pcm, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind,
                  const float** out) {

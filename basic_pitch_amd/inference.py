@@ -379,6 +379,22 @@ class Model:
         self._infer("bp_infer_flac", (data, len(data)), out)
         return out
 
+    # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
+    def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
+        """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
+        `Stream.push(chunk)` returns the posteriorgram rows that became final, `Stream.finish()` the rest; concatenated
+        they are bit for bit `predict_pcm_raw` of the whole input (bp_stream_*)."""
+        from .streaming import Stream
+
+        return Stream(self, sample_rate, channels, fmt)
+
+    def push_streams(self, streams, chunks) -> "List[Dict[str, np.ndarray]]":
+        """One step for several of this model's streams: `chunks[i]` goes to `streams[i]`, the newly complete windows of
+        all of them run in full batches (bp_streams_push).  Each stream's new rows, as `Stream.push` would return them."""
+        from .streaming import push_streams
+
+        return push_streams(self, streams, chunks)
+
     # -- introspection ----------------------------------------------------------------------------
     def info(self) -> Dict[str, Any]:
         inf = _native.bp_info()

@@ -252,6 +252,61 @@ int64_t bp_handle_window_samples(bp_handle h);
 int bp_handle_sample_rate(bp_handle h);
 int64_t bp_handle_resampled_length(bp_handle h, int64_t n_frames, int sample_rate);
 
+/*
+ * ---- streaming sessions: audio that arrives over time (a microphone, a network stream, a recording too long to hold) ----
+ * The reference has no such interface: its user buffers the audio, windows it by hand and re-derives the un-overlapping of
+ * inference.py:194-279.  A bp_stream belongs to a handle and uses its geometry (window, hop, lead-in, sample rate: bf16 and
+ * extended-range handles stream too).  PCM goes in as it comes (format / channels / sample_rate fixed at open, the argument
+ * domain of bp_infer_pcm_raw); the rows of the three un-overlapped maps come out as soon as they are FINAL.
+ *
+ * The contract: the rows a stream emits, concatenated over its pushes and its finish, are bit for bit what
+ * bp_infer_pcm_raw returns for the concatenated input, however the input was cut into pushes.
+ *
+ * Finality: window w is complete once the resampled signal has w * hop - lead + window samples (22.05 kHz geometry:
+ * w * 36164 + 40004); it then yields rows [142 w, 142 (w + 1)).  A resampled sample exists once every input frame its
+ * filter reaches has arrived.  bp_stream_finish zero-extends the signal, makes the samples at its end (their sums clipped
+ * at the last frame, like the one-shot kernel's), runs the remaining windows and emits the rows up to
+ * T = bp_handle_track_n_frames(h, bp_handle_resampled_length(h, frames pushed, sample_rate)).
+ *
+ *   bp_stream_open    BP_ERR_INVALID_ARG as bp_infer_pcm_raw; BP_ERR_UNSUPPORTED for a rate whose filter the one-shot calls
+ *                     evaluate in the kernel instead of from a table (more than 2^22 taps, e.g. 44101 Hz): not streamed
+ *   bp_stream_push    appends n_frames interleaved frames (0 is fine; any amount: more than the stream's ring holds runs in
+ *                     several rounds inside the call) and writes the *rows rows that became final to note / onset [.,88],
+ *                     contour [.,264] (host or device per out_mem_kind; pcm per pcm_mem_kind)
+ *   bp_stream_finish  the end of the signal; afterwards only bp_stream_close is valid
+ *   bp_streams_push   one step for n DIFFERENT streams of handle h (formats and rates may differ, entries may be empty):
+ *                     ingest per stream, then the newly complete windows of ALL streams packed into full batches — one
+ *                     windowing launch, the model and one un-overlapping launch per batch, whatever n is.  Each stream gets
+ *                     exactly the rows bp_stream_push would have given it.
+ *   bp_stream_close   frees the stream (close every stream before bp_destroy of its handle)
+ *   bp_stream_rows_bound   the most rows a push of n_frames now, or a finish now, can emit: size the buffers with it
+ *   bp_stream_state_bytes  device memory the stream holds.  It does not depend on how much audio has passed: a ring of the
+ *                     resampled signal (window + 4 hops, reaching back to the first sample of the oldest incomplete window)
+ *                     and twice the resampler's input history (ceil(n_taps / up) frames); the counters are int64.
+ *   bp_stream_rows_after   rows emitted once the resampled signal has n samples, for the 22.05 kHz geometry (pure function,
+ *                     no handle, no GPU); finished != 0: bp_track_n_frames(n).  Never more than bp_track_n_frames(n) —
+ *                     which is what allows rows to leave before the length is known.
+ *
+ * Every argument is checked before anything is queued; a capacity_rows that is too small is BP_ERR_INVALID_ARG with
+ * NOTHING taken from the stream, so the same push can be repeated with larger buffers.  A call that fails after queuing
+ * returns once the handle's stream has drained; its streams then accept only bp_stream_close.  Calls on the streams of a
+ * handle are serialised by the caller like all calls on the handle; they may interleave freely with each other and with the
+ * one-shot calls (a stream keeps nothing in the handle between calls).  Errors are reported through bp_last_error(h).
+ */
+typedef struct bp_stream_state* bp_stream;
+int bp_stream_open(bp_handle h, int format, int channels, int sample_rate, bp_stream* out);
+int bp_stream_push(bp_stream s, const void* pcm, int64_t n_frames, int pcm_mem_kind, float* note, float* onset, float* contour,
+                   int64_t capacity_rows, int out_mem_kind, int64_t* rows);
+int bp_stream_finish(bp_stream s, float* note, float* onset, float* contour, int64_t capacity_rows, int out_mem_kind,
+                     int64_t* rows);
+int bp_streams_push(bp_handle h, int64_t n, const bp_stream* streams, const void* const* pcm, const int64_t* n_frames,
+                    int pcm_mem_kind, float* const* note, float* const* onset, float* const* contour,
+                    const int64_t* capacity_rows, int out_mem_kind, int64_t* rows);
+void bp_stream_close(bp_stream s);
+int64_t bp_stream_rows_bound(bp_stream s, int64_t n_frames);
+int64_t bp_stream_state_bytes(bp_stream s);
+int64_t bp_stream_rows_after(int64_t n_samples_22k, int finished);
+
 /* Run on an externally owned hipStream_t (e.g. torch's current stream); NULL = library stream. */
 int bp_set_stream(bp_handle h, void* hip_stream);
 int bp_synchronize(bp_handle h);

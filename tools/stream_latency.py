@@ -1,0 +1,175 @@
+"""What a streaming step costs beside the one-shot call on the same windows (recorded in profiles/stream_latency.md; no gate).
+
+    python tools/stream_latency.py --out profiles/stream_latency.md       # the wall-time tables (a) and (b)
+    rocprofv3 --kernel-trace --stats -d DIR -- python tools/stream_latency.py --trace 64 20
+    python tools/stream_latency.py --launches DIR 64 20                   # (c): kernel launches per step from that trace
+
+The yardstick is existing code in the same process on the same device: `bp_infer` with host buffers on the same number of
+windows in one call.  Every stream is a 22.05 kHz mono float stream primed with 3840 samples, so that each further push of
+one hop (36164 samples) completes exactly one window.  All calls are made at the C ABI with the argument arrays built once:
+what is timed is the library, not Python.  Medians of wall times, each call ending in the library's own wait for the device.
+"""
+from __future__ import annotations
+
+import argparse
+import csv
+import ctypes as C
+import glob
+import os
+import statistics
+import sys
+import time
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+HOP, WIN, LEAD = 36164, 43844, 3840
+
+
+class Bench:
+    def __init__(self, max_windows: int = 256):
+        from basic_pitch_amd import Model, streaming
+
+        self.model = Model(max_windows=max_windows)
+        self.lib = streaming.bind(self.model._lib)
+        self.h = self.model._handle
+        rng = np.random.default_rng(0)
+        self.hop = rng.uniform(-1, 1, HOP).astype(np.float32)
+        self.windows = rng.uniform(-1, 1, (max_windows, WIN)).astype(np.float32)
+        self.out = {k: np.empty((max_windows * 172, w), np.float32) for k, w in (("note", 88), ("onset", 88), ("contour", 264))}
+
+    def ok(self, rc: int, what: str) -> None:
+        if rc != 0:
+            raise RuntimeError(f"{what}: {rc}: {self.lib.bp_last_error(self.h).decode()}")
+
+    def infer(self, n: int):
+        o = self.out
+        args = (self.h, self.windows.ctypes.data, n, o["note"].ctypes.data, o["onset"].ctypes.data, o["contour"].ctypes.data, 0)
+        return lambda: self.ok(self.lib.bp_infer(*args), "bp_infer")
+
+    def open(self, n: int):
+        """n primed streams: the next hop-sized push of each completes exactly one window."""
+        streams = [self.model.open_stream(22050) for _ in range(n)]
+        for s in streams:
+            s.push(self.hop[: WIN - LEAD - HOP])
+        return streams
+
+    def single_push(self, s):
+        o, rows = self.out, C.c_int64(0)
+        args = (s._s, self.hop.ctypes.data, HOP, 0, o["note"].ctypes.data, o["onset"].ctypes.data, o["contour"].ctypes.data, 142,
+                0, C.byref(rows))
+
+        def call():
+            self.ok(self.lib.bp_stream_push(*args), "bp_stream_push")
+            assert rows.value == 142
+
+        return call
+
+    def step(self, active, idle=()):
+        """One bp_streams_push: a hop for every stream of `active`, an empty entry for every stream of `idle`."""
+        n, o = len(active) + len(idle), self.out
+        arr = lambda vals: (C.c_void_p * n)(*vals)  # noqa: E731
+        at = lambda k, i, w: o[k].ctypes.data + i * 142 * w * 4  # noqa: E731
+        rows = (C.c_int64 * n)()
+        slot = list(range(len(active))) + [0] * len(idle)  # an idle entry gets no rows: any valid pointer serves
+        args = (self.h, n, arr([s._s.value for s in list(active) + list(idle)]),
+                arr([self.hop.ctypes.data] * len(active) + [None] * len(idle)), (C.c_int64 * n)(*([HOP] * len(active) + [0] * len(idle))),
+                0, arr([at("note", i, 88) for i in slot]), arr([at("onset", i, 88) for i in slot]),
+                arr([at("contour", i, 264) for i in slot]), (C.c_int64 * n)(*([142] * n)), 0, rows)
+
+        def call():
+            self.ok(self.lib.bp_streams_push(*args), "bp_streams_push")
+            assert sum(rows) == 142 * len(active)
+
+        return call
+
+
+def median_ms(call, repeats: int, warmup: int = 10) -> float:
+    for _ in range(warmup):
+        call()
+    times = []
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        call()
+        times.append(time.perf_counter() - t0)
+    return 1e3 * statistics.median(times)
+
+
+def tables(out_path: str) -> None:
+    b = Bench()
+    lines = ["# Streaming steps beside the one-shot call (tools/stream_latency.py)", "",
+             "Wall time per call in ms, median; every call ends in the library's wait for the device.  22.05 kHz mono float",
+             "streams, each push one hop (36164 samples, 141 KB from pageable host memory) completing exactly one window; the",
+             "yardstick `bp_infer` takes the same number of windows (43844 samples each) from pageable host memory in one call.",
+             "Handle of 256 windows.", ""]
+    (s,) = b.open(1)
+    a_push, a_infer = median_ms(b.single_push(s), 300), median_ms(b.infer(1), 300)
+    lines += ["## (a) one stream, one window per push (median of 300)", "", "| call | ms |", "|---|---|",
+              f"| `bp_stream_push` completing 1 window | {a_push:.3f} |", f"| `bp_infer`, 1 window | {a_infer:.3f} |", ""]
+    s.close()
+    lines += ["## (b) N streams, one window each per step", "",
+              "`N single pushes`: the same N windows through N `bp_stream_push` calls, per step of N (median over the steps;",
+              "at least 300 pushes and 5 steps per row).  `+4N idle`: the same step with 4 N further streams in the call whose",
+              "entries are empty.", "",
+              "| N | `bp_streams_push` (300 steps) | `+4N idle` (300 steps) | `bp_infer`, N windows (300 calls) | N single pushes |",
+              "|---|---|---|---|---|"]
+    for n in (16, 64, 256):
+        streams = b.open(5 * n)
+        active, idle = streams[:n], streams[n:]
+        t_step = median_ms(b.step(active), 300)
+        t_idle = median_ms(b.step(active, idle), 300)
+        t_infer = median_ms(b.infer(n), 300)
+        pushes = [b.single_push(s) for s in active]
+        t_single = median_ms(lambda: [p() for p in pushes], max(5, -(-300 // n)), warmup=2)
+        lines.append(f"| {n} | {t_step:.3f} | {t_idle:.3f} | {t_infer:.3f} | {t_single:.3f} |")
+        for s in streams:
+            s.close()
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+
+
+def trace(n: int, steps: int) -> None:
+    """The traced program: n primed streams, `steps` steps of one window each (run it under rocprofv3)."""
+    b = Bench()
+    call = b.step(b.open(n))
+    for _ in range(steps):
+        call()
+
+
+def launches(trace_dir: str, n: int, steps: int) -> None:
+    """Kernel launches per step from the kernel statistics of the traced run: the n priming pushes launch one downmix
+    each and nothing else, everything beyond them belongs to the steps."""
+    calls = {}
+    for path in glob.glob(os.path.join(trace_dir, "**", "*kernel_stats.csv"), recursive=True):
+        with open(path) as f:
+            for row in csv.DictReader(f):
+                calls[row["Name"]] = calls.get(row["Name"], 0) + int(row["Calls"])
+    if not calls:
+        raise SystemExit(f"no *kernel_stats.csv under {trace_dir}")
+    print(f"## (c) kernel launches, {n} streams, {steps} steps of one window per stream (rocprofv3 --kernel-trace --stats)\n")
+    print("| kernel | launches | per step |\n|---|---|---|")
+    total = 0
+    for name, c in sorted(calls.items(), key=lambda kv: -kv[1]):
+        c_steps = c - n if "stream_downmix_kernel" in name else c
+        total += c_steps
+        print(f"| `{name[:90]}` | {c} | {c_steps / steps:.2f} |")
+    print(f"\nPer step: {total / steps:.2f} launches, of which {n} are the ingest of the {n} chunks (one per stream with input).")
+
+
+if __name__ == "__main__":
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default="")
+    ap.add_argument("--trace", nargs=2, type=int, metavar=("N", "STEPS"))
+    ap.add_argument("--launches", nargs=3, metavar=("DIR", "N", "STEPS"))
+    a = ap.parse_args()
+    if a.trace:
+        trace(*a.trace)
+    elif a.launches:
+        launches(a.launches[0], int(a.launches[1]), int(a.launches[2]))
+    else:
+        tables(a.out)
