@@ -15,9 +15,14 @@
 //     (tests/test_gpu_parity.py); other ratios are ONE polyphase stage of the same specification where libsoxr
 //     cascades several.  Ratios whose tap table would pass 2^22 entries (e.g. 44101 Hz) evaluate the taps on the
 //     fly from a tabulated window instead of failing.
+// Each operation is written once and shared by the one-shot calls and the streaming sessions (stream_api.hip), whose rows
+// must equal the one-shot calls' bit for bit: a frame's channel mean is mono_frame<FMT> (float PCM is the BP_PCM_F32 case of
+// the one downmix kernel), an output's float64 sum is resample_sum (the tiled and the 2 : 1 kernels add the same terms in
+// the same order in their own form), a run-time sample format reaches its instantiation through for_pcm_format.
 // Roofline: HBM — 4 B x channels read + 4 B x 22050 / rate written per input frame; 389 / 2 fp64 MACs per input sample
 // at 2 : 1 (0.16 ms for a 3-minute 44.1 kHz track at the chip's 78 TFLOP/s fp64 vector rate: negligible).
 #include <cmath>
+#include <type_traits>
 #include <vector>
 
 #include "../../include/basic_pitch_amd.h"
@@ -104,19 +109,10 @@ ResamplePlan make_resample_plan(int source_rate, int target_rate, std::vector<do
   return pl;
 }
 
-__global__ __launch_bounds__(256) void downmix_kernel(const float* __restrict__ pcm, int64_t n_frames, int channels,
-                                                      float* __restrict__ mono) {
-  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n_frames) return;
-  const float* p = pcm + i * channels;
-  float s = 0.0f;
-  for (int c = 0; c < channels; ++c) s += p[c];  // numpy mean(axis=1, dtype=float32): pairwise for > 8, plain here
-  mono[i] = s / (float)channels;
-}
-
-// The same downmix straight from the file's sample format (bp_pcm_format): 16-bit stereo is half the bytes of its float
-// form over PCIe and the host never converts it.  Scales as in basic_pitch_amd/audio.py read_wav / the WAV reader of
-// file_pipeline.cpp (powers of two: exact), so the mono signal is bit-identical to the float path's.
+// The downmix straight from the file's sample format (bp_pcm_format; float PCM is the BP_PCM_F32 case): 16-bit stereo is
+// half the bytes of its float form over PCIe and the host never converts it.  Scales as in basic_pitch_amd/audio.py
+// read_wav / the WAV reader of file_pipeline.cpp (powers of two: exact), so the mono signal of an integer file is
+// bit-identical to that of its float form.
 template <int FMT>
 __device__ __forceinline__ float pcm_sample(const uint8_t* __restrict__ raw, int64_t i) {
   if (FMT == BP_PCM_S16) return (float)reinterpret_cast<const int16_t*>(raw)[i] * (1.0f / 32768.0f);
@@ -130,6 +126,29 @@ __device__ __forceinline__ float pcm_sample(const uint8_t* __restrict__ raw, int
   if (FMT == BP_PCM_S32) return (float)((double)reinterpret_cast<const int32_t*>(raw)[i] * (1.0 / 2147483648.0));
   if (FMT == BP_PCM_F64) return (float)reinterpret_cast<const double*>(raw)[i];
   return reinterpret_cast<const float*>(raw)[i];
+}
+
+// A frame's mono value: numpy mean(axis=1, dtype=float32) — pairwise for > 8 channels, plain here.  The one place it is
+// computed for the one-shot calls and the streaming sessions alike.
+template <int FMT>
+__device__ __forceinline__ float mono_frame(const uint8_t* __restrict__ raw, int64_t i, int channels) {
+  if (channels == 1) return pcm_sample<FMT>(raw, i);
+  float s = 0.0f;
+  for (int c = 0; c < channels; ++c) s += pcm_sample<FMT>(raw, i * channels + c);
+  return s / (float)channels;
+}
+
+// One call of f(std::integral_constant<int, FMT>) for a run-time bp_pcm_format (validated by the callers: pcm_width)
+template <class F>
+void for_pcm_format(int format, F&& f) {
+  switch (format) {
+    case BP_PCM_S16: return f(std::integral_constant<int, BP_PCM_S16>{});
+    case BP_PCM_S24: return f(std::integral_constant<int, BP_PCM_S24>{});
+    case BP_PCM_S32: return f(std::integral_constant<int, BP_PCM_S32>{});
+    case BP_PCM_U8: return f(std::integral_constant<int, BP_PCM_U8>{});
+    case BP_PCM_F64: return f(std::integral_constant<int, BP_PCM_F64>{});
+    default: return f(std::integral_constant<int, BP_PCM_F32>{});
+  }
 }
 
 // Four frames per thread (round 5: one frame per thread moved 63 MB in 34 us, a quarter of what the memory system streams;
@@ -155,31 +174,32 @@ __global__ __launch_bounds__(256) void downmix_raw_kernel(const uint8_t* __restr
     *reinterpret_cast<float4*>(mono + i4) = float4{o[0], o[1], o[2], o[3]};
     return;
   }
-  for (int64_t i = i4; i < i4 + 4 && i < n_frames; ++i) {
-    if (channels == 1) {
-      mono[i] = pcm_sample<FMT>(raw, i);
-      continue;
-    }
-    float s = 0.0f;
-    for (int c = 0; c < channels; ++c) s += pcm_sample<FMT>(raw, i * channels + c);
-    mono[i] = s / (float)channels;
-  }
+  for (int64_t i = i4; i < i4 + 4 && i < n_frames; ++i) mono[i] = mono_frame<FMT>(raw, i, channels);
 }
 
-// y[k] = sum_j x[j] h[k * down + centre - j * up], the signal zero outside [0, n_in)
+// y[k] = sum_j x[j] h[k * down + centre - j * up], the signal zero outside [0, n_in): ascending j, float64 products and
+// accumulator, one rounding to fp32.  x_at(j) fetches frame j; j_min >= 0 is the first frame the caller can fetch.  Every
+// kernel that is not this function (tiled, 2 : 1) adds the same terms in the same order.
+template <class X>
+__device__ __forceinline__ float resample_sum(int64_t k, int64_t n_in, const double* __restrict__ taps, const ResamplePlan& pl,
+                                              int64_t j_min, X&& x_at) {
+  const int64_t base = k * (int64_t)pl.down + pl.centre;
+  int64_t j_hi = base / pl.up;
+  if (j_hi > n_in - 1) j_hi = n_in - 1;
+  const int64_t lo_num = base - (pl.n_taps - 1);
+  int64_t j_lo = lo_num <= 0 ? 0 : (lo_num + pl.up - 1) / pl.up;
+  if (j_lo < j_min) j_lo = j_min;
+  double acc = 0.0;
+  for (int64_t j = j_lo; j <= j_hi; ++j) acc += (double)x_at(j) * taps[base - j * pl.up];
+  return (float)acc;
+}
+
 __global__ __launch_bounds__(256) void resample_poly_kernel(const float* __restrict__ x, int64_t n_in,
                                                             const double* __restrict__ taps, ResamplePlan pl,
                                                             float* __restrict__ y, int64_t n_out) {
   const int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (k >= n_out) return;
-  const int64_t base = k * (int64_t)pl.down + pl.centre;
-  int64_t j_hi = base / pl.up;
-  if (j_hi > n_in - 1) j_hi = n_in - 1;
-  const int64_t lo_num = base - (pl.n_taps - 1);
-  const int64_t j_lo = lo_num <= 0 ? 0 : (lo_num + pl.up - 1) / pl.up;
-  double acc = 0.0;
-  for (int64_t j = j_lo; j <= j_hi; ++j) acc += (double)x[j] * taps[base - j * pl.up];
-  y[k] = (float)acc;
+  y[k] = resample_sum(k, n_in, taps, pl, 0, [&](int64_t j) { return x[j]; });
 }
 
 // The same sum, term for term in the same order, for a block of 256 outputs whose input span fits LDS: the block's slice of
@@ -310,24 +330,13 @@ __global__ __launch_bounds__(256) void resample_direct_kernel(const float* __res
   y[k] = (float)(acc * pl.gain);
 }
 
-void launch_downmix(const float* pcm, int64_t n_frames, int channels, float* mono, hipStream_t stream) {
-  if (n_frames <= 0) return;
-  hipLaunchKernelGGL(downmix_kernel, dim3((unsigned)((n_frames + 255) / 256)), dim3(256), 0, stream, pcm, n_frames,
-                     channels, mono);
-}
-
 void launch_downmix_raw(const void* raw, int format, int64_t n_frames, int channels, float* mono, hipStream_t stream) {
   if (n_frames <= 0) return;
   const dim3 grid((unsigned)((n_frames + 1023) / 1024));  // four frames per thread
   const uint8_t* p = static_cast<const uint8_t*>(raw);
-  switch (format) {
-    case BP_PCM_S16: hipLaunchKernelGGL(downmix_raw_kernel<BP_PCM_S16>, grid, dim3(256), 0, stream, p, n_frames, channels, mono); break;
-    case BP_PCM_S24: hipLaunchKernelGGL(downmix_raw_kernel<BP_PCM_S24>, grid, dim3(256), 0, stream, p, n_frames, channels, mono); break;
-    case BP_PCM_S32: hipLaunchKernelGGL(downmix_raw_kernel<BP_PCM_S32>, grid, dim3(256), 0, stream, p, n_frames, channels, mono); break;
-    case BP_PCM_U8: hipLaunchKernelGGL(downmix_raw_kernel<BP_PCM_U8>, grid, dim3(256), 0, stream, p, n_frames, channels, mono); break;
-    case BP_PCM_F64: hipLaunchKernelGGL(downmix_raw_kernel<BP_PCM_F64>, grid, dim3(256), 0, stream, p, n_frames, channels, mono); break;
-    default: hipLaunchKernelGGL(downmix_raw_kernel<BP_PCM_F32>, grid, dim3(256), 0, stream, p, n_frames, channels, mono); break;
-  }
+  for_pcm_format(format, [&](auto fmt) {
+    hipLaunchKernelGGL(downmix_raw_kernel<decltype(fmt)::value>, grid, dim3(256), 0, stream, p, n_frames, channels, mono);
+  });
 }
 
 // mode 0: the fastest kernel that fits; 1: the one-thread-per-output kernel; 2: at most the tiled one (A/B runs, BP_RESAMPLE)
@@ -350,21 +359,12 @@ void launch_resample(const float* x, int64_t n_in, const double* taps, const Res
     hipLaunchKernelGGL(resample_poly_kernel, per_output, dim3(256), 0, stream, x, n_in, taps, pl, y, n_out);
 }
 
-// ---- streaming ingest (stream_api.hip): the same two steps on a chunk of a signal that arrives in pieces ------------------
-// A frame's mono value, computed as downmix_raw_kernel computes it.
-template <int FMT>
-__device__ __forceinline__ float mono_frame(const uint8_t* __restrict__ raw, int64_t i, int channels) {
-  if (channels == 1) return pcm_sample<FMT>(raw, i);
-  float s = 0.0f;
-  for (int c = 0; c < channels; ++c) s += pcm_sample<FMT>(raw, i * channels + c);
-  return s / (float)channels;
-}
-
+// ---- streaming ingest (stream_api.hip): the same downmix and the same sum on a chunk of a signal that arrives in pieces ----
 // Threads [0, n_frames): frame i -> dst[(dst_pos + i) mod dst_cap] (dst_cap 0: dst[i]; n_frames <= dst_cap otherwise).
 // Threads [n_frames, n_frames + n_hist): entry t of the resampler's next input history, the last n_hist mono frames of
 // (hist_old | these frames): from the chunk where it reaches that far back, else from the old history.
 template <int FMT>
-__global__ __launch_bounds__(256) void stream_downmix_kernel(const uint8_t* __restrict__ raw, int64_t n_frames, int channels,
+__global__ __launch_bounds__(256) void stream_mono_kernel(const uint8_t* __restrict__ raw, int64_t n_frames, int channels,
                                                              float* __restrict__ dst, int dst_pos, int dst_cap,
                                                              const float* __restrict__ hist_old,
                                                              float* __restrict__ hist_new, int n_hist) {
@@ -379,11 +379,10 @@ __global__ __launch_bounds__(256) void stream_downmix_kernel(const uint8_t* __re
   }
 }
 
-// resample_poly_kernel at an ABSOLUTE output index: y[k] for k in [k0, k0 + n_k) — the same taps, the same j order, the same
-// float64 accumulator, the same clipping of the sum at n_in — of a signal whose frames [chunk_start - n_hist, chunk_start)
-// are `hist` and whose frames from chunk_start on are `chunk`.  The caller asks only for outputs whose first frame
-// ceil((k down + centre - (n_taps - 1)) / up) lies inside the history (n_hist = ceil(n_taps / up) frames suffice for every
-// output that was not complete before the chunk arrived).  Output k goes to ring[(ring_pos + k - k0) mod ring_cap].
+// resample_sum at an ABSOLUTE output index: y[k] for k in [k0, k0 + n_k) of a signal whose frames [chunk_start - n_hist,
+// chunk_start) are `hist` and whose frames from chunk_start on are `chunk`.  The caller asks only for outputs whose first
+// frame ceil((k down + centre - (n_taps - 1)) / up) lies inside the history (n_hist = ceil(n_taps / up) frames suffice for
+// every output that was not complete before the chunk arrived).  Output k goes to ring[(ring_pos + k - k0) mod ring_cap].
 __global__ __launch_bounds__(256) void stream_resample_kernel(const float* __restrict__ hist, int n_hist,
                                                               const float* __restrict__ chunk, int64_t chunk_start,
                                                               int64_t n_in, const double* __restrict__ taps, ResamplePlan pl,
@@ -391,21 +390,11 @@ __global__ __launch_bounds__(256) void stream_resample_kernel(const float* __res
                                                               int ring_cap) {
   const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (idx >= n_k) return;
-  const int64_t k = k0 + idx;
-  const int64_t base = k * (int64_t)pl.down + pl.centre;
-  int64_t j_hi = base / pl.up;
-  if (j_hi > n_in - 1) j_hi = n_in - 1;
-  const int64_t lo_num = base - (pl.n_taps - 1);
-  int64_t j_lo = lo_num <= 0 ? 0 : (lo_num + pl.up - 1) / pl.up;
-  if (j_lo < chunk_start - n_hist) j_lo = chunk_start - n_hist;  // never taken for the outputs the caller asks for
-  double acc = 0.0;
-  for (int64_t j = j_lo; j <= j_hi; ++j) {
-    const float x = j >= chunk_start ? chunk[j - chunk_start] : hist[j - (chunk_start - n_hist)];
-    acc += (double)x * taps[base - j * pl.up];
-  }
+  const int64_t hist_start = chunk_start - n_hist;
   int64_t p = ring_pos + idx;  // n_k <= ring_cap: one wrap at most
   if (p >= ring_cap) p -= ring_cap;
-  ring[p] = (float)acc;
+  ring[p] = resample_sum(k0 + idx, n_in, taps, pl, hist_start < 0 ? 0 : hist_start,
+                         [&](int64_t j) { return j >= chunk_start ? chunk[j - chunk_start] : hist[j - hist_start]; });
 }
 
 void launch_stream_downmix(const void* raw, int format, int64_t n_frames, int channels, float* dst, int dst_pos, int dst_cap,
@@ -413,17 +402,10 @@ void launch_stream_downmix(const void* raw, int format, int64_t n_frames, int ch
   if (n_frames + n_hist <= 0) return;
   const dim3 grid((unsigned)((n_frames + n_hist + 255) / 256));
   const uint8_t* p = static_cast<const uint8_t*>(raw);
-#define BP_STREAM_DOWNMIX(F) \
-  hipLaunchKernelGGL(stream_downmix_kernel<F>, grid, dim3(256), 0, stream, p, n_frames, channels, dst, dst_pos, dst_cap, hist_old, hist_new, n_hist)
-  switch (format) {
-    case BP_PCM_S16: BP_STREAM_DOWNMIX(BP_PCM_S16); break;
-    case BP_PCM_S24: BP_STREAM_DOWNMIX(BP_PCM_S24); break;
-    case BP_PCM_S32: BP_STREAM_DOWNMIX(BP_PCM_S32); break;
-    case BP_PCM_U8: BP_STREAM_DOWNMIX(BP_PCM_U8); break;
-    case BP_PCM_F64: BP_STREAM_DOWNMIX(BP_PCM_F64); break;
-    default: BP_STREAM_DOWNMIX(BP_PCM_F32); break;
-  }
-#undef BP_STREAM_DOWNMIX
+  for_pcm_format(format, [&](auto fmt) {
+    hipLaunchKernelGGL(stream_mono_kernel<decltype(fmt)::value>, grid, dim3(256), 0, stream, p, n_frames, channels, dst,
+                       dst_pos, dst_cap, hist_old, hist_new, n_hist);
+  });
 }
 
 void launch_stream_resample(const float* hist, int n_hist, const float* chunk, int64_t chunk_start, int64_t n_in,

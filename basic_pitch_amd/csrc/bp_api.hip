@@ -96,7 +96,7 @@ int free_all(bp_handle h) {
                    h->d_o1_bias, h->d_n1_bfrag, h->d_n1_bias, h->d_w_contour2, h->d_w_note2, h->d_w_onset2,
                    h->audio, h->pyr, h->lp, h->c1, h->contour, h->n1, h->note, h->o1, h->onset, h->track,
                    h->track_out, h->nd_buf, h->nd_tables, h->fb_scratch, h->pcm_dev, h->mono_dev, h->res_dev, reinterpret_cast<float*>(h->taps_dev),
-                   h->st_pcm, h->st_mono, h->st_out, h->st_slots};
+                   h->st_pcm, h->st_mono, h->st_out, h->st_segs};
   for (float* p : ptrs)
     if (p) (void)hipFree(p);
   for (auto& t : h->st_taps) (void)hipFree(t.dev);

@@ -170,37 +170,28 @@ __device__ __forceinline__ float relu_f32(float v) {
   return __int_as_float(b > 0 ? b : 0);
 }
 
-// The pieces of tracks that make up one chunk of windows (bp_infer_tracks packs the windows of consecutive tracks into
-// full chunks): one launch windows them all, one launch un-overlaps all three posteriorgrams of all of them — per-piece
-// launches of these small kernels cost 5-9 us each, ~10 % of a whole-tracks job.
+// A run of consecutive windows of ONE source inside a chunk of windows, and where their kept frames go.  The source is a
+// whole track (bp_infer_track: one segment per chunk; bp_infer_tracks packs the windows of consecutive tracks into full
+// chunks, one segment per piece) or the ring of a streaming session (stream_api.hip: the windows a stream completes in a
+// round).  One launch windows all segments of a chunk and one un-overlaps all three posteriorgrams of all of them
+// (cqt_pyramid.hip) — per-piece launches of these small kernels cost 5-9 us each, ~10 % of a whole-tracks job.
+struct WindowSeg {
+  const float* src;    // the model-rate signal (device): sample p at src[p], or at src[p % ring_cap] of a ring
+  float* out[3];       // un-overlapped note / onset / contour rows (device)
+  int64_t n_valid;     // samples the signal has: zeros in front of sample 0 and from n_valid on
+  int64_t start;       // index of the first window's first sample (negative inside the lead-in); window i: start + i hop
+  int64_t out_row;     // row of out[] the first window's first kept frame goes to; window i: out_row + 142 i
+  int64_t total_rows;  // rows of out[]: kept frames from this row on are dropped (the trim to T rows)
+  int ring_cap;        // 0: src is a linear buffer; else the ring's length, >= the window length
+  int n_windows;       // windows of this segment
+  int at;              // its first window's slot in the chunk
+};
+// The segment table of a launch: in the kernel arguments for the track calls (at most kMaxTrackSegs per launch), in device
+// memory for a streaming step (any number of streams).
 constexpr int kMaxTrackSegs = 16;
-struct TrackSeg {
-  const float* samples;  // the track (device)
-  float* out[3];         // its un-overlapped note / onset / contour maps (device), T rows each
-  int64_t n_samples;
-  int64_t first_window;  // first window of this piece within the track
-  int64_t total_rows;    // T of the track
-  int n_windows;         // windows of this piece
-  int at;                // its first window's slot in the chunk
-};
-struct TrackSegs {
-  TrackSeg seg[kMaxTrackSegs];
+struct WindowSegs {
+  WindowSeg seg[kMaxTrackSegs];
   int n;
-};
-
-// One window of a streaming step (stream_api.hip): where its samples lie in its stream's ring and where its kept frames go.
-// A step's windows come from any number of streams, so the table lives in device memory, one entry per window slot of a
-// chunk: one launch windows them all and one un-overlaps them all, whatever the number of streams.
-struct StreamSlot {
-  const float* ring;  // the stream's ring of the model-rate signal: sample p at ring[p % ring_cap]
-  float* out[3];      // the stream's note / onset / contour rows of this call (device)
-  int64_t start;      // absolute index of the window's first sample (negative inside the lead-in)
-  int64_t n_valid;    // samples the signal has: beyond them zeros (a finished stream is zero-extended)
-  int64_t out_row;    // row of out[] the window's first kept frame goes to
-  int ring_cap;       // >= the window length
-  int start_pos;      // start mod ring_cap, in [0, ring_cap)
-  int n_rows;         // kept frames to write: 142, fewer where finish trims to T rows, 0 for none
-  int reserved;
 };
 
 // order-preserving float <-> int map so per-window min/max can use integer atomics

@@ -1,5 +1,6 @@
-// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip and weight_pack.hip share of it — the
-// HIP error macro and the workspace / chunk / wait helpers (defined in bp_api.hip).
+// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip, stream_api.hip and weight_pack.hip share
+// of it — the HIP error macro, the workspace / chunk / wait helpers (defined in bp_api.hip), and the maps, filter and argument
+// helpers of the track calls and the streaming sessions (defined in track_api.hip).
 #pragma once
 #include "../../include/basic_pitch_amd.h"
 
@@ -72,10 +73,10 @@ struct bp_context {
   void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
   bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
-  // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window slots.  The
+  // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.
-  float *st_pcm = nullptr, *st_mono = nullptr, *st_out = nullptr, *st_slots = nullptr;
-  int64_t st_pcm_cap = 0, st_mono_cap = 0, st_out_cap = 0, st_slots_cap = 0;
+  float *st_pcm = nullptr, *st_mono = nullptr, *st_out = nullptr, *st_segs = nullptr;
+  int64_t st_pcm_cap = 0, st_mono_cap = 0, st_out_cap = 0, st_segs_cap = 0;
   struct StreamTaps {
     int rate;
     double* dev;
@@ -119,4 +120,13 @@ int wait_stream(bp_handle h);
 int finish(bp_handle h, int rc);
 int pcm_width(int format);
 int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind);
+// the resampling filter sample_rate -> the handle's rate on the device: the plan, the table (with the 2 : 1 kernel's reversed
+// copy behind it) in a new allocation at *dev.  tabulated_only: a plan whose taps are evaluated in the kernel is returned
+// in *plan with BP_ERR_UNSUPPORTED, nothing allocated and no message set.
+int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePlan* plan, double** dev);
+// the three maps of T rows: [T][88] note, [T][88] onset, [T][264] contour — one after the other when they share a block
+struct Maps { float *note, *onset, *contour; };
+constexpr int64_t kMapsRow = 2 * kFreqN + kFreqC;  // floats of one row of all three
+inline Maps maps_at(float* base, int64_t T) { return {base, base + T * kFreqN, base + T * 2 * kFreqN}; }
+int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcpyKind kind);
 }  // namespace bp

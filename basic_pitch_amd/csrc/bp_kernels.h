@@ -10,17 +10,15 @@ namespace bp {
 
 // cqt_pyramid.hip
 void launch_pyramid(const float* audio, float* pyr, const float* lowpass, int n_windows, hipStream_t s);
-void launch_window_track(const float* samples, int64_t n_samples, int64_t first_window, int n_windows,
-                         float* audio, int win_len, int hop, int lead, hipStream_t stream);
-void launch_window_tracks(const TrackSegs& ts, int n_slots, float* audio, int win_len, int hop, int lead,
+// windowing / un-overlapping over the segments of a chunk: the table in the kernel arguments (track calls) or in device
+// memory (streaming steps)
+void launch_window_tracks(const WindowSegs& ts, int n_slots, float* audio, int win_len, int hop, hipStream_t stream);
+void launch_unwrap_tracks(const WindowSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
                           hipStream_t stream);
-void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
-                          hipStream_t stream);
-void launch_unwrap3(const float* note, const float* onset, const float* contour, int64_t first_window, int n_windows,
-                    int64_t total_rows, float* o_note, float* o_onset, float* o_contour, hipStream_t stream);
-void launch_window_streams(const StreamSlot* slots, int n_slots, float* audio, int win_len, hipStream_t stream);
-void launch_unwrap_streams(const StreamSlot* slots, int n_slots, const float* note, const float* onset, const float* contour,
+void launch_window_streams(const WindowSeg* segs, int n_segs, int n_slots, float* audio, int win_len, int hop,
                            hipStream_t stream);
+void launch_unwrap_streams(const WindowSeg* segs, int n_segs, int n_slots, const float* note, const float* onset,
+                           const float* contour, hipStream_t stream);
 
 // cqt_filterbank.hip: the exact-f32 filterbank (BP_FLAG_F32_MFMA)
 size_t filterbank_scratch_floats(int n_windows);
@@ -101,7 +99,7 @@ void launch_onset_branch(const uint32_t* zp, const float* note, const void* wfra
 
 // audio_ingest.hip
 ResamplePlan make_resample_plan(int source_rate, int target_rate, std::vector<double>& taps);
-void launch_downmix(const float* pcm, int64_t n_frames, int channels, float* mono, hipStream_t stream);
+// channel mean of interleaved PCM of any bp_pcm_format (float PCM: BP_PCM_F32)
 void launch_downmix_raw(const void* raw, int format, int64_t n_frames, int channels, float* mono, hipStream_t stream);
 void launch_resample(const float* x, int64_t n_in, const double* taps, const ResamplePlan& pl, float* y,
                      int64_t n_out, int mode, hipStream_t stream);

@@ -1,5 +1,5 @@
-// CQT pyramid: 8 x decimate-by-2 with the 256-tap half-band FIR, plus the track windowing /
-// un-overlapping copies.
+// CQT pyramid: 8 x decimate-by-2 with the 256-tap half-band FIR, plus the windowing / un-overlapping copies of the track
+// calls and of the streaming steps: one gather and one scatter over window segments (bp_common.h WindowSeg).
 //
 // Reference behaviour (spotify/basic-pitch v0.4.0):
 //   basic_pitch/layers/nnaudio.py:259-284 downsampling_by_n(match_torch_exactly=True):
@@ -88,153 +88,92 @@ void launch_pyramid(const float* audio, float* pyr, const float* lowpass, int n_
   }
 }
 
-// ---- track windowing (inference.py:242 zero lead-in of 3840, 207-213 hop 36164 + tail pad) ----
-// win_len / hop / lead: 43844 / 36164 / 3840 samples at 22.05 kHz, doubled for the extended 44.1 kHz geometry
-__global__ __launch_bounds__(256) void window_track_kernel(const float* __restrict__ samples,
-                                                           int64_t n_samples, int64_t first_window,
-                                                           float* __restrict__ audio, int win_len, int hop,
-                                                           int lead) {
-  const int64_t w = first_window + blockIdx.y;
-  const int64_t start = w * hop - lead;  // index into the un-padded track
-  float* dst = audio + (int64_t)blockIdx.y * win_len;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < win_len; i += gridDim.x * 256) {
-    const int64_t g = start + i;
-    dst[i] = (g >= 0 && g < n_samples) ? samples[g] : 0.0f;
+// ---- windowing (inference.py:242 zero lead-in of 3840, 207-213 hop 36164 + tail pad) and unwrap_output (inference.py:
+// 267-279: keep frames 15..156 of every window, trim to T rows), over the segments of a chunk (bp_common.h WindowSeg).
+// win_len / hop: 43844 / 36164 samples at 22.05 kHz, doubled for the extended 44.1 kHz geometry.  blockIdx.y = window
+// slot of the chunk, blockIdx.z = map; everything about a slot is block-uniform.
+
+// the segment that holds `slot`: the last one whose first slot is <= slot (the table is in slot order)
+__device__ __forceinline__ const WindowSeg& seg_of_slot(const WindowSeg* __restrict__ seg, int n, int slot) {
+  int lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int mid = (lo + hi) >> 1;
+    if (seg[mid].at <= slot) lo = mid; else hi = mid;
   }
+  return seg[lo];
 }
 
-void launch_window_track(const float* samples, int64_t n_samples, int64_t first_window,
-                         int n_windows, float* audio, int win_len, int hop, int lead, hipStream_t stream) {
-  hipLaunchKernelGGL(window_track_kernel, dim3(43, n_windows), dim3(256), 0, stream, samples,
-                     n_samples, first_window, audio, win_len, hop, lead);
-}
-
-// all pieces of a chunk in one launch: blockIdx.y = window slot of the chunk
-__global__ __launch_bounds__(256) void window_tracks_kernel(TrackSegs ts, float* __restrict__ audio, int win_len, int hop,
-                                                            int lead) {
-  const int slot = blockIdx.y;
-  int k = 0;
-  while (k + 1 < ts.n && slot >= ts.seg[k + 1].at) ++k;  // block-uniform
-  const TrackSeg& g = ts.seg[k];
-  const int64_t start = (g.first_window + (slot - g.at)) * hop - lead;
+// window `slot`: sample start + i of the source, or 0 outside [0, n_valid)
+__device__ __forceinline__ void gather_window(const WindowSeg& g, int slot, float* __restrict__ audio, int win_len, int hop) {
+  const int64_t start = g.start + (int64_t)(slot - g.at) * hop;
+  int64_t off = start;  // sample start + i lies at src[off + i], in a ring at src[off + i - ring_cap] from i = wrap on
+  int wrap = win_len;
+  if (g.ring_cap > 0) {
+    off = ((start % g.ring_cap) + g.ring_cap) % g.ring_cap;
+    wrap = g.ring_cap - (int)off;  // win_len <= ring_cap: one wrap at most
+  }
   float* dst = audio + (int64_t)slot * win_len;
   for (int i = blockIdx.x * 256 + threadIdx.x; i < win_len; i += gridDim.x * 256) {
     const int64_t x = start + i;
-    dst[i] = (x >= 0 && x < g.n_samples) ? g.samples[x] : 0.0f;
+    dst[i] = (x >= 0 && x < g.n_valid) ? g.src[off + (i < wrap ? i : i - g.ring_cap)] : 0.0f;
   }
 }
 
-void launch_window_tracks(const TrackSegs& ts, int n_slots, float* audio, int win_len, int hop, int lead,
-                          hipStream_t stream) {
-  hipLaunchKernelGGL(window_tracks_kernel, dim3(43, n_slots), dim3(256), 0, stream, ts, audio, win_len, hop, lead);
+// kept frames 15..156 of window `slot` of one map -> rows out_row + 142 i onwards of out[map], below total_rows
+__device__ __forceinline__ void scatter_window(const WindowSeg& g, int slot, int map, const float* __restrict__ note,
+                                               const float* __restrict__ onset, const float* __restrict__ contour) {
+  const int64_t row0 = g.out_row + (int64_t)(slot - g.at) * 142;
+  const int64_t left = g.total_rows - row0;
+  if (row0 < 0 || left <= 0) return;
+  const int n_freq = map == 2 ? kFreqC : kFreqN;
+  const float* win_out = map == 0 ? note : (map == 1 ? onset : contour);
+  const float* src = win_out + ((int64_t)slot * kFrames + 15) * n_freq;
+  float* dst = g.out[map] + row0 * n_freq;
+  const int n = (int)(left < 142 ? left : 142) * n_freq;
+  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dst[i] = src[i];
 }
 
-// ---- unwrap_output (inference.py:267-279): keep frames 15..156 of every window, trim to T rows ----
-__global__ __launch_bounds__(256) void unwrap_kernel(const float* __restrict__ win_out, int n_freq,
-                                                     int64_t first_window, int64_t total_rows,
-                                                     float* __restrict__ out) {
-  const int lw = blockIdx.y;            // local window in this chunk
-  const int64_t row0 = (first_window + lw) * 142;
-  const float* src = win_out + ((int64_t)lw * kFrames + 15) * n_freq;
-  const int n = 142 * n_freq;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const int64_t row = row0 + i / n_freq;
-    if (row < total_rows) out[row0 * n_freq + i] = src[i];
-  }
+// The wrappers differ only in where the segment table lives: the kernel arguments (track calls) or device memory
+// (streaming steps).
+__global__ __launch_bounds__(256) void window_tracks_kernel(WindowSegs ts, float* __restrict__ audio, int win_len, int hop) {
+  gather_window(seg_of_slot(ts.seg, ts.n, blockIdx.y), blockIdx.y, audio, win_len, hop);
 }
 
-// the three maps of a chunk in ONE launch (blockIdx.z = map): three launches of this small kernel cost a track ~30 us
-__global__ __launch_bounds__(256) void unwrap3_kernel(const float* __restrict__ note, const float* __restrict__ onset,
-                                                      const float* __restrict__ contour, int64_t first_window,
-                                                      int64_t total_rows, float* __restrict__ o_note,
-                                                      float* __restrict__ o_onset, float* __restrict__ o_contour) {
-  const int m = blockIdx.z;
-  const int n_freq = m == 2 ? kFreqC : kFreqN;
-  const float* win_out = m == 0 ? note : (m == 1 ? onset : contour);
-  float* out = m == 0 ? o_note : (m == 1 ? o_onset : o_contour);
-  const int lw = blockIdx.y;
-  const int64_t row0 = (first_window + lw) * 142;
-  const float* src = win_out + ((int64_t)lw * kFrames + 15) * n_freq;
-  const int n = 142 * n_freq;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const int64_t row = row0 + i / n_freq;
-    if (row < total_rows) out[row0 * n_freq + i] = src[i];
-  }
-}
-void launch_unwrap3(const float* note, const float* onset, const float* contour, int64_t first_window, int n_windows,
-                    int64_t total_rows, float* o_note, float* o_onset, float* o_contour, hipStream_t stream) {
-  hipLaunchKernelGGL(unwrap3_kernel, dim3(16, n_windows, 3), dim3(256), 0, stream, note, onset, contour, first_window,
-                     total_rows, o_note, o_onset, o_contour);
+__global__ __launch_bounds__(256) void window_streams_kernel(const WindowSeg* __restrict__ segs, int n_segs,
+                                                             float* __restrict__ audio, int win_len, int hop) {
+  gather_window(seg_of_slot(segs, n_segs, blockIdx.y), blockIdx.y, audio, win_len, hop);
 }
 
-void launch_unwrap(const float* win_out, int n_freq, int64_t first_window, int n_windows,
-                   int64_t total_rows, float* out, hipStream_t stream) {
-  hipLaunchKernelGGL(unwrap_kernel, dim3(16, n_windows), dim3(256), 0, stream, win_out, n_freq,
-                     first_window, total_rows, out);
-}
-
-// all pieces of a chunk and all three maps in one launch: blockIdx.y = window slot, blockIdx.z = map
-__global__ __launch_bounds__(256) void unwrap_tracks_kernel(TrackSegs ts, const float* __restrict__ note,
+__global__ __launch_bounds__(256) void unwrap_tracks_kernel(WindowSegs ts, const float* __restrict__ note,
                                                             const float* __restrict__ onset,
                                                             const float* __restrict__ contour) {
-  const int slot = blockIdx.y, map = blockIdx.z;
-  int k = 0;
-  while (k + 1 < ts.n && slot >= ts.seg[k + 1].at) ++k;
-  const TrackSeg& g = ts.seg[k];
-  if (g.total_rows <= 0) return;
-  const int n_freq = map == 2 ? 264 : 88;
-  const float* win_out = map == 0 ? note : (map == 1 ? onset : contour);
-  float* out = g.out[map];
-  const int64_t row0 = (g.first_window + (slot - g.at)) * 142;
-  const float* src = win_out + ((int64_t)slot * kFrames + 15) * n_freq;
-  const int n = 142 * n_freq;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) {
-    const int64_t row = row0 + i / n_freq;
-    if (row < g.total_rows) out[row0 * n_freq + i] = src[i];
-  }
+  scatter_window(seg_of_slot(ts.seg, ts.n, blockIdx.y), blockIdx.y, blockIdx.z, note, onset, contour);
 }
 
-void launch_unwrap_tracks(const TrackSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
+__global__ __launch_bounds__(256) void unwrap_streams_kernel(const WindowSeg* __restrict__ segs, int n_segs,
+                                                             const float* __restrict__ note,
+                                                             const float* __restrict__ onset,
+                                                             const float* __restrict__ contour) {
+  scatter_window(seg_of_slot(segs, n_segs, blockIdx.y), blockIdx.y, blockIdx.z, note, onset, contour);
+}
+
+void launch_window_tracks(const WindowSegs& ts, int n_slots, float* audio, int win_len, int hop, hipStream_t stream) {
+  hipLaunchKernelGGL(window_tracks_kernel, dim3(43, n_slots), dim3(256), 0, stream, ts, audio, win_len, hop);
+}
+
+void launch_unwrap_tracks(const WindowSegs& ts, int n_slots, const float* note, const float* onset, const float* contour,
                           hipStream_t stream) {
   hipLaunchKernelGGL(unwrap_tracks_kernel, dim3(16, n_slots, 3), dim3(256), 0, stream, ts, note, onset, contour);
 }
 
-// ---- streaming steps (stream_api.hip): the same two kernels over windows that lie in the rings of any number of streams;
-// blockIdx.y = window slot of the chunk, its entry of the slot table says where the window is and where its rows go ----
-__global__ __launch_bounds__(256) void window_streams_kernel(const StreamSlot* __restrict__ slots, float* __restrict__ audio,
-                                                             int win_len) {
-  const StreamSlot g = slots[blockIdx.y];  // block-uniform
-  float* dst = audio + (int64_t)blockIdx.y * win_len;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < win_len; i += gridDim.x * 256) {
-    const int64_t x = g.start + i;
-    int p = g.start_pos + i;  // win_len <= ring_cap: one wrap at most
-    if (p >= g.ring_cap) p -= g.ring_cap;
-    dst[i] = (x >= 0 && x < g.n_valid) ? g.ring[p] : 0.0f;
-  }
-}
-
-void launch_window_streams(const StreamSlot* slots, int n_slots, float* audio, int win_len, hipStream_t stream) {
-  hipLaunchKernelGGL(window_streams_kernel, dim3(43, n_slots), dim3(256), 0, stream, slots, audio, win_len);
-}
-
-__global__ __launch_bounds__(256) void unwrap_streams_kernel(const StreamSlot* __restrict__ slots,
-                                                             const float* __restrict__ note,
-                                                             const float* __restrict__ onset,
-                                                             const float* __restrict__ contour) {
-  const int slot = blockIdx.y, map = blockIdx.z;
-  const StreamSlot g = slots[slot];
-  if (g.n_rows <= 0) return;
-  const int n_freq = map == 2 ? kFreqC : kFreqN;
-  const float* win_out = map == 0 ? note : (map == 1 ? onset : contour);
-  const float* src = win_out + ((int64_t)slot * kFrames + 15) * n_freq;
-  float* dst = g.out[map] + g.out_row * n_freq;
-  const int n = g.n_rows * n_freq;
-  for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) dst[i] = src[i];
-}
-
-void launch_unwrap_streams(const StreamSlot* slots, int n_slots, const float* note, const float* onset, const float* contour,
+void launch_window_streams(const WindowSeg* segs, int n_segs, int n_slots, float* audio, int win_len, int hop,
                            hipStream_t stream) {
-  hipLaunchKernelGGL(unwrap_streams_kernel, dim3(16, n_slots, 3), dim3(256), 0, stream, slots, note, onset, contour);
+  hipLaunchKernelGGL(window_streams_kernel, dim3(43, n_slots), dim3(256), 0, stream, segs, n_segs, audio, win_len, hop);
+}
+
+void launch_unwrap_streams(const WindowSeg* segs, int n_segs, int n_slots, const float* note, const float* onset,
+                           const float* contour, hipStream_t stream) {
+  hipLaunchKernelGGL(unwrap_streams_kernel, dim3(16, n_slots, 3), dim3(256), 0, stream, segs, n_segs, note, onset, contour);
 }
 
 }  // namespace bp

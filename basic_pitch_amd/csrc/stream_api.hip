@@ -5,13 +5,16 @@
 // incomplete window and, when it resamples, the last ceil(n_taps / up) mono input frames; its counters are absolute int64
 // on the host.  A step (step()) is: validate everything -> plan -> queue -> wait.  The plan is made on the host from the
 // counters alone: rounds of (per stream: as much of the chunk as the ring has room for, resampled at absolute output
-// indices) + (the windows that are now complete, of all streams, packed into one chunk of the handle's workspace).  A round
-// queues one windowing launch, the model and one un-overlapping launch, however many streams take part; the window slots
-// of all rounds travel to the device in one copy.
+// indices) + (the windows that are now complete, of all streams, packed into one chunk of the handle's workspace: one
+// WindowSeg per stream, the track calls' descriptor with a source that wraps).  A round queues one windowing launch, the
+// model and one un-overlapping launch, however many streams take part; the segments of all rounds travel to the device in
+// one copy.
 //
-// Why the rows equal the one-shot call's, bit for bit: a resampled sample is one float64 sum over the same frames with the
-// same taps in the same order wherever the chunk boundaries fall (stream_resample_kernel), a window's samples depend on
-// its index alone, and a window's result does not depend on its batch or its slot.
+// Why the rows equal the one-shot call's, bit for bit: the downmix, the resampling sum, the window gather and the row
+// scatter are the one-shot calls' own device functions (audio_ingest.hip mono_frame / resample_sum, cqt_pyramid.hip
+// gather_window / scatter_window); a resampled sample is one float64 sum over the same frames with the same taps in the
+// same order wherever the chunk boundaries fall, a window's samples depend on its index alone, and a window's result does
+// not depend on its batch or its slot.
 #include <algorithm>
 #include <cstring>
 
@@ -73,21 +76,14 @@ int stream_taps(bp_handle h, bp_stream_state* s) {
       s->taps = t.dev;
       return BP_OK;
     }
-  std::vector<double> taps;
-  ResamplePlan pl = make_resample_plan(s->sample_rate, h->rate, taps);
-  pl.rev_off = 0;
-  if (pl.direct) {
-    h->err = "bp_stream_open: " + std::to_string(s->sample_rate) + " Hz -> " + std::to_string(h->rate) +
-             " Hz needs a filter of " + std::to_string(pl.n_taps) +
-             " taps, which the one-shot calls evaluate in the kernel; such ratios are not streamed";
-    return BP_ERR_UNSUPPORTED;
-  }
+  ResamplePlan pl{};
   double* dev = nullptr;
-  BP_HIP(hipMalloc(&dev, taps.size() * sizeof(double)));
-  if (hipMemcpy(dev, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(dev);
-    h->err = "bp_stream_open: copying the filter failed";
-    return BP_ERR_HIP;
+  if (int rc = upload_filter(h, s->sample_rate, true, &pl, &dev)) {
+    if (rc == BP_ERR_UNSUPPORTED)
+      h->err = "bp_stream_open: " + std::to_string(s->sample_rate) + " Hz -> " + std::to_string(h->rate) +
+               " Hz needs a filter of " + std::to_string(pl.n_taps) +
+               " taps, which the one-shot calls evaluate in the kernel; such ratios are not streamed";
+    return rc;
   }
   h->st_taps.push_back({s->sample_rate, dev, pl});
   s->plan = pl;
@@ -107,8 +103,8 @@ struct Entry {
   const uint8_t* pcm;  // the chunk where the kernels read it (device)
   int64_t n_frames;
   bool finish;
-  float* out[3];       // the rows of this call where the kernels write them (device)
-  float* user[3];
+  Maps out;            // the rows of this call where the kernels write them (device)
+  Maps user;
   int64_t rows;
   const float* mono;   // the chunk's mono form (resampling streams)
   // the plan's copy of the counters
@@ -121,11 +117,11 @@ struct Ingest {
 };
 struct Round {
   std::vector<Ingest> ingests;
-  int slot0 = 0, n_slots = 0;
+  int seg0 = 0, n_segs = 0, n_slots = 0;  // its segments in the step's table, its windows
 };
 
 int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int pcm_mem_kind, int out_mem_kind,
-               std::vector<StreamSlot>& slots) {
+               std::vector<WindowSeg>& segs) {
   hipStream_t q = h->stream;
   // scratch of the step, grown before anything is queued: the chunks (host PCM), their mono form, the rows (host outputs)
   int64_t pcm_floats = 0, mono_floats = 0, out_floats = 0;
@@ -133,7 +129,7 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
     const int64_t bytes = e.n_frames * e.s->channels * pcm_width(e.s->format);
     if (pcm_mem_kind == BP_MEM_HOST) pcm_floats += (bytes + 15) / 16 * 4;
     if (e.s->resamples) mono_floats += (e.n_frames + 3) / 4 * 4;
-    if (out_mem_kind == BP_MEM_HOST) out_floats += e.rows * (88 + 88 + 264);
+    if (out_mem_kind == BP_MEM_HOST) out_floats += e.rows * kMapsRow;
   }
   int rc;
   if ((rc = grow(h, &h->st_pcm, &h->st_pcm_cap, pcm_floats)) || (rc = grow(h, &h->st_mono, &h->st_mono_cap, mono_floats)) ||
@@ -150,21 +146,19 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
     }
     e.mono = h->st_mono + mono_at;
     if (e.s->resamples) mono_at += (e.n_frames + 3) / 4 * 4;
-    for (int m = 0; m < 3; ++m) e.out[m] = e.user[m];
+    e.out = e.user;
     if (out_mem_kind == BP_MEM_HOST) {
-      e.out[0] = h->st_out + out_at;
-      e.out[1] = e.out[0] + e.rows * 88;
-      e.out[2] = e.out[0] + e.rows * 176;
-      out_at += e.rows * 440;
+      e.out = maps_at(h->st_out + out_at, e.rows);
+      out_at += e.rows * kMapsRow;
     }
   }
 
   // ---- the plan: rounds of ingest + complete windows, from the counters alone
   std::vector<Round> rounds;
-  slots.clear();
+  segs.clear();
   for (;;) {
     Round r;
-    r.slot0 = (int)slots.size();
+    r.seg0 = (int)segs.size();
     for (size_t i = 0; i < es.size(); ++i) {
       Entry& e = es[i];
       const bp_stream_state* s = e.s;
@@ -182,27 +176,21 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
       const bp_stream_state* s = e.s;
       const int64_t n_win = e.finish && e.n_res == e.n_total ? bp_handle_track_n_windows(h, e.n_total)
                                                              : complete_windows(e.n_res, h->win_len, h->hop, h->lead);
-      const int64_t total_rows = s->rows_out + e.rows;  // finish: T
-      for (; e.w_next < n_win && r.n_slots < h->cap; ++e.w_next, ++r.n_slots) {
-        StreamSlot sl{};
-        sl.ring = s->ring;
-        for (int m = 0; m < 3; ++m) sl.out[m] = e.out[m];
-        sl.start = e.w_next * h->hop - h->lead;
-        sl.n_valid = e.n_res;
-        sl.ring_cap = s->ring_cap;
-        sl.start_pos = (int)(((sl.start % s->ring_cap) + s->ring_cap) % s->ring_cap);
-        const int64_t row0 = e.w_next * BP_FRAMES_PER_WINDOW;
-        sl.out_row = row0 - s->rows_out;
-        sl.n_rows = (int)std::max<int64_t>(0, std::min<int64_t>(BP_FRAMES_PER_WINDOW, total_rows - row0));
-        if (sl.out_row < 0) sl.n_rows = 0;  // cannot happen: a window's rows are emitted by the step that runs it
-        slots.push_back(sl);
-      }
+      const int n = (int)std::min<int64_t>(n_win - e.w_next, h->cap - r.n_slots);
+      if (n <= 0) continue;
+      // the stream's windows of this round: a track's piece whose source wraps, its rows counted from this call's first
+      // (a window's rows are emitted by the step that runs it; finish: e.rows ends at T)
+      segs.push_back(WindowSeg{s->ring, {e.out.note, e.out.onset, e.out.contour}, e.n_res, e.w_next * h->hop - h->lead,
+                               e.w_next * BP_FRAMES_PER_WINDOW - s->rows_out, e.rows, s->ring_cap, n, r.n_slots});
+      e.w_next += n;
+      r.n_slots += n;
     }
+    r.n_segs = (int)segs.size() - r.seg0;
     if (r.ingests.empty() && r.n_slots == 0) break;
     rounds.push_back(std::move(r));
   }
 
-  // ---- queue: the chunks, their mono form and the next history; the slot table; the rounds; the rows
+  // ---- queue: the chunks, their mono form and the next history; the segment table; the rounds; the rows
   for (size_t i = 0; i < es.size(); ++i) {
     Entry& e = es[i];
     bp_stream_state* s = e.s;
@@ -214,12 +202,12 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
       launch_stream_downmix(e.pcm, s->format, e.n_frames, s->channels, const_cast<float*>(e.mono), 0, 0, s->hist[s->cur_hist],
                             s->hist[s->cur_hist ^ 1], s->n_hist, q);
   }
-  if (!slots.empty()) {
-    const int64_t floats = (int64_t)(slots.size() * sizeof(StreamSlot) + 3) / 4;
-    if ((rc = grow(h, &h->st_slots, &h->st_slots_cap, floats))) return rc;
-    BP_HIP(hipMemcpyAsync(h->st_slots, slots.data(), slots.size() * sizeof(StreamSlot), hipMemcpyHostToDevice, q));
+  if (!segs.empty()) {
+    const int64_t floats = (int64_t)(segs.size() * sizeof(WindowSeg) + 3) / 4;
+    if ((rc = grow(h, &h->st_segs, &h->st_segs_cap, floats))) return rc;
+    BP_HIP(hipMemcpyAsync(h->st_segs, segs.data(), segs.size() * sizeof(WindowSeg), hipMemcpyHostToDevice, q));
   }
-  const StreamSlot* d_slots = reinterpret_cast<const StreamSlot*>(h->st_slots);
+  const WindowSeg* d_segs = reinterpret_cast<const WindowSeg*>(h->st_segs);
   for (const Round& r : rounds) {
     for (const Ingest& g : r.ingests) {
       const Entry& e = es[g.e];
@@ -233,17 +221,13 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
                               s->ring, pos, s->ring_cap, nullptr, nullptr, 0, q);
     }
     if (r.n_slots == 0) continue;
-    launch_window_streams(d_slots + r.slot0, r.n_slots, h->audio, h->win_len, q);
+    launch_window_streams(d_segs + r.seg0, r.n_segs, r.n_slots, h->audio, h->win_len, h->hop, q);
     if ((rc = run_chunk(h, h->audio, r.n_slots, h->note, h->onset, h->contour))) return rc;
-    launch_unwrap_streams(d_slots + r.slot0, r.n_slots, h->note, h->onset, h->contour, q);
+    launch_unwrap_streams(d_segs + r.seg0, r.n_segs, r.n_slots, h->note, h->onset, h->contour, q);
   }
   BP_HIP(hipGetLastError());
-  for (const Entry& e : es) {
-    if (out_mem_kind != BP_MEM_HOST || e.rows == 0) continue;
-    BP_HIP(hipMemcpyAsync(e.user[0], e.out[0], (size_t)e.rows * 88 * 4, hipMemcpyDeviceToHost, q));
-    BP_HIP(hipMemcpyAsync(e.user[1], e.out[1], (size_t)e.rows * 88 * 4, hipMemcpyDeviceToHost, q));
-    BP_HIP(hipMemcpyAsync(e.user[2], e.out[2], (size_t)e.rows * 264 * 4, hipMemcpyDeviceToHost, q));
-  }
+  for (const Entry& e : es)
+    if (out_mem_kind == BP_MEM_HOST && e.rows > 0 && (rc = copy_maps(h, e.user, e.out, e.rows, hipMemcpyDeviceToHost))) return rc;
   return BP_OK;
 }
 
@@ -281,7 +265,7 @@ int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, con
       return invalid("capacity_rows " + std::to_string(capacity_rows[i]) + " is too small for the " + std::to_string(e.rows) +
                      " rows of this step (bp_stream_rows_bound); nothing was taken from the stream");
     if (e.rows > 0 && (!note[i] || !onset[i] || !contour[i])) return invalid("null output pointer");
-    e.user[0] = note[i], e.user[1] = onset[i], e.user[2] = contour[i];
+    e.user = {note[i], onset[i], contour[i]};
     e.n_res = s->n_res;
     e.w_next = s->w_next;
     e.n_total = finish_streams ? bp_handle_resampled_length(h, s->n_in, s->sample_rate) : -1;
@@ -289,8 +273,8 @@ int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, con
   }
   if (work) {
     BP_HIP(hipSetDevice(h->device));
-    std::vector<StreamSlot> slots;  // read by an asynchronous copy: alive until the wait
-    if (int rc = finish(h, queue_step(h, es, pcm, pcm_mem_kind, out_mem_kind, slots))) {
+    std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
+    if (int rc = finish(h, queue_step(h, es, pcm, pcm_mem_kind, out_mem_kind, segs))) {
       for (auto& e : es) e.s->broken = true;
       return rc;
     }

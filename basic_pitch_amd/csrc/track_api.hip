@@ -3,7 +3,7 @@
 // note candidates of those maps.
 //
 // Every entry point is a source, the track and a sink on one driver (run_track):
-//   validate everything -> queue the source -> track_core -> queue the sink -> wait -> the FLAC decoder's verdict.
+//   validate everything -> queue the source -> tracks_core -> queue the sink -> wait -> the FLAC decoder's verdict.
 // Nothing is queued before every argument has been checked, and a call that fails after queuing work returns only once the
 // handle's stream has drained (finish): the caller may reuse its buffers as soon as any call returns.
 #include <algorithm>
@@ -16,7 +16,8 @@ extern "C" void bp_internal_bend_tables(int32_t* tab, double* gauss);
 extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
-// ---- what the streaming sessions (stream_api.hip) share with this file (declared in bp_context.h)
+// ---- what the streaming sessions (stream_api.hip) share with this file (declared in bp_context.h): the end of a call, the
+// argument domain of raw PCM, the resampling filter's builder, the copies of the three maps
 namespace bp {
 
 // The end of a call that has queued work: the wait, or on the first error the drained stream (its own status ignored), so
@@ -39,6 +40,38 @@ int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int 
     h->err = "audio ingest: bad argument (n_frames, channels, sample_rate, format, mem_kind or null pcm)";
     return BP_ERR_INVALID_ARG;
   }
+  return BP_OK;
+}
+
+int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePlan* plan, double** dev) {
+  std::vector<double> taps;
+  ResamplePlan pl = make_resample_plan(sample_rate, h->rate, taps);
+  pl.rev_off = 0;
+  *plan = pl;
+  if (pl.direct && tabulated_only) return BP_ERR_UNSUPPORTED;
+  if (!pl.direct && pl.up == 1 && pl.down == 2) {
+    // the 2 : 1 kernel walks the taps backwards, a block of 32 per scalar load: a reversed copy behind the table, padded
+    // with zeros to whole blocks (a zero tap adds x * 0 = 0 to a float64 sum)
+    const size_t M = taps.size(), base = (M + 31) / 32 * 32;
+    taps.resize(2 * base, 0.0);
+    for (size_t i = 0; i < M; ++i) taps[base + i] = taps[M - 1 - i];
+    plan->rev_off = (int64_t)base;
+  }
+  double* d = nullptr;
+  BP_HIP(hipMalloc(&d, taps.size() * sizeof(double)));
+  if (hipMemcpy(d, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
+    (void)hipFree(d);
+    h->err = "audio ingest: copying the resampling filter to the device failed";
+    return BP_ERR_HIP;
+  }
+  *dev = d;
+  return BP_OK;
+}
+
+int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcpyKind kind) {
+  BP_HIP(hipMemcpyAsync(dst.note, src.note, (size_t)T * kFreqN * 4, kind, h->stream));
+  BP_HIP(hipMemcpyAsync(dst.onset, src.onset, (size_t)T * kFreqN * 4, kind, h->stream));
+  BP_HIP(hipMemcpyAsync(dst.contour, src.contour, (size_t)T * kFreqC * 4, kind, h->stream));
   return BP_OK;
 }
 
@@ -66,26 +99,13 @@ int64_t resampled_length(int64_t n_frames, int sample_rate, int rate) {
 int64_t h_windows(bp_handle h, int64_t n) { return n_windows_of(n, h->hop, h->lead); }
 int64_t h_frames(bp_handle h, int64_t n) { return n_frames_of(n, h->hop, h->lead); }
 
-// ---- maps: [T][88] note, [T][88] onset, [T][264] contour
-struct Maps { float *note, *onset, *contour; };
-
-Maps maps_at(float* base, int64_t T) { return {base, base + T * 88, base + T * 176}; }
-
 // The only way to h->track_out: grown for `rows` rows of maps.  Whatever a *_candidates call left there for bp_track_maps
 // is gone from then on.
 int take_track_out(bp_handle h, int64_t rows, Maps* m) {
   h->maps_rows = 0;
-  int rc = grow(h, &h->track_out, &h->track_out_cap, rows * (88 + 88 + 264));
+  int rc = grow(h, &h->track_out, &h->track_out_cap, rows * kMapsRow);
   if (rc) return rc;
   *m = maps_at(h->track_out, rows);
-  return BP_OK;
-}
-
-int copy_maps(bp_handle h, const Maps& dst, const float* note, const float* onset, const float* contour, int64_t T,
-              hipMemcpyKind kind) {
-  BP_HIP(hipMemcpyAsync(dst.note, note, (size_t)T * 88 * 4, kind, h->stream));
-  BP_HIP(hipMemcpyAsync(dst.onset, onset, (size_t)T * 88 * 4, kind, h->stream));
-  BP_HIP(hipMemcpyAsync(dst.contour, contour, (size_t)T * 264 * 4, kind, h->stream));
   return BP_OK;
 }
 
@@ -120,34 +140,18 @@ int queue_ingest(bp_handle h, const void* pcm, int format, int64_t n_frames, int
   if (channels > 1 || format != BP_PCM_F32) {
     int rc = grow(h, &h->mono_dev, &h->mono_cap, n_frames);
     if (rc) return rc;
-    if (format == BP_PCM_F32)
-      launch_downmix(static_cast<const float*>(d_pcm), n_frames, channels, h->mono_dev, s);
-    else
-      launch_downmix_raw(d_pcm, format, n_frames, channels, h->mono_dev, s);
+    launch_downmix_raw(d_pcm, format, n_frames, channels, h->mono_dev, s);
     d_mono = h->mono_dev;
   }
   if (sample_rate == h->rate) {
     *out = d_mono;
     return BP_OK;
   }
-  if (h->taps_rate != sample_rate) {
-    std::vector<double> taps;
-    ResamplePlan pl = make_resample_plan(sample_rate, h->rate, taps);
-    pl.rev_off = 0;
-    if (!pl.direct && pl.up == 1 && pl.down == 2) {
-      // the 2 : 1 kernel walks the taps backwards, a block of 32 per scalar load: a reversed copy behind the table, padded
-      // with zeros to whole blocks (a zero tap adds x * 0 = 0 to a float64 sum)
-      const size_t M = taps.size(), base = (M + 31) / 32 * 32, padded = (M + 31) / 32 * 32;
-      taps.resize(base + padded, 0.0);
-      for (size_t i = 0; i < M; ++i) taps[base + i] = taps[M - 1 - i];
-      pl.rev_off = (int64_t)base;
-    }
+  if (h->taps_rate != sample_rate) {  // one cached filter: replaced when the rate changes
     if (h->taps_dev) BP_HIP(hipFree(h->taps_dev));
     h->taps_dev = nullptr;
     h->taps_rate = 0;
-    BP_HIP(hipMalloc(&h->taps_dev, taps.size() * sizeof(double)));
-    BP_HIP(hipMemcpy(h->taps_dev, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice));
-    h->plan = pl;
+    if (int rc = upload_filter(h, sample_rate, false, &h->plan, &h->taps_dev)) return rc;
     h->taps_rate = sample_rate;
   }
   int rc = grow(h, &h->res_dev, &h->res_cap, n_out);
@@ -216,17 +220,52 @@ int flac_device_verdict(bp_handle h) {
   return BP_ERR_BAD_AUDIO;
 }
 
-// ---- the track: windows of a device-resident 22.05 kHz signal -> un-overlapped maps of T rows at `out` (device memory)
-int track_core(bp_handle h, const float* d_samples, int64_t n_samples, int64_t T, const Maps& out) {
+// ---- the tracks: windows of device-resident model-rate signals -> their un-overlapped maps (device memory).  The windows of
+// consecutive tracks are packed into full chunks; the pieces of a chunk — one WindowSeg each; a single track: one per
+// chunk — are windowed by ONE launch and un-overlapped by one launch (more than kMaxTrackSegs pieces per chunk: several)
+int tracks_core(bp_handle h, int64_t n_tracks, const float* const* d_in, const int64_t* n_samples, const Maps* d_out) {
   hipStream_t s = h->stream;
-  const int64_t n_win = h_windows(h, n_samples);
-  for (int64_t w0 = 0; w0 < n_win; w0 += h->cap) {
-    const int n = (int)((n_win - w0) < h->cap ? (n_win - w0) : h->cap);
-    launch_window_track(d_samples, n_samples, w0, n, h->audio, h->win_len, h->hop, h->lead, s);
-    int rc = run_chunk(h, h->audio, n, h->note, h->onset, h->contour);
-    if (rc) return rc;
-    if (T > 0) launch_unwrap3(h->note, h->onset, h->contour, w0, n, T, out.note, out.onset, out.contour, s);
+  std::vector<WindowSeg> segs;
+  int cur = 0;
+  auto for_groups = [&](auto&& fn) {
+    for (size_t g0 = 0; g0 < segs.size(); g0 += kMaxTrackSegs) {
+      WindowSegs ts{};
+      ts.n = (int)std::min<size_t>(kMaxTrackSegs, segs.size() - g0);
+      for (int k = 0; k < ts.n; ++k) ts.seg[k] = segs[g0 + k];
+      const int first = ts.seg[0].at, slots = ts.seg[ts.n - 1].at + ts.seg[ts.n - 1].n_windows - first;
+      for (int k = 0; k < ts.n; ++k) ts.seg[k].at -= first;  // slots relative to the group's first window
+      fn(ts, first, slots);
+    }
+  };
+  auto flush = [&]() -> int {
+    if (cur == 0) return BP_OK;
+    for_groups([&](const WindowSegs& ts, int first, int slots) {
+      launch_window_tracks(ts, slots, h->audio + (int64_t)first * h->win_len, h->win_len, h->hop, s);
+    });
+    if (int rc = run_chunk(h, h->audio, cur, h->note, h->onset, h->contour)) return rc;
+    for_groups([&](const WindowSegs& ts, int first, int slots) {
+      launch_unwrap_tracks(ts, slots, h->note + (int64_t)first * kPlaneN, h->onset + (int64_t)first * kPlaneN,
+                           h->contour + (int64_t)first * kPlaneC, s);
+    });
+    segs.clear();
+    cur = 0;
+    return BP_OK;
+  };
+  for (int64_t t = 0; t < n_tracks; ++t) {
+    const int64_t n_win = h_windows(h, n_samples[t]);
+    const int64_t T = h_frames(h, n_samples[t]);
+    for (int64_t w0 = 0; w0 < n_win;) {
+      const int64_t room = h->cap - cur;
+      const int n = (int)((n_win - w0) < room ? (n_win - w0) : room);
+      segs.push_back(WindowSeg{d_in[t], {d_out[t].note, d_out[t].onset, d_out[t].contour}, n_samples[t], w0 * h->hop - h->lead,
+                               w0 * BP_FRAMES_PER_WINDOW, T, 0, n, cur});
+      cur += n;
+      w0 += n;
+      if (cur == h->cap)
+        if (int rc = flush()) return rc;
+    }
   }
+  if (int rc = flush()) return rc;
   BP_HIP(hipGetLastError());
   return BP_OK;
 }
@@ -386,7 +425,8 @@ int queue_all(bp_handle h, const Source& src, const Sink& k, int64_t T, bool* ex
     rc = queue_ingest(h, h->pcm_dev, flac_format(src.lay), src.lay.n_frames, src.lay.channels, src.lay.sample_rate,
                       BP_MEM_DEVICE, &d);
   } else if (src.kind == kMaps && !(rc = take_track_out(h, T, &m)) && T > 0) {
-    rc = copy_maps(h, m, d, src.onset, src.contour, T, src.mem_kind == BP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice);
+    const Maps given{const_cast<float*>(d), const_cast<float*>(src.onset), const_cast<float*>(src.contour)};  // only read
+    rc = copy_maps(h, m, given, T, src.mem_kind == BP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice);
   }
   if (rc) return rc;
   switch (k.kind) {
@@ -399,11 +439,11 @@ int queue_all(bp_handle h, const Source& src, const Sink& k, int64_t T, bool* ex
     case kDeviceMaps:
       if (h_windows(h, src.n) == 0) return BP_OK;
       if (k.kind == kHostMaps && (rc = take_track_out(h, T, &m))) return rc;
-      if ((rc = track_core(h, d, src.n, T, m))) return rc;
-      return k.kind == kHostMaps && T > 0 ? copy_maps(h, k.maps, m.note, m.onset, m.contour, T, hipMemcpyDeviceToHost) : BP_OK;
+      if ((rc = tracks_core(h, 1, &d, &src.n, &m))) return rc;
+      return k.kind == kHostMaps && T > 0 ? copy_maps(h, k.maps, m, T, hipMemcpyDeviceToHost) : BP_OK;
     case kCandidates:
       if (T == 0) return BP_OK;
-      if (src.kind != kMaps && ((rc = take_track_out(h, T, &m)) || (rc = track_core(h, d, src.n, T, m)))) return rc;
+      if (src.kind != kMaps && ((rc = take_track_out(h, T, &m)) || (rc = tracks_core(h, 1, &d, &src.n, &m)))) return rc;
       return queue_candidates(h, m, T, k.params, k.note_out, k.cand_bits, k.bend_map, exported_by_kernel);
   }
   return BP_OK;
@@ -433,11 +473,9 @@ int run_track(bp_handle h, const char* what, Source src, const Sink& k, bp_flac_
   return flac ? flac_device_verdict(h) : BP_OK;
 }
 
-// bp_infer_tracks: the windows of consecutive tracks are packed into full chunks; the pieces of a chunk are windowed by ONE
-// launch and un-overlapped by one launch (bp_common.h TrackSegs; more than kMaxTrackSegs pieces per chunk: several launches)
+// bp_infer_tracks: host tracks are staged one after the other, their maps come back from one block
 int queue_tracks(bp_handle h, int64_t n_tracks, const float* const* samples, const int64_t* n_samples, float* const* note,
                  float* const* onset, float* const* contour, int mem_kind, int64_t total_samples, int64_t total_rows) {
-  hipStream_t s = h->stream;
   // device views of every track's input and outputs
   std::vector<const float*> d_in(samples, samples + n_tracks);
   std::vector<Maps> d_out(n_tracks);
@@ -447,52 +485,11 @@ int queue_tracks(bp_handle h, int64_t n_tracks, const float* const* samples, con
       ((rc = take_track_out(h, total_rows, &all)) || (rc = stage_samples(h, n_tracks, samples, n_samples, total_samples, d_in.data()))))
     return rc;
   for (int64_t t = 0, ro = 0; t < n_tracks; ro += h_frames(h, n_samples[t++]))
-    d_out[t] = mem_kind == BP_MEM_HOST ? maps_at(all.note + ro * 440, h_frames(h, n_samples[t])) : Maps{note[t], onset[t], contour[t]};
-  std::vector<TrackSeg> segs;
-  int cur = 0;
-  auto for_groups = [&](auto&& fn) {
-    for (size_t g0 = 0; g0 < segs.size(); g0 += kMaxTrackSegs) {
-      TrackSegs ts{};
-      ts.n = (int)std::min<size_t>(kMaxTrackSegs, segs.size() - g0);
-      for (int k = 0; k < ts.n; ++k) ts.seg[k] = segs[g0 + k];
-      const int first = ts.seg[0].at, slots = ts.seg[ts.n - 1].at + ts.seg[ts.n - 1].n_windows - first;
-      for (int k = 0; k < ts.n; ++k) ts.seg[k].at -= first;  // slots relative to the group's first window
-      fn(ts, first, slots);
-    }
-  };
-  auto flush = [&]() -> int {
-    if (cur == 0) return BP_OK;
-    for_groups([&](const TrackSegs& ts, int first, int slots) {
-      launch_window_tracks(ts, slots, h->audio + (int64_t)first * h->win_len, h->win_len, h->hop, h->lead, s);
-    });
-    if ((rc = run_chunk(h, h->audio, cur, h->note, h->onset, h->contour))) return rc;
-    for_groups([&](const TrackSegs& ts, int first, int slots) {
-      launch_unwrap_tracks(ts, slots, h->note + (int64_t)first * kPlaneN, h->onset + (int64_t)first * kPlaneN,
-                           h->contour + (int64_t)first * kPlaneC, s);
-    });
-    segs.clear();
-    cur = 0;
-    return BP_OK;
-  };
-  for (int64_t t = 0; t < n_tracks; ++t) {
-    const int64_t n_win = h_windows(h, n_samples[t]);
-    const int64_t T = h_frames(h, n_samples[t]);
-    for (int64_t w0 = 0; w0 < n_win;) {
-      const int64_t room = h->cap - cur;
-      const int n = (int)((n_win - w0) < room ? (n_win - w0) : room);
-      segs.push_back(TrackSeg{d_in[t], {d_out[t].note, d_out[t].onset, d_out[t].contour}, n_samples[t], w0, T, n, cur});
-      cur += n;
-      w0 += n;
-      if (cur == h->cap && (rc = flush())) return rc;
-    }
-  }
-  if ((rc = flush())) return rc;
-  BP_HIP(hipGetLastError());
+    d_out[t] = mem_kind == BP_MEM_HOST ? maps_at(all.note + ro * kMapsRow, h_frames(h, n_samples[t])) : Maps{note[t], onset[t], contour[t]};
+  if ((rc = tracks_core(h, n_tracks, d_in.data(), n_samples, d_out.data()))) return rc;
   for (int64_t t = 0; t < n_tracks && mem_kind == BP_MEM_HOST; ++t) {
     const int64_t T = h_frames(h, n_samples[t]);
-    if (T > 0 && (rc = copy_maps(h, {note[t], onset[t], contour[t]}, d_out[t].note, d_out[t].onset, d_out[t].contour, T,
-                                 hipMemcpyDeviceToHost)))
-      return rc;
+    if (T > 0 && (rc = copy_maps(h, {note[t], onset[t], contour[t]}, d_out[t], T, hipMemcpyDeviceToHost))) return rc;
   }
   return BP_OK;
 }
@@ -580,7 +577,7 @@ int bp_track_maps(bp_handle h, int64_t n_frames, float* note, float* onset, floa
   }
   BP_HIP(hipSetDevice(h->device));
   const Maps m = maps_at(h->track_out, n_frames);
-  return finish(h, copy_maps(h, {note, onset, contour}, m.note, m.onset, m.contour, n_frames,
+  return finish(h, copy_maps(h, {note, onset, contour}, m, n_frames,
                              mem_kind == BP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
 }
 

@@ -155,7 +155,7 @@ def launches(trace_dir: str, n: int, steps: int) -> None:
     print("| kernel | launches | per step |\n|---|---|---|")
     total = 0
     for name, c in sorted(calls.items(), key=lambda kv: -kv[1]):
-        c_steps = c - n if "stream_downmix_kernel" in name else c
+        c_steps = c - n if "stream_mono_kernel" in name else c
         total += c_steps
         print(f"| `{name[:90]}` | {c} | {c_steps / steps:.2f} |")
     print(f"\nPer step: {total / steps:.2f} launches, of which {n} are the ingest of the {n} chunks (one per stream with input).")
