@@ -13,6 +13,7 @@ from . import build as _build
 
 BP_OK = 0
 BP_ERR_INVALID_ARG = -1
+BP_ERR_OUT_OF_MEMORY = -5
 BP_ERR_UNSUPPORTED = -6
 BP_MEM_HOST = 0
 BP_MEM_DEVICE = 1
@@ -212,6 +213,13 @@ EXPORTED_SYMBOLS = [
     "bp_stream_rows_bound",
     "bp_stream_state_bytes",
     "bp_stream_rows_after",
+]
+# every symbol include/basic_pitch_amd_live.h declares
+LIVE_SYMBOLS = [
+    "bp_stream_peek",
+    "bp_streams_peek",
+    "bp_stream_keep",
+    "bp_stream_candidates",
 ]
 
 _lib: Optional[C.CDLL] = None

@@ -129,4 +129,7 @@ struct Maps { float *note, *onset, *contour; };
 constexpr int64_t kMapsRow = 2 * kFreqN + kFreqC;  // floats of one row of all three
 inline Maps maps_at(float* base, int64_t T) { return {base, base + T * kFreqN, base + T * 2 * kFreqN}; }
 int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcpyKind kind);
+// the handle's tables of the device-side note candidates (note_device.hip), made on first use: the bend windows and the
+// Gaussian on the device, the page-locked copy of the stats record
+int note_tables(bp_handle h, const void** tab, const double** gauss);
 }  // namespace bp

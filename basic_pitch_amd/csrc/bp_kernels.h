@@ -144,5 +144,11 @@ void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, co
                         int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
                         void* stats_dst, hipStream_t s);
 void launch_note_stats_init(void* stats, hipStream_t s);
+// the three steps of launch_note_candidates on their own, for maps that grow (stream_api.hip): frames [t0, t1) join the
+// stats record; the bitmap of all T frames from a record; the bend map of T rows
+void launch_note_fold(float* note, float* onset, int64_t t0, int64_t t1, int lo, int hi, int infer, void* stats, hipStream_t s);
+void launch_note_peaks(const float* note, const float* onset, int64_t T, int infer, double onset_thresh, const void* stats,
+                       uint8_t* bits, hipStream_t s);
+void launch_note_bends(const float* contour, int64_t T, const void* tab, const double* gauss, int8_t* bend, hipStream_t s);
 
 }  // namespace bp

@@ -48,8 +48,11 @@ __global__ __launch_bounds__(64) void nd_stats_init_kernel(NdStats* st) {
 // Extrema of the two maps.  A wave walks frames (lanes take bins lane and lane + 64), a workgroup folds its four waves in
 // LDS and publishes ONE atomic per quantity (as first written, every frame's wave published its own: 15 k serialised
 // atomics per 3-minute track on three addresses, 0.36 ms — more than the CQT of the track).
-__global__ __launch_bounds__(256) void nd_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t T,
-                                                       int infer, NdStats* __restrict__ st) {
+// The range form: frames [t0, T) JOIN the record (maxima and the NaN flag only ever grow), the differences of a frame reach
+// back to frames t - 1 and t - 2 of the same maps whether or not those lie in the range — a record that has seen [0, a) and
+// then [a, b) equals one that has seen [0, b), which is what lets a stream carry it over its final rows.
+__global__ __launch_bounds__(256) void nd_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t t0,
+                                                       int64_t T, int infer, NdStats* __restrict__ st) {
   __shared__ float s_mo[4];
   __shared__ double s_fd[4];
   __shared__ int s_nan[4];
@@ -57,7 +60,7 @@ __global__ __launch_bounds__(256) void nd_stats_kernel(const float* __restrict__
   float mo = -__int_as_float(0x7f800000);
   double mfd = 0.0;
   int nan = 0;
-  for (int64_t t = (int64_t)blockIdx.x * 4 + wave; t < T; t += (int64_t)gridDim.x * 4) {
+  for (int64_t t = t0 + (int64_t)blockIdx.x * 4 + wave; t < T; t += (int64_t)gridDim.x * 4) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int f = lane + 64 * h;
@@ -257,22 +260,43 @@ __global__ __launch_bounds__(256) void nd_export_kernel(const uint32_t* __restri
   }
 }
 
+// Frames [t0, t1) of the device maps note / onset join the stats record: constrain_frequency on them (`lo`, `hi`: the bins
+// it keeps; 0, 88: none to zero), then their extrema.  Frames t0 - 1 and t0 - 2 are read (never written) when t0 > 0.
+void launch_note_fold(float* note, float* onset, int64_t t0, int64_t t1, int lo, int hi, int infer, void* stats, hipStream_t s) {
+  if (t1 <= t0) return;
+  const int64_t n = t1 - t0;
+  const unsigned frames4 = (unsigned)((n + 3) / 4);
+  if (lo > 0 || hi < kNdF)
+    hipLaunchKernelGGL(nd_constrain_kernel, dim3((unsigned)((n * kNdF + 255) / 256)), dim3(256), 0, s, note + t0 * kNdF,
+                       onset + t0 * kNdF, n * kNdF, lo, hi);
+  hipLaunchKernelGGL(nd_stats_kernel, dim3(frames4 < 512u ? frames4 : 512u), dim3(256), 0, s, note, onset, t0, t1, infer,
+                     static_cast<NdStats*>(stats));
+}
+
+// the onset-peak bitmap of all T frames ([T][12] bytes) from maps whose extrema `stats` holds
+void launch_note_peaks(const float* note, const float* onset, int64_t T, int infer, double onset_thresh, const void* stats,
+                       uint8_t* bits, hipStream_t s) {
+  if (T <= 0) return;
+  hipLaunchKernelGGL(nd_candidates_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, note, onset, T, infer, onset_thresh,
+                     static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
+}
+
+// the bend map of T contour rows ([T][88] bytes); a row's bends depend on that row alone
+void launch_note_bends(const float* contour, int64_t T, const void* tab, const double* gauss, int8_t* bend, hipStream_t s) {
+  if (T <= 0) return;
+  hipLaunchKernelGGL(nd_bend_kernel, dim3((unsigned)((T + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s, contour, T,
+                     static_cast<const int4*>(tab), gauss, bend);
+}
+
 // note / onset / contour: device maps of T frames.  Leaves the bitmap ([T][12] bytes), the bend map ([T][88] bytes, when
 // `bend` != null) and the stats on the device (the stats record must hold its initial values: launch_note_stats_init); `lo`, `hi`: the bins constrain_frequency keeps (0, 88: none to zero).
 void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,
                             double onset_thresh, const void* tab, const double* gauss, void* stats, uint8_t* bits,
                             int8_t* bend, hipStream_t s) {
   if (T <= 0) return;
-  NdStats* st = static_cast<NdStats*>(stats);
-  const unsigned frames4 = (unsigned)((T + 3) / 4);
-  if (lo > 0 || hi < kNdF)
-    hipLaunchKernelGGL(nd_constrain_kernel, dim3((unsigned)((T * kNdF + 255) / 256)), dim3(256), 0, s, note, onset, T * kNdF, lo, hi);
-  hipLaunchKernelGGL(nd_stats_kernel, dim3(frames4 < 512u ? frames4 : 512u), dim3(256), 0, s, note, onset, T, infer, st);
-  hipLaunchKernelGGL(nd_candidates_kernel, dim3(frames4), dim3(256), 0, s, note, onset, T, infer, onset_thresh, st,
-                     reinterpret_cast<uint32_t*>(bits));
-  if (bend)
-    hipLaunchKernelGGL(nd_bend_kernel, dim3((unsigned)((T + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s, contour, T,
-                       static_cast<const int4*>(tab), gauss, bend);
+  launch_note_fold(note, onset, 0, T, lo, hi, infer, stats, s);
+  launch_note_peaks(note, onset, T, infer, onset_thresh, stats, bits, s);
+  if (bend) launch_note_bends(contour, T, tab, gauss, bend, s);
 }
 
 void launch_note_stats_init(void* stats, hipStream_t s) {

@@ -1,4 +1,4 @@
-// C ABI of the streaming sessions (include/basic_pitch_amd.h): audio that arrives over time -> the rows of the un-overlapped
+// C ABI of the streaming sessions (include/basic_pitch_amd.h, include/basic_pitch_amd_live.h): audio that arrives over time -> the rows of the un-overlapped
 // posteriorgrams as they become final, for one stream or for many streams of one handle per step.
 //
 // A stream keeps on the device a ring of the model-rate signal that reaches back to the first sample of its oldest
@@ -15,12 +15,33 @@
 // gather_window / scatter_window); a resampled sample is one float64 sum over the same frames with the same taps in the
 // same order wherever the chunk boundaries fall, a window's samples depend on its index alone, and a window's result does
 // not depend on its batch or its slot.
+//
+// A step has three modes.  A push and a finish commit: the plan's copies of the counters become the stream's.  A PEEK is the
+// finish plan made on the same copies and never written back: "the rows a finish would emit now".  Its only trace on the
+// device is the tail of the model-rate signal (samples n_res up to the resampled length, their sums clipped at the last
+// frame) in the ring's free room beyond n_res:
+//   * the room always suffices — every step runs all complete windows, so the ring holds less than one window of samples
+//     afterwards and more than kRingHops hops are free, while the tail is at most centre / down + 2 samples (the samples whose
+//     filter reaches past the last frame); tail_fits() checks it before anything is queued;
+//   * a later push ingests from the stream's own n_res, which the peek left alone: it rewrites those ring positions with the
+//     complete sums before its windows are planned, and a window is gathered only up to the plan's n_res — no clipped,
+//     provisional sum can reach a final row.
+// The history buffers and cur_hist belong to the downmix of a chunk, and a peek has no chunk.
+//
+// bp_stream_keep adds to a stream the three maps of every final row (1,760 bytes per row) and a stats record that those rows
+// join as they are emitted (note_device.hip, launch_note_fold).  bp_stream_candidates puts the peek's rows behind them,
+// joins them to a copy of the record and leaves on the host what the note tracker needs: an update costs the tail's
+// windows, the bitmap of all rows (12 bytes each: it depends on both maxima and on the row count) and the note and bend
+// rows from `first_row` on — not the maps, and nothing else that grows with the session.
 #include <algorithm>
 #include <cstring>
 
 #include "bp_context.h"
+#include "../../include/basic_pitch_amd_live.h"
 
 using namespace bp;
+
+extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);  // note_decode.cpp
 
 struct bp_stream_state {
   bp_handle h = nullptr;
@@ -38,6 +59,18 @@ struct bp_stream_state {
   int64_t w_next = 0;    // first window that has not run
   int64_t rows_out = 0;  // rows emitted
   bool finished = false, broken = false;
+  // bp_stream_keep: the maps of the rows emitted so far ([keep_cap] note, onset, contour: max_rows + the room of a tail),
+  // frequency-constrained for `prm`, and behind them two stats records: of the kept rows, and of an update (kept + tail)
+  bool keep = false;
+  bp_note_params prm{};
+  int lo = 0, hi = 88;
+  int64_t max_rows = 0, keep_cap = 0;
+  float* kept = nullptr;
+#ifdef BP_AB_KERNELS
+  // bp_ab_stream_poison (the A/B library only): the cell of the kept copy that becomes a NaN when its row is written
+  int64_t ab_nan_row = -1;
+  int ab_nan_map = 0, ab_nan_bin = 0;
+#endif
 };
 
 namespace {
@@ -92,17 +125,51 @@ int stream_taps(bp_handle h, bp_stream_state* s) {
 }
 
 void free_stream(bp_stream_state* s) {
+  if (s->kept) (void)hipFree(s->kept);
   if (s->ring) (void)hipFree(s->ring);
   if (s->hist[0]) (void)hipFree(s->hist[0]);
   delete s;
 }
 
+// rows a peek can have: the windows that have not run when every complete one has are at most two (window > hop)
+constexpr int64_t kTailRows = 2 * BP_FRAMES_PER_WINDOW;
+constexpr int64_t kStatsFloats = 4;  // a stats record of note_device.hip: 16 bytes
+
+Maps kept_maps(const bp_stream_state* s) { return maps_at(s->kept, s->keep_cap); }
+Maps rows_from(const Maps& m, int64_t r) { return {m.note + r * kFreqN, m.onset + r * kFreqN, m.contour + r * kFreqC}; }
+void* kept_stats(const bp_stream_state* s, int which) { return s->kept + s->keep_cap * kMapsRow + which * kStatsFloats; }
+int64_t kept_bytes(const bp_stream_state* s) { return s->keep ? (s->keep_cap * kMapsRow + 2 * kStatsFloats) * 4 : 0; }
+
+// Test hook of the A/B library (bp_ab_stream_poison): rows [r0, r1) of the kept copy have just been written and have not
+// joined a stats record yet; the poisoned cell, if it lies in them, becomes a quiet NaN.  The product library has no such hook.
+#ifdef BP_AB_KERNELS
+int ab_poison(bp_handle h, const bp_stream_state* s, int64_t r0, int64_t r1) {
+  if (s->ab_nan_row < r0 || s->ab_nan_row >= r1) return BP_OK;
+  const Maps kept = kept_maps(s);
+  float* cell = (s->ab_nan_map ? kept.onset : kept.note) + s->ab_nan_row * kFreqN + s->ab_nan_bin;
+  BP_HIP(hipMemsetD32Async(cell, 0x7fc00000, 1, h->stream));
+  return BP_OK;
+}
+#else
+inline int ab_poison(bp_handle, const bp_stream_state*, int64_t, int64_t) { return BP_OK; }
+#endif
+
+// the tail of the signal a peek makes (samples n_res ... resampled length) fits the ring's free room: see the file header
+bool tail_fits(const bp_stream_state* s) {
+  bp_handle h = s->h;
+  const int64_t keep = std::max<int64_t>(0, s->w_next * h->hop - h->lead);
+  return bp_handle_resampled_length(h, s->n_in, s->sample_rate) - s->n_res <= s->ring_cap - (s->n_res - keep);
+}
+
 // ---- one step of n streams ------------------------------------------------------------------------------------------------
+enum Mode { kPush, kFinish, kPeek };
+
 struct Entry {
   bp_stream_state* s;
   const uint8_t* pcm;  // the chunk where the kernels read it (device)
   int64_t n_frames;
-  bool finish;
+  bool finish;         // planned as the end of the signal (a finish, a peek)
+  bool peek;           // ... on copies of the counters that are not written back
   Maps out;            // the rows of this call where the kernels write them (device)
   Maps user;
   int64_t rows;
@@ -226,15 +293,74 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
     launch_unwrap_streams(d_segs + r.seg0, r.n_segs, r.n_slots, h->note, h->onset, h->contour, q);
   }
   BP_HIP(hipGetLastError());
+  // streams that keep their maps: the final rows of this step go behind the kept ones and join the stats record
+  for (const Entry& e : es) {
+    const bp_stream_state* s = e.s;
+    if (!s->keep || e.peek || e.rows == 0) continue;
+    const Maps kept = kept_maps(s);
+    if ((rc = copy_maps(h, rows_from(kept, s->rows_out), e.out, e.rows, hipMemcpyDeviceToDevice))) return rc;
+    if ((rc = ab_poison(h, s, s->rows_out, s->rows_out + e.rows))) return rc;
+    launch_note_fold(kept.note, kept.onset, s->rows_out, s->rows_out + e.rows, s->lo, s->hi, s->prm.infer_onsets != 0,
+                     kept_stats(s, 0), q);
+    BP_HIP(hipGetLastError());
+  }
   for (const Entry& e : es)
     if (out_mem_kind == BP_MEM_HOST && e.rows > 0 && (rc = copy_maps(h, e.user, e.out, e.rows, hipMemcpyDeviceToHost))) return rc;
   return BP_OK;
 }
 
-// validate everything -> queue -> wait -> the streams' counters.  pcm / n_frames: NULL for finish.
+// An update of a stream that keeps its maps: the peek's rows behind the kept ones (device to device, nothing committed), a
+// copy of the stats record joined with them, the bitmap of all T rows, the bends of the rows from first_row on, and home.
+int queue_update(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t first_row, float* note_out, uint8_t* cand_bits,
+                 int8_t* bend_map, std::vector<WindowSeg>& segs) {
+  hipStream_t q = h->stream;
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  int rc = note_tables(h, &tab, &gauss);
+  if (rc) return rc;
+  const int64_t T = s->rows_out + tail_rows, n_new = T - first_row;
+  const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15, bend_bytes = n_new * kFreqN;
+  if ((rc = grow(h, &h->nd_buf, &h->nd_cap, (bits_room + bend_bytes + 3) / 4))) return rc;
+  uint8_t* d_bits = reinterpret_cast<uint8_t*>(h->nd_buf);
+  int8_t* d_bend = reinterpret_cast<int8_t*>(d_bits + bits_room);
+  const Maps kept = kept_maps(s);
+  if (tail_rows > 0) {
+    std::vector<Entry> es(1);
+    Entry& e = es[0];
+    e = Entry{};
+    e.s = s;
+    e.finish = e.peek = true;
+    e.rows = tail_rows;
+    e.user = rows_from(kept, s->rows_out);
+    e.n_res = s->n_res;
+    e.w_next = s->w_next;
+    e.n_total = bp_handle_resampled_length(h, s->n_in, s->sample_rate);
+    if ((rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
+  }
+  const int infer = s->prm.infer_onsets != 0;
+  const bool want_bends = s->prm.include_pitch_bends != 0 && bend_map != nullptr;
+  void* st = kept_stats(s, 1);
+  BP_HIP(hipMemcpyAsync(st, kept_stats(s, 0), kStatsFloats * 4, hipMemcpyDeviceToDevice, q));
+  if ((rc = ab_poison(h, s, s->rows_out, T))) return rc;
+  launch_note_fold(kept.note, kept.onset, s->rows_out, T, s->lo, s->hi, infer, st, q);
+  launch_note_peaks(kept.note, kept.onset, T, infer, s->prm.onset_threshold, st, d_bits, q);
+  if (want_bends) launch_note_bends(kept.contour + first_row * kFreqC, n_new, tab, gauss, d_bend, q);
+  BP_HIP(hipGetLastError());
+  BP_HIP(hipMemcpyAsync(h->nd_stats_host, st, kStatsFloats * 4, hipMemcpyDeviceToHost, q));
+  BP_HIP(hipMemcpyAsync(cand_bits, d_bits, (size_t)bits_bytes, hipMemcpyDeviceToHost, q));
+  if (n_new > 0) {
+    BP_HIP(hipMemcpyAsync(note_out + first_row * kFreqN, kept.note + first_row * kFreqN, (size_t)n_new * kFreqN * 4,
+                          hipMemcpyDeviceToHost, q));
+    if (want_bends) BP_HIP(hipMemcpyAsync(bend_map + first_row * kFreqN, d_bend, (size_t)bend_bytes, hipMemcpyDeviceToHost, q));
+  }
+  return BP_OK;
+}
+
+// validate everything -> queue -> wait -> the streams' counters (a peek leaves them).  pcm / n_frames: NULL for finish / peek.
 int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, const void* const* pcm, const int64_t* n_frames,
          int pcm_mem_kind, float* const* note, float* const* onset, float* const* contour, const int64_t* capacity_rows,
-         int out_mem_kind, int64_t* rows, bool finish_streams) {
+         int out_mem_kind, int64_t* rows, Mode mode) {
+  const bool finish_streams = mode != kPush;
   auto invalid = [&](const std::string& why) {
     h->err = std::string(what) + ": " + why;
     return BP_ERR_INVALID_ARG;
@@ -258,6 +384,7 @@ int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, con
     e = Entry{};
     e.s = s;
     e.finish = finish_streams;
+    e.peek = mode == kPeek;
     e.n_frames = finish_streams ? 0 : n_frames[i];
     if (e.n_frames < 0 || (e.n_frames > 0 && !pcm[i])) return invalid("negative n_frames or null pcm");
     e.rows = rows_of_step(s, e.n_frames, finish_streams);
@@ -265,11 +392,20 @@ int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, con
       return invalid("capacity_rows " + std::to_string(capacity_rows[i]) + " is too small for the " + std::to_string(e.rows) +
                      " rows of this step (bp_stream_rows_bound); nothing was taken from the stream");
     if (e.rows > 0 && (!note[i] || !onset[i] || !contour[i])) return invalid("null output pointer");
+    if (mode == kPeek && !tail_fits(s)) {
+      h->err = std::string(what) + ": the end of the resampled signal does not fit the stream's ring";
+      return BP_ERR_UNSUPPORTED;
+    }
+    if (mode != kPeek && s->keep && s->rows_out + e.rows > s->max_rows) {
+      h->err = std::string(what) + ": the " + std::to_string(e.rows) + " rows of this step would exceed the " +
+               std::to_string(s->max_rows) + " rows bp_stream_keep reserved; nothing was taken from the stream";
+      return BP_ERR_OUT_OF_MEMORY;
+    }
     e.user = {note[i], onset[i], contour[i]};
     e.n_res = s->n_res;
     e.w_next = s->w_next;
     e.n_total = finish_streams ? bp_handle_resampled_length(h, s->n_in, s->sample_rate) : -1;
-    work = work || e.n_frames > 0 || finish_streams;
+    work = work || e.n_frames > 0 || mode == kFinish || e.rows > 0;
   }
   if (work) {
     BP_HIP(hipSetDevice(h->device));
@@ -282,13 +418,14 @@ int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, con
   for (int64_t i = 0; i < n; ++i) {
     const Entry& e = es[(size_t)i];
     bp_stream_state* s = e.s;
+    rows[i] = e.rows;
+    if (mode == kPeek) continue;
     if (s->resamples && e.n_frames > 0) s->cur_hist ^= 1;
     s->n_in += e.n_frames;
     s->n_res = e.n_res;
     s->w_next = e.w_next;
     s->rows_out += e.rows;
     s->finished = finish_streams;
-    rows[i] = e.rows;
   }
   return BP_OK;
 }
@@ -346,7 +483,7 @@ void bp_stream_close(bp_stream s) {
   free_stream(s);
 }
 
-int64_t bp_stream_state_bytes(bp_stream s) { return s ? ((int64_t)s->ring_cap + 2 * (int64_t)s->n_hist) * 4 : 0; }
+int64_t bp_stream_state_bytes(bp_stream s) { return s ? ((int64_t)s->ring_cap + 2 * (int64_t)s->n_hist) * 4 + kept_bytes(s) : 0; }
 
 int64_t bp_stream_rows_bound(bp_stream s, int64_t n_frames) {
   if (!s || s->finished || n_frames < 0) return 0;
@@ -357,14 +494,27 @@ int bp_stream_push(bp_stream s, const void* pcm, int64_t n_frames, int pcm_mem_k
                    int64_t capacity_rows, int out_mem_kind, int64_t* rows) {
   if (!s) return BP_ERR_INVALID_ARG;
   return step(s->h, "bp_stream_push", 1, &s, &pcm, &n_frames, pcm_mem_kind, &note, &onset, &contour, &capacity_rows, out_mem_kind,
-              rows, false);
+              rows, kPush);
 }
 
 int bp_stream_finish(bp_stream s, float* note, float* onset, float* contour, int64_t capacity_rows, int out_mem_kind,
                      int64_t* rows) {
   if (!s) return BP_ERR_INVALID_ARG;
   return step(s->h, "bp_stream_finish", 1, &s, nullptr, nullptr, BP_MEM_HOST, &note, &onset, &contour, &capacity_rows,
-              out_mem_kind, rows, true);
+              out_mem_kind, rows, kFinish);
+}
+
+int bp_stream_peek(bp_stream s, float* note, float* onset, float* contour, int64_t capacity_rows, int out_mem_kind, int64_t* rows) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  return step(s->h, "bp_stream_peek", 1, &s, nullptr, nullptr, BP_MEM_HOST, &note, &onset, &contour, &capacity_rows, out_mem_kind,
+              rows, kPeek);
+}
+
+int bp_streams_peek(bp_handle h, int64_t n, const bp_stream* streams, float* const* note, float* const* onset,
+                    float* const* contour, const int64_t* capacity_rows, int out_mem_kind, int64_t* rows) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  return step(h, "bp_streams_peek", n, streams, nullptr, nullptr, BP_MEM_HOST, note, onset, contour, capacity_rows, out_mem_kind,
+              rows, kPeek);
 }
 
 int bp_streams_push(bp_handle h, int64_t n, const bp_stream* streams, const void* const* pcm, const int64_t* n_frames,
@@ -372,7 +522,84 @@ int bp_streams_push(bp_handle h, int64_t n, const bp_stream* streams, const void
                     const int64_t* capacity_rows, int out_mem_kind, int64_t* rows) {
   if (!h) return BP_ERR_INVALID_ARG;
   return step(h, "bp_streams_push", n, streams, pcm, n_frames, pcm_mem_kind, note, onset, contour, capacity_rows, out_mem_kind,
-              rows, false);
+              rows, kPush);
 }
+
+int bp_stream_keep(bp_stream s, const bp_note_params* params, int64_t max_rows) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  bp_handle h = s->h;
+  auto invalid = [&](const char* why) {
+    h->err = std::string("bp_stream_keep: ") + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (!params || max_rows <= 0) return invalid("null params or a max_rows that is not positive");
+  if (s->broken || s->finished) return invalid("a finished or broken stream");
+  if (s->keep) return invalid("the stream keeps its maps already (the decoding parameters are fixed by the first call)");
+  if (s->rows_out > 0) return invalid("rows have left the stream already: call it before the first window completes");
+  BP_HIP(hipSetDevice(h->device));
+  if (int rc = note_tables(h, nullptr, nullptr)) return rc;
+  const int64_t cap = max_rows + kTailRows;
+  if (cap > (int64_t)1 << 40) return invalid("max_rows is out of range");
+  BP_HIP(hipMalloc(&s->kept, (size_t)(cap * kMapsRow + 2 * kStatsFloats) * 4));
+  s->keep_cap = cap;
+  launch_note_stats_init(kept_stats(s, 0), h->stream);
+  if (int rc = finish(h, hipGetLastError() == hipSuccess ? BP_OK : BP_ERR_HIP)) {
+    (void)hipFree(s->kept);
+    s->kept = nullptr;
+    return rc;
+  }
+  s->prm = *params;
+  bp_internal_freq_limits(params, &s->lo, &s->hi);
+  s->max_rows = max_rows;
+  s->keep = true;
+  return BP_OK;
+}
+
+int bp_stream_candidates(bp_stream s, int with_tail, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int64_t first_row,
+                         int64_t capacity_rows, int64_t* n_rows, int* status) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  bp_handle h = s->h;
+  auto invalid = [&](const std::string& why) {
+    h->err = "bp_stream_candidates: " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (!n_rows || !status) return invalid("null n_rows / status");
+  if (!s->keep) return invalid("the stream does not keep its maps (bp_stream_keep)");
+  if (s->broken) return invalid("a stream whose earlier call failed on the device: only bp_stream_close is valid");
+  // every argument, before anything is queued.  A finished stream has no tail: its kept rows are the whole track.
+  const int64_t tail_rows = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
+  const int64_t T = s->rows_out + tail_rows;
+  if (first_row < 0 || first_row > s->rows_out)
+    return invalid("first_row " + std::to_string(first_row) + " is not in 0 ... " + std::to_string(s->rows_out) + ", the final rows");
+  if (capacity_rows < T)
+    return invalid("capacity_rows " + std::to_string(capacity_rows) + " is too small for the " + std::to_string(T) + " rows");
+  if (T > 0 && (!note_out || !cand_bits)) return invalid("null output pointer");
+  if (tail_rows > kTailRows || (tail_rows > 0 && !tail_fits(s))) {
+    h->err = "bp_stream_candidates: the end of the signal does not fit the stream's ring or the room behind the kept rows";
+    return BP_ERR_UNSUPPORTED;
+  }
+  *n_rows = T;
+  *status = s->prm.onset_threshold > 0.0 ? 0 : 1;
+  if (T == 0) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
+  if (int rc = finish(h, queue_update(h, s, tail_rows, first_row, note_out, cand_bits, bend_map, segs))) {
+    s->broken = true;
+    return rc;
+  }
+  if (reinterpret_cast<const int*>(h->nd_stats_host)[1]) *status = 1;  // a NaN in the maps: the host decodes the maps themselves
+  return BP_OK;
+}
+
+#ifdef BP_AB_KERNELS
+// The A/B library's test hook for the NaN path of a keeping stream (declared nowhere: the tests name it).  From now on the
+// cell (map: 0 note, 1 onset; absolute row; bin) of the KEPT copy is a NaN whenever its row is written there — as a row of
+// a tail at an update, as a final row at the step that emits it.  The rows handed to the caller are not touched.
+int bp_ab_stream_poison(bp_stream s, int map, int64_t row, int bin) {
+  if (!s || !s->keep || map < 0 || map > 1 || row < 0 || bin < 0 || bin >= kFreqN) return BP_ERR_INVALID_ARG;
+  s->ab_nan_map = map, s->ab_nan_row = row, s->ab_nan_bin = bin;
+  return BP_OK;
+}
+#endif
 
 }  // extern "C"

@@ -278,16 +278,10 @@ constexpr size_t kTabBytes = 88 * 16, kGaussBytes = 51 * 8, kStatsBytes = 16;
 int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params* prm, float* note_out, uint8_t* cand_out,
                      int8_t* bend_out, bool* exported_by_kernel) {
   hipStream_t s = h->stream;
-  if (!h->nd_tables) {
-    std::vector<float> raw((kTabBytes + kGaussBytes + kStatsBytes) / 4, 0.f);
-    bp_internal_bend_tables(reinterpret_cast<int32_t*>(raw.data()), reinterpret_cast<double*>(raw.data() + kTabBytes / 4));
-    int rc = upload(h, raw.data(), raw.size() * sizeof(float), &h->nd_tables);
-    if (rc) return rc;
-    BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->nd_stats_host), kStatsBytes, hipHostMallocPortable));
-    BP_HIP(hipHostGetDevicePointer(&h->nd_stats_host_dev, h->nd_stats_host, 0));
-  }
+  int rc = note_tables(h, nullptr, nullptr);
+  if (rc) return rc;
   const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bend_bytes = T * 88;  // multiples of 4
-  int rc = grow(h, &h->nd_buf, &h->nd_cap, (((bits_bytes + 15) & ~(int64_t)15) + bend_bytes + 3) / 4);
+  rc = grow(h, &h->nd_buf, &h->nd_cap, (((bits_bytes + 15) & ~(int64_t)15) + bend_bytes + 3) / 4);
   if (rc) return rc;
   uint8_t* d_bits = reinterpret_cast<uint8_t*>(h->nd_buf);
   int8_t* d_bend = reinterpret_cast<int8_t*>(d_bits + ((bits_bytes + 15) & ~(int64_t)15));
@@ -495,6 +489,20 @@ int queue_tracks(bp_handle h, int64_t n_tracks, const float* const* samples, con
 }
 
 }  // namespace
+
+int bp::note_tables(bp_handle h, const void** tab, const double** gauss) {
+  if (!h->nd_tables) {
+    std::vector<float> raw((kTabBytes + kGaussBytes + kStatsBytes) / 4, 0.f);
+    bp_internal_bend_tables(reinterpret_cast<int32_t*>(raw.data()), reinterpret_cast<double*>(raw.data() + kTabBytes / 4));
+    int rc = upload(h, raw.data(), raw.size() * sizeof(float), &h->nd_tables);
+    if (rc) return rc;
+    BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->nd_stats_host), kStatsBytes, hipHostMallocPortable));
+    BP_HIP(hipHostGetDevicePointer(&h->nd_stats_host_dev, h->nd_stats_host, 0));
+  }
+  if (tab) *tab = h->nd_tables;
+  if (gauss) *gauss = reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->nd_tables) + kTabBytes);
+  return BP_OK;
+}
 
 extern "C" {
 

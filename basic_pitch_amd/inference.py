@@ -395,6 +395,13 @@ class Model:
 
         return push_streams(self, streams, chunks)
 
+    def peek_streams(self, streams) -> "List[Dict[str, np.ndarray]]":
+        """`Stream.peek` for several of this model's streams in one step: the rows a finish would emit now for each of
+        them, nothing committed, their tail windows in full batches (bp_streams_peek)."""
+        from .streaming import peek_streams
+
+        return peek_streams(self, streams)
+
     # -- introspection ----------------------------------------------------------------------------
     def info(self) -> Dict[str, Any]:
         inf = _native.bp_info()

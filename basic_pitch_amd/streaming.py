@@ -4,6 +4,10 @@ The reference has no such interface (its `predict` takes a finished file); this 
 (include/basic_pitch_amd.h, csrc/stream_api.hip) behind `Model.open_stream`, `Model.push_streams` and
 `StreamingTranscriber`.  The rows a stream emits, concatenated, are bit for bit what `Model.predict_pcm_raw` returns for
 the concatenated input, for any chunking.
+
+Live use: `Stream.peek()` returns the rows a finish would emit now and commits nothing, so emitted rows + peeked rows are
+`predict_pcm_raw` of the audio so far at any moment; `StreamingTranscriber(live=True).transcript()` decodes the notes of the
+audio so far from what the device keeps (`bp_stream_keep`, `bp_stream_candidates`; include/basic_pitch_amd_live.h).
 """
 from __future__ import annotations
 
@@ -14,6 +18,7 @@ import numpy as np
 
 from . import _native
 from . import inference as _inf
+from . import note_creation as _notes
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
 _pi64 = C.POINTER(C.c_int64)
@@ -29,6 +34,13 @@ PROTOTYPES = {
     "bp_stream_state_bytes": (_i64, [_vp]),
     "bp_stream_rows_after": (_i64, [_i64, _int]),
 }
+# the same for include/basic_pitch_amd_live.h (tests/test_stream_peek_cpu.py compares)
+LIVE_PROTOTYPES = {
+    "bp_stream_peek": (_int, [_vp, _vp, _vp, _vp, _i64, _int, _pi64]),
+    "bp_streams_peek": (_int, [_vp, _i64, C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), C.POINTER(_vp), _pi64, _int, _pi64]),
+    "bp_stream_keep": (_int, [_vp, _vp, _i64]),
+    "bp_stream_candidates": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _i64, _pi64, _vp]),
+}
 
 # the numpy type a chunk of each format is made of (BP_PCM_S24: packed bytes)
 _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native.BP_PCM_S24: np.uint8,
@@ -36,8 +48,8 @@ _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Declare the streaming family's prototypes on a loaded library."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    """Declare the streaming family's prototypes (both headers) on a loaded library."""
+    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
@@ -129,6 +141,53 @@ class Stream:
         _native.check(self._lib, self._model._handle, rc, "bp_stream_finish")
         return self._taken(out, int(rows.value))
 
+    def peek(self) -> Dict[str, np.ndarray]:
+        """The rows `finish()` would return now, with nothing committed (`bp_stream_peek`): the rows emitted so far followed
+        by these are bit for bit `predict_pcm_raw` of the audio so far, and later pushes are unaffected."""
+        out = _inf._empty_maps((self.rows_bound(0),))
+        rows = C.c_int64(0)
+        rc = self._lib.bp_stream_peek(self._s, *[_inf._ptr(out[k]) for k, _ in _inf._MAPS], out["note"].shape[0],
+                                      _native.BP_MEM_HOST, C.byref(rows))
+        _native.check(self._lib, self._model._handle, rc, "bp_stream_peek")
+        return {k: v[: int(rows.value)] for k, v in out.items()}
+
+    def keep(self, prm: Any, max_rows: int) -> None:
+        """Keep the maps of every emitted row on the device for `candidates` (`bp_stream_keep`; before the first row leaves).
+        `prm`: `note_creation._note_params`, fixed from here on; `max_rows`: the rows reserved, 1,760 bytes each."""
+        rc = self._lib.bp_stream_keep(self._s, C.addressof(prm), int(max_rows))
+        _native.check(self._lib, self._model._handle, rc, "bp_stream_keep")
+
+    def candidates(self, note: np.ndarray, bits: np.ndarray, bend: Optional[np.ndarray], first_row: int,
+                   with_tail: bool = True) -> Tuple[int, int]:
+        """`bp_stream_candidates` into the caller's host arrays (note (cap, 88) float32, bits (cap, 12) uint8, bend (cap, 88)
+        int8 or None): rows from `first_row` on of note / bend, all rows of bits.  Returns (T, status)."""
+        n_rows, status = C.c_int64(0), C.c_int(0)
+        rc = self._lib.bp_stream_candidates(self._s, int(bool(with_tail)), note.ctypes.data, bits.ctypes.data,
+                                            bend.ctypes.data if bend is not None else None, int(first_row), note.shape[0],
+                                            C.byref(n_rows), C.addressof(status))
+        _native.check(self._lib, self._model._handle, rc, "bp_stream_candidates")
+        return int(n_rows.value), int(status.value)
+
+
+def _step_arrays(n: int):
+    return lambda vals: (C.c_void_p * n)(*vals)
+
+
+def peek_streams(model: "_inf.Model", streams: Sequence[Stream]) -> List[Dict[str, np.ndarray]]:
+    """`Stream.peek` for several streams of `model` in one step (`bp_streams_peek`): their tail windows run in full batches."""
+    n = len(streams)
+    if n == 0:
+        return []
+    lib = bind(model._lib)
+    outs = [_inf._empty_maps((s.rows_bound(0),)) for s in streams]
+    arr = _step_arrays(n)
+    rows = (C.c_int64 * n)()
+    rc = lib.bp_streams_peek(model._handle, n, arr([s._s.value for s in streams]),
+                             *[arr([_inf._ptr(o[k]) for o in outs]) for k, _ in _inf._MAPS],
+                             (C.c_int64 * n)(*[o["note"].shape[0] for o in outs]), _native.BP_MEM_HOST, rows)
+    _native.check(lib, model._handle, rc, "bp_streams_peek")
+    return [{k: v[: int(r)] for k, v in o.items()} for o, r in zip(outs, rows)]
+
 
 def push_streams(model: "_inf.Model", streams: Sequence[Stream], chunks: Sequence[Any]) -> List[Dict[str, np.ndarray]]:
     """One step for several streams of `model` (`bp_streams_push`): each stream's chunk is ingested, the newly complete
@@ -141,7 +200,7 @@ def push_streams(model: "_inf.Model", streams: Sequence[Stream], chunks: Sequenc
     lib = bind(model._lib)
     parts = [s._chunk(c) for s, c in zip(streams, chunks)]
     outs = [_inf._empty_maps((s.rows_bound(k),)) for s, (_, k) in zip(streams, parts)]
-    arr = lambda vals: (C.c_void_p * n)(*vals)  # noqa: E731
+    arr = _step_arrays(n)
     rows = (C.c_int64 * n)()
     rc = lib.bp_streams_push(
         model._handle, n, arr([s._s.value for s in streams]), arr([b.ctypes.data if k else None for b, k in parts]),
@@ -157,9 +216,16 @@ class StreamingTranscriber:
     """`predict()` for audio that arrives in chunks: `push(chunk)` feeds a stream and keeps the emitted rows on the host,
     `finish()` returns `(model_output, midi_data, note_events)` exactly as `predict()` does for the same audio.
 
-    Note decoding stays a whole-track step at `finish()`: the melodia pass of `output_to_notes_polyphonic` walks the whole
-    posteriorgram, so a note is only known once the track is.  Incremental note events are out of scope; what arrives
-    incrementally are the posteriorgram rows (`push` returns them)."""
+    With `live=True`, `transcript()` returns `(midi_data, note_events)` for the audio pushed so far — exactly what `predict()`
+    returns for that prefix — at any moment between pushes.  The stream then keeps its maps on the device
+    (`bp_stream_keep`; `max_rows` rows of 1,760 bytes are reserved in device memory when the transcriber is made — the
+    default, 52,200 rows, is ten minutes of audio and 92 MB; an hour is 313,200 rows and 551 MB — and a push past them
+    raises), an update sends only the note and
+    bend rows that are new since the last one plus the 12-byte-per-row peak bitmap, and the sequential half of the decoder
+    runs on the host (`bp_notes_decode_candidates`).  Events are NOT final until `finish()`: `get_infered_onsets` scales the
+    note-map differences by two maxima taken over the whole track and the melodia pass walks the whole posteriorgram, so an
+    event of an earlier transcript can move or vanish when later audio arrives.  What is exact at every update is the answer
+    to "what if the audio ended now"."""
 
     def __init__(
         self,
@@ -175,16 +241,60 @@ class StreamingTranscriber:
         multiple_pitch_bends: bool = False,
         melodia_trick: bool = True,
         midi_tempo: float = _inf.DEFAULT_MINIMUM_MIDI_TEMPO,
+        live: bool = False,
+        max_rows: int = 600 * 87,
     ):
         self._decoding = (onset_threshold, frame_threshold, minimum_note_length, minimum_frequency, maximum_frequency,
                           multiple_pitch_bends, melodia_trick, midi_tempo)
         self.stream = Stream(_inf._model_from(model_or_model_path), sample_rate, channels, fmt)
         self._rows: List[Dict[str, np.ndarray]] = []
+        self.live = bool(live)
+        if self.live:
+            # the parameters model_output_to_notes decodes with (note_creation.py:52-116 defaults: inferred onsets, pitch bends)
+            self._prm = _notes._note_params(onset_threshold, frame_threshold, _inf._min_note_len_frames(minimum_note_length), True,
+                                            maximum_frequency, minimum_frequency, melodia_trick, _notes.ENERGY_TOLERANCE, True)
+            self.stream.keep(self._prm, max_rows)
+            self._held = 0  # final rows of the note and bend maps already on the host
+            self._note = np.empty((0, _inf.N_FREQ_BINS_NOTES), np.float32)
+            self._bend = np.empty((0, _inf.N_FREQ_BINS_NOTES), np.int8)
+            self._bits = np.empty((0, 12), np.uint8)
 
     def push(self, chunk: Any) -> Dict[str, np.ndarray]:
         out = self.stream.push(chunk)
         self._rows.append(out)
         return out
+
+    def _room(self, rows: int) -> None:
+        """Host note / bend / bitmap arrays of at least `rows` rows, the held final rows carried over."""
+        if rows <= self._note.shape[0]:
+            return
+        cap = max(rows, 2 * self._note.shape[0], 1024)
+        for name in ("_note", "_bend", "_bits"):
+            old = getattr(self, name)
+            new = np.empty((cap, old.shape[1]), old.dtype)
+            new[: self._held] = old[: self._held]
+            setattr(self, name, new)
+
+    def transcript(self):
+        """`(midi_data, note_events)` of the audio pushed so far, as `predict()` returns them for that audio."""
+        if not self.live:
+            raise ValueError("transcript() needs StreamingTranscriber(live=True)")
+        s = self.stream
+        multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
+        status = 1  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
+        if self._prm.onset_threshold > 0:
+            self._room(s.rows + s.rows_bound(0))
+            T, status = s.candidates(self._note, self._bits, self._bend, self._held)
+            self._held = s.rows  # rows at or after it were a tail's: sent again next time
+        if status == 0:
+            events = _notes.decode_candidates(self._note[:T], self._bits[:T], self._bend[:T], self._prm)
+            return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+        # a NaN in the maps or an onset threshold <= 0: numpy's rules, the host decodes the maps themselves.  (After a NaN the
+        # tail's windows run a second time here: the update wrote them behind the kept rows, frequency-constrained, and the
+        # decoder needs the rows as the caller gets them.  The price of a broken input, not of an update.)
+        parts = self._rows + [s.peek()]
+        model_output = {k: np.ascontiguousarray(np.concatenate([r[k] for r in parts])) for k, _ in _inf._MAPS}
+        return _inf._output_to_notes(model_output, *self._decoding)
 
     def finish(self):
         self._rows.append(self.stream.finish())

@@ -463,6 +463,10 @@ int bp_notes_decode_candidates(const float* note, const uint8_t* cand_bits, cons
                                int64_t max_bends, int64_t* n_events, int64_t* n_bends);
 const char* bp_notes_last_error(void);
 
+/* Live transcripts of a stream — the rows a finish would emit now with nothing committed, the maps of the emitted rows kept
+ * on the device, and what note decoding needs of the audio so far — are declared in basic_pitch_amd_live.h, which includes
+ * this header. */
+
 /* ---- whole files, natively: decode -> posteriorgrams -> note events -> .mid / .csv (host C++ threads) ----------
  * Replaces the per-file Python loop of predict_and_save (basic_pitch/inference.py:509-604) for WAV and FLAC input:
  * librosa.load (239: decode; downmix + resampling on the device), run_inference (282-330), model_output_to_notes

@@ -3,6 +3,8 @@
     python tools/stream_latency.py --out profiles/stream_latency.md       # the wall-time tables (a) and (b)
     rocprofv3 --kernel-trace --stats -d DIR -- python tools/stream_latency.py --trace 64 20
     python tools/stream_latency.py --launches DIR 64 20                   # (c): kernel launches per step from that trace
+    python tools/stream_latency.py --peek --out profiles/stream_peek_latency.md   # (d): a live session, per update
+    python tools/stream_latency.py --push-only [--package DIR]            # (d)'s push-only row; DIR: another checkout's root
 
 The yardstick is existing code in the same process on the same device: `bp_infer` with host buffers on the same number of
 windows in one call.  Every stream is a 22.05 kHz mono float stream primed with 3840 samples, so that each further push of
@@ -22,7 +24,9 @@ import time
 
 import numpy as np
 
-sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+# --package DIR: the basic_pitch_amd of another checkout (built there), e.g. the parent commit's for a same-box comparison
+_pkg = sys.argv[sys.argv.index("--package") + 1] if "--package" in sys.argv[:-1] else os.path.join(os.path.dirname(os.path.abspath(__file__)), "..")
+sys.path.insert(0, os.path.abspath(_pkg))
 
 HOP, WIN, LEAD = 36164, 43844, 3840
 
@@ -133,6 +137,91 @@ def tables(out_path: str) -> None:
             f.write(text)
 
 
+def live_signal(seconds: float) -> np.ndarray:
+    """A seeded melody of decaying three-partial tones, 22.05 kHz mono float: notes for the decoder to find."""
+    rng = np.random.default_rng(3)
+    n = int(seconds * 22050)
+    x = 1e-3 * rng.standard_normal(n)
+    for a in range(0, n, 22050 // 3):
+        t = np.arange(min(22050 // 3, n - a)) / 22050.0
+        f0 = 220.0 * 2 ** (int(rng.integers(0, 24)) / 12.0)
+        x[a : a + t.size] += sum(0.3 / h * np.sin(2 * np.pi * f0 * h * t) for h in (1, 2, 3)) * np.exp(-3.0 * t)
+    return x.astype(np.float32)
+
+
+def push_only_times(model, x: np.ndarray, chunk: int) -> list:
+    """Wall time of every `Stream.push` of a session that only pushes (ms)."""
+    times = []
+    with model.open_stream(22050) as s:
+        for a in range(0, len(x), chunk):
+            t0 = time.perf_counter()
+            s.push(x[a : a + chunk])
+            times.append(1e3 * (time.perf_counter() - t0))
+    return times
+
+
+def push_only(sessions: int = 3, updates: int = 120, chunk_s: float = 0.25) -> None:
+    """The push-only row of (d) on its own, with nothing but `Model.open_stream` and `Stream.push`: runs on any commit that
+    has streams (--package), so the same box can time the commit before a change to the push path beside the one after."""
+    import basic_pitch_amd
+    from basic_pitch_amd import Model
+
+    model = Model(max_windows=8)
+    chunk = int(chunk_s * 22050)
+    x = live_signal(updates * chunk_s)
+    push_only_times(model, x[: 20 * chunk], chunk)
+    print(f"package: {os.path.dirname(os.path.abspath(basic_pitch_amd.__file__))}")
+    print("| session | median ms | worst ms |\n|---|---|---|")
+    for i in range(sessions):
+        t = push_only_times(model, x, chunk)
+        print(f"| push only, {len(t)} pushes, run {i} | {statistics.median(t):.3f} | {max(t):.3f} |")
+    model.close()
+
+
+def peek_table(out_path: str, updates: int = 120, chunk_s: float = 0.25) -> None:
+    """(d) A live session: 0.25-second chunks of a 22.05 kHz mono float stream; after every push a `Stream.peek()` (the rows
+    of the audio so far) and a `StreamingTranscriber.transcript()` (its note events).  Wall times at the Python interface,
+    which is where a live user stands; a session that only pushes, on the same chunks, beside it."""
+    from basic_pitch_amd import Model
+    from basic_pitch_amd.streaming import StreamingTranscriber
+
+    model = Model(max_windows=8)
+    chunk = int(chunk_s * 22050)
+    x = live_signal(updates * chunk_s)
+    push_only_times(model, x[: 20 * chunk], chunk)  # warm-up: allocations, the first launches
+    base = push_only_times(model, x, chunk)
+    t_push, t_peek, t_tr, n_events, tail_rows = [], [], [], 0, []
+    with StreamingTranscriber(model, 22050, live=True) as t:
+        for a in range(0, len(x), chunk):
+            t0 = time.perf_counter()
+            t.push(x[a : a + chunk])
+            t1 = time.perf_counter()
+            tail = t.stream.peek()
+            t2 = time.perf_counter()
+            _, events = t.transcript()
+            t3 = time.perf_counter()
+            t_push.append(1e3 * (t1 - t0)), t_peek.append(1e3 * (t2 - t1)), t_tr.append(1e3 * (t3 - t2))
+            tail_rows.append(tail["note"].shape[0])
+            n_events = len(events)
+    row = lambda name, v: f"| {name} | {statistics.median(v):.3f} | {max(v):.3f} |"  # noqa: E731
+    lines = ["# A live session, per update (tools/stream_latency.py --peek)", "",
+             f"{len(t_push)} updates of {chunk_s} s ({chunk} samples, 22.05 kHz mono float32 from pageable host memory), handle of 8",
+             "windows, wall time in ms at the Python interface; every call ends in the library's wait for the device.  A peek runs",
+             f"the one or two tail windows ({min(tail_rows)} to {max(tail_rows)} rows here); `transcript()` runs them again behind the",
+             "kept maps, the stats fold, the peak bitmap of all rows and the bends of the new rows, then the host's note tracker",
+             f"({n_events} events at the last update, {updates * chunk_s:.0f} s of audio).  No time is gated.", "",
+             "| call | median | worst |", "|---|---|---|",
+             row("`push` in a session that only pushes", base), row("`push` in the live session (rows kept on the device)", t_push),
+             row("`Stream.peek()`", t_peek), row("`StreamingTranscriber.transcript()`", t_tr), ""]
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+    model.close()
+
+
 def trace(n: int, steps: int) -> None:
     """The traced program: n primed streams, `steps` steps of one window each (run it under rocprofv3)."""
     b = Bench()
@@ -166,8 +255,15 @@ if __name__ == "__main__":
     ap.add_argument("--out", default="")
     ap.add_argument("--trace", nargs=2, type=int, metavar=("N", "STEPS"))
     ap.add_argument("--launches", nargs=3, metavar=("DIR", "N", "STEPS"))
+    ap.add_argument("--peek", action="store_true", help="(d): push, peek and transcript() per update of a live session")
+    ap.add_argument("--push-only", action="store_true", help="the push-only sessions of (d) alone")
+    ap.add_argument("--package", default="", help="root of the checkout whose basic_pitch_amd is timed (default: this one)")
     a = ap.parse_args()
-    if a.trace:
+    if a.push_only:
+        push_only()
+    elif a.peek:
+        peek_table(a.out)
+    elif a.trace:
         trace(*a.trace)
     elif a.launches:
         launches(a.launches[0], int(a.launches[1]), int(a.launches[2]))
