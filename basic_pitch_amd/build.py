@@ -52,7 +52,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

@@ -1,6 +1,7 @@
 // Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip, stream_api.hip and weight_pack.hip share
-// of it — the HIP error macro, the workspace / chunk / wait helpers (defined in bp_api.hip), and the maps, filter and argument
-// helpers of the track calls and the streaming sessions (defined in track_api.hip).
+// of it — the HIP error macro, the chunk / wait helpers (defined in bp_api.hip), and the maps, filter and argument
+// helpers of the track calls and the streaming sessions (defined in track_api.hip).  The handle's memory is owned by the
+// buffers of device_buffer.h: deleting the handle frees it.
 #pragma once
 #include "../../include/basic_pitch_amd.h"
 
@@ -28,58 +29,58 @@ struct bp_context {
 
   bp::LogConsts kc{};
   float b_contour2 = 0, b_note2 = 0, b_onset2 = 0;
+  // Every allocation of the handle is a buffer that frees itself (device_buffer.h).  The operand tables weight_pack.hip
+  // packs are raw bytes (PackedWeights::tables names them by member pointer): f16 fragments go to the launchers as they
+  // are, fp32 tables through as<float>().
+  using Table = bp::DeviceBuffer<uint8_t>;
+  template <class T>
+  using Buffer = bp::DeviceBuffer<T>;
   // device constants
-  float *d_lowpass = nullptr, *d_sqrt_len = nullptr, *d_fb_bfrag = nullptr;
-  float* d_pl_bin_k = nullptr;  // cqt_planes.hip filterbank: per-bin eps / s^2, s = sqrt(len) 2^-12
-  // fused branches (conv_branch.hip): f16 hi/lo A fragments (raw bytes) + {bias1[32], extra[9], bias2}
-  float *d_note_wfrag = nullptr, *d_note_w16 = nullptr, *d_note_wf32 = nullptr, *d_onset_wfrag = nullptr, *d_onset_wf32 = nullptr,
-        *d_onset_w16 = nullptr;
-  float* zp = nullptr;  // uint32 [cap][kZRowsP][kZRow] pre-split z, zero padded (bp_common.h)
+  Table d_lowpass, d_sqrt_len, d_fb_bfrag;
+  Table d_pl_bin_k;  // cqt_planes.hip filterbank: per-bin eps / s^2, s = sqrt(len) 2^-12
+  // fused branches (conv_branch.hip): f16 hi/lo A fragments + {bias1[32], extra[9], bias2}
+  Table d_note_wfrag, d_note_w16, d_note_wf32, d_onset_wfrag, d_onset_wf32, d_onset_w16;
+  Buffer<uint32_t> zp;  // [cap][kZRowsP][kZRow] pre-split z, zero padded (bp_common.h)
   // contour branch: conv1 A fragments (interior march, round-2 folded, rim GEMM, rim march), bias[8], conv2 taps [5][5][8]
-  float *d_d1_wfold = nullptr, *d_d1_wmarch = nullptr, *d_d1_wrim = nullptr, *d_d1_wrimm = nullptr, *d_d1_bias = nullptr,
-        *d_d2_w = nullptr, *d_d2_wproj = nullptr;
+  Table d_d1_wfold, d_d1_wmarch, d_d1_wrim, d_d1_wrimm, d_d1_bias, d_d2_w, d_d2_wproj;
   int resample_mode = 0;  // BP_RESAMPLE=plain|tiled: 1 | 2 (A/B runs of the resampling kernels)
-  float* c1s = nullptr;  // [cap][172][kC1Row][8] relu(conv1); pad bins zeroed once at allocation
-  // cqt_planes.hip: decimator / filterbank fragments (raw bytes of f16 hi / lo), the planes of a chunk [cap][2][stride] f16
-  float *d_pl_tfrag = nullptr, *d_pl_bfrag = nullptr, *planes = nullptr;
-  float *d_c1_bfrag = nullptr, *d_c1_bias = nullptr, *d_o1_bfrag = nullptr, *d_o1_bias = nullptr;
-  float *d_n1_bfrag = nullptr, *d_n1_bias = nullptr, *d_w_contour2 = nullptr, *d_w_note2 = nullptr,
-        *d_w_onset2 = nullptr;
+  Buffer<float> c1s;  // [cap][172][kC1Row][8] relu(conv1); pad bins zeroed once at allocation
+  // cqt_planes.hip: decimator / filterbank fragments (f16 hi / lo), the planes of a chunk [cap][2][stride] f16
+  Table d_pl_tfrag, d_pl_bfrag;
+  Buffer<uint16_t> planes;
+  Table d_c1_bfrag, d_c1_bias, d_o1_bfrag, d_o1_bias;
+  Table d_n1_bfrag, d_n1_bias, d_w_contour2, d_w_note2, d_w_onset2;
   // workspace (per chunk of `cap` windows)
-  float *audio = nullptr, *pyr = nullptr, *lp = nullptr, *c1 = nullptr, *contour = nullptr, *n1 = nullptr,
-        *note = nullptr, *o1 = nullptr, *onset = nullptr;
-  int* mm = nullptr;
-  float* fb_scratch = nullptr;  // filterbank partial extrema (grow-only; >= cap windows)
-  int64_t fb_scratch_windows = 0;
+  Buffer<float> audio, pyr, lp, c1, contour, n1, note, o1, onset;
+  Buffer<int> mm;
+  Buffer<float> fb_scratch;  // filterbank partial extrema (grow-only; >= cap windows)
   // track path staging (grow-only)
-  float* track = nullptr;
-  int64_t track_cap = 0;
-  // audio ingest (audio_ingest.hip): staging for PCM / mono / 22.05 kHz signal (grow-only), cached filter
-  float *pcm_dev = nullptr, *mono_dev = nullptr, *res_dev = nullptr;
-  int64_t pcm_cap = 0, mono_cap = 0, res_cap = 0;
-  double* taps_dev = nullptr;
+  Buffer<float> track;
+  // audio ingest (audio_ingest.hip): staging for PCM (bytes) / mono / 22.05 kHz signal (grow-only), cached filter
+  Buffer<uint8_t> pcm_dev;
+  Buffer<float> mono_dev, res_dev;
+  Buffer<double> taps_dev;
   int taps_rate = 0;
   bp::ResamplePlan plan{};
-  float* track_out = nullptr;  // [T, 88+88+264] staging when outputs are host pointers
-  int64_t track_out_cap = 0;
-  int64_t maps_rows = 0;       // rows of the maps a *_candidates call left in track_out (bp_track_maps); 0: none
-  // device-side note candidates (note_device.hip): bitmap [T][11] + bend map [T][88] (bytes), stats, the bend tables
-  float* nd_buf = nullptr;
-  int64_t nd_cap = 0;          // floats
-  float* nd_tables = nullptr;  // [88] int4 windows, [51] double Gaussian, then the stats record
+  Buffer<float> track_out;  // [T, 88+88+264] staging when outputs are host pointers
+  int64_t maps_rows = 0;    // rows of the maps a *_candidates call left in track_out (bp_track_maps); 0: none
+  // device-side note candidates (note_device.hip): bitmap [T][11] + bend map [T][88], the bend tables with the stats record
+  Buffer<uint8_t> nd_buf;
+  Table nd_tables;                     // [88] int4 windows, [51] double Gaussian, then the stats record
   bp::FlacDeviceBuffers fd;            // flac_device.hip: the file's bytes, the frame lists, the scratch rows
-  int* fd_status_host = nullptr;   // page-locked: the device decoder's error bits of the last call
-  float* nd_stats_host = nullptr;  // page-locked copy of the stats record
+  bp::PinnedBuffer<int> fd_status_host;  // the device decoder's error bits of the last call
+  bp::PinnedBuffer<int> nd_stats_host;   // copy of the stats record (4 words; [1]: a NaN was seen)
   void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
   bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.
-  float *st_pcm = nullptr, *st_mono = nullptr, *st_out = nullptr, *st_segs = nullptr;
-  int64_t st_pcm_cap = 0, st_mono_cap = 0, st_out_cap = 0, st_segs_cap = 0;
+  Buffer<uint8_t> st_pcm;
+  Buffer<float> st_mono, st_out;
+  Buffer<bp::WindowSeg> st_segs;
   struct StreamTaps {
     int rate;
-    double* dev;
+    Buffer<double> dev;
     bp::ResamplePlan plan;
   };
   std::vector<StreamTaps> st_taps;
@@ -93,9 +94,17 @@ struct bp_context {
   // stage id of the interval between ev[c][i] and ev[c][i+1]; -1: not a stage (skipped)
   int seq[kTimedRing][kMaxMarks] = {};
   int n_seq[kTimedRing] = {};
-  bool ev_valid = false;
   int64_t timed_chunks = 0;  // chunks recorded since the last bp_get_stage_ms
   int64_t dom_chunks = 0;    // chunks seen in BP_FLAG_TIME_DOMINANT mode (every kDomEvery-th is recorded)
+
+  // what is not memory; the buffers free themselves after it.  The handle's device is current (bp_destroy, bp_create).
+  ~bp_context() {
+    for (auto& row : ev)
+      for (auto& e : row)
+        if (e) (void)hipEventDestroy(e);
+    if (done) (void)hipEventDestroy(done);
+    if (own_stream) (void)hipStreamDestroy(own_stream);
+  }
 };
 
 #define BP_HIP(call)                                                                       \
@@ -111,9 +120,6 @@ struct bp_context {
   } while (0)
 
 namespace bp {
-int upload(bp_handle h, const void* host, size_t bytes, float** dev);
-int alloc(bp_handle h, float** p, int64_t floats);
-int grow(bp_handle h, float** buf, int64_t* cap, int64_t need);
 int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float* onset_dev, float* contour_dev);
 int wait_stream(bp_handle h);
 // track_api.hip: the end of a call that has queued work, and the argument domain of raw PCM
@@ -121,9 +127,9 @@ int finish(bp_handle h, int rc);
 int pcm_width(int format);
 int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int channels, int sample_rate, int mem_kind);
 // the resampling filter sample_rate -> the handle's rate on the device: the plan, the table (with the 2 : 1 kernel's reversed
-// copy behind it) in a new allocation at *dev.  tabulated_only: a plan whose taps are evaluated in the kernel is returned
+// copy behind it) in *dev, which owns it.  tabulated_only: a plan whose taps are evaluated in the kernel is returned
 // in *plan with BP_ERR_UNSUPPORTED, nothing allocated and no message set.
-int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePlan* plan, double** dev);
+int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePlan* plan, DeviceBuffer<double>* dev);
 // the three maps of T rows: [T][88] note, [T][88] onset, [T][264] contour — one after the other when they share a block
 struct Maps { float *note, *onset, *contour; };
 constexpr int64_t kMapsRow = 2 * kFreqN + kFreqC;  // floats of one row of all three

@@ -5,6 +5,7 @@
 #include <vector>
 
 #include "bp_common.h"
+#include "device_buffer.h"
 
 namespace bp {
 
@@ -119,22 +120,14 @@ struct FdStream {
   uint32_t audio_start, nbytes;
 };
 struct FlacDeviceBuffers {
-  uint8_t* file = nullptr;      // the file's bytes + 64 zero bytes
-  size_t file_cap = 0;
-  void* cands = nullptr;        // FdCand [chunks][kFdChunkCands]
-  uint32_t* counts = nullptr;
-  size_t cands_cap = 0, counts_cap = 0;
-  void* packed = nullptr;       // FdCand, in file order
-  uint32_t* offs = nullptr;
-  size_t packed_cap = 0, offs_cap = 0;
-  void* frames = nullptr;       // FdFrame
-  int32_t* scratch = nullptr;
-  size_t frames_cap = 0, scratch_cap = 0;
-  int* meta = nullptr;          // [0] status, [1] n_frames
-  uint16_t* crc_tab = nullptr;
+  DeviceBuffer<uint8_t> file;                   // the file's bytes + 64 zero bytes
+  DeviceBuffer<uint8_t> cands, packed, frames;  // FdCand [chunks][kFdChunkCands]; FdCand, in file order; FdFrame
+  DeviceBuffer<uint32_t> counts, offs;
+  DeviceBuffer<int32_t> scratch;
+  DeviceBuffer<int> meta;                       // [0] status, [1] n_frames
+  DeviceBuffer<uint16_t> crc_tab;
 };
 int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream);
-void flac_device_free(FlacDeviceBuffers& b);
 
 // note_device.hip
 void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,

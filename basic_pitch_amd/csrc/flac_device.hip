@@ -967,14 +967,10 @@ __global__ __launch_bounds__(256) void flac_finalize_kernel(FdDecodeParams p) {
 }
 
 // ---- host side --------------------------------------------------------------------------------------------------------------------
-static int fd_grow(void** p, size_t* cap, size_t want, size_t elem) {
-  if (want <= *cap) return 0;
-  if (*p) (void)hipFree(*p);
-  *p = nullptr, *cap = 0;
-  const size_t n = want + want / 4 + 64;
-  if (hipMalloc(p, n * elem) != hipSuccess) return -1;
-  *cap = n;
-  return 0;
+// Room for `want` items of `elem` elements each, with a quarter of slack when it grows: files of similar length reuse it.
+template <class T>
+static bool fd_reserve(DeviceBuffer<T>& b, size_t want, size_t elem = 1) {
+  return want * elem <= b.capacity() || b.reserve((want + want / 4 + 64) * elem) == hipSuccess;
 }
 
 // Decode the FLAC stream at `d_file` (already on the device, padded with >= 64 zero bytes) into interleaved PCM at `d_pcm`
@@ -982,14 +978,12 @@ static int fd_grow(void** p, size_t* cap, size_t want, size_t elem) {
 int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream) {
   const int n_chunks = (int)((st.nbytes - st.audio_start + kFdChunk - 1) / kFdChunk);
   const int64_t max_frames = (st.total + st.min_block - 1) / st.min_block + 1;
-  if (fd_grow(&b.cands, &b.cands_cap, (size_t)n_chunks * kFdChunkCands, sizeof(FdCand))) return -1;
-  if (fd_grow(reinterpret_cast<void**>(&b.counts), &b.counts_cap, (size_t)n_chunks, sizeof(uint32_t))) return -1;
-  if (fd_grow(&b.packed, &b.packed_cap, (size_t)n_chunks * kFdChunkCands, sizeof(FdCand))) return -1;
-  if (fd_grow(reinterpret_cast<void**>(&b.offs), &b.offs_cap, (size_t)n_chunks, sizeof(uint32_t))) return -1;
-  if (fd_grow(&b.frames, &b.frames_cap, (size_t)max_frames, sizeof(FdFrame))) return -1;
-  const size_t rows = (size_t)max_frames * st.max_block * st.channels;
-  if (fd_grow(reinterpret_cast<void**>(&b.scratch), &b.scratch_cap, rows, sizeof(int32_t))) return -1;
-  if (!b.meta && hipMalloc(&b.meta, 2 * sizeof(int)) != hipSuccess) return -1;
+  if (!fd_reserve(b.cands, (size_t)n_chunks * kFdChunkCands, sizeof(FdCand)) || !fd_reserve(b.counts, (size_t)n_chunks) ||
+      !fd_reserve(b.packed, (size_t)n_chunks * kFdChunkCands, sizeof(FdCand)) || !fd_reserve(b.offs, (size_t)n_chunks) ||
+      !fd_reserve(b.frames, (size_t)max_frames, sizeof(FdFrame)) ||
+      !fd_reserve(b.scratch, (size_t)max_frames * st.max_block * st.channels))
+    return -1;
+  if (!b.meta && b.meta.reserve(2) != hipSuccess) return -1;
   if (!b.crc_tab) {
     uint16_t tab[8][256];
     for (int i = 0; i < 256; ++i) {
@@ -999,25 +993,17 @@ int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hi
     }
     for (int k = 1; k < 8; ++k)
       for (int i = 0; i < 256; ++i) tab[k][i] = (uint16_t)((tab[k - 1][i] << 8) ^ tab[0][tab[k - 1][i] >> 8]);
-    if (hipMalloc(&b.crc_tab, sizeof tab) != hipSuccess) return -1;
-    if (hipMemcpy(b.crc_tab, tab, sizeof tab, hipMemcpyHostToDevice) != hipSuccess) return -1;
+    if (b.crc_tab.upload(&tab[0][0], 8 * 256) != hipSuccess) return -1;
   }
   if (hipMemsetAsync(b.meta, 0, 2 * sizeof(int), stream) != hipSuccess) return -1;
-  hipLaunchKernelGGL(flac_scan_kernel, dim3(n_chunks), dim3(256), 0, stream, b.file, st, static_cast<FdCand*>(b.cands), b.counts, b.meta);
-  hipLaunchKernelGGL(flac_chain_kernel, dim3(1), dim3(kFdChainThreads), 0, stream, static_cast<const FdCand*>(b.cands), b.counts, n_chunks,
-                     st, static_cast<FdCand*>(b.packed), b.offs, static_cast<FdFrame*>(b.frames), (int)max_frames, b.meta + 1, b.meta);
-  FdDecodeParams p{b.file, static_cast<const FdFrame*>(b.frames), b.meta + 1, st, b.scratch, d_pcm, st.bits <= 16 ? 16 - st.bits : 32 - st.bits,
+  hipLaunchKernelGGL(flac_scan_kernel, dim3(n_chunks), dim3(256), 0, stream, b.file, st, b.cands.as<FdCand>(), b.counts, b.meta);
+  hipLaunchKernelGGL(flac_chain_kernel, dim3(1), dim3(kFdChainThreads), 0, stream, b.cands.as<const FdCand>(), b.counts, n_chunks,
+                     st, b.packed.as<FdCand>(), b.offs, b.frames.as<FdFrame>(), (int)max_frames, b.meta + 1, b.meta);
+  FdDecodeParams p{b.file, b.frames.as<const FdFrame>(), b.meta + 1, st, b.scratch, d_pcm, st.bits <= 16 ? 16 - st.bits : 32 - st.bits,
                    st.bits <= 16 ? 0 : 1, b.meta, b.crc_tab};
   hipLaunchKernelGGL(flac_decode_kernel, dim3((unsigned)((max_frames + kFdLanes - 1) / kFdLanes)), dim3(3 * kFdLanes), 0, stream, p);
   hipLaunchKernelGGL(flac_finalize_kernel, dim3((unsigned)((st.max_block + 255) / 256), (unsigned)max_frames), dim3(256), 0, stream, p);
   return hipGetLastError() == hipSuccess ? 0 : -1;
-}
-
-void flac_device_free(FlacDeviceBuffers& b) {
-  void* ptrs[] = {b.file, b.cands, b.counts, b.packed, b.offs, b.frames, b.scratch, b.meta, b.crc_tab};
-  for (void* q : ptrs)
-    if (q) (void)hipFree(q);
-  b = FlacDeviceBuffers();
 }
 
 }  // namespace bp

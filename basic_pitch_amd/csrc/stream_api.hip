@@ -33,8 +33,12 @@
 // joins them to a copy of the record and leaves on the host what the note tracker needs: an update costs the tail's
 // windows, the bitmap of all rows (12 bytes each: it depends on both maxima and on the row count) and the note and bend
 // rows from `first_row` on — not the maps, and nothing else that grows with the session.
+//
+// A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the
+// handle's device and deletes the state, and an open or keep that fails leaves nothing behind.
 #include <algorithm>
 #include <cstring>
+#include <memory>
 
 #include "bp_context.h"
 #include "../../include/basic_pitch_amd_live.h"
@@ -51,8 +55,8 @@ struct bp_stream_state {
   const double* taps = nullptr;  // the handle's table for this rate
   int n_hist = 0;                // ceil(n_taps / up) frames; 0 without resampling
   int ring_cap = 0;
-  float* ring = nullptr;
-  float* hist[2] = {nullptr, nullptr};
+  DeviceBuffer<float> ring;
+  DeviceBuffer<float> hist;  // both halves in one block: half i at hist + i * n_hist
   int cur_hist = 0;
   int64_t n_in = 0;      // input frames taken
   int64_t n_res = 0;     // samples of the model-rate signal made
@@ -65,7 +69,7 @@ struct bp_stream_state {
   bp_note_params prm{};
   int lo = 0, hi = 88;
   int64_t max_rows = 0, keep_cap = 0;
-  float* kept = nullptr;
+  DeviceBuffer<float> kept;
 #ifdef BP_AB_KERNELS
   // bp_ab_stream_poison (the A/B library only): the cell of the kept copy that becomes a NaN when its row is written
   int64_t ab_nan_row = -1;
@@ -110,7 +114,7 @@ int stream_taps(bp_handle h, bp_stream_state* s) {
       return BP_OK;
     }
   ResamplePlan pl{};
-  double* dev = nullptr;
+  DeviceBuffer<double> dev;
   if (int rc = upload_filter(h, s->sample_rate, true, &pl, &dev)) {
     if (rc == BP_ERR_UNSUPPORTED)
       h->err = "bp_stream_open: " + std::to_string(s->sample_rate) + " Hz -> " + std::to_string(h->rate) +
@@ -118,17 +122,10 @@ int stream_taps(bp_handle h, bp_stream_state* s) {
                " taps, which the one-shot calls evaluate in the kernel; such ratios are not streamed";
     return rc;
   }
-  h->st_taps.push_back({s->sample_rate, dev, pl});
   s->plan = pl;
   s->taps = dev;
+  h->st_taps.push_back({s->sample_rate, std::move(dev), pl});
   return BP_OK;
-}
-
-void free_stream(bp_stream_state* s) {
-  if (s->kept) (void)hipFree(s->kept);
-  if (s->ring) (void)hipFree(s->ring);
-  if (s->hist[0]) (void)hipFree(s->hist[0]);
-  delete s;
 }
 
 // rows a peek can have: the windows that have not run when every complete one has are at most two (window > hop)
@@ -190,26 +187,27 @@ struct Round {
 int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int pcm_mem_kind, int out_mem_kind,
                std::vector<WindowSeg>& segs) {
   hipStream_t q = h->stream;
-  // scratch of the step, grown before anything is queued: the chunks (host PCM), their mono form, the rows (host outputs)
-  int64_t pcm_floats = 0, mono_floats = 0, out_floats = 0;
+  // scratch of the step, grown before anything is queued: the chunks (host PCM; each at a multiple of 16 bytes), their mono
+  // form, the rows (host outputs)
+  int64_t pcm_bytes = 0, mono_floats = 0, out_floats = 0;
   for (auto& e : es) {
     const int64_t bytes = e.n_frames * e.s->channels * pcm_width(e.s->format);
-    if (pcm_mem_kind == BP_MEM_HOST) pcm_floats += (bytes + 15) / 16 * 4;
+    if (pcm_mem_kind == BP_MEM_HOST) pcm_bytes += (bytes + 15) / 16 * 16;
     if (e.s->resamples) mono_floats += (e.n_frames + 3) / 4 * 4;
     if (out_mem_kind == BP_MEM_HOST) out_floats += e.rows * kMapsRow;
   }
   int rc;
-  if ((rc = grow(h, &h->st_pcm, &h->st_pcm_cap, pcm_floats)) || (rc = grow(h, &h->st_mono, &h->st_mono_cap, mono_floats)) ||
-      (rc = grow(h, &h->st_out, &h->st_out_cap, out_floats)))
-    return rc;
+  BP_HIP(h->st_pcm.reserve((size_t)pcm_bytes));
+  BP_HIP(h->st_mono.reserve((size_t)mono_floats));
+  BP_HIP(h->st_out.reserve((size_t)out_floats));
   int64_t pcm_at = 0, mono_at = 0, out_at = 0;
   for (size_t i = 0; i < es.size(); ++i) {
     Entry& e = es[i];
     const int64_t bytes = e.n_frames * e.s->channels * pcm_width(e.s->format);
     e.pcm = static_cast<const uint8_t*>(pcm ? pcm[i] : nullptr);
     if (pcm_mem_kind == BP_MEM_HOST) {
-      e.pcm = reinterpret_cast<const uint8_t*>(h->st_pcm + pcm_at);
-      pcm_at += (bytes + 15) / 16 * 4;
+      e.pcm = h->st_pcm + pcm_at;
+      pcm_at += (bytes + 15) / 16 * 16;
     }
     e.mono = h->st_mono + mono_at;
     if (e.s->resamples) mono_at += (e.n_frames + 3) / 4 * 4;
@@ -266,22 +264,21 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
       BP_HIP(hipMemcpyAsync(const_cast<uint8_t*>(e.pcm), pcm[i], (size_t)(e.n_frames * s->channels * pcm_width(s->format)),
                             hipMemcpyHostToDevice, q));
     if (s->resamples)
-      launch_stream_downmix(e.pcm, s->format, e.n_frames, s->channels, const_cast<float*>(e.mono), 0, 0, s->hist[s->cur_hist],
-                            s->hist[s->cur_hist ^ 1], s->n_hist, q);
+      launch_stream_downmix(e.pcm, s->format, e.n_frames, s->channels, const_cast<float*>(e.mono), 0, 0, s->hist + s->cur_hist * s->n_hist,
+                            s->hist + (s->cur_hist ^ 1) * s->n_hist, s->n_hist, q);
   }
   if (!segs.empty()) {
-    const int64_t floats = (int64_t)(segs.size() * sizeof(WindowSeg) + 3) / 4;
-    if ((rc = grow(h, &h->st_segs, &h->st_segs_cap, floats))) return rc;
+    BP_HIP(h->st_segs.reserve(segs.size()));
     BP_HIP(hipMemcpyAsync(h->st_segs, segs.data(), segs.size() * sizeof(WindowSeg), hipMemcpyHostToDevice, q));
   }
-  const WindowSeg* d_segs = reinterpret_cast<const WindowSeg*>(h->st_segs);
+  const WindowSeg* d_segs = h->st_segs;
   for (const Round& r : rounds) {
     for (const Ingest& g : r.ingests) {
       const Entry& e = es[g.e];
       bp_stream_state* s = e.s;
       const int pos = (int)(g.k0 % s->ring_cap);
       if (s->resamples)
-        launch_stream_resample(s->hist[s->cur_hist], s->n_hist, e.mono, s->n_in, s->n_in + e.n_frames, s->taps, s->plan, g.k0,
+        launch_stream_resample(s->hist + s->cur_hist * s->n_hist, s->n_hist, e.mono, s->n_in, s->n_in + e.n_frames, s->taps, s->plan, g.k0,
                                g.n_k, s->ring, pos, s->ring_cap, q);
       else  // frames [k0, k0 + n_k) of the signal are frames k0 - n_in onwards of the chunk
         launch_stream_downmix(e.pcm + (g.k0 - s->n_in) * s->channels * pcm_width(s->format), s->format, g.n_k, s->channels,
@@ -320,9 +317,9 @@ int queue_update(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t fir
   if (rc) return rc;
   const int64_t T = s->rows_out + tail_rows, n_new = T - first_row;
   const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15, bend_bytes = n_new * kFreqN;
-  if ((rc = grow(h, &h->nd_buf, &h->nd_cap, (bits_room + bend_bytes + 3) / 4))) return rc;
-  uint8_t* d_bits = reinterpret_cast<uint8_t*>(h->nd_buf);
-  int8_t* d_bend = reinterpret_cast<int8_t*>(d_bits + bits_room);
+  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_bytes)));
+  uint8_t* d_bits = h->nd_buf;
+  int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
   const Maps kept = kept_maps(s);
   if (tail_rows > 0) {
     std::vector<Entry> es(1);
@@ -448,31 +445,23 @@ int bp_stream_open(bp_handle h, int format, int channels, int sample_rate, bp_st
   *out = nullptr;
   if (int rc = check_ingest(h, false, format, 0, channels, sample_rate, BP_MEM_HOST)) return rc;
   BP_HIP(hipSetDevice(h->device));
-  bp_stream_state* s = new bp_stream_state;
+  std::unique_ptr<bp_stream_state> s(new bp_stream_state);
   s->h = h;
   s->format = format, s->channels = channels, s->sample_rate = sample_rate;
   s->resamples = sample_rate != h->rate;
   if (s->resamples) {
-    if (int rc = stream_taps(h, s)) {
-      delete s;
-      return rc;
-    }
+    if (int rc = stream_taps(h, s.get())) return rc;
     s->n_hist = (int)((s->plan.n_taps + s->plan.up - 1) / s->plan.up);
   }
   s->ring_cap = h->win_len + kRingHops * h->hop;
-  hipError_t e = hipMalloc(&s->ring, (size_t)s->ring_cap * 4);
-  if (e == hipSuccess && s->n_hist > 0) {
+  BP_HIP(s->ring.reserve((size_t)s->ring_cap));
+  if (s->n_hist > 0) {
     // both halves of the history in one block; zeros stand for the frames in front of the signal (never read: the sums are
     // clipped at frame 0)
-    e = hipMalloc(&s->hist[0], (size_t)s->n_hist * 2 * 4);
-    if (e == hipSuccess) e = hipMemset(s->hist[0], 0, (size_t)s->n_hist * 2 * 4);
-    s->hist[1] = s->hist[0] ? s->hist[0] + s->n_hist : nullptr;
+    BP_HIP(s->hist.reserve((size_t)s->n_hist * 2));
+    BP_HIP(hipMemset(s->hist, 0, (size_t)s->n_hist * 2 * sizeof(float)));
   }
-  if (e != hipSuccess) {
-    free_stream(s);
-    BP_HIP(e);
-  }
-  *out = s;
+  *out = s.release();
   return BP_OK;
 }
 
@@ -480,7 +469,7 @@ void bp_stream_close(bp_stream s) {
   if (!s) return;
   // no call returns with work of the stream still queued (finish), so its buffers are idle
   (void)hipSetDevice(s->h->device);
-  free_stream(s);
+  delete s;
 }
 
 int64_t bp_stream_state_bytes(bp_stream s) { return s ? ((int64_t)s->ring_cap + 2 * (int64_t)s->n_hist) * 4 + kept_bytes(s) : 0; }
@@ -540,12 +529,11 @@ int bp_stream_keep(bp_stream s, const bp_note_params* params, int64_t max_rows) 
   if (int rc = note_tables(h, nullptr, nullptr)) return rc;
   const int64_t cap = max_rows + kTailRows;
   if (cap > (int64_t)1 << 40) return invalid("max_rows is out of range");
-  BP_HIP(hipMalloc(&s->kept, (size_t)(cap * kMapsRow + 2 * kStatsFloats) * 4));
+  BP_HIP(s->kept.reserve((size_t)(cap * kMapsRow + 2 * kStatsFloats)));
   s->keep_cap = cap;
   launch_note_stats_init(kept_stats(s, 0), h->stream);
   if (int rc = finish(h, hipGetLastError() == hipSuccess ? BP_OK : BP_ERR_HIP)) {
-    (void)hipFree(s->kept);
-    s->kept = nullptr;
+    (void)s->kept.reset();
     return rc;
   }
   s->prm = *params;
@@ -587,7 +575,7 @@ int bp_stream_candidates(bp_stream s, int with_tail, float* note_out, uint8_t* c
     s->broken = true;
     return rc;
   }
-  if (reinterpret_cast<const int*>(h->nd_stats_host)[1]) *status = 1;  // a NaN in the maps: the host decodes the maps themselves
+  if (h->nd_stats_host[1]) *status = 1;  // a NaN in the maps: the host decodes the maps themselves
   return BP_OK;
 }
 

@@ -6,6 +6,9 @@
 //   validate everything -> queue the source -> tracks_core -> queue the sink -> wait -> the FLAC decoder's verdict.
 // Nothing is queued before every argument has been checked, and a call that fails after queuing work returns only once the
 // handle's stream has drained (finish): the caller may reuse its buffers as soon as any call returns.
+//
+// The staging buffers of these calls are the handle's typed, grow-only buffers (device_buffer.h): a call reserves what it
+// needs before it queues work on them, and nothing here frees by hand.
 #include <algorithm>
 
 #include "bp_context.h"
@@ -43,7 +46,7 @@ int check_ingest(bp_handle h, bool pcm_given, int format, int64_t n_frames, int 
   return BP_OK;
 }
 
-int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePlan* plan, double** dev) {
+int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePlan* plan, DeviceBuffer<double>* dev) {
   std::vector<double> taps;
   ResamplePlan pl = make_resample_plan(sample_rate, h->rate, taps);
   pl.rev_off = 0;
@@ -57,14 +60,7 @@ int upload_filter(bp_handle h, int sample_rate, bool tabulated_only, ResamplePla
     for (size_t i = 0; i < M; ++i) taps[base + i] = taps[M - 1 - i];
     plan->rev_off = (int64_t)base;
   }
-  double* d = nullptr;
-  BP_HIP(hipMalloc(&d, taps.size() * sizeof(double)));
-  if (hipMemcpy(d, taps.data(), taps.size() * sizeof(double), hipMemcpyHostToDevice) != hipSuccess) {
-    (void)hipFree(d);
-    h->err = "audio ingest: copying the resampling filter to the device failed";
-    return BP_ERR_HIP;
-  }
-  *dev = d;
+  BP_HIP(dev->upload(taps.data(), taps.size()));
   return BP_OK;
 }
 
@@ -103,8 +99,7 @@ int64_t h_frames(bp_handle h, int64_t n) { return n_frames_of(n, h->hop, h->lead
 // is gone from then on.
 int take_track_out(bp_handle h, int64_t rows, Maps* m) {
   h->maps_rows = 0;
-  int rc = grow(h, &h->track_out, &h->track_out_cap, rows * kMapsRow);
-  if (rc) return rc;
+  BP_HIP(h->track_out.reserve((size_t)(rows * kMapsRow)));
   *m = maps_at(h->track_out, rows);
   return BP_OK;
 }
@@ -112,8 +107,7 @@ int take_track_out(bp_handle h, int64_t rows, Maps* m) {
 // host samples of n_tracks tracks (`total` in all) into h->track, one after the other; d_in[t]: track t's device view
 int stage_samples(bp_handle h, int64_t n_tracks, const float* const* samples, const int64_t* n_samples, int64_t total,
                   const float** d_in) {
-  int rc = grow(h, &h->track, &h->track_cap, total);
-  if (rc) return rc;
+  BP_HIP(h->track.reserve((size_t)total));
   for (int64_t t = 0, so = 0; t < n_tracks; so += n_samples[t++]) {
     if (n_samples[t] > 0)
       BP_HIP(hipMemcpyAsync(h->track + so, samples[t], (size_t)n_samples[t] * 4, hipMemcpyHostToDevice, h->stream));
@@ -131,15 +125,13 @@ int queue_ingest(bp_handle h, const void* pcm, int format, int64_t n_frames, int
   const void* d_pcm = pcm;
   if (mem_kind == BP_MEM_HOST) {
     const int64_t bytes = n_frames * channels * pcm_width(format);
-    int rc = grow(h, &h->pcm_dev, &h->pcm_cap, (bytes + 3) / 4);
-    if (rc) return rc;
+    BP_HIP(h->pcm_dev.reserve((size_t)bytes));
     BP_HIP(hipMemcpyAsync(h->pcm_dev, pcm, (size_t)bytes, hipMemcpyHostToDevice, s));
     d_pcm = h->pcm_dev;
   }
   const float* d_mono = static_cast<const float*>(d_pcm);
   if (channels > 1 || format != BP_PCM_F32) {
-    int rc = grow(h, &h->mono_dev, &h->mono_cap, n_frames);
-    if (rc) return rc;
+    BP_HIP(h->mono_dev.reserve((size_t)n_frames));
     launch_downmix_raw(d_pcm, format, n_frames, channels, h->mono_dev, s);
     d_mono = h->mono_dev;
   }
@@ -148,14 +140,12 @@ int queue_ingest(bp_handle h, const void* pcm, int format, int64_t n_frames, int
     return BP_OK;
   }
   if (h->taps_rate != sample_rate) {  // one cached filter: replaced when the rate changes
-    if (h->taps_dev) BP_HIP(hipFree(h->taps_dev));
-    h->taps_dev = nullptr;
     h->taps_rate = 0;
+    BP_HIP(h->taps_dev.reset());
     if (int rc = upload_filter(h, sample_rate, false, &h->plan, &h->taps_dev)) return rc;
     h->taps_rate = sample_rate;
   }
-  int rc = grow(h, &h->res_dev, &h->res_cap, n_out);
-  if (rc) return rc;
+  BP_HIP(h->res_dev.reserve((size_t)n_out));
   launch_resample(d_mono, n_frames, h->taps_dev, h->plan, h->res_dev, n_out, h->resample_mode, s);
   BP_HIP(hipGetLastError());
   *out = h->res_dev;
@@ -186,19 +176,12 @@ int flac_format(const bp_flac_stream_layout& lay) { return lay.bits_per_sample >
 // page-locked word; the PCM (flac_format) is being written to h->pcm_dev.
 int queue_flac(bp_handle h, const void* file, size_t nbytes, const bp_flac_stream_layout& lay) {
   hipStream_t s = h->stream;
-  if (!h->fd_status_host) BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->fd_status_host), 2 * sizeof(int), hipHostMallocPortable));
-  if (nbytes + 64 > h->fd.file_cap) {
-    if (h->fd.file) BP_HIP(hipFree(h->fd.file));
-    h->fd.file = nullptr, h->fd.file_cap = 0;
-    const size_t cap = nbytes + nbytes / 4 + 4096;
-    BP_HIP(hipMalloc(&h->fd.file, cap));
-    h->fd.file_cap = cap;
-  }
+  BP_HIP(h->fd_status_host.alloc(2));
+  if (nbytes + 64 > h->fd.file.capacity()) BP_HIP(h->fd.file.reserve(nbytes + nbytes / 4 + 4096));
   BP_HIP(hipMemcpyAsync(h->fd.file, file, nbytes, hipMemcpyHostToDevice, s));
   BP_HIP(hipMemsetAsync(h->fd.file + nbytes, 0, 64, s));
   const int64_t bytes = lay.n_frames * lay.channels * (flac_format(lay) == BP_PCM_S32 ? 4 : 2);
-  int rc = grow(h, &h->pcm_dev, &h->pcm_cap, (bytes + 3) / 4);
-  if (rc) return rc;
+  BP_HIP(h->pcm_dev.reserve((size_t)bytes));
   FdStream st{lay.channels, lay.bits_per_sample, lay.min_block, lay.max_block, lay.n_frames, (uint32_t)lay.audio_start,
               (uint32_t)nbytes};
   if (flac_device_decode(h->fd, st, h->pcm_dev, s) != 0) {
@@ -278,22 +261,22 @@ constexpr size_t kTabBytes = 88 * 16, kGaussBytes = 51 * 8, kStatsBytes = 16;
 int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params* prm, float* note_out, uint8_t* cand_out,
                      int8_t* bend_out, bool* exported_by_kernel) {
   hipStream_t s = h->stream;
-  int rc = note_tables(h, nullptr, nullptr);
-  if (rc) return rc;
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  if (int rc = note_tables(h, &tab, &gauss)) return rc;
   const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bend_bytes = T * 88;  // multiples of 4
-  rc = grow(h, &h->nd_buf, &h->nd_cap, (((bits_bytes + 15) & ~(int64_t)15) + bend_bytes + 3) / 4);
-  if (rc) return rc;
-  uint8_t* d_bits = reinterpret_cast<uint8_t*>(h->nd_buf);
-  int8_t* d_bend = reinterpret_cast<int8_t*>(d_bits + ((bits_bytes + 15) & ~(int64_t)15));
-  char* tables = reinterpret_cast<char*>(h->nd_tables);
-  void* d_stats = tables + kTabBytes + kGaussBytes;
+  const int64_t bits_room = (bits_bytes + 15) & ~(int64_t)15;
+  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_bytes)));
+  uint8_t* d_bits = h->nd_buf;
+  int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
+  void* d_stats = h->nd_tables + kTabBytes + kGaussBytes;
   int lo = 0, hi = 88;
   bp_internal_freq_limits(prm, &lo, &hi);
   const bool want_bends = prm->include_pitch_bends != 0 && bend_out != nullptr;
   if (!h->nd_stats_ready) launch_note_stats_init(d_stats, s);
   h->nd_stats_ready = false;
-  launch_note_candidates(m.note, m.onset, m.contour, T, lo, hi, prm->infer_onsets != 0, prm->onset_threshold, tables,
-                         reinterpret_cast<const double*>(tables + kTabBytes), d_stats, d_bits, want_bends ? d_bend : nullptr, s);
+  launch_note_candidates(m.note, m.onset, m.contour, T, lo, hi, prm->infer_onsets != 0, prm->onset_threshold, tab, gauss,
+                         d_stats, d_bits, want_bends ? d_bend : nullptr, s);
   BP_HIP(hipGetLastError());
   // The results go home.  Into page-locked buffers (bp_host_alloc) a kernel of this stream writes them over PCIe itself:
   // the copy engine serialises the copies of all lanes in both directions (measured: a lane's 27 MB of posteriorgrams
@@ -460,7 +443,7 @@ int run_track(bp_handle h, const char* what, Source src, const Sink& k, bp_flac_
     if (exported_by_kernel) h->nd_stats_ready = true;  // only now: the export kernel, which re-initialises the record, has run
     // numpy's rules for NaN cells, and an onset threshold <= 0 (every cell that is not a peak qualifies), need the maps
     // themselves: the host decoder takes over (bp_track_maps + bp_notes_decode)
-    const int nan_flag = reinterpret_cast<const int*>(h->nd_stats_host)[1];
+    const int nan_flag = h->nd_stats_host[1];
     if (nan_flag || !(k.params->onset_threshold > 0.0)) *k.status = 1;
     if (src.kind != kMaps) h->maps_rows = T;  // the track's maps stay in track_out for bp_track_maps
   }
@@ -492,15 +475,15 @@ int queue_tracks(bp_handle h, int64_t n_tracks, const float* const* samples, con
 
 int bp::note_tables(bp_handle h, const void** tab, const double** gauss) {
   if (!h->nd_tables) {
-    std::vector<float> raw((kTabBytes + kGaussBytes + kStatsBytes) / 4, 0.f);
-    bp_internal_bend_tables(reinterpret_cast<int32_t*>(raw.data()), reinterpret_cast<double*>(raw.data() + kTabBytes / 4));
-    int rc = upload(h, raw.data(), raw.size() * sizeof(float), &h->nd_tables);
-    if (rc) return rc;
-    BP_HIP(hipHostMalloc(reinterpret_cast<void**>(&h->nd_stats_host), kStatsBytes, hipHostMallocPortable));
+    std::vector<uint8_t> raw(kTabBytes + kGaussBytes + kStatsBytes, 0);
+    bp_internal_bend_tables(reinterpret_cast<int32_t*>(raw.data()), reinterpret_cast<double*>(raw.data() + kTabBytes));
+    BP_HIP(h->nd_stats_host.alloc(kStatsBytes / sizeof(int)));
     BP_HIP(hipHostGetDevicePointer(&h->nd_stats_host_dev, h->nd_stats_host, 0));
+    BP_HIP(h->nd_tables.upload(raw.data(), raw.size()));
+    h->workspace_bytes += raw.size();  // the one table bp_get_info reports that bp_create does not make
   }
   if (tab) *tab = h->nd_tables;
-  if (gauss) *gauss = reinterpret_cast<const double*>(reinterpret_cast<const char*>(h->nd_tables) + kTabBytes);
+  if (gauss) *gauss = reinterpret_cast<const double*>(h->nd_tables + kTabBytes);
   return BP_OK;
 }
 

@@ -13,7 +13,7 @@ namespace bp {
 struct PackedWeights {
   LogConsts kc{};
   float b_contour2 = 0, b_note2 = 0, b_onset2 = 0;
-  std::vector<std::pair<float* bp_context::*, std::vector<uint8_t>>> tables;
+  std::vector<std::pair<bp_context::Table bp_context::*, std::vector<uint8_t>>> tables;
 };
 
 // Parses and checks the blob and packs every operand table `flags` (BP_FLAG_*) needs.  Host only: touches no device.

@@ -561,7 +561,7 @@ namespace {
 
 // a device table of the handle: `field` receives the bytes of `parts`, one after the other
 template <class... V>
-void add(PackedWeights& pw, float* bp_context::*field, const V&... parts) {
+void add(PackedWeights& pw, bp_context::Table bp_context::*field, const V&... parts) {
   std::vector<uint8_t> bytes;
   (bytes.insert(bytes.end(), reinterpret_cast<const uint8_t*>(parts.data()),
                 reinterpret_cast<const uint8_t*>(parts.data() + parts.size())),

@@ -299,6 +299,26 @@ def test_product_library_reads_no_behaviour_switch_from_the_environment():
         assert src not in build.SOURCES
 
 
+def test_only_the_owner_types_allocate_and_free_device_and_page_locked_memory():
+    """hipMalloc, hipFree, hipHostMalloc and hipHostFree are called in csrc only by DeviceBuffer / PinnedBuffer
+    (device_buffer.h) and by bp_host_alloc / bp_host_free, which hand page-locked memory to the caller: whatever a handle
+    or a stream holds is freed by its owner's destructor, not by a list kept by hand.  Comments do not count."""
+    from basic_pitch_amd import build
+
+    call = re.compile(r"\bhip(?:Host)?(?:Malloc|Free)\b")
+    found = {}
+    for f in sorted(os.listdir(build.CSRC)):
+        src = open(os.path.join(build.CSRC, f)).read()
+        src = re.sub(r"/\*.*?\*/", "", re.sub(r"//[^\n]*", "", src), flags=re.S)
+        if f == "bp_api.hip":  # the bodies of the two ABI functions (their closing brace is the first in column 0)
+            src, n = re.subn(r"\n(?:void\* bp_host_alloc|void bp_host_free)\([^)]*\) \{\n.*?\n\}\n", "\n", src, flags=re.S)
+            assert n == 2, n
+        found[f] = len(call.findall(src))
+    assert found.pop("device_buffer.h") >= 4
+    assert not any(found.values()), {f: n for f, n in found.items() if n}
+    assert "device_buffer.h" in [os.path.basename(h) for h in build.HEADERS]
+
+
 def test_native_file_reader_direct_io_reads_the_same_bytes(tmp_path):
     """bp_transcribe_files' reader (csrc/file_pipeline.cpp read_file_into) with and without O_DIRECT: the same bytes as
     Python's read for lengths around the 4 KiB block size (an O_DIRECT read is issued in whole blocks and stops at the end of
