@@ -221,6 +221,14 @@ LIVE_SYMBOLS = [
     "bp_stream_keep",
     "bp_stream_candidates",
 ]
+# every symbol include/basic_pitch_amd_rolling.h declares
+ROLLING_SYMBOLS = [
+    "bp_stream_keep_rolling",
+    "bp_stream_horizon_first_row",
+    "bp_stream_candidates_rolling",
+    "bp_stream_rolling_maps",
+    "bp_notes_decode_candidates_at",
+]
 
 _lib: Optional[C.CDLL] = None
 
@@ -337,6 +345,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
         vp, vp, vp, i64, C.POINTER(bp_note_params), vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)
     ]
     lib.bp_notes_decode_candidates.restype = C.c_int
+    lib.bp_notes_decode_candidates_at.argtypes = [
+        vp, vp, vp, i64, i64, vp, vp, i64, vp, i64, C.POINTER(i64), C.POINTER(i64)
+    ]
+    lib.bp_notes_decode_candidates_at.restype = C.c_int
     lib.bp_notes_last_error.argtypes = []
     lib.bp_notes_last_error.restype = C.c_char_p
     pi = C.POINTER(C.c_int)

@@ -143,5 +143,24 @@ void launch_note_fold(float* note, float* onset, int64_t t0, int64_t t1, int lo,
 void launch_note_peaks(const float* note, const float* onset, int64_t T, int infer, double onset_thresh, const void* stats,
                        uint8_t* bits, hipStream_t s);
 void launch_note_bends(const float* contour, int64_t T, const void* tab, const double* gauss, int8_t* bend, hipStream_t s);
+// The rolling forms (a stream's horizon, stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r
+// at slot r % cap; `records` is note_ring_records(cap) stats records of 16 bytes — the table of per-block extrema of the
+// final rows and, last (note_ring_stats), the record of an update.
+int64_t note_ring_records(int64_t cap);
+void* note_ring_stats(void* records, int64_t cap);
+// rows [t0, t0 + n), n <= cap, of linear maps into their slots, frequency-constrained to the bins [lo, hi)
+void launch_ring_put(const float* src_note, const float* src_onset, const float* src_contour, float* ring, int64_t cap,
+                     int64_t t0, int64_t n, int lo, int hi, hipStream_t s);
+// final rows [t0, t1), t1 - t0 <= cap, join the table; blocks that start at or after fresh_from begin anew
+void launch_ring_fold(const float* ring, int64_t cap, int64_t t0, int64_t t1, int64_t fresh_from, int infer, void* records,
+                      hipStream_t s);
+// the record of rows [a, T) as a whole track (R <= T: the final rows), then its peak bitmap ([T - a][12] bytes), the bends of
+// rows [t0, t0 + n) ([n][88] bytes) and the note rows [t0, t0 + n) un-wrapped ([n][88] floats, 16-byte aligned)
+void launch_ring_stats(const float* ring, int64_t cap, int64_t a, int64_t R, int64_t T, int infer, void* records, hipStream_t s);
+void launch_ring_peaks(const float* ring, int64_t cap, int64_t a, int64_t T, int infer, double onset_thresh, const void* stats,
+                       uint8_t* bits, hipStream_t s);
+void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, const void* tab, const double* gauss, int8_t* bend,
+                       hipStream_t s);
+void launch_ring_gather_note(const float* ring, int64_t cap, int64_t t0, int64_t n, float* dst, hipStream_t s);
 
 }  // namespace bp

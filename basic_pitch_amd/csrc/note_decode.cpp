@@ -22,7 +22,7 @@
 // restatement oracle/note_oracle.py — which reproduces the reference's golden note events — including the
 // float32 pairwise summation numpy uses for np.mean (amplitudes), float64 everywhere the reference is
 // float64, round-half-even where it calls np.round.
-#include "../../include/basic_pitch_amd.h"
+#include "../../include/basic_pitch_amd_rolling.h"
 
 #include <algorithm>
 #include <cmath>
@@ -175,8 +175,10 @@ void bp_note_params_default(bp_note_params* p) {
 //   cand_bits != null: the device extracted them (bp_note_candidates, csrc/note_device.hip): bit f of byte row t
 //     ([T][12] bytes, BP_NOTE_CAND_ROW_BYTES) marks an onset peak that reaches the threshold, bend_map [T][88] holds the pitch bend of bin f at
 //     frame t; `note` is already frequency-constrained, `onset` / `contour` are not looked at.
+// first_frame: the maps are rows first_frame ... of a longer track, decoded as a whole track (bp_notes_decode_candidates_at):
+// the frames of the events and their times are those of the absolute rows, nothing else looks at it.
 static int decode_core(float* note, float* onset, const float* contour, const uint8_t* cand_bits, const int8_t* bend_map,
-                       int64_t n_frames, const bp_note_params* prm, bp_note_event* events, int64_t max_events,
+                       int64_t n_frames, int64_t first_frame, const bp_note_params* prm, bp_note_event* events, int64_t max_events,
                        int32_t* bends, int64_t max_bends, int64_t* n_events_out, int64_t* n_bends_out) {
   const bool cand = cand_bits != nullptr;
   if (!prm || !n_events_out || !n_bends_out || n_frames < 0 ||
@@ -438,10 +440,10 @@ static int decode_core(float* note, float* onset, const float* contour, const ui
   for (size_t e = 0; e < notes.size(); ++e) {
     const Raw& r = notes[e];
     bp_note_event& ev = events[e];
-    ev.start_frame = r.start;
-    ev.end_frame = r.end;
-    ev.start_s = frame_time(r.start);
-    ev.end_s = frame_time(r.end);
+    ev.start_frame = (int32_t)(r.start + first_frame);
+    ev.end_frame = (int32_t)(r.end + first_frame);
+    ev.start_s = frame_time(r.start + first_frame);
+    ev.end_s = frame_time(r.end + first_frame);
     ev.pitch_midi = r.pitch;
     ev.amplitude = r.amp;
     ev.bend_offset = bo;
@@ -479,20 +481,31 @@ static int decode_core(float* note, float* onset, const float* contour, const ui
 int bp_notes_decode(float* note, float* onset, const float* contour, int64_t n_frames,
                     const bp_note_params* prm, bp_note_event* events, int64_t max_events, int32_t* bends,
                     int64_t max_bends, int64_t* n_events_out, int64_t* n_bends_out) {
-  return decode_core(note, onset, contour, nullptr, nullptr, n_frames, prm, events, max_events, bends, max_bends, n_events_out,
+  return decode_core(note, onset, contour, nullptr, nullptr, n_frames, 0, prm, events, max_events, bends, max_bends, n_events_out,
                      n_bends_out);
+}
+
+int bp_notes_decode_candidates_at(const float* note, const uint8_t* cand_bits, const int8_t* bend_map, int64_t n_frames,
+                                  int64_t first_frame, const bp_note_params* prm, bp_note_event* events, int64_t max_events,
+                                  int32_t* bends, int64_t max_bends, int64_t* n_events_out, int64_t* n_bends_out) {
+  if (!cand_bits) {
+    g_notes_error = "bp_notes_decode_candidates: null candidate bitmap";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (first_frame < 0 || (n_frames > 0 && first_frame > INT32_MAX - n_frames)) {
+    g_notes_error = "bp_notes_decode_candidates_at: first_frame is negative or the absolute frames pass INT32_MAX";
+    return BP_ERR_INVALID_ARG;
+  }
+  // the note map is only read in this mode (frequency limits were applied where the candidates were made)
+  return decode_core(const_cast<float*>(note), nullptr, nullptr, cand_bits, bend_map, n_frames, first_frame, prm, events,
+                     max_events, bends, max_bends, n_events_out, n_bends_out);
 }
 
 int bp_notes_decode_candidates(const float* note, const uint8_t* cand_bits, const int8_t* bend_map, int64_t n_frames,
                                const bp_note_params* prm, bp_note_event* events, int64_t max_events, int32_t* bends,
                                int64_t max_bends, int64_t* n_events_out, int64_t* n_bends_out) {
-  if (!cand_bits) {
-    g_notes_error = "bp_notes_decode_candidates: null candidate bitmap";
-    return BP_ERR_INVALID_ARG;
-  }
-  // the note map is only read in this mode (frequency limits were applied where the candidates were made)
-  return decode_core(const_cast<float*>(note), nullptr, nullptr, cand_bits, bend_map, n_frames, prm, events, max_events, bends,
-                     max_bends, n_events_out, n_bends_out);
+  return bp_notes_decode_candidates_at(note, cand_bits, bend_map, n_frames, 0, prm, events, max_events, bends, max_bends,
+                                       n_events_out, n_bends_out);
 }
 
 // The per-pitch windows of get_pitch_bends (note_creation.py:182-219) for note bins 0 .. 87, and its Gaussian: the tables

@@ -103,35 +103,47 @@ __device__ __forceinline__ double nd_np_maximum(double a, double b) {
   return a > b ? a : b;
 }
 
+// kRing (a stream's rolling horizon, stream_api.hip): the maps are a ring of `cap` rows, absolute row r at slot r % cap,
+// and the bitmap is that of rows [a, T) decoded AS A WHOLE TRACK — frame t of the slice is absolute row a + t, whatever rows
+// a - 1 and a - 2 still hold in the ring, the `t < 2` and `1 <= t <= n - 2` cases count from a.  Linear: a = 0, cap unused.
+// One body: the arithmetic of the two forms cannot drift apart.
+template <bool kRing>
 __global__ __launch_bounds__(256) void nd_candidates_kernel(const float* __restrict__ note, const float* __restrict__ onset,
-                                                            int64_t T, int infer, double onset_thresh,
+                                                            int64_t a, int64_t T, int64_t cap, int infer, double onset_thresh,
                                                             const NdStats* __restrict__ st, uint32_t* __restrict__ bits) {
   const int lane = threadIdx.x & 63;
-  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
-  if (t >= T) return;
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n = T - a;  // t: the frame of the slice
+  if (t >= n) return;
   const double max_on_d = (double)ord2f(st->max_on_ord);
   const double max_fd = __longlong_as_double((long long)st->max_fd_bits);
-  auto fd_at = [&](int64_t tt, int f) -> double {
-    if (tt < 2) return 0.0;
-    const double n0 = (double)note[tt * kNdF + f];
-    const double d1 = n0 - (double)note[(tt - 1) * kNdF + f], d2 = n0 - (double)note[(tt - 2) * kNdF + f];
+  const int64_t s0 = kRing ? (a + t) % cap : t;
+  // the row of frame t + k in the maps (k = -3 ... 1; cap > 3)
+  auto row = [&](int k) -> int64_t {
+    const int64_t r = s0 + k;
+    if (!kRing) return r;
+    return r < 0 ? r + cap : (r >= cap ? r - cap : r);
+  };
+  auto fd_at = [&](int k, int f) -> double {
+    if (t + k < 2) return 0.0;
+    const double n0 = (double)note[row(k) * kNdF + f];
+    const double d1 = n0 - (double)note[row(k - 1) * kNdF + f], d2 = n0 - (double)note[row(k - 2) * kNdF + f];
     const double d = d1 < d2 ? d1 : d2;
     return d < 0 ? 0.0 : d;
   };
-  auto on_at = [&](int64_t tt, int f) -> double {
-    const double o = (double)onset[tt * kNdF + f];
+  auto on_at = [&](int k, int f) -> double {
+    const double o = (double)onset[row(k) * kNdF + f];
     if (!infer) return o;
-    const double scaled = (max_on_d * fd_at(tt, f)) / max_fd;  // 0 / 0 -> NaN when nothing rises, like numpy
+    const double scaled = (max_on_d * fd_at(k, f)) / max_fd;  // 0 / 0 -> NaN when nothing rises, like numpy
     return nd_np_maximum(o, scaled);
   };
   bool c[2] = {false, false};
-  if (t >= 1 && t <= T - 2) {
+  if (t >= 1 && t <= n - 2) {
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
       const int f = lane + 64 * h;
       if (f >= kNdF) break;
-      const double v = on_at(t, f);
-      c[h] = v > on_at(t - 1, f) && v > on_at(t + 1, f) && v >= onset_thresh;
+      const double v = on_at(0, f);
+      c[h] = v > on_at(-1, f) && v > on_at(1, f) && v >= onset_thresh;
     }
   }
   const unsigned long long b0 = __ballot(c[0]), b1 = __ballot(c[1]);
@@ -177,8 +189,12 @@ __device__ __forceinline__ int nd_bend_argmax_nan(const double* __restrict__ win
   return best;
 }
 
-__global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict__ contour, int64_t T, const int4* __restrict__ tab,
-                                                      const double* __restrict__ gauss, int8_t* __restrict__ bend) {
+// kRing: row t of the T rows is absolute row first + t of a ring of `cap` contour rows (slot r % cap); the bends are written
+// linear, row t at bend + t * 88, as in the linear form (first = 0, cap unused).
+template <bool kRing>
+__global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict__ contour, int64_t first, int64_t T, int64_t cap,
+                                                      const int4* __restrict__ tab, const double* __restrict__ gauss,
+                                                      int8_t* __restrict__ bend) {
   __shared__ __attribute__((aligned(16))) double s_row[kNdBendFrames * kNdBendPitch];
   __shared__ int s_start[kNdF], s_first[kNdF];
   __shared__ double s_g[51];
@@ -209,11 +225,11 @@ __global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict
   // the block's rows are contiguous in memory: 16 x 264 floats as float4s (264 = 4 x 66: no float4 straddles two rows)
   int nan = 0;
   const int64_t n_rows = T - t0 < kNdBendFrames ? T - t0 : kNdBendFrames;
-  const float4* src = reinterpret_cast<const float4*>(contour + t0 * kNdFC);
+  const float4* src = reinterpret_cast<const float4*>(contour + (kRing ? 0 : t0 * kNdFC));
   for (int e = tid; e < kNdBendFrames * (kNdFC / 4); e += 256) {
     const int r = e / (kNdFC / 4), c4 = e - r * (kNdFC / 4);
     float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-    if (r < n_rows) v = src[e];
+    if (r < n_rows) v = kRing ? src[((first + t0 + r) % cap) * (kNdFC / 4) + c4] : src[e];
     nan |= (v.x != v.x) | (v.y != v.y) | (v.z != v.z) | (v.w != v.w);
     double* d = &s_row[r * kNdBendPitch + kNdBendPad + 4 * c4];
     *reinterpret_cast<double2*>(d) = double2{(double)v.x, (double)v.y};
@@ -277,15 +293,15 @@ void launch_note_fold(float* note, float* onset, int64_t t0, int64_t t1, int lo,
 void launch_note_peaks(const float* note, const float* onset, int64_t T, int infer, double onset_thresh, const void* stats,
                        uint8_t* bits, hipStream_t s) {
   if (T <= 0) return;
-  hipLaunchKernelGGL(nd_candidates_kernel, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, note, onset, T, infer, onset_thresh,
-                     static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
+  hipLaunchKernelGGL(nd_candidates_kernel<false>, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, note, onset, (int64_t)0, T,
+                     (int64_t)0, infer, onset_thresh, static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
 }
 
 // the bend map of T contour rows ([T][88] bytes); a row's bends depend on that row alone
 void launch_note_bends(const float* contour, int64_t T, const void* tab, const double* gauss, int8_t* bend, hipStream_t s) {
   if (T <= 0) return;
-  hipLaunchKernelGGL(nd_bend_kernel, dim3((unsigned)((T + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s, contour, T,
-                     static_cast<const int4*>(tab), gauss, bend);
+  hipLaunchKernelGGL(nd_bend_kernel<false>, dim3((unsigned)((T + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s, contour,
+                     (int64_t)0, T, (int64_t)0, static_cast<const int4*>(tab), gauss, bend);
 }
 
 // note / onset / contour: device maps of T frames.  Leaves the bitmap ([T][12] bytes), the bend map ([T][88] bytes, when
@@ -313,5 +329,205 @@ void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, co
                      static_cast<uint32_t*>(bend_dst), bend_dst ? bend_bytes / 4 : 0, static_cast<NdStats*>(stats),
                      static_cast<NdStats*>(stats_dst));
 }
+
+// ---- the rolling horizon of a stream (stream_api.hip, bp_stream_keep_rolling) -------------------------------------------------
+// The kept maps are a ring of `cap` rows ([cap] note, [cap] onset, [cap] contour; absolute row r at slot r % cap) and a
+// transcript decodes rows [a, T) as a whole track.  The two maxima of that slice cannot be carried in one record: a record
+// only grows, and a row that leaves the horizon cannot be taken out of it.  So the final rows fill a TABLE of records, one
+// per block of kNdRingBlock absolute rows (block b at table slot b % n_tab; fd from the real predecessors), and an update
+// joins the blocks that lie wholly in [a + 2, R) (R: the final rows) and scans the rest — the partial first block with rows a
+// and a + 1, whose fd is zero by the decoder's t >= 2 rule, the partial last block and the tail — directly.  Maxima and an
+// OR are exact: the joined record is nd_stats_kernel's on the linear slice whatever the order.
+constexpr int kNdRingBlock = 64;
+
+// the extrema of one row (lanes: bins lane and lane + 64) join the lane's; with_fd: the row has two predecessors in its track
+__device__ __forceinline__ void nd_ring_row(const float* __restrict__ note, const float* __restrict__ onset, int64_t t, int64_t cap,
+                                            bool with_fd, int lane, float& mo, double& mfd, int& nan) {
+  const int64_t s0 = t % cap, s1 = s0 >= 1 ? s0 - 1 : s0 - 1 + cap, s2 = s0 >= 2 ? s0 - 2 : s0 - 2 + cap;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int f = lane + 64 * h;
+    if (f >= kNdF) break;
+    const float o = onset[s0 * kNdF + f], n0 = note[s0 * kNdF + f];
+    nan |= (o != o) | (n0 != n0);
+    mo = o > mo ? o : mo;
+    if (with_fd) {
+      const double d1 = (double)n0 - (double)note[s1 * kNdF + f], d2 = (double)n0 - (double)note[s2 * kNdF + f];
+      const double d = d1 < d2 ? d1 : d2;
+      mfd = d > mfd ? d : mfd;
+    }
+  }
+}
+
+// the workgroup's extrema in thread 0 (wave shuffles, then the four waves through LDS, as nd_stats_kernel)
+__device__ __forceinline__ void nd_ring_reduce(float& mo, double& mfd, int& nan) {
+  __shared__ float s_mo[4];
+  __shared__ double s_fd[4];
+  __shared__ int s_nan[4];
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const float a = __shfl_xor(mo, o);
+    mo = a > mo ? a : mo;
+    const double b = __shfl_xor(mfd, o);
+    mfd = b > mfd ? b : mfd;
+    nan |= __shfl_xor(nan, o);
+  }
+  if (lane == 0) s_mo[wave] = mo, s_fd[wave] = mfd, s_nan[wave] = nan;
+  __syncthreads();
+  if (threadIdx.x == 0)
+    for (int w = 1; w < 4; ++w) {
+      mo = s_mo[w] > mo ? s_mo[w] : mo;
+      mfd = s_fd[w] > mfd ? s_fd[w] : mfd;
+      nan |= s_nan[w];
+    }
+}
+
+// Rows [t0, t0 + n) of linear maps (row 0 of src_* is absolute row t0) go to their slots, constrain_frequency applied on the
+// way (bins outside [lo, hi) of note and onset become 0).  An item is one float; n <= cap, so no slot is written twice.  Scalar
+// loads: the source may be a caller's device buffer, of which only float alignment is known.
+__global__ __launch_bounds__(256) void nd_ring_put_kernel(const float* __restrict__ src_note, const float* __restrict__ src_onset,
+                                                          const float* __restrict__ src_contour, float* __restrict__ note,
+                                                          float* __restrict__ onset, float* __restrict__ contour, int64_t t0,
+                                                          int64_t n, int64_t cap, int lo, int hi) {
+  constexpr int kRow = 2 * kNdF + kNdFC;
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * kRow; i += step) {
+    const int64_t r = i / kRow, slot = (t0 + r) % cap;
+    const int c = (int)(i - r * kRow);
+    if (c < kNdF)
+      note[slot * kNdF + c] = c < lo || c >= hi ? 0.0f : src_note[r * kNdF + c];
+    else if (c < 2 * kNdF)
+      onset[slot * kNdF + c - kNdF] = c - kNdF < lo || c - kNdF >= hi ? 0.0f : src_onset[r * kNdF + c - kNdF];
+    else
+      contour[slot * kNdFC + c - 2 * kNdF] = src_contour[r * kNdFC + c - 2 * kNdF];
+  }
+}
+
+// Final rows [t0, t1) join the table: workgroup i takes block t0 / kNdRingBlock + i, a wave walks its rows.  A block that
+// starts at or after `fresh_from` begins anew (its table slot held a block that left the ring); the block t0 lies inside
+// joins what earlier steps left.  One workgroup per block and launches of one queue: plain stores, no atomics.
+__global__ __launch_bounds__(256) void nd_ring_fold_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t t0,
+                                                           int64_t t1, int64_t cap, int infer, int64_t fresh_from,
+                                                           NdStats* __restrict__ table, int64_t n_tab) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t b = t0 / kNdRingBlock + blockIdx.x, b0 = b * kNdRingBlock;
+  const int64_t lo = b0 > t0 ? b0 : t0, hi = b0 + kNdRingBlock < t1 ? b0 + kNdRingBlock : t1;
+  float mo = -__int_as_float(0x7f800000);
+  double mfd = 0.0;
+  int nan = 0;
+  for (int64_t t = lo + wave; t < hi; t += 4) nd_ring_row(note, onset, t, cap, infer && t >= 2, lane, mo, mfd, nan);
+  nd_ring_reduce(mo, mfd, nan);
+  if (threadIdx.x == 0) {
+    NdStats* rec = table + b % n_tab;
+    int ord = f2ord(mo);
+    unsigned long long fd_bits = (unsigned long long)__double_as_longlong(mfd);  // mfd >= 0: its bits order like the value
+    if (b0 < fresh_from) {
+      ord = rec->max_on_ord > ord ? rec->max_on_ord : ord;
+      fd_bits = rec->max_fd_bits > fd_bits ? rec->max_fd_bits : fd_bits;
+      nan |= rec->nan;
+    }
+    rec->max_on_ord = ord, rec->nan = nan, rec->max_fd_bits = fd_bits;
+  }
+}
+
+// The record of the slice [a, T) (st holds the initial values): the table's blocks [e0, e1) / kNdRingBlock, which lie wholly in
+// [a + 2, R), joined by workgroup 0, and the rows [a, e0) and [e1, T) scanned, a wave per row, fd only from frame 2 of the
+// slice on.  Without a whole block e0 == e1 and the two ranges are the slice.
+__global__ __launch_bounds__(256) void nd_ring_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t a,
+                                                            int64_t e0, int64_t e1, int64_t T, int64_t cap, int infer,
+                                                            const NdStats* __restrict__ table, int64_t n_tab,
+                                                            NdStats* __restrict__ st) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float mo = -__int_as_float(0x7f800000);
+  double mfd = 0.0;
+  int nan = 0;
+  const int64_t n_head = e0 - a, n_edge = n_head + (T - e1);
+  for (int64_t j = (int64_t)blockIdx.x * 4 + wave; j < n_edge; j += (int64_t)gridDim.x * 4) {
+    const int64_t t = j < n_head ? a + j : e1 + (j - n_head);
+    nd_ring_row(note, onset, t, cap, infer && t - a >= 2, lane, mo, mfd, nan);
+  }
+  if (blockIdx.x == 0)
+    for (int64_t b = e0 / kNdRingBlock + threadIdx.x; b < e1 / kNdRingBlock; b += 256) {
+      const NdStats rec = table[b % n_tab];
+      const float o = ord2f(rec.max_on_ord);
+      const double d = __longlong_as_double((long long)rec.max_fd_bits);
+      mo = o > mo ? o : mo;
+      mfd = d > mfd ? d : mfd;
+      nan |= rec.nan;
+    }
+  nd_ring_reduce(mo, mfd, nan);
+  if (threadIdx.x == 0) {
+    atomicMax(&st->max_on_ord, f2ord(mo));
+    if (mfd > 0.0) atomicMax(&st->max_fd_bits, (unsigned long long)__double_as_longlong(mfd));
+    if (nan) atomicOr(&st->nan, 1);
+  }
+}
+
+// the export's un-wrap: rows [t0, t0 + n) of one map of the ring (row_vec float4s per row) into a linear block, from where
+// one or two copies take them home
+__global__ __launch_bounds__(256) void nd_ring_gather_kernel(const float4* __restrict__ ring, int64_t cap, int64_t t0, int64_t n,
+                                                             int row_vec, float4* __restrict__ dst) {
+  const int64_t step = (int64_t)gridDim.x * 256;
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * row_vec; i += step) {
+    const int64_t r = i / row_vec;
+    dst[i] = ring[((t0 + r) % cap) * row_vec + (i - r * row_vec)];
+  }
+}
+
+int64_t note_ring_records(int64_t cap) { return (cap + kNdRingBlock - 1) / kNdRingBlock + 2 + 1; }
+
+static NdStats* ring_table(void* records) { return static_cast<NdStats*>(records); }
+static int64_t ring_n_tab(int64_t cap) { return note_ring_records(cap) - 1; }
+static unsigned ring_grid(int64_t items) { return (unsigned)(items < 2048 * 256 ? (items + 255) / 256 : 2048); }
+
+void launch_ring_put(const float* src_note, const float* src_onset, const float* src_contour, float* ring, int64_t cap,
+                     int64_t t0, int64_t n, int lo, int hi, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(nd_ring_put_kernel, dim3(ring_grid(n * (2 * kNdF + kNdFC))), dim3(256), 0, s, src_note, src_onset,
+                     src_contour, ring, ring + cap * kNdF, ring + cap * 2 * kNdF, t0, n, cap, lo, hi);
+}
+
+void launch_ring_fold(const float* ring, int64_t cap, int64_t t0, int64_t t1, int64_t fresh_from, int infer, void* records,
+                      hipStream_t s) {
+  if (t1 <= t0) return;
+  const int64_t n_blocks = (t1 - 1) / kNdRingBlock - t0 / kNdRingBlock + 1;  // <= n_tab for t1 - t0 <= cap: no slot twice
+  hipLaunchKernelGGL(nd_ring_fold_kernel, dim3((unsigned)n_blocks), dim3(256), 0, s, ring, ring + cap * kNdF, t0, t1, cap, infer,
+                     fresh_from, ring_table(records), ring_n_tab(cap));
+}
+
+void launch_ring_stats(const float* ring, int64_t cap, int64_t a, int64_t R, int64_t T, int infer, void* records, hipStream_t s) {
+  if (T <= a) return;
+  int64_t e0 = (a + 2 + kNdRingBlock - 1) / kNdRingBlock * kNdRingBlock, e1 = R / kNdRingBlock * kNdRingBlock;
+  if (e0 >= e1) e0 = e1 = T;
+  const int64_t n_edge = (e0 - a) + (T - e1);
+  const unsigned rows4 = (unsigned)((n_edge + 3) / 4);
+  NdStats* st = ring_table(records) + ring_n_tab(cap);
+  hipLaunchKernelGGL(nd_stats_init_kernel, dim3(1), dim3(64), 0, s, st);
+  hipLaunchKernelGGL(nd_ring_stats_kernel, dim3(rows4 < 512u ? rows4 : 512u), dim3(256), 0, s, ring, ring + cap * kNdF, a, e0, e1, T,
+                     cap, infer, ring_table(records), ring_n_tab(cap), st);
+}
+
+void launch_ring_peaks(const float* ring, int64_t cap, int64_t a, int64_t T, int infer, double onset_thresh, const void* stats,
+                       uint8_t* bits, hipStream_t s) {
+  if (T <= a) return;
+  hipLaunchKernelGGL(nd_candidates_kernel<true>, dim3((unsigned)((T - a + 3) / 4)), dim3(256), 0, s, ring, ring + cap * kNdF, a, T,
+                     cap, infer, onset_thresh, static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
+}
+
+void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, const void* tab, const double* gauss, int8_t* bend,
+                       hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(nd_bend_kernel<true>, dim3((unsigned)((n + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s,
+                     ring + cap * 2 * kNdF, t0, n, cap, static_cast<const int4*>(tab), gauss, bend);
+}
+
+void launch_ring_gather_note(const float* ring, int64_t cap, int64_t t0, int64_t n, float* dst, hipStream_t s) {
+  if (n <= 0) return;
+  hipLaunchKernelGGL(nd_ring_gather_kernel, dim3(ring_grid(n * (kNdF / 4))), dim3(256), 0, s, reinterpret_cast<const float4*>(ring),
+                     cap, t0, n, kNdF / 4, reinterpret_cast<float4*>(dst));
+}
+
+void* note_ring_stats(void* records, int64_t cap) { return ring_table(records) + ring_n_tab(cap); }
 
 }  // namespace bp

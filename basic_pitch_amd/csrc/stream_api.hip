@@ -1,4 +1,4 @@
-// C ABI of the streaming sessions (include/basic_pitch_amd.h, include/basic_pitch_amd_live.h): audio that arrives over time -> the rows of the un-overlapped
+// C ABI of the streaming sessions (include/basic_pitch_amd.h, include/basic_pitch_amd_live.h, include/basic_pitch_amd_rolling.h): audio that arrives over time -> the rows of the un-overlapped
 // posteriorgrams as they become final, for one stream or for many streams of one handle per step.
 //
 // A stream keeps on the device a ring of the model-rate signal that reaches back to the first sample of its oldest
@@ -34,6 +34,12 @@
 // windows, the bitmap of all rows (12 bytes each: it depends on both maxima and on the row count) and the note and bend
 // rows from `first_row` on — not the maps, and nothing else that grows with the session.
 //
+// bp_stream_keep_rolling keeps, instead, the last `horizon` rows (and the room of a tail) in a ring of rows, absolute row r at
+// slot r % roll_cap, and beside it a table of stats records, one per block of 64 absolute rows (note_device.hip, "the rolling
+// horizon").  bp_stream_candidates_rolling decodes rows [a, T), a = max(0, T - horizon), as a whole track: the record of that
+// slice is joined from the table's whole blocks and a scan of the edge rows, the bitmap and the bends count their frames from
+// a.  Nothing such a stream owns, sends home or computes per update grows with its age.
+//
 // A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the
 // handle's device and deletes the state, and an open or keep that fails leaves nothing behind.
 #include <algorithm>
@@ -41,7 +47,7 @@
 #include <memory>
 
 #include "bp_context.h"
-#include "../../include/basic_pitch_amd_live.h"
+#include "../../include/basic_pitch_amd_rolling.h"
 
 using namespace bp;
 
@@ -70,6 +76,11 @@ struct bp_stream_state {
   int lo = 0, hi = 88;
   int64_t max_rows = 0, keep_cap = 0;
   DeviceBuffer<float> kept;
+  // bp_stream_keep_rolling: the last `horizon` rows of the maps and a tail's room in a ring ([roll_cap] note, onset, contour;
+  // absolute row r at slot r % roll_cap), frequency-constrained for `prm`; the block table and the update's record
+  bool rolling = false;
+  int64_t horizon = 0, roll_cap = 0;
+  DeviceBuffer<float> roll, roll_rec;
 #ifdef BP_AB_KERNELS
   // bp_ab_stream_poison (the A/B library only): the cell of the kept copy that becomes a NaN when its row is written
   int64_t ab_nan_row = -1;
@@ -135,15 +146,19 @@ constexpr int64_t kStatsFloats = 4;  // a stats record of note_device.hip: 16 by
 Maps kept_maps(const bp_stream_state* s) { return maps_at(s->kept, s->keep_cap); }
 Maps rows_from(const Maps& m, int64_t r) { return {m.note + r * kFreqN, m.onset + r * kFreqN, m.contour + r * kFreqC}; }
 void* kept_stats(const bp_stream_state* s, int which) { return s->kept + s->keep_cap * kMapsRow + which * kStatsFloats; }
-int64_t kept_bytes(const bp_stream_state* s) { return s->keep ? (s->keep_cap * kMapsRow + 2 * kStatsFloats) * 4 : 0; }
+int64_t kept_bytes(const bp_stream_state* s) {
+  if (s->rolling) return (s->roll_cap * kMapsRow + note_ring_records(s->roll_cap) * kStatsFloats) * 4;
+  return s->keep ? (s->keep_cap * kMapsRow + 2 * kStatsFloats) * 4 : 0;
+}
 
 // Test hook of the A/B library (bp_ab_stream_poison): rows [r0, r1) of the kept copy have just been written and have not
 // joined a stats record yet; the poisoned cell, if it lies in them, becomes a quiet NaN.  The product library has no such hook.
 #ifdef BP_AB_KERNELS
 int ab_poison(bp_handle h, const bp_stream_state* s, int64_t r0, int64_t r1) {
   if (s->ab_nan_row < r0 || s->ab_nan_row >= r1) return BP_OK;
-  const Maps kept = kept_maps(s);
-  float* cell = (s->ab_nan_map ? kept.onset : kept.note) + s->ab_nan_row * kFreqN + s->ab_nan_bin;
+  const Maps kept = s->rolling ? maps_at(s->roll, s->roll_cap) : kept_maps(s);
+  const int64_t at = s->rolling ? s->ab_nan_row % s->roll_cap : s->ab_nan_row;  // a rolling stream: the row's slot
+  float* cell = (s->ab_nan_map ? kept.onset : kept.note) + at * kFreqN + s->ab_nan_bin;
   BP_HIP(hipMemsetD32Async(cell, 0x7fc00000, 1, h->stream));
   return BP_OK;
 }
@@ -293,6 +308,15 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
   // streams that keep their maps: the final rows of this step go behind the kept ones and join the stats record
   for (const Entry& e : es) {
     const bp_stream_state* s = e.s;
+    if (s->rolling && !e.peek && e.rows > 0) {
+      // the last roll_cap of them at most: a row further back has left every later slice, and so has the block it starts
+      const int64_t r1 = s->rows_out + e.rows, r0 = std::max(s->rows_out, r1 - s->roll_cap), skip = r0 - s->rows_out;
+      launch_ring_put(e.out.note + skip * kFreqN, e.out.onset + skip * kFreqN, e.out.contour + skip * kFreqC, s->roll, s->roll_cap,
+                      r0, r1 - r0, s->lo, s->hi, q);
+      if ((rc = ab_poison(h, s, r0, r1))) return rc;
+      launch_ring_fold(s->roll, s->roll_cap, r0, r1, skip ? 0 : r0, s->prm.infer_onsets != 0, s->roll_rec, q);
+      BP_HIP(hipGetLastError());
+    }
     if (!s->keep || e.peek || e.rows == 0) continue;
     const Maps kept = kept_maps(s);
     if ((rc = copy_maps(h, rows_from(kept, s->rows_out), e.out, e.rows, hipMemcpyDeviceToDevice))) return rc;
@@ -349,6 +373,84 @@ int queue_update(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t fir
     BP_HIP(hipMemcpyAsync(note_out + first_row * kFreqN, kept.note + first_row * kFreqN, (size_t)n_new * kFreqN * 4,
                           hipMemcpyDeviceToHost, q));
     if (want_bends) BP_HIP(hipMemcpyAsync(bend_map + first_row * kFreqN, d_bend, (size_t)bend_bytes, hipMemcpyDeviceToHost, q));
+  }
+  return BP_OK;
+}
+
+// The tail of a rolling stream: the peek's rows through the step's scratch into the slots behind the final rows (nothing
+// committed; the next final rows overwrite them).
+int queue_tail_rolling(bp_handle h, bp_stream_state* s, int64_t tail_rows, std::vector<WindowSeg>& segs) {
+  if (tail_rows <= 0) return BP_OK;
+  int rc;
+  BP_HIP(h->st_out.reserve((size_t)(tail_rows * kMapsRow)));
+  std::vector<Entry> es(1);
+  Entry& e = es[0];
+  e = Entry{};
+  e.s = s;
+  e.finish = e.peek = true;
+  e.rows = tail_rows;
+  e.user = maps_at(h->st_out, tail_rows);
+  e.n_res = s->n_res;
+  e.w_next = s->w_next;
+  e.n_total = bp_handle_resampled_length(h, s->n_in, s->sample_rate);
+  if ((rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
+  launch_ring_put(e.user.note, e.user.onset, e.user.contour, s->roll, s->roll_cap, s->rows_out, tail_rows, s->lo, s->hi, h->stream);
+  BP_HIP(hipGetLastError());
+  return ab_poison(h, s, s->rows_out, s->rows_out + tail_rows);
+}
+
+// rows [r0, r1) of a linear device block (row_bytes each) to a host ring of ring_rows rows: one copy, two where they wrap
+int copy_to_host_ring(bp_handle h, void* ring, int64_t ring_rows, const void* src, int64_t row_bytes, int64_t r0, int64_t r1) {
+  for (int64_t r = r0; r < r1;) {
+    const int64_t at = r % ring_rows, n = std::min(r1 - r, ring_rows - at);
+    BP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ring) + at * row_bytes, static_cast<const uint8_t*>(src) + (r - r0) * row_bytes,
+                          (size_t)(n * row_bytes), hipMemcpyDeviceToHost, h->stream));
+    r += n;
+  }
+  return BP_OK;
+}
+
+// An update of a rolling stream: the tail into the ring, the record of the slice [a, T), its bitmap, the bends and the
+// un-wrapped note rows from n0 = max(held, a) on, and home into the caller's rings.
+int queue_update_rolling(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t held, float* note_ring, uint8_t* bits_ring,
+                         int8_t* bend_ring, int64_t ring_rows, std::vector<WindowSeg>& segs) {
+  hipStream_t q = h->stream;
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  int rc = note_tables(h, &tab, &gauss);
+  if (rc) return rc;
+  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->horizon), n0 = std::max(held, a), n_new = T - n0;
+  const int64_t bits_bytes = (T - a) * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15;
+  const int64_t bend_bytes = n_new * kFreqN, bend_room = (bend_bytes + 15) & ~(int64_t)15;
+  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_room + n_new * kFreqN * 4)));
+  uint8_t* d_bits = h->nd_buf;
+  int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
+  float* d_note = reinterpret_cast<float*>(h->nd_buf.as<uint8_t>() + bits_room + bend_room);
+  if ((rc = queue_tail_rolling(h, s, tail_rows, segs))) return rc;
+  const bool want_bends = s->prm.include_pitch_bends != 0 && bend_ring != nullptr;
+  void* st = note_ring_stats(s->roll_rec, s->roll_cap);
+  launch_ring_stats(s->roll, s->roll_cap, a, s->rows_out, T, s->prm.infer_onsets != 0, s->roll_rec, q);
+  launch_ring_peaks(s->roll, s->roll_cap, a, T, s->prm.infer_onsets != 0, s->prm.onset_threshold, st, d_bits, q);
+  if (want_bends) launch_ring_bends(s->roll, s->roll_cap, n0, n_new, tab, gauss, d_bend, q);
+  launch_ring_gather_note(s->roll, s->roll_cap, n0, n_new, d_note, q);
+  BP_HIP(hipGetLastError());
+  BP_HIP(hipMemcpyAsync(h->nd_stats_host, st, kStatsFloats * 4, hipMemcpyDeviceToHost, q));
+  if ((rc = copy_to_host_ring(h, bits_ring, ring_rows, d_bits, BP_NOTE_CAND_ROW_BYTES, a, T))) return rc;
+  if ((rc = copy_to_host_ring(h, note_ring, ring_rows, d_note, kFreqN * 4, n0, T))) return rc;
+  if (want_bends && (rc = copy_to_host_ring(h, bend_ring, ring_rows, d_bend, kFreqN, n0, T))) return rc;
+  return BP_OK;
+}
+
+// the slice [a, T) of the ring, linear, to the caller's host maps: one copy per map, two where the slots wrap
+int queue_rolling_maps(bp_handle h, bp_stream_state* s, int64_t tail_rows, const Maps& out, std::vector<WindowSeg>& segs) {
+  int rc;
+  if ((rc = queue_tail_rolling(h, s, tail_rows, segs))) return rc;
+  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->horizon);
+  const Maps ring = maps_at(s->roll, s->roll_cap);
+  for (int64_t r = a; r < T;) {
+    const int64_t at = r % s->roll_cap, n = std::min(T - r, s->roll_cap - at);
+    if ((rc = copy_maps(h, rows_from(out, r - a), rows_from(ring, at), n, hipMemcpyDeviceToHost))) return rc;
+    r += n;
   }
   return BP_OK;
 }
@@ -524,6 +626,7 @@ int bp_stream_keep(bp_stream s, const bp_note_params* params, int64_t max_rows) 
   if (!params || max_rows <= 0) return invalid("null params or a max_rows that is not positive");
   if (s->broken || s->finished) return invalid("a finished or broken stream");
   if (s->keep) return invalid("the stream keeps its maps already (the decoding parameters are fixed by the first call)");
+  if (s->rolling) return invalid("the stream keeps a rolling horizon already (bp_stream_keep_rolling): one or the other");
   if (s->rows_out > 0) return invalid("rows have left the stream already: call it before the first window completes");
   BP_HIP(hipSetDevice(h->device));
   if (int rc = note_tables(h, nullptr, nullptr)) return rc;
@@ -579,12 +682,126 @@ int bp_stream_candidates(bp_stream s, int with_tail, float* note_out, uint8_t* c
   return BP_OK;
 }
 
+int64_t bp_stream_horizon_first_row(int64_t n_rows, int64_t horizon_rows) {
+  return n_rows > horizon_rows ? n_rows - horizon_rows : 0;
+}
+
+int bp_stream_keep_rolling(bp_stream s, const bp_note_params* params, int64_t horizon_rows) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  bp_handle h = s->h;
+  auto invalid = [&](const char* why) {
+    h->err = std::string("bp_stream_keep_rolling: ") + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (!params) return invalid("null params");
+  if (horizon_rows < 3 || horizon_rows > (int64_t)1 << 40)
+    return invalid("horizon_rows is out of range (at least 3: a peak needs a row on either side)");
+  if (s->broken || s->finished) return invalid("a finished or broken stream");
+  if (s->keep) return invalid("the stream keeps all its maps already (bp_stream_keep): one or the other");
+  if (s->rolling) return invalid("the stream keeps a rolling horizon already (the parameters are fixed by the first call)");
+  if (s->rows_out > 0) return invalid("rows have left the stream already: call it before the first window completes");
+  BP_HIP(hipSetDevice(h->device));
+  if (int rc = note_tables(h, nullptr, nullptr)) return rc;
+  // the slice and the two windows of a tail; the block table starts empty: a block is written anew by the step that emits
+  // its first row
+  const int64_t cap = horizon_rows + kTailRows;
+  hipError_t e = s->roll.reserve((size_t)(cap * kMapsRow));
+  if (e == hipSuccess) e = s->roll_rec.reserve((size_t)(note_ring_records(cap) * kStatsFloats));
+  if (e != hipSuccess) {
+    (void)s->roll.reset();
+    (void)s->roll_rec.reset();
+    BP_HIP(e);
+  }
+  s->prm = *params;
+  bp_internal_freq_limits(params, &s->lo, &s->hi);
+  s->horizon = horizon_rows;
+  s->roll_cap = cap;
+  s->rolling = true;
+  return BP_OK;
+}
+
+// the arguments of the two calls that read a rolling stream, before anything is queued; *tail_rows: the rows of the peek
+static int check_rolling(bp_stream s, const char* what, int with_tail, int64_t* tail_rows) {
+  bp_handle h = s->h;
+  auto invalid = [&](const char* why) {
+    h->err = std::string(what) + ": " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (!s->rolling) return invalid("the stream keeps no rolling horizon (bp_stream_keep_rolling)");
+  if (s->broken) return invalid("a stream whose earlier call failed on the device: only bp_stream_close is valid");
+  *tail_rows = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
+  if (*tail_rows > kTailRows || (*tail_rows > 0 && !tail_fits(s))) {
+    h->err = std::string(what) + ": the end of the signal does not fit the stream's ring or the room behind the final rows";
+    return BP_ERR_UNSUPPORTED;
+  }
+  return BP_OK;
+}
+
+int bp_stream_candidates_rolling(bp_stream s, int with_tail, float* note_ring, uint8_t* bits_ring, int8_t* bend_ring,
+                                 int64_t ring_rows, int64_t held_rows, int64_t* first_row, int64_t* n_rows, int* status) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  bp_handle h = s->h;
+  auto invalid = [&](const std::string& why) {
+    h->err = "bp_stream_candidates_rolling: " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (!first_row || !n_rows || !status) return invalid("null first_row / n_rows / status");
+  int64_t tail_rows = 0;
+  if (int rc = check_rolling(s, "bp_stream_candidates_rolling", with_tail, &tail_rows)) return rc;
+  if (ring_rows < s->roll_cap)
+    return invalid("ring_rows " + std::to_string(ring_rows) + " is less than the " + std::to_string(s->roll_cap) +
+                   " rows of the stream's ring (horizon_rows + 284)");
+  if (held_rows < 0 || held_rows > s->rows_out)
+    return invalid("held_rows " + std::to_string(held_rows) + " is not in 0 ... " + std::to_string(s->rows_out) + ", the final rows");
+  const int64_t T = s->rows_out + tail_rows;
+  if (T > 0 && (!note_ring || !bits_ring)) return invalid("null output pointer");
+  *first_row = bp_stream_horizon_first_row(T, s->horizon);
+  *n_rows = T;
+  *status = s->prm.onset_threshold > 0.0 ? 0 : 1;
+  if (T == 0) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
+  if (int rc = finish(h, queue_update_rolling(h, s, tail_rows, held_rows, note_ring, bits_ring, bend_ring, ring_rows, segs))) {
+    s->broken = true;
+    return rc;
+  }
+  if (h->nd_stats_host[1]) *status = 1;  // a NaN in the slice: the host decodes the maps themselves
+  return BP_OK;
+}
+
+int bp_stream_rolling_maps(bp_stream s, int with_tail, float* note, float* onset, float* contour, int64_t capacity_rows,
+                           int64_t* first_row, int64_t* n_rows) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  bp_handle h = s->h;
+  auto invalid = [&](const std::string& why) {
+    h->err = "bp_stream_rolling_maps: " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (!first_row || !n_rows) return invalid("null first_row / n_rows");
+  int64_t tail_rows = 0;
+  if (int rc = check_rolling(s, "bp_stream_rolling_maps", with_tail, &tail_rows)) return rc;
+  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->horizon);
+  if (capacity_rows < T - a)
+    return invalid("capacity_rows " + std::to_string(capacity_rows) + " is too small for the " + std::to_string(T - a) + " rows");
+  if (T > a && (!note || !onset || !contour)) return invalid("null output pointer");
+  *first_row = a;
+  *n_rows = T;
+  if (T == 0) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
+  if (int rc = finish(h, queue_rolling_maps(h, s, tail_rows, Maps{note, onset, contour}, segs))) {
+    s->broken = true;
+    return rc;
+  }
+  return BP_OK;
+}
+
 #ifdef BP_AB_KERNELS
 // The A/B library's test hook for the NaN path of a keeping stream (declared nowhere: the tests name it).  From now on the
 // cell (map: 0 note, 1 onset; absolute row; bin) of the KEPT copy is a NaN whenever its row is written there — as a row of
 // a tail at an update, as a final row at the step that emits it.  The rows handed to the caller are not touched.
 int bp_ab_stream_poison(bp_stream s, int map, int64_t row, int bin) {
-  if (!s || !s->keep || map < 0 || map > 1 || row < 0 || bin < 0 || bin >= kFreqN) return BP_ERR_INVALID_ARG;
+  if (!s || (!s->keep && !s->rolling) || map < 0 || map > 1 || row < 0 || bin < 0 || bin >= kFreqN) return BP_ERR_INVALID_ARG;
   s->ab_nan_map = map, s->ab_nan_row = row, s->ab_nan_bin = bin;
   return BP_OK;
 }

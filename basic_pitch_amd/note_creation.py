@@ -115,10 +115,13 @@ def _decode(
     return decoded
 
 
-def decode_candidates(note: np.ndarray, cand_bits: np.ndarray, bend_map: Optional[np.ndarray], prm) -> List[NoteEvent]:
+def decode_candidates(note: np.ndarray, cand_bits: np.ndarray, bend_map: Optional[np.ndarray], prm,
+                      first_frame: Optional[int] = None) -> List[NoteEvent]:
     """The sequential half of note decoding from what the device extracted (`bp_note_candidates` /
     `bp_infer_pcm_raw_candidates`: the frequency-constrained note map, the bitmap of onset peaks, the pitch-bend map):
-    note_creation.py:404-509 + the bends and frame times of 182-219, 346-357 -> [(start_s, end_s, pitch, amplitude, bends)]."""
+    note_creation.py:404-509 + the bends and frame times of 182-219, 346-357 -> [(start_s, end_s, pitch, amplitude, bends)].
+    With `first_frame`, the arrays are rows first_frame ... of a longer track decoded as a whole track, and the times are
+    those of the absolute frames (`bp_notes_decode_candidates_at`, include/basic_pitch_amd_rolling.h)."""
     lib = _native.load_library()
     note = np.require(note, np.float32, ["C"])
     cand_bits = np.require(cand_bits, np.uint8, ["C"])
@@ -129,11 +132,12 @@ def decode_candidates(note: np.ndarray, cand_bits: np.ndarray, bend_map: Optiona
         bend_map = np.require(bend_map, np.int8, ["C"])
         if bend_map.shape != (T, N_FREQ_BINS_NOTES):
             raise ValueError("expected bend_map (T, 88) int8")
-    events, bends, n = _grow_and_call(
-        lib.bp_notes_decode_candidates,
-        (note.ctypes.data, cand_bits.ctypes.data, bend_map.ctypes.data if bend_map is not None else None, T, C.byref(prm)),
-        T, "bp_notes_decode_candidates",
-    )
+    maps = (note.ctypes.data, cand_bits.ctypes.data, bend_map.ctypes.data if bend_map is not None else None, T)
+    if first_frame is None:
+        events, bends, n = _grow_and_call(lib.bp_notes_decode_candidates, maps + (C.byref(prm),), T, "bp_notes_decode_candidates")
+    else:
+        events, bends, n = _grow_and_call(lib.bp_notes_decode_candidates_at, maps + (int(first_frame), C.addressof(prm)), T,
+                                          "bp_notes_decode_candidates_at")
     return _note_events(events, bends, n, bool(prm.include_pitch_bends))
 
 
@@ -153,6 +157,15 @@ def model_frames_to_time(n_frames: int) -> np.ndarray:
     """note_creation.py:346-357."""
     original_times = (np.arange(n_frames) * FFT_HOP).astype(int) / float(AUDIO_SAMPLE_RATE)
     window_numbers = np.floor(np.arange(n_frames) / ANNOT_N_FRAMES)
+    window_offset = (FFT_HOP / AUDIO_SAMPLE_RATE) * (ANNOT_N_FRAMES - (AUDIO_N_SAMPLES / FFT_HOP)) + MAGIC_ALIGNMENT_OFFSET
+    return original_times - (window_offset * window_numbers)
+
+
+def frames_to_time_at(frames: np.ndarray) -> np.ndarray:
+    """`model_frames_to_time(n)[frames]` for any frames, without the table of all n: the same float64 operations."""
+    frames = np.asarray(frames, dtype=np.int64)
+    original_times = (frames * FFT_HOP).astype(int) / float(AUDIO_SAMPLE_RATE)
+    window_numbers = np.floor(frames / ANNOT_N_FRAMES)
     window_offset = (FFT_HOP / AUDIO_SAMPLE_RATE) * (ANNOT_N_FRAMES - (AUDIO_N_SAMPLES / FFT_HOP)) + MAGIC_ALIGNMENT_OFFSET
     return original_times - (window_offset * window_numbers)
 

@@ -8,6 +8,10 @@ the concatenated input, for any chunking.
 Live use: `Stream.peek()` returns the rows a finish would emit now and commits nothing, so emitted rows + peeked rows are
 `predict_pcm_raw` of the audio so far at any moment; `StreamingTranscriber(live=True).transcript()` decodes the notes of the
 audio so far from what the device keeps (`bp_stream_keep`, `bp_stream_candidates`; include/basic_pitch_amd_live.h).
+
+Endless use: `StreamingTranscriber(live=True, horizon_seconds=H)` keeps the last H seconds in a ring on the device
+(`bp_stream_keep_rolling`, `bp_stream_candidates_rolling`; include/basic_pitch_amd_rolling.h) and `transcript()` is the exact
+decode of those rows in absolute stream time: device memory, host memory and the work of an update do not grow with the session.
 """
 from __future__ import annotations
 
@@ -41,6 +45,15 @@ LIVE_PROTOTYPES = {
     "bp_stream_keep": (_int, [_vp, _vp, _i64]),
     "bp_stream_candidates": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _i64, _pi64, _vp]),
 }
+# the same for include/basic_pitch_amd_rolling.h (tests/test_stream_rolling_cpu.py compares)
+ROLLING_PROTOTYPES = {
+    "bp_stream_keep_rolling": (_int, [_vp, _vp, _i64]),
+    "bp_stream_horizon_first_row": (_i64, [_i64, _i64]),
+    "bp_stream_candidates_rolling": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _i64, _pi64, _pi64, _vp]),
+    "bp_stream_rolling_maps": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _pi64, _pi64]),
+    "bp_notes_decode_candidates_at": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _pi64, _pi64]),
+}
+TAIL_ROWS = 2 * 142  # the rows a peek can have: what a rolling stream's ring holds beyond its horizon
 
 # the numpy type a chunk of each format is made of (BP_PCM_S24: packed bytes)
 _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native.BP_PCM_S24: np.uint8,
@@ -48,11 +61,16 @@ _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Declare the streaming family's prototypes (both headers) on a loaded library."""
-    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES}.items():
+    """Declare the streaming family's prototypes (the three headers) on a loaded library."""
+    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
+
+
+def horizon_first_row(n_rows: int, horizon_rows: int) -> int:
+    """The first row of a rolling transcript of `n_rows` rows, max(0, n_rows - horizon_rows) (`bp_stream_horizon_first_row`; no GPU)."""
+    return int(bind(_native.load_library()).bp_stream_horizon_first_row(int(n_rows), int(horizon_rows)))
 
 
 def rows_after(n_samples: int, finished: bool = False) -> int:
@@ -168,6 +186,44 @@ class Stream:
         _native.check(self._lib, self._model._handle, rc, "bp_stream_candidates")
         return int(n_rows.value), int(status.value)
 
+    def keep_rolling(self, prm: Any, horizon_rows: int) -> None:
+        """Keep the last `horizon_rows` rows of the maps in a ring on the device for `candidates_rolling`
+        (`bp_stream_keep_rolling`; before the first row leaves, instead of `keep`): horizon_rows + 284 rows of 1,760 bytes
+        and a small table of records, whatever the age of the stream."""
+        rc = self._lib.bp_stream_keep_rolling(self._s, C.addressof(prm), int(horizon_rows))
+        _native.check(self._lib, self._model._handle, rc, "bp_stream_keep_rolling")
+        self.horizon_rows = int(horizon_rows)
+
+    def candidates_rolling(self, note: np.ndarray, bits: np.ndarray, bend: Optional[np.ndarray], held_rows: int,
+                           with_tail: bool = True) -> Tuple[int, int, int]:
+        """`bp_stream_candidates_rolling` into the caller's host RINGS (note (R, 88) float32, bits (R, 12) uint8, bend (R, 88)
+        int8 or None; R >= horizon_rows + 284; absolute row r at index r % R): the note / bend rows from max(held_rows, a) on,
+        the bits of all rows of [a, T).  Returns (a, T, status)."""
+        first, n_rows, status = C.c_int64(0), C.c_int64(0), C.c_int(0)
+        rc = self._lib.bp_stream_candidates_rolling(self._s, int(bool(with_tail)), note.ctypes.data, bits.ctypes.data,
+                                                    bend.ctypes.data if bend is not None else None, note.shape[0], int(held_rows),
+                                                    C.byref(first), C.byref(n_rows), C.addressof(status))
+        _native.check(self._lib, self._model._handle, rc, "bp_stream_candidates_rolling")
+        return int(first.value), int(n_rows.value), int(status.value)
+
+    def rolling_maps(self, with_tail: bool = True) -> Tuple[int, Dict[str, np.ndarray]]:
+        """`bp_stream_rolling_maps`: (a, the kept, frequency-constrained maps of rows [a, T), linear)."""
+        out = _inf._empty_maps((min(self.horizon_rows, self.rows + self.rows_bound(0)),))
+        first, n_rows = C.c_int64(0), C.c_int64(0)
+        rc = self._lib.bp_stream_rolling_maps(self._s, int(bool(with_tail)), *[_inf._ptr(out[k]) for k, _ in _inf._MAPS],
+                                              out["note"].shape[0], C.byref(first), C.byref(n_rows))
+        _native.check(self._lib, self._model._handle, rc, "bp_stream_rolling_maps")
+        a, T = int(first.value), int(n_rows.value)
+        return a, {k: v[: T - a] for k, v in out.items()}
+
+
+def _unwrapped(ring: np.ndarray, a: int, T: int) -> np.ndarray:
+    """Rows [a, T) of a host ring (row r at index r % len(ring)), linear: a view, or one copy where they wrap."""
+    lo, n = a % ring.shape[0], T - a
+    if lo + n <= ring.shape[0]:
+        return ring[lo : lo + n]
+    return np.concatenate((ring[lo:], ring[: lo + n - ring.shape[0]]))
+
 
 def _step_arrays(n: int):
     return lambda vals: (C.c_void_p * n)(*vals)
@@ -225,7 +281,14 @@ class StreamingTranscriber:
     runs on the host (`bp_notes_decode_candidates`).  Events are NOT final until `finish()`: `get_infered_onsets` scales the
     note-map differences by two maxima taken over the whole track and the melodia pass walks the whole posteriorgram, so an
     event of an earlier transcript can move or vanish when later audio arrives.  What is exact at every update is the answer
-    to "what if the audio ended now"."""
+    to "what if the audio ended now".
+
+    With `horizon_seconds` as well (it needs `live=True`; `max_rows` is then ignored), the session can stay open for ever:
+    the stream keeps the last ceil(horizon_seconds * 22050 / 256) rows in a ring on the device (`bp_stream_keep_rolling`),
+    `transcript()` returns `(midi_data, note_events)` of exactly those rows decoded as a whole track, in absolute stream time
+    (`horizon_first_time`: where they start), `push()` hands out the rows and retains none, the host arrays are rings of a
+    fixed size, and `finish()` returns `(the rows finish emitted, midi_data, note_events)` for the final slice.  While the
+    session is shorter than the horizon the transcripts are those of the mode without it."""
 
     def __init__(
         self,
@@ -243,13 +306,26 @@ class StreamingTranscriber:
         midi_tempo: float = _inf.DEFAULT_MINIMUM_MIDI_TEMPO,
         live: bool = False,
         max_rows: int = 600 * 87,
+        horizon_seconds: Optional[float] = None,
     ):
+        if horizon_seconds is not None and not live:
+            raise ValueError("horizon_seconds needs StreamingTranscriber(live=True)")
         self._decoding = (onset_threshold, frame_threshold, minimum_note_length, minimum_frequency, maximum_frequency,
                           multiple_pitch_bends, melodia_trick, midi_tempo)
         self.stream = Stream(_inf._model_from(model_or_model_path), sample_rate, channels, fmt)
         self._rows: List[Dict[str, np.ndarray]] = []
         self.live = bool(live)
-        if self.live:
+        self.horizon_rows = None if horizon_seconds is None else int(np.ceil(horizon_seconds * _inf.AUDIO_SAMPLE_RATE / _inf.FFT_HOP))
+        if self.horizon_rows is not None:
+            self._prm = _notes._note_params(onset_threshold, frame_threshold, _inf._min_note_len_frames(minimum_note_length), True,
+                                            maximum_frequency, minimum_frequency, melodia_trick, _notes.ENERGY_TOLERANCE, True)
+            self.stream.keep_rolling(self._prm, self.horizon_rows)
+            self._held = 0  # final rows of the note and bend rings already on the host
+            ring = self.horizon_rows + TAIL_ROWS
+            self._note = np.empty((ring, _inf.N_FREQ_BINS_NOTES), np.float32)
+            self._bend = np.empty((ring, _inf.N_FREQ_BINS_NOTES), np.int8)
+            self._bits = np.empty((ring, 12), np.uint8)
+        elif self.live:
             # the parameters model_output_to_notes decodes with (note_creation.py:52-116 defaults: inferred onsets, pitch bends)
             self._prm = _notes._note_params(onset_threshold, frame_threshold, _inf._min_note_len_frames(minimum_note_length), True,
                                             maximum_frequency, minimum_frequency, melodia_trick, _notes.ENERGY_TOLERANCE, True)
@@ -261,8 +337,40 @@ class StreamingTranscriber:
 
     def push(self, chunk: Any) -> Dict[str, np.ndarray]:
         out = self.stream.push(chunk)
-        self._rows.append(out)
+        if self.horizon_rows is None:
+            self._rows.append(out)
         return out
+
+    @property
+    def horizon_first_time(self) -> float:
+        """The absolute time of the first row of the rolling transcript the stream would give now."""
+        s = self.stream
+        tail = 0 if not s._s.value else s.rows_bound(0)
+        return float(_notes.frames_to_time_at(np.array([horizon_first_row(s.rows + tail, self.horizon_rows)]))[0])
+
+    def _rolling_transcript(self):
+        s = self.stream
+        multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
+        status = 1  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
+        if self._prm.onset_threshold > 0:
+            a, T, status = s.candidates_rolling(self._note, self._bits, self._bend, self._held)
+            self._held = s.rows  # rows at or after it were a tail's: sent again next time
+        if status == 0:
+            events = _notes.decode_candidates(_unwrapped(self._note, a, T), _unwrapped(self._bits, a, T),
+                                              _unwrapped(self._bend, a, T), self._prm, first_frame=a)
+            return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+        # a NaN in the slice or an onset threshold <= 0: the host decodes the kept maps of the slice themselves, numpy's rules
+        a, maps = s.rolling_maps()
+        p = self._prm
+        ev, bends, n = _notes._decode(maps["note"], maps["onset"], maps["contour"], self._decoding[0], self._decoding[1],
+                                      p.min_note_len, True, self._decoding[4], self._decoding[3], bool(p.melodia_trick),
+                                      _notes.ENERGY_TOLERANCE, True)
+        flat = bends.tolist()
+        frames = np.array([[e.start_frame, e.end_frame] for e in ev[:n]], dtype=np.int64).reshape(n, 2) + a
+        times = _notes.frames_to_time_at(frames)
+        events = [(float(t[0]), float(t[1]), int(e.pitch_midi), np.float32(e.amplitude), flat[e.bend_offset : e.bend_offset + e.n_bends])
+                  for e, t in zip(ev[:n], times)]
+        return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
 
     def _room(self, rows: int) -> None:
         """Host note / bend / bitmap arrays of at least `rows` rows, the held final rows carried over."""
@@ -279,6 +387,8 @@ class StreamingTranscriber:
         """`(midi_data, note_events)` of the audio pushed so far, as `predict()` returns them for that audio."""
         if not self.live:
             raise ValueError("transcript() needs StreamingTranscriber(live=True)")
+        if self.horizon_rows is not None:
+            return self._rolling_transcript()
         s = self.stream
         multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
         status = 1  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
@@ -297,6 +407,11 @@ class StreamingTranscriber:
         return _inf._output_to_notes(model_output, *self._decoding)
 
     def finish(self):
+        if self.horizon_rows is not None:
+            rows = self.stream.finish()
+            midi_data, note_events = self._rolling_transcript()  # a finished stream has no tail: the final slice
+            self.stream.close()
+            return rows, midi_data, note_events
         self._rows.append(self.stream.finish())
         self.stream.close()
         model_output = {k: np.ascontiguousarray(np.concatenate([r[k] for r in self._rows])) for k, _ in _inf._MAPS}

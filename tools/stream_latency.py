@@ -5,6 +5,8 @@
     python tools/stream_latency.py --launches DIR 64 20                   # (c): kernel launches per step from that trace
     python tools/stream_latency.py --peek --out profiles/stream_peek_latency.md   # (d): a live session, per update
     python tools/stream_latency.py --push-only [--package DIR]            # (d)'s push-only row; DIR: another checkout's root
+    python tools/stream_latency.py --ages rolling --out profiles/stream_rolling_latency.md   # (e): an update at session ages
+    python tools/stream_latency.py --ages plain [--package DIR]           # (e) for the mode that keeps every row
 
 The yardstick is existing code in the same process on the same device: `bp_infer` with host buffers on the same number of
 windows in one call.  Every stream is a 22.05 kHz mono float stream primed with 3840 samples, so that each further push of
@@ -222,6 +224,64 @@ def peek_table(out_path: str, updates: int = 120, chunk_s: float = 0.25) -> None
     model.close()
 
 
+def ages_table(mode: str, out_path: str, updates: int = 40, chunk_s: float = 0.25, runs: int = 2) -> None:
+    """(e) What an update costs at a session age.  One live session is aged with pushes of eight hops (not timed) to just
+    short of 1, 10 and 60 minutes; at each age `updates` chunks of 0.25 s are pushed, each followed by a `transcript()`; the
+    wall time of push + transcript() is taken per update.  mode "rolling": horizon_seconds = 600; mode "plain": the mode that
+    keeps every row (`bp_stream_keep`, default max_rows of ten minutes), which uses nothing newer than `live=True` and so runs
+    on an older checkout (--package); it stops after the ten-minute age, beyond which its pushes are refused."""
+    import basic_pitch_amd
+    from basic_pitch_amd import Model
+    from basic_pitch_amd.streaming import StreamingTranscriber
+
+    model = Model(max_windows=8)
+    chunk = int(chunk_s * 22050)
+    loop = live_signal(60.0)
+    span = updates * chunk
+    ages = (1, 10, 60) if mode == "rolling" else (1, 10)
+    push_only_times(model, loop[: 20 * chunk], chunk)  # warm-up: allocations, the first launches
+    lines = [f"package: {os.path.dirname(os.path.abspath(basic_pitch_amd.__file__))}", "",
+             f"mode {mode}: {updates} updates of {chunk_s} s per age, wall time of `push` + `transcript()` in ms", "",
+             "| run | age at the last update | rows decoded | events | median | p10 | p90 | worst | bytes home per update | state bytes |",
+             "|---|---|---|---|---|---|---|---|---|---|"]
+    for run in range(runs):
+        kw = {"horizon_seconds": 600.0} if mode == "rolling" else {}
+        with StreamingTranscriber(model, 22050, live=True, **kw) as t:
+            at = 0
+
+            def feed(n):
+                nonlocal at
+                t.push(np.take(loop, np.arange(at, at + n) % loop.size))  # the 60-second melody, over and over
+                at += n
+
+            for age in ages:
+                target = int(age * 60 * 22050) - span
+                while at < target:
+                    feed(min(8 * HOP, target - at))
+                t.transcript()  # the rows of the ageing pushes come home here, not in a timed update
+                times, n_events, sent = [], 0, []
+                for _ in range(updates):
+                    held = t.stream.rows
+                    t0 = time.perf_counter()
+                    feed(chunk)
+                    _, events = t.transcript()
+                    times.append(1e3 * (time.perf_counter() - t0))
+                    total = t.stream.rows + t.stream.rows_bound(0)
+                    decoded = min(total, t.horizon_rows) if mode == "rolling" else total
+                    sent.append((total - held) * (88 * 4 + 88) + 12 * decoded + 16)
+                    n_events = len(events)
+                q = np.percentile(times, [50, 10, 90])
+                lines.append(f"| {run} | {at / 22050 / 60:.2f} min | {decoded} | {n_events} | {q[0]:.3f} | {q[1]:.3f} | {q[2]:.3f} | "
+                             f"{max(times):.3f} | {int(np.median(sent))} | {t.stream.state_bytes()} |")
+    text = "\n".join(lines) + "\n"
+    print(text)
+    if out_path:
+        os.makedirs(os.path.dirname(os.path.abspath(out_path)), exist_ok=True)
+        with open(out_path, "w") as f:
+            f.write(text)
+    model.close()
+
+
 def trace(n: int, steps: int) -> None:
     """The traced program: n primed streams, `steps` steps of one window each (run it under rocprofv3)."""
     b = Bench()
@@ -257,9 +317,12 @@ if __name__ == "__main__":
     ap.add_argument("--launches", nargs=3, metavar=("DIR", "N", "STEPS"))
     ap.add_argument("--peek", action="store_true", help="(d): push, peek and transcript() per update of a live session")
     ap.add_argument("--push-only", action="store_true", help="the push-only sessions of (d) alone")
+    ap.add_argument("--ages", choices=("rolling", "plain"), help="(e): push + transcript() at session ages of 1, 10 (, 60) minutes")
     ap.add_argument("--package", default="", help="root of the checkout whose basic_pitch_amd is timed (default: this one)")
     a = ap.parse_args()
-    if a.push_only:
+    if a.ages:
+        ages_table(a.ages, a.out)
+    elif a.push_only:
         push_only()
     elif a.peek:
         peek_table(a.out)
