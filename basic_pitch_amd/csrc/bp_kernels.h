@@ -137,30 +137,24 @@ void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, co
                         int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
                         void* stats_dst, hipStream_t s);
 void launch_note_stats_init(void* stats, hipStream_t s);
-// the three steps of launch_note_candidates on their own, for maps that grow (stream_api.hip): frames [t0, t1) join the
-// stats record; the bitmap of all T frames from a record; the bend map of T rows
-void launch_note_fold(float* note, float* onset, int64_t t0, int64_t t1, int lo, int hi, int infer, void* stats, hipStream_t s);
-void launch_note_peaks(const float* note, const float* onset, int64_t T, int infer, double onset_thresh, const void* stats,
-                       uint8_t* bits, hipStream_t s);
-void launch_note_bends(const float* contour, int64_t T, const void* tab, const double* gauss, int8_t* bend, hipStream_t s);
-// The rolling forms (a stream's horizon, stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r
-// at slot r % cap; `records` is note_ring_records(cap) stats records of 16 bytes — the table of per-block extrema of the
-// final rows and, last (note_ring_stats), the record of an update.
+// frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
+void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
+// The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot
+// r % cap.  A rolling horizon has beside it `records`, note_ring_records(cap) stats records of 16 bytes: the table of
+// per-block extrema of the final rows and, last, the record of an update.
 int64_t note_ring_records(int64_t cap);
-void* note_ring_stats(void* records, int64_t cap);
 // rows [t0, t0 + n), n <= cap, of linear maps into their slots, frequency-constrained to the bins [lo, hi)
 void launch_ring_put(const float* src_note, const float* src_onset, const float* src_contour, float* ring, int64_t cap,
                      int64_t t0, int64_t n, int lo, int hi, hipStream_t s);
 // final rows [t0, t1), t1 - t0 <= cap, join the table; blocks that start at or after fresh_from begin anew
 void launch_ring_fold(const float* ring, int64_t cap, int64_t t0, int64_t t1, int64_t fresh_from, int infer, void* records,
                       hipStream_t s);
-// the record of rows [a, T) as a whole track (R <= T: the final rows), then its peak bitmap ([T - a][12] bytes), the bends of
-// rows [t0, t0 + n) ([n][88] bytes) and the note rows [t0, t0 + n) un-wrapped ([n][88] floats, 16-byte aligned)
+// the record of rows [a, T) as a whole track from the table (R <= T: the final rows), into the last of `records`
 void launch_ring_stats(const float* ring, int64_t cap, int64_t a, int64_t R, int64_t T, int infer, void* records, hipStream_t s);
+// from a record of rows [a, T): their peak bitmap ([T - a][12] bytes); the bends of rows [t0, t0 + n) ([n][88] bytes)
 void launch_ring_peaks(const float* ring, int64_t cap, int64_t a, int64_t T, int infer, double onset_thresh, const void* stats,
                        uint8_t* bits, hipStream_t s);
 void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, const void* tab, const double* gauss, int8_t* bend,
                        hipStream_t s);
-void launch_ring_gather_note(const float* ring, int64_t cap, int64_t t0, int64_t n, float* dst, hipStream_t s);
 
 }  // namespace bp

@@ -45,36 +45,35 @@ __global__ __launch_bounds__(64) void nd_stats_init_kernel(NdStats* st) {
   }
 }
 
-// Extrema of the two maps.  A wave walks frames (lanes take bins lane and lane + 64), a workgroup folds its four waves in
-// LDS and publishes ONE atomic per quantity (as first written, every frame's wave published its own: 15 k serialised
-// atomics per 3-minute track on three addresses, 0.36 ms — more than the CQT of the track).
-// The range form: frames [t0, T) JOIN the record (maxima and the NaN flag only ever grow), the differences of a frame reach
-// back to frames t - 1 and t - 2 of the same maps whether or not those lie in the range — a record that has seen [0, a) and
-// then [a, b) equals one that has seen [0, b), which is what lets a stream carry it over its final rows.
-__global__ __launch_bounds__(256) void nd_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t t0,
-                                                       int64_t T, int infer, NdStats* __restrict__ st) {
+// The extrema of one row join the lane's (lanes take bins lane and lane + 64).  with_fd: the row has two predecessors in its
+// track, rows t - 1 and t - 2 of the same maps.  kRing: the maps are a ring of `cap` rows, absolute row t at slot t % cap
+// (a stream's retained rows, below); linear: row t at t, cap unused.  One body: the arithmetic of the forms cannot drift apart.
+template <bool kRing>
+__device__ __forceinline__ void nd_row(const float* __restrict__ note, const float* __restrict__ onset, int64_t t, int64_t cap,
+                                       bool with_fd, int lane, float& mo, double& mfd, int& nan) {
+  const int64_t s0 = kRing ? t % cap : t;
+  const int64_t s1 = !kRing || s0 >= 1 ? s0 - 1 : s0 - 1 + cap, s2 = !kRing || s0 >= 2 ? s0 - 2 : s0 - 2 + cap;
+#pragma unroll
+  for (int h = 0; h < 2; ++h) {
+    const int f = lane + 64 * h;
+    if (f >= kNdF) break;
+    const float o = onset[s0 * kNdF + f], n0 = note[s0 * kNdF + f];
+    nan |= (o != o) | (n0 != n0);
+    mo = o > mo ? o : mo;
+    if (with_fd) {
+      const double d1 = (double)n0 - (double)note[s1 * kNdF + f], d2 = (double)n0 - (double)note[s2 * kNdF + f];
+      const double d = d1 < d2 ? d1 : d2;
+      mfd = d > mfd ? d : mfd;
+    }
+  }
+}
+
+// the workgroup's extrema in thread 0: wave shuffles, then the four waves through LDS
+__device__ __forceinline__ void nd_reduce(float& mo, double& mfd, int& nan) {
   __shared__ float s_mo[4];
   __shared__ double s_fd[4];
   __shared__ int s_nan[4];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float mo = -__int_as_float(0x7f800000);
-  double mfd = 0.0;
-  int nan = 0;
-  for (int64_t t = t0 + (int64_t)blockIdx.x * 4 + wave; t < T; t += (int64_t)gridDim.x * 4) {
-#pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int f = lane + 64 * h;
-      if (f >= kNdF) break;
-      const float o = onset[t * kNdF + f], n0 = note[t * kNdF + f];
-      nan |= (o != o) | (n0 != n0);
-      mo = o > mo ? o : mo;
-      if (infer && t >= 2) {
-        const double d1 = (double)n0 - (double)note[(t - 1) * kNdF + f], d2 = (double)n0 - (double)note[(t - 2) * kNdF + f];
-        const double d = d1 < d2 ? d1 : d2;
-        mfd = d > mfd ? d : mfd;
-      }
-    }
-  }
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float a = __shfl_xor(mo, o);
@@ -85,16 +84,37 @@ __global__ __launch_bounds__(256) void nd_stats_kernel(const float* __restrict__
   }
   if (lane == 0) s_mo[wave] = mo, s_fd[wave] = mfd, s_nan[wave] = nan;
   __syncthreads();
-  if (threadIdx.x == 0) {
+  if (threadIdx.x == 0)
     for (int w = 1; w < 4; ++w) {
       mo = s_mo[w] > mo ? s_mo[w] : mo;
       mfd = s_fd[w] > mfd ? s_fd[w] : mfd;
       nan |= s_nan[w];
     }
-    atomicMax(&st->max_on_ord, f2ord(mo));
-    if (mfd > 0.0) atomicMax(&st->max_fd_bits, (unsigned long long)__double_as_longlong(mfd));
-    if (nan) atomicOr(&st->nan, 1);
-  }
+}
+
+// thread 0's extrema join a record that other workgroups join too: ONE atomic per quantity and workgroup (as first written,
+// every frame's wave published its own: 15 k serialised atomics per 3-minute track on three addresses, 0.36 ms — more than
+// the CQT of the track)
+__device__ __forceinline__ void nd_publish(NdStats* __restrict__ st, float mo, double mfd, int nan) {
+  atomicMax(&st->max_on_ord, f2ord(mo));
+  if (mfd > 0.0) atomicMax(&st->max_fd_bits, (unsigned long long)__double_as_longlong(mfd));
+  if (nan) atomicOr(&st->nan, 1);
+}
+
+// Extrema of the two maps: a wave walks frames, a workgroup folds its four waves and publishes.
+// The range form: frames [t0, T) JOIN the record (maxima and the NaN flag only ever grow), the differences of a frame reach
+// back to frames t - 1 and t - 2 of the same maps whether or not those lie in the range — a record that has seen [0, a) and
+// then [a, b) equals one that has seen [0, b), which is what lets a stream carry it over its final rows.
+__global__ __launch_bounds__(256) void nd_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t t0,
+                                                       int64_t T, int infer, NdStats* __restrict__ st) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  float mo = -__int_as_float(0x7f800000);
+  double mfd = 0.0;
+  int nan = 0;
+  for (int64_t t = t0 + (int64_t)blockIdx.x * 4 + wave; t < T; t += (int64_t)gridDim.x * 4)
+    nd_row<false>(note, onset, t, 0, infer && t >= 2, lane, mo, mfd, nan);
+  nd_reduce(mo, mfd, nan);
+  if (threadIdx.x == 0) nd_publish(st, mo, mfd, nan);
 }
 
 // np.maximum: NaN if either operand is NaN
@@ -276,43 +296,30 @@ __global__ __launch_bounds__(256) void nd_export_kernel(const uint32_t* __restri
   }
 }
 
-// Frames [t0, t1) of the device maps note / onset join the stats record: constrain_frequency on them (`lo`, `hi`: the bins
-// it keeps; 0, 88: none to zero), then their extrema.  Frames t0 - 1 and t0 - 2 are read (never written) when t0 > 0.
-void launch_note_fold(float* note, float* onset, int64_t t0, int64_t t1, int lo, int hi, int infer, void* stats, hipStream_t s) {
+// Frames [t0, t1) of the device maps note / onset join the stats record.  Frames t0 - 1 and t0 - 2 are read when t0 > 0.
+void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s) {
   if (t1 <= t0) return;
-  const int64_t n = t1 - t0;
-  const unsigned frames4 = (unsigned)((n + 3) / 4);
-  if (lo > 0 || hi < kNdF)
-    hipLaunchKernelGGL(nd_constrain_kernel, dim3((unsigned)((n * kNdF + 255) / 256)), dim3(256), 0, s, note + t0 * kNdF,
-                       onset + t0 * kNdF, n * kNdF, lo, hi);
+  const unsigned frames4 = (unsigned)((t1 - t0 + 3) / 4);
   hipLaunchKernelGGL(nd_stats_kernel, dim3(frames4 < 512u ? frames4 : 512u), dim3(256), 0, s, note, onset, t0, t1, infer,
                      static_cast<NdStats*>(stats));
 }
 
-// the onset-peak bitmap of all T frames ([T][12] bytes) from maps whose extrema `stats` holds
-void launch_note_peaks(const float* note, const float* onset, int64_t T, int infer, double onset_thresh, const void* stats,
-                       uint8_t* bits, hipStream_t s) {
-  if (T <= 0) return;
-  hipLaunchKernelGGL(nd_candidates_kernel<false>, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, note, onset, (int64_t)0, T,
-                     (int64_t)0, infer, onset_thresh, static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
-}
-
-// the bend map of T contour rows ([T][88] bytes); a row's bends depend on that row alone
-void launch_note_bends(const float* contour, int64_t T, const void* tab, const double* gauss, int8_t* bend, hipStream_t s) {
-  if (T <= 0) return;
-  hipLaunchKernelGGL(nd_bend_kernel<false>, dim3((unsigned)((T + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s, contour,
-                     (int64_t)0, T, (int64_t)0, static_cast<const int4*>(tab), gauss, bend);
-}
-
-// note / onset / contour: device maps of T frames.  Leaves the bitmap ([T][12] bytes), the bend map ([T][88] bytes, when
-// `bend` != null) and the stats on the device (the stats record must hold its initial values: launch_note_stats_init); `lo`, `hi`: the bins constrain_frequency keeps (0, 88: none to zero).
+// note / onset / contour: device maps of T frames.  constrain_frequency on them (`lo`, `hi`: the bins it keeps; 0, 88: none to
+// zero), their extrema into `stats` (which must hold its initial values: launch_note_stats_init), the onset-peak bitmap of
+// all T frames ([T][12] bytes) and, when `bend` != null, the bend map ([T][88] bytes; a row's bends depend on that row alone).
+// All three results stay on the device.
 void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,
                             double onset_thresh, const void* tab, const double* gauss, void* stats, uint8_t* bits,
                             int8_t* bend, hipStream_t s) {
   if (T <= 0) return;
-  launch_note_fold(note, onset, 0, T, lo, hi, infer, stats, s);
-  launch_note_peaks(note, onset, T, infer, onset_thresh, stats, bits, s);
-  if (bend) launch_note_bends(contour, T, tab, gauss, bend, s);
+  if (lo > 0 || hi < kNdF)
+    hipLaunchKernelGGL(nd_constrain_kernel, dim3((unsigned)((T * kNdF + 255) / 256)), dim3(256), 0, s, note, onset, T * kNdF, lo, hi);
+  launch_note_fold(note, onset, 0, T, infer, stats, s);
+  hipLaunchKernelGGL(nd_candidates_kernel<false>, dim3((unsigned)((T + 3) / 4)), dim3(256), 0, s, note, onset, (int64_t)0, T,
+                     (int64_t)0, infer, onset_thresh, static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
+  if (bend)
+    hipLaunchKernelGGL(nd_bend_kernel<false>, dim3((unsigned)((T + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s, contour,
+                       (int64_t)0, T, (int64_t)0, static_cast<const int4*>(tab), gauss, bend);
 }
 
 void launch_note_stats_init(void* stats, hipStream_t s) {
@@ -330,58 +337,20 @@ void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, co
                      static_cast<NdStats*>(stats_dst));
 }
 
-// ---- the rolling horizon of a stream (stream_api.hip, bp_stream_keep_rolling) -------------------------------------------------
-// The kept maps are a ring of `cap` rows ([cap] note, [cap] onset, [cap] contour; absolute row r at slot r % cap) and a
-// transcript decodes rows [a, T) as a whole track.  The two maxima of that slice cannot be carried in one record: a record
-// only grows, and a row that leaves the horizon cannot be taken out of it.  So the final rows fill a TABLE of records, one
+// ---- the rows a stream retains (stream_api.hip, bp_stream_keep / bp_stream_keep_rolling) ------------------------------------
+// The retained maps are a ring of `cap` rows ([cap] note, [cap] onset, [cap] contour; absolute row r at slot r % cap),
+// frequency-constrained as they are put, and a transcript decodes rows [a, T) as a whole track: nd_candidates_kernel<true>
+// and nd_bend_kernel<true>.  A stream that keeps every row reserves a ring that never wraps: a = 0, slot r is row r, and the
+// extrema of its rows are carried in ONE record, which the final rows join with launch_note_fold on the ring as the linear
+// maps it then is.
+//
+// A rolling horizon cannot carry the two maxima of its slice in one record: a record only grows, and a row that leaves the
+// horizon cannot be taken out of it.  So its final rows fill a TABLE of records, one
 // per block of kNdRingBlock absolute rows (block b at table slot b % n_tab; fd from the real predecessors), and an update
 // joins the blocks that lie wholly in [a + 2, R) (R: the final rows) and scans the rest — the partial first block with rows a
 // and a + 1, whose fd is zero by the decoder's t >= 2 rule, the partial last block and the tail — directly.  Maxima and an
 // OR are exact: the joined record is nd_stats_kernel's on the linear slice whatever the order.
 constexpr int kNdRingBlock = 64;
-
-// the extrema of one row (lanes: bins lane and lane + 64) join the lane's; with_fd: the row has two predecessors in its track
-__device__ __forceinline__ void nd_ring_row(const float* __restrict__ note, const float* __restrict__ onset, int64_t t, int64_t cap,
-                                            bool with_fd, int lane, float& mo, double& mfd, int& nan) {
-  const int64_t s0 = t % cap, s1 = s0 >= 1 ? s0 - 1 : s0 - 1 + cap, s2 = s0 >= 2 ? s0 - 2 : s0 - 2 + cap;
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    const int f = lane + 64 * h;
-    if (f >= kNdF) break;
-    const float o = onset[s0 * kNdF + f], n0 = note[s0 * kNdF + f];
-    nan |= (o != o) | (n0 != n0);
-    mo = o > mo ? o : mo;
-    if (with_fd) {
-      const double d1 = (double)n0 - (double)note[s1 * kNdF + f], d2 = (double)n0 - (double)note[s2 * kNdF + f];
-      const double d = d1 < d2 ? d1 : d2;
-      mfd = d > mfd ? d : mfd;
-    }
-  }
-}
-
-// the workgroup's extrema in thread 0 (wave shuffles, then the four waves through LDS, as nd_stats_kernel)
-__device__ __forceinline__ void nd_ring_reduce(float& mo, double& mfd, int& nan) {
-  __shared__ float s_mo[4];
-  __shared__ double s_fd[4];
-  __shared__ int s_nan[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float a = __shfl_xor(mo, o);
-    mo = a > mo ? a : mo;
-    const double b = __shfl_xor(mfd, o);
-    mfd = b > mfd ? b : mfd;
-    nan |= __shfl_xor(nan, o);
-  }
-  if (lane == 0) s_mo[wave] = mo, s_fd[wave] = mfd, s_nan[wave] = nan;
-  __syncthreads();
-  if (threadIdx.x == 0)
-    for (int w = 1; w < 4; ++w) {
-      mo = s_mo[w] > mo ? s_mo[w] : mo;
-      mfd = s_fd[w] > mfd ? s_fd[w] : mfd;
-      nan |= s_nan[w];
-    }
-}
 
 // Rows [t0, t0 + n) of linear maps (row 0 of src_* is absolute row t0) go to their slots, constrain_frequency applied on the
 // way (bins outside [lo, hi) of note and onset become 0).  An item is one float; n <= cap, so no slot is written twice.  Scalar
@@ -416,8 +385,8 @@ __global__ __launch_bounds__(256) void nd_ring_fold_kernel(const float* __restri
   float mo = -__int_as_float(0x7f800000);
   double mfd = 0.0;
   int nan = 0;
-  for (int64_t t = lo + wave; t < hi; t += 4) nd_ring_row(note, onset, t, cap, infer && t >= 2, lane, mo, mfd, nan);
-  nd_ring_reduce(mo, mfd, nan);
+  for (int64_t t = lo + wave; t < hi; t += 4) nd_row<true>(note, onset, t, cap, infer && t >= 2, lane, mo, mfd, nan);
+  nd_reduce(mo, mfd, nan);
   if (threadIdx.x == 0) {
     NdStats* rec = table + b % n_tab;
     int ord = f2ord(mo);
@@ -445,7 +414,7 @@ __global__ __launch_bounds__(256) void nd_ring_stats_kernel(const float* __restr
   const int64_t n_head = e0 - a, n_edge = n_head + (T - e1);
   for (int64_t j = (int64_t)blockIdx.x * 4 + wave; j < n_edge; j += (int64_t)gridDim.x * 4) {
     const int64_t t = j < n_head ? a + j : e1 + (j - n_head);
-    nd_ring_row(note, onset, t, cap, infer && t - a >= 2, lane, mo, mfd, nan);
+    nd_row<true>(note, onset, t, cap, infer && t - a >= 2, lane, mo, mfd, nan);
   }
   if (blockIdx.x == 0)
     for (int64_t b = e0 / kNdRingBlock + threadIdx.x; b < e1 / kNdRingBlock; b += 256) {
@@ -456,23 +425,8 @@ __global__ __launch_bounds__(256) void nd_ring_stats_kernel(const float* __restr
       mfd = d > mfd ? d : mfd;
       nan |= rec.nan;
     }
-  nd_ring_reduce(mo, mfd, nan);
-  if (threadIdx.x == 0) {
-    atomicMax(&st->max_on_ord, f2ord(mo));
-    if (mfd > 0.0) atomicMax(&st->max_fd_bits, (unsigned long long)__double_as_longlong(mfd));
-    if (nan) atomicOr(&st->nan, 1);
-  }
-}
-
-// the export's un-wrap: rows [t0, t0 + n) of one map of the ring (row_vec float4s per row) into a linear block, from where
-// one or two copies take them home
-__global__ __launch_bounds__(256) void nd_ring_gather_kernel(const float4* __restrict__ ring, int64_t cap, int64_t t0, int64_t n,
-                                                             int row_vec, float4* __restrict__ dst) {
-  const int64_t step = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * row_vec; i += step) {
-    const int64_t r = i / row_vec;
-    dst[i] = ring[((t0 + r) % cap) * row_vec + (i - r * row_vec)];
-  }
+  nd_reduce(mo, mfd, nan);
+  if (threadIdx.x == 0) nd_publish(st, mo, mfd, nan);
 }
 
 int64_t note_ring_records(int64_t cap) { return (cap + kNdRingBlock - 1) / kNdRingBlock + 2 + 1; }
@@ -521,13 +475,5 @@ void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, co
   hipLaunchKernelGGL(nd_bend_kernel<true>, dim3((unsigned)((n + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s,
                      ring + cap * 2 * kNdF, t0, n, cap, static_cast<const int4*>(tab), gauss, bend);
 }
-
-void launch_ring_gather_note(const float* ring, int64_t cap, int64_t t0, int64_t n, float* dst, hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(nd_ring_gather_kernel, dim3(ring_grid(n * (kNdF / 4))), dim3(256), 0, s, reinterpret_cast<const float4*>(ring),
-                     cap, t0, n, kNdF / 4, reinterpret_cast<float4*>(dst));
-}
-
-void* note_ring_stats(void* records, int64_t cap) { return ring_table(records) + ring_n_tab(cap); }
 
 }  // namespace bp

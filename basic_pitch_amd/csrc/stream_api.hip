@@ -28,17 +28,20 @@
 //     provisional sum can reach a final row.
 // The history buffers and cur_hist belong to the downmix of a chunk, and a peek has no chunk.
 //
-// bp_stream_keep adds to a stream the three maps of every final row (1,760 bytes per row) and a stats record that those rows
-// join as they are emitted (note_device.hip, launch_note_fold).  bp_stream_candidates puts the peek's rows behind them,
-// joins them to a copy of the record and leaves on the host what the note tracker needs: an update costs the tail's
-// windows, the bitmap of all rows (12 bytes each: it depends on both maxima and on the row count) and the note and bend
-// rows from `first_row` on — not the maps, and nothing else that grows with the session.
-//
-// bp_stream_keep_rolling keeps, instead, the last `horizon` rows (and the room of a tail) in a ring of rows, absolute row r at
-// slot r % roll_cap, and beside it a table of stats records, one per block of 64 absolute rows (note_device.hip, "the rolling
-// horizon").  bp_stream_candidates_rolling decodes rows [a, T), a = max(0, T - horizon), as a whole track: the record of that
-// slice is joined from the table's whole blocks and a scan of the edge rows, the bitmap and the bends count their frames from
-// a.  Nothing such a stream owns, sends home or computes per update grows with its age.
+// bp_stream_keep and bp_stream_keep_rolling give a stream ONE store of retained rows (bp_stream_state::KeptRows): the three
+// maps of its rows (1,760 bytes per row), frequency-constrained, in a ring of `cap` rows, absolute row r at slot r % cap, that
+// holds the last `horizon` rows and the room of a tail (note_device.hip, "the rows a stream retains").  Final rows enter it
+// as they are emitted, the rows of a tail at every update, both through launch_ring_put.  An update (queue_update) decodes
+// rows [a, T), a = max(0, T - horizon), as a whole track — their stats record, the bitmap (12 bytes a row: it depends on
+// both maxima and on the row count) and the bends, all counted from a — and sends home into the caller's host rings the
+// bitmap and the note and bend rows the caller does not hold yet: not the maps.
+//   * bp_stream_keep reserves cap = horizon = max_rows + a tail's room: the ring never wraps, a stays 0, the caller's linear
+//     arrays are host rings that never wrap either, and a step past max_rows is refused.  The extrema of the final rows are
+//     carried in one record, which they join as they are emitted; an update joins the tail to a copy of it.
+//   * bp_stream_keep_rolling reserves horizon_rows + a tail's room.  Rows leave the slice, which one record cannot follow, so
+//     the final rows fill a table of records, one per block of 64 absolute rows, and an update joins the record of the slice
+//     from the table's whole blocks and a scan of the edge rows.  Nothing such a stream owns, sends home or computes per
+//     update grows with its age.
 //
 // A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the
 // handle's device and deletes the state, and an open or keep that fails leaves nothing behind.
@@ -69,18 +72,17 @@ struct bp_stream_state {
   int64_t w_next = 0;    // first window that has not run
   int64_t rows_out = 0;  // rows emitted
   bool finished = false, broken = false;
-  // bp_stream_keep: the maps of the rows emitted so far ([keep_cap] note, onset, contour: max_rows + the room of a tail),
-  // frequency-constrained for `prm`, and behind them two stats records: of the kept rows, and of an update (kept + tail)
-  bool keep = false;
+  // bp_stream_keep / bp_stream_keep_rolling: the maps of the last `horizon` rows and a tail's room ([cap] note, onset, contour;
+  // absolute row r at slot r % cap), frequency-constrained for `prm`, and the stats records of note_device.hip that carry
+  // their extrema: the record the final rows join (table: the block table of a rolling horizon) and, last, an update's
+  struct KeptRows {
+    int64_t cap = 0, horizon = 0;  // cap == 0: the stream retains nothing
+    int64_t limit = INT64_MAX;     // final rows a step may reach: bp_stream_keep reserves no more
+    bool table = false;
+    DeviceBuffer<float> rows, rec;
+  } kept;
   bp_note_params prm{};
   int lo = 0, hi = 88;
-  int64_t max_rows = 0, keep_cap = 0;
-  DeviceBuffer<float> kept;
-  // bp_stream_keep_rolling: the last `horizon` rows of the maps and a tail's room in a ring ([roll_cap] note, onset, contour;
-  // absolute row r at slot r % roll_cap), frequency-constrained for `prm`; the block table and the update's record
-  bool rolling = false;
-  int64_t horizon = 0, roll_cap = 0;
-  DeviceBuffer<float> roll, roll_rec;
 #ifdef BP_AB_KERNELS
   // bp_ab_stream_poison (the A/B library only): the cell of the kept copy that becomes a NaN when its row is written
   int64_t ab_nan_row = -1;
@@ -143,28 +145,30 @@ int stream_taps(bp_handle h, bp_stream_state* s) {
 constexpr int64_t kTailRows = 2 * BP_FRAMES_PER_WINDOW;
 constexpr int64_t kStatsFloats = 4;  // a stats record of note_device.hip: 16 bytes
 
-Maps kept_maps(const bp_stream_state* s) { return maps_at(s->kept, s->keep_cap); }
 Maps rows_from(const Maps& m, int64_t r) { return {m.note + r * kFreqN, m.onset + r * kFreqN, m.contour + r * kFreqC}; }
-void* kept_stats(const bp_stream_state* s, int which) { return s->kept + s->keep_cap * kMapsRow + which * kStatsFloats; }
+int64_t n_records(const bp_stream_state::KeptRows& k) { return k.table ? note_ring_records(k.cap) : 2; }
+float* update_record(const bp_stream_state::KeptRows& k) { return k.rec + (n_records(k) - 1) * kStatsFloats; }
 int64_t kept_bytes(const bp_stream_state* s) {
-  if (s->rolling) return (s->roll_cap * kMapsRow + note_ring_records(s->roll_cap) * kStatsFloats) * 4;
-  return s->keep ? (s->keep_cap * kMapsRow + 2 * kStatsFloats) * 4 : 0;
+  return s->kept.cap ? (s->kept.cap * kMapsRow + n_records(s->kept) * kStatsFloats) * 4 : 0;
 }
 
-// Test hook of the A/B library (bp_ab_stream_poison): rows [r0, r1) of the kept copy have just been written and have not
-// joined a stats record yet; the poisoned cell, if it lies in them, becomes a quiet NaN.  The product library has no such hook.
+// Rows [r0, r1) of the linear device maps `src` (its row 0 is row r0; r1 - r0 <= cap) go to their slots of the store,
+// frequency-constrained on the way; they have not joined a stats record yet.  In the A/B library the cell that
+// bp_ab_stream_poison names, if it lies in them, then becomes a quiet NaN — after the constraint, so a poisoned cell outside
+// [lo, hi) stays a NaN in either mode.  The product library has no such hook.
+int put_rows(bp_handle h, const bp_stream_state* s, const Maps& src, int64_t r0, int64_t r1) {
+  const auto& k = s->kept;
+  launch_ring_put(src.note, src.onset, src.contour, k.rows, k.cap, r0, r1 - r0, s->lo, s->hi, h->stream);
+  BP_HIP(hipGetLastError());
 #ifdef BP_AB_KERNELS
-int ab_poison(bp_handle h, const bp_stream_state* s, int64_t r0, int64_t r1) {
-  if (s->ab_nan_row < r0 || s->ab_nan_row >= r1) return BP_OK;
-  const Maps kept = s->rolling ? maps_at(s->roll, s->roll_cap) : kept_maps(s);
-  const int64_t at = s->rolling ? s->ab_nan_row % s->roll_cap : s->ab_nan_row;  // a rolling stream: the row's slot
-  float* cell = (s->ab_nan_map ? kept.onset : kept.note) + at * kFreqN + s->ab_nan_bin;
-  BP_HIP(hipMemsetD32Async(cell, 0x7fc00000, 1, h->stream));
+  if (s->ab_nan_row >= r0 && s->ab_nan_row < r1) {
+    const Maps kept = maps_at(k.rows, k.cap);
+    float* cell = (s->ab_nan_map ? kept.onset : kept.note) + (s->ab_nan_row % k.cap) * kFreqN + s->ab_nan_bin;
+    BP_HIP(hipMemsetD32Async(cell, 0x7fc00000, 1, h->stream));
+  }
+#endif
   return BP_OK;
 }
-#else
-inline int ab_poison(bp_handle, const bp_stream_state*, int64_t, int64_t) { return BP_OK; }
-#endif
 
 // the tail of the signal a peek makes (samples n_res ... resampled length) fits the ring's free room: see the file header
 bool tail_fits(const bp_stream_state* s) {
@@ -189,6 +193,21 @@ struct Entry {
   // the plan's copy of the counters
   int64_t n_res, w_next, n_total;
 };
+
+// a stream's entry of a step: the plan's copies start as the stream's counters
+Entry plan_entry(bp_stream_state* s, Mode mode, int64_t n_frames, int64_t rows, const Maps& user) {
+  Entry e{};
+  e.s = s;
+  e.finish = mode != kPush;
+  e.peek = mode == kPeek;
+  e.n_frames = n_frames;
+  e.rows = rows;
+  e.user = user;
+  e.n_res = s->n_res;
+  e.w_next = s->w_next;
+  e.n_total = e.finish ? bp_handle_resampled_length(s->h, s->n_in, s->sample_rate) : -1;
+  return e;
+}
 
 struct Ingest {
   int e;
@@ -305,24 +324,18 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
     launch_unwrap_streams(d_segs + r.seg0, r.n_segs, r.n_slots, h->note, h->onset, h->contour, q);
   }
   BP_HIP(hipGetLastError());
-  // streams that keep their maps: the final rows of this step go behind the kept ones and join the stats record
+  // streams that retain their maps: the final rows of this step go to their slots and join the record or the table — the
+  // last `cap` of them at most: a row further back has left every later slice, and so has the block it starts
   for (const Entry& e : es) {
     const bp_stream_state* s = e.s;
-    if (s->rolling && !e.peek && e.rows > 0) {
-      // the last roll_cap of them at most: a row further back has left every later slice, and so has the block it starts
-      const int64_t r1 = s->rows_out + e.rows, r0 = std::max(s->rows_out, r1 - s->roll_cap), skip = r0 - s->rows_out;
-      launch_ring_put(e.out.note + skip * kFreqN, e.out.onset + skip * kFreqN, e.out.contour + skip * kFreqC, s->roll, s->roll_cap,
-                      r0, r1 - r0, s->lo, s->hi, q);
-      if ((rc = ab_poison(h, s, r0, r1))) return rc;
-      launch_ring_fold(s->roll, s->roll_cap, r0, r1, skip ? 0 : r0, s->prm.infer_onsets != 0, s->roll_rec, q);
-      BP_HIP(hipGetLastError());
-    }
-    if (!s->keep || e.peek || e.rows == 0) continue;
-    const Maps kept = kept_maps(s);
-    if ((rc = copy_maps(h, rows_from(kept, s->rows_out), e.out, e.rows, hipMemcpyDeviceToDevice))) return rc;
-    if ((rc = ab_poison(h, s, s->rows_out, s->rows_out + e.rows))) return rc;
-    launch_note_fold(kept.note, kept.onset, s->rows_out, s->rows_out + e.rows, s->lo, s->hi, s->prm.infer_onsets != 0,
-                     kept_stats(s, 0), q);
+    const auto& k = s->kept;
+    if (!k.cap || e.peek || e.rows == 0) continue;
+    const int64_t r1 = s->rows_out + e.rows, r0 = std::max(s->rows_out, r1 - k.cap);
+    if ((rc = put_rows(h, s, rows_from(e.out, r0 - s->rows_out), r0, r1))) return rc;
+    if (k.table)
+      launch_ring_fold(k.rows, k.cap, r0, r1, r0 > s->rows_out ? 0 : r0, s->prm.infer_onsets != 0, k.rec, q);
+    else  // the ring never wraps: linear maps
+      launch_note_fold(k.rows, k.rows + k.cap * kFreqN, r0, r1, s->prm.infer_onsets != 0, k.rec, q);
     BP_HIP(hipGetLastError());
   }
   for (const Entry& e : es)
@@ -330,125 +343,77 @@ int queue_step(bp_handle h, std::vector<Entry>& es, const void* const* pcm, int 
   return BP_OK;
 }
 
-// An update of a stream that keeps its maps: the peek's rows behind the kept ones (device to device, nothing committed), a
-// copy of the stats record joined with them, the bitmap of all T rows, the bends of the rows from first_row on, and home.
-int queue_update(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t first_row, float* note_out, uint8_t* cand_bits,
-                 int8_t* bend_map, std::vector<WindowSeg>& segs) {
-  hipStream_t q = h->stream;
-  const void* tab = nullptr;
-  const double* gauss = nullptr;
-  int rc = note_tables(h, &tab, &gauss);
-  if (rc) return rc;
-  const int64_t T = s->rows_out + tail_rows, n_new = T - first_row;
-  const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15, bend_bytes = n_new * kFreqN;
-  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_bytes)));
-  uint8_t* d_bits = h->nd_buf;
-  int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
-  const Maps kept = kept_maps(s);
-  if (tail_rows > 0) {
-    std::vector<Entry> es(1);
-    Entry& e = es[0];
-    e = Entry{};
-    e.s = s;
-    e.finish = e.peek = true;
-    e.rows = tail_rows;
-    e.user = rows_from(kept, s->rows_out);
-    e.n_res = s->n_res;
-    e.w_next = s->w_next;
-    e.n_total = bp_handle_resampled_length(h, s->n_in, s->sample_rate);
-    if ((rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
-  }
-  const int infer = s->prm.infer_onsets != 0;
-  const bool want_bends = s->prm.include_pitch_bends != 0 && bend_map != nullptr;
-  void* st = kept_stats(s, 1);
-  BP_HIP(hipMemcpyAsync(st, kept_stats(s, 0), kStatsFloats * 4, hipMemcpyDeviceToDevice, q));
-  if ((rc = ab_poison(h, s, s->rows_out, T))) return rc;
-  launch_note_fold(kept.note, kept.onset, s->rows_out, T, s->lo, s->hi, infer, st, q);
-  launch_note_peaks(kept.note, kept.onset, T, infer, s->prm.onset_threshold, st, d_bits, q);
-  if (want_bends) launch_note_bends(kept.contour + first_row * kFreqC, n_new, tab, gauss, d_bend, q);
-  BP_HIP(hipGetLastError());
-  BP_HIP(hipMemcpyAsync(h->nd_stats_host, st, kStatsFloats * 4, hipMemcpyDeviceToHost, q));
-  BP_HIP(hipMemcpyAsync(cand_bits, d_bits, (size_t)bits_bytes, hipMemcpyDeviceToHost, q));
-  if (n_new > 0) {
-    BP_HIP(hipMemcpyAsync(note_out + first_row * kFreqN, kept.note + first_row * kFreqN, (size_t)n_new * kFreqN * 4,
-                          hipMemcpyDeviceToHost, q));
-    if (want_bends) BP_HIP(hipMemcpyAsync(bend_map + first_row * kFreqN, d_bend, (size_t)bend_bytes, hipMemcpyDeviceToHost, q));
-  }
-  return BP_OK;
-}
-
-// The tail of a rolling stream: the peek's rows through the step's scratch into the slots behind the final rows (nothing
-// committed; the next final rows overwrite them).
-int queue_tail_rolling(bp_handle h, bp_stream_state* s, int64_t tail_rows, std::vector<WindowSeg>& segs) {
+// The tail of a stream that retains its maps: the peek's rows through the step's scratch into the slots behind the final
+// rows (nothing committed; the next final rows overwrite them).
+int queue_tail(bp_handle h, bp_stream_state* s, int64_t tail_rows, std::vector<WindowSeg>& segs) {
   if (tail_rows <= 0) return BP_OK;
-  int rc;
   BP_HIP(h->st_out.reserve((size_t)(tail_rows * kMapsRow)));
-  std::vector<Entry> es(1);
-  Entry& e = es[0];
-  e = Entry{};
-  e.s = s;
-  e.finish = e.peek = true;
-  e.rows = tail_rows;
-  e.user = maps_at(h->st_out, tail_rows);
-  e.n_res = s->n_res;
-  e.w_next = s->w_next;
-  e.n_total = bp_handle_resampled_length(h, s->n_in, s->sample_rate);
-  if ((rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
-  launch_ring_put(e.user.note, e.user.onset, e.user.contour, s->roll, s->roll_cap, s->rows_out, tail_rows, s->lo, s->hi, h->stream);
-  BP_HIP(hipGetLastError());
-  return ab_poison(h, s, s->rows_out, s->rows_out + tail_rows);
+  std::vector<Entry> es{plan_entry(s, kPeek, 0, tail_rows, maps_at(h->st_out, tail_rows))};
+  if (int rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs)) return rc;
+  return put_rows(h, s, es[0].user, s->rows_out, s->rows_out + tail_rows);
 }
 
-// rows [r0, r1) of a linear device block (row_bytes each) to a host ring of ring_rows rows: one copy, two where they wrap
-int copy_to_host_ring(bp_handle h, void* ring, int64_t ring_rows, const void* src, int64_t row_bytes, int64_t r0, int64_t r1) {
+// Rows [r0, r1) from the device to a host ring of ring_rows rows (row r at r % ring_rows).  The source is a device ring of
+// src_rows rows, row r at r % src_rows, or (src_rows = kLinear) a linear block whose first row is r0.  One copy, and one
+// more wherever either ring wraps.
+constexpr int64_t kLinear = 0;
+int copy_to_host_ring(bp_handle h, void* ring, int64_t ring_rows, const void* src, int64_t src_rows, int64_t row_bytes, int64_t r0,
+                      int64_t r1) {
   for (int64_t r = r0; r < r1;) {
-    const int64_t at = r % ring_rows, n = std::min(r1 - r, ring_rows - at);
-    BP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ring) + at * row_bytes, static_cast<const uint8_t*>(src) + (r - r0) * row_bytes,
+    const int64_t at = r % ring_rows, from = src_rows ? r % src_rows : r - r0;
+    const int64_t n = std::min({r1 - r, ring_rows - at, src_rows ? src_rows - from : r1 - r});
+    BP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ring) + at * row_bytes, static_cast<const uint8_t*>(src) + from * row_bytes,
                           (size_t)(n * row_bytes), hipMemcpyDeviceToHost, h->stream));
     r += n;
   }
   return BP_OK;
 }
 
-// An update of a rolling stream: the tail into the ring, the record of the slice [a, T), its bitmap, the bends and the
-// un-wrapped note rows from n0 = max(held, a) on, and home into the caller's rings.
-int queue_update_rolling(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t held, float* note_ring, uint8_t* bits_ring,
-                         int8_t* bend_ring, int64_t ring_rows, std::vector<WindowSeg>& segs) {
+// An update of a stream that retains its maps: the tail into the store, the record of the slice [a, T), its bitmap, the
+// bends of the rows from n0 = max(held, a) on, and home into the caller's rings of ring_rows rows — the bitmap of the whole
+// slice, the note rows from n0 on straight from their slots, their bends.
+int queue_update(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t held, float* note_ring, uint8_t* bits_ring,
+                 int8_t* bend_ring, int64_t ring_rows, std::vector<WindowSeg>& segs) {
   hipStream_t q = h->stream;
+  const auto& k = s->kept;
   const void* tab = nullptr;
   const double* gauss = nullptr;
   int rc = note_tables(h, &tab, &gauss);
   if (rc) return rc;
-  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->horizon), n0 = std::max(held, a), n_new = T - n0;
-  const int64_t bits_bytes = (T - a) * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15;
-  const int64_t bend_bytes = n_new * kFreqN, bend_room = (bend_bytes + 15) & ~(int64_t)15;
-  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_room + n_new * kFreqN * 4)));
+  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, k.horizon), n0 = std::max(held, a), n_new = T - n0;
+  const int64_t bits_bytes = (T - a) * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15, bend_bytes = n_new * kFreqN;
+  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_bytes)));
   uint8_t* d_bits = h->nd_buf;
   int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
-  float* d_note = reinterpret_cast<float*>(h->nd_buf.as<uint8_t>() + bits_room + bend_room);
-  if ((rc = queue_tail_rolling(h, s, tail_rows, segs))) return rc;
+  if ((rc = queue_tail(h, s, tail_rows, segs))) return rc;
+  const int infer = s->prm.infer_onsets != 0;
   const bool want_bends = s->prm.include_pitch_bends != 0 && bend_ring != nullptr;
-  void* st = note_ring_stats(s->roll_rec, s->roll_cap);
-  launch_ring_stats(s->roll, s->roll_cap, a, s->rows_out, T, s->prm.infer_onsets != 0, s->roll_rec, q);
-  launch_ring_peaks(s->roll, s->roll_cap, a, T, s->prm.infer_onsets != 0, s->prm.onset_threshold, st, d_bits, q);
-  if (want_bends) launch_ring_bends(s->roll, s->roll_cap, n0, n_new, tab, gauss, d_bend, q);
-  launch_ring_gather_note(s->roll, s->roll_cap, n0, n_new, d_note, q);
+  float* st = update_record(k);
+  if (k.table) {
+    launch_ring_stats(k.rows, k.cap, a, s->rows_out, T, infer, k.rec, q);
+  } else {  // a copy of the record of the final rows, joined by the tail
+    BP_HIP(hipMemcpyAsync(st, k.rec, kStatsFloats * 4, hipMemcpyDeviceToDevice, q));
+    launch_note_fold(k.rows, k.rows + k.cap * kFreqN, s->rows_out, T, infer, st, q);
+  }
+  launch_ring_peaks(k.rows, k.cap, a, T, infer, s->prm.onset_threshold, st, d_bits, q);
+  if (want_bends) launch_ring_bends(k.rows, k.cap, n0, n_new, tab, gauss, d_bend, q);
   BP_HIP(hipGetLastError());
   BP_HIP(hipMemcpyAsync(h->nd_stats_host, st, kStatsFloats * 4, hipMemcpyDeviceToHost, q));
-  if ((rc = copy_to_host_ring(h, bits_ring, ring_rows, d_bits, BP_NOTE_CAND_ROW_BYTES, a, T))) return rc;
-  if ((rc = copy_to_host_ring(h, note_ring, ring_rows, d_note, kFreqN * 4, n0, T))) return rc;
-  if (want_bends && (rc = copy_to_host_ring(h, bend_ring, ring_rows, d_bend, kFreqN, n0, T))) return rc;
+  if ((rc = copy_to_host_ring(h, bits_ring, ring_rows, d_bits, kLinear, BP_NOTE_CAND_ROW_BYTES, a, T))) return rc;
+  if ((rc = copy_to_host_ring(h, note_ring, ring_rows, k.rows, k.cap, kFreqN * 4, n0, T))) return rc;
+  if (want_bends && (rc = copy_to_host_ring(h, bend_ring, ring_rows, d_bend, kLinear, kFreqN, n0, T))) return rc;
   return BP_OK;
 }
 
-// the slice [a, T) of the ring, linear, to the caller's host maps: one copy per map, two where the slots wrap
+// the slice [a, T) of the store, linear, to the caller's host maps: one copy per map, two where the slots wrap
 int queue_rolling_maps(bp_handle h, bp_stream_state* s, int64_t tail_rows, const Maps& out, std::vector<WindowSeg>& segs) {
   int rc;
-  if ((rc = queue_tail_rolling(h, s, tail_rows, segs))) return rc;
-  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->horizon);
-  const Maps ring = maps_at(s->roll, s->roll_cap);
+  if ((rc = queue_tail(h, s, tail_rows, segs))) return rc;
+  const auto& k = s->kept;
+  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, k.horizon);
+  const Maps ring = maps_at(k.rows, k.cap);
   for (int64_t r = a; r < T;) {
-    const int64_t at = r % s->roll_cap, n = std::min(T - r, s->roll_cap - at);
+    const int64_t at = r % k.cap, n = std::min(T - r, k.cap - at);
     if ((rc = copy_maps(h, rows_from(out, r - a), rows_from(ring, at), n, hipMemcpyDeviceToHost))) return rc;
     r += n;
   }
@@ -479,32 +444,24 @@ int step(bp_handle h, const char* what, int64_t n, const bp_stream* streams, con
     if (s->finished) return invalid("a finished stream: only bp_stream_close is valid");
     for (int64_t j = 0; j < i; ++j)
       if (streams[j] == s) return invalid("the same stream twice in one step");
-    Entry& e = es[(size_t)i];
-    e = Entry{};
-    e.s = s;
-    e.finish = finish_streams;
-    e.peek = mode == kPeek;
-    e.n_frames = finish_streams ? 0 : n_frames[i];
-    if (e.n_frames < 0 || (e.n_frames > 0 && !pcm[i])) return invalid("negative n_frames or null pcm");
-    e.rows = rows_of_step(s, e.n_frames, finish_streams);
-    if (capacity_rows[i] < e.rows)
-      return invalid("capacity_rows " + std::to_string(capacity_rows[i]) + " is too small for the " + std::to_string(e.rows) +
+    const int64_t n_in = finish_streams ? 0 : n_frames[i];
+    if (n_in < 0 || (n_in > 0 && !pcm[i])) return invalid("negative n_frames or null pcm");
+    const int64_t n_rows = rows_of_step(s, n_in, finish_streams);
+    if (capacity_rows[i] < n_rows)
+      return invalid("capacity_rows " + std::to_string(capacity_rows[i]) + " is too small for the " + std::to_string(n_rows) +
                      " rows of this step (bp_stream_rows_bound); nothing was taken from the stream");
-    if (e.rows > 0 && (!note[i] || !onset[i] || !contour[i])) return invalid("null output pointer");
+    if (n_rows > 0 && (!note[i] || !onset[i] || !contour[i])) return invalid("null output pointer");
     if (mode == kPeek && !tail_fits(s)) {
       h->err = std::string(what) + ": the end of the resampled signal does not fit the stream's ring";
       return BP_ERR_UNSUPPORTED;
     }
-    if (mode != kPeek && s->keep && s->rows_out + e.rows > s->max_rows) {
-      h->err = std::string(what) + ": the " + std::to_string(e.rows) + " rows of this step would exceed the " +
-               std::to_string(s->max_rows) + " rows bp_stream_keep reserved; nothing was taken from the stream";
+    if (mode != kPeek && s->rows_out + n_rows > s->kept.limit) {
+      h->err = std::string(what) + ": the " + std::to_string(n_rows) + " rows of this step would exceed the " +
+               std::to_string(s->kept.limit) + " rows bp_stream_keep reserved; nothing was taken from the stream";
       return BP_ERR_OUT_OF_MEMORY;
     }
-    e.user = {note[i], onset[i], contour[i]};
-    e.n_res = s->n_res;
-    e.w_next = s->w_next;
-    e.n_total = finish_streams ? bp_handle_resampled_length(h, s->n_in, s->sample_rate) : -1;
-    work = work || e.n_frames > 0 || mode == kFinish || e.rows > 0;
+    es[(size_t)i] = plan_entry(s, mode, n_in, n_rows, {note[i], onset[i], contour[i]});
+    work = work || n_in > 0 || mode == kFinish || n_rows > 0;
   }
   if (work) {
     BP_HIP(hipSetDevice(h->device));
@@ -616,70 +573,127 @@ int bp_streams_push(bp_handle h, int64_t n, const bp_stream* streams, const void
               rows, kPush);
 }
 
-int bp_stream_keep(bp_stream s, const bp_note_params* params, int64_t max_rows) {
-  if (!s) return BP_ERR_INVALID_ARG;
+// bp_stream_keep and bp_stream_keep_rolling after the checks of their own argument: from now on the stream retains its maps
+// in a ring of `rows` rows and a tail's room.  table: `rows` is a rolling horizon.  No table: they are all the final rows the
+// stream may emit, and the horizon is the whole ring — the first row of a slice stays 0.
+static int keep_rows(bp_stream s, const char* what, const bp_note_params* params, int64_t rows, bool table) {
   bp_handle h = s->h;
   auto invalid = [&](const char* why) {
-    h->err = std::string("bp_stream_keep: ") + why;
+    h->err = std::string(what) + ": " + why;
     return BP_ERR_INVALID_ARG;
   };
-  if (!params || max_rows <= 0) return invalid("null params or a max_rows that is not positive");
+  auto& k = s->kept;
   if (s->broken || s->finished) return invalid("a finished or broken stream");
-  if (s->keep) return invalid("the stream keeps its maps already (the decoding parameters are fixed by the first call)");
-  if (s->rolling) return invalid("the stream keeps a rolling horizon already (bp_stream_keep_rolling): one or the other");
+  if (k.cap && !k.table)
+    return invalid(table ? "the stream keeps all its maps already (bp_stream_keep): one or the other"
+                         : "the stream keeps its maps already (the decoding parameters are fixed by the first call)");
+  if (k.cap)
+    return invalid(table ? "the stream keeps a rolling horizon already (the parameters are fixed by the first call)"
+                         : "the stream keeps a rolling horizon already (bp_stream_keep_rolling): one or the other");
   if (s->rows_out > 0) return invalid("rows have left the stream already: call it before the first window completes");
   BP_HIP(hipSetDevice(h->device));
   if (int rc = note_tables(h, nullptr, nullptr)) return rc;
-  const int64_t cap = max_rows + kTailRows;
-  if (cap > (int64_t)1 << 40) return invalid("max_rows is out of range");
-  BP_HIP(s->kept.reserve((size_t)(cap * kMapsRow + 2 * kStatsFloats)));
-  s->keep_cap = cap;
-  launch_note_stats_init(kept_stats(s, 0), h->stream);
-  if (int rc = finish(h, hipGetLastError() == hipSuccess ? BP_OK : BP_ERR_HIP)) {
-    (void)s->kept.reset();
-    return rc;
+  const int64_t cap = rows + kTailRows;
+  if (!table && cap > (int64_t)1 << 40) return invalid("max_rows is out of range");
+  // The record that final rows join starts with the initial values; a block table starts empty: a block is written anew by
+  // the step that emits its first row.  A setup that fails frees what it reserved.
+  DeviceBuffer<float> maps, rec;
+  BP_HIP(maps.reserve((size_t)(cap * kMapsRow)));
+  BP_HIP(rec.reserve((size_t)((table ? note_ring_records(cap) : 2) * kStatsFloats)));
+  if (!table) {
+    launch_note_stats_init(rec, h->stream);
+    if (int rc = finish(h, hipGetLastError() == hipSuccess ? BP_OK : BP_ERR_HIP)) return rc;
   }
+  k.rows = std::move(maps), k.rec = std::move(rec);
+  k.cap = cap, k.horizon = table ? rows : cap, k.table = table;
+  if (!table) k.limit = rows;
   s->prm = *params;
   bp_internal_freq_limits(params, &s->lo, &s->hi);
-  s->max_rows = max_rows;
-  s->keep = true;
   return BP_OK;
 }
 
-int bp_stream_candidates(bp_stream s, int with_tail, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int64_t first_row,
-                         int64_t capacity_rows, int64_t* n_rows, int* status) {
+int bp_stream_keep(bp_stream s, const bp_note_params* params, int64_t max_rows) {
   if (!s) return BP_ERR_INVALID_ARG;
+  if (!params || max_rows <= 0) {
+    s->h->err = "bp_stream_keep: null params or a max_rows that is not positive";
+    return BP_ERR_INVALID_ARG;
+  }
+  return keep_rows(s, "bp_stream_keep", params, max_rows, false);
+}
+
+// the arguments of the calls that read a stream's retained rows (table: those of a rolling horizon), before anything is
+// queued; *tail_rows: the rows of the peek.  A finished stream has no tail: its final rows are the whole track.  Whether the
+// tail fits is tail_refused's verdict, which each call applies where it always has among its own checks.
+static int check_kept(bp_stream s, const char* what, bool table, int with_tail, int64_t* tail_rows) {
   bp_handle h = s->h;
-  auto invalid = [&](const std::string& why) {
-    h->err = "bp_stream_candidates: " + why;
+  auto invalid = [&](const char* why) {
+    h->err = std::string(what) + ": " + why;
     return BP_ERR_INVALID_ARG;
   };
-  if (!n_rows || !status) return invalid("null n_rows / status");
-  if (!s->keep) return invalid("the stream does not keep its maps (bp_stream_keep)");
+  if (!s->kept.cap || s->kept.table != table)
+    return invalid(table ? "the stream keeps no rolling horizon (bp_stream_keep_rolling)" : "the stream does not keep its maps (bp_stream_keep)");
   if (s->broken) return invalid("a stream whose earlier call failed on the device: only bp_stream_close is valid");
-  // every argument, before anything is queued.  A finished stream has no tail: its kept rows are the whole track.
-  const int64_t tail_rows = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
+  *tail_rows = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
+  return BP_OK;
+}
+
+static int tail_refused(bp_stream s, const char* what, bool table, int64_t tail_rows) {
+  if (tail_rows <= kTailRows && (tail_rows == 0 || tail_fits(s))) return BP_OK;
+  s->h->err = std::string(what) + ": the end of the signal does not fit the stream's ring or the room behind the " +
+              (table ? "final" : "kept") + " rows";
+  return BP_ERR_UNSUPPORTED;
+}
+
+// bp_stream_candidates and bp_stream_candidates_rolling: an update into host rings of ring_rows rows of which the caller
+// holds the rows before `held`, an argument the caller knows as `held_name`
+static int candidates(bp_stream s, const char* what, bool table, int with_tail, float* note_ring, uint8_t* bits_ring,
+                      int8_t* bend_ring, int64_t ring_rows, int64_t held, const char* held_name, int64_t* first_row,
+                      int64_t* n_rows, int* status) {
+  bp_handle h = s->h;
+  auto invalid = [&](const std::string& why) {
+    h->err = std::string(what) + ": " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  // every argument, before anything is queued
+  int64_t tail_rows = 0;
+  if (int rc = check_kept(s, what, table, with_tail, &tail_rows)) return rc;
+  if (int rc = table ? tail_refused(s, what, table, tail_rows) : BP_OK) return rc;
   const int64_t T = s->rows_out + tail_rows;
-  if (first_row < 0 || first_row > s->rows_out)
-    return invalid("first_row " + std::to_string(first_row) + " is not in 0 ... " + std::to_string(s->rows_out) + ", the final rows");
-  if (capacity_rows < T)
-    return invalid("capacity_rows " + std::to_string(capacity_rows) + " is too small for the " + std::to_string(T) + " rows");
-  if (T > 0 && (!note_out || !cand_bits)) return invalid("null output pointer");
-  if (tail_rows > kTailRows || (tail_rows > 0 && !tail_fits(s))) {
-    h->err = "bp_stream_candidates: the end of the signal does not fit the stream's ring or the room behind the kept rows";
-    return BP_ERR_UNSUPPORTED;
-  }
+  if (table && ring_rows < s->kept.cap)
+    return invalid("ring_rows " + std::to_string(ring_rows) + " is less than the " + std::to_string(s->kept.cap) +
+                   " rows of the stream's ring (horizon_rows + 284)");
+  if (held < 0 || held > s->rows_out)
+    return invalid(std::string(held_name) + " " + std::to_string(held) + " is not in 0 ... " + std::to_string(s->rows_out) +
+                   ", the final rows");
+  if (!table && ring_rows < T)
+    return invalid("capacity_rows " + std::to_string(ring_rows) + " is too small for the " + std::to_string(T) + " rows");
+  if (T > 0 && (!note_ring || !bits_ring)) return invalid("null output pointer");
+  if (int rc = table ? BP_OK : tail_refused(s, what, table, tail_rows)) return rc;
+  *first_row = bp_stream_horizon_first_row(T, s->kept.horizon);
   *n_rows = T;
   *status = s->prm.onset_threshold > 0.0 ? 0 : 1;
   if (T == 0) return BP_OK;
   BP_HIP(hipSetDevice(h->device));
   std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
-  if (int rc = finish(h, queue_update(h, s, tail_rows, first_row, note_out, cand_bits, bend_map, segs))) {
+  if (int rc = finish(h, queue_update(h, s, tail_rows, held, note_ring, bits_ring, bend_ring, ring_rows, segs))) {
     s->broken = true;
     return rc;
   }
-  if (h->nd_stats_host[1]) *status = 1;  // a NaN in the maps: the host decodes the maps themselves
+  if (h->nd_stats_host[1]) *status = 1;  // a NaN in the slice: the host decodes the maps themselves
   return BP_OK;
+}
+
+// the caller's linear arrays of capacity_rows rows are host rings that never wrap: the slice starts at row 0
+int bp_stream_candidates(bp_stream s, int with_tail, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int64_t first_row,
+                         int64_t capacity_rows, int64_t* n_rows, int* status) {
+  if (!s) return BP_ERR_INVALID_ARG;
+  if (!n_rows || !status) {
+    s->h->err = "bp_stream_candidates: null n_rows / status";
+    return BP_ERR_INVALID_ARG;
+  }
+  int64_t a = 0;
+  return candidates(s, "bp_stream_candidates", false, with_tail, note_out, cand_bits, bend_map, capacity_rows, first_row, "first_row",
+                    &a, n_rows, status);
 }
 
 int64_t bp_stream_horizon_first_row(int64_t n_rows, int64_t horizon_rows) {
@@ -688,85 +702,26 @@ int64_t bp_stream_horizon_first_row(int64_t n_rows, int64_t horizon_rows) {
 
 int bp_stream_keep_rolling(bp_stream s, const bp_note_params* params, int64_t horizon_rows) {
   if (!s) return BP_ERR_INVALID_ARG;
-  bp_handle h = s->h;
-  auto invalid = [&](const char* why) {
-    h->err = std::string("bp_stream_keep_rolling: ") + why;
+  const char* why = !params ? "null params"
+                    : horizon_rows < 3 || horizon_rows > (int64_t)1 << 40
+                        ? "horizon_rows is out of range (at least 3: a peak needs a row on either side)"
+                        : nullptr;
+  if (why) {
+    s->h->err = std::string("bp_stream_keep_rolling: ") + why;
     return BP_ERR_INVALID_ARG;
-  };
-  if (!params) return invalid("null params");
-  if (horizon_rows < 3 || horizon_rows > (int64_t)1 << 40)
-    return invalid("horizon_rows is out of range (at least 3: a peak needs a row on either side)");
-  if (s->broken || s->finished) return invalid("a finished or broken stream");
-  if (s->keep) return invalid("the stream keeps all its maps already (bp_stream_keep): one or the other");
-  if (s->rolling) return invalid("the stream keeps a rolling horizon already (the parameters are fixed by the first call)");
-  if (s->rows_out > 0) return invalid("rows have left the stream already: call it before the first window completes");
-  BP_HIP(hipSetDevice(h->device));
-  if (int rc = note_tables(h, nullptr, nullptr)) return rc;
-  // the slice and the two windows of a tail; the block table starts empty: a block is written anew by the step that emits
-  // its first row
-  const int64_t cap = horizon_rows + kTailRows;
-  hipError_t e = s->roll.reserve((size_t)(cap * kMapsRow));
-  if (e == hipSuccess) e = s->roll_rec.reserve((size_t)(note_ring_records(cap) * kStatsFloats));
-  if (e != hipSuccess) {
-    (void)s->roll.reset();
-    (void)s->roll_rec.reset();
-    BP_HIP(e);
   }
-  s->prm = *params;
-  bp_internal_freq_limits(params, &s->lo, &s->hi);
-  s->horizon = horizon_rows;
-  s->roll_cap = cap;
-  s->rolling = true;
-  return BP_OK;
-}
-
-// the arguments of the two calls that read a rolling stream, before anything is queued; *tail_rows: the rows of the peek
-static int check_rolling(bp_stream s, const char* what, int with_tail, int64_t* tail_rows) {
-  bp_handle h = s->h;
-  auto invalid = [&](const char* why) {
-    h->err = std::string(what) + ": " + why;
-    return BP_ERR_INVALID_ARG;
-  };
-  if (!s->rolling) return invalid("the stream keeps no rolling horizon (bp_stream_keep_rolling)");
-  if (s->broken) return invalid("a stream whose earlier call failed on the device: only bp_stream_close is valid");
-  *tail_rows = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
-  if (*tail_rows > kTailRows || (*tail_rows > 0 && !tail_fits(s))) {
-    h->err = std::string(what) + ": the end of the signal does not fit the stream's ring or the room behind the final rows";
-    return BP_ERR_UNSUPPORTED;
-  }
-  return BP_OK;
+  return keep_rows(s, "bp_stream_keep_rolling", params, horizon_rows, true);
 }
 
 int bp_stream_candidates_rolling(bp_stream s, int with_tail, float* note_ring, uint8_t* bits_ring, int8_t* bend_ring,
                                  int64_t ring_rows, int64_t held_rows, int64_t* first_row, int64_t* n_rows, int* status) {
   if (!s) return BP_ERR_INVALID_ARG;
-  bp_handle h = s->h;
-  auto invalid = [&](const std::string& why) {
-    h->err = "bp_stream_candidates_rolling: " + why;
+  if (!first_row || !n_rows || !status) {
+    s->h->err = "bp_stream_candidates_rolling: null first_row / n_rows / status";
     return BP_ERR_INVALID_ARG;
-  };
-  if (!first_row || !n_rows || !status) return invalid("null first_row / n_rows / status");
-  int64_t tail_rows = 0;
-  if (int rc = check_rolling(s, "bp_stream_candidates_rolling", with_tail, &tail_rows)) return rc;
-  if (ring_rows < s->roll_cap)
-    return invalid("ring_rows " + std::to_string(ring_rows) + " is less than the " + std::to_string(s->roll_cap) +
-                   " rows of the stream's ring (horizon_rows + 284)");
-  if (held_rows < 0 || held_rows > s->rows_out)
-    return invalid("held_rows " + std::to_string(held_rows) + " is not in 0 ... " + std::to_string(s->rows_out) + ", the final rows");
-  const int64_t T = s->rows_out + tail_rows;
-  if (T > 0 && (!note_ring || !bits_ring)) return invalid("null output pointer");
-  *first_row = bp_stream_horizon_first_row(T, s->horizon);
-  *n_rows = T;
-  *status = s->prm.onset_threshold > 0.0 ? 0 : 1;
-  if (T == 0) return BP_OK;
-  BP_HIP(hipSetDevice(h->device));
-  std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
-  if (int rc = finish(h, queue_update_rolling(h, s, tail_rows, held_rows, note_ring, bits_ring, bend_ring, ring_rows, segs))) {
-    s->broken = true;
-    return rc;
   }
-  if (h->nd_stats_host[1]) *status = 1;  // a NaN in the slice: the host decodes the maps themselves
-  return BP_OK;
+  return candidates(s, "bp_stream_candidates_rolling", true, with_tail, note_ring, bits_ring, bend_ring, ring_rows, held_rows,
+                    "held_rows", first_row, n_rows, status);
 }
 
 int bp_stream_rolling_maps(bp_stream s, int with_tail, float* note, float* onset, float* contour, int64_t capacity_rows,
@@ -779,8 +734,9 @@ int bp_stream_rolling_maps(bp_stream s, int with_tail, float* note, float* onset
   };
   if (!first_row || !n_rows) return invalid("null first_row / n_rows");
   int64_t tail_rows = 0;
-  if (int rc = check_rolling(s, "bp_stream_rolling_maps", with_tail, &tail_rows)) return rc;
-  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->horizon);
+  if (int rc = check_kept(s, "bp_stream_rolling_maps", true, with_tail, &tail_rows)) return rc;
+  if (int rc = tail_refused(s, "bp_stream_rolling_maps", true, tail_rows)) return rc;
+  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, s->kept.horizon);
   if (capacity_rows < T - a)
     return invalid("capacity_rows " + std::to_string(capacity_rows) + " is too small for the " + std::to_string(T - a) + " rows");
   if (T > a && (!note || !onset || !contour)) return invalid("null output pointer");
@@ -797,11 +753,12 @@ int bp_stream_rolling_maps(bp_stream s, int with_tail, float* note, float* onset
 }
 
 #ifdef BP_AB_KERNELS
-// The A/B library's test hook for the NaN path of a keeping stream (declared nowhere: the tests name it).  From now on the
-// cell (map: 0 note, 1 onset; absolute row; bin) of the KEPT copy is a NaN whenever its row is written there — as a row of
-// a tail at an update, as a final row at the step that emits it.  The rows handed to the caller are not touched.
+// The A/B library's test hook for the NaN path of a stream that retains its maps (declared nowhere: the tests name it).  From
+// now on the cell (map: 0 note, 1 onset; absolute row; bin) of the RETAINED copy is a NaN whenever its row is written there
+// (put_rows) — as a row of a tail at an update, as a final row at the step that emits it.  The rows handed to the caller are
+// not touched.
 int bp_ab_stream_poison(bp_stream s, int map, int64_t row, int bin) {
-  if (!s || (!s->keep && !s->rolling) || map < 0 || map > 1 || row < 0 || bin < 0 || bin >= kFreqN) return BP_ERR_INVALID_ARG;
+  if (!s || !s->kept.cap || map < 0 || map > 1 || row < 0 || bin < 0 || bin >= kFreqN) return BP_ERR_INVALID_ARG;
   s->ab_nan_map = map, s->ab_nan_row = row, s->ab_nan_bin = bin;
   return BP_OK;
 }

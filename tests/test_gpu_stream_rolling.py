@@ -85,12 +85,13 @@ def prefixes(model, nat, x):
     return out
 
 
-def slice_events(maps, a, T, onset_threshold=0.5):
-    """The contract's right-hand side: bp_notes_decode on copies of maps[a:T] as a whole track, frames shifted by a, times of
-    the absolute frames.  -> [(start_frame, end_frame, start_s bits, end_s bits, pitch, amplitude bits, bends)]"""
+def slice_events(maps, a, T, onset_threshold=0.5, base=0):
+    """The contract's right-hand side: bp_notes_decode on copies of rows [a, T) of maps (whose row 0 is absolute row `base`) as
+    a whole track, frames shifted by a, times of the absolute frames.
+    -> [(start_frame, end_frame, start_s bits, end_s bits, pitch, amplitude bits, bends)]"""
     from basic_pitch_amd import note_creation as nc
 
-    sl = {m: np.ascontiguousarray(maps[m][a:T]).copy() for m in MAPS}
+    sl = {m: np.ascontiguousarray(maps[m][a - base : T - base]).copy() for m in MAPS}
     ev, bends, n = nc._decode(sl["note"], sl["onset"], sl["contour"], onset_threshold, 0.3, 11, True, None, None, True, 11, True)
     times = nc.model_frames_to_time(T + 1)
     return [(e.start_frame + a, e.end_frame + a, times[e.start_frame + a].tobytes(), times[e.end_frame + a].tobytes(), e.pitch_midi,
@@ -234,6 +235,43 @@ def test_a_rolling_stream_emits_the_bytes_of_a_plain_stream(model, x, prm):
         for m in MAPS:
             assert p[m].shape == q[m].shape and np.array_equal(p[m].view(np.uint32), q[m].view(np.uint32)), (i, m)
     assert sum(p["note"].shape[0] for p in runs[0]) == 1205
+
+
+def test_rows_go_from_the_device_ring_straight_into_a_host_ring_of_another_size(model, prm):
+    """The note rows of an update are copied home from their slots, split wherever either ring wraps, and the two rings wrap
+    at different rows: H = 200, so 484 slots on the device, beside host rings of 484 + 37 rows.  Twelve pushes of one to two
+    hops of seeded noise (at least 1,562 rows: both rings wrap twice and more); held_rows runs with the final rows.  The new
+    rows [max(held_rows, a), T) of an update cross a wrap of the device ring in some updates, of the host ring in others and
+    of both in at least one: counted here from the row numbers.  After every update the slice of all three rings is, byte
+    for byte, that of an update into fresh rings that hold nothing (held_rows = 0)."""
+    from basic_pitch_amd import note_creation as nc
+
+    rng = np.random.default_rng(5)
+    note, bits, bend = rings(484 + 37)
+    with model.open_stream(22050) as s:
+        s.keep_rolling(prm, 200)
+        held, n_events, wraps = 0, 0, []
+        for _ in range(12):
+            s.push((0.1 * rng.standard_normal(int(rng.integers(HOP, 2 * HOP + 1)))).astype(np.float32))
+            a, T, status = s.candidates_rolling(note, bits, bend, held)
+            n0 = max(held, a)
+            wraps.append((n0 // 484 != (T - 1) // 484, n0 // 521 != (T - 1) // 521))
+            held = s.rows
+            a2, maps = s.rolling_maps()
+            assert (a2, status) == (a, 0) and a == max(0, T - 200) and maps["note"].shape[0] == T - a
+            assert np.array_equal(unwrap(note, a, T).view(np.uint32), maps["note"].view(np.uint32)), T
+            fresh = rings(484 + 37)
+            assert s.candidates_rolling(*fresh, 0) == (a, T, 0)
+            for ring, whole in zip((note, bits, bend), fresh):
+                assert np.array_equal(unwrap(ring, a, T).view(np.uint8), unwrap(whole, a, T).view(np.uint8)), T
+            got = nc.decode_candidates(unwrap(note, a, T), unwrap(bits, a, T), unwrap(bend, a, T), prm, first_frame=a)
+            ref = slice_events(maps, a, T, base=a)
+            print(f"rows [{a}, {T}): {len(got)} events, {len(ref)} in the reference")
+            assert as_tuples(got) == [r[2:] for r in ref], T
+            n_events += len(ref)
+        assert s.rows >= 2 * (484 + 37) + 484, s.rows
+        assert sum(d for d, _ in wraps) >= 2 and sum(h for _, h in wraps) >= 2 and (True, True) in wraps, wraps
+        assert n_events > 0
 
 
 # ---- 4. bounded ------------------------------------------------------------------------------------------------------------------
