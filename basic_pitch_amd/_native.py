@@ -229,6 +229,11 @@ ROLLING_SYMBOLS = [
     "bp_stream_rolling_maps",
     "bp_notes_decode_candidates_at",
 ]
+# every symbol include/basic_pitch_amd_clips.h declares (bound in basic_pitch_amd/clips.py)
+CLIPS_SYMBOLS = [
+    "bp_clips_row_offsets",
+    "bp_infer_clips_candidates",
+]
 
 _lib: Optional[C.CDLL] = None
 

@@ -17,6 +17,7 @@ LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd.so")
 HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd.h")
 LIVE_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_live.h")
 ROLLING_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_rolling.h")
+CLIPS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_clips.h")
 
 SOURCES = [
     "bp_api.hip",
@@ -53,7 +54,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

@@ -1,0 +1,157 @@
+"""Many short clips in one native call: raw PCM in, note events out (include/basic_pitch_amd_clips.h).
+
+A clip of 1 to 15 windows is under 40 us of device work behind about ten launches and a wait when it goes through
+`bp_infer_pcm_raw_candidates` alone.  `bp_infer_clips_candidates` takes a whole job of clips: one downmix and one resampling
+launch for all of them, their windows packed into full batches, the dense half of note decoding for every clip as its own
+track.  Clip by clip the bytes are those of the single-clip call (tests/test_gpu_clips.py), so the events are those of
+`predict`.  `Model.transcribe_clips` is the public entry; this module binds the two prototypes and holds the host side.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from concurrent.futures import ThreadPoolExecutor
+from typing import Any, List, Optional, Sequence, Tuple, Union
+
+import numpy as np
+
+from . import _native
+from . import note_creation as _notes
+
+_vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
+_pi64 = C.POINTER(C.c_int64)
+
+
+class bp_clip(C.Structure):
+    _fields_ = [("pcm", C.c_void_p), ("n_frames", C.c_int64), ("format", C.c_int), ("channels", C.c_int)]
+
+
+# name -> (restype, argtypes), as include/basic_pitch_amd_clips.h declares them (tests/test_clips_cpu.py compares)
+PROTOTYPES = {
+    "bp_clips_row_offsets": (_int, [_vp, _i64, _vp, _int, _pi64]),
+    "bp_infer_clips_candidates": (_int, [_vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
+}
+
+# the BP_PCM_* code of each numpy sample type a clip may have (24-bit PCM has no numpy type: widen it to int32)
+FORMATS = {np.dtype(np.float32): _native.BP_PCM_F32, np.dtype(np.int16): _native.BP_PCM_S16,
+           np.dtype(np.int32): _native.BP_PCM_S32, np.dtype(np.uint8): _native.BP_PCM_U8,
+           np.dtype(np.float64): _native.BP_PCM_F64}
+
+
+def bind(lib: C.CDLL) -> C.CDLL:
+    """Declare the prototypes of include/basic_pitch_amd_clips.h on a loaded library."""
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
+def as_clip(clip: Any, index: int) -> np.ndarray:
+    """Clip `index` as the C-contiguous [n_frames, channels] array the library reads; ValueError names the clip."""
+    a = np.asarray(clip)
+    if a.dtype not in FORMATS:
+        raise ValueError(f"clip {index}: samples must be float32, int16, int32, uint8 or float64, got {a.dtype}")
+    if a.ndim == 1:
+        a = a[:, None]
+    if a.ndim != 2 or not 1 <= a.shape[1] <= 64:
+        raise ValueError(f"clip {index}: expected [n_frames] or [n_frames, channels] with 1 to 64 channels, got shape {np.shape(clip)}")
+    return np.ascontiguousarray(a)
+
+
+def clip_table(arrays: Sequence[np.ndarray]):
+    """The `bp_clip` array of [n_frames, channels] arrays (which must outlive it)."""
+    tab = (bp_clip * max(1, len(arrays)))()
+    for i, a in enumerate(arrays):
+        tab[i] = bp_clip(a.ctypes.data if a.size else None, a.shape[0], FORMATS[a.dtype], a.shape[1])
+    return tab
+
+
+def n_rows(n_frames: int, sample_rate: int, model_rate: int = 22050, hop: int = 36164, lead: int = 3840) -> int:
+    """Rows of the maps of a clip of `n_frames` at `sample_rate`, without the library: ceil(n * rate / sample_rate) samples at
+    the model's rate, then min(int(samples / hop * 142), windows * 142) with windows = ceil((samples + lead) / hop)
+    (`bp_handle_track_n_frames(bp_handle_resampled_length(...))`; hop and lead-in double for the extended 44.1 kHz geometry)."""
+    if n_frames <= 0:
+        return 0
+    n = (int(n_frames) * model_rate + sample_rate - 1) // sample_rate
+    windows = (n + lead + hop - 1) // hop
+    return min(int(n / hop * 142), windows * 142)
+
+
+def row_offsets(n_frames: Sequence[int], sample_rate: int, **geometry: int) -> np.ndarray:
+    """The pure-Python mirror of `bp_clips_row_offsets`: offsets[i] = rows of the clips before clip i, offsets[-1] = all rows."""
+    return np.concatenate([[0], np.cumsum([n_rows(n, sample_rate, **geometry) for n in n_frames], dtype=np.int64)]).astype(np.int64)
+
+
+def clips_row_offsets(model: Any, arrays: Sequence[np.ndarray], sample_rate: int) -> np.ndarray:
+    """`bp_clips_row_offsets` for [n_frames, channels] arrays on `model`'s handle (no GPU work)."""
+    lib = bind(model._lib)
+    offs = np.zeros(len(arrays) + 1, np.int64)
+    rc = lib.bp_clips_row_offsets(model._handle, len(arrays), clip_table(arrays), int(sample_rate), offs.ctypes.data_as(_pi64))
+    _native.check(lib, model._handle, rc, "bp_clips_row_offsets")
+    return offs
+
+
+def infer_clips_candidates(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, prm: Any
+                           ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
+    """One `bp_infer_clips_candidates` call for [n_frames, channels] arrays at one rate: (offsets, note (T, 88) float32,
+    onset-peak bitmap (T, 12) uint8, bend map (T, 88) int8 or None, status per clip), the rows of clip i at
+    offsets[i]:offsets[i + 1]."""
+    lib = bind(model._lib)
+    tab = clip_table(arrays)
+    offs = np.zeros(len(arrays) + 1, np.int64)
+    rc = lib.bp_clips_row_offsets(model._handle, len(arrays), tab, int(sample_rate), offs.ctypes.data_as(_pi64))
+    _native.check(lib, model._handle, rc, "bp_clips_row_offsets")
+    T = int(offs[-1])
+    note = np.empty((T, 88), np.float32)
+    bits = np.empty((T, 12), np.uint8)
+    bend = np.empty((T, 88), np.int8) if prm.include_pitch_bends else None
+    status = np.zeros(max(1, len(arrays)), np.int32)
+    rc = lib.bp_infer_clips_candidates(model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST, C.addressof(prm),
+                                       note.ctypes.data, bits.ctypes.data, bend.ctypes.data if bend is not None else None,
+                                       status.ctypes.data)
+    _native.check(lib, model._handle, rc, "bp_infer_clips_candidates")
+    return offs, note, bits, bend, status[: len(arrays)]
+
+
+def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], onset_threshold: float,
+                     frame_threshold: float, minimum_note_length: float, minimum_frequency: Optional[float],
+                     maximum_frequency: Optional[float], multiple_pitch_bends: bool, melodia_trick: bool, midi_tempo: float,
+                     threads: int = 8) -> List[Tuple[Any, List["_notes.NoteEvent"]]]:
+    """`Model.transcribe_clips`: clips grouped by rate, one native call per group, the sequential half of note decoding per clip
+    on a thread pool (the native decoder releases the GIL), results in input order."""
+    from . import inference as _inf
+
+    arrays = [as_clip(c, i) for i, c in enumerate(clips)]
+    if isinstance(sample_rates, (int, np.integer)):
+        rates = [int(sample_rates)] * len(arrays)
+    else:
+        rates = [int(r) for r in sample_rates]
+        if len(rates) != len(arrays):
+            raise ValueError(f"{len(arrays)} clips but {len(rates)} sample rates")
+    prm = _notes._note_params(onset_threshold, frame_threshold, _inf._min_note_len_frames(minimum_note_length), True,
+                              maximum_frequency, minimum_frequency, melodia_trick, _notes.ENERGY_TOLERANCE, True)
+    results: List[Any] = [None] * len(arrays)
+
+    def host_decoded(i: int):
+        a = arrays[i]  # status 1 (a NaN, or an onset threshold <= 0): the maps themselves decide, as predict does
+        out = model.predict_pcm_raw(a, FORMATS[a.dtype], a.shape[0], a.shape[1], rates[i])
+        return _inf._output_to_notes(out, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency,
+                                     maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo)
+
+    def decoded(note, bits, bend):
+        events = _notes.decode_candidates(note, bits, bend, prm)
+        return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+
+    with ThreadPoolExecutor(max_workers=max(1, int(threads))) as pool:
+        pending = []
+        for rate in dict.fromkeys(rates):  # the rates in order of first appearance
+            ids = [i for i, r in enumerate(rates) if r == rate]
+            offs, note, bits, bend, status = infer_clips_candidates(model, [arrays[i] for i in ids], rate, prm)
+            for k, i in enumerate(ids):
+                if status[k]:
+                    results[i] = host_decoded(i)  # uses the handle: on this thread, between the native calls
+                    continue
+                r0, r1 = int(offs[k]), int(offs[k + 1])
+                pending.append((i, pool.submit(decoded, note[r0:r1], bits[r0:r1], bend[r0:r1] if bend is not None else None)))
+        for i, fut in pending:
+            results[i] = fut.result()
+    return results

@@ -359,6 +359,83 @@ void launch_resample(const float* x, int64_t n_in, const double* taps, const Res
     hipLaunchKernelGGL(resample_poly_kernel, per_output, dim3(256), 0, stream, x, n_in, taps, pl, y, n_out);
 }
 
+// ---- batched ingest (bp_infer_clips_candidates, track_api.hip): many short clips, one downmix launch and one resampling launch
+// for all of them.  The table of clips (bp_kernels.h ClipDesc) is in device memory; a workgroup finds its clip by binary search
+// over the clips' first workgroups and works on that clip alone, so everything about the clip is workgroup-uniform.
+template <int64_t ClipDesc::*kFirst>
+__device__ __forceinline__ int64_t clip_of_block(const ClipDesc* __restrict__ clips, int64_t n, int64_t block) {
+  int64_t lo = 0, hi = n;  // the last clip whose first workgroup is <= block (a clip without workgroups shares its successor's)
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (clips[mid].*kFirst <= block) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+// Four frames per thread, each mono_frame<FMT> of its clip: the format switch is taken once per workgroup.
+__global__ __launch_bounds__(256) void clips_downmix_kernel(const ClipDesc* __restrict__ clips, int64_t n_clips) {
+  const ClipDesc c = clips[clip_of_block<&ClipDesc::mono_block>(clips, n_clips, blockIdx.x)];
+  const int64_t i4 = (((int64_t)blockIdx.x - c.mono_block) * 256 + threadIdx.x) * 4, n = c.n_frames;
+  const uint8_t* raw = static_cast<const uint8_t*>(c.src);
+  float* mono = const_cast<float*>(c.mono);
+  const int channels = c.channels;
+  auto frames = [&](auto fmt) {
+    for (int64_t i = i4; i < i4 + 4 && i < n; ++i) mono[i] = mono_frame<decltype(fmt)::value>(raw, i, channels);
+  };
+  switch (c.format) {
+    case BP_PCM_S16: frames(std::integral_constant<int, BP_PCM_S16>{}); break;
+    case BP_PCM_S24: frames(std::integral_constant<int, BP_PCM_S24>{}); break;
+    case BP_PCM_S32: frames(std::integral_constant<int, BP_PCM_S32>{}); break;
+    case BP_PCM_U8: frames(std::integral_constant<int, BP_PCM_U8>{}); break;
+    case BP_PCM_F64: frames(std::integral_constant<int, BP_PCM_F64>{}); break;
+    default: frames(std::integral_constant<int, BP_PCM_F32>{}); break;
+  }
+}
+
+// Output k of a clip is resample_sum at the clip-local index k with the clip's own n_in: the signal is zero outside the clip,
+// whatever lies beside it in the buffer.  kTiled (the span of 256 outputs and the taps fit LDS, as in resample_tiled_kernel):
+// the workgroup's slice of the clip and the taps are staged once and the sum reads them there; the terms and their order are
+// resample_sum's either way.
+template <bool kTiled>
+__global__ __launch_bounds__(256) void clips_resample_kernel(const ClipDesc* __restrict__ clips, int64_t n_clips,
+                                                             const double* __restrict__ taps, ResamplePlan pl) {
+  __shared__ float xs[kTiled ? kResTileX : 1];
+  __shared__ double hs[kTiled ? kResTileTaps : 1];
+  const ClipDesc c = clips[clip_of_block<&ClipDesc::out_block>(clips, n_clips, blockIdx.x)];
+  const float* __restrict__ x = c.mono;
+  const int64_t n_in = c.n_frames, n_out = c.n_out;
+  const int64_t k0 = ((int64_t)blockIdx.x - c.out_block) * 256, k = k0 + threadIdx.x;
+  if (!kTiled) {
+    if (k < n_out) c.out[k] = resample_sum(k, n_in, taps, pl, 0, [&](int64_t j) { return x[j]; });
+    return;
+  }
+  // the frames the workgroup's outputs reach: from the first frame of output k0 to the last frame of its last output
+  const int64_t k_last = k0 + 255 < n_out - 1 ? k0 + 255 : n_out - 1;
+  const int64_t lo_num = k0 * (int64_t)pl.down + pl.centre - (pl.n_taps - 1);
+  const int64_t j0 = lo_num <= 0 ? 0 : (lo_num + pl.up - 1) / pl.up;
+  int64_t j1 = (k_last * (int64_t)pl.down + pl.centre) / pl.up;
+  if (j1 > n_in - 1) j1 = n_in - 1;
+  for (int64_t j = j0 + threadIdx.x; j <= j1; j += 256) xs[j - j0] = x[j];
+  for (int i = threadIdx.x; i < (int)pl.n_taps; i += 256) hs[i] = taps[i];
+  __syncthreads();
+  if (k < n_out) c.out[k] = resample_sum(k, n_in, hs, pl, 0, [&](int64_t j) { return xs[j - j0]; });
+}
+
+void launch_clips_downmix(const ClipDesc* clips, int64_t n_clips, int64_t n_blocks, hipStream_t stream) {
+  if (n_blocks <= 0) return;
+  hipLaunchKernelGGL(clips_downmix_kernel, dim3((unsigned)n_blocks), dim3(256), 0, stream, clips, n_clips);
+}
+
+void launch_clips_resample(const ClipDesc* clips, int64_t n_clips, int64_t n_blocks, const double* taps, const ResamplePlan& pl,
+                           hipStream_t stream) {
+  if (n_blocks <= 0) return;
+  const int64_t span = (255 * (int64_t)pl.down + pl.n_taps - 1) / pl.up + 2;  // inputs 256 outputs reach (upper bound)
+  if (span <= kResTileX && pl.n_taps <= kResTileTaps)
+    hipLaunchKernelGGL(clips_resample_kernel<true>, dim3((unsigned)n_blocks), dim3(256), 0, stream, clips, n_clips, taps, pl);
+  else
+    hipLaunchKernelGGL(clips_resample_kernel<false>, dim3((unsigned)n_blocks), dim3(256), 0, stream, clips, n_clips, taps, pl);
+}
+
 // ---- streaming ingest (stream_api.hip): the same downmix and the same sum on a chunk of a signal that arrives in pieces ----
 // Threads [0, n_frames): frame i -> dst[(dst_pos + i) mod dst_cap] (dst_cap 0: dst[i]; n_frames <= dst_cap otherwise).
 // Threads [n_frames, n_frames + n_hist): entry t of the resampler's next input history, the last n_hist mono frames of

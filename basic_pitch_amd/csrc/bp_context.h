@@ -72,6 +72,13 @@ struct bp_context {
   bp::PinnedBuffer<int> nd_stats_host;   // copy of the stats record (4 words; [1]: a NaN was seen)
   void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
   bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
+  // many clips in one call (bp_infer_clips_candidates, track_api.hip), all grow-only: the table of clips, the clips' row
+  // offsets, one stats record of 16 bytes per clip and the page-locked copy of the records (4 words per clip)
+  Buffer<bp::ClipDesc> clip_tab;
+  Buffer<int64_t> clip_rows;
+  Table clip_stats;
+  bp::PinnedBuffer<int> clip_stats_host;
+  int64_t clip_stats_ready = 0;  // the first so many device records hold their initial values (the export kernel leaves them so)
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

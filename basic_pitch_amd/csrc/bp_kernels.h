@@ -113,6 +113,24 @@ void launch_stream_resample(const float* hist, int n_hist, const float* chunk, i
                             const double* taps, const ResamplePlan& pl, int64_t k0, int64_t n_k, float* ring, int ring_pos,
                             int ring_cap, hipStream_t stream);
 
+// batched ingest (bp_infer_clips_candidates): one clip of the table a call uploads.  The downmix launch gives clip c the
+// workgroups [mono_block, next clip's mono_block), the resampling launch [out_block, next clip's out_block); a clip that
+// needs no downmix (mono float32) or no resampling (already at the handle's rate) takes none and is read where it lies.
+struct ClipDesc {
+  const void* src;     // the clip's interleaved PCM (device)
+  const float* mono;   // its mono float32 form: src itself, or where the downmix writes it
+  float* out;          // its signal at the handle's rate, where the resampling writes it
+  int64_t n_frames;    // frames of PCM
+  int64_t n_out;       // samples at the handle's rate
+  int64_t mono_block;  // first workgroup of the downmix launch (1024 frames each)
+  int64_t out_block;   // first workgroup of the resampling launch (256 outputs each)
+  int format, channels;
+};
+// clips: the table in device memory, n_blocks: the workgroups of all clips together
+void launch_clips_downmix(const ClipDesc* clips, int64_t n_clips, int64_t n_blocks, hipStream_t stream);
+void launch_clips_resample(const ClipDesc* clips, int64_t n_clips, int64_t n_blocks, const double* taps, const ResamplePlan& pl,
+                           hipStream_t stream);
+
 // flac_device.hip
 struct FdStream {
   int channels, bits, min_block, max_block;
@@ -135,7 +153,13 @@ void launch_note_candidates(float* note, float* onset, const float* contour, int
                             int8_t* bend, hipStream_t s);
 void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, const void* bits, void* bits_dst,
                         int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
-                        void* stats_dst, hipStream_t s);
+                        void* stats_dst, int64_t n_stats, hipStream_t s);
+// many clips in one buffer, clip c at rows [offs[c], offs[c + 1]) (offs: device memory), each decoded as its own whole track:
+// n_clips stats records of 16 bytes to their initial values; launch_note_candidates for every clip (its record: table[c])
+void launch_clips_stats_init(void* table, int64_t n_clips, hipStream_t s);
+void launch_clips_candidates(float* note, float* onset, const float* contour, const int64_t* offs, int64_t n_clips,
+                             int64_t total_rows, int lo, int hi, int infer, double onset_thresh, const void* tab,
+                             const double* gauss, void* table, uint8_t* bits, int8_t* bend, hipStream_t s);
 void launch_note_stats_init(void* stats, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);

@@ -81,7 +81,7 @@ class DeviceBuffer {
   size_t cap_ = 0;
 };
 
-// n page-locked elements, allocated once (hipHostMallocPortable): the words a stream's copy or kernel leaves for the host
+// n page-locked elements, allocated once or grown between calls (hipHostMallocPortable): the words a stream's copy or kernel leaves for the host
 template <class T>
 class PinnedBuffer {
  public:
@@ -95,12 +95,21 @@ class PinnedBuffer {
   hipError_t alloc(size_t n) {
     void* p = nullptr;
     const hipError_t e = p_ ? hipSuccess : hipHostMalloc(&p, n * sizeof(T), hipHostMallocPortable);
-    if (p) p_ = static_cast<T*>(p);
+    if (p) p_ = static_cast<T*>(p), cap_ = n;
     return e;
+  }
+  // Room for n elements: grows only, the contents are not kept (the words of a call whose count the caller chooses).  The
+  // stream that wrote the old block must have drained.
+  hipError_t reserve(size_t n) {
+    if (p_ && n <= cap_) return hipSuccess;
+    if (p_) (void)hipHostFree(p_);
+    p_ = nullptr, cap_ = 0;
+    return alloc(n ? n : 1);
   }
 
  private:
   T* p_ = nullptr;
+  size_t cap_ = 0;
 };
 
 }  // namespace bp

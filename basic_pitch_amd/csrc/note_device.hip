@@ -123,20 +123,17 @@ __device__ __forceinline__ double nd_np_maximum(double a, double b) {
   return a > b ? a : b;
 }
 
-// kRing (a stream's rolling horizon, stream_api.hip): the maps are a ring of `cap` rows, absolute row r at slot r % cap,
-// and the bitmap is that of rows [a, T) decoded AS A WHOLE TRACK — frame t of the slice is absolute row a + t, whatever rows
-// a - 1 and a - 2 still hold in the ring, the `t < 2` and `1 <= t <= n - 2` cases count from a.  Linear: a = 0, cap unused.
-// One body: the arithmetic of the two forms cannot drift apart.
+// The bitmap words of frame t of a track of n frames, decoded AS A WHOLE TRACK: the `t < 2` and `1 <= t <= n - 2` cases count
+// from the track's first frame.  s0: the row of frame t in the maps.  kRing (a stream's rolling horizon, stream_api.hip): the
+// maps are a ring of `cap` rows and s0 = (a + t) % cap for the slice that starts at absolute row a, whatever rows a - 1 and
+// a - 2 still hold in the ring.  Linear: s0 = t of maps whose row 0 is the track's first frame — a whole buffer, or ONE clip
+// of a buffer of many (the segmented form below); cap unused.  One body: the arithmetic of the three forms cannot drift apart.
 template <bool kRing>
-__global__ __launch_bounds__(256) void nd_candidates_kernel(const float* __restrict__ note, const float* __restrict__ onset,
-                                                            int64_t a, int64_t T, int64_t cap, int infer, double onset_thresh,
-                                                            const NdStats* __restrict__ st, uint32_t* __restrict__ bits) {
-  const int lane = threadIdx.x & 63;
-  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n = T - a;  // t: the frame of the slice
-  if (t >= n) return;
+__device__ __forceinline__ void nd_candidates_row(const float* __restrict__ note, const float* __restrict__ onset, int64_t t,
+                                                  int64_t n, int64_t s0, int64_t cap, int infer, double onset_thresh,
+                                                  const NdStats* __restrict__ st, uint32_t* __restrict__ bits, int lane) {
   const double max_on_d = (double)ord2f(st->max_on_ord);
   const double max_fd = __longlong_as_double((long long)st->max_fd_bits);
-  const int64_t s0 = kRing ? (a + t) % cap : t;
   // the row of frame t + k in the maps (k = -3 ... 1; cap > 3)
   auto row = [&](int k) -> int64_t {
     const int64_t r = s0 + k;
@@ -168,6 +165,80 @@ __global__ __launch_bounds__(256) void nd_candidates_kernel(const float* __restr
   }
   const unsigned long long b0 = __ballot(c[0]), b1 = __ballot(c[1]);
   if (lane < 3) bits[t * 3 + lane] = lane == 0 ? (uint32_t)b0 : (lane == 1 ? (uint32_t)(b0 >> 32) : (uint32_t)b1);
+}
+
+// A wave per frame.  kRing: the bitmap is that of rows [a, T) of the ring; linear: a = 0, cap unused.
+template <bool kRing>
+__global__ __launch_bounds__(256) void nd_candidates_kernel(const float* __restrict__ note, const float* __restrict__ onset,
+                                                            int64_t a, int64_t T, int64_t cap, int infer, double onset_thresh,
+                                                            const NdStats* __restrict__ st, uint32_t* __restrict__ bits) {
+  const int64_t t = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6), n = T - a;  // t: the frame of the slice
+  if (t >= n) return;
+  nd_candidates_row<kRing>(note, onset, t, n, kRing ? (a + t) % cap : t, cap, infer, onset_thresh, st, bits, threadIdx.x & 63);
+}
+
+// ---- many clips in one buffer (bp_infer_clips_candidates, track_api.hip) -------------------------------------------------------
+// The maps of n_clips clips lie one after the other: clip c owns rows [offs[c], offs[c + 1]) and is decoded as its own whole
+// track.  The table offs[0 ... n_clips] is in device memory; a row finds its clip by binary search.  Every clip has one stats
+// record, table[c].  Frequency limits and bends are row-local and run over all rows with the kernels of a single track.
+
+// the clip that owns row r < offs[n]: the last c with offs[c] <= r (clips without rows own none)
+__device__ __forceinline__ int64_t nd_clip_of_row(const int64_t* __restrict__ offs, int64_t n, int64_t r) {
+  int64_t lo = 0, hi = n;
+  while (hi - lo > 1) {
+    const int64_t mid = (lo + hi) >> 1;
+    if (offs[mid] <= r) lo = mid; else hi = mid;
+  }
+  return lo;
+}
+
+__global__ __launch_bounds__(256) void nd_clips_stats_init_kernel(NdStats* __restrict__ table, int64_t n) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  table[c].max_on_ord = f2ord(-__int_as_float(0x7f800000));
+  table[c].nan = 0;
+  table[c].max_fd_bits = 0ull;
+}
+
+// Extrema per clip.  A workgroup takes kNdClipRows consecutive rows and, for every clip that owns some of them, folds those
+// rows (a wave per row, nd_row with the difference term only from the clip's third row on: rows 0 and 1 of a clip never read
+// the rows before them, which are another clip's) and publishes: one atomic per quantity, workgroup and clip touched.
+constexpr int kNdClipRows = 64;
+__global__ __launch_bounds__(256) void nd_clips_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset,
+                                                             const int64_t* __restrict__ offs, int64_t n_clips, int infer,
+                                                             NdStats* __restrict__ table) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t total = offs[n_clips], r0 = (int64_t)blockIdx.x * kNdClipRows;
+  const int64_t r1 = r0 + kNdClipRows < total ? r0 + kNdClipRows : total;
+  for (int64_t c = nd_clip_of_row(offs, n_clips, r0); c < n_clips && offs[c] < r1; ++c) {  // block-uniform
+    const int64_t first = offs[c], lo = first > r0 ? first : r0, hi = offs[c + 1] < r1 ? offs[c + 1] : r1;
+    if (hi <= lo) continue;
+    float mo = -__int_as_float(0x7f800000);
+    double mfd = 0.0;
+    int nan = 0;
+    for (int64_t t = lo + wave; t < hi; t += 4) nd_row<false>(note, onset, t, 0, infer && t - first >= 2, lane, mo, mfd, nan);
+    nd_reduce(mo, mfd, nan);
+    if (threadIdx.x == 0) nd_publish(table + c, mo, mfd, nan);
+    __syncthreads();  // thread 0 has read the waves' words before the next clip's are written
+  }
+}
+
+// The bitmap: a wave per row of the buffer, the frame counted from its clip's first row, the clip's own length and record.  A
+// clip whose record has the NaN flag gets a zero bitmap (the caller decodes its maps on the host: status 1).
+__global__ __launch_bounds__(256) void nd_clips_candidates_kernel(const float* __restrict__ note, const float* __restrict__ onset,
+                                                                  const int64_t* __restrict__ offs, int64_t n_clips, int infer,
+                                                                  double onset_thresh, const NdStats* __restrict__ table,
+                                                                  uint32_t* __restrict__ bits) {
+  const int lane = threadIdx.x & 63;
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= offs[n_clips]) return;
+  const int64_t c = nd_clip_of_row(offs, n_clips, r), first = offs[c], t = r - first;
+  if (table[c].nan) {  // wave-uniform
+    if (lane < 3) bits[r * 3 + lane] = 0u;
+    return;
+  }
+  nd_candidates_row<false>(note + first * kNdF, onset + first * kNdF, t, offs[c + 1] - first, t, 0, infer, onset_thresh, table + c,
+                           bits + first * 3, lane);
 }
 
 // Pitch bends.  A workgroup takes kNdBendFrames consecutive frames: their contour rows go to LDS as float64 once (264
@@ -279,21 +350,22 @@ __global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict
 // device -> page-locked host memory, by the compute queue: the note map, the bitmap and the bend map of a track in one
 // launch (4-byte words, a wave writes 256 contiguous bytes; the copy engine stays free for the next file's samples), the
 // stats record with them — and the device record back to its initial values for the next track (one launch and one
-// 16-byte copy fewer per track).
+// 16-byte copy fewer per track).  n_st records: one for a track, one per clip of a buffer of many.
 __global__ __launch_bounds__(256) void nd_export_kernel(const uint32_t* __restrict__ s0, uint32_t* __restrict__ d0, int64_t n0,
                                                         const uint32_t* __restrict__ s1, uint32_t* __restrict__ d1, int64_t n1,
                                                         const uint32_t* __restrict__ s2, uint32_t* __restrict__ d2, int64_t n2,
-                                                        NdStats* __restrict__ st, NdStats* __restrict__ st_dst) {
+                                                        NdStats* __restrict__ st, NdStats* __restrict__ st_dst, int64_t n_st) {
   const int64_t step = (int64_t)gridDim.x * 256;
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n0; i += step) d0[i] = s0[i];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n1; i += step) d1[i] = s1[i];
   for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n2; i += step) d2[i] = s2[i];
-  if (blockIdx.x == 0 && threadIdx.x == 0) {
-    *st_dst = *st;
-    st->max_on_ord = f2ord(-__int_as_float(0x7f800000));
-    st->nan = 0;
-    st->max_fd_bits = 0ull;
-  }
+  if (blockIdx.x == 0)
+    for (int64_t c = threadIdx.x; c < n_st; c += 256) {
+      st_dst[c] = st[c];
+      st[c].max_on_ord = f2ord(-__int_as_float(0x7f800000));
+      st[c].nan = 0;
+      st[c].max_fd_bits = 0ull;
+    }
 }
 
 // Frames [t0, t1) of the device maps note / onset join the stats record.  Frames t0 - 1 and t0 - 2 are read when t0 > 0.
@@ -326,15 +398,43 @@ void launch_note_stats_init(void* stats, hipStream_t s) {
   hipLaunchKernelGGL(nd_stats_init_kernel, dim3(1), dim3(64), 0, s, static_cast<NdStats*>(stats));
 }
 
-// the three results to device-visible host pointers (sizes in bytes, multiples of 4; a null destination is skipped)
+// the three results to device-visible host pointers (sizes in bytes, multiples of 4; a null destination is skipped), and
+// the n_stats records at `stats`, which are left holding their initial values
 void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, const void* bits, void* bits_dst,
                         int64_t bits_bytes, const void* bend, void* bend_dst, int64_t bend_bytes, void* stats,
-                        void* stats_dst, hipStream_t s) {
+                        void* stats_dst, int64_t n_stats, hipStream_t s) {
   hipLaunchKernelGGL(nd_export_kernel, dim3(64), dim3(256), 0, s, static_cast<const uint32_t*>(note),
                      static_cast<uint32_t*>(note_dst), note_dst ? note_bytes / 4 : 0, static_cast<const uint32_t*>(bits),
                      static_cast<uint32_t*>(bits_dst), bits_dst ? bits_bytes / 4 : 0, static_cast<const uint32_t*>(bend),
                      static_cast<uint32_t*>(bend_dst), bend_dst ? bend_bytes / 4 : 0, static_cast<NdStats*>(stats),
-                     static_cast<NdStats*>(stats_dst));
+                     static_cast<NdStats*>(stats_dst), n_stats);
+}
+
+void launch_clips_stats_init(void* table, int64_t n_clips, hipStream_t s) {
+  if (n_clips <= 0) return;
+  hipLaunchKernelGGL(nd_clips_stats_init_kernel, dim3((unsigned)((n_clips + 255) / 256)), dim3(256), 0, s,
+                     static_cast<NdStats*>(table), n_clips);
+}
+
+// note / onset / contour: the device maps of n_clips clips, total_rows > 0 rows in all, clip c at rows [offs[c], offs[c + 1]) (offs:
+// device memory).  What launch_note_candidates does for one track, for every clip as its own track: `table` (n_clips records
+// holding their initial values) receives the clips' extrema.
+void launch_clips_candidates(float* note, float* onset, const float* contour, const int64_t* offs, int64_t n_clips,
+                             int64_t total_rows, int lo, int hi, int infer, double onset_thresh, const void* tab,
+                             const double* gauss, void* table, uint8_t* bits, int8_t* bend, hipStream_t s) {
+  if (total_rows <= 0 || n_clips <= 0) return;
+  if (lo > 0 || hi < kNdF)
+    hipLaunchKernelGGL(nd_constrain_kernel, dim3((unsigned)((total_rows * kNdF + 255) / 256)), dim3(256), 0, s, note, onset,
+                       total_rows * kNdF, lo, hi);
+  hipLaunchKernelGGL(nd_clips_stats_kernel, dim3((unsigned)((total_rows + kNdClipRows - 1) / kNdClipRows)), dim3(256), 0, s, note,
+                     onset, offs, n_clips, infer, static_cast<NdStats*>(table));
+  hipLaunchKernelGGL(nd_clips_candidates_kernel, dim3((unsigned)((total_rows + 3) / 4)), dim3(256), 0, s, note, onset, offs, n_clips,
+                     infer, onset_thresh, static_cast<const NdStats*>(table), reinterpret_cast<uint32_t*>(bits));
+  // a row's bends depend on that row alone (a NaN elsewhere in a block of 16 rows only chooses between two loops that give a
+  // row without NaN the same first maximum): the kernel of a single track, its blocks free to straddle clips
+  if (bend)
+    hipLaunchKernelGGL(nd_bend_kernel<false>, dim3((unsigned)((total_rows + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s,
+                       contour, (int64_t)0, total_rows, (int64_t)0, static_cast<const int4*>(tab), gauss, bend);
 }
 
 // ---- the rows a stream retains (stream_api.hip, bp_stream_keep / bp_stream_keep_rolling) ------------------------------------

@@ -11,6 +11,7 @@
 // needs before it queues work on them, and nothing here frees by hand.
 #include <algorithm>
 
+#include "../../include/basic_pitch_amd_clips.h"
 #include "bp_context.h"
 
 using namespace bp;
@@ -256,36 +257,22 @@ int tracks_core(bp_handle h, int64_t n_tracks, const float* const* d_in, const i
 // ---- device-side note candidates (note_device.hip): what note decoding needs of a track's maps
 constexpr size_t kTabBytes = 88 * 16, kGaussBytes = 51 * 8, kStatsBytes = 16;
 
-// m: device maps of T > 0 frames (note / onset are modified when the parameters set a frequency range, like
-// constrain_frequency does).  Outputs: host buffers, complete once the stream has been waited for.
-int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params* prm, float* note_out, uint8_t* cand_out,
-                     int8_t* bend_out, bool* exported_by_kernel) {
+// The results of T rows go home: the note map, the bitmap and the bends (null: not wanted), and the n_stats records at d_stats
+// into stats_host (stats_host_dev: the same page-locked block as the device sees it).
+// Into page-locked buffers (bp_host_alloc) a kernel of this stream writes them over PCIe itself:
+// the copy engine serialises the copies of all lanes in both directions (measured: a lane's 27 MB of posteriorgrams
+// going out kept the next file's samples from coming in), and it is busy with the inbound samples.  Pageable
+// destinations take ordinary copies.
+// (the attributes describe the START of a buffer only — a pointer into a page-locked block that ends before
+// `bytes` would send the kernel's writes past the registration.  The whole extent must lie inside the allocation the
+// pointer belongs to: hipMemGetAddressRange gives its base and size for the device view of a page-locked block; where that
+// cannot be established the copies take over.)
+int send_candidates(bp_handle h, const float* d_note, int64_t T, const uint8_t* d_bits, const int8_t* d_bend, float* note_out,
+                    uint8_t* cand_out, int8_t* bend_out, void* d_stats, int* stats_host, void* stats_host_dev, int64_t n_stats,
+                    bool* exported_by_kernel) {
   hipStream_t s = h->stream;
-  const void* tab = nullptr;
-  const double* gauss = nullptr;
-  if (int rc = note_tables(h, &tab, &gauss)) return rc;
   const int64_t bits_bytes = T * BP_NOTE_CAND_ROW_BYTES, bend_bytes = T * 88;  // multiples of 4
-  const int64_t bits_room = (bits_bytes + 15) & ~(int64_t)15;
-  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_bytes)));
-  uint8_t* d_bits = h->nd_buf;
-  int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
-  void* d_stats = h->nd_tables + kTabBytes + kGaussBytes;
-  int lo = 0, hi = 88;
-  bp_internal_freq_limits(prm, &lo, &hi);
-  const bool want_bends = prm->include_pitch_bends != 0 && bend_out != nullptr;
-  if (!h->nd_stats_ready) launch_note_stats_init(d_stats, s);
-  h->nd_stats_ready = false;
-  launch_note_candidates(m.note, m.onset, m.contour, T, lo, hi, prm->infer_onsets != 0, prm->onset_threshold, tab, gauss,
-                         d_stats, d_bits, want_bends ? d_bend : nullptr, s);
-  BP_HIP(hipGetLastError());
-  // The results go home.  Into page-locked buffers (bp_host_alloc) a kernel of this stream writes them over PCIe itself:
-  // the copy engine serialises the copies of all lanes in both directions (measured: a lane's 27 MB of posteriorgrams
-  // going out kept the next file's samples from coming in), and it is busy with the inbound samples.  Pageable
-  // destinations take ordinary copies.
-  // (the attributes describe the START of a buffer only — a pointer into a page-locked block that ends before
-  // `bytes` would send the kernel's writes past the registration.  The whole extent must lie inside the allocation the
-  // pointer belongs to: hipMemGetAddressRange gives its base and size for the device view of a page-locked block; where that
-  // cannot be established the copies take over.)
+  const bool want_bends = d_bend != nullptr;
   auto device_view = [](void* p, size_t bytes) -> void* {
     hipPointerAttribute_t at;
     hipDeviceptr_t base = nullptr;
@@ -304,18 +291,83 @@ int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params
        *v_bend = want_bends ? device_view(bend_out, (size_t)bend_bytes) : nullptr;
   const bool aligned = !((reinterpret_cast<uintptr_t>(v_note) | reinterpret_cast<uintptr_t>(v_bits) | reinterpret_cast<uintptr_t>(v_bend)) & 3);
   if (v_note && v_bits && (v_bend || !want_bends) && aligned) {
-    // ... the stats record with them; the same kernel leaves the device record initialised for the next track
-    launch_note_export(m.note, v_note, T * 88 * 4, d_bits, v_bits, bits_bytes, d_bend, v_bend, bend_bytes, d_stats,
-                       h->nd_stats_host_dev, s);
+    // ... the stats records with them; the same kernel leaves the device records initialised for the next call
+    launch_note_export(d_note, v_note, T * 88 * 4, d_bits, v_bits, bits_bytes, d_bend, v_bend, bend_bytes, d_stats,
+                       stats_host_dev, n_stats, s);
     BP_HIP(hipGetLastError());
     *exported_by_kernel = true;
   } else {
-    BP_HIP(hipMemcpyAsync(h->nd_stats_host, d_stats, kStatsBytes, hipMemcpyDeviceToHost, s));
-    BP_HIP(hipMemcpyAsync(note_out, m.note, (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
+    BP_HIP(hipMemcpyAsync(stats_host, d_stats, (size_t)n_stats * kStatsBytes, hipMemcpyDeviceToHost, s));
+    BP_HIP(hipMemcpyAsync(note_out, d_note, (size_t)T * 88 * 4, hipMemcpyDeviceToHost, s));
     BP_HIP(hipMemcpyAsync(cand_out, d_bits, (size_t)bits_bytes, hipMemcpyDeviceToHost, s));
     if (want_bends) BP_HIP(hipMemcpyAsync(bend_out, d_bend, (size_t)bend_bytes, hipMemcpyDeviceToHost, s));
   }
   return BP_OK;
+}
+
+// room for the bitmap and the bends of T rows in h->nd_buf
+int reserve_candidates(bp_handle h, int64_t T, uint8_t** d_bits, int8_t** d_bend) {
+  const int64_t bits_room = (T * BP_NOTE_CAND_ROW_BYTES + 15) & ~(int64_t)15;
+  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + T * 88)));
+  *d_bits = h->nd_buf;
+  *d_bend = h->nd_buf.as<int8_t>() + bits_room;
+  return BP_OK;
+}
+
+// m: device maps of T > 0 frames (note / onset are modified when the parameters set a frequency range, like
+// constrain_frequency does).  Outputs: host buffers, complete once the stream has been waited for.
+int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params* prm, float* note_out, uint8_t* cand_out,
+                     int8_t* bend_out, bool* exported_by_kernel) {
+  hipStream_t s = h->stream;
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  if (int rc = note_tables(h, &tab, &gauss)) return rc;
+  uint8_t* d_bits = nullptr;
+  int8_t* d_bend = nullptr;
+  if (int rc = reserve_candidates(h, T, &d_bits, &d_bend)) return rc;
+  void* d_stats = h->nd_tables + kTabBytes + kGaussBytes;
+  int lo = 0, hi = 88;
+  bp_internal_freq_limits(prm, &lo, &hi);
+  const bool want_bends = prm->include_pitch_bends != 0 && bend_out != nullptr;
+  if (!h->nd_stats_ready) launch_note_stats_init(d_stats, s);
+  h->nd_stats_ready = false;
+  launch_note_candidates(m.note, m.onset, m.contour, T, lo, hi, prm->infer_onsets != 0, prm->onset_threshold, tab, gauss,
+                         d_stats, d_bits, want_bends ? d_bend : nullptr, s);
+  BP_HIP(hipGetLastError());
+  return send_candidates(h, m.note, T, d_bits, want_bends ? d_bend : nullptr, note_out, cand_out, bend_out, d_stats,
+                         h->nd_stats_host, h->nd_stats_host_dev, 1, exported_by_kernel);
+}
+
+// The same for the maps of n_clips clips that lie one after the other in m, clip c at rows [offs[c], offs[c + 1]) of
+// offs[n_clips] = T > 0 rows, each clip decoded as its own whole track; its record comes home as h->clip_stats_host[4 c ...].
+// offs (host) must stay as it is until the stream has been waited for.
+int queue_clips_candidates(bp_handle h, const Maps& m, int64_t n_clips, const int64_t* offs, const bp_note_params* prm,
+                           float* note_out, uint8_t* cand_out, int8_t* bend_out, bool* exported_by_kernel) {
+  hipStream_t s = h->stream;
+  const int64_t T = offs[n_clips];
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  if (int rc = note_tables(h, &tab, &gauss)) return rc;
+  uint8_t* d_bits = nullptr;
+  int8_t* d_bend = nullptr;
+  if (int rc = reserve_candidates(h, T, &d_bits, &d_bend)) return rc;
+  if ((size_t)n_clips * kStatsBytes > h->clip_stats.capacity()) h->clip_stats_ready = 0;  // a new block: nothing initialised
+  BP_HIP(h->clip_stats.reserve((size_t)n_clips * kStatsBytes));
+  BP_HIP(h->clip_stats_host.reserve((size_t)n_clips * (kStatsBytes / sizeof(int))));
+  void* stats_host_dev = nullptr;
+  BP_HIP(hipHostGetDevicePointer(&stats_host_dev, h->clip_stats_host, 0));
+  BP_HIP(h->clip_rows.reserve((size_t)n_clips + 1));
+  BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  int lo = 0, hi = 88;
+  bp_internal_freq_limits(prm, &lo, &hi);
+  const bool want_bends = prm->include_pitch_bends != 0 && bend_out != nullptr;
+  if (h->clip_stats_ready < n_clips) launch_clips_stats_init(h->clip_stats, n_clips, s);
+  h->clip_stats_ready = 0;
+  launch_clips_candidates(m.note, m.onset, m.contour, h->clip_rows, n_clips, T, lo, hi, prm->infer_onsets != 0,
+                          prm->onset_threshold, tab, gauss, h->clip_stats, d_bits, want_bends ? d_bend : nullptr, s);
+  BP_HIP(hipGetLastError());
+  return send_candidates(h, m.note, T, d_bits, want_bends ? d_bend : nullptr, note_out, cand_out, bend_out, h->clip_stats,
+                         h->clip_stats_host, stats_host_dev, n_clips, exported_by_kernel);
 }
 
 // ---- the driver ------------------------------------------------------------------------------------------------------------
@@ -471,6 +523,125 @@ int queue_tracks(bp_handle h, int64_t n_tracks, const float* const* samples, con
   return BP_OK;
 }
 
+// ---- many clips in one call (include/basic_pitch_amd_clips.h) -------------------------------------------------------------
+// Every argument of every clip (check_ingest; with_pcm: the samples are needed too), before anything is queued: n_model[i] =
+// clip i's samples at the handle's rate, offsets[i] = the rows of the clips before it, offsets[n_clips] = all rows.
+int check_clips(bp_handle h, const char* what, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, bool with_pcm,
+                int64_t* n_model, int64_t* offsets) {
+  if (n_clips < 0 || (n_clips > 0 && !clips) || !offsets) {
+    h->err = std::string(what) + ": negative n_clips, null clips or null offsets";
+    return BP_ERR_INVALID_ARG;
+  }
+  offsets[0] = 0;
+  for (int64_t i = 0; i < n_clips; ++i) {
+    const bp_clip& c = clips[i];
+    if (int rc = check_ingest(h, !with_pcm || c.pcm != nullptr, c.format, c.n_frames, c.channels, sample_rate, mem_kind)) {
+      h->err = std::string(what) + ": clip " + std::to_string(i) + ": " + h->err;
+      return rc;
+    }
+    const int64_t n = resampled_length(c.n_frames, sample_rate, h->rate);
+    if (n_model) n_model[i] = n;
+    offsets[i + 1] = offsets[i] + h_frames(h, n);
+  }
+  return BP_OK;
+}
+
+// The handle's cached filter becomes that of sample_rate (queue_ingest's cache); a ratio whose taps the one-shot path
+// evaluates in the kernel is refused and leaves the cache as it was.  Nothing is queued: the table goes up with a plain copy.
+int clips_filter(bp_handle h, const char* what, int sample_rate) {
+  if (h->taps_rate != sample_rate) {
+    ResamplePlan pl{};
+    DeviceBuffer<double> dev;
+    const int rc = upload_filter(h, sample_rate, true, &pl, &dev);
+    if (rc != BP_OK && rc != BP_ERR_UNSUPPORTED) return rc;
+    if (rc == BP_OK) {
+      h->taps_rate = 0;
+      h->taps_dev = std::move(dev);
+      h->plan = pl;
+      h->taps_rate = sample_rate;
+      return BP_OK;
+    }
+  } else if (!h->plan.direct) {
+    return BP_OK;
+  }
+  h->err = std::string(what) + ": " + std::to_string(sample_rate) + " Hz -> " + std::to_string(h->rate) +
+           " Hz needs a filter whose taps the one-shot calls evaluate in the kernel; such ratios are not taken in batches";
+  return BP_ERR_UNSUPPORTED;
+}
+
+// Batched ingest: the clips' PCM to the device (host clips one after the other in h->pcm_dev), ONE downmix launch and ONE
+// resampling launch for all of them; d_in[i] = clip i's signal at the handle's rate (n_model[i] samples).  `tab` (n_clips
+// records, filled here) must stay as it is until the stream has been waited for.
+int queue_clips_ingest(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
+                       ClipDesc* tab, const float** d_in) {
+  hipStream_t s = h->stream;
+  auto up = [](int64_t v, int64_t a) { return (v + a - 1) / a * a; };
+  // offsets of every clip in the three staging buffers (bytes of PCM 16-byte aligned; floats 4-float aligned)
+  int64_t pcm_bytes = 0, mono_floats = 0, out_floats = 0, mono_blocks = 0, out_blocks = 0;
+  std::vector<int64_t> pcm_off(n_clips), mono_off(n_clips, -1), out_off(n_clips, -1);
+  for (int64_t i = 0; i < n_clips; ++i) {
+    const bp_clip& c = clips[i];
+    if (c.n_frames == 0) continue;
+    pcm_off[i] = pcm_bytes;
+    if (mem_kind == BP_MEM_HOST) pcm_bytes += up(c.n_frames * c.channels * pcm_width(c.format), 16);
+    if (c.channels > 1 || c.format != BP_PCM_F32) mono_off[i] = mono_floats, mono_floats += up(c.n_frames, 4);
+    if (sample_rate != h->rate) out_off[i] = out_floats, out_floats += up(n_model[i], 4);
+  }
+  if (pcm_bytes) BP_HIP(h->pcm_dev.reserve((size_t)pcm_bytes));
+  if (mono_floats) BP_HIP(h->mono_dev.reserve((size_t)mono_floats));
+  if (out_floats) BP_HIP(h->res_dev.reserve((size_t)out_floats));
+  BP_HIP(h->clip_tab.reserve((size_t)n_clips));
+  for (int64_t i = 0; i < n_clips; ++i) {
+    const bp_clip& c = clips[i];
+    ClipDesc& d = tab[i];
+    d = ClipDesc{nullptr, nullptr, nullptr, c.n_frames, n_model[i], mono_blocks, out_blocks, c.format, c.channels};
+    d_in[i] = nullptr;
+    if (c.n_frames == 0) continue;
+    d.src = c.pcm;
+    if (mem_kind == BP_MEM_HOST) {
+      d.src = h->pcm_dev + pcm_off[i];
+      BP_HIP(hipMemcpyAsync(h->pcm_dev + pcm_off[i], c.pcm, (size_t)(c.n_frames * c.channels * pcm_width(c.format)),
+                            hipMemcpyHostToDevice, s));
+    }
+    d.mono = static_cast<const float*>(d.src);
+    if (mono_off[i] >= 0) d.mono = h->mono_dev + mono_off[i], mono_blocks += (c.n_frames + 1023) / 1024;
+    d.out = const_cast<float*>(d.mono);  // already at the handle's rate: windowed where it lies, never written
+    if (out_off[i] >= 0) d.out = h->res_dev + out_off[i], out_blocks += (n_model[i] + 255) / 256;
+    d_in[i] = d.out;
+  }
+  if (mono_blocks + out_blocks == 0) return BP_OK;
+  BP_HIP(hipMemcpyAsync(h->clip_tab, tab, (size_t)n_clips * sizeof(ClipDesc), hipMemcpyHostToDevice, s));
+  launch_clips_downmix(h->clip_tab, n_clips, mono_blocks, s);
+  launch_clips_resample(h->clip_tab, n_clips, out_blocks, h->taps_dev, h->plan, s);
+  BP_HIP(hipGetLastError());
+  return BP_OK;
+}
+
+// everything bp_infer_clips_candidates queues: the ingest, the model on the clips' windows packed into full chunks (the maps
+// to h->track_out, concatenated by offs), the candidates of every clip.  offs[n_clips] > 0.
+int queue_clips(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
+                const int64_t* offs, const bp_note_params* prm, float* note_out, uint8_t* cand_bits, int8_t* bend_map,
+                std::vector<ClipDesc>& tab, bool* exported_by_kernel) {
+  std::vector<const float*> d_in(n_clips);
+  std::vector<Maps> d_out(n_clips);
+  Maps all;
+  int rc = BP_OK;
+  if ((rc = take_track_out(h, offs[n_clips], &all)) ||
+      (rc = queue_clips_ingest(h, n_clips, clips, sample_rate, mem_kind, n_model, tab.data(), d_in.data())))
+    return rc;
+  for (int64_t i = 0; i < n_clips; ++i)
+    d_out[i] = Maps{all.note + offs[i] * kFreqN, all.onset + offs[i] * kFreqN, all.contour + offs[i] * kFreqC};
+  if ((rc = tracks_core(h, n_clips, d_in.data(), n_model, d_out.data()))) return rc;
+  return queue_clips_candidates(h, all, n_clips, offs, prm, note_out, cand_bits, bend_map, exported_by_kernel);
+}
+
+// after the stream has been waited for: what the clips' records say (a clip without rows: 0)
+void clips_status(bp_handle h, int64_t n_clips, const int64_t* offs, const bp_note_params* prm, bool exported_by_kernel, int* status) {
+  if (exported_by_kernel) h->clip_stats_ready = n_clips;  // only now: the export kernel, which re-initialises the records, has run
+  for (int64_t i = 0; i < n_clips; ++i)
+    status[i] = offs[i + 1] > offs[i] && (h->clip_stats_host[4 * i + 1] || !(prm->onset_threshold > 0.0)) ? 1 : 0;
+}
+
 }  // namespace
 
 int bp::note_tables(bp_handle h, const void** tab, const double** gauss) {
@@ -571,6 +742,69 @@ int bp_track_maps(bp_handle h, int64_t n_frames, float* note, float* onset, floa
   return finish(h, copy_maps(h, {note, onset, contour}, m, n_frames,
                              mem_kind == BP_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice));
 }
+
+int bp_clips_row_offsets(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int64_t* offsets) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  return check_clips(h, "bp_clips_row_offsets", n_clips, clips, sample_rate, BP_MEM_HOST, false, nullptr, offsets);
+}
+
+int bp_infer_clips_candidates(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                              const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_infer_clips_candidates";
+  if (!params || (n_clips > 0 && !status)) {
+    h->err = std::string(what) + ": null params / status";
+    return BP_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> n_model((size_t)(n_clips > 0 ? n_clips : 0)), offs((size_t)(n_clips > 0 ? n_clips : 0) + 1);
+  if (int rc = check_clips(h, what, n_clips, clips, sample_rate, pcm_mem_kind, true, n_model.data(), offs.data())) return rc;
+  const int64_t total = offs[(size_t)n_clips];
+  if (total > 0 && (!note_out || !cand_bits)) {
+    h->err = std::string(what) + ": null output pointer";
+    return BP_ERR_INVALID_ARG;
+  }
+  for (int64_t i = 0; i < n_clips; ++i) status[i] = 0;
+  if (total == 0) return BP_OK;  // no clip has a row: nothing to queue
+  BP_HIP(hipSetDevice(h->device));
+  if (sample_rate != h->rate)
+    if (int rc = clips_filter(h, what, sample_rate)) return rc;
+  std::vector<ClipDesc> tab((size_t)n_clips);
+  bool exported_by_kernel = false;
+  if (int rc = finish(h, queue_clips(h, n_clips, clips, sample_rate, pcm_mem_kind, n_model.data(), offs.data(), params, note_out,
+                                     cand_bits, bend_map, tab, &exported_by_kernel)))
+    return rc;
+  clips_status(h, n_clips, offs.data(), params, exported_by_kernel, status);
+  return BP_OK;
+}
+
+#ifdef BP_AB_KERNELS
+// The A/B library's test hook for the segmented note candidates (declared nowhere: the tests name it): the clips' maps are
+// given, not made — host maps of offsets[n_clips] rows, clip c at rows [offsets[c], offsets[c + 1]) — and go through what
+// bp_infer_clips_candidates runs behind the model.  The product library has no such call.
+int bp_ab_clips_candidates_from_maps(bp_handle h, int64_t n_clips, const int64_t* offsets, const float* note, const float* onset,
+                                     const float* contour, const bp_note_params* params, float* note_out, uint8_t* cand_bits,
+                                     int8_t* bend_map, int* status) {
+  if (!h || n_clips < 1 || !offsets || !note || !onset || !contour || !params || !note_out || !cand_bits || !status ||
+      offsets[0] != 0 || offsets[n_clips] < 1)
+    return BP_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n_clips; ++i)
+    if (offsets[i + 1] < offsets[i]) return BP_ERR_INVALID_ARG;
+  BP_HIP(hipSetDevice(h->device));
+  const int64_t T = offsets[n_clips];
+  bool exported_by_kernel = false;
+  Maps m;
+  int rc = take_track_out(h, T, &m);
+  if (!rc) {
+    const Maps given{const_cast<float*>(note), const_cast<float*>(onset), const_cast<float*>(contour)};  // only read
+    if (!(rc = copy_maps(h, m, given, T, hipMemcpyHostToDevice)))
+      rc = queue_clips_candidates(h, m, n_clips, offsets, params, note_out, cand_bits, bend_map, &exported_by_kernel);
+    rc = finish(h, rc);
+  }
+  if (rc) return rc;
+  clips_status(h, n_clips, offsets, params, exported_by_kernel, status);
+  return BP_OK;
+}
+#endif
 
 int bp_flac_decode_device(bp_handle h, const void* file, size_t nbytes, int32_t* pcm, int64_t capacity_frames, int64_t* n_frames) {
   if (!h || !n_frames) return BP_ERR_INVALID_ARG;

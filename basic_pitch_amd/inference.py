@@ -379,6 +379,32 @@ class Model:
         self._infer("bp_infer_flac", (data, len(data)), out)
         return out
 
+    # -- many clips in one call (basic_pitch_amd/clips.py) -----------------------------------------
+    def transcribe_clips(
+        self,
+        clips: Sequence[Any],
+        sample_rates: Union[int, Sequence[int]],
+        onset_threshold: float = DEFAULT_ONSET_THRESHOLD,
+        frame_threshold: float = DEFAULT_FRAME_THRESHOLD,
+        minimum_note_length: float = DEFAULT_MINIMUM_NOTE_LENGTH_MS,
+        minimum_frequency: Optional[float] = None,
+        maximum_frequency: Optional[float] = None,
+        multiple_pitch_bends: bool = False,
+        melodia_trick: bool = True,
+        midi_tempo: float = DEFAULT_MINIMUM_MIDI_TEMPO,
+        threads: int = 8,
+    ) -> "List[Tuple[Any, List[Any]]]":
+        """Many short clips -> [(midi_data, note_events)] in input order, with the decoding parameters of `predict`.
+        `clips`: numpy arrays [n] or [n, channels] of float32, int16, int32, uint8 or float64 samples; `sample_rates`: one int
+        for all or one per clip.  The clips of a rate go to the device in ONE call (`bp_infer_clips_candidates`: a constant
+        number of launches per batch of windows instead of about ten per clip) and come back as what the sequential half of
+        note decoding needs; the events of a clip are those of `predict_pcm_raw` + `model_output_to_notes` on it alone."""
+        from . import clips as _clips
+
+        return _clips.transcribe_clips(self, clips, sample_rates, onset_threshold, frame_threshold, minimum_note_length,
+                                       minimum_frequency, maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo,
+                                       threads)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
