@@ -16,6 +16,6 @@ from .inference import (  # noqa: F401
 from .inference import predict, predict_and_save, predict_and_save_many, predict_many, transcribe_files  # noqa: F401
 from . import clips  # noqa: F401
 from .sharding import predict_and_save_sharded, predict_many_sharded  # noqa: F401
-from .streaming import Stream, StreamingTranscriber, peek_streams, push_streams  # noqa: F401
+from .streaming import Stream, StreamingTranscriber, peek_streams, push_streams, transcripts  # noqa: F401
 
 __version__ = "0.1.0"

@@ -151,6 +151,21 @@ class bp_note_event(C.Structure):
     ]
 
 
+class bp_stream_update(C.Structure):
+    """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
+
+    _fields_ = [
+        ("stream", C.c_void_p),
+        ("held_rows", C.c_int64),
+        ("first_row", C.c_int64),
+        ("n_rows", C.c_int64),
+        ("new_row", C.c_int64),
+        ("note_offset", C.c_int64),
+        ("bits_offset", C.c_int64),
+        ("status", C.c_int),
+    ]
+
+
 # every symbol include/basic_pitch_amd.h declares (tests check they are all exported)
 EXPORTED_SYMBOLS = [
     "bp_create",
@@ -228,6 +243,11 @@ ROLLING_SYMBOLS = [
     "bp_stream_candidates_rolling",
     "bp_stream_rolling_maps",
     "bp_notes_decode_candidates_at",
+]
+# every symbol include/basic_pitch_amd_update.h declares (bound in basic_pitch_amd/streaming.py)
+UPDATE_SYMBOLS = [
+    "bp_streams_update_layout",
+    "bp_streams_candidates",
 ]
 # every symbol include/basic_pitch_amd_clips.h declares (bound in basic_pitch_amd/clips.py)
 CLIPS_SYMBOLS = [

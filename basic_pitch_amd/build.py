@@ -18,6 +18,7 @@ HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd.h")
 LIVE_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_live.h")
 ROLLING_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_rolling.h")
 CLIPS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_clips.h")
+UPDATE_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_update.h")
 
 SOURCES = [
     "bp_api.hip",
@@ -54,7 +55,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

@@ -91,6 +91,15 @@ struct bp_context {
     bp::ResamplePlan plan;
   };
   std::vector<StreamTaps> st_taps;
+  // the updates of many streams in one step (bp_streams_candidates), all grow-only and scratch of one call: the table of
+  // streams with its prefix arrays, the packed note rows, bends and bitmaps on their way home, one stats record of 16 bytes per
+  // stream and the page-locked copy of the records (4 words per stream)
+  Table up_tab;
+  Buffer<float> up_note;
+  Buffer<int8_t> up_bend;
+  Buffer<uint8_t> up_bits;
+  Table up_stats;
+  bp::PinnedBuffer<int> up_stats_host;
 
   // stage timing: a ring of event sets, one per chunk, averaged by bp_get_stage_ms
   static constexpr int kTimedRing = 128;

@@ -180,5 +180,34 @@ void launch_ring_peaks(const float* ring, int64_t cap, int64_t a, int64_t T, int
                        uint8_t* bits, hipStream_t s);
 void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, const void* tab, const double* gauss, int8_t* bend,
                        hipStream_t s);
+// the rows of [a, T) that launch_ring_stats scans are [a, *e0) and [*e1, T); the table's blocks [*e0, *e1) / 64 join whole
+void note_ring_edges(int64_t a, int64_t R, int64_t T, int64_t* e0, int64_t* e1);
+
+// The updates of many streams in one step (bp_streams_candidates): one stream of the table a call uploads.  Behind the table
+// lie kStreamUpdatePrefixes arrays of n + 1 int64, the running totals over the streams of: tail rows, workgroups of the stats
+// launch (streams_stats_chunks of the edge rows), bitmap rows T - a, workgroups of the bend launch (streams_bend_blocks of
+// T - n0, 0 without bends), note rows T - n0.
+struct StreamUpdate {
+  float* ring;                                         // the store: [cap] note, [cap] onset, [cap] contour
+  const float *tail_note, *tail_onset, *tail_contour;  // the tail's rows, linear, row 0 = absolute row R (the step's scratch)
+  const void* records;   // the stream's records: the block table (n_tab > 0), or the one record its final rows have joined
+  int64_t cap, a, R, T, n0;
+  int64_t e0, e1;        // the stats launch scans rows [a, e0) and [e1, T) (note_ring_edges; a keeping stream: a and R)
+  int64_t n_tab;         // records of the block table; 0: one carried record
+  int64_t note_offset, bits_offset;  // its first row of the packed note / bend rows, of the packed bitmap
+  double onset_thresh;
+  int lo, hi, infer, bends;
+};
+constexpr int kStreamUpdatePrefixes = 5;
+int64_t streams_stats_chunks(int64_t n_edge);
+int64_t streams_bend_blocks(int64_t n_rows);
+// the tails' rows to their slots, frequency-constrained per stream (launch_ring_put for every stream)
+void launch_streams_put(const StreamUpdate* u, const int64_t* pre, int64_t n, int64_t tail_rows, hipStream_t s);
+// per stream: its update record (`stats`: n records of 16 bytes) from its table or carried record and its edge rows, then, packed
+// and linear in argument order, the bitmap of [a, T), the bends and the note rows of [n0, T); the last four arguments before the
+// queue are device buffers
+void launch_streams_candidates(const StreamUpdate* u, const int64_t* pre, int64_t n, int64_t chunks, int64_t bits_rows,
+                               int64_t bend_blocks, int64_t note_rows, const void* tab, const double* gauss, void* stats,
+                               uint8_t* bits, int8_t* bend, float* note, hipStream_t s);
 
 }  // namespace bp

@@ -37,12 +37,15 @@ __global__ __launch_bounds__(256) void nd_constrain_kernel(float* __restrict__ n
   if (f < lo || f >= hi) note[i] = onset[i] = 0.0f;
 }
 
+// the initial values of a record: maxima that any row exceeds or equals, no NaN seen
+__device__ __forceinline__ void nd_stats_reset(NdStats* st) {
+  st->max_on_ord = f2ord(-__int_as_float(0x7f800000));
+  st->nan = 0;
+  st->max_fd_bits = 0ull;
+}
+
 __global__ __launch_bounds__(64) void nd_stats_init_kernel(NdStats* st) {
-  if (threadIdx.x == 0) {
-    st->max_on_ord = f2ord(-__int_as_float(0x7f800000));
-    st->nan = 0;
-    st->max_fd_bits = 0ull;
-  }
+  if (threadIdx.x == 0) nd_stats_reset(st);
 }
 
 // The extrema of one row join the lane's (lanes take bins lane and lane + 64).  with_fd: the row has two predecessors in its
@@ -195,9 +198,7 @@ __device__ __forceinline__ int64_t nd_clip_of_row(const int64_t* __restrict__ of
 __global__ __launch_bounds__(256) void nd_clips_stats_init_kernel(NdStats* __restrict__ table, int64_t n) {
   const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (c >= n) return;
-  table[c].max_on_ord = f2ord(-__int_as_float(0x7f800000));
-  table[c].nan = 0;
-  table[c].max_fd_bits = 0ull;
+  nd_stats_reset(table + c);
 }
 
 // Extrema per clip.  A workgroup takes kNdClipRows consecutive rows and, for every clip that owns some of them, folds those
@@ -282,16 +283,18 @@ __device__ __forceinline__ int nd_bend_argmax_nan(const double* __restrict__ win
 
 // kRing: row t of the T rows is absolute row first + t of a ring of `cap` contour rows (slot r % cap); the bends are written
 // linear, row t at bend + t * 88, as in the linear form (first = 0, cap unused).
+// `block`: which kNdBendFrames rows of the T the workgroup takes.  A device function: the kernel of one track or ring and the
+// kernel of many streams (nd_streams_bend_kernel, below) run this one body.
 template <bool kRing>
-__global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict__ contour, int64_t first, int64_t T, int64_t cap,
-                                                      const int4* __restrict__ tab, const double* __restrict__ gauss,
-                                                      int8_t* __restrict__ bend) {
+__device__ __forceinline__ void nd_bend_block(const float* __restrict__ contour, int64_t first, int64_t T, int64_t cap,
+                                              const int4* __restrict__ tab, const double* __restrict__ gauss,
+                                              int8_t* __restrict__ bend, int64_t block) {
   __shared__ __attribute__((aligned(16))) double s_row[kNdBendFrames * kNdBendPitch];
   __shared__ int s_start[kNdF], s_first[kNdF];
   __shared__ double s_g[51];
   __shared__ int s_nan;
   const int tid = threadIdx.x;
-  const int64_t t0 = (int64_t)blockIdx.x * kNdBendFrames;
+  const int64_t t0 = block * kNdBendFrames;
   const double ninf = -__longlong_as_double(0x7ff0000000000000ll);
   if (tid == 0) s_nan = 0;
   if (tid >= 128 && tid < 128 + 51) s_g[tid - 128] = gauss[tid - 128];
@@ -345,6 +348,13 @@ __global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict
       bend[t0 * kNdF + item] = (int8_t)(best - 25);
     }
   }
+}
+
+template <bool kRing>
+__global__ __launch_bounds__(256, 3) void nd_bend_kernel(const float* __restrict__ contour, int64_t first, int64_t T, int64_t cap,
+                                                      const int4* __restrict__ tab, const double* __restrict__ gauss,
+                                                      int8_t* __restrict__ bend) {
+  nd_bend_block<kRing>(contour, first, T, cap, tab, gauss, bend, (int64_t)blockIdx.x);
 }
 
 // device -> page-locked host memory, by the compute queue: the note map, the bitmap and the bend map of a track in one
@@ -453,23 +463,30 @@ void launch_clips_candidates(float* note, float* onset, const float* contour, co
 constexpr int kNdRingBlock = 64;
 
 // Rows [t0, t0 + n) of linear maps (row 0 of src_* is absolute row t0) go to their slots, constrain_frequency applied on the
-// way (bins outside [lo, hi) of note and onset become 0).  An item is one float; n <= cap, so no slot is written twice.  Scalar
-// loads: the source may be a caller's device buffer, of which only float alignment is known.
+// way (bins outside [lo, hi) of note and onset become 0).  An item is one float, float c of row r of the source; n <= cap, so no
+// slot is written twice.  Scalar loads: the source may be a caller's device buffer, of which only float alignment is known.
+constexpr int kNdPutRow = 2 * kNdF + kNdFC;
+__device__ __forceinline__ void nd_ring_put_item(const float* __restrict__ src_note, const float* __restrict__ src_onset,
+                                                 const float* __restrict__ src_contour, float* __restrict__ note,
+                                                 float* __restrict__ onset, float* __restrict__ contour, int64_t t0, int64_t cap,
+                                                 int lo, int hi, int64_t r, int c) {
+  const int64_t slot = (t0 + r) % cap;
+  if (c < kNdF)
+    note[slot * kNdF + c] = c < lo || c >= hi ? 0.0f : src_note[r * kNdF + c];
+  else if (c < 2 * kNdF)
+    onset[slot * kNdF + c - kNdF] = c - kNdF < lo || c - kNdF >= hi ? 0.0f : src_onset[r * kNdF + c - kNdF];
+  else
+    contour[slot * kNdFC + c - 2 * kNdF] = src_contour[r * kNdFC + c - 2 * kNdF];
+}
+
 __global__ __launch_bounds__(256) void nd_ring_put_kernel(const float* __restrict__ src_note, const float* __restrict__ src_onset,
                                                           const float* __restrict__ src_contour, float* __restrict__ note,
                                                           float* __restrict__ onset, float* __restrict__ contour, int64_t t0,
                                                           int64_t n, int64_t cap, int lo, int hi) {
-  constexpr int kRow = 2 * kNdF + kNdFC;
   const int64_t step = (int64_t)gridDim.x * 256;
-  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * kRow; i += step) {
-    const int64_t r = i / kRow, slot = (t0 + r) % cap;
-    const int c = (int)(i - r * kRow);
-    if (c < kNdF)
-      note[slot * kNdF + c] = c < lo || c >= hi ? 0.0f : src_note[r * kNdF + c];
-    else if (c < 2 * kNdF)
-      onset[slot * kNdF + c - kNdF] = c - kNdF < lo || c - kNdF >= hi ? 0.0f : src_onset[r * kNdF + c - kNdF];
-    else
-      contour[slot * kNdFC + c - 2 * kNdF] = src_contour[r * kNdFC + c - 2 * kNdF];
+  for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n * kNdPutRow; i += step) {
+    const int64_t r = i / kNdPutRow;
+    nd_ring_put_item(src_note, src_onset, src_contour, note, onset, contour, t0, cap, lo, hi, r, (int)(i - r * kNdPutRow));
   }
 }
 
@@ -502,7 +519,33 @@ __global__ __launch_bounds__(256) void nd_ring_fold_kernel(const float* __restri
 
 // The record of the slice [a, T) (st holds the initial values): the table's blocks [e0, e1) / kNdRingBlock, which lie wholly in
 // [a + 2, R), joined by workgroup 0, and the rows [a, e0) and [e1, T) scanned, a wave per row, fd only from frame 2 of the
-// slice on.  Without a whole block e0 == e1 and the two ranges are the slice.
+// slice on.  Without a whole block e0 == e1 and the two ranges are the slice.  The two halves are device functions: the kernel
+// of one stream and the kernel of many (nd_streams_stats_kernel, below) run the same bodies.
+
+// edge rows j0, j0 + step, ... < j1 of the n_edge = (e0 - a) + (T - e1) join the wave's extrema
+__device__ __forceinline__ void nd_edge_rows(const float* __restrict__ note, const float* __restrict__ onset, int64_t a, int64_t e0,
+                                             int64_t e1, int64_t cap, int infer, int64_t j0, int64_t j1, int64_t step, int lane,
+                                             float& mo, double& mfd, int& nan) {
+  const int64_t n_head = e0 - a;
+  for (int64_t j = j0; j < j1; j += step) {
+    const int64_t t = j < n_head ? a + j : e1 + (j - n_head);
+    nd_row<true>(note, onset, t, cap, infer && t - a >= 2, lane, mo, mfd, nan);
+  }
+}
+
+// the records of the table's blocks [e0, e1) / kNdRingBlock join the thread's extrema, a thread per block
+__device__ __forceinline__ void nd_join_blocks(const NdStats* __restrict__ table, int64_t n_tab, int64_t e0, int64_t e1, float& mo,
+                                               double& mfd, int& nan) {
+  for (int64_t b = e0 / kNdRingBlock + threadIdx.x; b < e1 / kNdRingBlock; b += 256) {
+    const NdStats rec = table[b % n_tab];
+    const float o = ord2f(rec.max_on_ord);
+    const double d = __longlong_as_double((long long)rec.max_fd_bits);
+    mo = o > mo ? o : mo;
+    mfd = d > mfd ? d : mfd;
+    nan |= rec.nan;
+  }
+}
+
 __global__ __launch_bounds__(256) void nd_ring_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t a,
                                                             int64_t e0, int64_t e1, int64_t T, int64_t cap, int infer,
                                                             const NdStats* __restrict__ table, int64_t n_tab,
@@ -511,25 +554,19 @@ __global__ __launch_bounds__(256) void nd_ring_stats_kernel(const float* __restr
   float mo = -__int_as_float(0x7f800000);
   double mfd = 0.0;
   int nan = 0;
-  const int64_t n_head = e0 - a, n_edge = n_head + (T - e1);
-  for (int64_t j = (int64_t)blockIdx.x * 4 + wave; j < n_edge; j += (int64_t)gridDim.x * 4) {
-    const int64_t t = j < n_head ? a + j : e1 + (j - n_head);
-    nd_row<true>(note, onset, t, cap, infer && t - a >= 2, lane, mo, mfd, nan);
-  }
-  if (blockIdx.x == 0)
-    for (int64_t b = e0 / kNdRingBlock + threadIdx.x; b < e1 / kNdRingBlock; b += 256) {
-      const NdStats rec = table[b % n_tab];
-      const float o = ord2f(rec.max_on_ord);
-      const double d = __longlong_as_double((long long)rec.max_fd_bits);
-      mo = o > mo ? o : mo;
-      mfd = d > mfd ? d : mfd;
-      nan |= rec.nan;
-    }
+  nd_edge_rows(note, onset, a, e0, e1, cap, infer, (int64_t)blockIdx.x * 4 + wave, (e0 - a) + (T - e1), (int64_t)gridDim.x * 4, lane,
+               mo, mfd, nan);
+  if (blockIdx.x == 0) nd_join_blocks(table, n_tab, e0, e1, mo, mfd, nan);
   nd_reduce(mo, mfd, nan);
   if (threadIdx.x == 0) nd_publish(st, mo, mfd, nan);
 }
 
 int64_t note_ring_records(int64_t cap) { return (cap + kNdRingBlock - 1) / kNdRingBlock + 2 + 1; }
+
+void note_ring_edges(int64_t a, int64_t R, int64_t T, int64_t* e0, int64_t* e1) {
+  *e0 = (a + 2 + kNdRingBlock - 1) / kNdRingBlock * kNdRingBlock, *e1 = R / kNdRingBlock * kNdRingBlock;
+  if (*e0 >= *e1) *e0 = *e1 = T;
+}
 
 static NdStats* ring_table(void* records) { return static_cast<NdStats*>(records); }
 static int64_t ring_n_tab(int64_t cap) { return note_ring_records(cap) - 1; }
@@ -552,8 +589,8 @@ void launch_ring_fold(const float* ring, int64_t cap, int64_t t0, int64_t t1, in
 
 void launch_ring_stats(const float* ring, int64_t cap, int64_t a, int64_t R, int64_t T, int infer, void* records, hipStream_t s) {
   if (T <= a) return;
-  int64_t e0 = (a + 2 + kNdRingBlock - 1) / kNdRingBlock * kNdRingBlock, e1 = R / kNdRingBlock * kNdRingBlock;
-  if (e0 >= e1) e0 = e1 = T;
+  int64_t e0, e1;
+  note_ring_edges(a, R, T, &e0, &e1);
   const int64_t n_edge = (e0 - a) + (T - e1);
   const unsigned rows4 = (unsigned)((n_edge + 3) / 4);
   NdStats* st = ring_table(records) + ring_n_tab(cap);
@@ -574,6 +611,124 @@ void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, co
   if (n <= 0) return;
   hipLaunchKernelGGL(nd_bend_kernel<true>, dim3((unsigned)((n + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s,
                      ring + cap * 2 * kNdF, t0, n, cap, static_cast<const int4*>(tab), gauss, bend);
+}
+
+// ---- the updates of many streams in one step (bp_streams_candidates, stream_api.hip) -------------------------------------------
+// What the kernels above do for one stream's store, for n stores at once: the segmented form the clips call introduced, a
+// segment being a stream.  Stream c is u[c]; the work items of each launch are counted over all streams and an item finds its
+// stream by nd_clip_of_row in a prefix array (pre + k * (n + 1), k = one of the kNdPre* below).  Every body is the device
+// function of the single-stream kernel: nd_ring_put_item, nd_edge_rows / nd_join_blocks / nd_reduce / nd_publish,
+// nd_candidates_row<true>, nd_bend_block<true>.  The update records are a table of the handle's, record c for stream c.
+enum { kNdPreTail, kNdPreChunk, kNdPreBits, kNdPreBend, kNdPreNote, kNdPreArrays };
+static_assert(kNdPreArrays == kStreamUpdatePrefixes, "the host's table has one array per launch");
+constexpr int kNdEdgeChunk = 64;  // edge rows a workgroup of the stats launch scans
+
+// the rows of all tails to their slots: a workgroup walks rows, its threads the 440 floats of one
+__global__ __launch_bounds__(256) void nd_streams_put_kernel(const StreamUpdate* __restrict__ u, const int64_t* __restrict__ offs,
+                                                             int64_t n) {
+  const int64_t total = offs[n];
+  for (int64_t r = blockIdx.x; r < total; r += gridDim.x) {  // block-uniform
+    const int64_t c = nd_clip_of_row(offs, n, r), local = r - offs[c];
+    const StreamUpdate& d = u[c];
+    for (int col = threadIdx.x; col < kNdPutRow; col += 256)
+      nd_ring_put_item(d.tail_note, d.tail_onset, d.tail_contour, d.ring, d.ring + d.cap * kNdF, d.ring + d.cap * 2 * kNdF, d.R, d.cap,
+                       d.lo, d.hi, local, col);
+  }
+}
+
+// record c: the initial values for a rolling stream, a copy of the record its final rows have joined for a keeping stream
+__global__ __launch_bounds__(256) void nd_streams_stats_init_kernel(const StreamUpdate* __restrict__ u, int64_t n,
+                                                                    NdStats* __restrict__ st) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= n) return;
+  if (u[c].n_tab == 0 && u[c].records)
+    st[c] = *static_cast<const NdStats*>(u[c].records);
+  else
+    nd_stats_reset(st + c);
+}
+
+// A workgroup per stream and chunk of kNdEdgeChunk edge rows; the first of a rolling stream also joins the whole blocks of
+// its table.  A keeping stream's edge rows are its tail (e0 = a, e1 = R).  Maxima and an OR: the record is the single
+// update's whatever the partition.
+__global__ __launch_bounds__(256) void nd_streams_stats_kernel(const StreamUpdate* __restrict__ u, const int64_t* __restrict__ offs,
+                                                               int64_t n, NdStats* __restrict__ st) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int64_t c = nd_clip_of_row(offs, n, blockIdx.x), chunk = blockIdx.x - offs[c];
+  const StreamUpdate& d = u[c];
+  float mo = -__int_as_float(0x7f800000);
+  double mfd = 0.0;
+  int nan = 0;
+  const int64_t n_edge = (d.e0 - d.a) + (d.T - d.e1), j0 = chunk * kNdEdgeChunk;
+  nd_edge_rows(d.ring, d.ring + d.cap * kNdF, d.a, d.e0, d.e1, d.cap, d.infer, j0 + wave,
+               j0 + kNdEdgeChunk < n_edge ? j0 + kNdEdgeChunk : n_edge, 4, lane, mo, mfd, nan);
+  if (chunk == 0 && d.n_tab) nd_join_blocks(static_cast<const NdStats*>(d.records), d.n_tab, d.e0, d.e1, mo, mfd, nan);
+  nd_reduce(mo, mfd, nan);
+  if (threadIdx.x == 0) nd_publish(st + c, mo, mfd, nan);
+}
+
+// the bitmaps of all slices, packed: a wave per row, the frame counted from its stream's row a
+__global__ __launch_bounds__(256) void nd_streams_candidates_kernel(const StreamUpdate* __restrict__ u,
+                                                                    const int64_t* __restrict__ offs, int64_t n,
+                                                                    const NdStats* __restrict__ st, uint32_t* __restrict__ bits) {
+  const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (r >= offs[n]) return;
+  const int64_t c = nd_clip_of_row(offs, n, r), t = r - offs[c];
+  const StreamUpdate& d = u[c];
+  nd_candidates_row<true>(d.ring, d.ring + d.cap * kNdF, t, d.T - d.a, (d.a + t) % d.cap, d.cap, d.infer, d.onset_thresh, st + c,
+                          bits + d.bits_offset * 3, threadIdx.x & 63);
+}
+
+// A workgroup takes kNdBendFrames rows of ONE stream, counted from its row n0 as the single update counts them: a block's NaN
+// switch sees the rows it would see there.
+__global__ __launch_bounds__(256, 3) void nd_streams_bend_kernel(const StreamUpdate* __restrict__ u, const int64_t* __restrict__ offs,
+                                                                 int64_t n, const int4* __restrict__ tab,
+                                                                 const double* __restrict__ gauss, int8_t* __restrict__ bend) {
+  const int64_t c = nd_clip_of_row(offs, n, blockIdx.x);
+  const StreamUpdate& d = u[c];
+  nd_bend_block<true>(d.ring + d.cap * 2 * kNdF, d.n0, d.T - d.n0, d.cap, tab, gauss, bend + d.note_offset * kNdF,
+                      (int64_t)blockIdx.x - offs[c]);
+}
+
+// note rows [n0, T) of every stream from their slots to the packed buffer: 32 threads a row, 22 of them a float4 each (a row is
+// 352 bytes and both bases come from the allocator: every float4 is aligned)
+static_assert(kNdF % 4 == 0, "whole float4s");
+__global__ __launch_bounds__(256) void nd_streams_gather_kernel(const StreamUpdate* __restrict__ u, const int64_t* __restrict__ offs,
+                                                                int64_t n, float4* __restrict__ out) {
+  const int64_t r = (int64_t)blockIdx.x * 8 + (threadIdx.x >> 5);
+  const int q = threadIdx.x & 31;
+  if (r >= offs[n] || q >= kNdF / 4) return;
+  const int64_t c = nd_clip_of_row(offs, n, r);
+  const StreamUpdate& d = u[c];
+  const int64_t slot = (d.n0 + (r - offs[c])) % d.cap;
+  out[r * (kNdF / 4) + q] = reinterpret_cast<const float4*>(d.ring + slot * kNdF)[q];
+}
+
+void launch_streams_put(const StreamUpdate* u, const int64_t* pre, int64_t n, int64_t tail_rows, hipStream_t s) {
+  if (tail_rows <= 0) return;
+  hipLaunchKernelGGL(nd_streams_put_kernel, dim3((unsigned)(tail_rows < 4096 ? tail_rows : 4096)), dim3(256), 0, s, u,
+                     pre + kNdPreTail * (n + 1), n);
+}
+
+int64_t streams_stats_chunks(int64_t n_edge) { return (n_edge + kNdEdgeChunk - 1) / kNdEdgeChunk; }
+int64_t streams_bend_blocks(int64_t n_rows) { return (n_rows + kNdBendFrames - 1) / kNdBendFrames; }
+
+void launch_streams_candidates(const StreamUpdate* u, const int64_t* pre, int64_t n, int64_t chunks, int64_t bits_rows,
+                               int64_t bend_blocks, int64_t note_rows, const void* tab, const double* gauss, void* stats,
+                               uint8_t* bits, int8_t* bend, float* note, hipStream_t s) {
+  const int64_t m = n + 1;
+  NdStats* st = static_cast<NdStats*>(stats);
+  hipLaunchKernelGGL(nd_streams_stats_init_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, u, n, st);
+  if (chunks > 0)
+    hipLaunchKernelGGL(nd_streams_stats_kernel, dim3((unsigned)chunks), dim3(256), 0, s, u, pre + kNdPreChunk * m, n, st);
+  if (bits_rows > 0)
+    hipLaunchKernelGGL(nd_streams_candidates_kernel, dim3((unsigned)((bits_rows + 3) / 4)), dim3(256), 0, s, u, pre + kNdPreBits * m, n,
+                       st, reinterpret_cast<uint32_t*>(bits));
+  if (bend_blocks > 0)
+    hipLaunchKernelGGL(nd_streams_bend_kernel, dim3((unsigned)bend_blocks), dim3(256), 0, s, u, pre + kNdPreBend * m, n,
+                       static_cast<const int4*>(tab), gauss, bend);
+  if (note_rows > 0)
+    hipLaunchKernelGGL(nd_streams_gather_kernel, dim3((unsigned)((note_rows + 7) / 8)), dim3(256), 0, s, u, pre + kNdPreNote * m, n,
+                       reinterpret_cast<float4*>(note));
 }
 
 }  // namespace bp

@@ -1,4 +1,5 @@
-// C ABI of the streaming sessions (include/basic_pitch_amd.h, include/basic_pitch_amd_live.h, include/basic_pitch_amd_rolling.h): audio that arrives over time -> the rows of the un-overlapped
+// C ABI of the streaming sessions (include/basic_pitch_amd.h, include/basic_pitch_amd_live.h, include/basic_pitch_amd_rolling.h,
+// include/basic_pitch_amd_update.h): audio that arrives over time -> the rows of the un-overlapped
 // posteriorgrams as they become final, for one stream or for many streams of one handle per step.
 //
 // A stream keeps on the device a ring of the model-rate signal that reaches back to the first sample of its oldest
@@ -43,6 +44,9 @@
 //     from the table's whole blocks and a scan of the edge rows.  Nothing such a stream owns, sends home or computes per
 //     update grows with its age.
 //
+// bp_streams_candidates is that update for n streams of either mode in one step (queue_updates): one peek step for all tails,
+// one table of streams (StreamUpdate, note_device.hip "the updates of many streams"), the segmented launches, packed rows home.
+//
 // A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the
 // handle's device and deletes the state, and an open or keep that fails leaves nothing behind.
 #include <algorithm>
@@ -50,7 +54,7 @@
 #include <memory>
 
 #include "bp_context.h"
-#include "../../include/basic_pitch_amd_rolling.h"
+#include "../../include/basic_pitch_amd_update.h"
 
 using namespace bp;
 
@@ -156,11 +160,9 @@ int64_t kept_bytes(const bp_stream_state* s) {
 // frequency-constrained on the way; they have not joined a stats record yet.  In the A/B library the cell that
 // bp_ab_stream_poison names, if it lies in them, then becomes a quiet NaN — after the constraint, so a poisoned cell outside
 // [lo, hi) stays a NaN in either mode.  The product library has no such hook.
-int put_rows(bp_handle h, const bp_stream_state* s, const Maps& src, int64_t r0, int64_t r1) {
-  const auto& k = s->kept;
-  launch_ring_put(src.note, src.onset, src.contour, k.rows, k.cap, r0, r1 - r0, s->lo, s->hi, h->stream);
-  BP_HIP(hipGetLastError());
+int poison_rows(bp_handle h, const bp_stream_state* s, int64_t r0, int64_t r1) {
 #ifdef BP_AB_KERNELS
+  const auto& k = s->kept;
   if (s->ab_nan_row >= r0 && s->ab_nan_row < r1) {
     const Maps kept = maps_at(k.rows, k.cap);
     float* cell = (s->ab_nan_map ? kept.onset : kept.note) + (s->ab_nan_row % k.cap) * kFreqN + s->ab_nan_bin;
@@ -168,6 +170,13 @@ int put_rows(bp_handle h, const bp_stream_state* s, const Maps& src, int64_t r0,
   }
 #endif
   return BP_OK;
+}
+
+int put_rows(bp_handle h, const bp_stream_state* s, const Maps& src, int64_t r0, int64_t r1) {
+  const auto& k = s->kept;
+  launch_ring_put(src.note, src.onset, src.contour, k.rows, k.cap, r0, r1 - r0, s->lo, s->hi, h->stream);
+  BP_HIP(hipGetLastError());
+  return poison_rows(h, s, r0, r1);
 }
 
 // the tail of the signal a peek makes (samples n_res ... resampled length) fits the ring's free room: see the file header
@@ -749,6 +758,156 @@ int bp_stream_rolling_maps(bp_stream s, int with_tail, float* note, float* onset
     s->broken = true;
     return rc;
   }
+  return BP_OK;
+}
+
+// ---- the updates of n streams in one step (include/basic_pitch_amd_update.h) -------------------------------------------------
+// every per-stream argument, in index order, and the out fields but status; tail[i]: the rows of stream i's peek
+static int plan_updates(bp_handle h, const char* what, int64_t n, bp_stream_update* u, int with_tail, std::vector<int64_t>& tail,
+                        int64_t* note_rows, int64_t* bits_rows) {
+  auto invalid = [&](const std::string& why) {
+    h->err = std::string(what) + ": " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (n < 0 || (n > 0 && !u)) return invalid("negative count or null array of updates");
+  tail.assign((size_t)n, 0);
+  *note_rows = *bits_rows = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    bp_stream_state* s = u[i].stream;
+    const std::string at = "stream " + std::to_string(i) + ": ";
+    if (!s) return invalid(at + "null stream");
+    if (s->h != h) return invalid(at + "a stream of another handle");
+    for (int64_t j = 0; j < i; ++j)
+      if (u[j].stream == s) return invalid(at + "the same stream twice in one step (also stream " + std::to_string(j) + ")");
+    if (!s->kept.cap) return invalid(at + "the stream retains nothing (bp_stream_keep or bp_stream_keep_rolling)");
+    if (s->broken) return invalid(at + "a stream whose earlier call failed on the device: only bp_stream_close is valid");
+    if (u[i].held_rows < 0 || u[i].held_rows > s->rows_out)
+      return invalid(at + "held_rows " + std::to_string(u[i].held_rows) + " is not in 0 ... " + std::to_string(s->rows_out) +
+                     ", the final rows");
+    tail[(size_t)i] = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
+    const std::string who = std::string(what) + ": stream " + std::to_string(i);
+    if (int rc = tail_refused(s, who.c_str(), s->kept.table, tail[(size_t)i])) return rc;
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const bp_stream_state* s = u[i].stream;
+    const int64_t T = s->rows_out + tail[(size_t)i], a = bp_stream_horizon_first_row(T, s->kept.horizon);
+    u[i].first_row = a, u[i].n_rows = T, u[i].new_row = std::max(u[i].held_rows, a);
+    u[i].note_offset = *note_rows, u[i].bits_offset = *bits_rows;
+    *note_rows += T - u[i].new_row, *bits_rows += T - a;
+  }
+  return BP_OK;
+}
+
+// The step: the tails of all streams through one peek step into the scratch, the table of streams in one copy, the segmented
+// launches of note_device.hip, the packed results and the n records home.  `tab`: the table's host form, alive until the wait.
+static int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, const std::vector<int64_t>& tail, int64_t note_rows,
+                         int64_t bits_rows, float* note_out, int8_t* bend_out, uint8_t* bits_out, std::vector<WindowSeg>& segs,
+                         std::vector<uint8_t>& tab) {
+  hipStream_t q = h->stream;
+  const void* bend_tab = nullptr;
+  const double* gauss = nullptr;
+  int rc = note_tables(h, &bend_tab, &gauss);
+  if (rc) return rc;
+  const size_t m = (size_t)n + 1;
+  tab.assign((size_t)n * sizeof(StreamUpdate) + kStreamUpdatePrefixes * m * sizeof(int64_t), 0);
+  StreamUpdate* d = reinterpret_cast<StreamUpdate*>(tab.data());
+  int64_t* pre = reinterpret_cast<int64_t*>(tab.data() + (size_t)n * sizeof(StreamUpdate));
+  int64_t *pre_tail = pre, *pre_chunk = pre + m, *pre_bits = pre + 2 * m, *pre_bend = pre + 3 * m, *pre_note = pre + 4 * m;
+  // everything the step needs, before anything is queued
+  int64_t tail_rows = 0;
+  for (int64_t t : tail) tail_rows += t;
+  bool bends = false;
+  for (int64_t i = 0; i < n; ++i) bends = bends || (bend_out && u[i].stream->prm.include_pitch_bends != 0 && u[i].n_rows > u[i].new_row);
+  BP_HIP(h->st_out.reserve((size_t)(tail_rows * kMapsRow)));
+  BP_HIP(h->up_tab.reserve(tab.size()));
+  BP_HIP(h->up_note.reserve((size_t)(note_rows * kFreqN)));
+  BP_HIP(h->up_bend.reserve(bends ? (size_t)(note_rows * kFreqN) : 0));
+  BP_HIP(h->up_bits.reserve((size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES)));
+  BP_HIP(h->up_stats.reserve((size_t)(n * kStatsFloats * 4)));
+  BP_HIP(h->up_stats_host.reserve((size_t)(n * kStatsFloats)));
+
+  std::vector<Entry> es;
+  int64_t at = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    bp_stream_state* s = u[i].stream;
+    const auto& k = s->kept;
+    const int64_t t = tail[(size_t)i], T = u[i].n_rows, a = u[i].first_row, n0 = u[i].new_row, R = s->rows_out;
+    const Maps rows = maps_at(h->st_out + at * kMapsRow, t);
+    if (t > 0) es.push_back(plan_entry(s, kPeek, 0, t, rows));
+    at += t;
+    StreamUpdate& e = d[i];
+    e.ring = k.rows;
+    e.tail_note = rows.note, e.tail_onset = rows.onset, e.tail_contour = rows.contour;
+    e.records = k.rec;
+    e.cap = k.cap, e.a = a, e.R = R, e.T = T, e.n0 = n0;
+    e.e0 = a, e.e1 = R;  // a keeping stream: the tail joins a copy of the carried record
+    if (k.table && T > a) note_ring_edges(a, R, T, &e.e0, &e.e1);
+    e.n_tab = k.table ? n_records(k) - 1 : 0;
+    e.note_offset = u[i].note_offset, e.bits_offset = u[i].bits_offset;
+    e.onset_thresh = s->prm.onset_threshold;
+    e.lo = s->lo, e.hi = s->hi, e.infer = s->prm.infer_onsets != 0;
+    e.bends = bend_out && s->prm.include_pitch_bends != 0;
+    pre_tail[i + 1] = pre_tail[i] + t;
+    pre_chunk[i + 1] = pre_chunk[i] + streams_stats_chunks((e.e0 - a) + (T - e.e1));
+    pre_bits[i + 1] = pre_bits[i] + (T - a);
+    pre_bend[i + 1] = pre_bend[i] + (e.bends ? streams_bend_blocks(T - n0) : 0);
+    pre_note[i + 1] = pre_note[i] + (T - n0);
+  }
+  if (!es.empty() && (rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
+  BP_HIP(hipMemcpyAsync(h->up_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, q));
+  const StreamUpdate* d_tab = h->up_tab.as<StreamUpdate>();
+  const int64_t* d_pre = reinterpret_cast<const int64_t*>(h->up_tab + (size_t)n * sizeof(StreamUpdate));
+  launch_streams_put(d_tab, d_pre, n, tail_rows, q);
+  BP_HIP(hipGetLastError());
+  for (int64_t i = 0; i < n; ++i)  // the A/B library's hook, as put_rows applies it
+    if ((rc = poison_rows(h, u[i].stream, d[i].R, d[i].T))) return rc;
+  launch_streams_candidates(d_tab, d_pre, n, pre_chunk[n], bits_rows, pre_bend[n], note_rows, bend_tab, gauss, h->up_stats, h->up_bits,
+                            h->up_bend, h->up_note, q);
+  BP_HIP(hipGetLastError());
+  BP_HIP(hipMemcpyAsync(h->up_stats_host, h->up_stats, (size_t)(n * kStatsFloats * 4), hipMemcpyDeviceToHost, q));
+  BP_HIP(hipMemcpyAsync(bits_out, h->up_bits, (size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES), hipMemcpyDeviceToHost, q));
+  if (note_rows > 0) BP_HIP(hipMemcpyAsync(note_out, h->up_note, (size_t)(note_rows * kFreqN * 4), hipMemcpyDeviceToHost, q));
+  if (bends) BP_HIP(hipMemcpyAsync(bend_out, h->up_bend, (size_t)(note_rows * kFreqN), hipMemcpyDeviceToHost, q));
+  return BP_OK;
+}
+
+int bp_streams_update_layout(bp_handle h, int64_t n, bp_stream_update* u, int with_tail, int64_t* note_rows, int64_t* bits_rows) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  if (!note_rows || !bits_rows) {
+    h->err = "bp_streams_update_layout: null note_rows / bits_rows";
+    return BP_ERR_INVALID_ARG;
+  }
+  std::vector<int64_t> tail;
+  return plan_updates(h, "bp_streams_update_layout", n, u, with_tail, tail, note_rows, bits_rows);
+}
+
+int bp_streams_candidates(bp_handle h, int64_t n, bp_stream_update* u, int with_tail, float* note_out, int8_t* bend_out,
+                          uint8_t* bits_out, int64_t note_capacity_rows, int64_t bits_capacity_rows) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_streams_candidates";
+  auto invalid = [&](const std::string& why) {
+    h->err = std::string(what) + ": " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  std::vector<int64_t> tail;
+  int64_t note_rows = 0, bits_rows = 0;
+  if (int rc = plan_updates(h, what, n, u, with_tail, tail, &note_rows, &bits_rows)) return rc;
+  if (note_capacity_rows < note_rows || bits_capacity_rows < bits_rows)
+    return invalid("note_capacity_rows " + std::to_string(note_capacity_rows) + " / bits_capacity_rows " +
+                   std::to_string(bits_capacity_rows) + " are too small for the " + std::to_string(note_rows) + " / " +
+                   std::to_string(bits_rows) + " rows of this update (bp_streams_update_layout)");
+  if ((note_rows > 0 && !note_out) || (bits_rows > 0 && !bits_out)) return invalid("null output pointer");
+  for (int64_t i = 0; i < n; ++i) u[i].status = u[i].stream->prm.onset_threshold > 0.0 ? 0 : 1;
+  if (bits_rows == 0) return BP_OK;  // no stream has a row yet
+  BP_HIP(hipSetDevice(h->device));
+  std::vector<WindowSeg> segs;  // both read by asynchronous copies: alive until the wait
+  std::vector<uint8_t> tab;
+  if (int rc = finish(h, queue_updates(h, n, u, tail, note_rows, bits_rows, note_out, bend_out, bits_out, segs, tab))) {
+    for (int64_t i = 0; i < n; ++i) u[i].stream->broken = true;
+    return rc;
+  }
+  for (int64_t i = 0; i < n; ++i)
+    if (h->up_stats_host[i * kStatsFloats + 1]) u[i].status = 1;  // a NaN in the slice: the host decodes the maps themselves
   return BP_OK;
 }
 

@@ -428,6 +428,13 @@ class Model:
 
         return peek_streams(self, streams)
 
+    def transcripts(self, transcribers, workers=None):
+        """`transcript()` of many live `StreamingTranscriber`s of this model behind one device step
+        (`streaming.transcripts`, `bp_streams_candidates`): `(midi_data, note_events)` per transcriber, in order."""
+        from .streaming import transcripts
+
+        return transcripts(self, transcribers, workers)
+
     # -- introspection ----------------------------------------------------------------------------
     def info(self) -> Dict[str, Any]:
         inf = _native.bp_info()

@@ -9,6 +9,9 @@ Live use: `Stream.peek()` returns the rows a finish would emit now and commits n
 `predict_pcm_raw` of the audio so far at any moment; `StreamingTranscriber(live=True).transcript()` decodes the notes of the
 audio so far from what the device keeps (`bp_stream_keep`, `bp_stream_candidates`; include/basic_pitch_amd_live.h).
 
+Many live sessions: `transcripts(model, transcribers)` is `transcript()` of every one of them behind ONE device step
+(`bp_streams_candidates`; include/basic_pitch_amd_update.h), the host half of the decoding on a thread pool.
+
 Endless use: `StreamingTranscriber(live=True, horizon_seconds=H)` keeps the last H seconds in a ring on the device
 (`bp_stream_keep_rolling`, `bp_stream_candidates_rolling`; include/basic_pitch_amd_rolling.h) and `transcript()` is the exact
 decode of those rows in absolute stream time: device memory, host memory and the work of an update do not grow with the session.
@@ -53,6 +56,11 @@ ROLLING_PROTOTYPES = {
     "bp_stream_rolling_maps": (_int, [_vp, _int, _vp, _vp, _vp, _i64, _pi64, _pi64]),
     "bp_notes_decode_candidates_at": (_int, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _i64, _pi64, _pi64]),
 }
+# the same for include/basic_pitch_amd_update.h (tests/test_streams_update_cpu.py compares)
+UPDATE_PROTOTYPES = {
+    "bp_streams_update_layout": (_int, [_vp, _i64, _vp, _int, _pi64, _pi64]),
+    "bp_streams_candidates": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _i64, _i64]),
+}
 TAIL_ROWS = 2 * 142  # the rows a peek can have: what a rolling stream's ring holds beyond its horizon
 
 # the numpy type a chunk of each format is made of (BP_PCM_S24: packed bytes)
@@ -61,8 +69,8 @@ _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Declare the streaming family's prototypes (the three headers) on a loaded library."""
-    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES}.items():
+    """Declare the streaming family's prototypes (the four headers) on a loaded library."""
+    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES, **UPDATE_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
@@ -268,6 +276,85 @@ def push_streams(model: "_inf.Model", streams: Sequence[Stream], chunks: Sequenc
     return [s._taken(o, int(r)) for s, o, r in zip(streams, outs, rows)]
 
 
+def update_table(streams: Sequence[Stream], held_rows: Sequence[int]):
+    """The `bp_stream_update` array of `bp_streams_update_layout` / `bp_streams_candidates` for these streams."""
+    tab = (_native.bp_stream_update * max(1, len(streams)))()
+    for i, (s, held) in enumerate(zip(streams, held_rows)):
+        tab[i].stream, tab[i].held_rows = s._s.value, int(held)
+    return tab
+
+
+def streams_candidates(model: "_inf.Model", streams: Sequence[Stream], held_rows: Sequence[int], with_tail: bool = True,
+                       bends: bool = True):
+    """One `bp_streams_candidates` call: (the `bp_stream_update` array, note (rows, 88) float32, bend (rows, 88) int8 or None,
+    bits (rows, 12) uint8), packed: stream i's note / bend rows [new_row, n_rows) at `note_offset`, its bitmap rows
+    [first_row, n_rows) at `bits_offset`."""
+    lib = bind(model._lib)
+    n = len(streams)
+    tab = update_table(streams, held_rows)
+    note_rows, bits_rows = C.c_int64(0), C.c_int64(0)
+    rc = lib.bp_streams_update_layout(model._handle, n, C.addressof(tab), int(bool(with_tail)), C.byref(note_rows), C.byref(bits_rows))
+    _native.check(lib, model._handle, rc, "bp_streams_update_layout")
+    note = np.empty((note_rows.value, 88), np.float32)
+    bend = np.empty((note_rows.value, 88), np.int8) if bends else None
+    bits = np.empty((bits_rows.value, 12), np.uint8)
+    rc = lib.bp_streams_candidates(model._handle, n, C.addressof(tab), int(bool(with_tail)), note.ctypes.data,
+                                   bend.ctypes.data if bends else None, bits.ctypes.data, note.shape[0], bits.shape[0])
+    _native.check(lib, model._handle, rc, "bp_streams_candidates")
+    return tab, note, bend, bits
+
+
+def scatter_rows(ring: np.ndarray, packed: np.ndarray, r0: int, r1: int) -> None:
+    """Packed rows (row 0 is absolute row r0) into a host ring, absolute row r at index r % len(ring): one slice assignment,
+    two where the rows wrap.  An array that never wraps is a ring longer than r1."""
+    R, at = ring.shape[0], 0
+    while r0 + at < r1:
+        lo = (r0 + at) % R
+        k = min(r1 - r0 - at, R - lo)
+        ring[lo : lo + k] = packed[at : at + k]
+        at += k
+
+
+def transcripts(model: "_inf.Model", transcribers: Sequence["StreamingTranscriber"], workers: Optional[int] = None) -> List[Any]:
+    """`t.transcript()` for every live transcriber of `model`, of either mode, in order — behind one native call
+    (`bp_streams_candidates`): the tails' windows of all sessions run in shared batches, each session's packed rows are
+    scattered into its own host arrays, and the sequential half of the decoding runs per session on a pool of `workers`
+    threads (default 8; the native decoder releases the GIL).  A transcriber whose onset threshold is <= 0 or whose slice holds
+    a NaN takes the fallback `transcript()` takes."""
+    from concurrent.futures import ThreadPoolExecutor
+
+    ts = list(transcribers)
+    for t in ts:
+        if not t.live:
+            raise ValueError("transcripts() needs StreamingTranscriber(live=True)")
+    if not ts:
+        return []
+    results: List[Any] = [None] * len(ts)
+    ids = [i for i, t in enumerate(ts) if t._prm.onset_threshold > 0]  # the others: status 1 whatever the maps hold
+    if ids:
+        tab, note, bend, bits = streams_candidates(model, [ts[i].stream for i in ids], [ts[i]._held for i in ids])
+    with ThreadPoolExecutor(max_workers=max(1, int(workers or 8))) as pool:
+        pending = []
+        for k, i in enumerate(ids):
+            t, u = ts[i], tab[k]
+            a, T, n0 = int(u.first_row), int(u.n_rows), int(u.new_row)
+            if t.horizon_rows is None:
+                t._room(T)
+            scatter_rows(t._note, note[u.note_offset : u.note_offset + T - n0], n0, T)
+            scatter_rows(t._bend, bend[u.note_offset : u.note_offset + T - n0], n0, T)
+            scatter_rows(t._bits, bits[u.bits_offset : u.bits_offset + T - a], a, T)
+            t._held = t.stream.rows  # rows at or after it were a tail's: sent again next time
+            if u.status == 0:
+                pending.append((i, pool.submit(t._decoded, a, T)))
+        decoding = {i for i, _ in pending}
+        for i, t in enumerate(ts):  # the fallbacks use the handle: on this thread, after the native call
+            if i not in decoding:
+                results[i] = t._host_decoded()
+        for i, fut in pending:
+            results[i] = fut.result()
+    return results
+
+
 class StreamingTranscriber:
     """`predict()` for audio that arrives in chunks: `push(chunk)` feeds a stream and keeps the emitted rows on the host,
     `finish()` returns `(model_output, midi_data, note_events)` exactly as `predict()` does for the same audio.
@@ -348,19 +435,28 @@ class StreamingTranscriber:
         tail = 0 if not s._s.value else s.rows_bound(0)
         return float(_notes.frames_to_time_at(np.array([horizon_first_row(s.rows + tail, self.horizon_rows)]))[0])
 
-    def _rolling_transcript(self):
-        s = self.stream
+    def _decoded(self, a: int, T: int):
+        """Status 0: the host half of the decoding on rows [a, T) of the host arrays (rings, for a rolling horizon)."""
         multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
-        status = 1  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
-        if self._prm.onset_threshold > 0:
-            a, T, status = s.candidates_rolling(self._note, self._bits, self._bend, self._held)
-            self._held = s.rows  # rows at or after it were a tail's: sent again next time
-        if status == 0:
+        if self.horizon_rows is None:
+            events = _notes.decode_candidates(self._note[:T], self._bits[:T], self._bend[:T], self._prm)
+        else:
             events = _notes.decode_candidates(_unwrapped(self._note, a, T), _unwrapped(self._bits, a, T),
                                               _unwrapped(self._bend, a, T), self._prm, first_frame=a)
-            return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
-        # a NaN in the slice or an onset threshold <= 0: the host decodes the kept maps of the slice themselves, numpy's rules
-        a, maps = s.rolling_maps()
+        return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+
+    def _host_decoded(self):
+        """Status 1 — a NaN in the maps or an onset threshold <= 0: numpy's rules, the host decodes the maps themselves."""
+        s = self.stream
+        multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
+        if self.horizon_rows is None:
+            # (After a NaN the tail's windows run a second time here: the update wrote them behind the kept rows,
+            # frequency-constrained, and the decoder needs the rows as the caller gets them.  The price of a broken input, not
+            # of an update.)
+            parts = self._rows + [s.peek()]
+            model_output = {k: np.ascontiguousarray(np.concatenate([r[k] for r in parts])) for k, _ in _inf._MAPS}
+            return _inf._output_to_notes(model_output, *self._decoding)
+        a, maps = s.rolling_maps()  # the kept maps of the slice
         p = self._prm
         ev, bends, n = _notes._decode(maps["note"], maps["onset"], maps["contour"], self._decoding[0], self._decoding[1],
                                       p.min_note_len, True, self._decoding[4], self._decoding[3], bool(p.melodia_trick),
@@ -371,6 +467,14 @@ class StreamingTranscriber:
         events = [(float(t[0]), float(t[1]), int(e.pitch_midi), np.float32(e.amplitude), flat[e.bend_offset : e.bend_offset + e.n_bends])
                   for e, t in zip(ev[:n], times)]
         return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+
+    def _rolling_transcript(self):
+        s = self.stream
+        status = 1  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
+        if self._prm.onset_threshold > 0:
+            a, T, status = s.candidates_rolling(self._note, self._bits, self._bend, self._held)
+            self._held = s.rows  # rows at or after it were a tail's: sent again next time
+        return self._decoded(a, T) if status == 0 else self._host_decoded()
 
     def _room(self, rows: int) -> None:
         """Host note / bend / bitmap arrays of at least `rows` rows, the held final rows carried over."""
@@ -390,21 +494,12 @@ class StreamingTranscriber:
         if self.horizon_rows is not None:
             return self._rolling_transcript()
         s = self.stream
-        multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
-        status = 1  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
+        status, T = 1, 0  # an onset threshold <= 0 is status 1 whatever the maps hold: no device work for it
         if self._prm.onset_threshold > 0:
             self._room(s.rows + s.rows_bound(0))
             T, status = s.candidates(self._note, self._bits, self._bend, self._held)
             self._held = s.rows  # rows at or after it were a tail's: sent again next time
-        if status == 0:
-            events = _notes.decode_candidates(self._note[:T], self._bits[:T], self._bend[:T], self._prm)
-            return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
-        # a NaN in the maps or an onset threshold <= 0: numpy's rules, the host decodes the maps themselves.  (After a NaN the
-        # tail's windows run a second time here: the update wrote them behind the kept rows, frequency-constrained, and the
-        # decoder needs the rows as the caller gets them.  The price of a broken input, not of an update.)
-        parts = self._rows + [s.peek()]
-        model_output = {k: np.ascontiguousarray(np.concatenate([r[k] for r in parts])) for k, _ in _inf._MAPS}
-        return _inf._output_to_notes(model_output, *self._decoding)
+        return self._decoded(0, T) if status == 0 else self._host_decoded()
 
     def finish(self):
         if self.horizon_rows is not None:
