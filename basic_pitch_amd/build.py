@@ -27,7 +27,8 @@ SOURCES = [
     "weight_pack.hip",
     "cqt_pyramid.hip",
     "cqt_filterbank.hip",
-    "cqt_planes.hip",
+    "cqt_planes_pyramid.hip",
+    "cqt_planes_filterbank.hip",
     "conv_contour1.hip",
     "conv_contour_rim.hip",
     "conv_contour_rim_march.hip",
@@ -55,7 +56,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h", "march_common.h", "cqt_planes.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

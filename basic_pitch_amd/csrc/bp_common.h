@@ -91,6 +91,8 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 using f32x16 = __attribute__((ext_vector_type(16))) float;
 using f32x2 = __attribute__((ext_vector_type(2))) float;
 using f16x2 = __attribute__((ext_vector_type(2))) _Float16;
+using f16x8 = __attribute__((ext_vector_type(8))) _Float16;  // one operand fragment of a 16x16x32 / 32x32x16 f16 matrix instruction
+using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 // Whole-wave min / max by DPP (row scans + row_bcast15 / row_bcast31, GFX9 controls): the result is in lane 63.
 // 6 VALU operations instead of 6 x (address + ds_bpermute + op).

@@ -37,7 +37,7 @@ struct bp_context {
   using Buffer = bp::DeviceBuffer<T>;
   // device constants
   Table d_lowpass, d_sqrt_len, d_fb_bfrag;
-  Table d_pl_bin_k;  // cqt_planes.hip filterbank: per-bin eps / s^2, s = sqrt(len) 2^-12
+  Table d_pl_bin_k;  // cqt_planes_filterbank.hip: per-bin eps / s^2, s = sqrt(len) 2^-12
   // fused branches (conv_branch.hip): f16 hi/lo A fragments + {bias1[32], extra[9], bias2}
   Table d_note_wfrag, d_note_w16, d_note_wf32, d_onset_wfrag, d_onset_wf32, d_onset_w16;
   Buffer<uint32_t> zp;  // [cap][kZRowsP][kZRow] pre-split z, zero padded (bp_common.h)
@@ -45,7 +45,7 @@ struct bp_context {
   Table d_d1_wfold, d_d1_wmarch, d_d1_wrim, d_d1_wrimm, d_d1_bias, d_d2_w, d_d2_wproj;
   int resample_mode = 0;  // BP_RESAMPLE=plain|tiled: 1 | 2 (A/B runs of the resampling kernels)
   Buffer<float> c1s;  // [cap][172][kC1Row][8] relu(conv1); pad bins zeroed once at allocation
-  // cqt_planes.hip: decimator / filterbank fragments (f16 hi / lo), the planes of a chunk [cap][2][stride] f16
+  // cqt_planes.h: decimator / filterbank fragments (f16 hi / lo), the planes of a chunk [cap][2][stride] f16
   Table d_pl_tfrag, d_pl_bfrag;
   Buffer<uint16_t> planes;
   Table d_c1_bfrag, d_c1_bias, d_o1_bfrag, d_o1_bias;

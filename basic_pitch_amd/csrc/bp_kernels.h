@@ -28,7 +28,8 @@ void launch_filterbank(const float* audio, const float* pyr, const float* bfrag,
                        hipStream_t s);
 void launch_mm_reduce(const float* scratch, int* mm, int n_windows, int n_partials, hipStream_t stream);
 
-// cqt_planes.hip: the pyramid as pre-split, reflect-padded f16 planes; operands straight from HBM / L2
+// The pyramid as pre-split, reflect-padded f16 planes; operands straight from HBM / L2 (cqt_planes.h).
+// cqt_planes_pyramid.hip: the planes of every level from the fp32 audio
 int64_t planes_elements_per_window(bool ext);
 void launch_planes_split(const float* src, int64_t src_stride, int level, uint16_t* pl, int n_windows, bool ext,
                          hipStream_t stream);
@@ -38,6 +39,7 @@ void launch_planes_edge_rows(const float* audio, int64_t audio_stride, uint16_t*
                              hipStream_t stream);
 void launch_pyramid_planes(const float* audio, int64_t audio_stride, uint16_t* pl, const void* tfrag, int n_windows,
                            int n_cu, bool ext, hipStream_t stream);
+// cqt_planes_filterbank.hip: the filterbank over the planes, normalise / BatchNorm / split fused for whole windows
 int filterbank_planes_partials(bool ext);
 bool launch_filterbank_planes(const uint16_t* pl, const float* audio, int64_t audio_stride, const void* bfrag,
                               const float* bin_consts, float* lp, float* scratch,

@@ -38,8 +38,6 @@
 
 namespace bp {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 __device__ __forceinline__ void split_f16(float v, _Float16& hi, _Float16& lo) {
   hi = (_Float16)v;
   lo = (_Float16)((v - (float)hi) * kLoScale);

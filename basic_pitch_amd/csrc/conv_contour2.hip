@@ -29,7 +29,6 @@ namespace bp {
 //     the zero padding of "same" is c1's own pad columns, which sit between the windows in the flat index — no masks; rows
 //     outside the window contribute P = 0.
 // Roofline: HBM (1.48 MB in + 7 % strip overlap + 9 % slab halo, 182 KB out per window); matrix 4 instructions per 64 pixels.
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 constexpr int kP2Group = 16;                         // windows per flat index group
 constexpr int kP2Cols = kP2Group * kC1Row;           // 4288 flat columns per group
@@ -68,6 +67,7 @@ __global__ __launch_bounds__(256, kP2Occ) void contour_conv2_proj_kernel(Conv2Pr
   // XCD-aware order: workgroups go to the 8 XCDs round-robin (blockIdx % 8) and each XCD has its own L2.  Neighbouring
   // strips read 4 columns in common and neighbouring slabs 4 rows: a contiguous run of work items (whole windows) goes to ONE
   // XCD, so what two items share is fetched from HBM once, by one L2, instead of once per XCD that touches it.
+  // (Not march_common.h's xcd_logical_block(): this grid is not persistent — one item per wave, no CU pair to keep together.)
 #ifdef P2_NO_XCD
   const int lblock = (int)blockIdx.x;
 #else

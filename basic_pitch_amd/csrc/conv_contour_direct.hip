@@ -29,8 +29,6 @@
 
 namespace bp {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int kD1EdgeGroups = 5;                   // groups 0..4 and 61..65 see the crop of the stack (bins < 20, >= 244)
 
 struct Conv1Params {

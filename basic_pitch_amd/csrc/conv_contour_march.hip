@@ -31,10 +31,9 @@
 #include <string.h>
 
 #include "bp_kernels.h"
+#include "march_common.h"
 
 namespace bp {
-
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 constexpr int kCmWaves = 4;          // independent waves per workgroup
 constexpr int kCmStrips = 7;         // 32-bin strips: bins 20 .. 243
@@ -93,17 +92,12 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
   for (int i = lane; i < 2 * kCmRowU; i += 64) img[i] = uint4{0u, 0u, 0u, 0u};
 
   const int total_waves = gridDim.x * kCmWaves;
-  // XCD-aware task order: workgroups go to the 8 XCDs round-robin (blockIdx % 8) and each XCD has its own L2; consecutive
-  // tasks — the strips and chunks of ONE window, which read overlapping parts of the same zp rows — are given to
-  // workgroups of the same XCD, so a row is fetched from HBM by one L2 instead of by up to eight
-  // (inside each half of the grid: a CU hosts workgroups p and p + gridDim.x / 2, and when the tasks per wave are not a whole
-  // number the first half of the LOGICAL blocks carries the extra task — the pair of a CU must stay (first, second half))
+  // XCD-aware task order (march_common.h): consecutive tasks — the strips and chunks of ONE window — go to one XCD's L2.
   // (Round 5 tried equal shares of the frames per WAVE instead — wave g of 2048 marching the g-th 2048th of all frames,
   // 154 rows each instead of 4 x 45 for half the waves and 3 x 45 for the others: 0.228 ms against 0.2155.  The 3.5 tasks
   // per wave are no imbalance — every SIMD hosts one wave of each kind and the matrix pipe is what they share — while
   // consecutive tasks, the strips of one (window, chunk), read the same zp rows at the same time from the same CU.)
-  const int half_n = (int)gridDim.x / 2, pq = (int)blockIdx.x % (half_n > 0 ? half_n : 1);
-  const int lblock = (gridDim.x % 16 == 0) ? ((int)blockIdx.x / half_n) * half_n + (pq % 8) * (half_n / 8) + pq / 8 : (int)blockIdx.x;
+  const int lblock = BP_XCD_LOGICAL_BLOCK();
 #pragma unroll 1
   for (int task = lblock * kCmWaves + wave; task < p.n_tasks; task += total_waves) {  // wave-uniform; no barriers
     const int b = task / (p.chunks * kCmStrips);
@@ -145,13 +139,6 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
           cl[dw + 1] = l1;
         }
       }
-    };
-    // lane-private writes, cross-lane reads: ordered inside the wave by this fence — placed at the END of a row step, a
-    // whole row of matrix work behind the writes it waits for (right behind them it exposed the LDS write latency per row)
-    auto image_fence = [] {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
     };
 
     // ---- one z row: its fragments feed the three open output frames.  a0 <- dt = 0 (first contribution: starts from
@@ -210,7 +197,7 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
     uint4 ld1 = stage_issue(T0);
     uint4 ld2 = stage_issue(row_c(T0 + 1));
     stage_commit(0, ld0);
-    image_fence();
+    wave_lds_fence();
     ld0 = ld1, ld1 = ld2;
     int buf = 0;
     int zr = T0 - 1;
@@ -222,7 +209,7 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
     ld0 = ld1;                                                          \
     ld1 = stage_issue(row_c(zr + 3));                                   \
     row_step(buf, h##N0, x##N0, h##N1, x##N1, h##N2, x##N2);            \
-    image_fence();                                                      \
+    wave_lds_fence();                                                   \
     finish(zr - 1, h##N2[0], x##N2[0]);                                 \
     buf ^= 1;                                                           \
     ++zr;                                                               \

@@ -32,8 +32,6 @@
 
 namespace bp {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int kRimBlocks = 5;             // M blocks of 32 rows: 20 bins x 8 channels per side
 constexpr int kRimWaves = 4;              // wave w: block w, and k-steps [ks(w), ks(w + 1)) of block 4
 #ifndef BP_RIM_FRAMES

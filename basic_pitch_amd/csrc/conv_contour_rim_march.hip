@@ -29,8 +29,6 @@
 
 namespace bp {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int kRmBlocks = 10;                       // 16-row blocks per side: 20 bins x 8 channels
 constexpr int kRmThreads = 64 * kRmBlocks;          // one wave per block
 constexpr int kRmBins = 144;                        // z bins per frame a side reads (conv_contour_rim.hip RimGeo<144>)

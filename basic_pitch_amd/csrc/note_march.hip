@@ -27,8 +27,6 @@
 
 namespace bp {
 
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-
 constexpr int kNmWaves = 4;    // independent waves per workgroup
 #ifndef BP_NOTE_CHUNKS
 #define BP_NOTE_CHUNKS 4

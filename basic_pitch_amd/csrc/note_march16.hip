@@ -36,11 +36,9 @@
 #include <stdlib.h>
 
 #include "bp_kernels.h"
+#include "march_common.h"
 
 namespace bp {
-
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
-using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 
 constexpr int kN16Waves = 4;    // independent waves per workgroup
 constexpr int kN16Strips = 3;   // 32-pixel strips of a row, 30 inner pixels each
@@ -131,40 +129,19 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
   asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
   pt[npt++] = __builtin_amdgcn_s_memrealtime();
 #endif
-  // work distribution: onset_march16.hip's (XCD-aware order; equal contiguous shares of the frames of all (window, strip)
-  // pairs; at exactly 8 waves per window the three strips of a frame range are marched by neighbouring waves)
+  // work distribution: onset_march16.hip's (march_common.h: XCD-aware order; equal contiguous shares of the frames of all
+  // (window, strip) pairs; at exactly 8 waves per window the three strips of a frame range are marched by neighbouring waves)
   const int total_waves = gridDim.x * kN16Waves;
-  const int half_n = (int)gridDim.x / 2, pq = (int)blockIdx.x % (half_n > 0 ? half_n : 1);
-  const int lblock = (gridDim.x % 16 == 0) ? ((int)blockIdx.x / half_n) * half_n + (pq % 8) * (half_n / 8) + pq / 8 : (int)blockIdx.x;
-  const int gw = lblock * kN16Waves + wave;
-  const bool aligned = total_waves == 8 * (p.n_ws / kN16Strips);  // wave-uniform
+  const int gw = BP_XCD_LOGICAL_BLOCK() * kN16Waves + wave;
   // cuts by COST, not by frames: a share costs its frames + 3 rows of halo per cut end (rows outside the window are skipped) and
   // ~2.3 rows per prologue: 68 + 3 | 65 + 6 | 39 + 3 + (18 + 6) + prologue | (21 + 3) + (39 + 3) + prologue = 71, 71, 68.3, 68.3
   // (profiles/r06_note_phases.md: with the onset march's cuts 64 | 65 | 43 the two-share waves ran 75 rows against 67)
   constexpr int kCut1 = 68, kCut2 = 133, kCut3 = 151;
-  const int b8 = gw >> 3, j8 = gw & 7;
-  const int64_t total = (int64_t)p.n_ws * kFrames;
-  int64_t F0 = total * gw / total_waves;
-  const int64_t F1 = total * (gw + 1) / total_waves;
+  BP_MARCH_SHARES_STATE(gw, total_waves, p.n_ws, kN16Strips);
 #pragma unroll 1
   for (int pi = 0;; ++pi) {  // wave-uniform; no barriers
     int ws, T0, T1;
-    if (aligned) {
-      if (pi >= (j8 < 6 ? 1 : 2)) break;
-      if (j8 < 6) {
-        ws = kN16Strips * b8 + (j8 < 3 ? j8 : j8 - 3), T0 = j8 < 3 ? 0 : kCut1, T1 = j8 < 3 ? kCut1 : kCut2;
-      } else if (pi == 0) {
-        ws = kN16Strips * b8 + (j8 - 6), T0 = j8 == 6 ? kCut2 : kCut3, T1 = kFrames;
-      } else {
-        ws = kN16Strips * b8 + (j8 - 5), T0 = kCut2, T1 = j8 == 6 ? kCut3 : kFrames;
-      }
-    } else {
-      if (F0 >= F1) break;
-      ws = (int)(F0 / kFrames);
-      T0 = (int)(F0 - (int64_t)ws * kFrames);
-      T1 = F1 - (int64_t)ws * kFrames < kFrames ? (int)(F1 - (int64_t)ws * kFrames) : kFrames;
-      F0 = (int64_t)(ws + 1) * kFrames;
-    }
+    BP_MARCH_SHARES_TAKE(kN16Strips, kCut1, kCut2, kCut3, break)
     const int b = ws / kN16Strips, strip = ws - b * kN16Strips;
 
     // this lane's two pixels of the strip (tile nt: strip pixel 16 nt + n)
@@ -216,11 +193,6 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
       ring2[(slot * kN16Row + st_slot) * 2 + st_half] = h;
       ring2[(slot * kN16Row + kN16Lo + st_slot) * 2 + st_half] = l;
     };
-    auto ring_fence = [] {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
 
     // ---- the march: conv1 rows r = T0 - 3 .. T1 + 2; step i = r - r_first keeps image row r - 3 + j in slot (i + j) & 7
     const int r_first = T0 - 3, r_last = T1 + 2;
@@ -232,7 +204,7 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
       pend = stage_issue(r_first + 4);
 #pragma unroll
       for (int j = 0; j < 7; ++j) stage_commit(j, v[j], r_first - 3 + j);
-      ring_fence();
+      wave_lds_fence();
     }
     float V[2][8];  // V[nt][t & 7 relative]: the open output rows of this lane's (pixel, dw)
 #pragma unroll
@@ -287,7 +259,7 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
           for (int mb = 0; mb < 2; ++mb)
             acc[nt][mb] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a1h[s][mb]), bl[nt], acc[nt][mb], 0, 0, 0);
       };
-      ring_fence();  // k-step 1 touches the row committed in the middle of the last step
+      wave_lds_fence();  // k-step 1 touches the row committed in the middle of the last step
       if (!live) {  // at most six steps per share (the window's first and last rows)
         stage_commit((ph + 7) & 7, pend, r + 4);
         pend = stage_issue(r + 5);
@@ -415,7 +387,7 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
       step(N16Phase<7>{}, r);
       if (++r > r_last) break;
     }
-    ring_fence();  // the next piece's prologue overwrites the ring
+    wave_lds_fence();  // the next piece's prologue overwrites the ring
 #ifdef N16_PROF
     if (npt < 7) pt[npt++] = __builtin_amdgcn_s_memrealtime();
 #endif
@@ -434,9 +406,7 @@ void launch_note_march16(const float* contour, const void* wfrag, const float* w
   Note16Params p{static_cast<const uint4*>(wfrag), wf32, contour, note, n_windows * kN16Strips};
   if (p.n_ws <= 0) return;
   constexpr int kMinFrames = 12;
-  const int64_t waves = ((int64_t)p.n_ws * kFrames + kMinFrames - 1) / kMinFrames;
-  int grid = (int)((waves + kN16Waves - 1) / kN16Waves);
-  if (grid > kN16Occ * n_cu) grid = kN16Occ * n_cu;
+  const int grid = march_grid(p.n_ws, kMinFrames, kN16Waves, kN16Occ, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(note_march16_kernel<true>, dim3(grid), dim3(64 * kN16Waves), 0, stream, p);
   else

@@ -26,10 +26,9 @@
 #include <stdlib.h>
 
 #include "bp_kernels.h"
+#include "march_common.h"
 
 namespace bp {
-
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 constexpr int kOmWaves = 4;  // independent waves per workgroup
 #ifndef BP_ONSET_MARCH_CHUNKS
@@ -152,10 +151,7 @@ __global__ __launch_bounds__(64 * kOmWaves, 2) void onset_march_kernel(OnsetMarc
         ring[(slot * 2 + 0) * kOmSlots + 64 + lane] = vh;
         ring[(slot * 2 + 1) * kOmSlots + 64 + lane] = vl;
       }
-      // the ring is written lane-private and read across lanes: order the wave's LDS writes before the reads that follow
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+      wave_lds_fence();  // right behind every commit: this form pays the write latency once per row
     };
     auto note_at = [&](int row) {  // unconditional load from a clamped address, masked where it is used
       const int rc = row < 0 ? 0 : (row > kFrames - 1 ? kFrames - 1 : row);

@@ -32,10 +32,9 @@
 #include <stdlib.h>
 
 #include "bp_kernels.h"
+#include "march_common.h"
 
 namespace bp {
-
-using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
 constexpr int kO16Waves = 4;  // independent waves per workgroup
 constexpr int kO16Strips = 3;                  // 32-pixel strips of a row, 30 inner pixels each
@@ -117,46 +116,18 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
   const int at56 = 3 * n + 2;
 
   const int total_waves = gridDim.x * kO16Waves;
-  // XCD-aware order: workgroups go to the 8 XCDs round-robin (blockIdx % 8) and each XCD has its own L2; consecutive
-  // pieces of work — the strips of ONE window, which read overlapping parts of the same zp rows — are given to
-  // workgroups of the same XCD, so a row is fetched from HBM by one L2 instead of by up to eight
-  const int half_n = (int)gridDim.x / 2, pq = (int)blockIdx.x % (half_n > 0 ? half_n : 1);
-  const int lblock = (gridDim.x % 16 == 0) ? ((int)blockIdx.x / half_n) * half_n + (pq % 8) * (half_n / 8) + pq / 8 : (int)blockIdx.x;
-  // Work = the frames of all (window, strip) pairs; every wave takes an equal share of them as at most two marches
-  // (round 4: three tasks of an eighth of a window-strip each — three prologues and 3 x 2 warm-up rows per wave).
-  //  * exactly 8 waves per window (full batches: 2048 waves, 256 windows; 3 strips x 172 frames = 8 x 64.5): waves 0-2
-  //    of a window march frames 0..63 of strips 0, 1, 2, waves 3-5 frames 64..128, wave 6 the rest of strip 0 and half the
-  //    rest of strip 1, wave 7 the other half and the rest of strip 2 — 1.25 pieces per wave, and the three strips of a
-  //    frame range, which gather from the SAME zp rows, are marched at the same time by neighbouring waves of one
-  //    workgroup (laid end to end instead, the strips of a window were marched at different times: 183 MB of HBM reads
-  //    per launch where this order needs 121 — the time is the same);
-  //  * any other wave count: the pairs laid end to end, wave g of G takes the g-th G-th.
-  const int gw = lblock * kO16Waves + wave;
-  const bool aligned = total_waves == 8 * (p.n_ws / kO16Strips);  // wave-uniform
-  constexpr int kCut1 = 64, kCut2 = 129, kCut3 = 150;             // 64 | 65 | 43 = 21 + 22
-  const int b8 = gw >> 3, j8 = gw & 7;
-  const int64_t total = (int64_t)p.n_ws * kFrames;
-  int64_t F0 = total * gw / total_waves;  // the end-to-end order's share (a share may span several pairs)
-  const int64_t F1 = total * (gw + 1) / total_waves;
+  // Work = the frames of all (window, strip) pairs, in the XCD-aware order of workgroups; every wave takes an equal share
+  // of them as at most two marches (march_common.h: BP_MARCH_SHARES_TAKE.  Round 4: three tasks of an eighth of a window-strip each
+  // — three prologues and 3 x 2 warm-up rows per wave.  With the pairs laid end to end at full batches too, the strips of
+  // a window were marched at different times: 183 MB of HBM reads per launch where the aligned cut needs 121 — the time
+  // is the same.)
+  const int gw = BP_XCD_LOGICAL_BLOCK() * kO16Waves + wave;
+  constexpr int kCut1 = 64, kCut2 = 129, kCut3 = 150;  // 64 | 65 | 43 = 21 + 22
+  BP_MARCH_SHARES_STATE(gw, total_waves, p.n_ws, kO16Strips);
 #pragma unroll 1
   for (int pi = 0;; ++pi) {  // wave-uniform; no barriers
     int ws, T0, T1;
-    if (aligned) {
-      if (pi >= (j8 < 6 ? 1 : 2)) break;
-      if (j8 < 6) {
-        ws = kO16Strips * b8 + (j8 < 3 ? j8 : j8 - 3), T0 = j8 < 3 ? 0 : kCut1, T1 = j8 < 3 ? kCut1 : kCut2;
-      } else if (pi == 0) {
-        ws = kO16Strips * b8 + (j8 - 6), T0 = j8 == 6 ? kCut2 : kCut3, T1 = kFrames;
-      } else {
-        ws = kO16Strips * b8 + (j8 - 5), T0 = kCut2, T1 = j8 == 6 ? kCut3 : kFrames;
-      }
-    } else {
-      if (F0 >= F1) break;
-      ws = (int)(F0 / kFrames);
-      T0 = (int)(F0 - (int64_t)ws * kFrames);
-      T1 = F1 - (int64_t)ws * kFrames < kFrames ? (int)(F1 - (int64_t)ws * kFrames) : kFrames;
-      F0 = (int64_t)(ws + 1) * kFrames;
-    }
+    BP_MARCH_SHARES_TAKE(kO16Strips, kCut1, kCut2, kCut3, break)
     const int b = ws / kO16Strips, strip = ws - b * kO16Strips;
 
     // this lane's two pixels of the strip (tile nt: strip pixel 16 nt + n), and the stack bin of image slot 0
@@ -216,15 +187,6 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
         ring[slot * kO16Row + kO16Lo + 64 + lane] = vl;
       }
     };
-    // The ring is written lane-private and read across lanes: a wavefront fence orders the two.  Not right behind the commit
-    // (there it exposes the LDS write latency once per row): the row committed at the end of step r is image row (r + 1) + 2
-    // of the next step and first read by that step's k-step 4 — the fence sits in front of that read, three k-steps of matrix
-    // work behind the writes.
-    auto ring_fence = [] {
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    };
     auto note_at = [&](int row, int nt) {  // unconditional load from a clamped address, masked where it is used
       const int rc = row < 0 ? 0 : (row > kFrames - 1 ? kFrames - 1 : row);
       return nwin[rc * kFreqN + wc[nt]];
@@ -262,7 +224,7 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
       __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
       for (int s = 0; s < kO16KS; ++s) {
-        if (s + kO16Pf == 4) ring_fence();  // the next read touches the row committed at the end of the last step
+        if (s + kO16Pf == 4) wave_lds_fence();  // the next read touches the row committed at the end of the last step
         if (s + kO16Pf < kO16KS) issue(s + kO16Pf);
         __builtin_amdgcn_sched_barrier(0);
         // three passes over the four (tile, block) accumulator pairs: dependent instructions sit 4 and 8 apart
@@ -342,7 +304,7 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
       stage_issue(r_first + 2, ub);
       stage_commit(3, ua);
       stage_commit(4, ub);
-      ring_fence();
+      wave_lds_fence();
     }
     float note_nx[2] = {note_at(r_first, 0), note_at(r_first, 1)};
     float C[2] = {0.0f, 0.0f};  // the vertical sum in flight: group 0: q0(r), group 1: q0(r - 1) + q1(r)
@@ -385,9 +347,7 @@ void launch_onset_march16(const uint32_t* zp, const float* note, const void* wfr
   Onset16Params p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows * kO16Strips};
   if (p.n_ws <= 0) return;
   constexpr int kMinFrames = 6;
-  const int64_t waves = ((int64_t)p.n_ws * kFrames + kMinFrames - 1) / kMinFrames;
-  int grid = (int)((waves + kO16Waves - 1) / kO16Waves);
-  if (grid > 2 * n_cu) grid = 2 * n_cu;
+  const int grid = march_grid(p.n_ws, kMinFrames, kO16Waves, 2, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(onset_march16_kernel<true>, dim3(grid), dim3(64 * kO16Waves), 0, stream, p);
   else

@@ -443,7 +443,7 @@ bool pack_note16(const Tensor* w1, const Tensor* w2, std::vector<uint16_t>& out)
   return ok;
 }
 
-// cqt_planes.hip decimator (transposed: the filter is the A operand): T[u][i] = h[i - 2u - 1] — the input window starts one
+// cqt_planes_pyramid.hip decimator (transposed: the filter is the A operand): T[u][i] = h[i - 2u - 1] — the input window starts one
 // sample before the reference's (an 8-sample aligned element of the padded plane) — as [hi: 9 steps][lo: 9 steps] x 64
 // lanes x 8 f16; lane (u = lane & 15, kg = lane >> 4), element e: i = 32 s + 8 kg + e.
 void pack_decimator_f16(const Tensor* lowp, std::vector<uint16_t>& out, int shift = 1) {
@@ -460,7 +460,7 @@ void pack_decimator_f16(const Tensor* lowp, std::vector<uint16_t>& out, int shif
       }
 }
 
-// cqt_planes.hip filterbank: [29 step-fragments][hi|lo][64 lanes][8] f16.  Column groups of 16: 0 = re of filters 0..15,
+// cqt_planes_filterbank.hip: [29 step-fragments][hi|lo][64 lanes][8] f16.  Column groups of 16: 0 = re of filters 0..15,
 // 1 = im 0..15 (7 steps from tap 16), 2 = re 16..31, 3 = im 16..31, 4 = {re 32..35, im 32..35, 8 zero columns} (5 steps
 // from tap 48); lane (n = lane & 15, kg), element e: tap = 16 + 32 s + 8 kg + e of k-step s.
 void pack_filterbank_planes(const Tensor* re, const Tensor* im, std::vector<uint16_t>& out) {

@@ -37,7 +37,7 @@ FB_MAG_REL = 1e-5
 FB_MAG_FLOOR = 1e-9
 # Log-power, on every bin: |lp - fp64| <= FB_LP_FLOOR_DB + the magnitude bound carried into dB at that bin,
 # (10 / ln 10) (2 mag64 dmag + dmag^2) / (mag64^2 + eps).  FB_LP_FLOOR_DB is the rounding of the log itself near the
-# -100 dB floor: the device's log2 instruction and the per-bin constants (cqt_planes.hip) add a few ulp of 100 dB
+# -100 dB floor: the device's log2 instruction and the per-bin constants (cqt_planes_filterbank.hip) add a few ulp of 100 dB
 # (ulp 7.6e-6 dB) beside the fp32 oracle's correctly rounded log.
 FB_LP_FLOOR_DB = 4e-5  # measured on MI355X: the worst bin uses 0.28 of its bound (noise at -90 dBFS)
 LP_EPS = 1e-10

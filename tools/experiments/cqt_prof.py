@@ -1,7 +1,10 @@
 """Phase stamps of the per-window CQT kernels (tools only).  Build the instrumented library first:
 
-    bash tools/build_variant.sh prof cqt_planes.hip -DPL_PROF
+    bash tools/build_all_variant.sh prof -DPL_PROF
     BASIC_PITCH_AMD_LIB=$PWD/basic_pitch_amd/lib/var_prof.so python tools/experiments/cqt_prof.py
+
+(-DPL_PROF matters in cqt_planes_pyramid.hip and cqt_planes_filterbank.hip: each stamps a table of its own, and
+bp_debug_pl_prof returns the pyramid's followed by the filterbank's.)
 
 Prints, for two workgroups (blocks 0 and 131) and every wave, the s_memtime stamps relative to the wave's kernel entry in
 microseconds (scaled with the 100 MHz s_memrealtime pair taken at entry and exit of the same wave)."""

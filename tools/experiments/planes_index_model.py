@@ -1,4 +1,4 @@
-# Index model of csrc/cqt_planes.hip in numpy (float64, no operand split): the plane geometry, the transposed decimator
+# Index model of csrc/cqt_planes.h, cqt_planes_pyramid.hip and cqt_planes_filterbank.hip in numpy (float64, no operand split): the plane geometry, the transposed decimator
 # tile with its edge masks and reflect-pad writes, and the filterbank's fragment addressing, checked against the oracle's
 # pyramid / CQT on one window.  CPU only:  python tools/experiments/planes_index_model.py
 import os, sys
