@@ -254,6 +254,12 @@ CLIPS_SYMBOLS = [
     "bp_clips_row_offsets",
     "bp_infer_clips_candidates",
 ]
+# every symbol include/basic_pitch_amd_events.h declares (bound in basic_pitch_amd/events.py)
+EVENTS_SYMBOLS = [
+    "bp_events_capacity",
+    "bp_infer_clips_events",
+    "bp_note_events_from_maps",
+]
 
 _lib: Optional[C.CDLL] = None
 

@@ -19,6 +19,7 @@ LIVE_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_live.h")
 ROLLING_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_rolling.h")
 CLIPS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_clips.h")
 UPDATE_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_update.h")
+EVENTS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_events.h")
 
 SOURCES = [
     "bp_api.hip",
@@ -40,6 +41,7 @@ SOURCES = [
     "note_march16.hip",
     "onset_march16.hip",
     "note_device.hip",
+    "note_track.hip",
     "audio_ingest.hip",
     "flac_device.hip",
     "note_decode.cpp",
@@ -56,7 +58,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h", "march_common.h", "cqt_planes.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h", "march_common.h", "cqt_planes.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

@@ -115,9 +115,12 @@ def infer_clips_candidates(model: Any, arrays: Sequence[np.ndarray], sample_rate
 def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], onset_threshold: float,
                      frame_threshold: float, minimum_note_length: float, minimum_frequency: Optional[float],
                      maximum_frequency: Optional[float], multiple_pitch_bends: bool, melodia_trick: bool, midi_tempo: float,
-                     threads: int = 8) -> List[Tuple[Any, List["_notes.NoteEvent"]]]:
+                     threads: int = 8, decode: str = "host") -> List[Tuple[Any, List["_notes.NoteEvent"]]]:
     """`Model.transcribe_clips`: clips grouped by rate, one native call per group, the sequential half of note decoding per clip
-    on a thread pool (the native decoder releases the GIL), results in input order."""
+    on a thread pool (the native decoder releases the GIL), results in input order.  decode="device": that half runs on the
+    device too (`bp_infer_clips_events`, basic_pitch_amd/events.py) and only events and bends come home."""
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
     from . import inference as _inf
 
     arrays = [as_clip(c, i) for i, c in enumerate(clips)]
@@ -140,6 +143,20 @@ def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, 
     def decoded(note, bits, bend):
         events = _notes.decode_candidates(note, bits, bend, prm)
         return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+
+    if decode == "device":
+        from . import events as _events
+
+        for rate in dict.fromkeys(rates):  # the rates in order of first appearance
+            ids = [i for i, r in enumerate(rates) if r == rate]
+            events, bends, ev_offs, status = _events.infer_clips_events(model, [arrays[i] for i in ids], rate, prm)
+            for k, i in enumerate(ids):
+                if status[k]:  # 1 as below; 2: the clip passed its region's capacity
+                    results[i] = host_decoded(i)
+                    continue
+                ev = _events.clip_events(events, bends, ev_offs, k, True)
+                results[i] = (_notes.note_events_to_midi(ev, multiple_pitch_bends, midi_tempo), ev)
+        return results
 
     with ThreadPoolExecutor(max_workers=max(1, int(threads))) as pool:
         pending = []

@@ -79,6 +79,15 @@ struct bp_context {
   Table clip_stats;
   bp::PinnedBuffer<int> clip_stats_host;
   int64_t clip_stats_ready = 0;  // the first so many device records hold their initial values (the export kernel leaves them so)
+  // note events of many clips (bp_infer_clips_events, note_track.hip), all grow-only and scratch of one call: the first event
+  // record of each clip's region, the pool of regions (16-byte event records; bends, a byte each), the working state of the
+  // clips too long for LDS, per clip its counts and status, the packed events and bends with the offsets that go home first
+  // (ev_meta), and the page-locked block both copies land in
+  Buffer<int64_t> ev_first, ev_meta;
+  Table ev_pool, ev_counts, ev_out;
+  Buffer<int8_t> bd_pool, bd_out;
+  Buffer<float> ev_scratch;
+  bp::PinnedBuffer<int64_t> ev_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

@@ -163,6 +163,22 @@ void launch_clips_candidates(float* note, float* onset, const float* contour, co
                              int64_t total_rows, int lo, int hi, int infer, double onset_thresh, const void* tab,
                              const double* gauss, void* table, uint8_t* bits, int8_t* bend, hipStream_t s);
 void launch_note_stats_init(void* stats, hipStream_t s);
+
+// note_track.hip: the sequential half of note decoding for many clips, one workgroup per clip (bp_infer_clips_events).
+// A clip of at most kNoteTrackLdsRows rows keeps its working copy of the note rows in LDS, a longer one in `scratch`
+// (note_track_scratch_floats of all rows); one of more than kNoteTrackMaxRows rows is not decoded (status 2).
+constexpr int kNoteTrackLdsRows = 432, kNoteTrackMaxRows = 8192;
+// event records a clip's region of the pool holds (BP_EVENTS_CAPACITY of include/basic_pitch_amd_events.h)
+int64_t note_track_capacity(int64_t rows, int min_note_len);
+int64_t note_track_scratch_floats(int64_t total_rows);
+// note / bits / bend_map (null: no bends) / offs / stats: what launch_clips_candidates left on the device for n_clips > 0 clips.
+// ev_first [n_clips + 1]: the event records before each clip's region of ev_pool (16 bytes each); clip c's bends go to
+// bd_pool + 88 * offs[c].  counts: n_clips records of 16 bytes.  Then the second step: meta = [n_clips + 1] events before each
+// clip, [n_clips + 1] bends before each clip, [n_clips] status; ev_out / bd_out the events and bends contiguous in clip order.
+hipError_t launch_note_track(const float* note, const uint8_t* bits, const int8_t* bend_map, const int64_t* offs,
+                             const int64_t* ev_first, const void* stats, int64_t n_clips, int64_t max_rows, double frame_thresh,
+                             int energy_tol, int min_note_len, int melodia, float* scratch, void* ev_pool, int8_t* bd_pool,
+                             void* counts, int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -170,6 +170,15 @@ void bp_note_params_default(bp_note_params* p) {
   p->max_freq_hz = 0.0;
 }
 
+// model_frames_to_time()[fr] (note_creation.py:346-357): the one expression every event's times come from — decode_core
+// below, and the calls that bring events home from the device (track_api.hip, bp_infer_clips_events)
+double bp_internal_frame_time(int64_t fr) {
+  const double window_offset = (256.0 / 22050.0) * (172.0 - (43844.0 / 256.0)) + 0.0018;
+  const double original = (double)(fr * 256) / 22050.0;
+  const double window_number = std::floor((double)fr / 172.0);
+  return original - (window_offset * window_number);
+}
+
 // The decoder.  Two sources for the onset peaks and the pitch bends:
 //   cand_bits == null: the onset and contour maps (bp_notes_decode: everything on the host);
 //   cand_bits != null: the device extracted them (bp_note_candidates, csrc/note_device.hip): bit f of byte row t
@@ -430,12 +439,7 @@ static int decode_core(float* note, float* onset, const float* contour, const ui
     const double n = (double)i - 25.0;
     gauss[i] = std::exp(-(n * n) / (2.0 * 5.0 * 5.0));  // scipy.signal.windows.gaussian(51, std=5)
   }
-  const double window_offset = (256.0 / 22050.0) * (172.0 - (43844.0 / 256.0)) + 0.0018;
-  auto frame_time = [&](int64_t fr) {
-    const double original = (double)(fr * 256) / 22050.0;
-    const double window_number = std::floor((double)fr / 172.0);
-    return original - (window_offset * window_number);
-  };
+  auto frame_time = [](int64_t fr) { return bp_internal_frame_time(fr); };
   int64_t bo = 0;
   for (size_t e = 0; e < notes.size(); ++e) {
     const Raw& r = notes[e];

@@ -10,14 +10,16 @@
 // The staging buffers of these calls are the handle's typed, grow-only buffers (device_buffer.h): a call reserves what it
 // needs before it queues work on them, and nothing here frees by hand.
 #include <algorithm>
+#include <cstring>
 
-#include "../../include/basic_pitch_amd_clips.h"
+#include "../../include/basic_pitch_amd_events.h"
 #include "bp_context.h"
 
 using namespace bp;
 
 extern "C" void bp_internal_bend_tables(int32_t* tab, double* gauss);
 extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);
+extern "C" double bp_internal_frame_time(int64_t frame);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 // ---- what the streaming sessions (stream_api.hip) share with this file (declared in bp_context.h): the end of a call, the
@@ -338,11 +340,12 @@ int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params
                          h->nd_stats_host, h->nd_stats_host_dev, 1, exported_by_kernel);
 }
 
-// The same for the maps of n_clips clips that lie one after the other in m, clip c at rows [offs[c], offs[c + 1]) of
-// offs[n_clips] = T > 0 rows, each clip decoded as its own whole track; its record comes home as h->clip_stats_host[4 c ...].
-// offs (host) must stay as it is until the stream has been waited for.
-int queue_clips_candidates(bp_handle h, const Maps& m, int64_t n_clips, const int64_t* offs, const bp_note_params* prm,
-                           float* note_out, uint8_t* cand_out, int8_t* bend_out, bool* exported_by_kernel) {
+// The candidates of the maps of n_clips clips that lie one after the other in m, clip c at rows [offs[c], offs[c + 1]) of
+// offs[n_clips] = T > 0 rows, each clip decoded as its own whole track.  offs (host) must stay as it is until the stream has
+// been waited for.  The device half: *d_bits / *d_bend (null without want_bends) are where the bitmap and the bends of all
+// rows lie, the clips' records are in h->clip_stats and their row offsets in h->clip_rows; nothing goes home.
+int queue_clips_dense(bp_handle h, const Maps& m, int64_t n_clips, const int64_t* offs, const bp_note_params* prm, bool want_bends,
+                      uint8_t** d_bits_out, int8_t** d_bend_out) {
   hipStream_t s = h->stream;
   const int64_t T = offs[n_clips];
   const void* tab = nullptr;
@@ -353,21 +356,33 @@ int queue_clips_candidates(bp_handle h, const Maps& m, int64_t n_clips, const in
   if (int rc = reserve_candidates(h, T, &d_bits, &d_bend)) return rc;
   if ((size_t)n_clips * kStatsBytes > h->clip_stats.capacity()) h->clip_stats_ready = 0;  // a new block: nothing initialised
   BP_HIP(h->clip_stats.reserve((size_t)n_clips * kStatsBytes));
-  BP_HIP(h->clip_stats_host.reserve((size_t)n_clips * (kStatsBytes / sizeof(int))));
-  void* stats_host_dev = nullptr;
-  BP_HIP(hipHostGetDevicePointer(&stats_host_dev, h->clip_stats_host, 0));
   BP_HIP(h->clip_rows.reserve((size_t)n_clips + 1));
   BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
   int lo = 0, hi = 88;
   bp_internal_freq_limits(prm, &lo, &hi);
-  const bool want_bends = prm->include_pitch_bends != 0 && bend_out != nullptr;
   if (h->clip_stats_ready < n_clips) launch_clips_stats_init(h->clip_stats, n_clips, s);
   h->clip_stats_ready = 0;
   launch_clips_candidates(m.note, m.onset, m.contour, h->clip_rows, n_clips, T, lo, hi, prm->infer_onsets != 0,
                           prm->onset_threshold, tab, gauss, h->clip_stats, d_bits, want_bends ? d_bend : nullptr, s);
   BP_HIP(hipGetLastError());
-  return send_candidates(h, m.note, T, d_bits, want_bends ? d_bend : nullptr, note_out, cand_out, bend_out, h->clip_stats,
-                         h->clip_stats_host, stats_host_dev, n_clips, exported_by_kernel);
+  *d_bits_out = d_bits;
+  *d_bend_out = want_bends ? d_bend : nullptr;
+  return BP_OK;
+}
+
+// ... and home: the note rows, the bitmap and the bends to host buffers, clip c's record as h->clip_stats_host[4 c ...]
+int queue_clips_candidates(bp_handle h, const Maps& m, int64_t n_clips, const int64_t* offs, const bp_note_params* prm,
+                           float* note_out, uint8_t* cand_out, int8_t* bend_out, bool* exported_by_kernel) {
+  uint8_t* d_bits = nullptr;
+  int8_t* d_bend = nullptr;
+  // the page-locked copy of the records, before anything is queued
+  BP_HIP(h->clip_stats_host.reserve((size_t)n_clips * (kStatsBytes / sizeof(int))));
+  void* stats_host_dev = nullptr;
+  BP_HIP(hipHostGetDevicePointer(&stats_host_dev, h->clip_stats_host, 0));
+  if (int rc = queue_clips_dense(h, m, n_clips, offs, prm, prm->include_pitch_bends != 0 && bend_out != nullptr, &d_bits, &d_bend))
+    return rc;
+  return send_candidates(h, m.note, offs[n_clips], d_bits, d_bend, note_out, cand_out, bend_out, h->clip_stats, h->clip_stats_host,
+                         stats_host_dev, n_clips, exported_by_kernel);
 }
 
 // ---- the driver ------------------------------------------------------------------------------------------------------------
@@ -619,9 +634,8 @@ int queue_clips_ingest(bp_handle h, int64_t n_clips, const bp_clip* clips, int s
 
 // everything bp_infer_clips_candidates queues: the ingest, the model on the clips' windows packed into full chunks (the maps
 // to h->track_out, concatenated by offs), the candidates of every clip.  offs[n_clips] > 0.
-int queue_clips(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
-                const int64_t* offs, const bp_note_params* prm, float* note_out, uint8_t* cand_bits, int8_t* bend_map,
-                std::vector<ClipDesc>& tab, bool* exported_by_kernel) {
+int queue_clips_maps(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
+                     const int64_t* offs, std::vector<ClipDesc>& tab, Maps* all_out) {
   std::vector<const float*> d_in(n_clips);
   std::vector<Maps> d_out(n_clips);
   Maps all;
@@ -631,7 +645,15 @@ int queue_clips(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_r
     return rc;
   for (int64_t i = 0; i < n_clips; ++i)
     d_out[i] = Maps{all.note + offs[i] * kFreqN, all.onset + offs[i] * kFreqN, all.contour + offs[i] * kFreqC};
-  if ((rc = tracks_core(h, n_clips, d_in.data(), n_model, d_out.data()))) return rc;
+  *all_out = all;
+  return tracks_core(h, n_clips, d_in.data(), n_model, d_out.data());
+}
+
+int queue_clips(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
+                const int64_t* offs, const bp_note_params* prm, float* note_out, uint8_t* cand_bits, int8_t* bend_map,
+                std::vector<ClipDesc>& tab, bool* exported_by_kernel) {
+  Maps all;
+  if (int rc = queue_clips_maps(h, n_clips, clips, sample_rate, mem_kind, n_model, offs, tab, &all)) return rc;
   return queue_clips_candidates(h, all, n_clips, offs, prm, note_out, cand_bits, bend_map, exported_by_kernel);
 }
 
@@ -640,6 +662,118 @@ void clips_status(bp_handle h, int64_t n_clips, const int64_t* offs, const bp_no
   if (exported_by_kernel) h->clip_stats_ready = n_clips;  // only now: the export kernel, which re-initialises the records, has run
   for (int64_t i = 0; i < n_clips; ++i)
     status[i] = offs[i + 1] > offs[i] && (h->clip_stats_host[4 * i + 1] || !(prm->onset_threshold > 0.0)) ? 1 : 0;
+}
+
+// ---- note events of many clips (include/basic_pitch_amd_events.h): where a call's results go
+struct EventsSink {
+  bp_note_event* events;
+  int64_t max_events;
+  int32_t* bends;
+  int64_t max_bends;
+  int64_t* event_offsets;
+  int* status;
+};
+
+// every argument that is not a clip's, before anything is queued
+int check_events(bp_handle h, const char* what, int64_t n_clips, const bp_note_params* prm, const EventsSink& out) {
+  auto invalid = [&](const char* why) {
+    h->err = std::string(what) + ": " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  if (n_clips < 0 || !prm || !out.event_offsets || (n_clips > 0 && !out.status)) return invalid("negative n_clips, null params, event_offsets or status");
+  if (out.max_events < 0 || out.max_bends < 0 || (out.max_events > 0 && !out.events) || (out.max_bends > 0 && !out.bends))
+    return invalid("negative max_events / max_bends, or room without a buffer");
+  if (prm->melodia_trick && prm->frame_threshold < 0.0)
+    return invalid("a negative frame threshold with the melodia trick never terminates (note_creation.py:452)");
+  if (prm->min_note_len < 0) return invalid("negative min_note_len");
+  return BP_OK;
+}
+
+// The jobs that need no device work: no rows at all, or an onset threshold <= 0 (status 1 for every clip that has rows, as
+// bp_infer_clips_candidates reports it).  True: the outputs are complete.
+bool events_without_device(int64_t n_clips, const int64_t* offs, const bp_note_params* prm, const EventsSink& out) {
+  if (offs[n_clips] > 0 && prm->onset_threshold > 0.0) return false;
+  for (int64_t i = 0; i < n_clips; ++i) out.status[i] = offs[i + 1] > offs[i] ? 1 : 0;
+  for (int64_t i = 0; i <= n_clips; ++i) out.event_offsets[i] = 0;
+  return true;
+}
+
+// Behind the maps of the clips (m, in h->track_out; rc: what queuing them returned): the dense half, the tracker, the pack, the
+// wait; then the events and bends home in one copy each and the host's share, the frame-to-time arithmetic.
+int run_events(bp_handle h, const char* what, int rc, const Maps& m, int64_t n, const int64_t* offs, const bp_note_params* prm,
+               const EventsSink& out) {
+  hipStream_t s = h->stream;
+  const int64_t T = offs[n];
+  const bool want_bends = prm->include_pitch_bends != 0;
+  std::vector<int64_t> ev_first((size_t)n + 1, 0);
+  int64_t max_rows = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    ev_first[(size_t)i + 1] = ev_first[(size_t)i] + note_track_capacity(offs[i + 1] - offs[i], prm->min_note_len);
+    max_rows = std::max(max_rows, offs[i + 1] - offs[i]);
+  }
+  const int64_t pool_events = ev_first[(size_t)n], n_meta = 3 * n + 2;
+  auto queue = [&]() -> int {
+    uint8_t* d_bits = nullptr;
+    int8_t* d_bend = nullptr;
+    BP_HIP(h->ev_first.reserve((size_t)n + 1));
+    BP_HIP(h->ev_meta.reserve((size_t)n_meta));
+    BP_HIP(h->ev_counts.reserve((size_t)n * 16));
+    BP_HIP(h->ev_pool.reserve((size_t)pool_events * 16));
+    BP_HIP(h->ev_out.reserve((size_t)pool_events * 16));
+    BP_HIP(h->bd_pool.reserve((size_t)T * 88));
+    BP_HIP(h->bd_out.reserve((size_t)T * 88));
+    if (max_rows > kNoteTrackLdsRows) BP_HIP(h->ev_scratch.reserve((size_t)note_track_scratch_floats(T)));
+    BP_HIP(h->ev_home.reserve((size_t)n_meta));  // page-locked: the offsets and status come home first
+    if (int qrc = queue_clips_dense(h, m, n, offs, prm, want_bends, &d_bits, &d_bend)) return qrc;
+    BP_HIP(hipMemcpyAsync(h->ev_first, ev_first.data(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    BP_HIP(launch_note_track(m.note, d_bits, d_bend, h->clip_rows, h->ev_first, h->clip_stats, n, max_rows, prm->frame_threshold,
+                             prm->energy_tol, prm->min_note_len, prm->melodia_trick != 0, h->ev_scratch, h->ev_pool, h->bd_pool,
+                             h->ev_counts, h->ev_meta, h->ev_out, h->bd_out, s));
+    BP_HIP(hipMemcpyAsync(h->ev_home, h->ev_meta, (size_t)n_meta * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    return BP_OK;
+  };
+  if ((rc = finish(h, rc ? rc : queue()))) return rc;
+  const int64_t* meta = h->ev_home;
+  const int64_t n_events = meta[n], n_bends = meta[2 * n + 1];
+  for (int64_t i = 0; i <= n; ++i) out.event_offsets[i] = meta[i];
+  for (int64_t i = 0; i < n; ++i) out.status[i] = (int)meta[2 * n + 2 + i];
+  if (n_events > out.max_events || n_bends > out.max_bends) {
+    h->err = std::string(what) + ": output buffers too small: " + std::to_string(n_events) + " events and " +
+             std::to_string(n_bends) + " bends are needed (event_offsets[n_clips] holds the events)";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (n_events == 0) return BP_OK;
+  struct Raw {
+    int32_t start, end, pitch;
+    float amp;
+  };
+  Raw* raw = nullptr;
+  int8_t* raw_bends = nullptr;
+  auto home = [&]() -> int {
+    // the stream has drained and the offsets are out of the block: it may grow for the events and, behind them, the bends
+    BP_HIP(h->ev_home.reserve((size_t)std::max(n_meta, 2 * n_events + (n_bends + 7) / 8)));
+    raw = reinterpret_cast<Raw*>(static_cast<int64_t*>(h->ev_home));
+    raw_bends = reinterpret_cast<int8_t*>(raw + n_events);
+    BP_HIP(hipMemcpyAsync(raw, h->ev_out, (size_t)n_events * sizeof(Raw), hipMemcpyDeviceToHost, s));
+    if (n_bends) BP_HIP(hipMemcpyAsync(raw_bends, h->bd_out, (size_t)n_bends, hipMemcpyDeviceToHost, s));
+    return BP_OK;
+  };
+  if ((rc = finish(h, home()))) return rc;
+  for (int64_t i = 0; i < n_bends; ++i) out.bends[i] = (int32_t)raw_bends[i];
+  int64_t bo = 0;
+  for (int64_t e = 0; e < n_events; ++e) {
+    const Raw& r = raw[e];
+    bp_note_event& ev = out.events[e];
+    std::memset(&ev, 0, sizeof ev);  // reserved fields and padding
+    ev.start_frame = r.start, ev.end_frame = r.end;
+    ev.start_s = bp_internal_frame_time(r.start), ev.end_s = bp_internal_frame_time(r.end);
+    ev.pitch_midi = r.pitch;
+    ev.amplitude = r.amp;
+    ev.bend_offset = bo;
+    ev.n_bends = want_bends ? r.end - r.start : 0;
+    bo += ev.n_bends;
+  }
+  return BP_OK;
 }
 
 }  // namespace
@@ -775,6 +909,58 @@ int bp_infer_clips_candidates(bp_handle h, int64_t n_clips, const bp_clip* clips
     return rc;
   clips_status(h, n_clips, offs.data(), params, exported_by_kernel, status);
   return BP_OK;
+}
+
+// ---- note events of many clips from the device (include/basic_pitch_amd_events.h) --------------------------------------------
+int64_t bp_events_capacity(int64_t rows, int min_note_len) { return note_track_capacity(rows, min_note_len); }
+
+int bp_infer_clips_events(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                          const bp_note_params* params, bp_note_event* events, int64_t max_events, int32_t* bends,
+                          int64_t max_bends, int64_t* event_offsets, int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_infer_clips_events";
+  const EventsSink out{events, max_events, bends, max_bends, event_offsets, status};
+  if (int rc = check_events(h, what, n_clips, params, out)) return rc;
+  std::vector<int64_t> n_model((size_t)n_clips), offs((size_t)n_clips + 1);
+  if (int rc = check_clips(h, what, n_clips, clips, sample_rate, pcm_mem_kind, true, n_model.data(), offs.data())) return rc;
+  if (events_without_device(n_clips, offs.data(), params, out)) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  if (sample_rate != h->rate)
+    if (int rc = clips_filter(h, what, sample_rate)) return rc;
+  std::vector<ClipDesc> tab((size_t)n_clips);
+  Maps all;
+  return run_events(h, what, queue_clips_maps(h, n_clips, clips, sample_rate, pcm_mem_kind, n_model.data(), offs.data(), tab, &all),
+                    all, n_clips, offs.data(), params, out);
+}
+
+int bp_note_events_from_maps(bp_handle h, int64_t n_clips, const int64_t* row_offsets, const float* note, const float* onset,
+                             const float* contour, int mem_kind, const bp_note_params* params, bp_note_event* events,
+                             int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_note_events_from_maps";
+  const EventsSink out{events, max_events, bends, max_bends, event_offsets, status};
+  if (int rc = check_events(h, what, n_clips, params, out)) return rc;
+  bool ordered = row_offsets && row_offsets[0] == 0;
+  for (int64_t i = 0; ordered && i < n_clips; ++i) ordered = row_offsets[i + 1] >= row_offsets[i];
+  if (!ordered || (mem_kind != BP_MEM_HOST && mem_kind != BP_MEM_DEVICE)) {
+    h->err = std::string(what) + ": row_offsets must start at 0 and never decrease; mem_kind must be BP_MEM_HOST or BP_MEM_DEVICE";
+    return BP_ERR_INVALID_ARG;
+  }
+  const int64_t T = row_offsets[n_clips];
+  if (T > 0 && (!note || !onset || !contour)) {
+    h->err = std::string(what) + ": null input pointer";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (events_without_device(n_clips, row_offsets, params, out)) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  // a private copy of the maps: the frequency limits are applied in place
+  Maps m;
+  int rc = take_track_out(h, T, &m);
+  if (!rc) {
+    const Maps given{const_cast<float*>(note), const_cast<float*>(onset), const_cast<float*>(contour)};  // only read
+    rc = copy_maps(h, m, given, T, mem_kind == BP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice);
+  }
+  return run_events(h, what, rc, m, n_clips, row_offsets, params, out);
 }
 
 #ifdef BP_AB_KERNELS

@@ -393,17 +393,30 @@ class Model:
         melodia_trick: bool = True,
         midi_tempo: float = DEFAULT_MINIMUM_MIDI_TEMPO,
         threads: int = 8,
+        decode: str = "host",
     ) -> "List[Tuple[Any, List[Any]]]":
         """Many short clips -> [(midi_data, note_events)] in input order, with the decoding parameters of `predict`.
         `clips`: numpy arrays [n] or [n, channels] of float32, int16, int32, uint8 or float64 samples; `sample_rates`: one int
         for all or one per clip.  The clips of a rate go to the device in ONE call (`bp_infer_clips_candidates`: a constant
         number of launches per batch of windows instead of about ten per clip) and come back as what the sequential half of
-        note decoding needs; the events of a clip are those of `predict_pcm_raw` + `model_output_to_notes` on it alone."""
+        note decoding needs; the events of a clip are those of `predict_pcm_raw` + `model_output_to_notes` on it alone.
+        decode="device": the sequential half runs on the device as well (`bp_infer_clips_events`, one workgroup per clip) and
+        only events and bends come home; the same events."""
         from . import clips as _clips
 
         return _clips.transcribe_clips(self, clips, sample_rates, onset_threshold, frame_threshold, minimum_note_length,
                                        minimum_frequency, maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo,
-                                       threads)
+                                       threads, decode)
+
+    def note_events(self, outputs: Sequence[Dict[str, Any]], prm) -> "List[Tuple[Optional[List[Any]], int]]":
+        """Note events of many posteriorgram segments in one call, decoded on the device (`bp_note_events_from_maps`,
+        csrc/note_track.hip): `outputs` is a list of {"note", "onset", "contour"} dicts (numpy arrays or CUDA tensors), `prm`
+        `note_creation._note_params`.  Returns [(events, status)] per dict: the events `model_output_to_notes` decodes from
+        those maps, or None with status 1 (a NaN, or an onset threshold <= 0) or 2 (more events than the segment's region
+        holds) — decode such maps on the host."""
+        from . import events as _events
+
+        return _events.note_events(self, outputs, prm)
 
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
