@@ -2,13 +2,17 @@
 itself pinned to RFC 9639's worked example and to WAV <-> FLAC pairs in tests/test_audio_decode.py): the same integers,
 sample for sample, on the RFC's example file, on streams from the test-side encoder that exercise every subframe type /
 stereo mode / residual coding / sample size, and on the reference's second recording; the MD5 of STREAMINFO is checked
-here on the device's output; corrupt and truncated streams are errors; `predict()` on a .flac file goes through it."""
+here on the device's output; corrupt and truncated streams are errors; `predict()` on a .flac file goes through it.  The
+streams of tests/flac_streams.py take it off the encoder's usual operating point: LPC precision and shift, variable block
+sizes, long sample numbers, sample-rate codes 12 / 14, forced Rice parameters, escapes of 0 bits — all decoded, none refused
+— and frame headers planted in the payload, which the scan -> chain design either sees through or hands to the host."""
 import hashlib
 import os
 
 import numpy as np
 import pytest
 
+import flac_streams as FS
 import flac_writer as FW
 from conftest import GOLDEN
 
@@ -285,3 +289,146 @@ def test_corrupt_small_files_are_errors_or_the_host_decoders_samples(model):
         host, _ = _host_ints(bytes(bad), 16)
         assert np.array_equal(got, host), trial
     assert outcomes["error"] > 100, outcomes
+
+
+# ---- the streams of tests/flac_streams.py: valid files, every expected value is the PCM the stream was made from ------------
+def _device_decodes_to_the_source(model, st):
+    """device == source PCM == host decoder, the MD5 of STREAMINFO on the device's output, the sample count; no refusal"""
+    got, sr = model.flac_decode_device(st.data)
+    assert sr == st.sr and got.shape == st.pcm.shape
+    assert np.array_equal(got, st.pcm)
+    host, _ = _host_ints(st.data, st.bits)
+    assert np.array_equal(got, host)
+    md5_at = st.data.index(b"fLaC") + 8 + 18
+    assert _md5_of(got, st.bits) == st.data[md5_at : md5_at + 16]
+    assert model.flac_layout(st.data)["n_frames"] == len(st.pcm)
+
+
+@pytest.mark.parametrize("bits", [16, 24])
+def test_lpc_precision_and_shift_mixed_in_one_wave(model, bits):
+    """70 frames = lanes of two waves, and from lane to lane another precision (1..15 bits), shift (0..15, both ends of the funnel
+    shift that cuts the prediction out of the float64 sum) and order (the three register classes and the generic path)."""
+    _device_decodes_to_the_source(model, FS.precision_shift_mixed(bits))
+
+
+@pytest.mark.parametrize("bits", [16, 24])
+@pytest.mark.parametrize("prec,shift", FS.PREC_SHIFT)
+def test_lpc_precision_and_shift(model, prec, shift, bits):
+    _device_decodes_to_the_source(model, FS.precision_shift(prec, shift, bits))
+
+
+@pytest.mark.parametrize("mode", FS.MODES)
+def test_full_scale_24_bit_with_saturated_coefficients(model, mode):
+    """the largest sums the register predictor's float64 arithmetic meets in a valid stream: twelve 15-bit coefficients pinned
+    at -16384 / 16383 against 24- / 25-bit samples at full scale whose signs line up with them — |sum| = 2^40.6 and 2^41.6
+    (tests/flac_streams.py full_scale asserts the figure), cut out by the funnel shift at 14"""
+    _device_decodes_to_the_source(model, FS.full_scale(mode))
+
+
+@pytest.mark.parametrize("name,wide", [("mixed", False), ("one", False), ("tiny", False), ("mixed", True)])
+def test_variable_block_size(model, name, wide):
+    """The variable branch of the header parse, of the chain (a successor's number is its predecessor's plus the predecessor's
+    block size) and of the frames' places in the output; "mixed" and "tiny" put frames of 16 / 17 samples — less than one
+    burst of residuals — beside frames of 4,096 in one wave."""
+    _device_decodes_to_the_source(model, FS.variable(name, wide))
+
+
+@pytest.mark.parametrize("nbytes", [3, 4])
+def test_sample_numbers_of_three_and_four_bytes(model, nbytes):
+    """Coded numbers of three bytes, and of four and five in a stream of 2.2 million samples whose first 33 frames are
+    constant subframes of 65,535 samples (the largest block size a frame header can state)."""
+    _device_decodes_to_the_source(model, FS.long_numbers(nbytes))
+
+
+@pytest.mark.parametrize("sr,code", [(48000, 12), (8000, 12), (44100, 14), (22050, 14)])
+def test_sample_rate_codes_12_and_14(model, sr, code):
+    _device_decodes_to_the_source(model, FS.rate_code(sr, code))
+
+
+@pytest.mark.parametrize("k,rice2", [(0, False), (1, True), (14, False), (30, True)])
+def test_rice_parameter_extremes(model, k, rice2):
+    """Parameter 0 / 1 on residuals of hundreds: every burst of sixteen codes holds codes beyond the 32-bit window and is
+    replayed code by code, each code refuels the lane's ring several times.  14 / 30: codes of 15+ and 31+ bits."""
+    _device_decodes_to_the_source(model, FS.rice_forced(k, rice2))
+
+
+def test_escaped_partitions_of_zero_bits(model):
+    _device_decodes_to_the_source(model, FS.escape_zero())
+
+
+# what flac_decode_device makes of the files with planted headers (test_frame_headers_inside_the_payload): the chain keeps a
+# false header that a real frame "continues" or that continues a real frame, and then fails as a whole; the last real frame
+# behind a stray header has neither a predecessor it continues nor a successor, is dropped, and the sample count falls short
+OUTCOMES = {"stray": "decoded", "stray_late": "refused", "continues": "refused", "pair": "refused", "flood": "refused",
+            "variable_stray": "decoded", "variable_continues": "refused", "continues_long": "refused"}
+
+
+def _planted_outcome(model, st):
+    """the contract of a valid file with false sync codes: exactly the source PCM, or a refusal — never other samples"""
+    from basic_pitch_amd._native import NativeLibraryError
+
+    try:
+        got, sr = model.flac_decode_device(st.data)
+    except (ValueError, NativeLibraryError):
+        return "refused"
+    assert sr == st.sr and np.array_equal(got, st.pcm)
+    return "decoded"
+
+
+def test_frame_headers_inside_the_payload(model, tmp_path):
+    """Verbatim samples that spell complete frame headers (tests/flac_streams.py planted(): each checked to sit where it should
+    and to pass the sync, reserved-value and CRC-8 rules).  The chain drops a candidate that neither continues its predecessor
+    nor is continued by its successor: the stray ones in the middle of a stream must be decoded, fixed and variable block
+    size; the others (a false header that carries its predecessor's number + 1, a pair that continue each other, more
+    candidates than a chunk's list holds, a stray one in front of the last frame) may be refused, never decoded to other
+    samples.  Whatever the device decoder does, `predict()` on the file returns what the host-decoded samples give, and the
+    native file job falls back to the host decoder (file_pipeline.cpp, "the device decoder could not follow the stream")
+    and writes the bytes it writes with host_flac=True.
+
+    What happens to each file is recorded in OUTCOMES above (the stray header in the next-to-last frame: refused) and asserted,
+    so that a change of behaviour is noticed."""
+    from basic_pitch_amd import inference as inf, transcribe_files
+
+    outcomes = {}
+    for case in FS.PLANTED:
+        st = FS.planted(case)
+        FS.check_planted(st, FS.planted_shape(case)[0])
+        outcomes[case] = _planted_outcome(model, st)
+        path = tmp_path / (case + ".flac")
+        path.write_bytes(st.data)
+        calls, orig = [], model.predict_flac
+
+        def recorded(blob):
+            calls.append("refused")
+            maps = orig(blob)
+            calls[-1] = "decoded"
+            return maps
+
+        model.predict_flac = recorded
+        try:
+            mo, _, ev = inf.predict(str(path), model)
+        finally:
+            del model.predict_flac
+        assert calls == [outcomes[case]], (case, calls)  # predict() went to the device, and to the host where that refused
+        pcm = (st.pcm / 32768.0).astype(np.float32)
+        want = model.predict_pcm(pcm, st.sr)
+        assert all(np.array_equal(mo[k], want[k]) for k in want), case
+        _, ev_host = inf._output_to_notes(want, inf.DEFAULT_ONSET_THRESHOLD, inf.DEFAULT_FRAME_THRESHOLD,
+                                          inf.DEFAULT_MINIMUM_NOTE_LENGTH_MS, None, None, False, True, inf.DEFAULT_MINIMUM_MIDI_TEMPO)
+        assert ev == ev_host, case
+        if case == "continues_long":  # (the other clips are 70 ms, too short for a note: their event lists are empty)
+            assert len(ev) > 0
+    assert outcomes["stray"] == outcomes["variable_stray"] == "decoded", outcomes
+    assert OUTCOMES == outcomes
+    # the native job on the second of tone with a "continues" header, which the device decoder refuses (asserted above through
+    # flac_decode_device and predict_flac on the same bytes; the job's report does not say which decoder ran): status 0 and
+    # the same note events in the same files as with the host decoder asked for
+    written = {}
+    for name, kw in (("device_first", {}), ("host", {"host_flac": True})):
+        o = tmp_path / name
+        o.mkdir()
+        (rep,) = transcribe_files([str(tmp_path / "continues_long.flac")], o, models=[model], threads=1, **kw)
+        assert rep["status"] == 0 and rep["n_note_events"] > 0, rep
+        written[name] = {f: open(os.path.join(o, f), "rb").read() for f in sorted(os.listdir(o))}
+    assert sorted(written["host"]) == ["continues_long_basic_pitch.csv", "continues_long_basic_pitch.mid"]
+    assert written["device_first"] == written["host"]
