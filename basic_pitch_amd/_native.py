@@ -166,6 +166,17 @@ class bp_stream_update(C.Structure):
     ]
 
 
+class bp_stream_events(C.Structure):
+    """One stream of `bp_streams_events` (include/basic_pitch_amd_stream_events.h): `stream` in, the rest out."""
+
+    _fields_ = [
+        ("stream", C.c_void_p),
+        ("first_row", C.c_int64),
+        ("n_rows", C.c_int64),
+        ("status", C.c_int),
+    ]
+
+
 # every symbol include/basic_pitch_amd.h declares (tests check they are all exported)
 EXPORTED_SYMBOLS = [
     "bp_create",
@@ -248,6 +259,11 @@ ROLLING_SYMBOLS = [
 UPDATE_SYMBOLS = [
     "bp_streams_update_layout",
     "bp_streams_candidates",
+]
+# every symbol include/basic_pitch_amd_stream_events.h declares (bound in basic_pitch_amd/streaming.py)
+STREAM_EVENTS_SYMBOLS = [
+    "bp_streams_events_layout",
+    "bp_streams_events",
 ]
 # every symbol include/basic_pitch_amd_clips.h declares (bound in basic_pitch_amd/clips.py)
 CLIPS_SYMBOLS = [

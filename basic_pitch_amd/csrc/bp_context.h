@@ -87,6 +87,7 @@ struct bp_context {
   Table ev_pool, ev_counts, ev_out;
   Buffer<int8_t> bd_pool, bd_out;
   Buffer<float> ev_scratch;
+  Table ev_seg;  // bp_streams_events: the table of the segments' own parameters (NoteTrackSeg)
   bp::PinnedBuffer<int64_t> ev_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
@@ -163,4 +164,44 @@ int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcp
 // the handle's tables of the device-side note candidates (note_device.hip), made on first use: the bend windows and the
 // Gaussian on the device, the page-locked copy of the stats record
 int note_tables(bp_handle h, const void** tab, const double** gauss);
+
+// ---- the tracker (note_track.hip) behind any dense half: the clips calls (track_api.hip), bp_streams_events (stream_api.hip).
+// Where a call's results go:
+struct EventsSink {
+  bp_note_event* events;
+  int64_t max_events;
+  int32_t* bends;
+  int64_t max_bends;
+  int64_t* event_offsets;
+  int* status;
+};
+// A job of n segments, segment c at rows [offs[c], offs[c + 1]) of the dense half's outputs.  prm: the parameters of all
+// segments (the clips calls' launch), or seg: one record per segment.  first_frame (null: zeros) is added to a segment's frames.
+struct EventsJob {
+  const char *what, *count_name;  // for messages: the call, and its name for n
+  int64_t n;
+  const int64_t* offs;
+  const bp_note_params* prm;
+  const NoteTrackSeg* seg;
+  const int64_t* first_frame;
+  int form;
+};
+struct EventsPlan {
+  std::vector<int64_t> ev_first;  // read by an asynchronous copy: alive until the wait
+  int64_t max_rows = 0;
+};
+// what the dense half left on the device: note rows, bitmap, bend map (null: none), the row offsets, a record per segment
+struct TrackInputs {
+  const float* note;
+  const uint8_t* bits;
+  const int8_t* bend;
+  const int64_t* offs;
+  const void* stats;
+};
+// The handle's buffers grown to the job (nothing queued); the tracker, the pack and the offsets on their way home; and, after
+// the wait, the offsets and status, the events and bends home in one copy each and the frame-to-time arithmetic.
+// *device_error (may be null) is set where events_home fails after queuing; buffers too small is not such a failure.
+int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan);
+int events_queue(bp_handle h, const EventsJob& job, const EventsPlan& plan, const TrackInputs& in);
+int events_home(bp_handle h, const EventsJob& job, const EventsSink& out, bool* device_error);
 }  // namespace bp

@@ -179,6 +179,19 @@ hipError_t launch_note_track(const float* note, const uint8_t* bits, const int8_
                              const int64_t* ev_first, const void* stats, int64_t n_clips, int64_t max_rows, double frame_thresh,
                              int energy_tol, int min_note_len, int melodia, float* scratch, void* ev_pool, int8_t* bd_pool,
                              void* counts, int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s);
+// The same for segments that carry their own parameters (bp_streams_events: a segment is a stream's slice).  seg: a device table
+// of n_segs records; bend_map is read only for segments with `bends`; a segment with `skip` gets status 1 and no events.
+// form: kNoteTrackFormAuto — the LDS form up to kNoteTrackLdsRows rows, the scratch form beyond —, or kNoteTrackFormScratch to
+// keep every segment's working state in `scratch` (the A/B library's tests).
+struct NoteTrackSeg {
+  double frame_thresh;
+  int energy_tol, min_note_len, melodia, bends, skip, reserved;
+};
+constexpr int kNoteTrackFormAuto = 0, kNoteTrackFormScratch = 2;  // 1 was the bit-plane form (measured, not kept)
+hipError_t launch_note_track_segs(const float* note, const uint8_t* bits, const int8_t* bend_map, const int64_t* offs,
+                                  const int64_t* ev_first, const void* stats, const NoteTrackSeg* seg, int64_t n_segs,
+                                  int64_t max_rows, int form, float* scratch, void* ev_pool, int8_t* bd_pool, void* counts,
+                                  int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

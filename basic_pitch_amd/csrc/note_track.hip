@@ -316,6 +316,27 @@ __global__ __launch_bounds__(256) void nt_track_kernel(NtArgs a, int lds_rows) {
   nt_track(a, c, T, state);
 }
 
+// The same two forms for segments that carry their own parameters (bp_streams_events: a segment is a stream's slice): segment
+// c decodes with seg[c], read beside its row offsets; a segment marked `skip` (an onset threshold <= 0) is the host's, status 1.
+template <bool kLds>
+__global__ __launch_bounds__(256) void nt_track_segs_kernel(NtArgs a, const NoteTrackSeg* __restrict__ seg, int lds_rows) {
+  extern __shared__ float s_state[];
+  const int64_t c = blockIdx.x;
+  const int64_t rows = a.offs[c + 1] - a.offs[c];
+  if ((rows <= lds_rows) != kLds) return;
+  const NoteTrackSeg p = seg[c];
+  const bool host = p.skip != 0 || a.stats[c].y != 0;
+  if (rows == 0 || host || rows > kNoteTrackMaxRows) {
+    if (threadIdx.x == 0) a.counts[c] = make_int4(0, 0, rows == 0 ? 0 : (host ? 1 : 2), 0);
+    return;
+  }
+  a.frame_thresh = p.frame_thresh;
+  a.energy_tol = p.energy_tol, a.min_note_len = p.min_note_len, a.melodia = p.melodia;
+  if (!p.bends) a.bend_map = nullptr;
+  float* state = kLds ? s_state : a.scratch + a.offs[c] * kNtRowWords;
+  nt_track(a, c, (int)rows, state);
+}
+
 // ---- the second step: events and bends contiguous in clip order.  meta: [n + 1] events before each clip, [n + 1] bends before
 // each clip, [n] status.
 __global__ __launch_bounds__(256) void nt_offsets_kernel(const int4* __restrict__ counts, int64_t n, int64_t* __restrict__ meta) {
@@ -365,6 +386,35 @@ int64_t note_track_capacity(int64_t rows, int min_note_len) {
 
 int64_t note_track_scratch_floats(int64_t total_rows) { return total_rows * kNtRowWords; }
 
+// The tracker's launches for either kind of segment: the LDS form sized by the longest segment that takes it (a job of
+// one-window clips runs three workgroups per compute unit), the scratch form where a segment is longer (lds_limit 0: for every
+// segment); then the second step.  extra: what a kernel takes between the arguments and lds_rows.
+template <class Kernel, class... Extra>
+static hipError_t nt_launch(Kernel lds, Kernel scratch, const NtArgs& a, int64_t n, int64_t max_rows, int lds_limit, int64_t* meta,
+                            void* ev_out, int8_t* bd_out, hipStream_t s, Extra... extra) {
+  const int lds_rows = (int)(max_rows < lds_limit ? max_rows : lds_limit);
+  const size_t lds_bytes = (size_t)(lds_rows > 0 ? lds_rows : 1) * kNtRowWords * 4;
+  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(lds, dim3((unsigned)n), dim3(256), lds_bytes, s, a, extra..., lds_rows);
+  if (max_rows > lds_limit) hipLaunchKernelGGL(scratch, dim3((unsigned)n), dim3(256), 0, s, a, extra..., lds_rows);
+  hipLaunchKernelGGL(nt_offsets_kernel, dim3(1), dim3(256), 0, s, a.counts, n, meta);
+  hipLaunchKernelGGL(nt_pack_kernel, dim3((unsigned)n), dim3(256), 0, s, a.counts, a.offs, a.ev_first, meta, n,
+                     reinterpret_cast<const int4*>(a.ev_pool), a.bd_pool, static_cast<int4*>(ev_out), bd_out);
+  return hipGetLastError();
+}
+
+hipError_t launch_note_track_segs(const float* note, const uint8_t* bits, const int8_t* bend_map, const int64_t* offs,
+                                  const int64_t* ev_first, const void* stats, const NoteTrackSeg* seg, int64_t n_segs,
+                                  int64_t max_rows, int form, float* scratch, void* ev_pool, int8_t* bd_pool, void* counts,
+                                  int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s) {
+  if (n_segs <= 0) return hipSuccess;
+  const NtArgs a{note, reinterpret_cast<const uint32_t*>(bits), bend_map, offs, ev_first, static_cast<const int4*>(stats), scratch,
+                 static_cast<NtEvent*>(ev_pool), bd_pool, static_cast<int4*>(counts), 0.0, 0, 0, 0};
+  return nt_launch(&nt_track_segs_kernel<true>, &nt_track_segs_kernel<false>, a, n_segs, max_rows,
+                   form == kNoteTrackFormScratch ? 0 : kNoteTrackLdsRows, meta, ev_out, bd_out, s, seg);
+}
+
 hipError_t launch_note_track(const float* note, const uint8_t* bits, const int8_t* bend_map, const int64_t* offs,
                              const int64_t* ev_first, const void* stats, int64_t n_clips, int64_t max_rows, double frame_thresh,
                              int energy_tol, int min_note_len, int melodia, float* scratch, void* ev_pool, int8_t* bd_pool,
@@ -372,19 +422,7 @@ hipError_t launch_note_track(const float* note, const uint8_t* bits, const int8_
   if (n_clips <= 0) return hipSuccess;
   const NtArgs a{note, reinterpret_cast<const uint32_t*>(bits), bend_map, offs, ev_first, static_cast<const int4*>(stats), scratch,
                  static_cast<NtEvent*>(ev_pool), bd_pool, static_cast<int4*>(counts), frame_thresh, energy_tol, min_note_len, melodia};
-  // the LDS form is sized by the longest clip that takes it: a job of one-window clips runs three workgroups per compute unit
-  const int lds_rows = (int)(max_rows < kNoteTrackLdsRows ? max_rows : kNoteTrackLdsRows);
-  const size_t lds_bytes = (size_t)(lds_rows > 0 ? lds_rows : 1) * kNtRowWords * 4;
-  const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&nt_track_kernel<true>),
-                                           hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
-  if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(nt_track_kernel<true>, dim3((unsigned)n_clips), dim3(256), lds_bytes, s, a, lds_rows);
-  if (max_rows > kNoteTrackLdsRows)
-    hipLaunchKernelGGL(nt_track_kernel<false>, dim3((unsigned)n_clips), dim3(256), 0, s, a, lds_rows);
-  hipLaunchKernelGGL(nt_offsets_kernel, dim3(1), dim3(256), 0, s, static_cast<const int4*>(counts), n_clips, meta);
-  hipLaunchKernelGGL(nt_pack_kernel, dim3((unsigned)n_clips), dim3(256), 0, s, static_cast<const int4*>(counts), offs, ev_first,
-                     meta, n_clips, static_cast<const int4*>(ev_pool), bd_pool, static_cast<int4*>(ev_out), bd_out);
-  return hipGetLastError();
+  return nt_launch(&nt_track_kernel<true>, &nt_track_kernel<false>, a, n_clips, max_rows, kNoteTrackLdsRows, meta, ev_out, bd_out, s);
 }
 
 }  // namespace bp

@@ -1,5 +1,5 @@
 // C ABI of the streaming sessions (include/basic_pitch_amd.h, include/basic_pitch_amd_live.h, include/basic_pitch_amd_rolling.h,
-// include/basic_pitch_amd_update.h): audio that arrives over time -> the rows of the un-overlapped
+// include/basic_pitch_amd_update.h, include/basic_pitch_amd_stream_events.h): audio that arrives over time -> the rows of the un-overlapped
 // posteriorgrams as they become final, for one stream or for many streams of one handle per step.
 //
 // A stream keeps on the device a ring of the model-rate signal that reaches back to the first sample of its oldest
@@ -47,6 +47,10 @@
 // bp_streams_candidates is that update for n streams of either mode in one step (queue_updates): one peek step for all tails,
 // one table of streams (StreamUpdate, note_device.hip "the updates of many streams"), the segmented launches, packed rows home.
 //
+// bp_streams_events is that step with nothing sent home (every stream's whole slice stays packed in the handle's buffers) and
+// the tracker of the clips calls behind it (note_track.hip, a segment per stream with the stream's own parameters; track_api.hip
+// events_reserve / events_queue / events_home): the events and their bends are all that crosses PCIe.
+//
 // A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the
 // handle's device and deletes the state, and an open or keep that fails leaves nothing behind.
 #include <algorithm>
@@ -54,7 +58,7 @@
 #include <memory>
 
 #include "bp_context.h"
-#include "../../include/basic_pitch_amd_update.h"
+#include "../../include/basic_pitch_amd_stream_events.h"
 
 using namespace bp;
 
@@ -762,9 +766,10 @@ int bp_stream_rolling_maps(bp_stream s, int with_tail, float* note, float* onset
 }
 
 // ---- the updates of n streams in one step (include/basic_pitch_amd_update.h) -------------------------------------------------
-// every per-stream argument, in index order, and the out fields but status; tail[i]: the rows of stream i's peek
+// every per-stream argument, in index order, and the out fields but status; tail[i]: the rows of stream i's peek.  for_events:
+// the host decoder's rules for the stream's kept parameters and its absolute frames as well (bp_streams_events).
 static int plan_updates(bp_handle h, const char* what, int64_t n, bp_stream_update* u, int with_tail, std::vector<int64_t>& tail,
-                        int64_t* note_rows, int64_t* bits_rows) {
+                        int64_t* note_rows, int64_t* bits_rows, bool for_events = false) {
   auto invalid = [&](const std::string& why) {
     h->err = std::string(what) + ": " + why;
     return BP_ERR_INVALID_ARG;
@@ -787,6 +792,11 @@ static int plan_updates(bp_handle h, const char* what, int64_t n, bp_stream_upda
     tail[(size_t)i] = with_tail && !s->finished ? rows_of_step(s, 0, true) : 0;
     const std::string who = std::string(what) + ": stream " + std::to_string(i);
     if (int rc = tail_refused(s, who.c_str(), s->kept.table, tail[(size_t)i])) return rc;
+    if (!for_events) continue;
+    if (s->prm.melodia_trick && s->prm.frame_threshold < 0.0)
+      return invalid(at + "a negative frame threshold with the melodia trick never terminates (note_creation.py:452)");
+    if (s->prm.min_note_len < 0) return invalid(at + "negative min_note_len");
+    if (s->rows_out + tail[(size_t)i] > INT32_MAX) return invalid(at + "the absolute frames pass INT32_MAX");
   }
   for (int64_t i = 0; i < n; ++i) {
     const bp_stream_state* s = u[i].stream;
@@ -800,9 +810,11 @@ static int plan_updates(bp_handle h, const char* what, int64_t n, bp_stream_upda
 
 // The step: the tails of all streams through one peek step into the scratch, the table of streams in one copy, the segmented
 // launches of note_device.hip, the packed results and the n records home.  `tab`: the table's host form, alive until the wait.
+// device_only: nothing goes home and every stream whose parameters include bends gets them (bp_streams_events); the packed rows
+// stay in h->up_note / up_bend / up_bits, the records in h->up_stats, the prefix arrays behind the table in h->up_tab.
 static int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, const std::vector<int64_t>& tail, int64_t note_rows,
                          int64_t bits_rows, float* note_out, int8_t* bend_out, uint8_t* bits_out, std::vector<WindowSeg>& segs,
-                         std::vector<uint8_t>& tab) {
+                         std::vector<uint8_t>& tab, bool device_only = false) {
   hipStream_t q = h->stream;
   const void* bend_tab = nullptr;
   const double* gauss = nullptr;
@@ -817,7 +829,8 @@ static int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, cons
   int64_t tail_rows = 0;
   for (int64_t t : tail) tail_rows += t;
   bool bends = false;
-  for (int64_t i = 0; i < n; ++i) bends = bends || (bend_out && u[i].stream->prm.include_pitch_bends != 0 && u[i].n_rows > u[i].new_row);
+  const bool bends_wanted = bend_out || device_only;
+  for (int64_t i = 0; i < n; ++i) bends = bends || (bends_wanted && u[i].stream->prm.include_pitch_bends != 0 && u[i].n_rows > u[i].new_row);
   BP_HIP(h->st_out.reserve((size_t)(tail_rows * kMapsRow)));
   BP_HIP(h->up_tab.reserve(tab.size()));
   BP_HIP(h->up_note.reserve((size_t)(note_rows * kFreqN)));
@@ -846,7 +859,7 @@ static int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, cons
     e.note_offset = u[i].note_offset, e.bits_offset = u[i].bits_offset;
     e.onset_thresh = s->prm.onset_threshold;
     e.lo = s->lo, e.hi = s->hi, e.infer = s->prm.infer_onsets != 0;
-    e.bends = bend_out && s->prm.include_pitch_bends != 0;
+    e.bends = bends_wanted && s->prm.include_pitch_bends != 0;
     pre_tail[i + 1] = pre_tail[i] + t;
     pre_chunk[i + 1] = pre_chunk[i] + streams_stats_chunks((e.e0 - a) + (T - e.e1));
     pre_bits[i + 1] = pre_bits[i] + (T - a);
@@ -864,6 +877,7 @@ static int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, cons
   launch_streams_candidates(d_tab, d_pre, n, pre_chunk[n], bits_rows, pre_bend[n], note_rows, bend_tab, gauss, h->up_stats, h->up_bits,
                             h->up_bend, h->up_note, q);
   BP_HIP(hipGetLastError());
+  if (device_only) return BP_OK;
   BP_HIP(hipMemcpyAsync(h->up_stats_host, h->up_stats, (size_t)(n * kStatsFloats * 4), hipMemcpyDeviceToHost, q));
   BP_HIP(hipMemcpyAsync(bits_out, h->up_bits, (size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES), hipMemcpyDeviceToHost, q));
   if (note_rows > 0) BP_HIP(hipMemcpyAsync(note_out, h->up_note, (size_t)(note_rows * kFreqN * 4), hipMemcpyDeviceToHost, q));
@@ -909,6 +923,102 @@ int bp_streams_candidates(bp_handle h, int64_t n, bp_stream_update* u, int with_
   for (int64_t i = 0; i < n; ++i)
     if (h->up_stats_host[i * kStatsFloats + 1]) u[i].status = 1;  // a NaN in the slice: the host decodes the maps themselves
   return BP_OK;
+}
+
+// ---- the note events of n streams from the device (include/basic_pitch_amd_stream_events.h) ---------------------------------
+// plan_updates with held_rows = 0 for every stream (new_row = first_row: the whole slice is gathered), the out fields but status,
+// the tracker's segment of every stream and the capacities of the regions
+static int plan_events(bp_handle h, const char* what, int64_t n, bp_stream_events* u, int with_tail, std::vector<bp_stream_update>& up,
+                       std::vector<int64_t>& tail, std::vector<NoteTrackSeg>& seg, int64_t* rows, int64_t* events_capacity,
+                       int64_t* bends_capacity) {
+  if (n < 0 || (n > 0 && !u)) {
+    h->err = std::string(what) + ": negative count or null array of streams";
+    return BP_ERR_INVALID_ARG;
+  }
+  up.assign((size_t)n, bp_stream_update{});
+  for (int64_t i = 0; i < n; ++i) up[(size_t)i].stream = u[i].stream;
+  int64_t note_rows = 0;
+  if (int rc = plan_updates(h, what, n, up.data(), with_tail, tail, &note_rows, rows, true)) return rc;
+  seg.assign((size_t)n, NoteTrackSeg{});
+  *events_capacity = *bends_capacity = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const bp_note_params& p = u[i].stream->prm;
+    const int64_t slice = up[(size_t)i].n_rows - up[(size_t)i].first_row;
+    u[i].first_row = up[(size_t)i].first_row, u[i].n_rows = up[(size_t)i].n_rows;
+    seg[(size_t)i] = NoteTrackSeg{p.frame_threshold, p.energy_tol, p.min_note_len, p.melodia_trick != 0, p.include_pitch_bends != 0,
+                                  !(p.onset_threshold > 0.0), 0};
+    *events_capacity += note_track_capacity(slice, p.min_note_len);
+    if (p.include_pitch_bends && slice <= kNoteTrackMaxRows) *bends_capacity += slice * kFreqN;
+  }
+  return BP_OK;
+}
+
+int bp_streams_events_layout(bp_handle h, int64_t n, bp_stream_events* u, int with_tail, int64_t* events_capacity,
+                             int64_t* bends_capacity) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  if (!events_capacity || !bends_capacity) {
+    h->err = "bp_streams_events_layout: null events_capacity / bends_capacity";
+    return BP_ERR_INVALID_ARG;
+  }
+  std::vector<bp_stream_update> up;
+  std::vector<int64_t> tail;
+  std::vector<NoteTrackSeg> seg;
+  int64_t rows = 0;
+  return plan_events(h, "bp_streams_events_layout", n, u, with_tail, up, tail, seg, &rows, events_capacity, bends_capacity);
+}
+
+int bp_streams_events(bp_handle h, int64_t n, bp_stream_events* u, int with_tail, bp_note_event* events, int64_t max_events,
+                      int32_t* bends, int64_t max_bends, int64_t* event_offsets) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_streams_events";
+  const EventsSink out{events, max_events, bends, max_bends, event_offsets, nullptr};
+  auto invalid = [&](const char* why) {
+    h->err = std::string(what) + ": " + why;
+    return BP_ERR_INVALID_ARG;
+  };
+  std::vector<bp_stream_update> up;
+  std::vector<int64_t> tail;
+  std::vector<NoteTrackSeg> seg;
+  int64_t rows = 0, cap_e = 0, cap_b = 0;
+  if (int rc = plan_events(h, what, n, u, with_tail, up, tail, seg, &rows, &cap_e, &cap_b)) return rc;
+  if (!out.event_offsets) return invalid("null event_offsets");
+  if (out.max_events < 0 || out.max_bends < 0 || (out.max_events > 0 && !out.events) || (out.max_bends > 0 && !out.bends))
+    return invalid("negative max_events / max_bends, or room without a buffer");
+  bool work = false;
+  std::vector<int64_t> offs((size_t)n + 1, 0), first((size_t)n, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t slice = u[i].n_rows - u[i].first_row;
+    u[i].status = seg[(size_t)i].skip ? 1 : 0;
+    offs[(size_t)i + 1] = offs[(size_t)i] + slice;
+    first[(size_t)i] = u[i].first_row;
+    work = work || (slice > 0 && !seg[(size_t)i].skip);
+  }
+  for (int64_t i = 0; i <= n; ++i) out.event_offsets[i] = 0;
+  if (!work) return BP_OK;  // no stream has a row yet, or none that the device decodes
+  BP_HIP(hipSetDevice(h->device));
+  const EventsJob job{what, "n", n, offs.data(), nullptr, seg.data(), first.data(), kNoteTrackFormAuto};
+  EventsPlan plan;
+  std::vector<WindowSeg> segs;  // both read by asynchronous copies: alive until the wait
+  std::vector<uint8_t> tab;
+  auto broken = [&](int rc) {
+    for (int64_t i = 0; i < n; ++i) u[i].stream->broken = true;
+    return rc;
+  };
+  auto queue = [&]() -> int {
+    if (int rc = events_reserve(h, job, &plan)) return rc;
+    if (int rc = queue_updates(h, n, up.data(), tail, rows, rows, nullptr, nullptr, nullptr, segs, tab, true)) return rc;
+    // the rows before each stream's slice: the table's prefix array of the note rows (new_row = first_row)
+    const int64_t* d_pre = reinterpret_cast<const int64_t*>(h->up_tab + (size_t)n * sizeof(StreamUpdate));
+    return events_queue(h, job, plan,
+                        TrackInputs{h->up_note, h->up_bits, h->up_bend, d_pre + (kStreamUpdatePrefixes - 1) * (n + 1), h->up_stats});
+  };
+  if (int rc = finish(h, queue())) return broken(rc);
+  std::vector<int> status((size_t)n, 0);
+  bool device_error = false;
+  const EventsSink sink{out.events, out.max_events, out.bends, out.max_bends, out.event_offsets, status.data()};
+  const int rc = events_home(h, job, sink, &device_error);
+  for (int64_t i = 0; i < n; ++i) u[i].status = seg[(size_t)i].skip ? 1 : status[(size_t)i];
+  return device_error ? broken(rc) : rc;
 }
 
 #ifdef BP_AB_KERNELS

@@ -74,6 +74,108 @@ int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcp
   return BP_OK;
 }
 
+// ---- the tracker behind any dense half (declared in bp_context.h): the clips calls here, bp_streams_events in stream_api.hip
+static bool seg_bends(const EventsJob& job, int64_t c) {
+  return job.seg ? job.seg[c].bends != 0 : job.prm->include_pitch_bends != 0;
+}
+
+int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan) {
+  const int64_t n = job.n, T = job.offs[n];
+  plan->ev_first.assign((size_t)n + 1, 0);
+  plan->max_rows = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t rows = job.offs[i + 1] - job.offs[i];
+    plan->ev_first[(size_t)i + 1] =
+        plan->ev_first[(size_t)i] + note_track_capacity(rows, job.seg ? job.seg[i].min_note_len : job.prm->min_note_len);
+    plan->max_rows = std::max(plan->max_rows, rows);
+  }
+  const int64_t pool_events = plan->ev_first[(size_t)n], n_meta = 3 * n + 2;
+  const bool scratch = plan->max_rows > kNoteTrackLdsRows || job.form == kNoteTrackFormScratch;
+  BP_HIP(h->ev_first.reserve((size_t)n + 1));
+  BP_HIP(h->ev_meta.reserve((size_t)n_meta));
+  BP_HIP(h->ev_counts.reserve((size_t)n * 16));
+  BP_HIP(h->ev_pool.reserve((size_t)pool_events * 16));
+  BP_HIP(h->ev_out.reserve((size_t)pool_events * 16));
+  BP_HIP(h->bd_pool.reserve((size_t)T * 88));
+  BP_HIP(h->bd_out.reserve((size_t)T * 88));
+  if (scratch) BP_HIP(h->ev_scratch.reserve((size_t)note_track_scratch_floats(T)));
+  if (job.seg) BP_HIP(h->ev_seg.reserve((size_t)n * sizeof(NoteTrackSeg)));
+  BP_HIP(h->ev_home.reserve((size_t)n_meta));  // page-locked: the offsets and status come home first
+  return BP_OK;
+}
+
+int events_queue(bp_handle h, const EventsJob& job, const EventsPlan& plan, const TrackInputs& in) {
+  hipStream_t s = h->stream;
+  const int64_t n = job.n;
+  BP_HIP(hipMemcpyAsync(h->ev_first, plan.ev_first.data(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (job.seg) {
+    BP_HIP(hipMemcpyAsync(h->ev_seg, job.seg, (size_t)n * sizeof(NoteTrackSeg), hipMemcpyHostToDevice, s));
+    BP_HIP(launch_note_track_segs(in.note, in.bits, in.bend, in.offs, h->ev_first, in.stats, h->ev_seg.as<NoteTrackSeg>(), n,
+                                  plan.max_rows, job.form, h->ev_scratch, h->ev_pool, h->bd_pool, h->ev_counts, h->ev_meta, h->ev_out,
+                                  h->bd_out, s));
+  } else {
+    const bp_note_params* prm = job.prm;
+    BP_HIP(launch_note_track(in.note, in.bits, in.bend, in.offs, h->ev_first, in.stats, n, plan.max_rows, prm->frame_threshold,
+                             prm->energy_tol, prm->min_note_len, prm->melodia_trick != 0, h->ev_scratch, h->ev_pool, h->bd_pool,
+                             h->ev_counts, h->ev_meta, h->ev_out, h->bd_out, s));
+  }
+  BP_HIP(hipMemcpyAsync(h->ev_home, h->ev_meta, (size_t)(3 * n + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+int events_home(bp_handle h, const EventsJob& job, const EventsSink& out, bool* device_error) {
+  hipStream_t s = h->stream;
+  const int64_t n = job.n, n_meta = 3 * n + 2;
+  const int64_t* meta = h->ev_home;
+  const int64_t n_events = meta[n], n_bends = meta[2 * n + 1];
+  for (int64_t i = 0; i <= n; ++i) out.event_offsets[i] = meta[i];
+  for (int64_t i = 0; i < n; ++i) out.status[i] = (int)meta[2 * n + 2 + i];
+  if (n_events > out.max_events || n_bends > out.max_bends) {
+    h->err = std::string(job.what) + ": output buffers too small: " + std::to_string(n_events) + " events and " +
+             std::to_string(n_bends) + " bends are needed (event_offsets[" + job.count_name + "] holds the events)";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (n_events == 0) return BP_OK;
+  struct Raw {
+    int32_t start, end, pitch;
+    float amp;
+  };
+  Raw* raw = nullptr;
+  int8_t* raw_bends = nullptr;
+  auto home = [&]() -> int {
+    // the stream has drained and the offsets are out of the block: it may grow for the events and, behind them, the bends
+    BP_HIP(h->ev_home.reserve((size_t)std::max(n_meta, 2 * n_events + (n_bends + 7) / 8)));
+    raw = reinterpret_cast<Raw*>(static_cast<int64_t*>(h->ev_home));
+    raw_bends = reinterpret_cast<int8_t*>(raw + n_events);
+    BP_HIP(hipMemcpyAsync(raw, h->ev_out, (size_t)n_events * sizeof(Raw), hipMemcpyDeviceToHost, s));
+    if (n_bends) BP_HIP(hipMemcpyAsync(raw_bends, h->bd_out, (size_t)n_bends, hipMemcpyDeviceToHost, s));
+    return BP_OK;
+  };
+  if (int rc = finish(h, home())) {
+    if (device_error) *device_error = true;
+    return rc;
+  }
+  for (int64_t i = 0; i < n_bends; ++i) out.bends[i] = (int32_t)raw_bends[i];
+  int64_t bo = 0;
+  for (int64_t c = 0; c < n; ++c) {
+    const int64_t first = job.first_frame ? job.first_frame[c] : 0;
+    const bool want_bends = seg_bends(job, c);
+    for (int64_t e = out.event_offsets[c]; e < out.event_offsets[c + 1]; ++e) {
+      const Raw& r = raw[e];
+      bp_note_event& ev = out.events[e];
+      std::memset(&ev, 0, sizeof ev);  // reserved fields and padding
+      ev.start_frame = (int32_t)(first + r.start), ev.end_frame = (int32_t)(first + r.end);
+      ev.start_s = bp_internal_frame_time(first + r.start), ev.end_s = bp_internal_frame_time(first + r.end);
+      ev.pitch_midi = r.pitch;
+      ev.amplitude = r.amp;
+      ev.bend_offset = bo;
+      ev.n_bends = want_bends ? r.end - r.start : 0;
+      bo += ev.n_bends;
+    }
+  }
+  return BP_OK;
+}
+
 }  // namespace bp
 
 namespace {
@@ -664,16 +766,7 @@ void clips_status(bp_handle h, int64_t n_clips, const int64_t* offs, const bp_no
     status[i] = offs[i + 1] > offs[i] && (h->clip_stats_host[4 * i + 1] || !(prm->onset_threshold > 0.0)) ? 1 : 0;
 }
 
-// ---- note events of many clips (include/basic_pitch_amd_events.h): where a call's results go
-struct EventsSink {
-  bp_note_event* events;
-  int64_t max_events;
-  int32_t* bends;
-  int64_t max_bends;
-  int64_t* event_offsets;
-  int* status;
-};
-
+// ---- note events of many clips (include/basic_pitch_amd_events.h)
 // every argument that is not a clip's, before anything is queued
 int check_events(bp_handle h, const char* what, int64_t n_clips, const bp_note_params* prm, const EventsSink& out) {
   auto invalid = [&](const char* why) {
@@ -699,81 +792,20 @@ bool events_without_device(int64_t n_clips, const int64_t* offs, const bp_note_p
 }
 
 // Behind the maps of the clips (m, in h->track_out; rc: what queuing them returned): the dense half, the tracker, the pack, the
-// wait; then the events and bends home in one copy each and the host's share, the frame-to-time arithmetic.
+// wait; then the events and bends home (events_home).
 int run_events(bp_handle h, const char* what, int rc, const Maps& m, int64_t n, const int64_t* offs, const bp_note_params* prm,
                const EventsSink& out) {
-  hipStream_t s = h->stream;
-  const int64_t T = offs[n];
-  const bool want_bends = prm->include_pitch_bends != 0;
-  std::vector<int64_t> ev_first((size_t)n + 1, 0);
-  int64_t max_rows = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    ev_first[(size_t)i + 1] = ev_first[(size_t)i] + note_track_capacity(offs[i + 1] - offs[i], prm->min_note_len);
-    max_rows = std::max(max_rows, offs[i + 1] - offs[i]);
-  }
-  const int64_t pool_events = ev_first[(size_t)n], n_meta = 3 * n + 2;
+  const EventsJob job{what, "n_clips", n, offs, prm, nullptr, nullptr, kNoteTrackFormAuto};
+  EventsPlan plan;
   auto queue = [&]() -> int {
     uint8_t* d_bits = nullptr;
     int8_t* d_bend = nullptr;
-    BP_HIP(h->ev_first.reserve((size_t)n + 1));
-    BP_HIP(h->ev_meta.reserve((size_t)n_meta));
-    BP_HIP(h->ev_counts.reserve((size_t)n * 16));
-    BP_HIP(h->ev_pool.reserve((size_t)pool_events * 16));
-    BP_HIP(h->ev_out.reserve((size_t)pool_events * 16));
-    BP_HIP(h->bd_pool.reserve((size_t)T * 88));
-    BP_HIP(h->bd_out.reserve((size_t)T * 88));
-    if (max_rows > kNoteTrackLdsRows) BP_HIP(h->ev_scratch.reserve((size_t)note_track_scratch_floats(T)));
-    BP_HIP(h->ev_home.reserve((size_t)n_meta));  // page-locked: the offsets and status come home first
-    if (int qrc = queue_clips_dense(h, m, n, offs, prm, want_bends, &d_bits, &d_bend)) return qrc;
-    BP_HIP(hipMemcpyAsync(h->ev_first, ev_first.data(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
-    BP_HIP(launch_note_track(m.note, d_bits, d_bend, h->clip_rows, h->ev_first, h->clip_stats, n, max_rows, prm->frame_threshold,
-                             prm->energy_tol, prm->min_note_len, prm->melodia_trick != 0, h->ev_scratch, h->ev_pool, h->bd_pool,
-                             h->ev_counts, h->ev_meta, h->ev_out, h->bd_out, s));
-    BP_HIP(hipMemcpyAsync(h->ev_home, h->ev_meta, (size_t)n_meta * sizeof(int64_t), hipMemcpyDeviceToHost, s));
-    return BP_OK;
+    if (int qrc = events_reserve(h, job, &plan)) return qrc;
+    if (int qrc = queue_clips_dense(h, m, n, offs, prm, prm->include_pitch_bends != 0, &d_bits, &d_bend)) return qrc;
+    return events_queue(h, job, plan, TrackInputs{m.note, d_bits, d_bend, h->clip_rows, h->clip_stats});
   };
   if ((rc = finish(h, rc ? rc : queue()))) return rc;
-  const int64_t* meta = h->ev_home;
-  const int64_t n_events = meta[n], n_bends = meta[2 * n + 1];
-  for (int64_t i = 0; i <= n; ++i) out.event_offsets[i] = meta[i];
-  for (int64_t i = 0; i < n; ++i) out.status[i] = (int)meta[2 * n + 2 + i];
-  if (n_events > out.max_events || n_bends > out.max_bends) {
-    h->err = std::string(what) + ": output buffers too small: " + std::to_string(n_events) + " events and " +
-             std::to_string(n_bends) + " bends are needed (event_offsets[n_clips] holds the events)";
-    return BP_ERR_INVALID_ARG;
-  }
-  if (n_events == 0) return BP_OK;
-  struct Raw {
-    int32_t start, end, pitch;
-    float amp;
-  };
-  Raw* raw = nullptr;
-  int8_t* raw_bends = nullptr;
-  auto home = [&]() -> int {
-    // the stream has drained and the offsets are out of the block: it may grow for the events and, behind them, the bends
-    BP_HIP(h->ev_home.reserve((size_t)std::max(n_meta, 2 * n_events + (n_bends + 7) / 8)));
-    raw = reinterpret_cast<Raw*>(static_cast<int64_t*>(h->ev_home));
-    raw_bends = reinterpret_cast<int8_t*>(raw + n_events);
-    BP_HIP(hipMemcpyAsync(raw, h->ev_out, (size_t)n_events * sizeof(Raw), hipMemcpyDeviceToHost, s));
-    if (n_bends) BP_HIP(hipMemcpyAsync(raw_bends, h->bd_out, (size_t)n_bends, hipMemcpyDeviceToHost, s));
-    return BP_OK;
-  };
-  if ((rc = finish(h, home()))) return rc;
-  for (int64_t i = 0; i < n_bends; ++i) out.bends[i] = (int32_t)raw_bends[i];
-  int64_t bo = 0;
-  for (int64_t e = 0; e < n_events; ++e) {
-    const Raw& r = raw[e];
-    bp_note_event& ev = out.events[e];
-    std::memset(&ev, 0, sizeof ev);  // reserved fields and padding
-    ev.start_frame = r.start, ev.end_frame = r.end;
-    ev.start_s = bp_internal_frame_time(r.start), ev.end_s = bp_internal_frame_time(r.end);
-    ev.pitch_midi = r.pitch;
-    ev.amplitude = r.amp;
-    ev.bend_offset = bo;
-    ev.n_bends = want_bends ? r.end - r.start : 0;
-    bo += ev.n_bends;
-  }
-  return BP_OK;
+  return events_home(h, job, out, nullptr);
 }
 
 }  // namespace
@@ -989,6 +1021,48 @@ int bp_ab_clips_candidates_from_maps(bp_handle h, int64_t n_clips, const int64_t
   if (rc) return rc;
   clips_status(h, n_clips, offsets, params, exported_by_kernel, status);
   return BP_OK;
+}
+
+// The A/B library's test hook for the tracker with per-segment parameters (declared nowhere: the tests name it):
+// bp_note_events_from_maps on host maps with one bp_note_params per segment and the tracker form (0: as the product chooses,
+// 2: every segment's working state in the scratch buffer).  The dense half — frequency limits, inferred onsets, the onset
+// threshold — takes params[0], and makes the bend map where any segment wants bends; the tracker takes segment c's frame
+// threshold, tolerance, minimum length, melodia and bends.
+int bp_ab_note_events_from_maps_forms(bp_handle h, int64_t n, const int64_t* row_offsets, const float* note, const float* onset,
+                                      const float* contour, const bp_note_params* params, int form, bp_note_event* events,
+                                      int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
+  if (!h || n < 1 || !row_offsets || !note || !onset || !contour || !params || !event_offsets || !status || row_offsets[0] != 0 ||
+      row_offsets[n] < 1 || (form != kNoteTrackFormAuto && form != kNoteTrackFormScratch) || !(params[0].onset_threshold > 0.0))
+    return BP_ERR_INVALID_ARG;
+  const char* what = "bp_ab_note_events_from_maps_forms";
+  const EventsSink out{events, max_events, bends, max_bends, event_offsets, status};
+  std::vector<NoteTrackSeg> seg((size_t)n);
+  bool any_bends = false;
+  for (int64_t i = 0; i < n; ++i) {
+    any_bends = any_bends || params[i].include_pitch_bends != 0;
+    if (row_offsets[i + 1] < row_offsets[i]) return BP_ERR_INVALID_ARG;
+    if (int rc = check_events(h, what, n, params + i, out)) return rc;
+    const bp_note_params& p = params[i];
+    seg[(size_t)i] = NoteTrackSeg{p.frame_threshold, p.energy_tol, p.min_note_len, p.melodia_trick != 0,
+                                  p.include_pitch_bends != 0, 0, 0};
+  }
+  BP_HIP(hipSetDevice(h->device));
+  const int64_t T = row_offsets[n];
+  const EventsJob job{what, "n", n, row_offsets, nullptr, seg.data(), nullptr, form};
+  EventsPlan plan;
+  auto queue = [&]() -> int {
+    Maps m;
+    uint8_t* d_bits = nullptr;
+    int8_t* d_bend = nullptr;
+    const Maps given{const_cast<float*>(note), const_cast<float*>(onset), const_cast<float*>(contour)};  // only read
+    if (int rc = events_reserve(h, job, &plan)) return rc;
+    if (int rc = take_track_out(h, T, &m)) return rc;
+    if (int rc = copy_maps(h, m, given, T, hipMemcpyHostToDevice)) return rc;
+    if (int rc = queue_clips_dense(h, m, n, row_offsets, params, any_bends, &d_bits, &d_bend)) return rc;
+    return events_queue(h, job, plan, TrackInputs{m.note, d_bits, d_bend, h->clip_rows, h->clip_stats});
+  };
+  if (int rc = finish(h, queue())) return rc;
+  return events_home(h, job, out, nullptr);
 }
 #endif
 

@@ -441,12 +441,13 @@ class Model:
 
         return peek_streams(self, streams)
 
-    def transcripts(self, transcribers, workers=None):
+    def transcripts(self, transcribers, workers=None, decode="host", midi=True):
         """`transcript()` of many live `StreamingTranscriber`s of this model behind one device step
-        (`streaming.transcripts`, `bp_streams_candidates`): `(midi_data, note_events)` per transcriber, in order."""
+        (`streaming.transcripts`, `bp_streams_candidates`): `(midi_data, note_events)` per transcriber, in order.
+        `decode="device"` decodes the events on the device too (`bp_streams_events`); `midi=False` returns `(None, note_events)`."""
         from .streaming import transcripts
 
-        return transcripts(self, transcribers, workers)
+        return transcripts(self, transcribers, workers, decode, midi)
 
     # -- introspection ----------------------------------------------------------------------------
     def info(self) -> Dict[str, Any]:

@@ -12,6 +12,10 @@ audio so far from what the device keeps (`bp_stream_keep`, `bp_stream_candidates
 Many live sessions: `transcripts(model, transcribers)` is `transcript()` of every one of them behind ONE device step
 (`bp_streams_candidates`; include/basic_pitch_amd_update.h), the host half of the decoding on a thread pool.
 
+Many live sessions, decoded on the device: `transcripts(..., decode="device")` takes the events themselves from ONE native
+call (`bp_streams_events`; include/basic_pitch_amd_stream_events.h): the sequential half of the decoding runs on the device,
+a workgroup per session, and only events and bends come home.
+
 Endless use: `StreamingTranscriber(live=True, horizon_seconds=H)` keeps the last H seconds in a ring on the device
 (`bp_stream_keep_rolling`, `bp_stream_candidates_rolling`; include/basic_pitch_amd_rolling.h) and `transcript()` is the exact
 decode of those rows in absolute stream time: device memory, host memory and the work of an update do not grow with the session.
@@ -61,6 +65,11 @@ UPDATE_PROTOTYPES = {
     "bp_streams_update_layout": (_int, [_vp, _i64, _vp, _int, _pi64, _pi64]),
     "bp_streams_candidates": (_int, [_vp, _i64, _vp, _int, _vp, _vp, _vp, _i64, _i64]),
 }
+# the same for include/basic_pitch_amd_stream_events.h (tests/test_stream_events_cpu.py compares)
+STREAM_EVENTS_PROTOTYPES = {
+    "bp_streams_events_layout": (_int, [_vp, _i64, _vp, _int, _pi64, _pi64]),
+    "bp_streams_events": (_int, [_vp, _i64, _vp, _int, _vp, _i64, _vp, _i64, _pi64]),
+}
 TAIL_ROWS = 2 * 142  # the rows a peek can have: what a rolling stream's ring holds beyond its horizon
 
 # the numpy type a chunk of each format is made of (BP_PCM_S24: packed bytes)
@@ -69,8 +78,9 @@ _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
-    """Declare the streaming family's prototypes (the four headers) on a loaded library."""
-    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES, **UPDATE_PROTOTYPES}.items():
+    """Declare the streaming family's prototypes (the five headers) on a loaded library."""
+    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES, **UPDATE_PROTOTYPES,
+                                      **STREAM_EVENTS_PROTOTYPES}.items():
         fn = getattr(lib, name)
         fn.restype, fn.argtypes = restype, argtypes
     return lib
@@ -304,6 +314,56 @@ def streams_candidates(model: "_inf.Model", streams: Sequence[Stream], held_rows
     return tab, note, bend, bits
 
 
+def events_table(streams: Sequence[Stream]):
+    """The `bp_stream_events` array of `bp_streams_events_layout` / `bp_streams_events` for these streams."""
+    tab = (_native.bp_stream_events * max(1, len(streams)))()
+    for i, s in enumerate(streams):
+        tab[i].stream = s._s.value
+    return tab
+
+
+def slice_first_row(rows_out: int, tail_rows: int, horizon_rows: Optional[int]) -> Tuple[int, int]:
+    """The pure-Python mirror of the layout's arithmetic: (first_row, n_rows) of a stream that has emitted `rows_out` rows and
+    whose peek would add `tail_rows`; `horizon_rows` None for a stream that keeps all its rows."""
+    T = int(rows_out) + int(tail_rows)
+    return (0 if horizon_rows is None else max(0, T - int(horizon_rows))), T
+
+
+def streams_events_capacity(slices: Sequence[Tuple[int, int, bool]]) -> Tuple[int, int]:
+    """The pure-Python mirror of `bp_streams_events_layout`'s totals for (slice rows, min_note_len, pitch bends) per stream:
+    the events and the bends with which `bp_streams_events` cannot fail for room."""
+    from . import events as _events
+
+    return (sum(_events.events_capacity(r, m) for r, m, _ in slices),
+            sum(_events.bends_capacity(r) for r, _, b in slices if b))
+
+
+def streams_events_layout(model: "_inf.Model", streams: Sequence[Stream], with_tail: bool = True):
+    """`bp_streams_events_layout`: (the `bp_stream_events` array with first_row / n_rows, events capacity, bends capacity)."""
+    lib = bind(model._lib)
+    tab = events_table(streams)
+    cap_e, cap_b = C.c_int64(0), C.c_int64(0)
+    rc = lib.bp_streams_events_layout(model._handle, len(streams), C.addressof(tab), int(bool(with_tail)), C.byref(cap_e), C.byref(cap_b))
+    _native.check(lib, model._handle, rc, "bp_streams_events_layout")
+    return tab, int(cap_e.value), int(cap_b.value)
+
+
+def streams_events(model: "_inf.Model", streams: Sequence[Stream], with_tail: bool = True, room: Optional[Tuple[int, int]] = None):
+    """One `bp_streams_events` call: (the `bp_stream_events` array, events, bends, event_offsets), stream i's events at
+    event_offsets[i]:event_offsets[i + 1] where its status is 0.  `room`: (max_events, max_bends) to call with, once; without it
+    the call is repeated with the sizes it asks for when the first guess was too small."""
+    from . import events as _events
+
+    lib = bind(model._lib)
+    n = len(streams)
+    tab = events_table(streams)
+    fixed = (model._handle, n, C.addressof(tab), int(bool(with_tail)))
+    rows = sum(min(s.rows + TAIL_ROWS, getattr(s, "horizon_rows", None) or s.rows + TAIL_ROWS) for s in streams)  # a first guess
+    call = lambda *a: lib.bp_streams_events(*a[:-1])  # noqa: E731  (status lives in the array)
+    events, bends, offsets, _ = _events._call(lib, model._handle, "bp_streams_events", call, fixed, n, rows, room)
+    return tab, events, bends, offsets
+
+
 def scatter_rows(ring: np.ndarray, packed: np.ndarray, r0: int, r1: int) -> None:
     """Packed rows (row 0 is absolute row r0) into a host ring, absolute row r at index r % len(ring): one slice assignment,
     two where the rows wrap.  An array that never wraps is a ring longer than r1."""
@@ -315,20 +375,49 @@ def scatter_rows(ring: np.ndarray, packed: np.ndarray, r0: int, r1: int) -> None
         at += k
 
 
-def transcripts(model: "_inf.Model", transcribers: Sequence["StreamingTranscriber"], workers: Optional[int] = None) -> List[Any]:
+def _transcripts_device(model: "_inf.Model", ts: List["StreamingTranscriber"], workers: Optional[int], midi: bool) -> List[Any]:
+    """`transcripts(decode="device")`: the events of every session from one `bp_streams_events` call; a session with status 1 or
+    2 takes the host route.  No transcriber's host arrays or `_held` are touched for a session the device decodes."""
+    from . import events as _events
+
+    results: List[Any] = [None] * len(ts)
+    ids = [i for i, t in enumerate(ts) if t._prm.onset_threshold > 0]  # the others: status 1 whatever the maps hold
+    if ids:
+        tab, events, bends, offsets = streams_events(model, [ts[i].stream for i in ids])
+        for k, i in enumerate(ids):
+            if tab[k].status == 0:
+                ev = _events.clip_events(events, bends, offsets, k, True)
+                results[i] = (_notes.note_events_to_midi(ev, ts[i]._decoding[5], ts[i]._decoding[7]) if midi else None, ev)
+    rest = [i for i, r in enumerate(results) if r is None]
+    for i, r in zip(rest, transcripts(model, [ts[i] for i in rest], workers, "host", midi)):
+        results[i] = r
+    return results
+
+
+def transcripts(model: "_inf.Model", transcribers: Sequence["StreamingTranscriber"], workers: Optional[int] = None,
+                decode: str = "host", midi: bool = True) -> List[Any]:
     """`t.transcript()` for every live transcriber of `model`, of either mode, in order — behind one native call
     (`bp_streams_candidates`): the tails' windows of all sessions run in shared batches, each session's packed rows are
     scattered into its own host arrays, and the sequential half of the decoding runs per session on a pool of `workers`
     threads (default 8; the native decoder releases the GIL).  A transcriber whose onset threshold is <= 0 or whose slice holds
-    a NaN takes the fallback `transcript()` takes."""
+    a NaN takes the fallback `transcript()` takes.
+
+    `decode="device"`: the same list from one `bp_streams_events` call — the sequential half runs on the device, a workgroup
+    per session, and only the events and bends come home; sessions the device leaves out (a NaN, a slice of more than 8,192
+    rows) take the route above.  `midi=False` returns `(None, note_events)` and skips `note_events_to_midi`, which holds the
+    interpreter lock."""
     from concurrent.futures import ThreadPoolExecutor
 
+    if decode not in ("host", "device"):
+        raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
     ts = list(transcribers)
     for t in ts:
         if not t.live:
             raise ValueError("transcripts() needs StreamingTranscriber(live=True)")
     if not ts:
         return []
+    if decode == "device":
+        return _transcripts_device(model, ts, workers, bool(midi))
     results: List[Any] = [None] * len(ts)
     ids = [i for i, t in enumerate(ts) if t._prm.onset_threshold > 0]  # the others: status 1 whatever the maps hold
     if ids:
@@ -345,11 +434,11 @@ def transcripts(model: "_inf.Model", transcribers: Sequence["StreamingTranscribe
             scatter_rows(t._bits, bits[u.bits_offset : u.bits_offset + T - a], a, T)
             t._held = t.stream.rows  # rows at or after it were a tail's: sent again next time
             if u.status == 0:
-                pending.append((i, pool.submit(t._decoded, a, T)))
+                pending.append((i, pool.submit(t._decoded, a, T, midi)))
         decoding = {i for i, _ in pending}
         for i, t in enumerate(ts):  # the fallbacks use the handle: on this thread, after the native call
             if i not in decoding:
-                results[i] = t._host_decoded()
+                results[i] = t._host_decoded() if midi else (None, t._host_decoded()[1])
         for i, fut in pending:
             results[i] = fut.result()
     return results
@@ -435,7 +524,7 @@ class StreamingTranscriber:
         tail = 0 if not s._s.value else s.rows_bound(0)
         return float(_notes.frames_to_time_at(np.array([horizon_first_row(s.rows + tail, self.horizon_rows)]))[0])
 
-    def _decoded(self, a: int, T: int):
+    def _decoded(self, a: int, T: int, midi: bool = True):
         """Status 0: the host half of the decoding on rows [a, T) of the host arrays (rings, for a rolling horizon)."""
         multiple_pitch_bends, midi_tempo = self._decoding[5], self._decoding[7]
         if self.horizon_rows is None:
@@ -443,7 +532,7 @@ class StreamingTranscriber:
         else:
             events = _notes.decode_candidates(_unwrapped(self._note, a, T), _unwrapped(self._bits, a, T),
                                               _unwrapped(self._bend, a, T), self._prm, first_frame=a)
-        return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+        return (_notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo) if midi else None), events
 
     def _host_decoded(self):
         """Status 1 — a NaN in the maps or an onset threshold <= 0: numpy's rules, the host decodes the maps themselves."""
