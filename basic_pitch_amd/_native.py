@@ -276,6 +276,16 @@ EVENTS_SYMBOLS = [
     "bp_infer_clips_events",
     "bp_note_events_from_maps",
 ]
+# every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
+FLAC_CLIPS_SYMBOLS = [
+    "bp_flac_clips_row_offsets",
+    "bp_flac_clips_decode_device",
+    "bp_infer_flac_clips_candidates",
+    "bp_infer_flac_clips_events",
+]
+# status values of a clip in those calls, beside 0, 1 and 2 of the PCM clips calls
+BP_CLIP_FLAC_HOST = 3    # left to the host decoder, known before anything is queued: no rows
+BP_CLIP_FLAC_FAILED = 4  # the device decoder could not follow the stream
 
 _lib: Optional[C.CDLL] = None
 

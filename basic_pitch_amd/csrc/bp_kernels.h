@@ -144,10 +144,28 @@ struct FlacDeviceBuffers {
   DeviceBuffer<uint8_t> cands, packed, frames;  // FdCand [chunks][kFdChunkCands]; FdCand, in file order; FdFrame
   DeviceBuffer<uint32_t> counts, offs;
   DeviceBuffer<int32_t> scratch;
-  DeviceBuffer<int> meta;                       // [0] status, [1] n_frames
+  DeviceBuffer<int> meta;                       // [0] status, [1] n_frames (a job of clips: that pair per clip)
   DeviceBuffer<uint16_t> crc_tab;
+  DeviceBuffer<uint8_t> clips;                  // flac_clips.hip: the job's table (FdClip)
 };
 int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream);
+int flac_device_crc_table(FlacDeviceBuffers& b);  // b.crc_tab, made on first use; 0 or -1
+
+constexpr int kFdChunkBytes = 65536;  // bytes of a stream a scan workgroup owns (flac_kernels.h kFdChunk)
+// flac_clips.hip: one stream of a job of many (bp_infer_flac_clips_candidates).  The job's bytes lie in FlacDeviceBuffers::file,
+// clip by clip; st.audio_start and st.nbytes count from the clip's first byte.  The table is sorted by first_wg and first_slot.
+struct FdClip {
+  FdStream st;
+  uint64_t base;         // the clip's first byte in the job's buffer: 16-byte aligned, >= 64 zero bytes behind the clip
+  uint32_t first_wg;     // its first workgroup of the scan launch = its first slice of the candidate lists (n_chunks >= 1 of them)
+  uint32_t first_slot;   // its first frame slot (max_frames >= 1 of them)
+  int32_t n_chunks, max_frames;
+  uint64_t scratch_off;  // its rows of scratch ([max_frames][channels][max_block] int32), in int32s
+  uint64_t pcm_off;      // its interleaved PCM in the job's PCM buffer, in bytes (16-byte aligned)
+  int32_t out_shift, out_wide;  // sample << out_shift fills an int16 (0) or int32 (1) word: BP_PCM_S16 / BP_PCM_S32
+};
+int flac_clips_decode(FlacDeviceBuffers& b, const FdClip* tab, int64_t n_clips, int64_t wgs, int64_t slots, int64_t scratch,
+                      void* d_pcm, size_t pcm_bytes, hipStream_t stream);
 
 // note_device.hip
 void launch_note_candidates(float* note, float* onset, const float* contour, int64_t T, int lo, int hi, int infer,

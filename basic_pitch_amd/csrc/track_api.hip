@@ -12,7 +12,7 @@
 #include <algorithm>
 #include <cstring>
 
-#include "../../include/basic_pitch_amd_events.h"
+#include "../../include/basic_pitch_amd_flac_clips.h"
 #include "bp_context.h"
 
 using namespace bp;
@@ -808,6 +808,112 @@ int run_events(bp_handle h, const char* what, int rc, const Maps& m, int64_t n, 
   return events_home(h, job, out, nullptr);
 }
 
+// ---- a job of FLAC clips decoded on the device (include/basic_pitch_amd_flac_clips.h; flac_clips.hip) -------------
+// What the host knows of a job before anything is queued: every clip's layout, which clips are left to the host, the rows, and
+// where each device clip lies in the job's buffers (the table flac_clips_decode uploads).
+struct FlacJob {
+  std::vector<bp_flac_stream_layout> lay;
+  std::vector<int64_t> dev;            // clip -> its record of `tab`; -1: left to the host
+  std::vector<int64_t> n_model, offs;  // samples at the handle's rate; rows before each clip
+  std::vector<FdClip> tab;
+  int64_t file_bytes = 0, wgs = 0, slots = 0, scratch = 0, pcm_bytes = 0;
+};
+
+// sample_rate 0: no rate to agree with and no rows (bp_flac_clips_decode_device)
+int plan_flac_clips(bp_handle h, const char* what, int64_t n, const bp_flac_clip* clips, int sample_rate, FlacJob* job) {
+  if (n < 0 || (n > 0 && !clips)) {
+    h->err = std::string(what) + ": negative n_clips or null clips";
+    return BP_ERR_INVALID_ARG;
+  }
+  auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+  job->lay.assign((size_t)n, bp_flac_stream_layout{});
+  job->dev.assign((size_t)n, -1);
+  job->n_model.assign((size_t)n, 0);
+  job->offs.assign((size_t)n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const bp_flac_clip& c = clips[i];
+    bp_flac_stream_layout& l = job->lay[(size_t)i];
+    job->offs[(size_t)i + 1] = job->offs[(size_t)i];
+    if (!c.file && c.nbytes) {
+      h->err = std::string(what) + ": clip " + std::to_string(i) + ": null file";
+      return BP_ERR_INVALID_ARG;
+    }
+    if (c.nbytes < 42 || bp_flac_layout(c.file, c.nbytes, &l) != BP_OK) continue;
+    if (sample_rate && l.sample_rate != sample_rate) {
+      h->err = std::string(what) + ": clip " + std::to_string(i) + ": its STREAMINFO says " + std::to_string(l.sample_rate) +
+               " Hz, the call " + std::to_string(sample_rate) + " Hz (one rate per call)";
+      return BP_ERR_INVALID_ARG;
+    }
+    if (!bp_internal_flac_device_supported(&l, c.nbytes) || (size_t)l.audio_start >= c.nbytes) continue;
+    // scratch is bounded before anything is allocated: a row of max_block samples per frame SLOT, min_block samples a slot
+    const int64_t max_frames = (l.n_frames + l.min_block - 1) / l.min_block + 1;
+    if (max_frames * l.max_block > 8 * l.n_frames + 2 * (int64_t)l.max_block) continue;
+    if (sample_rate) {
+      if (int rc = check_ingest(h, true, flac_format(l), l.n_frames, l.channels, sample_rate, BP_MEM_DEVICE)) {
+        h->err = std::string(what) + ": clip " + std::to_string(i) + ": " + h->err;
+        return rc;
+      }
+      job->n_model[(size_t)i] = resampled_length(l.n_frames, sample_rate, h->rate);
+      job->offs[(size_t)i + 1] += h_frames(h, job->n_model[(size_t)i]);
+    }
+    const bool wide = flac_format(l) == BP_PCM_S32;
+    FdClip k{};
+    k.st = FdStream{l.channels, l.bits_per_sample, l.min_block, l.max_block, l.n_frames, (uint32_t)l.audio_start, (uint32_t)c.nbytes};
+    k.base = (uint64_t)job->file_bytes, k.first_wg = (uint32_t)job->wgs, k.first_slot = (uint32_t)job->slots;
+    k.n_chunks = (int32_t)((c.nbytes - (size_t)l.audio_start + kFdChunkBytes - 1) / kFdChunkBytes), k.max_frames = (int32_t)max_frames;
+    k.scratch_off = (uint64_t)job->scratch, k.pcm_off = (uint64_t)job->pcm_bytes;
+    k.out_shift = (wide ? 32 : 16) - l.bits_per_sample, k.out_wide = wide ? 1 : 0;
+    job->file_bytes += up16((int64_t)c.nbytes + 64);
+    job->wgs += k.n_chunks, job->slots += max_frames, job->scratch += max_frames * l.max_block * l.channels;
+    job->pcm_bytes += up16(l.n_frames * l.channels * (wide ? 4 : 2));
+    if (job->wgs >= ((int64_t)1 << 31) || job->slots >= ((int64_t)1 << 31)) {
+      h->err = std::string(what) + ": the job is too large for one call (2^31 scan chunks or frame slots)";
+      return BP_ERR_INVALID_ARG;
+    }
+    job->dev[(size_t)i] = (int64_t)job->tab.size();
+    job->tab.push_back(k);
+  }
+  return BP_OK;
+}
+
+// The job's bytes to the device (zeros between and behind the clips), the four decode launches, every clip's error bits and
+// frame count on their way to h->fd_status_host; the PCM is being written to h->pcm_dev.  job.tab is not empty.
+int queue_flac_clips(bp_handle h, const bp_flac_clip* clips, const FlacJob& job) {
+  hipStream_t s = h->stream;
+  const int64_t n_dev = (int64_t)job.tab.size();
+  BP_HIP(h->fd_status_host.reserve((size_t)(2 * n_dev)));
+  BP_HIP(h->fd.file.reserve((size_t)job.file_bytes));
+  BP_HIP(h->pcm_dev.reserve((size_t)job.pcm_bytes));
+  BP_HIP(hipMemsetAsync(h->fd.file, 0, (size_t)job.file_bytes, s));
+  for (size_t i = 0; i < job.dev.size(); ++i)
+    if (job.dev[i] >= 0)
+      BP_HIP(hipMemcpyAsync(h->fd.file + job.tab[(size_t)job.dev[i]].base, clips[i].file, clips[i].nbytes, hipMemcpyHostToDevice, s));
+  if (flac_clips_decode(h->fd, job.tab.data(), n_dev, job.wgs, job.slots, job.scratch, h->pcm_dev, (size_t)job.pcm_bytes, s) != 0) {
+    h->err = "FLAC clips on the device: allocation or launch failed";
+    (void)hipGetLastError();
+    return BP_ERR_HIP;
+  }
+  BP_HIP(hipMemcpyAsync(h->fd_status_host, h->fd.meta, (size_t)(2 * n_dev) * sizeof(int), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+// the decoded clips as the PCM clips calls take them: device memory, a clip left to the host without frames
+std::vector<bp_clip> flac_pcm_clips(bp_handle h, const FlacJob& job) {
+  std::vector<bp_clip> out(job.dev.size(), bp_clip{nullptr, 0, BP_PCM_S16, 1});
+  for (size_t i = 0; i < job.dev.size(); ++i)
+    if (job.dev[i] >= 0)
+      out[i] = bp_clip{h->pcm_dev + job.tab[(size_t)job.dev[i]].pcm_off, job.lay[i].n_frames, flac_format(job.lay[i]), job.lay[i].channels};
+  return out;
+}
+
+// the host-side statuses; with `decoded` (the stream has been waited for) the decoder's verdict on every device clip too
+void flac_clips_status(bp_handle h, const FlacJob& job, bool decoded, int* status) {
+  for (size_t i = 0; i < job.dev.size(); ++i) {
+    if (job.dev[i] < 0) status[i] = BP_CLIP_FLAC_HOST;
+    else if (decoded && h->fd_status_host[2 * job.dev[i]] != 0) status[i] = BP_CLIP_FLAC_FAILED;
+  }
+}
+
 }  // namespace
 
 int bp::note_tables(bp_handle h, const void** tab, const double** gauss) {
@@ -1093,6 +1199,150 @@ int bp_infer_flac_candidates(bp_handle h, const void* file, size_t nbytes, const
                              uint8_t* cand_bits, int8_t* bend_map, int* status) {
   return run_track(h, "bp_infer_flac_candidates", Source{kFlac, file, (int64_t)nbytes},
                    Sink{kCandidates, {}, nullptr, 0, params, note_out, cand_bits, bend_map, status});
+}
+
+// ---- a job of FLAC clips (include/basic_pitch_amd_flac_clips.h) ------------------------------------------------------------------
+int bp_flac_clips_row_offsets(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int sample_rate, int64_t* offsets, int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_flac_clips_row_offsets";
+  if (!offsets || (n_clips > 0 && !status) || sample_rate < 1) {
+    h->err = std::string(what) + ": null offsets / status or no sample rate";
+    return BP_ERR_INVALID_ARG;
+  }
+  FlacJob job;
+  if (int rc = plan_flac_clips(h, what, n_clips, clips, sample_rate, &job)) return rc;
+  for (int64_t i = 0; i <= n_clips; ++i) offsets[i] = job.offs[(size_t)i];
+  for (int64_t i = 0; i < n_clips; ++i) status[i] = 0;
+  flac_clips_status(h, job, false, status);
+  return BP_OK;
+}
+
+int bp_flac_clips_decode_device(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int32_t* pcm, const int64_t* pcm_offsets,
+                                int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_flac_clips_decode_device";
+  if (!pcm_offsets || (n_clips > 0 && !status)) {
+    h->err = std::string(what) + ": null pcm_offsets / status";
+    return BP_ERR_INVALID_ARG;
+  }
+  FlacJob job;
+  if (int rc = plan_flac_clips(h, what, n_clips, clips, 0, &job)) return rc;
+  for (int64_t i = 0; i < n_clips; ++i)
+    if (job.dev[(size_t)i] >= 0 && (!pcm || pcm_offsets[i] < 0 ||
+                                    pcm_offsets[i + 1] - pcm_offsets[i] < job.lay[(size_t)i].n_frames * job.lay[(size_t)i].channels)) {
+      h->err = std::string(what) + ": clip " + std::to_string(i) + ": null pcm or too little room between its offsets";
+      return BP_ERR_INVALID_ARG;
+    }
+  for (int64_t i = 0; i < n_clips; ++i) status[i] = 0;
+  flac_clips_status(h, job, false, status);
+  if (job.tab.empty()) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  h->maps_rows = 0;  // (the PCM staging is shared with the track calls; their maps are not, but a decode is no *_candidates call)
+  if (int rc = finish(h, queue_flac_clips(h, clips, job))) return rc;
+  std::vector<uint8_t> home((size_t)job.pcm_bytes);
+  BP_HIP(hipMemcpy(home.data(), h->pcm_dev, home.size(), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n_clips; ++i) {
+    if (job.dev[(size_t)i] < 0) continue;
+    const FdClip& k = job.tab[(size_t)job.dev[(size_t)i]];
+    const int64_t n = k.st.total * k.st.channels;
+    int32_t* out = pcm + pcm_offsets[i];
+    const int sh = k.out_shift;  // left-justified on the device
+    if (k.out_wide) {
+      const int32_t* src = reinterpret_cast<const int32_t*>(home.data() + k.pcm_off);
+      for (int64_t j = 0; j < n; ++j) out[j] = src[j] >> sh;
+    } else {
+      const int16_t* src = reinterpret_cast<const int16_t*>(home.data() + k.pcm_off);
+      for (int64_t j = 0; j < n; ++j) out[j] = (int32_t)src[j] >> sh;
+    }
+  }
+  flac_clips_status(h, job, true, status);
+  return BP_OK;
+}
+
+int bp_infer_flac_clips_candidates(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int sample_rate,
+                                   const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_infer_flac_clips_candidates";
+  if (!params || (n_clips > 0 && !status) || sample_rate < 1) {
+    h->err = std::string(what) + ": null params / status or no sample rate";
+    return BP_ERR_INVALID_ARG;
+  }
+  FlacJob job;
+  if (int rc = plan_flac_clips(h, what, n_clips, clips, sample_rate, &job)) return rc;
+  const int64_t total = job.offs[(size_t)n_clips];
+  if (total > 0 && (!note_out || !cand_bits)) {
+    h->err = std::string(what) + ": null output pointer";
+    return BP_ERR_INVALID_ARG;
+  }
+  for (int64_t i = 0; i < n_clips; ++i) status[i] = 0;
+  flac_clips_status(h, job, false, status);
+  if (total == 0) return BP_OK;  // no clip has a row: nothing to queue
+  BP_HIP(hipSetDevice(h->device));
+  if (sample_rate != h->rate)
+    if (int rc = clips_filter(h, what, sample_rate)) return rc;
+  std::vector<ClipDesc> tab((size_t)n_clips);
+  std::vector<bp_clip> decoded;
+  bool exported_by_kernel = false;
+  auto queue = [&]() -> int {
+    if (int rc = queue_flac_clips(h, clips, job)) return rc;
+    decoded = flac_pcm_clips(h, job);
+    return queue_clips(h, n_clips, decoded.data(), sample_rate, BP_MEM_DEVICE, job.n_model.data(), job.offs.data(), params, note_out,
+                       cand_bits, bend_map, tab, &exported_by_kernel);
+  };
+  if (int rc = finish(h, queue())) return rc;
+  clips_status(h, n_clips, job.offs.data(), params, exported_by_kernel, status);
+  flac_clips_status(h, job, true, status);
+  return BP_OK;
+}
+
+int bp_infer_flac_clips_events(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int sample_rate, const bp_note_params* params,
+                               bp_note_event* events, int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets,
+                               int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_infer_flac_clips_events";
+  const EventsSink out{events, max_events, bends, max_bends, event_offsets, status};
+  if (int rc = check_events(h, what, n_clips, params, out)) return rc;
+  if (sample_rate < 1) {
+    h->err = std::string(what) + ": no sample rate";
+    return BP_ERR_INVALID_ARG;
+  }
+  FlacJob job;
+  if (int rc = plan_flac_clips(h, what, n_clips, clips, sample_rate, &job)) return rc;
+  if (events_without_device(n_clips, job.offs.data(), params, out)) {
+    flac_clips_status(h, job, false, status);
+    return BP_OK;
+  }
+  BP_HIP(hipSetDevice(h->device));
+  if (sample_rate != h->rate)
+    if (int rc = clips_filter(h, what, sample_rate)) return rc;
+  std::vector<ClipDesc> tab((size_t)n_clips);
+  std::vector<bp_clip> decoded;
+  Maps all{};
+  int rc = queue_flac_clips(h, clips, job);
+  if (rc == BP_OK) {
+    decoded = flac_pcm_clips(h, job);
+    rc = queue_clips_maps(h, n_clips, decoded.data(), sample_rate, BP_MEM_DEVICE, job.n_model.data(), job.offs.data(), tab, &all);
+  }
+  if ((rc = run_events(h, what, rc, all, n_clips, job.offs.data(), params, out))) {
+    flac_clips_status(h, job, false, status);  // (buffers too small: status and event_offsets are complete but for the verdicts)
+    return rc;
+  }
+  // a clip the decoder failed on has no events: the others' move up, their bends with them
+  int64_t w = 0, bw = 0;
+  for (int64_t c = 0; c < n_clips; ++c) {
+    const bool drop = job.dev[(size_t)c] >= 0 && h->fd_status_host[2 * job.dev[(size_t)c]] != 0;
+    const int64_t e0 = event_offsets[c], e1 = event_offsets[c + 1];
+    event_offsets[c] = w;
+    for (int64_t e = e0; e < e1 && !drop; ++e) {
+      bp_note_event ev = events[e];
+      if (ev.n_bends && bw != ev.bend_offset) std::memmove(bends + bw, bends + ev.bend_offset, (size_t)ev.n_bends * sizeof(int32_t));
+      ev.bend_offset = bw, bw += ev.n_bends;
+      events[w++] = ev;
+    }
+    if (c + 1 == n_clips) event_offsets[n_clips] = w;
+  }
+  flac_clips_status(h, job, true, status);
+  return BP_OK;
 }
 
 }  // extern "C"

@@ -408,6 +408,33 @@ class Model:
                                        minimum_frequency, maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo,
                                        threads, decode)
 
+    def transcribe_flac_clips(
+        self,
+        blobs: Sequence[Any],
+        onset_threshold: float = DEFAULT_ONSET_THRESHOLD,
+        frame_threshold: float = DEFAULT_FRAME_THRESHOLD,
+        minimum_note_length: float = DEFAULT_MINIMUM_NOTE_LENGTH_MS,
+        minimum_frequency: Optional[float] = None,
+        maximum_frequency: Optional[float] = None,
+        multiple_pitch_bends: bool = False,
+        melodia_trick: bool = True,
+        midi_tempo: float = DEFAULT_MINIMUM_MIDI_TEMPO,
+        threads: int = 8,
+        decode: str = "host",
+        errors: str = "raise",
+    ) -> "List[Any]":
+        """Many short FLAC files (`bytes`-like) -> [(midi_data, note_events)] in input order: `transcribe_clips` for clips
+        that are still compressed.  The clips of a STREAMINFO rate go to the device in ONE call and are decoded there
+        (`bp_infer_flac_clips_candidates`; decode="device": `bp_infer_flac_clips_events`); the events of a clip are those
+        of `transcribe_clips` on the host decoder's samples.  A clip the device decoder leaves to the host or fails on is
+        decoded by the host decoder and takes the PCM path.  A clip the host decoder cannot decode either raises ValueError
+        with its index (errors="raise") or leaves that exception at its place in the list (errors="return")."""
+        from . import flac_clips as _flac_clips
+
+        return _flac_clips.transcribe_flac_clips(self, blobs, onset_threshold, frame_threshold, minimum_note_length,
+                                                 minimum_frequency, maximum_frequency, multiple_pitch_bends, melodia_trick,
+                                                 midi_tempo, threads, decode, errors)
+
     def note_events(self, outputs: Sequence[Dict[str, Any]], prm) -> "List[Tuple[Optional[List[Any]], int]]":
         """Note events of many posteriorgram segments in one call, decoded on the device (`bp_note_events_from_maps`,
         csrc/note_track.hip): `outputs` is a list of {"note", "onset", "contour"} dicts (numpy arrays or CUDA tensors), `prm`
