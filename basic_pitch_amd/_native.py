@@ -435,6 +435,14 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     return lib
 
 
+def bind(lib: C.CDLL, prototypes: dict) -> C.CDLL:
+    """Declare `prototypes` (name -> (restype, argtypes), as a header declares them) on a loaded library."""
+    for name, (restype, argtypes) in prototypes.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return lib
+
+
 def check(lib: C.CDLL, handle, rc: int, what: str) -> None:
     """Map a negative bp_status to the exception the reference's callers would see."""
     if rc == BP_OK:

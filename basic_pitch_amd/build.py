@@ -26,6 +26,7 @@ STREAM_EVENTS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_s
 SOURCES = [
     "bp_api.hip",
     "track_api.hip",
+    "clips_api.hip",
     "stream_api.hip",
     "weight_pack.hip",
     "cqt_pyramid.hip",

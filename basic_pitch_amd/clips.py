@@ -39,10 +39,7 @@ FORMATS = {np.dtype(np.float32): _native.BP_PCM_F32, np.dtype(np.int16): _native
 
 def bind(lib: C.CDLL) -> C.CDLL:
     """Declare the prototypes of include/basic_pitch_amd_clips.h on a loaded library."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
+    return _native.bind(lib, PROTOTYPES)
 
 
 def as_clip(clip: Any, index: int) -> np.ndarray:
@@ -90,26 +87,60 @@ def clips_row_offsets(model: Any, arrays: Sequence[np.ndarray], sample_rate: int
     return offs
 
 
-def infer_clips_candidates(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, prm: Any
-                           ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
-    """One `bp_infer_clips_candidates` call for [n_frames, channels] arrays at one rate: (offsets, note (T, 88) float32,
-    onset-peak bitmap (T, 12) uint8, bend map (T, 88) int8 or None, status per clip), the rows of clip i at
+def _call(lib, handle, what: str, fn, fixed: tuple, offs: np.ndarray, prm: Any
+          ) -> Tuple[np.ndarray, np.ndarray, np.ndarray, Optional[np.ndarray], np.ndarray]:
+    """`fn(*fixed, prm, note_out, cand_bits, bend_map, status)` with the outputs the row offsets ask for: (offsets, note (T, 88)
+    float32, onset-peak bitmap (T, 12) uint8, bend map (T, 88) int8 or None, status per clip), the rows of clip i at
     offsets[i]:offsets[i + 1]."""
-    lib = bind(model._lib)
-    tab = clip_table(arrays)
-    offs = np.zeros(len(arrays) + 1, np.int64)
-    rc = lib.bp_clips_row_offsets(model._handle, len(arrays), tab, int(sample_rate), offs.ctypes.data_as(_pi64))
-    _native.check(lib, model._handle, rc, "bp_clips_row_offsets")
-    T = int(offs[-1])
+    n, T = len(offs) - 1, int(offs[-1])
     note = np.empty((T, 88), np.float32)
     bits = np.empty((T, 12), np.uint8)
     bend = np.empty((T, 88), np.int8) if prm.include_pitch_bends else None
-    status = np.zeros(max(1, len(arrays)), np.int32)
-    rc = lib.bp_infer_clips_candidates(model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST, C.addressof(prm),
-                                       note.ctypes.data, bits.ctypes.data, bend.ctypes.data if bend is not None else None,
-                                       status.ctypes.data)
-    _native.check(lib, model._handle, rc, "bp_infer_clips_candidates")
-    return offs, note, bits, bend, status[: len(arrays)]
+    status = np.zeros(max(1, n), np.int32)
+    rc = fn(*fixed, C.addressof(prm), note.ctypes.data, bits.ctypes.data, bend.ctypes.data if bend is not None else None,
+            status.ctypes.data)
+    _native.check(lib, handle, rc, what)
+    return offs, note, bits, bend, status[:n]
+
+
+def infer_clips_candidates(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, prm: Any):
+    """One `bp_infer_clips_candidates` call for [n_frames, channels] arrays at one rate: as `_call` returns."""
+    lib = bind(model._lib)
+    fixed = (model._handle, len(arrays), clip_table(arrays), int(sample_rate), _native.BP_MEM_HOST)
+    return _call(lib, model._handle, "bp_infer_clips_candidates", lib.bp_infer_clips_candidates, fixed,
+                 clips_row_offsets(model, arrays, sample_rate), prm)
+
+
+def transcribe_groups(groups, candidates, events, fallback, results: List[Any], prm: Any, decode: str, multiple_pitch_bends: bool,
+                      midi_tempo: float, threads: int) -> None:
+    """The loop over the rate groups of a job, `groups` = [(rate, the indices of its clips)]: one native call per group —
+    `events(ids, rate)` for decode="device", else `candidates(ids, rate)` — then per clip either `fallback(i)` (a status: on
+    this thread, between the native calls, as it may use the handle), or the device's events straight to MIDI, or the
+    sequential half of note decoding on a thread pool (the native decoder releases the GIL).  Fills results[i]."""
+    from . import events as _events
+
+    def decoded(note, bits, bend):
+        ev = _notes.decode_candidates(note, bits, bend, prm)
+        return _notes.note_events_to_midi(ev, multiple_pitch_bends, midi_tempo), ev
+
+    with ThreadPoolExecutor(max_workers=max(1, int(threads))) as pool:
+        pending = []
+        for rate, ids in groups:
+            if decode == "device":
+                evs, bends, ev_offs, status = events(ids, rate)
+            else:
+                offs, note, bits, bend, status = candidates(ids, rate)
+            for k, i in enumerate(ids):
+                if status[k]:  # 1: a NaN, or an onset threshold <= 0; 2: the clip passed its region's capacity; 3, 4: FLAC
+                    fallback(i)
+                elif decode == "device":
+                    ev = _events.clip_events(evs, bends, ev_offs, k, True)
+                    results[i] = (_notes.note_events_to_midi(ev, multiple_pitch_bends, midi_tempo), ev)
+                else:
+                    r0, r1 = int(offs[k]), int(offs[k + 1])
+                    pending.append((i, pool.submit(decoded, note[r0:r1], bits[r0:r1], bend[r0:r1] if bend is not None else None)))
+        for i, fut in pending:
+            results[i] = fut.result()
 
 
 def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], onset_threshold: float,
@@ -135,40 +166,15 @@ def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, 
     results: List[Any] = [None] * len(arrays)
 
     def host_decoded(i: int):
-        a = arrays[i]  # status 1 (a NaN, or an onset threshold <= 0): the maps themselves decide, as predict does
+        a = arrays[i]  # a status: the maps themselves decide, as predict does
         out = model.predict_pcm_raw(a, FORMATS[a.dtype], a.shape[0], a.shape[1], rates[i])
-        return _inf._output_to_notes(out, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency,
-                                     maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo)
+        results[i] = _inf._output_to_notes(out, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency,
+                                           maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo)
 
-    def decoded(note, bits, bend):
-        events = _notes.decode_candidates(note, bits, bend, prm)
-        return _notes.note_events_to_midi(events, multiple_pitch_bends, midi_tempo), events
+    from . import events as _events
 
-    if decode == "device":
-        from . import events as _events
-
-        for rate in dict.fromkeys(rates):  # the rates in order of first appearance
-            ids = [i for i, r in enumerate(rates) if r == rate]
-            events, bends, ev_offs, status = _events.infer_clips_events(model, [arrays[i] for i in ids], rate, prm)
-            for k, i in enumerate(ids):
-                if status[k]:  # 1 as below; 2: the clip passed its region's capacity
-                    results[i] = host_decoded(i)
-                    continue
-                ev = _events.clip_events(events, bends, ev_offs, k, True)
-                results[i] = (_notes.note_events_to_midi(ev, multiple_pitch_bends, midi_tempo), ev)
-        return results
-
-    with ThreadPoolExecutor(max_workers=max(1, int(threads))) as pool:
-        pending = []
-        for rate in dict.fromkeys(rates):  # the rates in order of first appearance
-            ids = [i for i, r in enumerate(rates) if r == rate]
-            offs, note, bits, bend, status = infer_clips_candidates(model, [arrays[i] for i in ids], rate, prm)
-            for k, i in enumerate(ids):
-                if status[k]:
-                    results[i] = host_decoded(i)  # uses the handle: on this thread, between the native calls
-                    continue
-                r0, r1 = int(offs[k]), int(offs[k + 1])
-                pending.append((i, pool.submit(decoded, note[r0:r1], bits[r0:r1], bend[r0:r1] if bend is not None else None)))
-        for i, fut in pending:
-            results[i] = fut.result()
+    groups = [(rate, [i for i, r in enumerate(rates) if r == rate]) for rate in dict.fromkeys(rates)]  # by first appearance
+    transcribe_groups(groups, lambda ids, rate: infer_clips_candidates(model, [arrays[i] for i in ids], rate, prm),
+                      lambda ids, rate: _events.infer_clips_events(model, [arrays[i] for i in ids], rate, prm),
+                      host_decoded, results, prm, decode, multiple_pitch_bends, midi_tempo, threads)
     return results

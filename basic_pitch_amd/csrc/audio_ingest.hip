@@ -359,7 +359,7 @@ void launch_resample(const float* x, int64_t n_in, const double* taps, const Res
     hipLaunchKernelGGL(resample_poly_kernel, per_output, dim3(256), 0, stream, x, n_in, taps, pl, y, n_out);
 }
 
-// ---- batched ingest (bp_infer_clips_candidates, track_api.hip): many short clips, one downmix launch and one resampling launch
+// ---- batched ingest (bp_infer_clips_candidates, clips_api.hip): many short clips, one downmix launch and one resampling launch
 // for all of them.  The table of clips (bp_kernels.h ClipDesc) is in device memory; a workgroup finds its clip by binary search
 // over the clips' first workgroups and works on that clip alone, so everything about the clip is workgroup-uniform.
 template <int64_t ClipDesc::*kFirst>

@@ -1,7 +1,8 @@
-// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip, stream_api.hip and weight_pack.hip share
-// of it — the HIP error macro, the chunk / wait helpers (defined in bp_api.hip), and the maps, filter and argument
-// helpers of the track calls and the streaming sessions (defined in track_api.hip).  The handle's memory is owned by the
-// buffers of device_buffer.h: deleting the handle frees it.
+// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip, clips_api.hip, stream_api.hip and
+// weight_pack.hip share of it — the HIP error macro, the chunk / wait helpers (defined in bp_api.hip), the maps, filter,
+// argument and candidates helpers of the track calls, the clip jobs and the streaming sessions (defined in track_api.hip), and
+// the tracker's host half (defined in clips_api.hip).  The handle's memory is owned by the buffers of device_buffer.h:
+// deleting the handle frees it.
 #pragma once
 #include "../../include/basic_pitch_amd.h"
 
@@ -72,7 +73,7 @@ struct bp_context {
   bp::PinnedBuffer<int> nd_stats_host;   // copy of the stats record (4 words; [1]: a NaN was seen)
   void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
   bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
-  // many clips in one call (bp_infer_clips_candidates, track_api.hip), all grow-only: the table of clips, the clips' row
+  // many clips in one call (bp_infer_clips_candidates, clips_api.hip), all grow-only: the table of clips, the clips' row
   // offsets, one stats record of 16 bytes per clip and the page-locked copy of the records (4 words per clip)
   Buffer<bp::ClipDesc> clip_tab;
   Buffer<int64_t> clip_rows;
@@ -164,8 +165,27 @@ int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcp
 // the handle's tables of the device-side note candidates (note_device.hip), made on first use: the bend windows and the
 // Gaussian on the device, the page-locked copy of the stats record
 int note_tables(bp_handle h, const void** tab, const double** gauss);
+constexpr size_t kTabBytes = 88 * 16, kGaussBytes = 51 * 8, kStatsBytes = 16;  // of nd_tables; a stats record
+// track_api.hip, for the jobs of many clips (clips_api.hip).  The geometry of a handle: the length of a signal resampled to
+// `rate`, the rows of the maps of n samples at the handle's rate
+int64_t resampled_length(int64_t n_frames, int sample_rate, int rate);
+int64_t h_frames(bp_handle h, int64_t n);
+// the only way to h->track_out, grown for `rows` rows of maps (h->maps_rows = 0); the same with a private copy of given maps
+int take_track_out(bp_handle h, int64_t rows, Maps* m);
+int take_given_maps(bp_handle h, const float* note, const float* onset, const float* contour, int64_t T, int mem_kind, Maps* m);
+// the PCM format the device FLAC decoders write (left-justified), and n such samples as int32 (src may be out)
+int flac_format(const bp_flac_stream_layout& lay);
+void flac_pcm_to_int32(const void* src, bool wide, int shift, int64_t n, int32_t* out);
+// windows of device-resident signals at the handle's rate -> their un-overlapped maps, packed into full chunks
+int tracks_core(bp_handle h, int64_t n_tracks, const float* const* d_in, const int64_t* n_samples, const Maps* d_out);
+// room for the bitmap and the bends of T rows in h->nd_buf; the candidates of T rows and n_stats records on their way home
+int reserve_candidates(bp_handle h, int64_t T, uint8_t** d_bits, int8_t** d_bend);
+int send_candidates(bp_handle h, const float* d_note, int64_t T, const uint8_t* d_bits, const int8_t* d_bend, float* note_out,
+                    uint8_t* cand_out, int8_t* bend_out, void* d_stats, int* stats_host, void* stats_host_dev, int64_t n_stats,
+                    bool* exported_by_kernel);
 
-// ---- the tracker (note_track.hip) behind any dense half: the clips calls (track_api.hip), bp_streams_events (stream_api.hip).
+// ---- the tracker (note_track.hip) behind any dense half, its host half in clips_api.hip: the clips calls there,
+// bp_streams_events (stream_api.hip).
 // Where a call's results go:
 struct EventsSink {
   bp_note_event* events;

@@ -1,0 +1,701 @@
+// C ABI of the jobs of many clips (include/basic_pitch_amd_clips.h, _events.h, _flac_clips.h): many short clips through the
+// model in one call — raw PCM, FLAC files' bytes decoded on the device, or maps the caller already holds — and home either
+// the note candidates of every clip or, the tracker run on the device too, the note events alone.
+//
+// Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
+//   the sink's fixed arguments -> the source's plan (rows of every clip) -> the outputs against the rows -> statuses and the
+//   exits without device work -> the filter -> queue the source, the dense half, the sink -> wait -> statuses / events home ->
+//   the FLAC decoder's verdicts.
+// Nothing is queued before every argument has been checked, a call that fails after queuing work returns only once the
+// handle's stream has drained (finish), and every host buffer an asynchronous copy reads is a member of the driver's ClipsJob,
+// which outlives the wait.  The tracker's host half (events_reserve / events_queue / events_home) lives here too:
+// bp_streams_events (stream_api.hip) puts it behind its own dense half.
+#include <algorithm>
+#include <cstring>
+
+#include "../../include/basic_pitch_amd_flac_clips.h"
+#include "bp_context.h"
+
+using namespace bp;
+
+extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);
+extern "C" double bp_internal_frame_time(int64_t frame);
+extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
+
+namespace bp {
+
+// ---- the tracker behind any dense half (declared in bp_context.h): the clips calls here, bp_streams_events in stream_api.hip
+static bool seg_bends(const EventsJob& job, int64_t c) {
+  return job.seg ? job.seg[c].bends != 0 : job.prm->include_pitch_bends != 0;
+}
+
+int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan) {
+  const int64_t n = job.n, T = job.offs[n];
+  plan->ev_first.assign((size_t)n + 1, 0);
+  plan->max_rows = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t rows = job.offs[i + 1] - job.offs[i];
+    plan->ev_first[(size_t)i + 1] =
+        plan->ev_first[(size_t)i] + note_track_capacity(rows, job.seg ? job.seg[i].min_note_len : job.prm->min_note_len);
+    plan->max_rows = std::max(plan->max_rows, rows);
+  }
+  const int64_t pool_events = plan->ev_first[(size_t)n], n_meta = 3 * n + 2;
+  const bool scratch = plan->max_rows > kNoteTrackLdsRows || job.form == kNoteTrackFormScratch;
+  BP_HIP(h->ev_first.reserve((size_t)n + 1));
+  BP_HIP(h->ev_meta.reserve((size_t)n_meta));
+  BP_HIP(h->ev_counts.reserve((size_t)n * 16));
+  BP_HIP(h->ev_pool.reserve((size_t)pool_events * 16));
+  BP_HIP(h->ev_out.reserve((size_t)pool_events * 16));
+  BP_HIP(h->bd_pool.reserve((size_t)T * 88));
+  BP_HIP(h->bd_out.reserve((size_t)T * 88));
+  if (scratch) BP_HIP(h->ev_scratch.reserve((size_t)note_track_scratch_floats(T)));
+  if (job.seg) BP_HIP(h->ev_seg.reserve((size_t)n * sizeof(NoteTrackSeg)));
+  BP_HIP(h->ev_home.reserve((size_t)n_meta));  // page-locked: the offsets and status come home first
+  return BP_OK;
+}
+
+int events_queue(bp_handle h, const EventsJob& job, const EventsPlan& plan, const TrackInputs& in) {
+  hipStream_t s = h->stream;
+  const int64_t n = job.n;
+  BP_HIP(hipMemcpyAsync(h->ev_first, plan.ev_first.data(), (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  if (job.seg) {
+    BP_HIP(hipMemcpyAsync(h->ev_seg, job.seg, (size_t)n * sizeof(NoteTrackSeg), hipMemcpyHostToDevice, s));
+    BP_HIP(launch_note_track_segs(in.note, in.bits, in.bend, in.offs, h->ev_first, in.stats, h->ev_seg.as<NoteTrackSeg>(), n,
+                                  plan.max_rows, job.form, h->ev_scratch, h->ev_pool, h->bd_pool, h->ev_counts, h->ev_meta, h->ev_out,
+                                  h->bd_out, s));
+  } else {
+    const bp_note_params* prm = job.prm;
+    BP_HIP(launch_note_track(in.note, in.bits, in.bend, in.offs, h->ev_first, in.stats, n, plan.max_rows, prm->frame_threshold,
+                             prm->energy_tol, prm->min_note_len, prm->melodia_trick != 0, h->ev_scratch, h->ev_pool, h->bd_pool,
+                             h->ev_counts, h->ev_meta, h->ev_out, h->bd_out, s));
+  }
+  BP_HIP(hipMemcpyAsync(h->ev_home, h->ev_meta, (size_t)(3 * n + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+int events_home(bp_handle h, const EventsJob& job, const EventsSink& out, bool* device_error) {
+  hipStream_t s = h->stream;
+  const int64_t n = job.n, n_meta = 3 * n + 2;
+  const int64_t* meta = h->ev_home;
+  const int64_t n_events = meta[n], n_bends = meta[2 * n + 1];
+  for (int64_t i = 0; i <= n; ++i) out.event_offsets[i] = meta[i];
+  for (int64_t i = 0; i < n; ++i) out.status[i] = (int)meta[2 * n + 2 + i];
+  if (n_events > out.max_events || n_bends > out.max_bends) {
+    h->err = std::string(job.what) + ": output buffers too small: " + std::to_string(n_events) + " events and " +
+             std::to_string(n_bends) + " bends are needed (event_offsets[" + job.count_name + "] holds the events)";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (n_events == 0) return BP_OK;
+  struct Raw {
+    int32_t start, end, pitch;
+    float amp;
+  };
+  Raw* raw = nullptr;
+  int8_t* raw_bends = nullptr;
+  auto home = [&]() -> int {
+    // the stream has drained and the offsets are out of the block: it may grow for the events and, behind them, the bends
+    BP_HIP(h->ev_home.reserve((size_t)std::max(n_meta, 2 * n_events + (n_bends + 7) / 8)));
+    raw = reinterpret_cast<Raw*>(static_cast<int64_t*>(h->ev_home));
+    raw_bends = reinterpret_cast<int8_t*>(raw + n_events);
+    BP_HIP(hipMemcpyAsync(raw, h->ev_out, (size_t)n_events * sizeof(Raw), hipMemcpyDeviceToHost, s));
+    if (n_bends) BP_HIP(hipMemcpyAsync(raw_bends, h->bd_out, (size_t)n_bends, hipMemcpyDeviceToHost, s));
+    return BP_OK;
+  };
+  if (int rc = finish(h, home())) {
+    if (device_error) *device_error = true;
+    return rc;
+  }
+  for (int64_t i = 0; i < n_bends; ++i) out.bends[i] = (int32_t)raw_bends[i];
+  int64_t bo = 0;
+  for (int64_t c = 0; c < n; ++c) {
+    const int64_t first = job.first_frame ? job.first_frame[c] : 0;
+    const bool want_bends = seg_bends(job, c);
+    for (int64_t e = out.event_offsets[c]; e < out.event_offsets[c + 1]; ++e) {
+      const Raw& r = raw[e];
+      bp_note_event& ev = out.events[e];
+      std::memset(&ev, 0, sizeof ev);  // reserved fields and padding
+      ev.start_frame = (int32_t)(first + r.start), ev.end_frame = (int32_t)(first + r.end);
+      ev.start_s = bp_internal_frame_time(first + r.start), ev.end_s = bp_internal_frame_time(first + r.end);
+      ev.pitch_midi = r.pitch;
+      ev.amplitude = r.amp;
+      ev.bend_offset = bo;
+      ev.n_bends = want_bends ? r.end - r.start : 0;
+      bo += ev.n_bends;
+    }
+  }
+  return BP_OK;
+}
+
+}  // namespace bp
+
+namespace {
+
+int invalid(bp_handle h, const char* what, const std::string& why) {
+  h->err = std::string(what) + ": " + why;
+  return BP_ERR_INVALID_ARG;
+}
+
+// The candidates of the maps of n_clips clips that lie one after the other in m, clip c at rows [offs[c], offs[c + 1]) of
+// offs[n_clips] = T > 0 rows, each clip decoded as its own whole track.  offs (host) must stay as it is until the stream has
+// been waited for.  The device half: *d_bits / *d_bend (null without want_bends) are where the bitmap and the bends of all
+// rows lie, the clips' records are in h->clip_stats and their row offsets in h->clip_rows; nothing goes home.
+int queue_clips_dense(bp_handle h, const Maps& m, int64_t n_clips, const int64_t* offs, const bp_note_params* prm, bool want_bends,
+                      uint8_t** d_bits_out, int8_t** d_bend_out) {
+  hipStream_t s = h->stream;
+  const int64_t T = offs[n_clips];
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  if (int rc = note_tables(h, &tab, &gauss)) return rc;
+  uint8_t* d_bits = nullptr;
+  int8_t* d_bend = nullptr;
+  if (int rc = reserve_candidates(h, T, &d_bits, &d_bend)) return rc;
+  if ((size_t)n_clips * kStatsBytes > h->clip_stats.capacity()) h->clip_stats_ready = 0;  // a new block: nothing initialised
+  BP_HIP(h->clip_stats.reserve((size_t)n_clips * kStatsBytes));
+  BP_HIP(h->clip_rows.reserve((size_t)n_clips + 1));
+  BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n_clips + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  int lo = 0, hi = 88;
+  bp_internal_freq_limits(prm, &lo, &hi);
+  if (h->clip_stats_ready < n_clips) launch_clips_stats_init(h->clip_stats, n_clips, s);
+  h->clip_stats_ready = 0;
+  launch_clips_candidates(m.note, m.onset, m.contour, h->clip_rows, n_clips, T, lo, hi, prm->infer_onsets != 0,
+                          prm->onset_threshold, tab, gauss, h->clip_stats, d_bits, want_bends ? d_bend : nullptr, s);
+  BP_HIP(hipGetLastError());
+  *d_bits_out = d_bits;
+  *d_bend_out = want_bends ? d_bend : nullptr;
+  return BP_OK;
+}
+
+// ... and home: the note rows, the bitmap and the bends to host buffers, clip c's record as h->clip_stats_host[4 c ...]
+int queue_clips_candidates(bp_handle h, const Maps& m, int64_t n_clips, const int64_t* offs, const bp_note_params* prm,
+                           float* note_out, uint8_t* cand_out, int8_t* bend_out, bool* exported_by_kernel) {
+  uint8_t* d_bits = nullptr;
+  int8_t* d_bend = nullptr;
+  // the page-locked copy of the records, before anything is queued
+  BP_HIP(h->clip_stats_host.reserve((size_t)n_clips * (kStatsBytes / sizeof(int))));
+  void* stats_host_dev = nullptr;
+  BP_HIP(hipHostGetDevicePointer(&stats_host_dev, h->clip_stats_host, 0));
+  if (int rc = queue_clips_dense(h, m, n_clips, offs, prm, prm->include_pitch_bends != 0 && bend_out != nullptr, &d_bits, &d_bend))
+    return rc;
+  return send_candidates(h, m.note, offs[n_clips], d_bits, d_bend, note_out, cand_out, bend_out, h->clip_stats, h->clip_stats_host,
+                         stats_host_dev, n_clips, exported_by_kernel);
+}
+
+// ---- many clips in one call (include/basic_pitch_amd_clips.h) -------------------------------------------------------------
+// Every argument of every clip (check_ingest; with_pcm: the samples are needed too), before anything is queued: n_model[i] =
+// clip i's samples at the handle's rate, offsets[i] = the rows of the clips before it, offsets[n_clips] = all rows.
+int check_clips(bp_handle h, const char* what, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, bool with_pcm,
+                int64_t* n_model, int64_t* offsets) {
+  if (n_clips < 0 || (n_clips > 0 && !clips) || !offsets) return invalid(h, what, "negative n_clips, null clips or null offsets");
+  offsets[0] = 0;
+  for (int64_t i = 0; i < n_clips; ++i) {
+    const bp_clip& c = clips[i];
+    if (int rc = check_ingest(h, !with_pcm || c.pcm != nullptr, c.format, c.n_frames, c.channels, sample_rate, mem_kind)) {
+      h->err = std::string(what) + ": clip " + std::to_string(i) + ": " + h->err;
+      return rc;
+    }
+    const int64_t n = resampled_length(c.n_frames, sample_rate, h->rate);
+    if (n_model) n_model[i] = n;
+    offsets[i + 1] = offsets[i] + h_frames(h, n);
+  }
+  return BP_OK;
+}
+
+// The handle's cached filter becomes that of sample_rate (queue_ingest's cache); a ratio whose taps the one-shot path
+// evaluates in the kernel is refused and leaves the cache as it was.  Nothing is queued: the table goes up with a plain copy.
+int clips_filter(bp_handle h, const char* what, int sample_rate) {
+  if (h->taps_rate != sample_rate) {
+    ResamplePlan pl{};
+    DeviceBuffer<double> dev;
+    const int rc = upload_filter(h, sample_rate, true, &pl, &dev);
+    if (rc != BP_OK && rc != BP_ERR_UNSUPPORTED) return rc;
+    if (rc == BP_OK) {
+      h->taps_rate = 0;
+      h->taps_dev = std::move(dev);
+      h->plan = pl;
+      h->taps_rate = sample_rate;
+      return BP_OK;
+    }
+  } else if (!h->plan.direct) {
+    return BP_OK;
+  }
+  h->err = std::string(what) + ": " + std::to_string(sample_rate) + " Hz -> " + std::to_string(h->rate) +
+           " Hz needs a filter whose taps the one-shot calls evaluate in the kernel; such ratios are not taken in batches";
+  return BP_ERR_UNSUPPORTED;
+}
+
+// Batched ingest: the clips' PCM to the device (host clips one after the other in h->pcm_dev), ONE downmix launch and ONE
+// resampling launch for all of them; d_in[i] = clip i's signal at the handle's rate (n_model[i] samples).  `tab` (n_clips
+// records, filled here) must stay as it is until the stream has been waited for.
+int queue_clips_ingest(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
+                       ClipDesc* tab, const float** d_in) {
+  hipStream_t s = h->stream;
+  auto up = [](int64_t v, int64_t a) { return (v + a - 1) / a * a; };
+  // offsets of every clip in the three staging buffers (bytes of PCM 16-byte aligned; floats 4-float aligned)
+  int64_t pcm_bytes = 0, mono_floats = 0, out_floats = 0, mono_blocks = 0, out_blocks = 0;
+  std::vector<int64_t> pcm_off(n_clips), mono_off(n_clips, -1), out_off(n_clips, -1);
+  for (int64_t i = 0; i < n_clips; ++i) {
+    const bp_clip& c = clips[i];
+    if (c.n_frames == 0) continue;
+    pcm_off[i] = pcm_bytes;
+    if (mem_kind == BP_MEM_HOST) pcm_bytes += up(c.n_frames * c.channels * pcm_width(c.format), 16);
+    if (c.channels > 1 || c.format != BP_PCM_F32) mono_off[i] = mono_floats, mono_floats += up(c.n_frames, 4);
+    if (sample_rate != h->rate) out_off[i] = out_floats, out_floats += up(n_model[i], 4);
+  }
+  if (pcm_bytes) BP_HIP(h->pcm_dev.reserve((size_t)pcm_bytes));
+  if (mono_floats) BP_HIP(h->mono_dev.reserve((size_t)mono_floats));
+  if (out_floats) BP_HIP(h->res_dev.reserve((size_t)out_floats));
+  BP_HIP(h->clip_tab.reserve((size_t)n_clips));
+  for (int64_t i = 0; i < n_clips; ++i) {
+    const bp_clip& c = clips[i];
+    ClipDesc& d = tab[i];
+    d = ClipDesc{nullptr, nullptr, nullptr, c.n_frames, n_model[i], mono_blocks, out_blocks, c.format, c.channels};
+    d_in[i] = nullptr;
+    if (c.n_frames == 0) continue;
+    d.src = c.pcm;
+    if (mem_kind == BP_MEM_HOST) {
+      d.src = h->pcm_dev + pcm_off[i];
+      BP_HIP(hipMemcpyAsync(h->pcm_dev + pcm_off[i], c.pcm, (size_t)(c.n_frames * c.channels * pcm_width(c.format)),
+                            hipMemcpyHostToDevice, s));
+    }
+    d.mono = static_cast<const float*>(d.src);
+    if (mono_off[i] >= 0) d.mono = h->mono_dev + mono_off[i], mono_blocks += (c.n_frames + 1023) / 1024;
+    d.out = const_cast<float*>(d.mono);  // already at the handle's rate: windowed where it lies, never written
+    if (out_off[i] >= 0) d.out = h->res_dev + out_off[i], out_blocks += (n_model[i] + 255) / 256;
+    d_in[i] = d.out;
+  }
+  if (mono_blocks + out_blocks == 0) return BP_OK;
+  BP_HIP(hipMemcpyAsync(h->clip_tab, tab, (size_t)n_clips * sizeof(ClipDesc), hipMemcpyHostToDevice, s));
+  launch_clips_downmix(h->clip_tab, n_clips, mono_blocks, s);
+  launch_clips_resample(h->clip_tab, n_clips, out_blocks, h->taps_dev, h->plan, s);
+  BP_HIP(hipGetLastError());
+  return BP_OK;
+}
+
+// The ingest and the model on the clips' windows packed into full chunks: the maps to h->track_out (*all_out), concatenated by
+// offs.  offs[n_clips] > 0.
+int queue_clips_maps(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int mem_kind, const int64_t* n_model,
+                     const int64_t* offs, std::vector<ClipDesc>& tab, Maps* all_out) {
+  std::vector<const float*> d_in(n_clips);
+  std::vector<Maps> d_out(n_clips);
+  Maps all;
+  int rc = BP_OK;
+  if ((rc = take_track_out(h, offs[n_clips], &all)) ||
+      (rc = queue_clips_ingest(h, n_clips, clips, sample_rate, mem_kind, n_model, tab.data(), d_in.data())))
+    return rc;
+  for (int64_t i = 0; i < n_clips; ++i)
+    d_out[i] = Maps{all.note + offs[i] * kFreqN, all.onset + offs[i] * kFreqN, all.contour + offs[i] * kFreqC};
+  *all_out = all;
+  return tracks_core(h, n_clips, d_in.data(), n_model, d_out.data());
+}
+
+// ---- note events of many clips (include/basic_pitch_amd_events.h)
+// every argument that is not a clip's, before anything is queued
+int check_events(bp_handle h, const char* what, int64_t n_clips, const bp_note_params* prm, const EventsSink& out) {
+  auto invalid = [&](const char* why) { return ::invalid(h, what, why); };
+  if (n_clips < 0 || !prm || !out.event_offsets || (n_clips > 0 && !out.status)) return invalid("negative n_clips, null params, event_offsets or status");
+  if (out.max_events < 0 || out.max_bends < 0 || (out.max_events > 0 && !out.events) || (out.max_bends > 0 && !out.bends))
+    return invalid("negative max_events / max_bends, or room without a buffer");
+  if (prm->melodia_trick && prm->frame_threshold < 0.0)
+    return invalid("a negative frame threshold with the melodia trick never terminates (note_creation.py:452)");
+  if (prm->min_note_len < 0) return invalid("negative min_note_len");
+  return BP_OK;
+}
+
+// The jobs that need no device work: no rows at all, or an onset threshold <= 0 (status 1 for every clip that has rows, as
+// bp_infer_clips_candidates reports it).  True: the outputs are complete.
+bool events_without_device(int64_t n_clips, const int64_t* offs, const bp_note_params* prm, const EventsSink& out) {
+  if (offs[n_clips] > 0 && prm->onset_threshold > 0.0) return false;
+  for (int64_t i = 0; i < n_clips; ++i) out.status[i] = offs[i + 1] > offs[i] ? 1 : 0;
+  for (int64_t i = 0; i <= n_clips; ++i) out.event_offsets[i] = 0;
+  return true;
+}
+
+// ---- a job of FLAC clips decoded on the device (include/basic_pitch_amd_flac_clips.h; flac_clips.hip) -------------
+// What the host knows of a job before anything is queued: every clip's layout, which clips are left to the host, the rows, and
+// where each device clip lies in the job's buffers (the table flac_clips_decode uploads).
+struct FlacJob {
+  std::vector<bp_flac_stream_layout> lay;
+  std::vector<int64_t> dev;            // clip -> its record of `tab`; -1: left to the host
+  std::vector<int64_t> n_model, offs;  // samples at the handle's rate; rows before each clip
+  std::vector<FdClip> tab;
+  int64_t file_bytes = 0, wgs = 0, slots = 0, scratch = 0, pcm_bytes = 0;
+};
+
+// sample_rate 0: no rate to agree with and no rows (bp_flac_clips_decode_device)
+int plan_flac_clips(bp_handle h, const char* what, int64_t n, const bp_flac_clip* clips, int sample_rate, FlacJob* job) {
+  if (n < 0 || (n > 0 && !clips)) return invalid(h, what, "negative n_clips or null clips");
+  auto up16 = [](int64_t v) { return (v + 15) / 16 * 16; };
+  job->lay.assign((size_t)n, bp_flac_stream_layout{});
+  job->dev.assign((size_t)n, -1);
+  job->n_model.assign((size_t)n, 0);
+  job->offs.assign((size_t)n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    const bp_flac_clip& c = clips[i];
+    bp_flac_stream_layout& l = job->lay[(size_t)i];
+    job->offs[(size_t)i + 1] = job->offs[(size_t)i];
+    if (!c.file && c.nbytes) return invalid(h, what, "clip " + std::to_string(i) + ": null file");
+    if (c.nbytes < 42 || bp_flac_layout(c.file, c.nbytes, &l) != BP_OK) continue;
+    if (sample_rate && l.sample_rate != sample_rate)
+      return invalid(h, what, "clip " + std::to_string(i) + ": its STREAMINFO says " + std::to_string(l.sample_rate) + " Hz, the call " +
+                                  std::to_string(sample_rate) + " Hz (one rate per call)");
+    if (!bp_internal_flac_device_supported(&l, c.nbytes) || (size_t)l.audio_start >= c.nbytes) continue;
+    // scratch is bounded before anything is allocated: a row of max_block samples per frame SLOT, min_block samples a slot
+    const int64_t max_frames = (l.n_frames + l.min_block - 1) / l.min_block + 1;
+    if (max_frames * l.max_block > 8 * l.n_frames + 2 * (int64_t)l.max_block) continue;
+    if (sample_rate) {
+      if (int rc = check_ingest(h, true, flac_format(l), l.n_frames, l.channels, sample_rate, BP_MEM_DEVICE)) {
+        h->err = std::string(what) + ": clip " + std::to_string(i) + ": " + h->err;
+        return rc;
+      }
+      job->n_model[(size_t)i] = resampled_length(l.n_frames, sample_rate, h->rate);
+      job->offs[(size_t)i + 1] += h_frames(h, job->n_model[(size_t)i]);
+    }
+    const bool wide = flac_format(l) == BP_PCM_S32;
+    FdClip k{};
+    k.st = FdStream{l.channels, l.bits_per_sample, l.min_block, l.max_block, l.n_frames, (uint32_t)l.audio_start, (uint32_t)c.nbytes};
+    k.base = (uint64_t)job->file_bytes, k.first_wg = (uint32_t)job->wgs, k.first_slot = (uint32_t)job->slots;
+    k.n_chunks = (int32_t)((c.nbytes - (size_t)l.audio_start + kFdChunkBytes - 1) / kFdChunkBytes), k.max_frames = (int32_t)max_frames;
+    k.scratch_off = (uint64_t)job->scratch, k.pcm_off = (uint64_t)job->pcm_bytes;
+    k.out_shift = (wide ? 32 : 16) - l.bits_per_sample, k.out_wide = wide ? 1 : 0;
+    job->file_bytes += up16((int64_t)c.nbytes + 64);
+    job->wgs += k.n_chunks, job->slots += max_frames, job->scratch += max_frames * l.max_block * l.channels;
+    job->pcm_bytes += up16(l.n_frames * l.channels * (wide ? 4 : 2));
+    if (job->wgs >= ((int64_t)1 << 31) || job->slots >= ((int64_t)1 << 31))
+      return invalid(h, what, "the job is too large for one call (2^31 scan chunks or frame slots)");
+    job->dev[(size_t)i] = (int64_t)job->tab.size();
+    job->tab.push_back(k);
+  }
+  return BP_OK;
+}
+
+// The job's bytes to the device (zeros between and behind the clips), the four decode launches, every clip's error bits and
+// frame count on their way to h->fd_status_host; the PCM is being written to h->pcm_dev.  job.tab is not empty.
+int queue_flac_clips(bp_handle h, const bp_flac_clip* clips, const FlacJob& job) {
+  hipStream_t s = h->stream;
+  const int64_t n_dev = (int64_t)job.tab.size();
+  BP_HIP(h->fd_status_host.reserve((size_t)(2 * n_dev)));
+  BP_HIP(h->fd.file.reserve((size_t)job.file_bytes));
+  BP_HIP(h->pcm_dev.reserve((size_t)job.pcm_bytes));
+  BP_HIP(hipMemsetAsync(h->fd.file, 0, (size_t)job.file_bytes, s));
+  for (size_t i = 0; i < job.dev.size(); ++i)
+    if (job.dev[i] >= 0)
+      BP_HIP(hipMemcpyAsync(h->fd.file + job.tab[(size_t)job.dev[i]].base, clips[i].file, clips[i].nbytes, hipMemcpyHostToDevice, s));
+  if (flac_clips_decode(h->fd, job.tab.data(), n_dev, job.wgs, job.slots, job.scratch, h->pcm_dev, (size_t)job.pcm_bytes, s) != 0) {
+    h->err = "FLAC clips on the device: allocation or launch failed";
+    (void)hipGetLastError();
+    return BP_ERR_HIP;
+  }
+  BP_HIP(hipMemcpyAsync(h->fd_status_host, h->fd.meta, (size_t)(2 * n_dev) * sizeof(int), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+// the host-side statuses; with `decoded` (the stream has been waited for) the decoder's verdict on every device clip too
+void flac_clips_status(bp_handle h, const FlacJob& job, bool decoded, int* status) {
+  for (size_t i = 0; i < job.dev.size(); ++i) {
+    if (job.dev[i] < 0) status[i] = BP_CLIP_FLAC_HOST;
+    else if (decoded && h->fd_status_host[2 * job.dev[i]] != 0) status[i] = BP_CLIP_FLAC_FAILED;
+  }
+}
+
+// A clip the decoder failed on has no events: the others' move up, their bends with them.
+void drop_failed_clips(bp_handle h, const FlacJob& job, const EventsSink& out) {
+  const int64_t n = (int64_t)job.dev.size();
+  int64_t w = 0, bw = 0;
+  for (int64_t c = 0; c < n; ++c) {
+    const bool drop = job.dev[(size_t)c] >= 0 && h->fd_status_host[2 * job.dev[(size_t)c]] != 0;
+    const int64_t e0 = out.event_offsets[c], e1 = out.event_offsets[c + 1];
+    out.event_offsets[c] = w;
+    for (int64_t e = e0; e < e1 && !drop; ++e) {
+      bp_note_event ev = out.events[e];
+      if (ev.n_bends && bw != ev.bend_offset)
+        std::memmove(out.bends + bw, out.bends + ev.bend_offset, (size_t)ev.n_bends * sizeof(int32_t));
+      ev.bend_offset = bw, bw += ev.n_bends;
+      out.events[w++] = ev;
+    }
+    if (c + 1 == n) out.event_offsets[n] = w;
+  }
+}
+
+// ---- the driver ------------------------------------------------------------------------------------------------------------
+// Where the maps of the n segments come from.  kPcmClips: `clips` (PCM in host or device memory after mem_kind) at sample_rate;
+// kFlacClips: `flac` (bytes in host memory, STREAMINFO rate sample_rate), decoded on the device, then as kPcmClips in device
+// memory; kGivenMaps: no signal but maps already made (mem_kind), segment c at rows [row_offsets[c], row_offsets[c + 1]).
+enum JobSourceKind { kPcmClips, kFlacClips, kGivenMaps };
+struct JobSource {
+  JobSourceKind kind;
+  int64_t n;
+  int mem_kind, sample_rate;
+  const bp_clip* clips;
+  const bp_flac_clip* flac;
+  const int64_t* row_offsets;
+  const float *note, *onset, *contour;
+};
+
+// Where the results go.  kCandidatesHome: the note candidates of all rows (host buffers) and out.status, the maps stay in
+// track_out; kEventsHome: the events (out).  params: of the dense half, and of the tracker unless seg_params gives every
+// segment its own (with the tracker's form and the call's name for n: the A/B hook).
+enum JobSinkKind { kCandidatesHome, kEventsHome };
+struct JobSink {
+  JobSinkKind kind;
+  const bp_note_params* params;
+  EventsSink out;
+  float* note_out;
+  uint8_t* cand_bits;
+  int8_t* bend_map;
+  const bp_note_params* seg_params;
+  int form;
+  const char* count_name;
+};
+
+JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
+  return JobSink{kCandidatesHome, params, EventsSink{nullptr, 0, nullptr, 0, nullptr, status}, note_out, cand_bits, bend_map};
+}
+
+JobSink events_sink(const bp_note_params* params, bp_note_event* events, int64_t max_events, int32_t* bends, int64_t max_bends,
+                    int64_t* event_offsets, int* status) {
+  return JobSink{kEventsHome, params, EventsSink{events, max_events, bends, max_bends, event_offsets, status},
+                 nullptr, nullptr, nullptr, nullptr, kNoteTrackFormAuto, "n_clips"};
+}
+
+// What a job knows of itself, and every host buffer its asynchronous copies read: the driver holds it until the wait is over.
+struct ClipsJob {
+  FlacJob flac;                                // n_model and offs of the clips (kPcmClips too); the rest: kFlacClips
+  const int64_t* offs = nullptr;               // rows before each segment (kGivenMaps: the caller's)
+  std::vector<bp_clip> decoded;                // kFlacClips: the clips' PCM on the device
+  std::vector<ClipDesc> tab;
+  std::vector<NoteTrackSeg> seg;
+  bool dense_bends = false;                    // kEventsHome: the dense half makes the bend map
+  EventsJob ev{};
+  EventsPlan plan;
+  bool exported_by_kernel = false;
+};
+
+// everything a job queues: the source (the maps of all segments to track_out, concatenated by job.offs), the dense half of
+// note decoding for every segment as its own track, the sink
+int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) {
+  Maps all{};
+  int rc = BP_OK;
+  if (s.kind == kGivenMaps) {
+    rc = take_given_maps(h, s.note, s.onset, s.contour, job.offs[s.n], s.mem_kind, &all);
+  } else {
+    const bp_clip* clips = s.clips;
+    if (s.kind == kFlacClips) {
+      // the decoded clips as the PCM clips calls take them: device memory, a clip left to the host without frames
+      const FlacJob& f = job.flac;
+      if ((rc = queue_flac_clips(h, s.flac, f))) return rc;
+      job.decoded.assign(f.dev.size(), bp_clip{nullptr, 0, BP_PCM_S16, 1});
+      for (size_t i = 0; i < f.dev.size(); ++i)
+        if (f.dev[i] >= 0)
+          job.decoded[i] = bp_clip{h->pcm_dev + f.tab[(size_t)f.dev[i]].pcm_off, f.lay[i].n_frames, flac_format(f.lay[i]), f.lay[i].channels};
+      clips = job.decoded.data();
+    }
+    job.tab.resize((size_t)s.n);
+    rc = queue_clips_maps(h, s.n, clips, s.sample_rate, s.kind == kFlacClips ? BP_MEM_DEVICE : s.mem_kind, job.flac.n_model.data(),
+                          job.offs, job.tab, &all);
+  }
+  if (rc) return rc;
+  if (k.kind == kCandidatesHome)
+    return queue_clips_candidates(h, all, s.n, job.offs, k.params, k.note_out, k.cand_bits, k.bend_map, &job.exported_by_kernel);
+  uint8_t* d_bits = nullptr;
+  int8_t* d_bend = nullptr;
+  if ((rc = events_reserve(h, job.ev, &job.plan))) return rc;
+  if ((rc = queue_clips_dense(h, all, s.n, job.offs, k.params, job.dense_bends, &d_bits, &d_bend))) return rc;
+  return events_queue(h, job.ev, job.plan, TrackInputs{all.note, d_bits, d_bend, h->clip_rows, h->clip_stats});
+}
+
+int run_clips(bp_handle h, const char* what, const JobSource& src, const JobSink& k) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  auto invalid = [&](const char* why) { return ::invalid(h, what, why); };
+  const int64_t n = src.n;
+  const bool flac = src.kind == kFlacClips, events = k.kind == kEventsHome;
+  int rc = BP_OK;
+  // the sink's fixed arguments
+  if (events) {
+    if ((rc = check_events(h, what, n, k.params, k.out))) return rc;
+    if (flac && src.sample_rate < 1) return invalid("no sample rate");
+  } else if (!k.params || (n > 0 && !k.out.status) || (flac && src.sample_rate < 1)) {
+    return invalid(flac ? "null params / status or no sample rate" : "null params / status");
+  }
+  // the source's plan (every argument of every segment, its rows), the outputs against the rows
+  ClipsJob job;
+  if (src.kind == kGivenMaps) {
+    bool ordered = n >= 0 && src.row_offsets && src.row_offsets[0] == 0;
+    for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
+    if (!ordered || (src.mem_kind != BP_MEM_HOST && src.mem_kind != BP_MEM_DEVICE))
+      return invalid("row_offsets must start at 0 and never decrease; mem_kind must be BP_MEM_HOST or BP_MEM_DEVICE");
+    if (src.row_offsets[n] > 0 && (!src.note || !src.onset || !src.contour)) return invalid("null input pointer");
+    job.offs = src.row_offsets;
+  } else {
+    if (flac) {
+      rc = plan_flac_clips(h, what, n, src.flac, src.sample_rate, &job.flac);
+    } else {
+      job.flac.n_model.resize((size_t)std::max<int64_t>(n, 0)), job.flac.offs.resize(job.flac.n_model.size() + 1);
+      rc = check_clips(h, what, n, src.clips, src.sample_rate, src.mem_kind, true, job.flac.n_model.data(), job.flac.offs.data());
+    }
+    if (rc) return rc;
+    job.offs = job.flac.offs.data();
+  }
+  const int64_t total = job.offs[n];
+  if (!events && total > 0 && (!k.note_out || !k.cand_bits)) return invalid("null output pointer");
+  // the statuses the host knows, and the jobs that need no device work
+  if (!events)
+    for (int64_t i = 0; i < n; ++i) k.out.status[i] = 0;
+  const bool done = events ? events_without_device(n, job.offs, k.params, k.out) : total == 0;  // (no clip has a row)
+  if (flac && (done || !events)) flac_clips_status(h, job.flac, false, k.out.status);
+  if (done) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  if (src.kind != kGivenMaps && src.sample_rate != h->rate)
+    if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
+  if (events) {
+    job.dense_bends = !k.seg_params && k.params->include_pitch_bends != 0;
+    for (int64_t i = 0; k.seg_params && i < n; ++i) {
+      const bp_note_params& p = k.seg_params[i];
+      job.dense_bends = job.dense_bends || p.include_pitch_bends != 0;
+      job.seg.push_back(NoteTrackSeg{p.frame_threshold, p.energy_tol, p.min_note_len, p.melodia_trick != 0, p.include_pitch_bends != 0, 0, 0});
+    }
+    job.ev = EventsJob{what, k.count_name, n, job.offs, k.seg_params ? nullptr : k.params, k.seg_params ? job.seg.data() : nullptr,
+                       nullptr, k.form};
+  }
+  rc = finish(h, queue_job(h, src, k, job));
+  if (!events) {  // what the clips' records say (a clip without rows: 0)
+    if (rc) return rc;
+    if (job.exported_by_kernel) h->clip_stats_ready = n;  // only now: the export kernel, which re-initialises the records, has run
+    for (int64_t i = 0; i < n; ++i)
+      k.out.status[i] = job.offs[i + 1] > job.offs[i] && (h->clip_stats_host[4 * i + 1] || !(k.params->onset_threshold > 0.0)) ? 1 : 0;
+  } else if (rc || (rc = events_home(h, job.ev, k.out, nullptr))) {
+    // (buffers too small: status and event_offsets are complete but for the decoder's verdicts)
+    if (flac) flac_clips_status(h, job.flac, false, k.out.status);
+    return rc;
+  } else if (flac) {
+    drop_failed_clips(h, job.flac, k.out);
+  }
+  if (flac) flac_clips_status(h, job.flac, true, k.out.status);
+  return BP_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int bp_clips_row_offsets(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int64_t* offsets) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  return check_clips(h, "bp_clips_row_offsets", n_clips, clips, sample_rate, BP_MEM_HOST, false, nullptr, offsets);
+}
+
+int bp_infer_clips_candidates(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                              const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
+  return run_clips(h, "bp_infer_clips_candidates", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   candidates_sink(params, note_out, cand_bits, bend_map, status));
+}
+
+int64_t bp_events_capacity(int64_t rows, int min_note_len) { return note_track_capacity(rows, min_note_len); }
+
+int bp_infer_clips_events(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                          const bp_note_params* params, bp_note_event* events, int64_t max_events, int32_t* bends,
+                          int64_t max_bends, int64_t* event_offsets, int* status) {
+  return run_clips(h, "bp_infer_clips_events", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   events_sink(params, events, max_events, bends, max_bends, event_offsets, status));
+}
+
+int bp_note_events_from_maps(bp_handle h, int64_t n_clips, const int64_t* row_offsets, const float* note, const float* onset,
+                             const float* contour, int mem_kind, const bp_note_params* params, bp_note_event* events,
+                             int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
+  return run_clips(h, "bp_note_events_from_maps", JobSource{kGivenMaps, n_clips, mem_kind, 0, nullptr, nullptr, row_offsets, note, onset, contour},
+                   events_sink(params, events, max_events, bends, max_bends, event_offsets, status));
+}
+
+#ifdef BP_AB_KERNELS
+// The A/B library's test hook for the segmented note candidates (declared nowhere: the tests name it): the clips' maps are
+// given, not made — host maps of offsets[n_clips] rows, clip c at rows [offsets[c], offsets[c + 1]) — and go through what
+// bp_infer_clips_candidates runs behind the model.  The product library has no such call.
+int bp_ab_clips_candidates_from_maps(bp_handle h, int64_t n_clips, const int64_t* offsets, const float* note, const float* onset,
+                                     const float* contour, const bp_note_params* params, float* note_out, uint8_t* cand_bits,
+                                     int8_t* bend_map, int* status) {
+  if (!h || n_clips < 1 || !offsets || !note || !onset || !contour || !params || !note_out || !cand_bits || !status ||
+      offsets[0] != 0 || offsets[n_clips] < 1)
+    return BP_ERR_INVALID_ARG;
+  for (int64_t i = 0; i < n_clips; ++i)
+    if (offsets[i + 1] < offsets[i]) return BP_ERR_INVALID_ARG;
+  return run_clips(h, "bp_ab_clips_candidates_from_maps",
+                   JobSource{kGivenMaps, n_clips, BP_MEM_HOST, 0, nullptr, nullptr, offsets, note, onset, contour},
+                   candidates_sink(params, note_out, cand_bits, bend_map, status));
+}
+
+// The A/B library's test hook for the tracker with per-segment parameters (declared nowhere: the tests name it):
+// bp_note_events_from_maps on host maps with one bp_note_params per segment and the tracker form (0: as the product chooses,
+// 2: every segment's working state in the scratch buffer).  The dense half — frequency limits, inferred onsets, the onset
+// threshold — takes params[0], and makes the bend map where any segment wants bends; the tracker takes segment c's frame
+// threshold, tolerance, minimum length, melodia and bends.
+int bp_ab_note_events_from_maps_forms(bp_handle h, int64_t n, const int64_t* row_offsets, const float* note, const float* onset,
+                                      const float* contour, const bp_note_params* params, int form, bp_note_event* events,
+                                      int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
+  if (!h || n < 1 || !row_offsets || !note || !onset || !contour || !params || !event_offsets || !status || row_offsets[0] != 0 ||
+      row_offsets[n] < 1 || (form != kNoteTrackFormAuto && form != kNoteTrackFormScratch) || !(params[0].onset_threshold > 0.0))
+    return BP_ERR_INVALID_ARG;
+  const char* what = "bp_ab_note_events_from_maps_forms";
+  JobSink k = events_sink(params, events, max_events, bends, max_bends, event_offsets, status);
+  k.seg_params = params, k.form = form, k.count_name = "n";
+  for (int64_t i = 0; i < n; ++i) {
+    if (row_offsets[i + 1] < row_offsets[i]) return BP_ERR_INVALID_ARG;
+    if (int rc = check_events(h, what, n, params + i, k.out)) return rc;
+  }
+  return run_clips(h, what, JobSource{kGivenMaps, n, BP_MEM_HOST, 0, nullptr, nullptr, row_offsets, note, onset, contour}, k);
+}
+#endif
+
+// ---- a job of FLAC clips (include/basic_pitch_amd_flac_clips.h) ------------------------------------------------------------------
+int bp_flac_clips_row_offsets(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int sample_rate, int64_t* offsets, int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_flac_clips_row_offsets";
+  if (!offsets || (n_clips > 0 && !status) || sample_rate < 1) return invalid(h, what, "null offsets / status or no sample rate");
+  FlacJob job;
+  if (int rc = plan_flac_clips(h, what, n_clips, clips, sample_rate, &job)) return rc;
+  for (int64_t i = 0; i <= n_clips; ++i) offsets[i] = job.offs[(size_t)i];
+  for (int64_t i = 0; i < n_clips; ++i) status[i] = 0;
+  flac_clips_status(h, job, false, status);
+  return BP_OK;
+}
+
+int bp_flac_clips_decode_device(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int32_t* pcm, const int64_t* pcm_offsets,
+                                int* status) {
+  if (!h) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_flac_clips_decode_device";
+  if (!pcm_offsets || (n_clips > 0 && !status)) return invalid(h, what, "null pcm_offsets / status");
+  FlacJob job;
+  if (int rc = plan_flac_clips(h, what, n_clips, clips, 0, &job)) return rc;
+  for (int64_t i = 0; i < n_clips; ++i)
+    if (job.dev[(size_t)i] >= 0 && (!pcm || pcm_offsets[i] < 0 ||
+                                    pcm_offsets[i + 1] - pcm_offsets[i] < job.lay[(size_t)i].n_frames * job.lay[(size_t)i].channels))
+      return invalid(h, what, "clip " + std::to_string(i) + ": null pcm or too little room between its offsets");
+  for (int64_t i = 0; i < n_clips; ++i) status[i] = 0;
+  flac_clips_status(h, job, false, status);
+  if (job.tab.empty()) return BP_OK;
+  BP_HIP(hipSetDevice(h->device));
+  h->maps_rows = 0;  // (the PCM staging is shared with the track calls; their maps are not, but a decode is no *_candidates call)
+  if (int rc = finish(h, queue_flac_clips(h, clips, job))) return rc;
+  std::vector<uint8_t> home((size_t)job.pcm_bytes);
+  BP_HIP(hipMemcpy(home.data(), h->pcm_dev, home.size(), hipMemcpyDeviceToHost));
+  for (int64_t i = 0; i < n_clips; ++i) {
+    if (job.dev[(size_t)i] < 0) continue;
+    const FdClip& k = job.tab[(size_t)job.dev[(size_t)i]];
+    flac_pcm_to_int32(home.data() + k.pcm_off, k.out_wide != 0, k.out_shift, k.st.total * k.st.channels, pcm + pcm_offsets[i]);
+  }
+  flac_clips_status(h, job, true, status);
+  return BP_OK;
+}
+
+int bp_infer_flac_clips_candidates(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int sample_rate,
+                                   const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
+  return run_clips(h, "bp_infer_flac_clips_candidates", JobSource{kFlacClips, n_clips, BP_MEM_HOST, sample_rate, nullptr, clips},
+                   candidates_sink(params, note_out, cand_bits, bend_map, status));
+}
+
+int bp_infer_flac_clips_events(bp_handle h, int64_t n_clips, const bp_flac_clip* clips, int sample_rate, const bp_note_params* params,
+                               bp_note_event* events, int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets,
+                               int* status) {
+  return run_clips(h, "bp_infer_flac_clips_events", JobSource{kFlacClips, n_clips, BP_MEM_HOST, sample_rate, nullptr, clips},
+                   events_sink(params, events, max_events, bends, max_bends, event_offsets, status));
+}
+
+}  // extern "C"
+

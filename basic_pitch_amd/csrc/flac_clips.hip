@@ -1,4 +1,4 @@
-// FLAC decode on the device for a JOB of many streams (bp_infer_flac_clips_candidates, track_api.hip).  A short
+// FLAC decode on the device for a JOB of many streams (bp_infer_flac_clips_candidates, clips_api.hip).  A short
 // clip is a few dozen frames: decoded alone (flac_device.hip) it fills less than one wave of the decode kernel and pays four
 // launches, an upload and a wait for ~40 us of device work.  Here the four stages run ONCE for all clips of a job:
 //   * every clip's bytes lie in one buffer, each clip 16-byte aligned and followed by >= 64 zero bytes (the padding the scan's

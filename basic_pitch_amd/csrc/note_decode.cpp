@@ -171,7 +171,7 @@ void bp_note_params_default(bp_note_params* p) {
 }
 
 // model_frames_to_time()[fr] (note_creation.py:346-357): the one expression every event's times come from — decode_core
-// below, and the calls that bring events home from the device (track_api.hip, bp_infer_clips_events)
+// below, and the calls that bring events home from the device (clips_api.hip, bp_infer_clips_events)
 double bp_internal_frame_time(int64_t fr) {
   const double window_offset = (256.0 / 22050.0) * (172.0 - (43844.0 / 256.0)) + 0.0018;
   const double original = (double)(fr * 256) / 22050.0;

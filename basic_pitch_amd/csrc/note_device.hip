@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void nd_candidates_kernel(const float* __restr
   nd_candidates_row<kRing>(note, onset, t, n, kRing ? (a + t) % cap : t, cap, infer, onset_thresh, st, bits, threadIdx.x & 63);
 }
 
-// ---- many clips in one buffer (bp_infer_clips_candidates, track_api.hip) -------------------------------------------------------
+// ---- many clips in one buffer (bp_infer_clips_candidates, clips_api.hip) -------------------------------------------------------
 // The maps of n_clips clips lie one after the other: clip c owns rows [offs[c], offs[c + 1]) and is decoded as its own whole
 // track.  The table offs[0 ... n_clips] is in device memory; a row finds its clip by binary search.  Every clip has one stats
 // record, table[c].  Frequency limits and bends are row-local and run over all rows with the kernels of a single track.

@@ -48,7 +48,7 @@
 // one table of streams (StreamUpdate, note_device.hip "the updates of many streams"), the segmented launches, packed rows home.
 //
 // bp_streams_events is that step with nothing sent home (every stream's whole slice stays packed in the handle's buffers) and
-// the tracker of the clips calls behind it (note_track.hip, a segment per stream with the stream's own parameters; track_api.hip
+// the tracker of the clips calls behind it (note_track.hip, a segment per stream with the stream's own parameters; clips_api.hip
 // events_reserve / events_queue / events_home): the events and their bends are all that crosses PCIe.
 //
 // A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the

@@ -33,10 +33,7 @@ MAX_ROWS = 8192  # BP_EVENTS_MAX_ROWS
 
 def bind(lib: C.CDLL) -> C.CDLL:
     """Declare the prototypes of include/basic_pitch_amd_events.h on a loaded library."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
+    return _native.bind(lib, PROTOTYPES)
 
 
 def events_capacity(rows: int, min_note_len: int) -> int:

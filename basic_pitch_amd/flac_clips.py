@@ -10,7 +10,6 @@ to what the PCM clips calls run.  Clip by clip the bytes are those of the single
 from __future__ import annotations
 
 import ctypes as C
-from concurrent.futures import ThreadPoolExecutor
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -41,10 +40,7 @@ PROTOTYPES = {
 
 def bind(lib: C.CDLL) -> C.CDLL:
     """Declare the prototypes of include/basic_pitch_amd_flac_clips.h on a loaded library."""
-    for name, (restype, argtypes) in PROTOTYPES.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
+    return _native.bind(lib, PROTOTYPES)
 
 
 def clip_table(blobs: Sequence[Any]):
@@ -123,16 +119,9 @@ def infer_flac_clips_candidates(model: Any, blobs: Sequence[Any], sample_rate: i
     """One `bp_infer_flac_clips_candidates` call for FLAC clips of one rate: as `clips.infer_clips_candidates`."""
     lib = bind(model._lib)
     tab, keep = clip_table(blobs)
-    offs, _ = flac_clips_row_offsets(model, blobs, sample_rate)
-    T = int(offs[-1])
-    note = np.empty((T, 88), np.float32)
-    bits = np.empty((T, 12), np.uint8)
-    bend = np.empty((T, 88), np.int8) if prm.include_pitch_bends else None
-    status = np.zeros(max(1, len(keep)), np.int32)
-    rc = lib.bp_infer_flac_clips_candidates(model._handle, len(keep), tab, int(sample_rate), C.addressof(prm), note.ctypes.data,
-                                            bits.ctypes.data, bend.ctypes.data if bend is not None else None, status.ctypes.data)
-    _native.check(lib, model._handle, rc, "bp_infer_flac_clips_candidates")
-    return offs, note, bits, bend, status[: len(keep)]
+    fixed = (model._handle, len(keep), tab, int(sample_rate))
+    return _clips._call(lib, model._handle, "bp_infer_flac_clips_candidates", lib.bp_infer_flac_clips_candidates, fixed,
+                        flac_clips_row_offsets(model, blobs, sample_rate)[0], prm)
 
 
 def infer_flac_clips_events(model: Any, blobs: Sequence[Any], sample_rate: int, prm: Any, room: Optional[Tuple[int, int]] = None):
@@ -184,29 +173,9 @@ def transcribe_flac_clips(model: Any, blobs: Sequence[Any], onset_threshold: flo
     results: List[Any] = [None] * len(blobs)
     groups, on_host = group_by_rate(layouts)
 
-    def decoded(note, bits, bend):
-        ev = _notes.decode_candidates(note, bits, bend, prm)
-        return _notes.note_events_to_midi(ev, multiple_pitch_bends, midi_tempo), ev
-
-    with ThreadPoolExecutor(max_workers=max(1, int(threads))) as pool:
-        pending = []
-        for rate, ids in groups.items():
-            group = [blobs[i] for i in ids]
-            if decode == "device":
-                events, bends, ev_offs, status = infer_flac_clips_events(model, group, rate, prm)
-            else:
-                offs, note, bits, bend, status = infer_flac_clips_candidates(model, group, rate, prm)
-            for k, i in enumerate(ids):
-                if status[k]:
-                    on_host.append(i)
-                elif decode == "device":
-                    ev = _events.clip_events(events, bends, ev_offs, k, True)
-                    results[i] = (_notes.note_events_to_midi(ev, multiple_pitch_bends, midi_tempo), ev)
-                else:
-                    r0, r1 = int(offs[k]), int(offs[k + 1])
-                    pending.append((i, pool.submit(decoded, note[r0:r1], bits[r0:r1], bend[r0:r1] if bend is not None else None)))
-        for i, fut in pending:
-            results[i] = fut.result()
+    _clips.transcribe_groups(groups.items(), lambda ids, rate: infer_flac_clips_candidates(model, [blobs[i] for i in ids], rate, prm),
+                             lambda ids, rate: infer_flac_clips_events(model, [blobs[i] for i in ids], rate, prm),
+                             on_host.append, results, prm, decode, multiple_pitch_bends, midi_tempo, threads)
     # the host decoder's clips: the PCM path, all in one job (which itself falls back for its statuses 1 and 2)
     arrays, rates, ids = [], [], []
     for i in sorted(on_host):

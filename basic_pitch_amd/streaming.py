@@ -79,11 +79,7 @@ _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native
 
 def bind(lib: C.CDLL) -> C.CDLL:
     """Declare the streaming family's prototypes (the five headers) on a loaded library."""
-    for name, (restype, argtypes) in {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES, **UPDATE_PROTOTYPES,
-                                      **STREAM_EVENTS_PROTOTYPES}.items():
-        fn = getattr(lib, name)
-        fn.restype, fn.argtypes = restype, argtypes
-    return lib
+    return _native.bind(lib, {**PROTOTYPES, **LIVE_PROTOTYPES, **ROLLING_PROTOTYPES, **UPDATE_PROTOTYPES, **STREAM_EVENTS_PROTOTYPES})
 
 
 def horizon_first_row(n_rows: int, horizon_rows: int) -> int:

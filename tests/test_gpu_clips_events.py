@@ -354,3 +354,64 @@ def test_transcribe_clips_on_the_device_returns_the_hosts_events(model):
     after = model.predict_pcm(np.asarray(song, np.float32).reshape(len(song), -1), rate)
     for k in before:
         assert before[k].tobytes() == after[k].tobytes(), k
+
+
+def test_one_job_gives_the_same_events_by_every_route():
+    """What the job driver (csrc/clips_api.hip run_clips) holds in one place: a job of three segments of 142, 0 and 284 rows —
+    the smallest with an empty segment between two that have rows, on a handle of two windows so that chunks end inside it — as
+    44.1 kHz stereo int16 PCM through bp_infer_clips_candidates and bp_infer_clips_events, and as maps through
+    bp_note_events_from_maps from host and from device memory.  A job of clips leaves no maps for bp_track_maps (its rows
+    are those of the single-clip call, tests/test_gpu_clips.py), so the maps are fetched with it after
+    bp_infer_pcm_raw_candidates on each clip alone."""
+    import torch
+
+    from basic_pitch_amd import _native, clips as CL, events as EV, note_creation as NC
+    from basic_pitch_amd.inference import Model
+    from test_gpu_clips import _signal
+
+    rng = np.random.default_rng(31)
+    frames = (2 * 36164, 0, 4 * 36164)  # 36164 and 72328 samples at the model's rate: int(n / 36164 * 142) rows
+    arrays = [np.clip(np.round(np.stack([_signal(rng, f, 44100)] * 2, axis=1) * 32767), -32768, 32767).astype(np.int16)
+              if f else np.zeros((0, 2), np.int16) for f in frames]
+    prm = _prm({})
+    with Model(device=0, max_windows=2) as m:
+        offs, note, bits, bend, st_cand = CL.infer_clips_candidates(m, arrays, 44100, prm)
+        assert offs.tolist() == [0, 142, 142, 426]
+        by_pcm = EV.infer_clips_events(m, arrays, 44100, prm)
+        maps = {k: np.zeros((426, w), np.float32) for k, w in (("note", 88), ("onset", 88), ("contour", 264))}
+        for i, a in enumerate(arrays):
+            r0, r1 = int(offs[i]), int(offs[i + 1])
+            if r1 == r0:
+                continue
+            status = C.c_int(-1)
+            one = [np.empty((r1 - r0, w), t) for w, t in ((88, np.float32), (12, np.uint8), (88, np.int8))]
+            rc = m._lib.bp_infer_pcm_raw_candidates(m._handle, a.ctypes.data, CL.FORMATS[a.dtype], a.shape[0], 2, 44100, C.byref(prm),
+                                                    one[0].ctypes.data, one[1].ctypes.data, one[2].ctypes.data, C.byref(status))
+            _native.check(m._lib, m._handle, rc, "bp_infer_pcm_raw_candidates")
+            assert one[0].tobytes() == note[r0:r1].tobytes()  # the job's rows are this call's
+            part = {k: np.empty_like(v[r0:r1]) for k, v in maps.items()}
+            rc = m._lib.bp_track_maps(m._handle, r1 - r0, part["note"].ctypes.data, part["onset"].ctypes.data,
+                                      part["contour"].ctypes.data, _native.BP_MEM_HOST)
+            _native.check(m._lib, m._handle, rc, "bp_track_maps")
+            for k in maps:
+                maps[k][r0:r1] = part[k]
+        by_host = EV.note_events_from_maps(m, offs, *[maps[k].ctypes.data for k in ("note", "onset", "contour")], _native.BP_MEM_HOST, prm)
+        dev = {k: torch.from_numpy(v).cuda() for k, v in maps.items()}
+        torch.cuda.synchronize()
+        by_dev = EV.note_events_from_maps(m, offs, *[dev[k].data_ptr() for k in ("note", "onset", "contour")], _native.BP_MEM_DEVICE, prm)
+    routes = {"pcm": by_pcm, "host maps": by_host, "device maps": by_dev}
+    n_events = 0
+    for name, (events, bends, ev_offs, status) in routes.items():
+        assert ev_offs.tolist() == by_pcm[2].tolist() and ev_offs[1] == ev_offs[2], name
+        assert status.tolist() == st_cand.tolist() == [0, 0, 0], name
+        assert _records(events, bends, 0, int(ev_offs[-1]), True) == _records(by_pcm[0], by_pcm[1], 0, int(ev_offs[-1]), True), name
+        for i in range(3):
+            r0, r1 = int(offs[i]), int(offs[i + 1])
+            want = NC.decode_candidates(note[r0:r1], bits[r0:r1], bend[r0:r1], prm) if r1 > r0 else []
+            got = EV.clip_events(events, bends, ev_offs, i, True)
+            assert len(got) == len(want), (name, i)
+            for g, w in zip(got, want):
+                assert tuple(g[:3]) == tuple(w[:3]) and np.float32(g[3]).tobytes() == np.float32(w[3]).tobytes(), (name, i, g, w)
+                assert list(g[4]) == list(w[4]), (name, i)
+            n_events += len(want)
+    assert n_events >= 6  # the comparison is not one of empty lists
