@@ -214,7 +214,7 @@ hipError_t launch_note_track_segs(const float* note, const uint8_t* bits, const 
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot
 // r % cap.  A rolling horizon has beside it `records`, note_ring_records(cap) stats records of 16 bytes: the table of
-// per-block extrema of the final rows and, last, the record of an update.
+// per-block extrema of the final rows and, last, one record that is reserved and unused.
 int64_t note_ring_records(int64_t cap);
 // rows [t0, t0 + n), n <= cap, of linear maps into their slots, frequency-constrained to the bins [lo, hi)
 void launch_ring_put(const float* src_note, const float* src_onset, const float* src_contour, float* ring, int64_t cap,
@@ -222,17 +222,11 @@ void launch_ring_put(const float* src_note, const float* src_onset, const float*
 // final rows [t0, t1), t1 - t0 <= cap, join the table; blocks that start at or after fresh_from begin anew
 void launch_ring_fold(const float* ring, int64_t cap, int64_t t0, int64_t t1, int64_t fresh_from, int infer, void* records,
                       hipStream_t s);
-// the record of rows [a, T) as a whole track from the table (R <= T: the final rows), into the last of `records`
-void launch_ring_stats(const float* ring, int64_t cap, int64_t a, int64_t R, int64_t T, int infer, void* records, hipStream_t s);
-// from a record of rows [a, T): their peak bitmap ([T - a][12] bytes); the bends of rows [t0, t0 + n) ([n][88] bytes)
-void launch_ring_peaks(const float* ring, int64_t cap, int64_t a, int64_t T, int infer, double onset_thresh, const void* stats,
-                       uint8_t* bits, hipStream_t s);
-void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, const void* tab, const double* gauss, int8_t* bend,
-                       hipStream_t s);
-// the rows of [a, T) that launch_ring_stats scans are [a, *e0) and [*e1, T); the table's blocks [*e0, *e1) / 64 join whole
+// the rows of [a, T) (R <= T: the final rows) that an update of a rolling horizon scans are [a, *e0) and [*e1, T); the table's
+// blocks [*e0, *e1) / 64 join whole
 void note_ring_edges(int64_t a, int64_t R, int64_t T, int64_t* e0, int64_t* e1);
 
-// The updates of many streams in one step (bp_streams_candidates): one stream of the table a call uploads.  Behind the table
+// The updates of streams, one or many in a step (stream_api.hip queue_updates): one stream of the table a call uploads.  Behind the table
 // lie kStreamUpdatePrefixes arrays of n + 1 int64, the running totals over the streams of: tail rows, workgroups of the stats
 // launch (streams_stats_chunks of the edge rows), bitmap rows T - a, workgroups of the bend launch (streams_bend_blocks of
 // T - n0, 0 without bends), note rows T - n0.
@@ -250,7 +244,7 @@ struct StreamUpdate {
 constexpr int kStreamUpdatePrefixes = 5;
 int64_t streams_stats_chunks(int64_t n_edge);
 int64_t streams_bend_blocks(int64_t n_rows);
-// the tails' rows to their slots, frequency-constrained per stream (launch_ring_put for every stream)
+// the tails' rows to their slots, frequency-constrained per stream (what launch_ring_put does for a stream's final rows)
 void launch_streams_put(const StreamUpdate* u, const int64_t* pre, int64_t n, int64_t tail_rows, hipStream_t s);
 // per stream: its update record (`stats`: n records of 16 bytes) from its table or carried record and its edge rows, then, packed
 // and linear in argument order, the bitmap of [a, T), the bends and the note rows of [n0, T); the last four arguments before the

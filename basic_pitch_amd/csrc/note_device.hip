@@ -170,7 +170,8 @@ __device__ __forceinline__ void nd_candidates_row(const float* __restrict__ note
   if (lane < 3) bits[t * 3 + lane] = lane == 0 ? (uint32_t)b0 : (lane == 1 ? (uint32_t)(b0 >> 32) : (uint32_t)b1);
 }
 
-// A wave per frame.  kRing: the bitmap is that of rows [a, T) of the ring; linear: a = 0, cap unused.
+// A wave per frame.  kRing: the bitmap is that of rows [a, T) of the ring; linear: a = 0, cap unused.  Only the linear form is
+// launched (a track): the rows of rings go through nd_streams_candidates_kernel.
 template <bool kRing>
 __global__ __launch_bounds__(256) void nd_candidates_kernel(const float* __restrict__ note, const float* __restrict__ onset,
                                                             int64_t a, int64_t T, int64_t cap, int infer, double onset_thresh,
@@ -283,8 +284,8 @@ __device__ __forceinline__ int nd_bend_argmax_nan(const double* __restrict__ win
 
 // kRing: row t of the T rows is absolute row first + t of a ring of `cap` contour rows (slot r % cap); the bends are written
 // linear, row t at bend + t * 88, as in the linear form (first = 0, cap unused).
-// `block`: which kNdBendFrames rows of the T the workgroup takes.  A device function: the kernel of one track or ring and the
-// kernel of many streams (nd_streams_bend_kernel, below) run this one body.
+// `block`: which kNdBendFrames rows of the T the workgroup takes.  A device function: the kernel of a track (linear) and the
+// kernel of the streams' rings (nd_streams_bend_kernel, below) run this one body.
 template <bool kRing>
 __device__ __forceinline__ void nd_bend_block(const float* __restrict__ contour, int64_t first, int64_t T, int64_t cap,
                                               const int4* __restrict__ tab, const double* __restrict__ gauss,
@@ -449,10 +450,10 @@ void launch_clips_candidates(float* note, float* onset, const float* contour, co
 
 // ---- the rows a stream retains (stream_api.hip, bp_stream_keep / bp_stream_keep_rolling) ------------------------------------
 // The retained maps are a ring of `cap` rows ([cap] note, [cap] onset, [cap] contour; absolute row r at slot r % cap),
-// frequency-constrained as they are put, and a transcript decodes rows [a, T) as a whole track: nd_candidates_kernel<true>
-// and nd_bend_kernel<true>.  A stream that keeps every row reserves a ring that never wraps: a = 0, slot r is row r, and the
-// extrema of its rows are carried in ONE record, which the final rows join with launch_note_fold on the ring as the linear
-// maps it then is.
+// frequency-constrained as they are put, and a transcript decodes rows [a, T) as a whole track ("the updates of streams",
+// below).  This part is how rows enter the store and how the extrema of the final rows are carried.  A stream that keeps
+// every row reserves a ring that never wraps: a = 0, slot r is row r, and the extrema of its rows are carried in ONE record,
+// which the final rows join with launch_note_fold on the ring as the linear maps it then is.
 //
 // A rolling horizon cannot carry the two maxima of its slice in one record: a record only grows, and a row that leaves the
 // horizon cannot be taken out of it.  So its final rows fill a TABLE of records, one
@@ -465,6 +466,7 @@ constexpr int kNdRingBlock = 64;
 // Rows [t0, t0 + n) of linear maps (row 0 of src_* is absolute row t0) go to their slots, constrain_frequency applied on the
 // way (bins outside [lo, hi) of note and onset become 0).  An item is one float, float c of row r of the source; n <= cap, so no
 // slot is written twice.  Scalar loads: the source may be a caller's device buffer, of which only float alignment is known.
+// A device function: the kernel of a step's final rows and the kernel of the tails of an update run this one body.
 constexpr int kNdPutRow = 2 * kNdF + kNdFC;
 __device__ __forceinline__ void nd_ring_put_item(const float* __restrict__ src_note, const float* __restrict__ src_onset,
                                                  const float* __restrict__ src_contour, float* __restrict__ note,
@@ -519,8 +521,7 @@ __global__ __launch_bounds__(256) void nd_ring_fold_kernel(const float* __restri
 
 // The record of the slice [a, T) (st holds the initial values): the table's blocks [e0, e1) / kNdRingBlock, which lie wholly in
 // [a + 2, R), joined by workgroup 0, and the rows [a, e0) and [e1, T) scanned, a wave per row, fd only from frame 2 of the
-// slice on.  Without a whole block e0 == e1 and the two ranges are the slice.  The two halves are device functions: the kernel
-// of one stream and the kernel of many (nd_streams_stats_kernel, below) run the same bodies.
+// slice on.  Without a whole block e0 == e1 and the two ranges are the slice.  The two halves of nd_streams_stats_kernel, below.
 
 // edge rows j0, j0 + step, ... < j1 of the n_edge = (e0 - a) + (T - e1) join the wave's extrema
 __device__ __forceinline__ void nd_edge_rows(const float* __restrict__ note, const float* __restrict__ onset, int64_t a, int64_t e0,
@@ -544,21 +545,6 @@ __device__ __forceinline__ void nd_join_blocks(const NdStats* __restrict__ table
     mfd = d > mfd ? d : mfd;
     nan |= rec.nan;
   }
-}
-
-__global__ __launch_bounds__(256) void nd_ring_stats_kernel(const float* __restrict__ note, const float* __restrict__ onset, int64_t a,
-                                                            int64_t e0, int64_t e1, int64_t T, int64_t cap, int infer,
-                                                            const NdStats* __restrict__ table, int64_t n_tab,
-                                                            NdStats* __restrict__ st) {
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  float mo = -__int_as_float(0x7f800000);
-  double mfd = 0.0;
-  int nan = 0;
-  nd_edge_rows(note, onset, a, e0, e1, cap, infer, (int64_t)blockIdx.x * 4 + wave, (e0 - a) + (T - e1), (int64_t)gridDim.x * 4, lane,
-               mo, mfd, nan);
-  if (blockIdx.x == 0) nd_join_blocks(table, n_tab, e0, e1, mo, mfd, nan);
-  nd_reduce(mo, mfd, nan);
-  if (threadIdx.x == 0) nd_publish(st, mo, mfd, nan);
 }
 
 int64_t note_ring_records(int64_t cap) { return (cap + kNdRingBlock - 1) / kNdRingBlock + 2 + 1; }
@@ -587,38 +573,13 @@ void launch_ring_fold(const float* ring, int64_t cap, int64_t t0, int64_t t1, in
                      fresh_from, ring_table(records), ring_n_tab(cap));
 }
 
-void launch_ring_stats(const float* ring, int64_t cap, int64_t a, int64_t R, int64_t T, int infer, void* records, hipStream_t s) {
-  if (T <= a) return;
-  int64_t e0, e1;
-  note_ring_edges(a, R, T, &e0, &e1);
-  const int64_t n_edge = (e0 - a) + (T - e1);
-  const unsigned rows4 = (unsigned)((n_edge + 3) / 4);
-  NdStats* st = ring_table(records) + ring_n_tab(cap);
-  hipLaunchKernelGGL(nd_stats_init_kernel, dim3(1), dim3(64), 0, s, st);
-  hipLaunchKernelGGL(nd_ring_stats_kernel, dim3(rows4 < 512u ? rows4 : 512u), dim3(256), 0, s, ring, ring + cap * kNdF, a, e0, e1, T,
-                     cap, infer, ring_table(records), ring_n_tab(cap), st);
-}
-
-void launch_ring_peaks(const float* ring, int64_t cap, int64_t a, int64_t T, int infer, double onset_thresh, const void* stats,
-                       uint8_t* bits, hipStream_t s) {
-  if (T <= a) return;
-  hipLaunchKernelGGL(nd_candidates_kernel<true>, dim3((unsigned)((T - a + 3) / 4)), dim3(256), 0, s, ring, ring + cap * kNdF, a, T,
-                     cap, infer, onset_thresh, static_cast<const NdStats*>(stats), reinterpret_cast<uint32_t*>(bits));
-}
-
-void launch_ring_bends(const float* ring, int64_t cap, int64_t t0, int64_t n, const void* tab, const double* gauss, int8_t* bend,
-                       hipStream_t s) {
-  if (n <= 0) return;
-  hipLaunchKernelGGL(nd_bend_kernel<true>, dim3((unsigned)((n + kNdBendFrames - 1) / kNdBendFrames)), dim3(256), 0, s,
-                     ring + cap * 2 * kNdF, t0, n, cap, static_cast<const int4*>(tab), gauss, bend);
-}
-
-// ---- the updates of many streams in one step (bp_streams_candidates, stream_api.hip) -------------------------------------------
-// What the kernels above do for one stream's store, for n stores at once: the segmented form the clips call introduced, a
-// segment being a stream.  Stream c is u[c]; the work items of each launch are counted over all streams and an item finds its
-// stream by nd_clip_of_row in a prefix array (pre + k * (n + 1), k = one of the kNdPre* below).  Every body is the device
-// function of the single-stream kernel: nd_ring_put_item, nd_edge_rows / nd_join_blocks / nd_reduce / nd_publish,
-// nd_candidates_row<true>, nd_bend_block<true>.  The update records are a table of the handle's, record c for stream c.
+// ---- the updates of streams (bp_stream_candidates[_rolling], bp_streams_candidates, bp_streams_events; stream_api.hip) ---------
+// An update decodes rows [a, T) of every stream's store as a whole track, for n stores at once (a single update is n = 1): the
+// segmented form the clips call introduced, a segment being a stream.  Stream c is u[c]; the work items of each launch are
+// counted over all streams and an item finds its stream by nd_clip_of_row in a prefix array (pre + k * (n + 1), k = one of
+// the kNdPre* below).  The bodies are the device functions above, in their ring forms: nd_ring_put_item, nd_edge_rows /
+// nd_join_blocks / nd_reduce / nd_publish, nd_candidates_row<true>, nd_bend_block<true>.  The update records are a table of the
+// handle's, record c for stream c.
 enum { kNdPreTail, kNdPreChunk, kNdPreBits, kNdPreBend, kNdPreNote, kNdPreArrays };
 static_assert(kNdPreArrays == kStreamUpdatePrefixes, "the host's table has one array per launch");
 constexpr int kNdEdgeChunk = 64;  // edge rows a workgroup of the stats launch scans
@@ -648,8 +609,8 @@ __global__ __launch_bounds__(256) void nd_streams_stats_init_kernel(const Stream
 }
 
 // A workgroup per stream and chunk of kNdEdgeChunk edge rows; the first of a rolling stream also joins the whole blocks of
-// its table.  A keeping stream's edge rows are its tail (e0 = a, e1 = R).  Maxima and an OR: the record is the single
-// update's whatever the partition.
+// its table.  A keeping stream's edge rows are its tail (e0 = a, e1 = R).  Maxima and an OR: the record is that of the
+// slice whatever the partition.
 __global__ __launch_bounds__(256) void nd_streams_stats_kernel(const StreamUpdate* __restrict__ u, const int64_t* __restrict__ offs,
                                                                int64_t n, NdStats* __restrict__ st) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -678,8 +639,8 @@ __global__ __launch_bounds__(256) void nd_streams_candidates_kernel(const Stream
                           bits + d.bits_offset * 3, threadIdx.x & 63);
 }
 
-// A workgroup takes kNdBendFrames rows of ONE stream, counted from its row n0 as the single update counts them: a block's NaN
-// switch sees the rows it would see there.
+// A workgroup takes kNdBendFrames rows of ONE stream, counted from its row n0: a block's NaN switch sees the same rows
+// whichever streams share the step.
 __global__ __launch_bounds__(256, 3) void nd_streams_bend_kernel(const StreamUpdate* __restrict__ u, const int64_t* __restrict__ offs,
                                                                  int64_t n, const int4* __restrict__ tab,
                                                                  const double* __restrict__ gauss, int8_t* __restrict__ bend) {

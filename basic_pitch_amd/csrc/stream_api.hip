@@ -32,24 +32,29 @@
 // bp_stream_keep and bp_stream_keep_rolling give a stream ONE store of retained rows (bp_stream_state::KeptRows): the three
 // maps of its rows (1,760 bytes per row), frequency-constrained, in a ring of `cap` rows, absolute row r at slot r % cap, that
 // holds the last `horizon` rows and the room of a tail (note_device.hip, "the rows a stream retains").  Final rows enter it
-// as they are emitted, the rows of a tail at every update, both through launch_ring_put.  An update (queue_update) decodes
-// rows [a, T), a = max(0, T - horizon), as a whole track — their stats record, the bitmap (12 bytes a row: it depends on
-// both maxima and on the row count) and the bends, all counted from a — and sends home into the caller's host rings the
-// bitmap and the note and bend rows the caller does not hold yet: not the maps.
+// as they are emitted (launch_ring_put), the rows of a tail at every update.  An update decodes rows [a, T),
+// a = max(0, T - horizon), as a whole track — their stats record, the bitmap (12 bytes a row: it depends on both maxima and on
+// the row count) and the bends, all counted from a — and sends home the bitmap and the note and bend rows the caller does not
+// hold yet: not the maps.
 //   * bp_stream_keep reserves cap = horizon = max_rows + a tail's room: the ring never wraps, a stays 0, the caller's linear
 //     arrays are host rings that never wrap either, and a step past max_rows is refused.  The extrema of the final rows are
-//     carried in one record, which they join as they are emitted; an update joins the tail to a copy of it.
+//     carried in one record, which they join as they are emitted; an update joins the tail to a copy of it in the handle's
+//     table of update records.
 //   * bp_stream_keep_rolling reserves horizon_rows + a tail's room.  Rows leave the slice, which one record cannot follow, so
 //     the final rows fill a table of records, one per block of 64 absolute rows, and an update joins the record of the slice
 //     from the table's whole blocks and a scan of the edge rows.  Nothing such a stream owns, sends home or computes per
 //     update grows with its age.
 //
-// bp_streams_candidates is that update for n streams of either mode in one step (queue_updates): one peek step for all tails,
-// one table of streams (StreamUpdate, note_device.hip "the updates of many streams"), the segmented launches, packed rows home.
-//
-// bp_streams_events is that step with nothing sent home (every stream's whole slice stays packed in the handle's buffers) and
-// the tracker of the clips calls behind it (note_track.hip, a segment per stream with the stream's own parameters; clips_api.hip
-// events_reserve / events_queue / events_home): the events and their bends are all that crosses PCIe.
+// Every update is one step of n streams of either mode (queue_updates): one peek step for all tails, one table of streams
+// (StreamUpdate, note_device.hip "the updates of streams"), the segmented launches, and the results packed and linear in the
+// handle's buffers.  What becomes of them is the entry point's (UpdateResults):
+//   * bp_streams_candidates has the packed rows and the records copied home as they lie;
+//   * bp_stream_candidates and bp_stream_candidates_rolling are the step of ONE stream — their own argument checks and
+//     messages, then a table of one — and copy the rows from the packed buffers into the caller's host rings, split where a
+//     ring wraps (copy_to_host_ring);
+//   * bp_streams_events sends nothing home (every stream's whole slice stays packed) and runs the tracker of the clips calls
+//     behind it (note_track.hip, a segment per stream with the stream's own parameters; clips_api.hip events_reserve /
+//     events_queue / events_home): the events and their bends are all that crosses PCIe.
 //
 // A stream's ring, history and kept maps are buffers that free themselves (device_buffer.h): bp_stream_close sets the
 // handle's device and deletes the state, and an open or keep that fails leaves nothing behind.
@@ -82,7 +87,9 @@ struct bp_stream_state {
   bool finished = false, broken = false;
   // bp_stream_keep / bp_stream_keep_rolling: the maps of the last `horizon` rows and a tail's room ([cap] note, onset, contour;
   // absolute row r at slot r % cap), frequency-constrained for `prm`, and the stats records of note_device.hip that carry
-  // their extrema: the record the final rows join (table: the block table of a rolling horizon) and, last, an update's
+  // their extrema: the record the final rows join (table: the block table of a rolling horizon).  The last record of `rec` is
+  // reserved and unused (an update's record lies in the handle's table, h->up_stats); it stays in the documented
+  // bp_stream_state_bytes.
   struct KeptRows {
     int64_t cap = 0, horizon = 0;  // cap == 0: the stream retains nothing
     int64_t limit = INT64_MAX;     // final rows a step may reach: bp_stream_keep reserves no more
@@ -155,7 +162,6 @@ constexpr int64_t kStatsFloats = 4;  // a stats record of note_device.hip: 16 by
 
 Maps rows_from(const Maps& m, int64_t r) { return {m.note + r * kFreqN, m.onset + r * kFreqN, m.contour + r * kFreqC}; }
 int64_t n_records(const bp_stream_state::KeptRows& k) { return k.table ? note_ring_records(k.cap) : 2; }
-float* update_record(const bp_stream_state::KeptRows& k) { return k.rec + (n_records(k) - 1) * kStatsFloats; }
 int64_t kept_bytes(const bp_stream_state* s) {
   return s->kept.cap ? (s->kept.cap * kMapsRow + n_records(s->kept) * kStatsFloats) * 4 : 0;
 }
@@ -366,55 +372,107 @@ int queue_tail(bp_handle h, bp_stream_state* s, int64_t tail_rows, std::vector<W
   return put_rows(h, s, es[0].user, s->rows_out, s->rows_out + tail_rows);
 }
 
-// Rows [r0, r1) from the device to a host ring of ring_rows rows (row r at r % ring_rows).  The source is a device ring of
-// src_rows rows, row r at r % src_rows, or (src_rows = kLinear) a linear block whose first row is r0.  One copy, and one
-// more wherever either ring wraps.
-constexpr int64_t kLinear = 0;
-int copy_to_host_ring(bp_handle h, void* ring, int64_t ring_rows, const void* src, int64_t src_rows, int64_t row_bytes, int64_t r0,
-                      int64_t r1) {
+// Rows [r0, r1), linear on the device with row r0 first, to a host ring of ring_rows rows (row r at r % ring_rows): one copy,
+// and one more wherever the ring wraps.
+int copy_to_host_ring(bp_handle h, void* ring, int64_t ring_rows, const void* src, int64_t row_bytes, int64_t r0, int64_t r1) {
   for (int64_t r = r0; r < r1;) {
-    const int64_t at = r % ring_rows, from = src_rows ? r % src_rows : r - r0;
-    const int64_t n = std::min({r1 - r, ring_rows - at, src_rows ? src_rows - from : r1 - r});
-    BP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ring) + at * row_bytes, static_cast<const uint8_t*>(src) + from * row_bytes,
+    const int64_t at = r % ring_rows, n = std::min(r1 - r, ring_rows - at);
+    BP_HIP(hipMemcpyAsync(static_cast<uint8_t*>(ring) + at * row_bytes, static_cast<const uint8_t*>(src) + (r - r0) * row_bytes,
                           (size_t)(n * row_bytes), hipMemcpyDeviceToHost, h->stream));
     r += n;
   }
   return BP_OK;
 }
 
-// An update of a stream that retains its maps: the tail into the store, the record of the slice [a, T), its bitmap, the
-// bends of the rows from n0 = max(held, a) on, and home into the caller's rings of ring_rows rows — the bitmap of the whole
-// slice, the note rows from n0 on straight from their slots, their bends.
-int queue_update(bp_handle h, bp_stream_state* s, int64_t tail_rows, int64_t held, float* note_ring, uint8_t* bits_ring,
-                 int8_t* bend_ring, int64_t ring_rows, std::vector<WindowSeg>& segs) {
+// What becomes of the results of an update step, which queue_updates leaves packed and linear on the device: the bitmaps of
+// all slices in h->up_bits, the note rows and bends of [new_row, n_rows) in h->up_note / up_bend, the n records in h->up_stats,
+// the prefix arrays behind the table in h->up_tab.
+struct UpdateResults {
+  bool bends;         // the streams whose parameters include bends get them
+  bool records_home;  // the n records go to h->up_stats_host, where [i * 4 + 1] is stream i's NaN flag: the caller's status
+  float* note;        // the packed rows go home into these three as they lie; bits == null: they stay on the device
+  int8_t* bend;
+  uint8_t* bits;
+  // bp_streams_candidates: everything home, packed; bends if the caller gave room for them
+  static UpdateResults packed_home(float* note, int8_t* bend, uint8_t* bits) { return {bend != nullptr, true, note, bend, bits}; }
+  // bp_stream_candidates[_rolling]: the caller copies the rows into host rings; bends if it has a bend ring
+  static UpdateResults for_host_rings(bool bend_ring) { return {bend_ring, true, nullptr, nullptr, nullptr}; }
+  // bp_streams_events: the tracker reads rows and records where they lie
+  static UpdateResults for_tracker() { return {true, false, nullptr, nullptr, nullptr}; }
+};
+
+// An update of n streams that retain their maps (u: the out fields filled, plan_updates; tail[i]: the rows of stream i's peek):
+// the tails of all streams through one peek step into the scratch, the table of streams in one copy, the segmented launches
+// of note_device.hip — the tails into the stores, per stream the record of its slice [a, T), the bitmap, the bends and the
+// note rows from new_row on.  `tab`: the table's host form, alive until the wait.
+int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, const std::vector<int64_t>& tail, int64_t note_rows,
+                  int64_t bits_rows, std::vector<WindowSeg>& segs, std::vector<uint8_t>& tab, const UpdateResults& out) {
   hipStream_t q = h->stream;
-  const auto& k = s->kept;
-  const void* tab = nullptr;
+  const void* bend_tab = nullptr;
   const double* gauss = nullptr;
-  int rc = note_tables(h, &tab, &gauss);
+  int rc = note_tables(h, &bend_tab, &gauss);
   if (rc) return rc;
-  const int64_t T = s->rows_out + tail_rows, a = bp_stream_horizon_first_row(T, k.horizon), n0 = std::max(held, a), n_new = T - n0;
-  const int64_t bits_bytes = (T - a) * BP_NOTE_CAND_ROW_BYTES, bits_room = (bits_bytes + 15) & ~(int64_t)15, bend_bytes = n_new * kFreqN;
-  BP_HIP(h->nd_buf.reserve((size_t)(bits_room + bend_bytes)));
-  uint8_t* d_bits = h->nd_buf;
-  int8_t* d_bend = h->nd_buf.as<int8_t>() + bits_room;
-  if ((rc = queue_tail(h, s, tail_rows, segs))) return rc;
-  const int infer = s->prm.infer_onsets != 0;
-  const bool want_bends = s->prm.include_pitch_bends != 0 && bend_ring != nullptr;
-  float* st = update_record(k);
-  if (k.table) {
-    launch_ring_stats(k.rows, k.cap, a, s->rows_out, T, infer, k.rec, q);
-  } else {  // a copy of the record of the final rows, joined by the tail
-    BP_HIP(hipMemcpyAsync(st, k.rec, kStatsFloats * 4, hipMemcpyDeviceToDevice, q));
-    launch_note_fold(k.rows, k.rows + k.cap * kFreqN, s->rows_out, T, infer, st, q);
+  const size_t m = (size_t)n + 1;
+  tab.assign((size_t)n * sizeof(StreamUpdate) + kStreamUpdatePrefixes * m * sizeof(int64_t), 0);
+  StreamUpdate* d = reinterpret_cast<StreamUpdate*>(tab.data());
+  int64_t* pre = reinterpret_cast<int64_t*>(tab.data() + (size_t)n * sizeof(StreamUpdate));
+  int64_t *pre_tail = pre, *pre_chunk = pre + m, *pre_bits = pre + 2 * m, *pre_bend = pre + 3 * m, *pre_note = pre + 4 * m;
+  // everything the step needs, before anything is queued
+  int64_t tail_rows = 0;
+  for (int64_t t : tail) tail_rows += t;
+  bool bends = false;
+  for (int64_t i = 0; i < n; ++i) bends = bends || (out.bends && u[i].stream->prm.include_pitch_bends != 0 && u[i].n_rows > u[i].new_row);
+  BP_HIP(h->st_out.reserve((size_t)(tail_rows * kMapsRow)));
+  BP_HIP(h->up_tab.reserve(tab.size()));
+  BP_HIP(h->up_note.reserve((size_t)(note_rows * kFreqN)));
+  BP_HIP(h->up_bend.reserve(bends ? (size_t)(note_rows * kFreqN) : 0));
+  BP_HIP(h->up_bits.reserve((size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES)));
+  BP_HIP(h->up_stats.reserve((size_t)(n * kStatsFloats * 4)));
+  BP_HIP(h->up_stats_host.reserve((size_t)(n * kStatsFloats)));
+
+  std::vector<Entry> es;
+  int64_t at = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    bp_stream_state* s = u[i].stream;
+    const auto& k = s->kept;
+    const int64_t t = tail[(size_t)i], T = u[i].n_rows, a = u[i].first_row, n0 = u[i].new_row, R = s->rows_out;
+    const Maps rows = maps_at(h->st_out + at * kMapsRow, t);
+    if (t > 0) es.push_back(plan_entry(s, kPeek, 0, t, rows));
+    at += t;
+    StreamUpdate& e = d[i];
+    e.ring = k.rows;
+    e.tail_note = rows.note, e.tail_onset = rows.onset, e.tail_contour = rows.contour;
+    e.records = k.rec;
+    e.cap = k.cap, e.a = a, e.R = R, e.T = T, e.n0 = n0;
+    e.e0 = a, e.e1 = R;  // a keeping stream: the tail joins a copy of the carried record
+    if (k.table && T > a) note_ring_edges(a, R, T, &e.e0, &e.e1);
+    e.n_tab = k.table ? n_records(k) - 1 : 0;
+    e.note_offset = u[i].note_offset, e.bits_offset = u[i].bits_offset;
+    e.onset_thresh = s->prm.onset_threshold;
+    e.lo = s->lo, e.hi = s->hi, e.infer = s->prm.infer_onsets != 0;
+    e.bends = out.bends && s->prm.include_pitch_bends != 0;
+    pre_tail[i + 1] = pre_tail[i] + t;
+    pre_chunk[i + 1] = pre_chunk[i] + streams_stats_chunks((e.e0 - a) + (T - e.e1));
+    pre_bits[i + 1] = pre_bits[i] + (T - a);
+    pre_bend[i + 1] = pre_bend[i] + (e.bends ? streams_bend_blocks(T - n0) : 0);
+    pre_note[i + 1] = pre_note[i] + (T - n0);
   }
-  launch_ring_peaks(k.rows, k.cap, a, T, infer, s->prm.onset_threshold, st, d_bits, q);
-  if (want_bends) launch_ring_bends(k.rows, k.cap, n0, n_new, tab, gauss, d_bend, q);
+  if (!es.empty() && (rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
+  BP_HIP(hipMemcpyAsync(h->up_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, q));
+  const StreamUpdate* d_tab = h->up_tab.as<StreamUpdate>();
+  const int64_t* d_pre = reinterpret_cast<const int64_t*>(h->up_tab + (size_t)n * sizeof(StreamUpdate));
+  launch_streams_put(d_tab, d_pre, n, tail_rows, q);
   BP_HIP(hipGetLastError());
-  BP_HIP(hipMemcpyAsync(h->nd_stats_host, st, kStatsFloats * 4, hipMemcpyDeviceToHost, q));
-  if ((rc = copy_to_host_ring(h, bits_ring, ring_rows, d_bits, kLinear, BP_NOTE_CAND_ROW_BYTES, a, T))) return rc;
-  if ((rc = copy_to_host_ring(h, note_ring, ring_rows, k.rows, k.cap, kFreqN * 4, n0, T))) return rc;
-  if (want_bends && (rc = copy_to_host_ring(h, bend_ring, ring_rows, d_bend, kLinear, kFreqN, n0, T))) return rc;
+  for (int64_t i = 0; i < n; ++i)  // the A/B library's hook, as put_rows applies it
+    if ((rc = poison_rows(h, u[i].stream, d[i].R, d[i].T))) return rc;
+  launch_streams_candidates(d_tab, d_pre, n, pre_chunk[n], bits_rows, pre_bend[n], note_rows, bend_tab, gauss, h->up_stats, h->up_bits,
+                            h->up_bend, h->up_note, q);
+  BP_HIP(hipGetLastError());
+  if (out.records_home) BP_HIP(hipMemcpyAsync(h->up_stats_host, h->up_stats, (size_t)(n * kStatsFloats * 4), hipMemcpyDeviceToHost, q));
+  if (!out.bits) return BP_OK;
+  BP_HIP(hipMemcpyAsync(out.bits, h->up_bits, (size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES), hipMemcpyDeviceToHost, q));
+  if (note_rows > 0) BP_HIP(hipMemcpyAsync(out.note, h->up_note, (size_t)(note_rows * kFreqN * 4), hipMemcpyDeviceToHost, q));
+  if (bends) BP_HIP(hipMemcpyAsync(out.bend, h->up_bend, (size_t)(note_rows * kFreqN), hipMemcpyDeviceToHost, q));
   return BP_OK;
 }
 
@@ -682,17 +740,33 @@ static int candidates(bp_stream s, const char* what, bool table, int with_tail, 
     return invalid("capacity_rows " + std::to_string(ring_rows) + " is too small for the " + std::to_string(T) + " rows");
   if (T > 0 && (!note_ring || !bits_ring)) return invalid("null output pointer");
   if (int rc = table ? BP_OK : tail_refused(s, what, table, tail_rows)) return rc;
-  *first_row = bp_stream_horizon_first_row(T, s->kept.horizon);
+  const int64_t a = bp_stream_horizon_first_row(T, s->kept.horizon);
+  *first_row = a;
   *n_rows = T;
   *status = s->prm.onset_threshold > 0.0 ? 0 : 1;
   if (T == 0) return BP_OK;
   BP_HIP(hipSetDevice(h->device));
-  std::vector<WindowSeg> segs;  // read by an asynchronous copy: alive until the wait
-  if (int rc = finish(h, queue_update(h, s, tail_rows, held, note_ring, bits_ring, bend_ring, ring_rows, segs))) {
+  // the step of one stream, then from its packed results into the rings: the bitmap of the whole slice, the note rows the
+  // caller does not hold yet, their bends
+  bp_stream_update u{};
+  u.stream = s, u.held_rows = held;
+  u.first_row = a, u.n_rows = T, u.new_row = std::max(held, a);
+  const std::vector<int64_t> tail{tail_rows};
+  std::vector<WindowSeg> segs;  // both read by asynchronous copies: alive until the wait
+  std::vector<uint8_t> tab;
+  const bool want_bends = s->prm.include_pitch_bends != 0 && bend_ring != nullptr;
+  auto queue = [&]() -> int {
+    if (int rc = queue_updates(h, 1, &u, tail, T - u.new_row, T - a, segs, tab, UpdateResults::for_host_rings(bend_ring != nullptr)))
+      return rc;
+    if (int rc = copy_to_host_ring(h, bits_ring, ring_rows, h->up_bits, BP_NOTE_CAND_ROW_BYTES, a, T)) return rc;
+    if (int rc = copy_to_host_ring(h, note_ring, ring_rows, h->up_note, kFreqN * 4, u.new_row, T)) return rc;
+    return want_bends ? copy_to_host_ring(h, bend_ring, ring_rows, h->up_bend, kFreqN, u.new_row, T) : BP_OK;
+  };
+  if (int rc = finish(h, queue())) {
     s->broken = true;
     return rc;
   }
-  if (h->nd_stats_host[1]) *status = 1;  // a NaN in the slice: the host decodes the maps themselves
+  if (h->up_stats_host[1]) *status = 1;  // a NaN in the slice: the host decodes the maps themselves
   return BP_OK;
 }
 
@@ -808,83 +882,6 @@ static int plan_updates(bp_handle h, const char* what, int64_t n, bp_stream_upda
   return BP_OK;
 }
 
-// The step: the tails of all streams through one peek step into the scratch, the table of streams in one copy, the segmented
-// launches of note_device.hip, the packed results and the n records home.  `tab`: the table's host form, alive until the wait.
-// device_only: nothing goes home and every stream whose parameters include bends gets them (bp_streams_events); the packed rows
-// stay in h->up_note / up_bend / up_bits, the records in h->up_stats, the prefix arrays behind the table in h->up_tab.
-static int queue_updates(bp_handle h, int64_t n, const bp_stream_update* u, const std::vector<int64_t>& tail, int64_t note_rows,
-                         int64_t bits_rows, float* note_out, int8_t* bend_out, uint8_t* bits_out, std::vector<WindowSeg>& segs,
-                         std::vector<uint8_t>& tab, bool device_only = false) {
-  hipStream_t q = h->stream;
-  const void* bend_tab = nullptr;
-  const double* gauss = nullptr;
-  int rc = note_tables(h, &bend_tab, &gauss);
-  if (rc) return rc;
-  const size_t m = (size_t)n + 1;
-  tab.assign((size_t)n * sizeof(StreamUpdate) + kStreamUpdatePrefixes * m * sizeof(int64_t), 0);
-  StreamUpdate* d = reinterpret_cast<StreamUpdate*>(tab.data());
-  int64_t* pre = reinterpret_cast<int64_t*>(tab.data() + (size_t)n * sizeof(StreamUpdate));
-  int64_t *pre_tail = pre, *pre_chunk = pre + m, *pre_bits = pre + 2 * m, *pre_bend = pre + 3 * m, *pre_note = pre + 4 * m;
-  // everything the step needs, before anything is queued
-  int64_t tail_rows = 0;
-  for (int64_t t : tail) tail_rows += t;
-  bool bends = false;
-  const bool bends_wanted = bend_out || device_only;
-  for (int64_t i = 0; i < n; ++i) bends = bends || (bends_wanted && u[i].stream->prm.include_pitch_bends != 0 && u[i].n_rows > u[i].new_row);
-  BP_HIP(h->st_out.reserve((size_t)(tail_rows * kMapsRow)));
-  BP_HIP(h->up_tab.reserve(tab.size()));
-  BP_HIP(h->up_note.reserve((size_t)(note_rows * kFreqN)));
-  BP_HIP(h->up_bend.reserve(bends ? (size_t)(note_rows * kFreqN) : 0));
-  BP_HIP(h->up_bits.reserve((size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES)));
-  BP_HIP(h->up_stats.reserve((size_t)(n * kStatsFloats * 4)));
-  BP_HIP(h->up_stats_host.reserve((size_t)(n * kStatsFloats)));
-
-  std::vector<Entry> es;
-  int64_t at = 0;
-  for (int64_t i = 0; i < n; ++i) {
-    bp_stream_state* s = u[i].stream;
-    const auto& k = s->kept;
-    const int64_t t = tail[(size_t)i], T = u[i].n_rows, a = u[i].first_row, n0 = u[i].new_row, R = s->rows_out;
-    const Maps rows = maps_at(h->st_out + at * kMapsRow, t);
-    if (t > 0) es.push_back(plan_entry(s, kPeek, 0, t, rows));
-    at += t;
-    StreamUpdate& e = d[i];
-    e.ring = k.rows;
-    e.tail_note = rows.note, e.tail_onset = rows.onset, e.tail_contour = rows.contour;
-    e.records = k.rec;
-    e.cap = k.cap, e.a = a, e.R = R, e.T = T, e.n0 = n0;
-    e.e0 = a, e.e1 = R;  // a keeping stream: the tail joins a copy of the carried record
-    if (k.table && T > a) note_ring_edges(a, R, T, &e.e0, &e.e1);
-    e.n_tab = k.table ? n_records(k) - 1 : 0;
-    e.note_offset = u[i].note_offset, e.bits_offset = u[i].bits_offset;
-    e.onset_thresh = s->prm.onset_threshold;
-    e.lo = s->lo, e.hi = s->hi, e.infer = s->prm.infer_onsets != 0;
-    e.bends = bends_wanted && s->prm.include_pitch_bends != 0;
-    pre_tail[i + 1] = pre_tail[i] + t;
-    pre_chunk[i + 1] = pre_chunk[i] + streams_stats_chunks((e.e0 - a) + (T - e.e1));
-    pre_bits[i + 1] = pre_bits[i] + (T - a);
-    pre_bend[i + 1] = pre_bend[i] + (e.bends ? streams_bend_blocks(T - n0) : 0);
-    pre_note[i + 1] = pre_note[i] + (T - n0);
-  }
-  if (!es.empty() && (rc = queue_step(h, es, nullptr, BP_MEM_HOST, BP_MEM_DEVICE, segs))) return rc;
-  BP_HIP(hipMemcpyAsync(h->up_tab, tab.data(), tab.size(), hipMemcpyHostToDevice, q));
-  const StreamUpdate* d_tab = h->up_tab.as<StreamUpdate>();
-  const int64_t* d_pre = reinterpret_cast<const int64_t*>(h->up_tab + (size_t)n * sizeof(StreamUpdate));
-  launch_streams_put(d_tab, d_pre, n, tail_rows, q);
-  BP_HIP(hipGetLastError());
-  for (int64_t i = 0; i < n; ++i)  // the A/B library's hook, as put_rows applies it
-    if ((rc = poison_rows(h, u[i].stream, d[i].R, d[i].T))) return rc;
-  launch_streams_candidates(d_tab, d_pre, n, pre_chunk[n], bits_rows, pre_bend[n], note_rows, bend_tab, gauss, h->up_stats, h->up_bits,
-                            h->up_bend, h->up_note, q);
-  BP_HIP(hipGetLastError());
-  if (device_only) return BP_OK;
-  BP_HIP(hipMemcpyAsync(h->up_stats_host, h->up_stats, (size_t)(n * kStatsFloats * 4), hipMemcpyDeviceToHost, q));
-  BP_HIP(hipMemcpyAsync(bits_out, h->up_bits, (size_t)(bits_rows * BP_NOTE_CAND_ROW_BYTES), hipMemcpyDeviceToHost, q));
-  if (note_rows > 0) BP_HIP(hipMemcpyAsync(note_out, h->up_note, (size_t)(note_rows * kFreqN * 4), hipMemcpyDeviceToHost, q));
-  if (bends) BP_HIP(hipMemcpyAsync(bend_out, h->up_bend, (size_t)(note_rows * kFreqN), hipMemcpyDeviceToHost, q));
-  return BP_OK;
-}
-
 int bp_streams_update_layout(bp_handle h, int64_t n, bp_stream_update* u, int with_tail, int64_t* note_rows, int64_t* bits_rows) {
   if (!h) return BP_ERR_INVALID_ARG;
   if (!note_rows || !bits_rows) {
@@ -916,7 +913,7 @@ int bp_streams_candidates(bp_handle h, int64_t n, bp_stream_update* u, int with_
   BP_HIP(hipSetDevice(h->device));
   std::vector<WindowSeg> segs;  // both read by asynchronous copies: alive until the wait
   std::vector<uint8_t> tab;
-  if (int rc = finish(h, queue_updates(h, n, u, tail, note_rows, bits_rows, note_out, bend_out, bits_out, segs, tab))) {
+  if (int rc = finish(h, queue_updates(h, n, u, tail, note_rows, bits_rows, segs, tab, UpdateResults::packed_home(note_out, bend_out, bits_out)))) {
     for (int64_t i = 0; i < n; ++i) u[i].stream->broken = true;
     return rc;
   }
@@ -1006,7 +1003,7 @@ int bp_streams_events(bp_handle h, int64_t n, bp_stream_events* u, int with_tail
   };
   auto queue = [&]() -> int {
     if (int rc = events_reserve(h, job, &plan)) return rc;
-    if (int rc = queue_updates(h, n, up.data(), tail, rows, rows, nullptr, nullptr, nullptr, segs, tab, true)) return rc;
+    if (int rc = queue_updates(h, n, up.data(), tail, rows, rows, segs, tab, UpdateResults::for_tracker())) return rc;
     // the rows before each stream's slice: the table's prefix array of the note rows (new_row = first_row)
     const int64_t* d_pre = reinterpret_cast<const int64_t*>(h->up_tab + (size_t)n * sizeof(StreamUpdate));
     return events_queue(h, job, plan,

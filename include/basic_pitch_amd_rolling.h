@@ -27,7 +27,7 @@ extern "C" {
  *                     other is BP_ERR_INVALID_ARG; horizon_rows < 3 is refused).  The stream then owns cap = horizon_rows +
  *                     2 * 142 rows of 1,760 bytes (the slice and the two windows of a tail; absolute row r lives at slot
  *                     r mod cap) and (cap + 63) / 64 + 3 records of 16 bytes: the two maxima and the NaN flag of every block
- *                     of 64 absolute rows, filled as the rows become final, and the record of an update.  That is all:
+ *                     of 64 absolute rows, filled as the rows become final, and one record that is reserved.  That is all:
  *                     bp_stream_state_bytes grows by cap * 1760 + 16 * ((cap + 63) / 64 + 3) and reads the same after 3
  *                     windows and after 300.  No push is ever refused for the age of the stream.  The decoding parameters
  *                     are fixed here and constrain_frequency is applied to the kept copy, as with bp_stream_keep; the rows

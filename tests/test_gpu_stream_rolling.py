@@ -13,7 +13,7 @@ from oracle import note_oracle as NO
 
 pytestmark = pytest.mark.gpu
 
-HOP = 36164
+HOP, WIN, LEAD = 36164, 43844, 3840
 MAPS = ("note", "onset", "contour")
 DECODING = (0.5, 0.3, 127.70, None, None, False, True, 120)  # predict()'s defaults, as _output_to_notes takes them
 H, CAP = 300, 300 + 2 * 142
@@ -237,9 +237,9 @@ def test_a_rolling_stream_emits_the_bytes_of_a_plain_stream(model, x, prm):
     assert sum(p["note"].shape[0] for p in runs[0]) == 1205
 
 
-def test_rows_go_from_the_device_ring_straight_into_a_host_ring_of_another_size(model, prm):
-    """The note rows of an update are copied home from their slots, split wherever either ring wraps, and the two rings wrap
-    at different rows: H = 200, so 484 slots on the device, beside host rings of 484 + 37 rows.  Twelve pushes of one to two
+def test_rows_reach_a_host_ring_of_another_size_than_the_device_ring(model, prm):
+    """The note rows of an update are gathered from their slots and copied home, split wherever the host ring wraps, and the
+    two rings wrap at different rows: H = 200, so 484 slots on the device, beside host rings of 484 + 37 rows.  Twelve pushes of one to two
     hops of seeded noise (at least 1,562 rows: both rings wrap twice and more); held_rows runs with the final rows.  The new
     rows [max(held_rows, a), T) of an update cross a wrap of the device ring in some updates, of the host ring in others and
     of both in at least one: counted here from the row numbers.  After every update the slice of all three rings is, byte
@@ -272,6 +272,97 @@ def test_rows_go_from_the_device_ring_straight_into_a_host_ring_of_another_size(
         assert s.rows >= 2 * (484 + 37) + 484, s.rows
         assert sum(d for d, _ in wraps) >= 2 and sum(h for _, h in wraps) >= 2 and (True, True) in wraps, wraps
         assert n_events > 0
+
+
+# ---- 3b. the smallest one-stream shapes: a handle of ONE window, so a tail of two windows takes two rounds of the peek step ----
+@pytest.fixture(scope="module")
+def tiny():
+    from basic_pitch_amd.inference import Model
+
+    m = Model(max_windows=1)
+    yield m
+    m.close()
+
+
+def same_bytes(got, want):
+    return all(g.shape == w.shape and g.tobytes() == w.tobytes() for g, w in zip(got, want))
+
+
+def test_a_rolling_stream_alone_on_a_handle_of_one_window(tiny, nat, x, prm):
+    """horizon_rows = 3 (287 slots), nothing final at any update.  One sample: bp_track_n_frames(1) = int(1 / 36164 * 142) = 0
+    rows, so the call returns before the step and writes nothing.  HOP - LEAD = 32,324 samples are the longest signal of one
+    window, 32,325 the shortest of two: 126 rows either way, the slice is rows [123, 126).  Each update is held to the host
+    decoder on the one-shot maps (three rows hold no note of 11 frames: the anchor that bites is the note rows, which with
+    these parameters are the one-shot rows) and, without a bend ring, writes the same note rows and bitmap."""
+    note, bits, bend = rings(3 + 284)
+    note[:], bits[:], bend[:] = -7.0, 7, 99
+    with tiny.open_stream(22050) as s:
+        s.keep_rolling(prm, 3)
+        s.push(x[:1])
+        assert s.candidates_rolling(note, bits, bend, 0) == (0, 0, 0) and s.rows == 0
+        assert (note == -7.0).all() and (bits == 7).all() and (bend == 99).all()
+        at = 1
+        for n, windows in ((HOP - LEAD, 1), (HOP - LEAD + 1, 2)):
+            s.push(x[at:n])
+            at, T = n, int(n / HOP * 142)
+            assert s.rows == 0 and (n + LEAD + HOP - 1) // HOP == windows and T == 126
+            a, T2, status, got = rolling_events(s, note, bits, bend, 0, prm)
+            assert (a, T2, status) == (T - 3, T, 0), n
+            maps = tiny.predict_pcm_raw(x[:n], nat.BP_PCM_F32, n, 1, 22050)
+            assert maps["note"].shape[0] == T and got == slice_events(maps, a, T), n
+            assert np.array_equal(unwrap(note, a, T).view(np.uint32), maps["note"][a:T].view(np.uint32)), n
+            bare = rings(3 + 284)
+            assert s.candidates_rolling(bare[0], bare[1], None, 0) == (a, T, 0)  # a null bend ring: the bends are skipped
+            assert same_bytes([unwrap(r, a, T) for r in bare[:2]], [unwrap(r, a, T) for r in (note, bits)]), n
+            assert (bend[a:T] != 99).all()  # the call with a bend ring wrote its bends (-25 ... 25)
+
+
+def test_a_keeping_stream_alone_on_a_handle_of_one_window(tiny, nat, x, prm):
+    """max_rows = 142 (426 slots).  40,004 = WIN - LEAD samples complete window 0: one window final, a tail of one window,
+    T = int(40,004 / 36,164 * 142) = 157; at 72,000 samples the tail is two windows and T = 282 (window 1 completes at 76,168
+    samples, which max_rows = 142 would refuse).  Each update is the host decoder's answer on the one-shot maps.  A second
+    stream is finished at 36,164 samples, the 142 rows max_rows allows (two windows, none complete before the finish): there
+    with_tail changes nothing, and with every final row held the note and bend arrays come back as they went in while the
+    bitmap of the whole slice is written."""
+    from basic_pitch_amd import note_creation as nc
+
+    def update(s, n, held=0, **kw):
+        """-> (T, the three arrays, the events as slice_events gives them without the frames)"""
+        out = rings(142 + 284)
+        T, status = s.candidates(out[0], out[1], out[2], held, **kw)
+        assert status == 0 and T == int(n / HOP * 142), n
+        return T, out, as_tuples(nc.decode_candidates(out[0][:T], out[1][:T], out[2][:T], prm))
+
+    with tiny.open_stream(22050) as s:
+        s.keep(prm, 142)
+        at = 0
+        for n, tail_windows, T_want in ((WIN - LEAD, 1, 157), (72_000, 2, 282)):
+            s.push(x[at:n])
+            at = n
+            assert s.rows == 142 and (n + LEAD + HOP - 1) // HOP - 1 == tail_windows
+            T, out, got = update(s, n)
+            maps = tiny.predict_pcm_raw(x[:n], nat.BP_PCM_F32, n, 1, 22050)
+            ref = slice_events(maps, 0, T)
+            print(f"{n} samples: {T} rows, {len(got)} events, {len(ref)} in the reference")
+            assert T == T_want == maps["note"].shape[0] and got == [r[2:] for r in ref], n
+            assert np.array_equal(out[0][:T].view(np.uint32), maps["note"].view(np.uint32)), n
+            bare = rings(142 + 284)
+            assert s.candidates(bare[0], bare[1], None, 0) == (T, 0)  # a null bend ring: the bends are skipped
+            assert same_bytes(bare[:2], out[:2]) and not bare[2].any() and out[2][:T].any(), n
+        assert len(ref) >= 1
+    with tiny.open_stream(22050) as s:
+        s.keep(prm, 142)
+        s.push(x[:HOP])
+        assert s.rows == 0 and s.finish()["note"].shape[0] == 142 == s.rows
+        T, out, got = update(s, HOP)
+        maps = tiny.predict_pcm_raw(x[:HOP], nat.BP_PCM_F32, HOP, 1, 22050)
+        assert T == 142 and got == [r[2:] for r in slice_events(maps, 0, T)]
+        T2, final_only, _ = update(s, HOP, with_tail=False)
+        assert T2 == T and same_bytes(final_only, out)
+        held = rings(142 + 284)
+        held[0][:], held[2][:] = -7.0, 99
+        assert s.candidates(held[0], held[1], held[2], s.rows) == (T, 0)
+        assert (held[0] == -7.0).all() and (held[2] == 99).all() and same_bytes(held[1:2], out[1:2])
 
 
 # ---- 4. bounded ------------------------------------------------------------------------------------------------------------------

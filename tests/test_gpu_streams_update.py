@@ -3,7 +3,10 @@ include/basic_pitch_amd_update.h; streaming.transcripts): for every stream of th
 rows and the bitmap of the slice are byte for byte what the single-stream update — bp_stream_candidates for a keeping stream,
 bp_stream_candidates_rolling for a rolling one — writes with the same held_rows, for any set, order and mixture of streams,
 and nothing is committed.  An update changes no counter, so the same streams serve both sides of every comparison: the
-many-stream call first, the single calls after it.  Every test does ordinary work; refusals are argument errors.
+many-stream call first, the single calls after it.  The single update is the many-stream step with one stream, so the
+comparison holds a step to its own n = 1 case; what holds both to the decoder is the host anchor of the first test: the
+events of every update are the host decoder's on the same rows of the one-shot maps.  Every test does ordinary work; refusals
+are argument errors.
 
 Not provoked here, because no legitimate input reaches them: a broken stream (it takes a failed device call) and a tail that
 does not fit the ring (tail_refused's verdict, which no supported rate produces); both are the single calls' own checks."""
@@ -77,13 +80,31 @@ def x():
     return melody()
 
 
+# the three parameter sets, as note_creation._note_params and note_creation._decode take them
+PRM_ARGS = {"a": (0.5, 0.3, 11, True, None, None, True, 11, True),
+            "b": (0.4, 0.3, 11, True, 2000.0, 100.0, True, 11, True),
+            "c": (0.5, 0.3, 11, False, None, None, True, 11, False)}
+
+
 @pytest.fixture(scope="module")
 def prms():
     from basic_pitch_amd import note_creation as nc
 
-    return {"a": nc._note_params(0.5, 0.3, 11, True, None, None, True, 11, True),
-            "b": nc._note_params(0.4, 0.3, 11, True, 2000.0, 100.0, True, 11, True),
-            "c": nc._note_params(0.5, 0.3, 11, False, None, None, True, 11, False)}
+    return {k: nc._note_params(*v) for k, v in PRM_ARGS.items()}
+
+
+def slice_events(maps, a, T, args):
+    """slice_events of tests/test_gpu_stream_rolling.py for any parameter set: bp_notes_decode on copies of rows [a, T) of the
+    one-shot maps as a whole track, frames shifted by a, times of the absolute frames, in the form of as_tuples (no bends:
+    None)."""
+    from basic_pitch_amd import note_creation as nc
+
+    sl = [np.ascontiguousarray(maps[m][a:T]).copy() for m in ("note", "onset", "contour")]
+    ev, bends, n = nc._decode(*sl, *args)
+    times = nc.model_frames_to_time(T + 1)
+    return [(times[e.start_frame + a].tobytes(), times[e.end_frame + a].tobytes(), int(e.pitch_midi),
+             np.float32(e.amplitude).tobytes(), bends[e.bend_offset : e.bend_offset + e.n_bends].tolist() if args[-1] else None)
+            for e in ev[:n]]
 
 
 class Sess:
@@ -92,14 +113,15 @@ class Sess:
 
     def __init__(self, model, nat, spec, prms, x):
         mode, rows, rate, key, self.totals, self.finishes = spec
-        self.rolling, self.prm, self.rate = mode == "roll", prms[key], rate
+        self.rolling, self.prm, self.key, self.rate = mode == "roll", prms[key], key, rate
         if rate == 44100:
             up = np.repeat(x[:150_000], 2)
             self.pcm = np.stack([np.round(up * 24000), np.round(up * 12000)], axis=1).astype(np.int16)
-            self.s = model.open_stream(44100, 2, nat.BP_PCM_S16)
+            self.fmt, self.channels = nat.BP_PCM_S16, 2
         else:
             self.pcm = x
-            self.s = model.open_stream(22050)
+            self.fmt, self.channels = nat.BP_PCM_F32, 1
+        self.s = model.open_stream(rate, self.channels, self.fmt)
         if self.rolling:
             self.s.keep_rolling(self.prm, rows)
             self.ring_rows = rows + 284
@@ -135,6 +157,10 @@ class Sess:
             return self.s.candidates_rolling(note, bits, bend, held)
         T, status = self.s.candidates(note, bits, bend, held)
         return 0, T, status
+
+    def one_shot(self, model):
+        """The one-shot maps of the audio fed so far, in the stream's own format, channels and rate."""
+        return model.predict_pcm_raw(self.pcm[: self.at], self.fmt, self.at, self.channels, self.rate)
 
     def close(self):
         self.s.close()
@@ -201,7 +227,7 @@ def test_every_stream_gets_the_bytes_of_its_single_update(model, nat, prms, x):
     from basic_pitch_amd import streaming
 
     ss = open_set(model, nat, prms, x, 0)
-    tails, n_events, wrapped = [], 0, False
+    tails, n_events, wrapped, anchors = [], 0, False, {}
     try:
         for rnd in range(4):
             for s in ss:
@@ -231,6 +257,13 @@ def test_every_stream_gets_the_bytes_of_its_single_update(model, nat, prms, x):
                 ev = [nc.decode_candidates(unwrap(r[0], a, T), unwrap(r[1], a, T), unwrap(r[2], a, T) if bends else None, s.prm,
                                            first_frame=a) for r in (s.mine, s.ref)]
                 assert as_tuples(ev[0]) == as_tuples(ev[1]), (rnd, i)
+                # the host anchor: the host decoder on rows [a, T) of the one-shot maps of the audio fed so far
+                if (i, s.at) not in anchors:
+                    maps = s.one_shot(model)
+                    assert maps["note"].shape[0] == T, (rnd, i)
+                    anchors[i, s.at] = slice_events(maps, a, T, PRM_ARGS[s.key])
+                print(f"round {rnd} stream {i}: {len(ev[0])} events, {len(anchors[i, s.at])} in the host reference")
+                assert as_tuples(ev[0]) == anchors[i, s.at], (rnd, i)
                 n_events += len(ev[1])
             assert (tab[5].n_rows, tab[5].note_offset, tab[5].bits_offset) == (0, tab[6].note_offset, tab[6].bits_offset)
             assert tab[6].first_row == 192 and tab[6].n_rows == 392
