@@ -15,6 +15,7 @@ BP_OK = 0
 BP_ERR_INVALID_ARG = -1
 BP_ERR_OUT_OF_MEMORY = -5
 BP_ERR_UNSUPPORTED = -6
+BP_ERR_BAD_AUDIO = -7
 BP_MEM_HOST = 0
 BP_MEM_DEVICE = 1
 BP_FLAG_STAGE_TIMING = 1
@@ -30,6 +31,7 @@ BP_PCM_F32, BP_PCM_S16, BP_PCM_S24, BP_PCM_S32, BP_PCM_U8, BP_PCM_F64 = range(6)
 BP_PCM_WAV = {BP_PCM_U8: (1, 8), BP_PCM_S16: (1, 16), BP_PCM_S24: (1, 24), BP_PCM_S32: (1, 32), BP_PCM_F32: (3, 32),
               BP_PCM_F64: (3, 64)}
 BP_N_STAGES = 15
+BP_FILES_CLIP_MAX_WINDOWS = 15  # the longest file, in windows, that bp_transcribe_params.clip_batch sends to a batched call
 BP_Z_ROW = 448
 BP_Z_ROWS = 174
 BP_Z_PAD = 56
@@ -119,7 +121,7 @@ class bp_transcribe_params(C.Structure):
         ("host_decode", C.c_int32),
         ("direct_io", C.c_int32),
         ("host_flac", C.c_int32),
-        ("reserved", C.c_int32 * 1),
+        ("clip_batch", C.c_int32),
     ]
 
 
@@ -195,6 +197,8 @@ EXPORTED_SYMBOLS = [
     "bp_files_release_buffers",
     "bp_files_direct_reads",
     "bp_files_read_probe",
+    "bp_files_batched",
+    "bp_files_batch_probe",
     "bp_track_n_windows",
     "bp_handle_track_n_windows",
     "bp_handle_track_n_frames",
@@ -354,6 +358,11 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bp_files_direct_reads.restype = C.c_int64
     lib.bp_files_read_probe.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_int)]
     lib.bp_files_read_probe.restype = C.c_int64
+    lib.bp_files_batched.argtypes = []
+    lib.bp_files_batched.restype = C.c_int64
+    lib.bp_files_batch_probe.argtypes = [C.POINTER(vp), C.c_int, C.POINTER(C.c_char_p), i64, C.POINTER(bp_transcribe_params),
+                                         C.POINTER(C.c_int32)]
+    lib.bp_files_batch_probe.restype = C.c_int
     lib.bp_handle_track_n_windows.argtypes = [vp, i64]
     lib.bp_handle_track_n_windows.restype = i64
     lib.bp_handle_track_n_frames.argtypes = [vp, i64]

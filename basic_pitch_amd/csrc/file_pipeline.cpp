@@ -30,7 +30,7 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
-#include "../../include/basic_pitch_amd.h"
+#include "../../include/basic_pitch_amd_flac_clips.h"
 
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);  // flac_decode.cpp
 
@@ -50,23 +50,53 @@ struct WavInfo {
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
 
-bool wav_parse(const uint8_t* d, size_t n, WavInfo& w) {
-  if (n < 12 || std::memcmp(d, "RIFF", 4) != 0 || std::memcmp(d + 8, "WAVE", 4) != 0) {
+// The bytes of a file by position: the whole file in memory, or an open file of which only the bytes asked for are read
+// (bp_files_batch_probe and the batching workers decide a file's route from its headers alone).
+struct ByteSource {
+  const uint8_t* mem = nullptr;
+  int fd = -1;
+  size_t size = 0;
+  bool at(size_t pos, size_t len, uint8_t* out) const {  // [pos, pos + len) lies inside the file
+    if (mem) {
+      std::memcpy(out, mem + pos, len);
+      return true;
+    }
+    size_t done = 0;
+    while (done < len) {
+      const ssize_t got = pread(fd, out + done, len - done, (off_t)(pos + done));
+      if (got < 0 && errno == EINTR) continue;
+      if (got <= 0) {
+        g_file_error = got < 0 ? std::string("read failed: ") + std::strerror(errno) : "the file is shorter than its size";
+        return false;
+      }
+      done += (size_t)got;
+    }
+    return true;
+  }
+};
+
+// the chunk walk of a RIFF/WAVE file: the format and where the samples lie (data_pos; w.pcm is the caller's to set).  Reads
+// the 12-byte head, every chunk's 8-byte head and up to 26 bytes of a fmt chunk, nothing else.
+bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos) {
+  const size_t n = src.size;
+  uint8_t head[12], body[26];
+  if (n < 12 || !src.at(0, 12, head) || std::memcmp(head, "RIFF", 4) != 0 || std::memcmp(head + 8, "WAVE", 4) != 0) {
     g_file_error = "not a RIFF/WAVE file";
     return false;
   }
   size_t pos = 12;
   bool have_fmt = false, have_data = false;
   while (pos + 8 <= n) {
-    const uint32_t size = rd32(d + pos + 4);
-    const uint8_t* body = d + pos + 8;
+    if (!src.at(pos, 8, head)) return false;
+    const uint32_t size = rd32(head + 4);
     const size_t avail = n - (pos + 8) < size ? n - (pos + 8) : size;  // a truncated last chunk: what is there
-    if (std::memcmp(d + pos, "fmt ", 4) == 0 && avail >= 16) {
+    if (std::memcmp(head, "fmt ", 4) == 0 && avail >= 16) {
+      if (!src.at(pos + 8, avail < 26 ? avail : 26, body)) return false;
       w.tag = rd16(body), w.channels = rd16(body + 2), w.sample_rate = (int)rd32(body + 4), w.bits = rd16(body + 14);
       if (w.tag == 0xFFFE && avail >= 26) w.tag = rd16(body + 24);  // the real tag sits in the GUID
       have_fmt = true;
-    } else if (std::memcmp(d + pos, "data", 4) == 0) {
-      w.pcm = body, w.pcm_bytes = avail;
+    } else if (std::memcmp(head, "data", 4) == 0) {
+      data_pos = pos + 8, w.pcm_bytes = avail;
       have_data = true;
     }
     pos += 8 + (size_t)size + (size & 1);
@@ -88,6 +118,15 @@ bool wav_parse(const uint8_t* d, size_t n, WavInfo& w) {
     return false;
   }
   w.n_frames = (int64_t)(w.pcm_bytes / (size_t)width) / w.channels;
+  return true;
+}
+
+bool wav_parse(const uint8_t* d, size_t n, WavInfo& w) {
+  ByteSource src;
+  src.mem = d, src.size = n;
+  size_t data_pos = 0;
+  if (!wav_walk(src, w, data_pos)) return false;
+  w.pcm = d + data_pos;
   return true;
 }
 
@@ -486,6 +525,106 @@ int wav_pcm_format(const WavInfo& w) {
   return w.bits == 32 ? BP_PCM_F32 : BP_PCM_F64;
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// Batches of short files (params.clip_batch > 0).  A worker claims a run of files, decides every file's
+// route from its headers, and takes the short ones through one clips-events call per container and sample rate; every
+// other file, and every file a call could not finish, goes the per-file route below, unchanged.
+//
+// What a worker holds is bounded whatever the caller asks for: a run has at most kClipBatchMax files, and the files of
+// one lane acquisition have at most kClipBatchBytes of file bytes (the worker's page-locked batch buffer) and
+// kClipBatchWindows windows (the lane's maps on the device: 142 rows of 440 floats a window); a run that passes either is
+// taken in several parts.
+constexpr int64_t kClipBatchMax = 1024;
+constexpr size_t kClipBatchBytes = (size_t)64 << 20;
+constexpr int64_t kClipBatchWindows = 1024;
+
+std::atomic<int64_t> g_batched{0};  // files whose outputs came from a batched call since the library was loaded
+
+struct ClipFile {
+  int route = 0;  // 0: the per-file route; 1: a batched PCM call; 2: a batched FLAC call; negative: a bp_status
+  int channels = 0, sample_rate = 0, format = BP_PCM_F32;
+  int64_t n_frames = 0, windows = 0;
+  size_t data_pos = 0;  // WAV: where the samples lie in the file
+};
+
+// the windows of n_frames frames at sample_rate at the lanes' geometry (no handle: that of the default mode)
+int64_t clip_windows(bp_handle h, int64_t n_frames, int sample_rate) {
+  return h ? bp_handle_track_n_windows(h, bp_handle_resampled_length(h, n_frames, sample_rate))
+           : bp_track_n_windows(bp_resampled_length(n_frames, sample_rate));
+}
+
+// The one place that decides a file's route, from its headers: the probe asks with an open file, a worker once with the open
+// file (before it reads anything else) and once more with the bytes it then read.  A file whose channels or rate the clips
+// calls would refuse (check_ingest: 1 - 64 channels, 1,000 - 768,000 Hz) keeps the per-file route, which reports it.
+// the jobs whose maps the host decodes (host_decode, or an onset threshold <= 0, with which every clip of a clips call has
+// status 1): nothing of them is batched
+bool host_decodes(const bp_transcribe_params& prm) { return prm.host_decode || !(prm.notes.onset_threshold > 0.0); }
+
+int clip_route(const ByteSource& src, bp_handle h, const bp_transcribe_params& prm, ClipFile& c) {
+  c = ClipFile{};
+  uint8_t magic[12] = {0};
+  if (src.size && !src.at(0, src.size < 12 ? src.size : 12, magic)) return c.route = BP_ERR_BAD_AUDIO;
+  auto in_domain = [&]() { return c.channels >= 1 && c.channels <= 64 && c.sample_rate >= 1000 && c.sample_rate <= 768000; };
+  if (src.size >= 12 && std::memcmp(magic, "RIFF", 4) == 0 && std::memcmp(magic + 8, "WAVE", 4) == 0) {
+    WavInfo w;
+    if (!wav_walk(src, w, c.data_pos)) return c.route = BP_ERR_BAD_AUDIO;
+    c.channels = w.channels, c.sample_rate = w.sample_rate, c.n_frames = w.n_frames, c.format = wav_pcm_format(w);
+    if (host_decodes(prm) || !in_domain() || src.size > kClipBatchBytes) return c.route = 0;
+    c.windows = clip_windows(h, c.n_frames, c.sample_rate);  // a file without frames: a clip without rows
+    return c.route = c.windows <= BP_FILES_CLIP_MAX_WINDOWS ? 1 : 0;
+  }
+  if (src.size >= 4 && (std::memcmp(magic, "fLaC", 4) == 0 || std::memcmp(magic, "ID3", 3) == 0)) {
+    if (host_decodes(prm) || prm.host_flac) return c.route = 0;
+    // STREAMINFO lies in the metadata in front of the first frame: from memory as it is, from a file a prefix that grows
+    // until the metadata fits in it (a parse that succeeds has read nothing behind the metadata)
+    bp_flac_stream_layout lay;
+    int rc = BP_ERR_BAD_AUDIO;
+    if (src.mem) {
+      rc = bp_flac_layout(src.mem, src.size, &lay);
+    } else {
+      std::vector<uint8_t> head;
+      for (size_t want = (size_t)64 << 10; rc != BP_OK; want *= 4) {
+        const size_t n = want < src.size ? want : src.size;
+        head.resize(n);
+        if (!src.at(0, n, head.data())) return c.route = BP_ERR_BAD_AUDIO;
+        rc = bp_flac_layout(head.data(), n, &lay);
+        if (n == src.size) break;
+      }
+    }
+    if (rc != BP_OK) {
+      g_file_error = bp_audio_last_error();
+      return c.route = BP_ERR_BAD_AUDIO;
+    }
+    c.channels = lay.channels, c.sample_rate = lay.sample_rate, c.n_frames = lay.n_frames, c.format = BP_PCM_S16;
+    // the streams the device decoders leave to the host (bp_infer_flac; the clips call's scratch bound)
+    if (!bp_internal_flac_device_supported(&lay, src.size) || (size_t)lay.audio_start >= src.size || src.size < 42) return c.route = 0;
+    if (((lay.n_frames + lay.min_block - 1) / lay.min_block + 1) * lay.max_block > 8 * lay.n_frames + 2 * (int64_t)lay.max_block) return c.route = 0;
+    if (!in_domain() || src.size > kClipBatchBytes) return c.route = 0;
+    c.windows = clip_windows(h, c.n_frames, c.sample_rate);
+    return c.route = c.windows >= 1 && c.windows <= BP_FILES_CLIP_MAX_WINDOWS ? 2 : 0;
+  }
+  g_file_error = "not a WAV or FLAC file (the native pipeline reads RIFF/WAVE and FLAC)";
+  return c.route = BP_ERR_BAD_AUDIO;
+}
+
+// the route of the file at `path`, read from its headers alone
+int clip_route_of_path(const std::string& path, bp_handle h, const bp_transcribe_params& prm, ClipFile& c, size_t* size) {
+  c = ClipFile{};
+  const int fd = open(path.c_str(), O_RDONLY | O_CLOEXEC);
+  struct stat st;
+  if (fd < 0 || fstat(fd, &st) != 0 || !S_ISREG(st.st_mode)) {
+    if (fd >= 0) close(fd);
+    g_file_error = path + " is not a file path.";
+    return c.route = BP_ERR_BAD_AUDIO;
+  }
+  ByteSource src;
+  src.fd = fd, src.size = (size_t)st.st_size;
+  if (size) *size = src.size;
+  const int route = clip_route(src, h, prm, c);
+  close(fd);
+  return route;
+}
+
 // inference.py:401-404: never overwrite.  O_EXCL makes the existence check and the creation one step (two processes
 // writing into the same directory cannot both win), and a short or failed write removes the partial file, so that a retry
 // does not find a corpse and report "already exists".
@@ -579,6 +718,31 @@ extern "C" {
 const char* bp_files_last_error(void) { return g_file_error.c_str(); }
 
 int64_t bp_files_direct_reads(void) { return g_direct_reads.load(std::memory_order_relaxed); }
+
+int64_t bp_files_batched(void) { return g_batched.load(std::memory_order_relaxed); }
+
+// The route every file would take in a job with params->clip_batch > 0, from its headers alone: the function the workers ask.
+int bp_files_batch_probe(bp_handle* handles, int n_handles, const char* const* paths, int64_t n_files,
+                         const bp_transcribe_params* params, int32_t* route) {
+  if (n_handles < 0 || (n_handles > 0 && (!handles || !handles[0])) || n_files < 0 || (n_files && (!paths || !route)) || !params) {
+    g_file_error = "bp_files_batch_probe: null pointer or bad count";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (params->clip_batch < 0) {
+    g_file_error = "bp_files_batch_probe: negative clip_batch";
+    return BP_ERR_INVALID_ARG;
+  }
+  for (int64_t i = 0; i < n_files; ++i) {
+    ClipFile c;
+    if (!paths[i]) {
+      g_file_error = "bp_files_batch_probe: null path";
+      return BP_ERR_INVALID_ARG;
+    }
+    // (a job whose maps the host decodes opens no file here: the per-file route reads and reports every one of them)
+    route[i] = host_decodes(*params) ? 0 : clip_route_of_path(paths[i], n_handles > 0 ? handles[0] : nullptr, *params, c, nullptr);
+  }
+  return BP_OK;
+}
 
 // The pipeline's file reader on its own, into ordinary page-aligned host memory (no device needed): the file's length, a
 // 64-bit FNV-1a of its bytes and whether O_DIRECT was really used — what the CPU tests compare with Python's read.
@@ -687,6 +851,10 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
     g_file_error = "bp_transcribe_files: null pointer or bad count";
     return BP_ERR_INVALID_ARG;
   }
+  if (params->clip_batch < 0) {
+    g_file_error = "bp_transcribe_files: negative clip_batch";
+    return BP_ERR_INVALID_ARG;
+  }
   for (int i = 0; i < n_handles; ++i)
     if (!handles[i]) {
       g_file_error = "bp_transcribe_files: null handle";
@@ -753,10 +921,8 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
     std::vector<int32_t> bends;
     std::vector<uint8_t> midi;
     std::string csv;
-    for (;;) {
-      const int64_t i = next.fetch_add(1);
-      if (i >= n_files) break;
-      if (dup[(size_t)i]) continue;
+    // the per-file route: one file from its bytes to its outputs
+    auto one_file = [&](const int64_t i) {
       bp_file_report* rep = &reports[i];
       rep->n_note_events = 0, rep->n_frames = 0;
       rep->ms_read = rep->ms_lane_wait = rep->ms_device = rep->ms_notes = rep->ms_write = 0.0f;
@@ -773,12 +939,12 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
       if ((prm.save_midi && stat((base + "mid").c_str(), &st) == 0) || (prm.save_notes && stat((base + "csv").c_str(), &st) == 0)) {
         set_report(rep, BP_ERR_INVALID_ARG,
                    two_path_message("", base + "*", " already exists and would be overwritten. Skipping output files for ", path, "."));
-        continue;
+        return;
       }
       size_t n_bytes = 0;
       if (!read_file_pinned(path, file, n_bytes, prm.direct_io != 0)) {
         set_report(rep, BP_ERR_BAD_AUDIO, g_file_error);
-        continue;
+        return;
       }
       const uint8_t* fb = static_cast<const uint8_t*>(file.p);
       int channels = 0, sr = 0, format = BP_PCM_F32;
@@ -808,7 +974,7 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
         WavInfo w;
         if (!wav_parse(fb, n_bytes, w)) {
           set_report(rep, BP_ERR_BAD_AUDIO, path + ": " + g_file_error);
-          continue;
+          return;
         }
         // the samples go to the device as the file stores them (bp_infer_pcm_raw converts there)
         channels = w.channels, sr = w.sample_rate, n_frames = w.n_frames, pcm = w.pcm, format = wav_pcm_format(w);
@@ -821,17 +987,17 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
           flac_on_device = true;
           channels = lay.channels, sr = lay.sample_rate, n_frames = lay.n_frames;
         } else if (!host_flac_decode()) {
-          continue;
+          return;
         }
       } else {
         set_report(rep, BP_ERR_BAD_AUDIO, path + ": not a WAV or FLAC file (the native pipeline reads RIFF/WAVE and FLAC)");
-        continue;
+        return;
       }
 
       const int64_t T = bp_handle_track_n_frames(handles[0], bp_handle_resampled_length(handles[0], n_frames, sr));
       if (T > 0 && !maps.ensure((size_t)T * (88 + 88 + 264) * sizeof(float))) {
         set_report(rep, BP_ERR_OUT_OF_MEMORY, path + ": " + g_file_error);
-        continue;
+        return;
       }
       float* note = static_cast<float*>(maps.p);
       float* onset = note + T * 88;
@@ -878,10 +1044,10 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
         }
         rep->ms_read += lap();
       }
-      if (reported) continue;
+      if (reported) return;
       if (rc != BP_OK) {
         set_report(rep, rc, path + ": " + err);
-        continue;
+        return;
       }
       rep->n_frames = T;
 
@@ -900,7 +1066,7 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
       }
       if (rc != BP_OK) {
         set_report(rep, rc, path + ": " + bp_notes_last_error());
-        continue;
+        return;
       }
       rep->n_note_events = (int32_t)n_ev;
       rep->ms_notes = lap();
@@ -917,10 +1083,187 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
       }
       if (!ok) {
         set_report(rep, BP_ERR_INVALID_ARG, g_file_error);
-        continue;
+        return;
       }
       rep->ms_write = lap();
       set_report(rep, BP_OK, "");
+    };
+    if (prm.clip_batch <= 0) {
+      for (;;) {
+        const int64_t i = next.fetch_add(1);
+        if (i >= n_files) break;
+        if (!dup[(size_t)i]) one_file(i);
+      }
+      return;
+    }
+
+    // ---- params.clip_batch > 0: runs of files, the short ones in batched calls -------------------------------------------------
+    struct Member {
+      int64_t index;
+      ClipFile c;
+      size_t size, offset, n_bytes;  // the file's size by its headers; where its bytes lie in `batch`; the bytes read
+      int64_t rows;
+    };
+    struct Group {  // the files of one clips-events call: one container, one sample rate
+      std::vector<size_t> members;
+      std::vector<bp_note_event> events;
+      std::vector<int32_t> bends;
+      std::vector<int64_t> offsets;
+      std::vector<int> status;
+      int rc = BP_OK;
+      float ms_device = 0.0f;
+    };
+    Pinned batch;  // the bytes of a part's short files, each from a 4 KiB boundary (O_DIRECT reads land there)
+    std::vector<Member> part;
+    std::vector<int64_t> later;  // files of the part that take the per-file route after all
+    size_t part_bytes = 0;
+    int64_t part_windows = 0;
+    constexpr size_t kAlign = 4096;
+    auto slot_bytes = [](size_t size) { return (size + kAlign - 1) / kAlign * kAlign + kAlign; };
+    // one part: its files' bytes, one lane acquisition, one call per group, the outputs; then the files left to the per-file route
+    auto flush = [&]() {
+      if (part.empty()) return;
+      later.clear();
+      auto clock = std::chrono::steady_clock::now();
+      auto lap = [&clock]() {
+        const auto t = std::chrono::steady_clock::now();
+        const float ms = std::chrono::duration<float, std::milli>(t - clock).count();
+        clock = t;
+        return ms;
+      };
+      std::map<std::pair<int, int>, Group> groups;
+      std::vector<char> in_group(part.size(), 0);
+      if (batch.ensure(part_bytes)) {
+        uint8_t* base = static_cast<uint8_t*>(batch.p);
+        size_t at = 0;
+        for (size_t k = 0; k < part.size(); ++k) {
+          Member& m = part[k];
+          m.offset = at;
+          const size_t room = slot_bytes(m.size);
+          at += room;
+          // (a file that grew since its headers were read does not fit its slot: the per-file route takes it)
+          const bool ok = read_file_into(paths[m.index], [&](size_t bytes) -> void* { return bytes <= room ? base + m.offset : nullptr; },
+                                         m.n_bytes, prm.direct_io != 0);
+          ByteSource src;
+          src.mem = base + m.offset, src.size = m.n_bytes;
+          const int route = m.c.route;
+          if (!ok || clip_route(src, handles[0], prm, m.c) != route) continue;  // the bytes read decide, as the headers did
+          m.rows = bp_handle_track_n_frames(handles[0], bp_handle_resampled_length(handles[0], m.c.n_frames, m.c.sample_rate));
+          groups[{route, m.c.sample_rate}].members.push_back(k);
+          in_group[k] = 1;
+        }
+      }
+      for (size_t k = 0; k < part.size(); ++k)
+        if (!in_group[k]) later.push_back(part[k].index);
+      size_t n_grouped = part.size() - later.size();
+      const float ms_read = n_grouped ? lap() / (float)n_grouped : 0.0f;
+      float ms_wait = 0.0f;
+      if (n_grouped) {
+        const int lane = acquire();
+        ms_wait = lap() / (float)n_grouped;
+        bp_handle h = handles[lane];
+        const uint8_t* base = static_cast<const uint8_t*>(batch.p);
+        for (auto& kv : groups) {
+          Group& g = kv.second;
+          const int64_t n = (int64_t)g.members.size();
+          const bool flac = kv.first.first == 2;
+          std::vector<bp_clip> pcm_clips;
+          std::vector<bp_flac_clip> flac_clips;
+          int64_t rows = 0;
+          for (size_t k : g.members) {
+            const Member& m = part[k];
+            rows += m.rows;
+            if (flac) flac_clips.push_back(bp_flac_clip{base + m.offset, m.n_bytes});
+            else pcm_clips.push_back(bp_clip{base + m.offset + m.c.data_pos, m.c.n_frames, m.c.format, m.c.channels});
+          }
+          g.offsets.assign((size_t)n + 1, 0), g.status.assign((size_t)n, 0);
+          int64_t cap_ev = std::max<int64_t>(256, rows / 2), cap_b = std::max<int64_t>(4096, 8 * rows);
+          for (int attempt = 0; attempt < 2; ++attempt) {
+            g.events.resize((size_t)cap_ev), g.bends.resize((size_t)cap_b);
+            g.rc = flac ? bp_infer_flac_clips_events(h, n, flac_clips.data(), kv.first.second, &prm.notes, g.events.data(), cap_ev,
+                                                     g.bends.data(), cap_b, g.offsets.data(), g.status.data())
+                        : bp_infer_clips_events(h, n, pcm_clips.data(), kv.first.second, BP_MEM_HOST, &prm.notes, g.events.data(),
+                                                cap_ev, g.bends.data(), cap_b, g.offsets.data(), g.status.data());
+            if (g.rc != BP_ERR_INVALID_ARG) break;
+            // "needs more room": the message holds both totals (event_offsets[n] the events); once more with that room
+            long long need_ev = 0, need_b = 0;
+            const char* msg = bp_last_error(h);
+            const char* p = msg ? std::strstr(msg, "output buffers too small: ") : nullptr;
+            if (!p || std::sscanf(p, "output buffers too small: %lld events and %lld bends", &need_ev, &need_b) != 2) break;
+            if (need_ev <= cap_ev && need_b <= cap_b) break;
+            cap_ev = std::max<int64_t>(cap_ev, need_ev), cap_b = std::max<int64_t>(cap_b, need_b);
+          }
+          g.ms_device = lap() / (float)n;
+        }
+        release(lane);
+      }
+      // the outputs: nothing of a file is written before its events are final.  A call that failed as a whole and every clip
+      // whose status is not 0 are left to the per-file route, whose outputs and report are today's by construction.
+      for (auto& kv : groups) {
+        Group& g = kv.second;
+        std::vector<size_t> written;
+        for (size_t q = 0; q < g.members.size(); ++q) {
+          const Member& m = part[g.members[q]];
+          if (g.rc != BP_OK || g.status[q] != 0) {
+            later.push_back(m.index);
+            continue;
+          }
+          bp_file_report* rep = &reports[m.index];
+          rep->n_note_events = 0, rep->n_frames = m.rows;
+          rep->ms_read = ms_read, rep->ms_lane_wait = ms_wait, rep->ms_device = g.ms_device, rep->ms_notes = rep->ms_write = 0.0f;
+          const bp_note_event* ev = g.events.data() + g.offsets[q];
+          const int64_t n_ev = g.offsets[q + 1] - g.offsets[q];
+          rep->n_note_events = (int32_t)n_ev;
+          const int32_t* bp = prm.notes.include_pitch_bends ? g.bends.data() : nullptr;
+          const std::string out_base = std::string(out_dir) + "/" + stem_of(paths[m.index]) + "_basic_pitch.";
+          bool ok = true;
+          if (prm.save_midi) {
+            ok = notes_midi(ev, n_ev, bp, prm.multiple_pitch_bends != 0, prm.midi_tempo, midi) &&
+                 write_new_file(out_base + "mid", midi.data(), midi.size());
+          }
+          if (ok && prm.save_notes) {
+            csv.clear();
+            notes_csv(ev, n_ev, bp, csv);
+            ok = write_new_file(out_base + "csv", csv.data(), csv.size());
+          }
+          if (!ok) {
+            set_report(rep, BP_ERR_INVALID_ARG, g_file_error);
+            continue;
+          }
+          set_report(rep, BP_OK, "");
+          written.push_back(q);
+          g_batched.fetch_add(1, std::memory_order_relaxed);
+        }
+        const float ms_write = written.empty() ? 0.0f : lap() / (float)written.size();
+        for (size_t q : written) reports[part[g.members[q]].index].ms_write = ms_write;
+      }
+      part.clear(), part_bytes = 0, part_windows = 0;
+      std::sort(later.begin(), later.end());
+      for (int64_t i : later) one_file(i);
+    };
+    const int64_t step = std::min<int64_t>(prm.clip_batch, kClipBatchMax);
+    for (;;) {
+      const int64_t lo = next.fetch_add(step);
+      if (lo >= n_files) break;
+      const int64_t hi = std::min(n_files, lo + step);
+      for (int64_t i = lo; i < hi; ++i) {
+        if (dup[(size_t)i]) continue;
+        const std::string path = paths[i];
+        const std::string out_base = std::string(out_dir) + "/" + stem_of(path) + "_basic_pitch.";
+        struct stat sb;
+        Member m{i, ClipFile{}, 0, 0, 0, 0};
+        // an output that exists is the per-file route's to report; so is every file the headers do not send to a batch
+        if ((prm.save_midi && stat((out_base + "mid").c_str(), &sb) == 0) || (prm.save_notes && stat((out_base + "csv").c_str(), &sb) == 0) ||
+            host_decodes(prm) || clip_route_of_path(path, handles[0], prm, m.c, &m.size) <= 0) {
+          one_file(i);
+          continue;
+        }
+        if (!part.empty() && (part_bytes + slot_bytes(m.size) > kClipBatchBytes + 2 * kAlign || part_windows + m.c.windows > kClipBatchWindows))
+          flush();
+        part_bytes += slot_bytes(m.size), part_windows += m.c.windows;
+        part.push_back(m);
+      }
+      flush();
     }
   };
   int n_threads = prm.threads > 0 ? prm.threads : default_threads();

@@ -455,7 +455,9 @@ def predict_and_save_sharded(
     `native=True` (round 4; with `native_lanes`, `native_threads`): every worker runs its share through the native
     pipeline (`inference.transcribe_files` -> `bp_transcribe_files`: C++ worker threads from a file's bytes to its
     `.mid` / `.csv`) instead of the Python one: 299 instead of 85 three-minute files per second and GPU with ONE process per
-    GPU; give each worker `native_threads` = usable cores / GPUs.  MIDI and note events only."""
+    GPU; give each worker `native_threads` = usable cores / GPUs.  MIDI and note events only.  The native job's own
+    keywords (`host_decode`, `direct_io`, `host_flac`, `clip_batch`: batches of short files, see `transcribe_files`) pass
+    through to every worker's call."""
     from . import inference
 
     paths = [os.fspath(p) for p in audio_paths]

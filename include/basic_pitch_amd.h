@@ -497,8 +497,19 @@ typedef struct bp_transcribe_params {
   int32_t host_flac;            /* 0 (default): FLAC files are decoded on the device (bp_infer_flac: the file's bytes over PCIe,
                                    no host core-time per sample; streams it leaves to the host fall back by themselves);
                                    1: on the host (bp_flac_decode), the round-4 path */
-  int32_t reserved[1];
+  int32_t clip_batch;           /* 0 (default): a worker owns one file at a time.  N > 0: a worker claims up to N consecutive
+                                   inputs (at most 1024) and takes the SHORT files among them — WAV, or FLAC the device
+                                   decodes, of at most BP_FILES_CLIP_MAX_WINDOWS windows — through one bp_infer_clips_events /
+                                   bp_infer_flac_clips_events call per container and sample rate on one lane acquisition; every
+                                   other file, and every file such a call does not finish (a clip status other than 0, a rate
+                                   whose filter is not tabulated, a failed call), goes the per-file route.  Same output
+                                   bytes and reports.  The files of one lane acquisition hold at most 64 MiB of file bytes
+                                   and 1024 windows; a run that passes either is taken in parts.  Negative: BP_ERR_INVALID_ARG */
 } bp_transcribe_params;
+
+/* the longest file, in windows at the lanes' geometry, that params.clip_batch sends to a batched call: the range the clips
+ * calls name (basic_pitch_amd_clips.h), far inside BP_EVENTS_MAX_ROWS */
+#define BP_FILES_CLIP_MAX_WINDOWS 15
 
 typedef struct bp_file_report {
   int32_t status;               /* BP_OK or the bp_status of the step that failed */
@@ -506,7 +517,9 @@ typedef struct bp_file_report {
   int64_t n_frames;             /* rows of the file's posteriorgrams */
   char message[240];            /* empty on success */
   /* where the worker's wall time for this file went, in milliseconds: reading the file (and FLAC decode), waiting for a
-   * GPU lane, the device call (copy in, resample, CQT + CNN, copy out), note decoding, MIDI / CSV encoding + writes */
+   * GPU lane, the device call (copy in, resample, CQT + CNN, copy out), note decoding, MIDI / CSV encoding + writes.  A file
+   * whose outputs came from a batched call (params.clip_batch) has its equal share of the batch's wall time of every stage —
+   * the sum over the files is the workers' time, as ever; ms_notes is 0, the device call decodes the notes */
   float ms_read, ms_lane_wait, ms_device, ms_notes, ms_write;
 } bp_file_report;
 
@@ -533,6 +546,18 @@ int64_t bp_files_direct_reads(void);
 /* bp_transcribe_files' file reader on its own, into ordinary host memory (test hook, no device): returns the number of bytes
  * read (or a negative bp_status), a 64-bit FNV-1a of them and whether O_DIRECT was really used. */
 int64_t bp_files_read_probe(const char* path, int direct_io, uint64_t* fnv1a, int* used_direct);
+/* files whose outputs came from a batched call (params.clip_batch) since the library was loaded; a file that went back to
+ * the per-file route is not counted */
+int64_t bp_files_batched(void);
+/* The route every file would take in a bp_transcribe_files job with params->clip_batch > 0, read from its headers alone (no
+ * GPU work, no look at the output directory; the workers decide with the same function): route[i] = 0 the per-file route,
+ * 1 a batched PCM call, 2 a batched FLAC call, a negative bp_status for a file that cannot be read or parsed (the job
+ * leaves those to the per-file route, which reports them).  With params->host_decode, or an onset threshold <= 0 (the host
+ * decodes those maps too), nothing is batched and no file is opened: every route is 0.  handles / n_handles: the job's
+ * lanes, whose geometry counts the windows; n_handles = 0 (handles may be NULL) counts with the default mode's geometry and
+ * needs no device.  A negative params->clip_batch is BP_ERR_INVALID_ARG; its value is not looked at otherwise. */
+int bp_files_batch_probe(bp_handle* handles, int n_handles, const char* const* paths, int64_t n_files,
+                         const bp_transcribe_params* params, int32_t* route);
 
 #ifdef __cplusplus
 }
