@@ -50,6 +50,9 @@ SOURCES = [
     "flac_clips.hip",
     "note_decode.cpp",
     "flac_decode.cpp",
+    "wav_file.cpp",
+    "note_writers.cpp",
+    "file_io.cpp",
     "file_pipeline.cpp",
 ]
 # Superseded decompositions of a kernel, kept for comparison runs: compiled only into the A/B library
@@ -62,7 +65,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h", "march_common.h", "cqt_planes.h", "flac_kernels.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER, STREAM_EVENTS_HEADER, FLAC_CLIPS_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h", "march_common.h", "cqt_planes.h", "flac_kernels.h", "file_host.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER, STREAM_EVENTS_HEADER, FLAC_CLIPS_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

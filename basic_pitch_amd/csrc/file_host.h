@@ -1,0 +1,54 @@
+// What the host side of the file job shares across its sources: wav_file.cpp (RIFF/WAVE), note_writers.cpp (.csv and
+// .mid bytes), file_io.cpp (reading and writing files, the thread's error string) and file_pipeline.cpp (the job itself,
+// the only one of the four that calls the device library).  Internal: nothing here is part of the library's interface.
+#pragma once
+#include <cstddef>
+#include <cstdint>
+#include <functional>
+#include <string>
+#include <vector>
+
+#include "../../include/basic_pitch_amd.h"
+
+namespace bp_file __attribute__((visibility("hidden"))) {
+
+// what bp_files_last_error returns: the last failure of this thread in any of the four sources
+extern thread_local std::string g_file_error;
+
+// ---- wav_file.cpp
+struct WavInfo {
+  int tag = 0, channels = 0, sample_rate = 0, bits = 0;
+  const uint8_t* pcm = nullptr;
+  size_t pcm_bytes = 0;
+  int64_t n_frames = 0;
+};
+
+// The bytes of a file by position: the whole file in memory, or an open file of which only the bytes asked for are read
+// (bp_files_batch_probe and the batching workers decide a file's route from its headers alone).
+struct ByteSource {
+  const uint8_t* mem = nullptr;
+  int fd = -1;
+  size_t size = 0;
+  bool at(size_t pos, size_t len, uint8_t* out) const;  // [pos, pos + len) lies inside the file
+};
+
+bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos);
+bool wav_parse(const uint8_t* d, size_t n, WavInfo& w);
+int wav_pcm_format(const WavInfo& w);  // the BP_PCM_* of the samples as the file stores them
+void wav_to_float(const WavInfo& w, float* out);
+
+// ---- note_writers.cpp
+void notes_csv(const bp_note_event* ev, int64_t n, const int32_t* bends, std::string& out);
+bool notes_midi(const bp_note_event* ev, int64_t n, const int32_t* bends, bool multiple_pitch_bends, double tempo,
+                std::vector<uint8_t>& out);
+
+// ---- file_io.cpp
+// ensure(bytes) -> page-aligned buffer of at least that many bytes, or null (g_file_error set)
+bool read_file_into(const std::string& path, const std::function<void*(size_t)>& ensure, size_t& n, bool direct,
+                    bool* was_direct = nullptr);
+bool write_new_file(const std::string& path, const void* data, size_t n);
+std::string stem_of(const std::string& path);
+std::string two_path_message(const std::string& t0, const std::string& p0, const std::string& t1, const std::string& p1,
+                             const std::string& t2);
+
+}  // namespace bp_file

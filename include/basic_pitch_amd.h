@@ -526,7 +526,8 @@ typedef struct bp_file_report {
 void bp_transcribe_params_default(bp_transcribe_params* p);
 int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* paths, int64_t n_files, const char* out_dir,
                         const bp_transcribe_params* params, bp_file_report* reports);
-/* The pieces on their own (host only; the CPU tests pin them to the Python writers and readers).
+/* The pieces on their own (host only: csrc/note_writers.cpp, csrc/wav_file.cpp and csrc/file_io.cpp call nothing of the
+ * device library; the CPU tests pin them to the Python writers and readers).
  * bp_notes_to_midi / bp_notes_to_csv return the number of bytes of the file (written to `out` if it fits `capacity`; call
  * with out = NULL to size the buffer), or a negative bp_status.  `bends` may be NULL (no pitch bends).
  * bp_wav_info / bp_wav_decode: RIFF/WAVE PCM 8 / 16 / 24 / 32 and IEEE float 32 / 64 -> float32 [n_frames, channels] in

@@ -1,4 +1,5 @@
-"""The native file pipeline's host pieces (csrc/file_pipeline.cpp) against the Python code they replace — no GPU:
+"""The native file pipeline's host pieces (csrc/note_writers.cpp, csrc/wav_file.cpp) against the Python code they
+replace — no GPU:
 
 * bp_notes_to_midi == `note_events_to_midi(...).write()` (basic_pitch_amd/midi.py, itself pinned byte for byte to
   pretty_midi + mido's layout by tests/golden/midi) on the 16 reference-generated note cases, and therefore == the
@@ -225,6 +226,68 @@ def test_transcribe_files_reports_keep_their_reason_with_long_paths(tmp_path):
     assert again[0]["status"] != 0 and len(m) <= 239 and m.startswith("..."), again
     assert ("o" * 40 + "/a_basic_pitch.* already exists and would be overwritten. Skipping output files for ...") in m, m
     assert m.endswith("e" * 40 + "/a.wav."), m
+    model.close()
+
+
+@pytest.mark.gpu
+def test_transcribe_files_failure_messages(tmp_path, request):
+    """What the job says of a file it cannot take, word for word, on the per-file route (clip_batch=0) and in a job that
+    batches (clip_batch=4: the route function refuses the file from its headers and the per-file route reports it): a
+    missing file, a RIFF/WAVE head without chunks, a text file, WAV files of a bit depth, a format tag and a channel count
+    nobody reads, and a FLAC head without a stream — the FLAC decoder words that one; it is held equal between the two jobs.
+    A message is a field of 239 characters and a longer text would be cut there, so the inputs lie in a short directory
+    (under a long temporary directory: one made in /tmp) and every expected text is checked to fit."""
+    import shutil
+    import tempfile
+    from pathlib import Path
+
+    from basic_pitch_amd import Model, transcribe_files
+
+    d = tmp_path / "i"
+    d.mkdir()
+    if len(str(d)) > 120:
+        d = Path(tempfile.mkdtemp(prefix="bp_msg_", dir="/tmp"))
+        request.addfinalizer(lambda: shutil.rmtree(d, ignore_errors=True))
+    t = np.arange(11025) / 22050.0
+    good = [d / "good0.wav", d / "good1.wav"]
+    for k, p in enumerate(good):
+        with wave.open(str(p), "wb") as w:
+            w.setnchannels(1), w.setsampwidth(2), w.setframerate(22050)
+            w.writeframes((0.3 * np.sin(2 * np.pi * (330.0 + 110.0 * k) * t) * 32767).astype("<i2").tobytes())
+    bad = [
+        ("missing.wav", None, "{p} is not a file path."),
+        ("broken.wav", b"RIFF\x00\x00\x00\x00WAVEjunk", "{p}: missing fmt or data chunk"),
+        ("text.wav", b"sixteen bytes .\n", "{p}: not a WAV or FLAC file (the native pipeline reads RIFF/WAVE and FLAC)"),
+        ("bits12.wav", _wav_bytes(1, 12, 1, 8000, b"\x00" * 64), "{p}: unsupported PCM bit depth 12"),
+        ("tag2.wav", _wav_bytes(2, 4, 1, 8000, b"\x00" * 64), "{p}: unsupported WAV format tag 2"),
+        ("nochannels.wav", _wav_bytes(1, 16, 0, 8000, b"\x00" * 64), "{p}: zero channels"),
+        ("empty.flac", b"fLaC" + b"\x00" * 60, None),
+    ]
+    assert len(bad[2][1]) == 16
+    for name, data, _ in bad:
+        if data is not None:
+            (d / name).write_bytes(data)
+    paths = [d / bad[0][0]] + good + [d / name for name, _, _ in bad[1:]]
+    is_good = [p in good for p in paths]
+    want = {str(d / name): text.format(p=d / name) for name, _, text in bad if text is not None}
+    assert all(len(text) <= 239 for text in want.values()), "an expected message does not fit the report's field"
+
+    model = Model(max_windows=16)
+    lib = model._lib
+    reports = []
+    for clip_batch, batched in ((0, 0), (4, 2)):
+        out = tmp_path / ("o%d" % clip_batch)
+        out.mkdir()
+        before = lib.bp_files_batched()
+        rep = transcribe_files(paths, out, models=[model], threads=2, clip_batch=clip_batch)
+        assert lib.bp_files_batched() - before == batched
+        assert [r["status"] == 0 for r in rep] == is_good, rep
+        for p, r in zip(paths, rep):
+            if str(p) in want:
+                assert r["message"] == want[str(p)], (clip_batch, r)
+        assert sorted(os.listdir(out)) == sorted(f"{p.stem}_basic_pitch.{e}" for p in good for e in ("mid", "csv"))
+        reports.append(rep)
+    assert reports[0][-1]["message"].startswith(str(d / "empty.flac") + ": ") and reports[0][-1]["message"] == reports[1][-1]["message"], reports
     model.close()
 
 

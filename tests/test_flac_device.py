@@ -382,7 +382,7 @@ def test_frame_headers_inside_the_payload(model, tmp_path):
     size; the others (a false header that carries its predecessor's number + 1, a pair that continue each other, more
     candidates than a chunk's list holds, a stray one in front of the last frame) may be refused, never decoded to other
     samples.  Whatever the device decoder does, `predict()` on the file returns what the host-decoded samples give, and the
-    native file job falls back to the host decoder (file_pipeline.cpp, "the device decoder could not follow the stream")
+    native file job falls back to the host decoder (file_pipeline.cpp Worker::infer, "a FLAC stream the device decoder could not follow")
     and writes the bytes it writes with host_flac=True.
 
     What happens to each file is recorded in OUTCOMES above (the stray header in the next-to-last frame: refused) and asserted,

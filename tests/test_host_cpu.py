@@ -320,7 +320,7 @@ def test_only_the_owner_types_allocate_and_free_device_and_page_locked_memory():
 
 
 def test_native_file_reader_direct_io_reads_the_same_bytes(tmp_path):
-    """bp_transcribe_files' reader (csrc/file_pipeline.cpp read_file_into) with and without O_DIRECT: the same bytes as
+    """bp_transcribe_files' reader (csrc/file_io.cpp read_file_into) with and without O_DIRECT: the same bytes as
     Python's read for lengths around the 4 KiB block size (an O_DIRECT read is issued in whole blocks and stops at the end of
     the file), an empty file included; a file system that refuses O_DIRECT is read through the page cache and says so; a missing file is an error, not a crash."""
     import ctypes as C

@@ -5,32 +5,23 @@
 #include <vector>
 #include <cstdint>
 #include "../../include/basic_pitch_amd.h"
-// stubs for the device entry points file_pipeline.cpp links against
-extern "C" {
-void* bp_host_alloc(size_t n) { return malloc(n); }
-void bp_host_free(void* p) { free(p); }
-int bp_infer_pcm_raw(bp_handle, const void*, int, int64_t, int, int, float*, float*, float*, int) { return -1; }
-const char* bp_last_error(bp_handle) { return ""; }
-int64_t bp_handle_track_n_frames(bp_handle, int64_t) { return 0; }
-int64_t bp_handle_resampled_length(bp_handle, int64_t, int) { return 0; }
-int bp_handle_sample_rate(bp_handle) { return 22050; }
-int bp_infer_pcm_raw_candidates(bp_handle, const void*, int, int64_t, int, int, const bp_note_params*, float*, uint8_t*, int8_t*,
-                                int*) { return -1; }
-int bp_infer_flac(bp_handle, const void*, size_t, float*, float*, float*, int) { return -1; }
-int bp_infer_flac_candidates(bp_handle, const void*, size_t, const bp_note_params*, float*, uint8_t*, int8_t*, int*) { return -1; }
-int bp_track_maps(bp_handle, int64_t, float*, float*, float*, int) { return -1; }
-}
+// Links against the device-free sources alone (wav_file.cpp, note_writers.cpp, file_io.cpp, note_decode.cpp, flac_decode.cpp):
+// no stub for any library function.  usage: fuzz_host FILE.wav [SCALE]; SCALE (default 1.0) scales the iteration counts.
 static uint64_t s = 88172645463325252ull;
 static uint32_t rnd() { s ^= s << 13; s ^= s >> 7; s ^= s << 17; return (uint32_t)(s >> 11); }
 static float frnd() { return (float)(rnd() & 0xffffff) / 16777216.0f; }
 int main(int argc, char** argv) {
+  if (argc < 2) { fprintf(stderr, "usage: %s FILE.wav [SCALE]\n", argv[0]); return 2; }
+  const double scale = argc > 2 ? atof(argv[2]) : 1.0;
+  const int n_wav = (int)(6000 * scale), n_maps = (int)(300 * scale);
   // ---- WAV parser
   FILE* f = fopen(argv[1], "rb");
+  if (!f) { fprintf(stderr, "cannot open %s\n", argv[1]); return 2; }
   std::vector<uint8_t> base(30000);
   base.resize(fread(base.data(), 1, base.size(), f));
   fclose(f);
   long ok = 0, bad = 0;
-  for (int it = 0; it < 6000; ++it) {
+  for (int it = 0; it < n_wav; ++it) {
     std::vector<uint8_t> d = base;
     int mode = it % 4;
     if (mode == 0) { for (int k = 0; k < 1 + (int)(rnd() % 5); ++k) d[rnd() % 64] = (uint8_t)rnd(); }
@@ -52,7 +43,7 @@ int main(int argc, char** argv) {
   printf("wav ok %ld bad %ld\n", ok, bad); fflush(stdout);
   // ---- note decoder + writers on random maps
   long ev_total = 0, cand_total = 0;
-  for (int it = 0; it < 300; ++it) {
+  for (int it = 0; it < n_maps; ++it) {
     const int64_t T = 1 + rnd() % 300;
     std::vector<float> note((size_t)T * 88), onset((size_t)T * 88), contour((size_t)T * 264);
     for (auto& v : note) v = powf(frnd(), 3.f);
