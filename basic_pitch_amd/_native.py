@@ -27,9 +27,15 @@ BP_FLAG_F16_CORRECTIONS = 32
 BP_FLAG_FP8_CORRECTIONS = 64
 BP_FLAG_BLOCKING_WAIT = 128
 BP_PCM_F32, BP_PCM_S16, BP_PCM_S24, BP_PCM_S32, BP_PCM_U8, BP_PCM_F64 = range(6)
+# what AIFF, CAF and AU files hold (include/basic_pitch_amd_containers.h): big-endian words, signed bytes, G.711
+BP_PCM_S16_BE, BP_PCM_S24_BE, BP_PCM_S32_BE, BP_PCM_F32_BE, BP_PCM_F64_BE, BP_PCM_S8, BP_PCM_ULAW, BP_PCM_ALAW = range(6, 14)
 # the WAV (format tag, bits per sample) each code stands for; a sample is bits // 8 bytes wide
 BP_PCM_WAV = {BP_PCM_U8: (1, 8), BP_PCM_S16: (1, 16), BP_PCM_S24: (1, 24), BP_PCM_S32: (1, 32), BP_PCM_F32: (3, 32),
               BP_PCM_F64: (3, 64)}
+# bytes per sample of every code
+BP_PCM_WIDTH = {BP_PCM_F32: 4, BP_PCM_S16: 2, BP_PCM_S24: 3, BP_PCM_S32: 4, BP_PCM_U8: 1, BP_PCM_F64: 8, BP_PCM_S16_BE: 2,
+                BP_PCM_S24_BE: 3, BP_PCM_S32_BE: 4, BP_PCM_F32_BE: 4, BP_PCM_F64_BE: 8, BP_PCM_S8: 1, BP_PCM_ULAW: 1, BP_PCM_ALAW: 1}
+BP_CONTAINER_WAV, BP_CONTAINER_AIFF, BP_CONTAINER_CAF, BP_CONTAINER_AU = 1, 2, 3, 4
 BP_N_STAGES = 15
 BP_FILES_CLIP_MAX_WINDOWS = 15  # the longest file, in windows, that bp_transcribe_params.clip_batch sends to a batched call
 BP_Z_ROW = 448
@@ -107,6 +113,19 @@ class bp_flac_stream_layout(C.Structure):
         ("max_block", C.c_int32),
         ("n_frames", C.c_int64),
         ("audio_start", C.c_int64),
+    ]
+
+
+class bp_pcm_file_layout(C.Structure):
+    _fields_ = [
+        ("container", C.c_int32),
+        ("format", C.c_int32),
+        ("channels", C.c_int32),
+        ("sample_rate", C.c_int32),
+        ("bits_per_sample", C.c_int32),
+        ("reserved", C.c_int32),
+        ("n_frames", C.c_int64),
+        ("data_start", C.c_int64),
     ]
 
 
@@ -287,6 +306,11 @@ FLAC_CLIPS_SYMBOLS = [
     "bp_infer_flac_clips_candidates",
     "bp_infer_flac_clips_events",
 ]
+# every symbol include/basic_pitch_amd_containers.h declares (bound below; basic_pitch_amd/audio.py pcm_raw is their numpy twin)
+CONTAINERS_SYMBOLS = [
+    "bp_pcm_file_layout_of",
+    "bp_pcm_file_decode",
+]
 # status values of a clip in those calls, beside 0, 1 and 2 of the PCM clips calls
 BP_CLIP_FLAC_HOST = 3    # left to the host decoder, known before anything is queued: no rows
 BP_CLIP_FLAC_FAILED = 4  # the device decoder could not follow the stream
@@ -437,6 +461,10 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bp_wav_info.restype = C.c_int
     lib.bp_wav_decode.argtypes = [C.c_char_p, C.c_size_t, fp, i64, C.POINTER(i64)]
     lib.bp_wav_decode.restype = C.c_int
+    lib.bp_pcm_file_layout_of.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(bp_pcm_file_layout)]
+    lib.bp_pcm_file_layout_of.restype = C.c_int
+    lib.bp_pcm_file_decode.argtypes = [C.c_char_p, C.c_size_t, fp, i64, C.POINTER(i64)]
+    lib.bp_pcm_file_decode.restype = C.c_int
     lib.bp_files_last_error.argtypes = []
     lib.bp_files_last_error.restype = C.c_char_p
     if path is None:

@@ -11,6 +11,7 @@ path and checks the device one.
 """
 from __future__ import annotations
 
+import math
 import pathlib
 import struct
 from fractions import Fraction
@@ -18,23 +19,32 @@ from typing import Tuple, Union
 
 import numpy as np
 
+from . import _native as _n
+
 AUDIO_SAMPLE_RATE = 22050
 
 
 def wav_raw(path: Union[str, pathlib.Path]):
     """The samples of a RIFF/WAVE file as the file stores them: (uint8 view of the data chunk, format tag, bits, channels,
-    sample_rate).  Tag 1 = integer PCM (8 / 16 / 24 / 32 bits), 3 = IEEE float (32 / 64)."""
+    sample_rate).  Tag 1 = integer PCM (8 / 16 / 24 / 32 bits), 3 = IEEE float (32 / 64).  RF64 / BW64 files, whose data
+    size lies in the ds64 chunk, are WAV files here."""
     with open(path, "rb") as f:
         data = memoryview(f.read())  # chunks below are views, not copies (a 3-minute stereo file is 31 MB)
-    if len(data) < 12 or data[:4] != b"RIFF" or data[8:12] != b"WAVE":
+    rf64 = len(data) >= 4 and bytes(data[:4]) in (b"RF64", b"BW64")
+    if len(data) < 12 or not (rf64 or data[:4] == b"RIFF") or data[8:12] != b"WAVE":
         raise ValueError(f"{path}: not a RIFF/WAVE file")
     pos = 12
     fmt = None
     pcm = None
+    ds64_data = None
     while pos + 8 <= len(data):
         cid = bytes(data[pos : pos + 4])
         size = struct.unpack_from("<I", data, pos + 4)[0]
+        if rf64 and cid == b"data" and size == 0xFFFFFFFF and ds64_data is not None:
+            size = ds64_data
         body = data[pos + 8 : pos + 8 + size]
+        if rf64 and cid == b"ds64" and len(body) >= 24:
+            ds64_data = struct.unpack_from("<Q", body, 8)[0]
         if cid == b"fmt ":
             tag, ch, sr, _br, _ba, bits = struct.unpack_from("<HHIIHH", body, 0)
             if tag == 0xFFFE and len(body) >= 26:  # WAVE_FORMAT_EXTENSIBLE: real tag in the GUID
@@ -80,6 +90,233 @@ def read_wav(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
         raise ValueError(f"{path}: unsupported WAV format tag {tag}")
     n = len(x) // ch
     return x[: n * ch].reshape(n, ch), sr
+
+
+_WAV_CODES = {wav: code for code, wav in _n.BP_PCM_WAV.items()}  # WAV (format tag, bits) -> BP_PCM_*
+
+
+def _ext80(b: bytes) -> float:
+    """An 80-bit extended float (AIFF's sample rate): sign and 15-bit exponent, 64-bit mantissa with its integer bit."""
+    se, mant = struct.unpack(">HQ", b)
+    v = math.ldexp(float(mant), (se & 0x7FFF) - 16383 - 63)
+    return -v if se & 0x8000 else v
+
+
+def _rate(path, v: float) -> int:
+    if not (0.5 <= v < 2147483647.0):
+        raise ValueError(f"{path}: bad sample rate in the header")
+    return int(math.floor(v + 0.5))
+
+
+def _int_code(nbytes: int, little: bool) -> int:
+    return {1: _n.BP_PCM_S8, 2: _n.BP_PCM_S16 if little else _n.BP_PCM_S16_BE, 3: _n.BP_PCM_S24 if little else _n.BP_PCM_S24_BE,
+            4: _n.BP_PCM_S32 if little else _n.BP_PCM_S32_BE}[nbytes]
+
+
+def _aiff_raw(path, data: memoryview):
+    """AIFF / AIFF-C (Apple's AIFF 1.3 and AIFF-C drafts): chunks in any order, padded to even size; COMM says what the
+    samples are, SSND holds them behind an offset."""
+    aifc = bytes(data[8:12]) == b"AIFC"
+    comm = ssnd = None
+    pos = 12
+    while pos + 8 <= len(data):
+        cid = bytes(data[pos : pos + 4])
+        size = struct.unpack_from(">I", data, pos + 4)[0]
+        body = data[pos + 8 : pos + 8 + size]
+        if cid == b"COMM":
+            need = 22 if aifc else 18
+            if len(body) < need:
+                raise ValueError(f"{path}: truncated COMM chunk: {len(body)} of {need} bytes")
+            ch, frames, bits = struct.unpack_from(">HIH", body, 0)
+            comm = (ch, frames, bits, _ext80(bytes(body[8:18])), bytes(body[18:22]) if aifc else b"NONE")
+        elif cid == b"SSND":
+            if len(body) < 8:
+                raise ValueError(f"{path}: truncated SSND chunk")
+            ssnd = body[8 + min(struct.unpack_from(">I", body, 0)[0], len(body) - 8) :]
+        pos += 8 + size + (size & 1)
+    if comm is None:
+        raise ValueError(f"{path}: missing COMM chunk")
+    ch, frames, bits, rate, ctype = comm
+    if ssnd is None:
+        if frames:
+            raise ValueError(f"{path}: missing SSND chunk")
+        ssnd = data[:0]
+    if ch < 1:
+        raise ValueError(f"{path}: zero channels")
+    if ctype in (b"NONE", b"twos", b"in24", b"in32", b"sowt"):
+        if not 1 <= bits <= 32:
+            raise ValueError(f"{path}: unsupported AIFF sample size {bits}")
+        code = _int_code((bits + 7) // 8, ctype == b"sowt")
+    elif ctype in (b"fl32", b"FL32") and bits == 32:
+        code = _n.BP_PCM_F32_BE
+    elif ctype in (b"fl64", b"FL64") and bits == 64:
+        code = _n.BP_PCM_F64_BE
+    elif ctype in (b"ulaw", b"ULAW"):
+        code = _n.BP_PCM_ULAW
+    elif ctype in (b"alaw", b"ALAW"):
+        code = _n.BP_PCM_ALAW
+    elif ctype == b"raw " and 1 <= bits <= 8:
+        code = _n.BP_PCM_U8
+    elif ctype in (b"fl32", b"FL32", b"fl64", b"FL64", b"raw "):
+        raise ValueError(f"{path}: unsupported sample size {bits} for AIFF-C compression type {ctype.decode('latin-1')!r}")
+    else:
+        raise ValueError(f"{path}: unsupported AIFF-C compression type {ctype.decode('latin-1')!r}")
+    return ssnd, code, ch, _rate(path, rate), frames
+
+
+def _caf_raw(path, data: memoryview):
+    """CAF (Apple Core Audio Format 1.0): `desc` says what the samples are, `data` holds them behind a 4-byte edit count."""
+    if len(data) < 8 or struct.unpack_from(">H", data, 4)[0] != 1:
+        raise ValueError(f"{path}: unsupported CAF version")
+    desc = pcm = None
+    pos = 8
+    while pos + 12 <= len(data):
+        cid = bytes(data[pos : pos + 4])
+        size = struct.unpack_from(">q", data, pos + 4)[0]
+        rest = len(data) - (pos + 12)
+        if size < 0 and cid != b"data":
+            raise ValueError(f"{path}: negative size of CAF chunk {cid.decode('latin-1')!r}")
+        body = data[pos + 12 : pos + 12 + (rest if size < 0 else min(size, rest))]
+        if cid == b"desc":
+            if len(body) < 32:
+                raise ValueError(f"{path}: truncated desc chunk")
+            desc = struct.unpack_from(">d4sIIIII", body, 0)
+        elif cid == b"data":
+            pcm = body[4:]
+        if size < 0:
+            break
+        pos += 12 + size
+    if desc is None or pcm is None:
+        raise ValueError(f"{path}: missing desc or data chunk")
+    rate, fid, flags, packet_bytes, packet_frames, ch, bits = desc
+    if ch < 1:
+        raise ValueError(f"{path}: zero channels")
+    is_float, little = bool(flags & 1), bool(flags & 2)
+    if fid == b"lpcm" and is_float and bits in (32, 64):
+        code = {(32, True): _n.BP_PCM_F32, (32, False): _n.BP_PCM_F32_BE, (64, True): _n.BP_PCM_F64, (64, False): _n.BP_PCM_F64_BE}[(bits, little)]
+    elif fid == b"lpcm" and not is_float and bits in (8, 16, 24, 32):
+        code = _int_code(bits // 8, little)
+    elif fid == b"lpcm":
+        raise ValueError(f"{path}: unsupported CAF lpcm of {bits}-bit {'floats' if is_float else 'integers'}")
+    elif fid in (b"ulaw", b"alaw"):
+        code = _n.BP_PCM_ULAW if fid == b"ulaw" else _n.BP_PCM_ALAW
+    else:
+        raise ValueError(f"{path}: unsupported CAF format {fid.decode('latin-1')!r}")
+    if packet_frames != 1 or packet_bytes != ch * _n.BP_PCM_WIDTH[code]:
+        raise ValueError(f"{path}: unsupported CAF packet layout: {packet_frames} frames in {packet_bytes} bytes a packet")
+    return pcm, code, ch, _rate(path, rate), None
+
+
+_AU_CODES = {1: _n.BP_PCM_ULAW, 2: _n.BP_PCM_S8, 3: _n.BP_PCM_S16_BE, 4: _n.BP_PCM_S24_BE, 5: _n.BP_PCM_S32_BE,
+             6: _n.BP_PCM_F32_BE, 7: _n.BP_PCM_F64_BE, 27: _n.BP_PCM_ALAW}
+
+
+def _au_raw(path, data: memoryview):
+    """AU (.snd, the Sun / NeXT header): six big-endian words, an annotation, the samples."""
+    if len(data) < 24:
+        raise ValueError(f"{path}: truncated AU header")
+    header_bytes, data_size, encoding, rate, ch = struct.unpack_from(">IIIII", data, 4)
+    if header_bytes < 24:
+        raise ValueError(f"{path}: bad AU header size {header_bytes}")
+    if encoding not in _AU_CODES:
+        raise ValueError(f"{path}: unsupported AU encoding {encoding}")
+    if ch < 1:
+        raise ValueError(f"{path}: zero channels")
+    pcm = data[header_bytes:]
+    if data_size != 0xFFFFFFFF:
+        pcm = pcm[:data_size]
+    return pcm, _AU_CODES[encoding], ch, _rate(path, float(rate)), None
+
+
+def pcm_raw(path: Union[str, pathlib.Path]):
+    """The samples of a WAV (RF64 / BW64 too), AIFF / AIFF-C, CAF or AU file as the file stores them: (uint8 view of the
+    samples, BP_PCM_* code, channels, sample_rate, n_frames) — what `Model.predict_pcm_raw` takes.  `wav_raw` for every
+    container the device converts itself; independent of the C++ parsers (csrc/pcm_file.cpp), which the tests hold to it.
+    Not read: the little-endian AU variant, Sony Wave64, ADPCM and the other compressed AIFF-C types."""
+    with open(path, "rb") as f:
+        head = f.read(12)
+    if head[:4] in (b"RIFF", b"RF64", b"BW64") and head[8:12] == b"WAVE":
+        pcm, tag, bits, ch, sr = wav_raw(path)
+        code, frames = _WAV_CODES[(tag, bits)], None
+    else:
+        with open(path, "rb") as f:
+            data = memoryview(f.read())
+        if head[:4] == b"FORM" and head[8:12] in (b"AIFF", b"AIFC"):
+            pcm, code, ch, sr, frames = _aiff_raw(path, data)
+        elif head[:4] == b"caff":
+            pcm, code, ch, sr, frames = _caf_raw(path, data)
+        elif head[:4] == b".snd":
+            pcm, code, ch, sr, frames = _au_raw(path, data)
+        else:
+            raise ValueError(f"{path}: not a WAV, AIFF, CAF or AU file")
+    held = len(pcm) // (_n.BP_PCM_WIDTH[code] * ch)
+    n = held if frames is None else min(frames, held)  # a file that ends early: what is there
+    return np.frombuffer(pcm, dtype=np.uint8)[: n * ch * _n.BP_PCM_WIDTH[code]], code, ch, sr, n
+
+
+def g711_expand(b: np.ndarray, law: str) -> np.ndarray:
+    """ITU-T G.711 bytes -> int32 values left-justified in 16 bits, in arithmetic (law: "ulaw" | "alaw")."""
+    b = b.astype(np.int32)
+    if law == "ulaw":
+        u = ~b & 0xFF
+        t = (((u & 15) << 3) + 0x84) << ((u >> 4) & 7)
+        return np.where(u & 0x80, 0x84 - t, t - 0x84)
+    a = b ^ 0x55
+    t, s = (a & 15) << 4, (a >> 4) & 7
+    t = np.where(s == 0, t + 8, np.where(s == 1, t + 0x108, (t + 0x108) << np.maximum(s - 1, 0)))
+    return np.where(a & 0x80, t, -t)
+
+
+def pcm_to_float(raw: np.ndarray, code: int, channels: int) -> np.ndarray:
+    """The uint8 samples `pcm_raw` returns -> float32 [n, channels], the scaling of libsndfile's float read: integers /
+    2^(bits-1), unsigned bytes (v - 128) / 128, G.711 expanded / 32768, float64 rounded (powers of two: exact)."""
+    raw = np.ascontiguousarray(raw)
+    if code in (_n.BP_PCM_S16, _n.BP_PCM_S16_BE):
+        x = raw.view("<i2" if code == _n.BP_PCM_S16 else ">i2").astype(np.float32) * np.float32(1.0 / 32768.0)
+    elif code in (_n.BP_PCM_S24, _n.BP_PCM_S24_BE):
+        b = raw.reshape(-1, 3).astype(np.int32)
+        lo, hi = (0, 2) if code == _n.BP_PCM_S24 else (2, 0)
+        v = b[:, lo] | (b[:, 1] << 8) | (b[:, hi] << 16)
+        x = np.where(v >= 1 << 23, v - (1 << 24), v).astype(np.float32) / np.float32(1 << 23)
+    elif code in (_n.BP_PCM_S32, _n.BP_PCM_S32_BE):
+        x = (raw.view("<i4" if code == _n.BP_PCM_S32 else ">i4").astype(np.float64) / float(1 << 31)).astype(np.float32)
+    elif code == _n.BP_PCM_U8:
+        x = (raw.astype(np.float32) - np.float32(128.0)) * np.float32(1.0 / 128.0)
+    elif code == _n.BP_PCM_S8:
+        x = raw.view(np.int8).astype(np.float32) * np.float32(1.0 / 128.0)
+    elif code in (_n.BP_PCM_ULAW, _n.BP_PCM_ALAW):
+        x = g711_expand(raw, "ulaw" if code == _n.BP_PCM_ULAW else "alaw").astype(np.float32) * np.float32(1.0 / 32768.0)
+    elif code in (_n.BP_PCM_F32, _n.BP_PCM_F32_BE):
+        x = raw.view("<f4" if code == _n.BP_PCM_F32 else ">f4").astype(np.float32)
+    elif code in (_n.BP_PCM_F64, _n.BP_PCM_F64_BE):
+        x = raw.view("<f8" if code == _n.BP_PCM_F64 else ">f8").astype(np.float32)
+    else:
+        raise ValueError(f"unknown BP_PCM_* code {code}")
+    return x.reshape(-1, channels)
+
+
+def _read_container(path, magics) -> Tuple[np.ndarray, int]:
+    with open(path, "rb") as f:
+        head = f.read(12)
+    if head[:4] not in magics:
+        raise ValueError(f"{path}: not such a file")
+    raw, code, ch, sr, _n_frames = pcm_raw(path)
+    return pcm_to_float(raw, code, ch), sr
+
+
+def read_aiff(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
+    """AIFF / AIFF-C -> (float32 samples [n, channels], sample_rate); in numpy, the checker of the native parser."""
+    return _read_container(path, (b"FORM",))
+
+
+def read_caf(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
+    """CAF (lpcm, ulaw, alaw) -> (float32 samples [n, channels], sample_rate)."""
+    return _read_container(path, (b"caff",))
+
+
+def read_au(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
+    """AU (.snd) -> (float32 samples [n, channels], sample_rate)."""
+    return _read_container(path, (b".snd",))
 
 
 def to_mono(x: np.ndarray) -> np.ndarray:
@@ -218,11 +455,15 @@ def _read_with_optional_backend(path: str) -> Tuple[np.ndarray, int]:
 
 def read_audio(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
     """Decode any supported file to (float32 [n, channels], sample_rate): the decode half of librosa.load
-    (inference.py:239).  Dispatch is by content, not extension: RIFF/WAVE and FLAC are read natively."""
+    (inference.py:239).  Dispatch is by content, not extension: RIFF/WAVE (RF64 / BW64 too), AIFF / AIFF-C, CAF, AU and
+    FLAC are read natively."""
     with open(path, "rb") as f:
         head = f.read(12)
-    if head[:4] == b"RIFF" and head[8:12] == b"WAVE":
+    if head[:4] in (b"RIFF", b"RF64", b"BW64") and head[8:12] == b"WAVE":
         return read_wav(path)
+    if (head[:4] == b"FORM" and head[8:12] in (b"AIFF", b"AIFC")) or head[:4] in (b"caff", b".snd"):
+        raw, code, ch, sr, _n_frames = pcm_raw(path)
+        return pcm_to_float(raw, code, ch), sr
     if head[:4] == b"fLaC" or (head[:3] == b"ID3" and str(path).lower().endswith(".flac")):
         return read_flac(path)
     return _read_with_optional_backend(str(path))

@@ -31,10 +31,15 @@ PROTOTYPES = {
     "bp_infer_clips_candidates": (_int, [_vp, _i64, _vp, _int, _int, _vp, _vp, _vp, _vp, _vp]),
 }
 
-# the BP_PCM_* code of each numpy sample type a clip may have (24-bit PCM has no numpy type: widen it to int32)
-FORMATS = {np.dtype(np.float32): _native.BP_PCM_F32, np.dtype(np.int16): _native.BP_PCM_S16,
-           np.dtype(np.int32): _native.BP_PCM_S32, np.dtype(np.uint8): _native.BP_PCM_U8,
-           np.dtype(np.float64): _native.BP_PCM_F64}
+# the BP_PCM_* code of each numpy sample type a clip may have: the little-endian types and their big-endian forms (what an
+# AIFF, CAF or AU file holds).  Packed 24-bit PCM and G.711 have no numpy type, and int8 stays refused here as it always
+# was (tests/test_clips_cpu.py): they go through predict_pcm_raw / open_stream(fmt=...) with BP_PCM_S24[_BE], BP_PCM_ULAW /
+# BP_PCM_ALAW and BP_PCM_S8.
+FORMATS = {np.dtype("<f4"): _native.BP_PCM_F32, np.dtype("<i2"): _native.BP_PCM_S16,
+           np.dtype("<i4"): _native.BP_PCM_S32, np.dtype(np.uint8): _native.BP_PCM_U8,
+           np.dtype("<f8"): _native.BP_PCM_F64, np.dtype(">i2"): _native.BP_PCM_S16_BE,
+           np.dtype(">i4"): _native.BP_PCM_S32_BE, np.dtype(">f4"): _native.BP_PCM_F32_BE,
+           np.dtype(">f8"): _native.BP_PCM_F64_BE}
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
@@ -46,7 +51,7 @@ def as_clip(clip: Any, index: int) -> np.ndarray:
     """Clip `index` as the C-contiguous [n_frames, channels] array the library reads; ValueError names the clip."""
     a = np.asarray(clip)
     if a.dtype not in FORMATS:
-        raise ValueError(f"clip {index}: samples must be float32, int16, int32, uint8 or float64, got {a.dtype}")
+        raise ValueError(f"clip {index}: samples must be float32, int16, int32, uint8 or float64 (either byte order), got {a.dtype}")
     if a.ndim == 1:
         a = a[:, None]
     if a.ndim != 2 or not 1 <= a.shape[1] <= 64:

@@ -109,22 +109,50 @@ ResamplePlan make_resample_plan(int source_rate, int target_rate, std::vector<do
   return pl;
 }
 
+// G.711 expansion in arithmetic (ITU-T G.711; no table in memory): the 14-bit (mu-law, +-32,124) and 13-bit (A-law, +-32,256)
+// values left-justified in 16 bits.  All 256 codes of both laws are pinned by tests/test_containers_cpu.py.
+__device__ __forceinline__ int ulaw_expand(uint32_t b) {
+  const uint32_t u = ~b & 0xffu;
+  const int t = (int)((((u & 15u) << 3) + 0x84u) << ((u >> 4) & 7u));
+  return (u & 0x80u) ? 0x84 - t : t - 0x84;
+}
+__device__ __forceinline__ int alaw_expand(uint32_t b) {
+  const uint32_t a = (b ^ 0x55u) & 0xffu, s = (a >> 4) & 7u;
+  int t = (int)((a & 15u) << 4);
+  t = s == 0 ? t + 8 : s == 1 ? t + 0x108 : (t + 0x108) << (s - 1);
+  return (a & 0x80u) ? t : -t;
+}
+
 // The downmix straight from the file's sample format (bp_pcm_format; float PCM is the BP_PCM_F32 case): 16-bit stereo is
 // half the bytes of its float form over PCIe and the host never converts it.  Scales as in basic_pitch_amd/audio.py
 // read_wav / the WAV reader of file_pipeline.cpp (powers of two: exact), so the mono signal of an integer file is
 // bit-identical to that of its float form.
+// The big-endian formats (AIFF, CAF, AU) are the little-endian ones of the byte-swapped word, signed 8-bit is the unsigned
+// form of b ^ 0x80, a companded byte is the 16-bit form of its expansion: bit for bit, whatever follows.
 template <int FMT>
 __device__ __forceinline__ float pcm_sample(const uint8_t* __restrict__ raw, int64_t i) {
   if (FMT == BP_PCM_S16) return (float)reinterpret_cast<const int16_t*>(raw)[i] * (1.0f / 32768.0f);
+  if (FMT == BP_PCM_S16_BE) {
+    const uint32_t w = reinterpret_cast<const uint16_t*>(raw)[i];
+    return (float)(int16_t)((w >> 8) | (w << 8)) * (1.0f / 32768.0f);
+  }
   if (FMT == BP_PCM_U8) return ((float)raw[i] - 128.0f) * (1.0f / 128.0f);
-  if (FMT == BP_PCM_S24) {
+  if (FMT == BP_PCM_S8) return (float)(int8_t)raw[i] * (1.0f / 128.0f);
+  if (FMT == BP_PCM_ULAW) return (float)ulaw_expand(raw[i]) * (1.0f / 32768.0f);
+  if (FMT == BP_PCM_ALAW) return (float)alaw_expand(raw[i]) * (1.0f / 32768.0f);
+  if (FMT == BP_PCM_S24 || FMT == BP_PCM_S24_BE) {
     const uint8_t* p = raw + 3 * i;
-    int32_t v = (int32_t)p[0] | ((int32_t)p[1] << 8) | ((int32_t)p[2] << 16);
+    const int lo = FMT == BP_PCM_S24 ? 0 : 2;
+    int32_t v = (int32_t)p[lo] | ((int32_t)p[1] << 8) | ((int32_t)p[2 - lo] << 16);
     if (v >= 1 << 23) v -= 1 << 24;
     return (float)v * (1.0f / 8388608.0f);
   }
   if (FMT == BP_PCM_S32) return (float)((double)reinterpret_cast<const int32_t*>(raw)[i] * (1.0 / 2147483648.0));
+  if (FMT == BP_PCM_S32_BE)
+    return (float)((double)(int32_t)__builtin_bswap32(reinterpret_cast<const uint32_t*>(raw)[i]) * (1.0 / 2147483648.0));
   if (FMT == BP_PCM_F64) return (float)reinterpret_cast<const double*>(raw)[i];
+  if (FMT == BP_PCM_F64_BE) return (float)__longlong_as_double((long long)__builtin_bswap64(reinterpret_cast<const uint64_t*>(raw)[i]));
+  if (FMT == BP_PCM_F32_BE) return __uint_as_float(__builtin_bswap32(reinterpret_cast<const uint32_t*>(raw)[i]));
   return reinterpret_cast<const float*>(raw)[i];
 }
 
@@ -138,32 +166,46 @@ __device__ __forceinline__ float mono_frame(const uint8_t* __restrict__ raw, int
   return s / (float)channels;
 }
 
-// One call of f(std::integral_constant<int, FMT>) for a run-time bp_pcm_format (validated by the callers: pcm_width)
+// One call of f(std::integral_constant<int, FMT>) for a run-time bp_pcm_format (validated by the callers: pcm_width), on
+// the host (which kernel to launch) and in a kernel that learns its format from a table (clips_downmix_kernel)
 template <class F>
-void for_pcm_format(int format, F&& f) {
+__host__ __device__ __forceinline__ void for_pcm_format(int format, F&& f) {
   switch (format) {
     case BP_PCM_S16: return f(std::integral_constant<int, BP_PCM_S16>{});
     case BP_PCM_S24: return f(std::integral_constant<int, BP_PCM_S24>{});
     case BP_PCM_S32: return f(std::integral_constant<int, BP_PCM_S32>{});
     case BP_PCM_U8: return f(std::integral_constant<int, BP_PCM_U8>{});
     case BP_PCM_F64: return f(std::integral_constant<int, BP_PCM_F64>{});
+    case BP_PCM_S16_BE: return f(std::integral_constant<int, BP_PCM_S16_BE>{});
+    case BP_PCM_S24_BE: return f(std::integral_constant<int, BP_PCM_S24_BE>{});
+    case BP_PCM_S32_BE: return f(std::integral_constant<int, BP_PCM_S32_BE>{});
+    case BP_PCM_F32_BE: return f(std::integral_constant<int, BP_PCM_F32_BE>{});
+    case BP_PCM_F64_BE: return f(std::integral_constant<int, BP_PCM_F64_BE>{});
+    case BP_PCM_S8: return f(std::integral_constant<int, BP_PCM_S8>{});
+    case BP_PCM_ULAW: return f(std::integral_constant<int, BP_PCM_ULAW>{});
+    case BP_PCM_ALAW: return f(std::integral_constant<int, BP_PCM_ALAW>{});
     default: return f(std::integral_constant<int, BP_PCM_F32>{});
   }
 }
 
 // Four frames per thread (round 5: one frame per thread moved 63 MB in 34 us, a quarter of what the memory system streams;
 // in a file job this kernel runs once per file).  16-bit stereo — what a CD-quality WAV holds — takes them as one 16-byte
-// load and one 16-byte store; every format and channel count computes a frame exactly as before.
+// load and one 16-byte store, and so does its big-endian form, what a CD-quality AIFF holds: both halves of a word are
+// byte-swapped by one byte permute; every format and channel count computes a frame exactly as before.
 template <int FMT>
 __global__ __launch_bounds__(256) void downmix_raw_kernel(const uint8_t* __restrict__ raw, int64_t n_frames, int channels,
                                                           float* __restrict__ mono) {
   const int64_t i4 = ((int64_t)blockIdx.x * 256 + threadIdx.x) * 4;
   if (i4 >= n_frames) return;
-  if (FMT == BP_PCM_S16 && channels == 2 && i4 + 4 <= n_frames &&
+  if ((FMT == BP_PCM_S16 || FMT == BP_PCM_S16_BE) && channels == 2 && i4 + 4 <= n_frames &&
       ((reinterpret_cast<uintptr_t>(raw) | reinterpret_cast<uintptr_t>(mono)) & 15) == 0) {
     const uint4 v = *reinterpret_cast<const uint4*>(raw + i4 * 4);
-    const uint32_t w[4] = {v.x, v.y, v.z, v.w};
+    uint32_t w[4] = {v.x, v.y, v.z, v.w};
     float o[4];
+    if (FMT == BP_PCM_S16_BE) {
+#pragma unroll
+      for (int k = 0; k < 4; ++k) w[k] = __builtin_amdgcn_perm(w[k], w[k], 0x02030001u);  // bytes 1 0 3 2 of the word
+    }
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
       float s = 0.0f;
@@ -382,14 +424,7 @@ __global__ __launch_bounds__(256) void clips_downmix_kernel(const ClipDesc* __re
   auto frames = [&](auto fmt) {
     for (int64_t i = i4; i < i4 + 4 && i < n; ++i) mono[i] = mono_frame<decltype(fmt)::value>(raw, i, channels);
   };
-  switch (c.format) {
-    case BP_PCM_S16: frames(std::integral_constant<int, BP_PCM_S16>{}); break;
-    case BP_PCM_S24: frames(std::integral_constant<int, BP_PCM_S24>{}); break;
-    case BP_PCM_S32: frames(std::integral_constant<int, BP_PCM_S32>{}); break;
-    case BP_PCM_U8: frames(std::integral_constant<int, BP_PCM_U8>{}); break;
-    case BP_PCM_F64: frames(std::integral_constant<int, BP_PCM_F64>{}); break;
-    default: frames(std::integral_constant<int, BP_PCM_F32>{}); break;
-  }
+  for_pcm_format(c.format, frames);
 }
 
 // Output k of a clip is resample_sum at the clip-local index k with the clip's own n_in: the signal is zero outside the clip,

@@ -1,6 +1,7 @@
-// What the host side of the file job shares across its sources: wav_file.cpp (RIFF/WAVE), note_writers.cpp (.csv and
-// .mid bytes), file_io.cpp (reading and writing files, the thread's error string) and file_pipeline.cpp (the job itself,
-// the only one of the four that calls the device library).  Internal: nothing here is part of the library's interface.
+// What the host side of the file job shares across its sources: wav_file.cpp (RIFF/WAVE, RF64), pcm_file.cpp (AIFF, CAF,
+// AU), note_writers.cpp (.csv and .mid bytes), file_io.cpp (reading and writing files, the thread's error string) and
+// file_pipeline.cpp (the job itself, the only one of the five that calls the device library).  Internal: nothing here is
+// part of the library's interface.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -8,7 +9,7 @@
 #include <string>
 #include <vector>
 
-#include "../../include/basic_pitch_amd.h"
+#include "../../include/basic_pitch_amd_containers.h"
 
 namespace bp_file __attribute__((visibility("hidden"))) {
 
@@ -36,6 +37,16 @@ bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos);
 bool wav_parse(const uint8_t* d, size_t n, WavInfo& w);
 int wav_pcm_format(const WavInfo& w);  // the BP_PCM_* of the samples as the file stores them
 void wav_to_float(const WavInfo& w, float* out);
+
+// ---- pcm_file.cpp: the other containers of uncompressed samples, read like wav_walk from the headers alone.  Each fills
+// every field of `lay` (format = the BP_PCM_* of the samples as the file stores them) or sets g_file_error.  Uses
+// wav_file.cpp and file_io.cpp; nothing of wav_file.cpp, note_writers.cpp, file_io.cpp or the decoders uses it.
+int pcm_container_of(const uint8_t* head, size_t size);  // BP_CONTAINER_* by a file's first 12 bytes (fewer: `size`), or 0
+bool aiff_walk(const ByteSource& src, bp_pcm_file_layout& lay);
+bool caf_walk(const ByteSource& src, bp_pcm_file_layout& lay);
+bool au_walk(const ByteSource& src, bp_pcm_file_layout& lay);
+bool pcm_file_walk(const ByteSource& src, bp_pcm_file_layout& lay);  // whichever of the four the file is (WAV: wav_walk)
+void pcm_to_float(int format, const uint8_t* p, int64_t n_samples, float* out);  // the device's conversion, on the host
 
 // ---- note_writers.cpp
 void notes_csv(const bp_note_event* ev, int64_t n, const int32_t* bends, std::string& out);

@@ -6,8 +6,8 @@
 // second against 2,600 per second of device capacity.  Here a worker thread owns a file from its bytes to
 // its outputs; the GPU is a shared resource the workers queue for (one lane per handle), everything else runs in parallel.
 //
-// This file is the job alone: what it does on the host without a device lies in wav_file.cpp (RIFF/WAVE), note_writers.cpp
-// (.csv / .mid bytes) and file_io.cpp (reading and writing files), declared in file_host.h.
+// This file is the job alone: what it does on the host without a device lies in wav_file.cpp (RIFF/WAVE, RF64), pcm_file.cpp
+// (AIFF, CAF, AU), note_writers.cpp (.csv / .mid bytes) and file_io.cpp (reading and writing files), declared in file_host.h.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -97,11 +97,16 @@ struct Pinned {
 
 // ---------------------------------------------------------------------------------------------------------------------
 // What a file is and who decodes it: asked by the per-file route with the file's bytes and by clip_route with its headers.
-enum class Container { Neither, Wav, Flac };
+// Pcm: AIFF / AIFF-C, CAF or AU (pcm_file.cpp), like Wav a header around samples the device converts as they are stored.
+enum class Container { Neither, Wav, Flac, Pcm };
 
 // from a file's first bytes (up to 12 of them; `size` is the file's)
 Container sniff(const uint8_t* head, size_t size) {
-  if (size >= 12 && std::memcmp(head, "RIFF", 4) == 0 && std::memcmp(head + 8, "WAVE", 4) == 0) return Container::Wav;
+  switch (pcm_container_of(head, size)) {
+    case 0: break;
+    case BP_CONTAINER_WAV: return Container::Wav;  // RIFF, RF64 or BW64
+    default: return Container::Pcm;
+  }
   if (size >= 4 && (std::memcmp(head, "fLaC", 4) == 0 || std::memcmp(head, "ID3", 3) == 0)) return Container::Flac;
   return Container::Neither;
 }
@@ -140,7 +145,7 @@ struct ClipFile {
   int route = 0;  // 0: the per-file route; 1: a batched PCM call; 2: a batched FLAC call; negative: a bp_status
   int channels = 0, sample_rate = 0, format = BP_PCM_F32;
   int64_t n_frames = 0, windows = 0;
-  size_t data_pos = 0;  // WAV: where the samples lie in the file
+  size_t data_pos = 0;  // WAV, AIFF, CAF, AU: where the samples lie in the file
 };
 
 // the windows of n_frames frames at sample_rate at the lanes' geometry (no handle: that of the default mode)
@@ -170,6 +175,15 @@ int clip_route(const ByteSource& src, bp_handle h, const bp_transcribe_params& p
       c.channels = w.channels, c.sample_rate = w.sample_rate, c.n_frames = w.n_frames, c.format = wav_pcm_format(w);
       if (host_decodes(prm) || !in_domain() || src.size > kClipBatchBytes) return c.route = 0;
       c.windows = clip_windows(h, c.n_frames, c.sample_rate);  // a file without frames: a clip without rows
+      return c.route = c.windows <= BP_FILES_CLIP_MAX_WINDOWS ? 1 : 0;
+    }
+    case Container::Pcm: {  // what the Wav case does, from the other headers
+      bp_pcm_file_layout lay;
+      if (!pcm_file_walk(src, lay)) return c.route = BP_ERR_BAD_AUDIO;
+      c.channels = lay.channels, c.sample_rate = lay.sample_rate, c.n_frames = lay.n_frames, c.format = lay.format;
+      c.data_pos = (size_t)lay.data_start;
+      if (host_decodes(prm) || !in_domain() || src.size > kClipBatchBytes) return c.route = 0;
+      c.windows = clip_windows(h, c.n_frames, c.sample_rate);
       return c.route = c.windows <= BP_FILES_CLIP_MAX_WINDOWS ? 1 : 0;
     }
     case Container::Flac: {
@@ -436,6 +450,18 @@ bool Worker::read_audio(const std::string& path, bp_file_report* rep, Audio& a) 
       }
       // the samples go to the device as the file stores them (bp_infer_pcm_raw converts there)
       a.channels = w.channels, a.sample_rate = w.sample_rate, a.n_frames = w.n_frames, a.pcm = w.pcm, a.format = wav_pcm_format(w);
+      return true;
+    }
+    case Container::Pcm: {
+      ByteSource src;
+      src.mem = a.bytes, src.size = a.n_bytes;
+      bp_pcm_file_layout lay;
+      if (!pcm_file_walk(src, lay)) {
+        set_report(rep, BP_ERR_BAD_AUDIO, path + ": " + g_file_error);
+        return false;
+      }
+      a.channels = lay.channels, a.sample_rate = lay.sample_rate, a.n_frames = lay.n_frames, a.pcm = a.bytes + lay.data_start;
+      a.format = lay.format;
       return true;
     }
     case Container::Flac: {

@@ -52,8 +52,9 @@ int finish(bp_handle h, int rc) {
 }
 
 int pcm_width(int format) {
-  static const int width[] = {4, 2, 3, 4, 1, 8};  // BP_PCM_F32, S16, S24, S32, U8, F64
-  return format >= BP_PCM_F32 && format <= BP_PCM_F64 ? width[format] : 0;
+  // BP_PCM_F32, S16, S24, S32, U8, F64; S16_BE, S24_BE, S32_BE, F32_BE, F64_BE, S8, ULAW, ALAW
+  static const int width[] = {4, 2, 3, 4, 1, 8, 2, 3, 4, 4, 8, 1, 1, 1};
+  return format >= BP_PCM_F32 && format <= BP_PCM_ALAW ? width[format] : 0;
 }
 
 // pcm_given: false for a null pcm pointer (the FLAC path's device buffer counts as given)

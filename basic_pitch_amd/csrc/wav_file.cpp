@@ -1,6 +1,6 @@
 // RIFF / WAVE, on the host alone (basic_pitch_amd/audio.py read_wav: PCM 8 / 16 / 24 / 32 and IEEE float 32 / 64,
-// WAVE_FORMAT_EXTENSIBLE): the chunk walk, the sample conversion, bp_wav_info and bp_wav_decode.  Nothing here calls the device
-// library; the file job (file_pipeline.cpp) parses its WAV files with wav_walk / wav_parse and sends the samples as stored.
+// WAVE_FORMAT_EXTENSIBLE; RF64 / BW64, whose 64-bit data size lies in a ds64 chunk: EBU Tech 3306): the chunk walk, the
+// sample conversion, bp_wav_info and bp_wav_decode.  Nothing here calls the device library; the file job (file_pipeline.cpp) parses its WAV files with wav_walk / wav_parse and sends the samples as stored.
 #include <cerrno>
 #include <cstring>
 #include <unistd.h>
@@ -12,6 +12,7 @@ namespace bp_file {
 namespace {
 uint32_t rd32(const uint8_t* p) { return (uint32_t)p[0] | ((uint32_t)p[1] << 8) | ((uint32_t)p[2] << 16) | ((uint32_t)p[3] << 24); }
 uint16_t rd16(const uint8_t* p) { return (uint16_t)(p[0] | (p[1] << 8)); }
+uint64_t rd64(const uint8_t* p) { return (uint64_t)rd32(p) | ((uint64_t)rd32(p + 4) << 32); }
 }  // namespace
 
 bool ByteSource::at(size_t pos, size_t len, uint8_t* out) const {
@@ -33,20 +34,29 @@ bool ByteSource::at(size_t pos, size_t len, uint8_t* out) const {
 }
 
 // the chunk walk of a RIFF/WAVE file: the format and where the samples lie (data_pos; w.pcm is the caller's to set).  Reads
-// the 12-byte head, every chunk's 8-byte head and up to 26 bytes of a fmt chunk, nothing else.
+// the 12-byte head, every chunk's 8-byte head, up to 26 bytes of a fmt chunk and 24 of a ds64 chunk, nothing else.
 bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos) {
   const size_t n = src.size;
-  uint8_t head[12], body[26];
-  if (n < 12 || !src.at(0, 12, head) || std::memcmp(head, "RIFF", 4) != 0 || std::memcmp(head + 8, "WAVE", 4) != 0) {
+  uint8_t head[12] = {0}, body[26];
+  if (n >= 12) (void)src.at(0, 12, head);
+  // RF64 / BW64: the sizes that do not fit 32 bits are 0xffffffff in place and stand in the ds64 chunk
+  const bool rf64 = std::memcmp(head, "RF64", 4) == 0 || std::memcmp(head, "BW64", 4) == 0;
+  if (n < 12 || !(rf64 || std::memcmp(head, "RIFF", 4) == 0) || std::memcmp(head + 8, "WAVE", 4) != 0) {
     g_file_error = "not a RIFF/WAVE file";
     return false;
   }
   size_t pos = 12;
-  bool have_fmt = false, have_data = false;
+  bool have_fmt = false, have_data = false, have_ds64 = false;
+  uint64_t ds64_data = 0;
   while (pos + 8 <= n) {
     if (!src.at(pos, 8, head)) return false;
-    const uint32_t size = rd32(head + 4);
-    const size_t avail = n - (pos + 8) < size ? n - (pos + 8) : size;  // a truncated last chunk: what is there
+    uint64_t size = rd32(head + 4);
+    if (rf64 && have_ds64 && size == 0xffffffffu && std::memcmp(head, "data", 4) == 0) size = ds64_data;
+    const size_t avail = n - (pos + 8) < size ? n - (pos + 8) : (size_t)size;  // a truncated last chunk: what is there
+    if (rf64 && std::memcmp(head, "ds64", 4) == 0 && avail >= 24) {  // RIFF size, data size, sample count
+      if (!src.at(pos + 8, 24, body)) return false;
+      ds64_data = rd64(body + 8), have_ds64 = true;
+    }
     if (std::memcmp(head, "fmt ", 4) == 0 && avail >= 16) {
       if (!src.at(pos + 8, avail < 26 ? avail : 26, body)) return false;
       w.tag = rd16(body), w.channels = rd16(body + 2), w.sample_rate = (int)rd32(body + 4), w.bits = rd16(body + 14);
@@ -56,6 +66,7 @@ bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos) {
       data_pos = pos + 8, w.pcm_bytes = avail;
       have_data = true;
     }
+    if (size >= n - (pos + 8)) break;  // the file ends in this chunk
     pos += 8 + (size_t)size + (size & 1);
   }
   if (!have_fmt || !have_data) {

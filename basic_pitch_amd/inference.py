@@ -342,7 +342,7 @@ class Model:
         of n_frames * channels of them): they cross PCIe as they are — 16-bit stereo is half the bytes of its float form
         — and become float on the device, bit-identical to converting on the host first (bp_infer_pcm_raw)."""
         buf = np.frombuffer(samples, dtype=np.uint8)
-        width = _native.BP_PCM_WAV[int(fmt)][1] // 8
+        width = _native.BP_PCM_WIDTH[int(fmt)]
         if buf.size < int(n_frames) * int(channels) * width:
             raise ValueError("predict_pcm_raw: the buffer is shorter than n_frames * channels samples")
         out = _empty_maps((self._pcm_frames(n_frames, sample_rate),))
@@ -396,8 +396,8 @@ class Model:
         decode: str = "host",
     ) -> "List[Tuple[Any, List[Any]]]":
         """Many short clips -> [(midi_data, note_events)] in input order, with the decoding parameters of `predict`.
-        `clips`: numpy arrays [n] or [n, channels] of float32, int16, int32, uint8 or float64 samples; `sample_rates`: one int
-        for all or one per clip.  The clips of a rate go to the device in ONE call (`bp_infer_clips_candidates`: a constant
+        `clips`: numpy arrays [n] or [n, channels] of float32, int16, int32, uint8 or float64 samples (either byte order);
+        `sample_rates`: one int for all or one per clip.  The clips of a rate go to the device in ONE call (`bp_infer_clips_candidates`: a constant
         number of launches per batch of windows instead of about ten per clip) and come back as what the sequential half of
         note decoding needs; the events of a clip are those of `predict_pcm_raw` + `model_output_to_notes` on it alone.
         decode="device": the sequential half runs on the device as well (`bp_infer_clips_events`, one workgroup per clip) and
@@ -604,6 +604,12 @@ def run_inference(
         raw, tag, bits, channels, file_sr = _audio.wav_raw(str(audio_path))
         n_file_frames = len(raw) // (bits // 8) // channels
         unwrapped_output = model.predict_pcm_raw(raw, _WAV_PCM[(tag, bits)], n_file_frames, channels, file_sr)
+    elif ((head[:4] in (b"RF64", b"BW64") and head[8:12] == b"WAVE") or (head[:4] == b"FORM" and head[8:12] in (b"AIFF", b"AIFC"))
+          or head[:4] in (b"caff", b".snd")) and hasattr(model, "predict_pcm_raw"):
+        # RF64 / BW64, AIFF / AIFF-C, CAF, AU: the same, in whichever of the fourteen sample formats the file holds (big-endian
+        # words, signed bytes, G.711: converted on the device like the WAV formats)
+        raw, fmt, channels, file_sr, n_file_frames = _audio.pcm_raw(str(audio_path))
+        unwrapped_output = model.predict_pcm_raw(raw, fmt, n_file_frames, channels, file_sr)
     elif head[:4] == b"fLaC" and hasattr(model, "predict_flac"):
         # a FLAC file's BYTES go to the device and are decoded there (csrc/flac_device.hip): half the PCIe bytes of the PCM and
         # no host core-time per sample; what the device decoder leaves to the host (or cannot follow) is decoded here as
@@ -1055,8 +1061,8 @@ def transcribe_files(
     host_flac: bool = False,
     clip_batch: int = 0,
 ) -> List[Dict[str, Any]]:
-    """The batch job of `predict_and_save` (inference.py:509-604) for WAV / FLAC input and MIDI / note-event output, run
-    natively: ONE call into the library (`bp_transcribe_files`, csrc/file_pipeline.cpp), C++ worker threads from the
+    """The batch job of `predict_and_save` (inference.py:509-604) for WAV / AIFF / CAF / AU / FLAC input and MIDI /
+    note-event output, run natively: ONE call into the library (`bp_transcribe_files`, csrc/file_pipeline.cpp), C++ worker threads from the
     file's bytes to its outputs, no Python in the loop.  Same bytes as `predict_and_save(..., save_midi, False, False,
     save_notes)`.  `models` (or `lanes` models per device of `devices` — default: device 0 — built from
     `model_or_model_path`) are the GPU lanes the workers queue for; lanes may live on different GPUs, a worker takes
@@ -1068,8 +1074,8 @@ def transcribe_files(
     path, all three posteriorgrams decoded on the host; same bytes).  `direct_io=True` reads the files with O_DIRECT straight
     into the page-locked buffers the GPU copies from (no page-cache copy; for corpora larger than the page cache).
     `clip_batch=N` (default 0: off) is for data sets of SHORT files — excerpts of at most 15 windows, about 25 s: a worker
-    claims up to N consecutive inputs (at most 1024) and takes the short WAV / device-decodable FLAC files among them through
-    one clips-events call per container and sample rate (`bp_infer_clips_events` / `bp_infer_flac_clips_events`) instead of one
+    claims up to N consecutive inputs (at most 1024) and takes the short WAV / AIFF / CAF / AU / device-decodable FLAC files
+    among them through one clips-events call per container and sample rate (`bp_infer_clips_events` / `bp_infer_flac_clips_events`) instead of one
     call per file; longer files, and whatever such a call does not finish, go the per-file route.  Same bytes, same reports.
     Measured on one MI355X with three lanes and 16 threads, jobs of 4,096 files with the outputs on a memory file system
     (profiles/files_clip_batches.md), files per second at N = 0 -> 64: one-window WAV 11,600 -> 61,200, four-window WAV 8,100 ->

@@ -72,9 +72,12 @@ STREAM_EVENTS_PROTOTYPES = {
 }
 TAIL_ROWS = 2 * 142  # the rows a peek can have: what a rolling stream's ring holds beyond its horizon
 
-# the numpy type a chunk of each format is made of (BP_PCM_S24: packed bytes)
+# the numpy type a chunk of each format is made of (packed 24-bit and G.711: bytes)
 _DTYPES = {_native.BP_PCM_F32: np.float32, _native.BP_PCM_S16: np.int16, _native.BP_PCM_S24: np.uint8,
-           _native.BP_PCM_S32: np.int32, _native.BP_PCM_U8: np.uint8, _native.BP_PCM_F64: np.float64}
+           _native.BP_PCM_S32: np.int32, _native.BP_PCM_U8: np.uint8, _native.BP_PCM_F64: np.float64,
+           _native.BP_PCM_S16_BE: np.dtype(">i2"), _native.BP_PCM_S24_BE: np.uint8, _native.BP_PCM_S32_BE: np.dtype(">i4"),
+           _native.BP_PCM_F32_BE: np.dtype(">f4"), _native.BP_PCM_F64_BE: np.dtype(">f8"), _native.BP_PCM_S8: np.int8,
+           _native.BP_PCM_ULAW: np.uint8, _native.BP_PCM_ALAW: np.uint8}
 
 
 def bind(lib: C.CDLL) -> C.CDLL:
@@ -103,7 +106,7 @@ class Stream:
         self._s = C.c_void_p()
         rc = self._lib.bp_stream_open(model._handle, self.fmt, self.channels, self.sample_rate, C.byref(self._s))
         _native.check(self._lib, model._handle, rc, "bp_stream_open")
-        self._frame_bytes = self.channels * _native.BP_PCM_WAV[self.fmt][1] // 8
+        self._frame_bytes = self.channels * _native.BP_PCM_WIDTH[self.fmt]
         self.rows = 0  # rows emitted so far
 
     # -- lifetime ---------------------------------------------------------------------------------

@@ -182,10 +182,13 @@ int bp_infer_pcm(bp_handle h, const float* pcm, int64_t n_frames, int channels, 
                  float* onset, float* contour, int mem_kind);
 
 /*
- * bp_infer_pcm on the samples as the file stores them: interleaved little-endian PCM in one of the formats below goes over
- * PCIe as it is (16-bit stereo: half the bytes of its float form) and becomes float on the device, with the scaling of
- * libsndfile's float read that librosa.load uses (inference.py:239): integers / 2^(bits-1), 8-bit unsigned (v - 128) / 128,
- * float64 rounded to float32.  Same result, bit for bit, as converting on the host and calling bp_infer_pcm.
+ * bp_infer_pcm on the samples as the file stores them: interleaved PCM in one of the formats below (little-endian where
+ * the name does not say _BE) goes over PCIe as it is (16-bit stereo: half the bytes of its float form) and becomes float on
+ * the device, with the scaling of libsndfile's float read that librosa.load uses (inference.py:239): integers / 2^(bits-1),
+ * 8-bit unsigned (v - 128) / 128, 8-bit signed v / 128, G.711 bytes expanded to 16 bits / 32768, float64 rounded to float32.
+ * Same result, bit for bit, as converting on the host and calling bp_infer_pcm.  Codes 6 to 13 are what AIFF, CAF and AU
+ * files hold (basic_pitch_amd_containers.h); each equals, bit for bit, the plain format named beside it on the converted
+ * bytes, for any channel count and any alignment of the buffer.  `format` of every call below: one of these 14 codes.
  * bp_host_alloc / bp_host_free: page-locked host memory (any thread, any device); copies to and from it are DMA without
  * the runtime's staging copy — for `pcm` and the three outputs of the BP_MEM_HOST calls.  NULL when the allocation fails.
  */
@@ -195,7 +198,15 @@ typedef enum bp_pcm_format {
   BP_PCM_S24 = 2, /* packed, 3 bytes per sample */
   BP_PCM_S32 = 3,
   BP_PCM_U8 = 4,
-  BP_PCM_F64 = 5
+  BP_PCM_F64 = 5,
+  BP_PCM_S16_BE = 6,  /* big-endian: BP_PCM_S16 of the byte-swapped samples */
+  BP_PCM_S24_BE = 7,  /* packed, big-endian: BP_PCM_S24 of the reversed triples */
+  BP_PCM_S32_BE = 8,  /* BP_PCM_S32 swapped */
+  BP_PCM_F32_BE = 9,  /* BP_PCM_F32 swapped */
+  BP_PCM_F64_BE = 10, /* BP_PCM_F64 swapped */
+  BP_PCM_S8 = 11,     /* signed 8-bit, v / 128: BP_PCM_U8 of b ^ 0x80 */
+  BP_PCM_ULAW = 12,   /* G.711 mu-law, one byte per sample: BP_PCM_S16 of the expanded values */
+  BP_PCM_ALAW = 13    /* G.711 A-law, one byte per sample: BP_PCM_S16 of the expanded values */
 } bp_pcm_format;
 int bp_infer_pcm_raw(bp_handle h, const void* pcm, int format, int64_t n_frames, int channels, int sample_rate, float* note,
                      float* onset, float* contour, int mem_kind);
@@ -468,7 +479,8 @@ const char* bp_notes_last_error(void);
  * this header. */
 
 /* ---- whole files, natively: decode -> posteriorgrams -> note events -> .mid / .csv (host C++ threads) ----------
- * Replaces the per-file Python loop of predict_and_save (basic_pitch/inference.py:509-604) for WAV and FLAC input:
+ * Replaces the per-file Python loop of predict_and_save (basic_pitch/inference.py:509-604) for WAV (RF64 / BW64 too), AIFF / AIFF-C, CAF, AU
+ * (basic_pitch_amd_containers.h) and FLAC input:
  * librosa.load (239: decode; downmix + resampling on the device), run_inference (282-330), model_output_to_notes
  * (note_creation.py:52-116), note_events_to_midi + pretty_midi write (222-267; inference.py:586) and save_note_events
  * (inference.py:409-428).  A worker thread owns a file from its bytes to its outputs; the handles are GPU lanes the
@@ -498,8 +510,8 @@ typedef struct bp_transcribe_params {
                                    no host core-time per sample; streams it leaves to the host fall back by themselves);
                                    1: on the host (bp_flac_decode), the round-4 path */
   int32_t clip_batch;           /* 0 (default): a worker owns one file at a time.  N > 0: a worker claims up to N consecutive
-                                   inputs (at most 1024) and takes the SHORT files among them — WAV, or FLAC the device
-                                   decodes, of at most BP_FILES_CLIP_MAX_WINDOWS windows — through one bp_infer_clips_events /
+                                   inputs (at most 1024) and takes the SHORT files among them — WAV, AIFF, CAF, AU, or FLAC the
+                                   device decodes, of at most BP_FILES_CLIP_MAX_WINDOWS windows — through one bp_infer_clips_events /
                                    bp_infer_flac_clips_events call per container and sample rate on one lane acquisition; every
                                    other file, and every file such a call does not finish (a clip status other than 0, a rate
                                    whose filter is not tabulated, a failed call), goes the per-file route.  Same output
@@ -530,7 +542,7 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
  * device library; the CPU tests pin them to the Python writers and readers).
  * bp_notes_to_midi / bp_notes_to_csv return the number of bytes of the file (written to `out` if it fits `capacity`; call
  * with out = NULL to size the buffer), or a negative bp_status.  `bends` may be NULL (no pitch bends).
- * bp_wav_info / bp_wav_decode: RIFF/WAVE PCM 8 / 16 / 24 / 32 and IEEE float 32 / 64 -> float32 [n_frames, channels] in
+ * bp_wav_info / bp_wav_decode: RIFF/WAVE (RF64 / BW64 too) PCM 8 / 16 / 24 / 32 and IEEE float 32 / 64 -> float32 [n_frames, channels] in
  * [-1, 1), the scaling of libsndfile's float read that librosa.load uses (inference.py:239). */
 int64_t bp_notes_to_midi(const bp_note_event* events, int64_t n_events, const int32_t* bends, int multiple_pitch_bends,
                          double midi_tempo, uint8_t* out, int64_t capacity);

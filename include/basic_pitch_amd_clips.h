@@ -24,7 +24,7 @@ extern "C" {
  * onset rows, or params->onset_threshold <= 0; the caller decodes that clip's maps itself (bp_infer_pcm_raw + bp_notes_decode).
  * A NaN in one clip changes no other clip's status or bytes.  A clip of n_frames = 0 has no rows and status 0.
  *
- *   format, channels   per clip (format: a BP_PCM_* code); one sample_rate per call.  A ratio sample_rate : the handle's rate
+ *   format, channels   per clip (format: any of the 14 BP_PCM_* codes); one sample_rate per call.  A ratio sample_rate : the handle's rate
  *                      whose filter the one-shot calls evaluate in the kernel is refused with BP_ERR_UNSUPPORTED, as
  *                      bp_stream_open refuses it.  Clips that are mono float32 at the handle's rate are windowed where they lie.
  *   pcm_mem_kind       BP_MEM_HOST or BP_MEM_DEVICE: where every clip's pcm lies.  The outputs are host buffers.
