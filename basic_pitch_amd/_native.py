@@ -31,11 +31,12 @@ BP_PCM_F32, BP_PCM_S16, BP_PCM_S24, BP_PCM_S32, BP_PCM_U8, BP_PCM_F64 = range(6)
 BP_PCM_S16_BE, BP_PCM_S24_BE, BP_PCM_S32_BE, BP_PCM_F32_BE, BP_PCM_F64_BE, BP_PCM_S8, BP_PCM_ULAW, BP_PCM_ALAW = range(6, 14)
 # the WAV (format tag, bits per sample) each code stands for; a sample is bits // 8 bytes wide
 BP_PCM_WAV = {BP_PCM_U8: (1, 8), BP_PCM_S16: (1, 16), BP_PCM_S24: (1, 24), BP_PCM_S32: (1, 32), BP_PCM_F32: (3, 32),
-              BP_PCM_F64: (3, 64)}
+              BP_PCM_F64: (3, 64), BP_PCM_ULAW: (7, 8), BP_PCM_ALAW: (6, 8)}
 # bytes per sample of every code
 BP_PCM_WIDTH = {BP_PCM_F32: 4, BP_PCM_S16: 2, BP_PCM_S24: 3, BP_PCM_S32: 4, BP_PCM_U8: 1, BP_PCM_F64: 8, BP_PCM_S16_BE: 2,
                 BP_PCM_S24_BE: 3, BP_PCM_S32_BE: 4, BP_PCM_F32_BE: 4, BP_PCM_F64_BE: 8, BP_PCM_S8: 1, BP_PCM_ULAW: 1, BP_PCM_ALAW: 1}
 BP_CONTAINER_WAV, BP_CONTAINER_AIFF, BP_CONTAINER_CAF, BP_CONTAINER_AU = 1, 2, 3, 4
+BP_ADPCM_IMA_WAV, BP_ADPCM_IMA4 = 1, 2  # include/basic_pitch_amd_adpcm.h: RIFF/WAVE format tag 0x11, CAF `ima4`
 BP_N_STAGES = 15
 BP_FILES_CLIP_MAX_WINDOWS = 15  # the longest file, in windows, that bp_transcribe_params.clip_batch sends to a batched call
 BP_Z_ROW = 448
@@ -127,6 +128,24 @@ class bp_pcm_file_layout(C.Structure):
         ("n_frames", C.c_int64),
         ("data_start", C.c_int64),
     ]
+
+
+class bp_adpcm_layout(C.Structure):
+    _fields_ = [
+        ("container", C.c_int32),
+        ("codec", C.c_int32),
+        ("channels", C.c_int32),
+        ("sample_rate", C.c_int32),
+        ("block_bytes", C.c_int32),
+        ("block_frames", C.c_int32),
+        ("n_frames", C.c_int64),
+        ("data_start", C.c_int64),
+        ("data_bytes", C.c_int64),
+    ]
+
+
+class bp_adpcm_clip(C.Structure):
+    _fields_ = [("file", C.c_void_p), ("nbytes", C.c_size_t)]
 
 
 class bp_transcribe_params(C.Structure):
@@ -311,6 +330,15 @@ CONTAINERS_SYMBOLS = [
     "bp_pcm_file_layout_of",
     "bp_pcm_file_decode",
 ]
+# every symbol include/basic_pitch_amd_adpcm.h declares (bound below)
+ADPCM_SYMBOLS = [
+    "bp_adpcm_layout_of",
+    "bp_adpcm_decode",
+    "bp_adpcm_decode_device",
+    "bp_infer_adpcm",
+    "bp_infer_adpcm_candidates",
+    "bp_infer_adpcm_clips_events",
+]
 # status values of a clip in those calls, beside 0, 1 and 2 of the PCM clips calls
 BP_CLIP_FLAC_HOST = 3    # left to the host decoder, known before anything is queued: no rows
 BP_CLIP_FLAC_FAILED = 4  # the device decoder could not follow the stream
@@ -465,6 +493,18 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bp_pcm_file_layout_of.restype = C.c_int
     lib.bp_pcm_file_decode.argtypes = [C.c_char_p, C.c_size_t, fp, i64, C.POINTER(i64)]
     lib.bp_pcm_file_decode.restype = C.c_int
+    lib.bp_adpcm_layout_of.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(bp_adpcm_layout)]
+    lib.bp_adpcm_layout_of.restype = C.c_int
+    lib.bp_adpcm_decode.argtypes = [C.c_char_p, C.c_size_t, vp, i64, C.POINTER(i64)]
+    lib.bp_adpcm_decode.restype = C.c_int
+    lib.bp_adpcm_decode_device.argtypes = [vp, C.c_char_p, C.c_size_t, vp, i64, C.POINTER(i64)]
+    lib.bp_adpcm_decode_device.restype = C.c_int
+    lib.bp_infer_adpcm.argtypes = [vp, C.c_char_p, C.c_size_t, fp, fp, fp, C.c_int]
+    lib.bp_infer_adpcm.restype = C.c_int
+    lib.bp_infer_adpcm_candidates.argtypes = [vp, C.c_char_p, C.c_size_t, C.POINTER(bp_note_params), vp, vp, vp, C.POINTER(C.c_int)]
+    lib.bp_infer_adpcm_candidates.restype = C.c_int
+    lib.bp_infer_adpcm_clips_events.argtypes = [vp, i64, C.POINTER(bp_adpcm_clip), vp, vp, i64, vp, i64, vp, vp]
+    lib.bp_infer_adpcm_clips_events.restype = C.c_int
     lib.bp_files_last_error.argtypes = []
     lib.bp_files_last_error.restype = C.c_char_p
     if path is None:

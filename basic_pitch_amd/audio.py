@@ -24,10 +24,12 @@ from . import _native as _n
 AUDIO_SAMPLE_RATE = 22050
 
 
-def wav_raw(path: Union[str, pathlib.Path]):
-    """The samples of a RIFF/WAVE file as the file stores them: (uint8 view of the data chunk, format tag, bits, channels,
-    sample_rate).  Tag 1 = integer PCM (8 / 16 / 24 / 32 bits), 3 = IEEE float (32 / 64).  RF64 / BW64 files, whose data
-    size lies in the ds64 chunk, are WAV files here."""
+WAV_TAG_IMA = 0x11  # IMA / DVI ADPCM: blocks, not samples (`adpcm_raw`, `ima_decode`)
+
+
+def _wav_chunks(path: Union[str, pathlib.Path]):
+    """The chunk walk of a RIFF/WAVE file (RF64 / BW64 too): (view of the data chunk, format tag, bits, channels, sample_rate,
+    block align, the fact chunk's sample count or None)."""
     with open(path, "rb") as f:
         data = memoryview(f.read())  # chunks below are views, not copies (a 3-minute stereo file is 31 MB)
     rf64 = len(data) >= 4 and bytes(data[:4]) in (b"RF64", b"BW64")
@@ -37,6 +39,7 @@ def wav_raw(path: Union[str, pathlib.Path]):
     fmt = None
     pcm = None
     ds64_data = None
+    fact = None
     while pos + 8 <= len(data):
         cid = bytes(data[pos : pos + 4])
         size = struct.unpack_from("<I", data, pos + 4)[0]
@@ -46,26 +49,204 @@ def wav_raw(path: Union[str, pathlib.Path]):
         if rf64 and cid == b"ds64" and len(body) >= 24:
             ds64_data = struct.unpack_from("<Q", body, 8)[0]
         if cid == b"fmt ":
-            tag, ch, sr, _br, _ba, bits = struct.unpack_from("<HHIIHH", body, 0)
+            tag, ch, sr, _br, align, bits = struct.unpack_from("<HHIIHH", body, 0)
             if tag == 0xFFFE and len(body) >= 26:  # WAVE_FORMAT_EXTENSIBLE: real tag in the GUID
                 tag = struct.unpack_from("<H", body, 24)[0]
-            fmt = (tag, ch, sr, bits)
+            fmt = (tag, ch, sr, bits, align)
         elif cid == b"data":
             pcm = body
+        elif cid == b"fact" and len(body) >= 4:
+            fact = struct.unpack_from("<I", body, 0)[0]
+            fact = None if fact == 0xFFFFFFFF else fact
         pos += 8 + size + (size & 1)
     if fmt is None or pcm is None:
         raise ValueError(f"{path}: missing fmt or data chunk")
-    tag, ch, sr, bits = fmt
-    if not ((tag == 1 and bits in (8, 16, 24, 32)) or (tag == 3 and bits in (32, 64))):
+    tag, ch, sr, bits, align = fmt
+    return pcm, tag, bits, ch, sr, align, fact
+
+
+def wav_raw(path: Union[str, pathlib.Path]):
+    """The samples of a RIFF/WAVE file as the file stores them: (uint8 view of the data chunk, format tag, bits, channels,
+    sample_rate).  Tag 1 = integer PCM (8 / 16 / 24 / 32 bits), 3 = IEEE float (32 / 64), 7 / 6 = G.711 mu-law / A-law (8).
+    RF64 / BW64 files, whose data size lies in the ds64 chunk, are WAV files here.  IMA ADPCM (tag 0x11) is not samples but
+    blocks: `adpcm_raw`."""
+    return _wav_pcm(path, _wav_chunks(path))
+
+
+def _wav_pcm(path, chunks):
+    pcm, tag, bits, ch, sr, _align, _fact = chunks
+    if tag == WAV_TAG_IMA:
+        raise ValueError(f"{path}: IMA ADPCM samples are blocks, not PCM (audio.adpcm_raw reads the file)")
+    if not ((tag == 1 and bits in (8, 16, 24, 32)) or (tag == 3 and bits in (32, 64)) or (tag in (6, 7) and bits == 8)):
         raise ValueError(f"{path}: unsupported PCM bit depth {bits}" if tag == 1 else f"{path}: unsupported WAV format tag {tag}")
     if ch < 1:
         raise ValueError(f"{path}: zero channels")
     return pcm, tag, bits, ch, sr
 
 
+_IMA_STEP = np.array([
+    7, 8, 9, 10, 11, 12, 13, 14, 16, 17, 19, 21, 23, 25, 28, 31, 34, 37, 41, 45, 50, 55, 60, 66, 73, 80, 88, 97, 107, 118, 130,
+    143, 157, 173, 190, 209, 230, 253, 279, 307, 337, 371, 408, 449, 494, 544, 598, 658, 724, 796, 876, 963, 1060, 1166, 1282,
+    1411, 1552, 1707, 1878, 2066, 2272, 2499, 2749, 3024, 3327, 3660, 4026, 4428, 4871, 5358, 5894, 6484, 7132, 7845, 8630,
+    9493, 10442, 11487, 12635, 13899, 15289, 16818, 18500, 20350, 22385, 24623, 27086, 29794, 32767], dtype=np.int32)
+_IMA_INDEX = np.array([-1, -1, -1, -1, 2, 4, 6, 8], dtype=np.int32)
+
+
+def is_adpcm_file(path: Union[str, pathlib.Path]) -> bool:
+    """Whether the format chunk of a RIFF/WAVE (RF64 / BW64) or CAF file says IMA ADPCM: tag 0x11, or `ima4`.  Reads the
+    chunk heads up to that chunk, nothing else."""
+    with open(path, "rb") as f:
+        head = f.read(12)
+        if head[:4] == b"caff":
+            f.seek(8)
+            while True:
+                h = f.read(12)
+                if len(h) < 12:
+                    return False
+                size = struct.unpack(">q", h[4:])[0]
+                if h[:4] == b"desc":
+                    return f.read(12)[8:12] == b"ima4"
+                if size < 0:
+                    return False
+                f.seek(size, 1)
+        if head[:4] not in (b"RIFF", b"RF64", b"BW64") or head[8:12] != b"WAVE":
+            return False
+        while True:
+            h = f.read(8)
+            if len(h) < 8:
+                return False
+            size = struct.unpack("<I", h[4:])[0]
+            if h[:4] == b"fmt ":
+                body = f.read(min(size, 26))
+                if len(body) < 16:
+                    return False
+                tag = struct.unpack_from("<H", body, 0)[0]
+                if tag == 0xFFFE and len(body) >= 26:
+                    tag = struct.unpack_from("<H", body, 24)[0]
+                return tag == WAV_TAG_IMA
+            if h[:4] == b"data":  # (a data chunk of 0xffffffff bytes in front of the format: not walked)
+                return False
+            f.seek(size + (size & 1), 1)
+
+
+def adpcm_raw(path: Union[str, pathlib.Path]):
+    """The blocks of an IMA ADPCM file as the file stores them, or None for a file that is something else: (uint8 view of the
+    whole blocks, codec BP_ADPCM_IMA_WAV | BP_ADPCM_IMA4, channels, sample_rate, block_bytes, block_frames, n_frames).  RIFF/WAVE
+    format tag 0x11 (plain, EXTENSIBLE, RF64 / BW64) and CAF `ima4`; the layouts are those of
+    include/basic_pitch_amd_adpcm.h, independent of the C++ parser (csrc/adpcm_file.cpp), which the tests hold to it."""
+    with open(path, "rb") as f:
+        head = f.read(12)
+    if head[:4] in (b"RIFF", b"RF64", b"BW64") and head[8:12] == b"WAVE":
+        try:
+            pcm, tag, bits, ch, sr, align, fact = _wav_chunks(path)
+        except ValueError:
+            return None
+        if tag != WAV_TAG_IMA:
+            return None
+        if bits != 4:
+            raise ValueError(f"{path}: unsupported IMA ADPCM sample size {bits} (4 bits a sample are read)")
+        if ch < 1:
+            raise ValueError(f"{path}: zero channels")
+        payload = align - 4 * ch
+        if payload <= 0 or payload % (4 * ch):
+            raise ValueError(f"{path}: unsupported IMA ADPCM block align {align} for {ch} channels (4 header bytes and whole "
+                             "groups of 4 bytes a channel are read)")
+        block_frames = payload * 2 // ch + 1
+        blocks = len(pcm) // align
+        n = blocks * block_frames if fact is None else min(fact, blocks * block_frames)
+        return np.frombuffer(pcm, dtype=np.uint8)[: blocks * align], _n.BP_ADPCM_IMA_WAV, ch, sr, align, block_frames, n
+    if head[:4] != b"caff":
+        return None
+    with open(path, "rb") as f:
+        data = memoryview(f.read())
+    if len(data) < 8 or struct.unpack_from(">H", data, 4)[0] != 1:
+        return None
+    desc = pcm = pakt = None
+    pos = 8
+    while pos + 12 <= len(data):
+        cid = bytes(data[pos : pos + 4])
+        size = struct.unpack_from(">q", data, pos + 4)[0]
+        rest = len(data) - (pos + 12)
+        body = data[pos + 12 : pos + 12 + (rest if size < 0 else min(size, rest))]
+        if cid == b"desc" and len(body) >= 32:
+            desc = struct.unpack_from(">d4sIIIII", body, 0)
+        elif cid == b"pakt" and len(body) >= 24:
+            pakt = struct.unpack_from(">qqii", body, 0)
+        elif cid == b"data":
+            pcm = body[4:]
+        if size < 0:
+            break
+        pos += 12 + size
+    if desc is None or desc[1] != b"ima4":
+        return None
+    if pcm is None:
+        raise ValueError(f"{path}: missing desc or data chunk")
+    rate, _fid, _flags, packet_bytes, packet_frames, ch, _bits = desc
+    if ch < 1:
+        raise ValueError(f"{path}: zero channels")
+    if packet_frames != 64 or packet_bytes != 34 * ch:
+        raise ValueError(f"{path}: unsupported CAF ima4 packet layout: {packet_frames} frames in {packet_bytes} bytes a packet "
+                         f"(read: 64 frames in {34 * ch} bytes)")
+    packets = len(pcm) // (34 * ch)
+    n = packets * 64
+    if pakt is not None:
+        if pakt[2] != 0:
+            raise ValueError(f"{path}: unsupported CAF pakt chunk: {pakt[2]} priming frames (read: 0)")
+        if 0 <= pakt[1] < n:
+            n = pakt[1]
+    return np.frombuffer(pcm, dtype=np.uint8)[: packets * 34 * ch], _n.BP_ADPCM_IMA4, ch, _rate(path, rate), 34 * ch, 64, n
+
+
+def ima_decode(blocks: np.ndarray, codec: int, channels: int, block_bytes: int, n_frames: int) -> np.ndarray:
+    """The whole blocks `adpcm_raw` returns -> int16 [n_frames, channels].  The chains (one channel of one block) run side by
+    side in numpy, a chain's codes one after the other: d = s>>3 (+ s, + s>>1, + s>>2 by the code's bits 2, 1, 0), subtracted
+    for bit 3, the predictor clamped to int16, the index moved by {-1, -1, -1, -1, 2, 4, 6, 8} and clamped to 0 ... 88."""
+    ch = int(channels)
+    b = np.ascontiguousarray(blocks, dtype=np.uint8).reshape(-1, block_bytes)
+    nb = b.shape[0]
+    if nb == 0 or n_frames <= 0:
+        return np.zeros((0, ch), np.int16)
+    if codec == _n.BP_ADPCM_IMA_WAV:
+        hdr = b[:, : 4 * ch].reshape(nb, ch, 4)
+        pred = (hdr[:, :, 0].astype(np.int32) | (hdr[:, :, 1].astype(np.int32) << 8)).astype(np.uint16).view(np.int16).astype(np.int32)
+        index = np.minimum(hdr[:, :, 2].astype(np.int32), 88)
+        codes = b[:, 4 * ch :].reshape(nb, -1, ch, 4).transpose(0, 2, 1, 3).reshape(nb, ch, -1)  # [block][channel][byte]
+        first = [pred.copy()]
+    else:
+        sub = b.reshape(nb, ch, 34)
+        h = (sub[:, :, 0].astype(np.int32) << 8) | sub[:, :, 1].astype(np.int32)
+        pred = (h & 0xFF80).astype(np.uint16).view(np.int16).astype(np.int32)
+        index = np.minimum(h & 0x7F, 88)
+        codes = sub[:, :, 2:]
+        first = []
+    nib = np.stack([codes & 15, codes >> 4], axis=-1).reshape(nb, ch, -1).astype(np.int32)  # low nibble first
+    out = first
+    for k in range(nib.shape[2]):
+        c = nib[:, :, k]
+        s = _IMA_STEP[index]
+        d = (s >> 3) + np.where(c & 4, s, 0) + np.where(c & 2, s >> 1, 0) + np.where(c & 1, s >> 2, 0)
+        pred = np.clip(np.where(c & 8, pred - d, pred + d), -32768, 32767)
+        index = np.clip(index + _IMA_INDEX[c & 7], 0, 88)
+        out.append(pred)
+    x = np.stack(out, axis=1)  # [block][frame][channel]
+    return np.ascontiguousarray(x.reshape(-1, ch)[:n_frames].astype(np.int16))
+
+
+def read_adpcm(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
+    """IMA ADPCM in RIFF/WAVE or CAF -> (float32 samples [n, channels], sample_rate): the decoded int16 / 32768."""
+    got = adpcm_raw(path)
+    if got is None:
+        raise ValueError(f"{path}: not an IMA ADPCM file (RIFF/WAVE format tag 0x11 or CAF ima4)")
+    blocks, codec, ch, sr, block_bytes, _block_frames, n = got
+    return ima_decode(blocks, codec, ch, block_bytes, n).astype(np.float32) * np.float32(1.0 / 32768.0), sr
+
+
 def read_wav(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
-    """Return (float32 samples [n, channels] in [-1, 1), sample_rate) for PCM8/16/24/32 or float WAV."""
-    pcm, tag, bits, ch, sr = wav_raw(path)
+    """Return (float32 samples [n, channels] in [-1, 1), sample_rate) for PCM8/16/24/32, float, G.711 or IMA ADPCM WAV."""
+    chunks = _wav_chunks(path)
+    if chunks[1] == WAV_TAG_IMA:
+        return read_adpcm(path)
+    pcm, tag, bits, ch, sr = _wav_pcm(path, chunks)
     if tag == 1:  # integer PCM; scale factors are powers of two: multiplying by the reciprocal is exact
         if bits == 8:
             x = np.frombuffer(pcm, dtype=np.uint8).astype(np.float32)
@@ -86,6 +267,8 @@ def read_wav(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
     elif tag == 3:  # IEEE float
         w = 4 if bits == 32 else 8
         x = np.frombuffer(pcm[: len(pcm) // w * w], dtype="<f4" if bits == 32 else "<f8").astype(np.float32)
+    elif tag in (6, 7):  # G.711
+        x = g711_expand(np.frombuffer(pcm, dtype=np.uint8), "ulaw" if tag == 7 else "alaw").astype(np.float32) * np.float32(1.0 / 32768.0)
     else:
         raise ValueError(f"{path}: unsupported WAV format tag {tag}")
     n = len(x) // ch
@@ -232,7 +415,8 @@ def pcm_raw(path: Union[str, pathlib.Path]):
     """The samples of a WAV (RF64 / BW64 too), AIFF / AIFF-C, CAF or AU file as the file stores them: (uint8 view of the
     samples, BP_PCM_* code, channels, sample_rate, n_frames) — what `Model.predict_pcm_raw` takes.  `wav_raw` for every
     container the device converts itself; independent of the C++ parsers (csrc/pcm_file.cpp), which the tests hold to it.
-    Not read: the little-endian AU variant, Sony Wave64, ADPCM and the other compressed AIFF-C types."""
+    Not read: the little-endian AU variant, Sony Wave64 and the compressed AIFF-C types; IMA ADPCM files hold blocks, not
+    samples: `adpcm_raw`."""
     with open(path, "rb") as f:
         head = f.read(12)
     if head[:4] in (b"RIFF", b"RF64", b"BW64") and head[8:12] == b"WAVE":
@@ -461,6 +645,8 @@ def read_audio(path: Union[str, pathlib.Path]) -> Tuple[np.ndarray, int]:
         head = f.read(12)
     if head[:4] in (b"RIFF", b"RF64", b"BW64") and head[8:12] == b"WAVE":
         return read_wav(path)
+    if head[:4] == b"caff" and adpcm_raw(path) is not None:
+        return read_adpcm(path)
     if (head[:4] == b"FORM" and head[8:12] in (b"AIFF", b"AIFC")) or head[:4] in (b"caff", b".snd"):
         raw, code, ch, sr, _n_frames = pcm_raw(path)
         return pcm_to_float(raw, code, ch), sr

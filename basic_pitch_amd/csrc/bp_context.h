@@ -5,6 +5,7 @@
 // deleting the handle frees it.
 #pragma once
 #include "../../include/basic_pitch_amd.h"
+#include "../../include/basic_pitch_amd_adpcm.h"
 
 #include <cstdio>
 #include <string>
@@ -70,6 +71,7 @@ struct bp_context {
   Table nd_tables;                     // [88] int4 windows, [51] double Gaussian, then the stats record
   bp::FlacDeviceBuffers fd;            // flac_device.hip: the file's bytes, the frame lists, the scratch rows
   bp::PinnedBuffer<int> fd_status_host;  // the device decoder's error bits of the last call
+  bp::AdpcmDeviceBuffers ad;           // adpcm_device.hip: the files' bytes, their int16 samples, the segment table (grow-only)
   bp::PinnedBuffer<int> nd_stats_host;   // copy of the stats record (4 words; [1]: a NaN was seen)
   void* nd_stats_host_dev = nullptr;  // the same buffer as the device sees it
   bool nd_stats_ready = false;     // the device record holds its initial values (the export kernel leaves it so)
@@ -173,6 +175,10 @@ int64_t h_frames(bp_handle h, int64_t n);
 // the only way to h->track_out, grown for `rows` rows of maps (h->maps_rows = 0); the same with a private copy of given maps
 int take_track_out(bp_handle h, int64_t rows, Maps* m);
 int take_given_maps(bp_handle h, const float* note, const float* onset, const float* contour, int64_t T, int mem_kind, Maps* m);
+// IMA ADPCM (adpcm_device.hip): the blocks of n files (lay[i] of files[i]; all of lay[0]'s codec) to the device and one decode
+// launch for all; file i's interleaved int16 samples at h->ad.pcm + pcm_off[i].  segs stays alive until the wait.
+int queue_adpcm(bp_handle h, int64_t n, const void* const* files, const bp_adpcm_layout* lay, std::vector<AdpcmSeg>& segs,
+                int64_t* pcm_off);
 // the PCM format the device FLAC decoders write (left-justified), and n such samples as int32 (src may be out)
 int flac_format(const bp_flac_stream_layout& lay);
 void flac_pcm_to_int32(const void* src, bool wide, int shift, int64_t n, int32_t* out);

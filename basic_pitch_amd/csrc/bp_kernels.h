@@ -151,6 +151,26 @@ struct FlacDeviceBuffers {
 int flac_device_decode(FlacDeviceBuffers& b, const FdStream& st, void* d_pcm, hipStream_t stream);
 int flac_device_crc_table(FlacDeviceBuffers& b);  // b.crc_tab, made on first use; 0 or -1
 
+// adpcm_device.hip: IMA ADPCM blocks -> interleaved int16.  One segment = the blocks of one file (a job of clips: n segments in
+// one launch; a single file: one).  Offsets count from the start of the buffers the launch is given.
+struct AdpcmSeg {
+  int64_t byte_off;     // the segment's first block in the bytes buffer
+  int64_t data_bytes;   // bytes of blocks that may be read from there
+  int64_t out_off;      // its first sample (int16) in the output buffer
+  int64_t frame_cap;    // frames of it that may be written: [0, frame_cap)
+  int64_t first_chain;  // chains (one channel of one block) of the segments before it
+  int32_t n_blocks, block_bytes, block_frames, channels;
+};
+struct AdpcmDeviceBuffers {
+  DeviceBuffer<uint8_t> file;   // the bytes of the call's files, one after the other
+  DeviceBuffer<int16_t> pcm;    // the decoded samples
+  DeviceBuffer<AdpcmSeg> segs;  // the launch's segment table
+};
+// codec: BP_ADPCM_IMA_WAV | BP_ADPCM_IMA4.  segs: n_segs records in device memory, first_chain ascending; n_chains: of all.
+// Every read lies inside [byte_off, byte_off + data_bytes) of its segment, every write inside its frame_cap.
+void launch_adpcm_decode(int codec, const uint8_t* bytes, const AdpcmSeg* segs, int n_segs, int64_t n_chains, int16_t* pcm,
+                         hipStream_t stream);
+
 constexpr int kFdChunkBytes = 65536;  // bytes of a stream a scan workgroup owns (flac_kernels.h kFdChunk)
 // flac_clips.hip: one stream of a job of many (bp_infer_flac_clips_candidates).  The job's bytes lie in FlacDeviceBuffers::file,
 // clip by clip; st.audio_start and st.nbytes count from the clip's first byte.  The table is sorted by first_wg and first_slot.

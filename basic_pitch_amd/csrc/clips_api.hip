@@ -1,5 +1,5 @@
 // C ABI of the jobs of many clips (include/basic_pitch_amd_clips.h, _events.h, _flac_clips.h): many short clips through the
-// model in one call — raw PCM, FLAC files' bytes decoded on the device, or maps the caller already holds — and home either
+// model in one call — raw PCM, FLAC or IMA ADPCM files' bytes decoded on the device, or maps the caller already holds — and home either
 // the note candidates of every clip or, the tracker run on the device too, the note events alone.
 //
 // Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
@@ -13,6 +13,7 @@
 #include <algorithm>
 #include <cstring>
 
+#include "../../include/basic_pitch_amd_adpcm.h"
 #include "../../include/basic_pitch_amd_flac_clips.h"
 #include "bp_context.h"
 
@@ -416,11 +417,59 @@ void drop_failed_clips(bp_handle h, const FlacJob& job, const EventsSink& out) {
   }
 }
 
+// ---- a job of IMA ADPCM clips decoded on the device (include/basic_pitch_amd_adpcm.h; adpcm_device.hip) --------------------------
+// What the host knows of a job before anything is queued: every clip's layout (all of one codec, rate and channel count), and
+// what queue_adpcm's asynchronous copies read.
+struct AdpcmJob {
+  std::vector<bp_adpcm_layout> lay;
+  std::vector<const void*> files;
+  std::vector<AdpcmSeg> segs;
+  std::vector<int64_t> pcm_off;
+};
+
+// every clip's headers and ingest arguments; *sample_rate: the clips' (no clips: the handle's); n_model / offs as check_clips
+int plan_adpcm_clips(bp_handle h, const char* what, int64_t n, const bp_adpcm_clip* clips, AdpcmJob* job, int* sample_rate,
+                     std::vector<int64_t>* n_model, std::vector<int64_t>* offs) {
+  if (n < 0 || (n > 0 && !clips)) return invalid(h, what, "negative n_clips or null clips");
+  job->lay.assign((size_t)n, bp_adpcm_layout{});
+  job->files.assign((size_t)n, nullptr);
+  job->pcm_off.assign((size_t)n, 0);
+  n_model->assign((size_t)n, 0);
+  offs->assign((size_t)n + 1, 0);
+  *sample_rate = h->rate;
+  for (int64_t i = 0; i < n; ++i) {
+    const std::string clip = "clip " + std::to_string(i) + ": ";
+    bp_adpcm_layout& l = job->lay[(size_t)i];
+    if (!clips[i].file) return invalid(h, what, clip + "null file");
+    if (bp_adpcm_layout_of(clips[i].file, clips[i].nbytes, &l) != BP_OK) {
+      h->err = std::string(what) + ": " + clip + bp_files_last_error();
+      return BP_ERR_BAD_AUDIO;
+    }
+    const bp_adpcm_layout& first = job->lay[0];
+    if (l.codec != first.codec || l.sample_rate != first.sample_rate || l.channels != first.channels)
+      return invalid(h, what, clip + "codec " + std::to_string(l.codec) + ", " + std::to_string(l.sample_rate) + " Hz, " +
+                                  std::to_string(l.channels) + " channels; clip 0 has codec " + std::to_string(first.codec) + ", " +
+                                  std::to_string(first.sample_rate) + " Hz, " + std::to_string(first.channels) +
+                                  " channels (one codec, rate and channel count per call)");
+    if (int rc = check_ingest(h, true, BP_PCM_S16, l.n_frames, l.channels, l.sample_rate, BP_MEM_DEVICE)) {
+      h->err = std::string(what) + ": " + clip + h->err;
+      return rc;
+    }
+    *sample_rate = l.sample_rate;
+    job->files[(size_t)i] = clips[i].file;
+    (*n_model)[(size_t)i] = resampled_length(l.n_frames, l.sample_rate, h->rate);
+    (*offs)[(size_t)i + 1] = (*offs)[(size_t)i] + h_frames(h, (*n_model)[(size_t)i]);
+  }
+  return BP_OK;
+}
+
 // ---- the driver ------------------------------------------------------------------------------------------------------------
 // Where the maps of the n segments come from.  kPcmClips: `clips` (PCM in host or device memory after mem_kind) at sample_rate;
 // kFlacClips: `flac` (bytes in host memory, STREAMINFO rate sample_rate), decoded on the device, then as kPcmClips in device
-// memory; kGivenMaps: no signal but maps already made (mem_kind), segment c at rows [row_offsets[c], row_offsets[c + 1]).
-enum JobSourceKind { kPcmClips, kFlacClips, kGivenMaps };
+// memory; kAdpcmClips: `adpcm` (IMA ADPCM files' bytes in host memory; the rate is the files'), decoded on the device by one
+// launch, then as kPcmClips in device memory; kGivenMaps: no signal but maps already made (mem_kind), segment c at rows
+// [row_offsets[c], row_offsets[c + 1]).
+enum JobSourceKind { kPcmClips, kFlacClips, kGivenMaps, kAdpcmClips };
 struct JobSource {
   JobSourceKind kind;
   int64_t n;
@@ -429,6 +478,7 @@ struct JobSource {
   const bp_flac_clip* flac;
   const int64_t* row_offsets;
   const float *note, *onset, *contour;
+  const bp_adpcm_clip* adpcm;
 };
 
 // Where the results go.  kCandidatesHome: the note candidates of all rows (host buffers) and out.status, the maps stay in
@@ -461,7 +511,8 @@ JobSink events_sink(const bp_note_params* params, bp_note_event* events, int64_t
 struct ClipsJob {
   FlacJob flac;                                // n_model and offs of the clips (kPcmClips too); the rest: kFlacClips
   const int64_t* offs = nullptr;               // rows before each segment (kGivenMaps: the caller's)
-  std::vector<bp_clip> decoded;                // kFlacClips: the clips' PCM on the device
+  std::vector<bp_clip> decoded;                // kFlacClips, kAdpcmClips: the clips' PCM on the device
+  AdpcmJob adpcm;                              // kAdpcmClips
   std::vector<ClipDesc> tab;
   std::vector<NoteTrackSeg> seg;
   bool dense_bends = false;                    // kEventsHome: the dense half makes the bend map
@@ -488,9 +539,16 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
         if (f.dev[i] >= 0)
           job.decoded[i] = bp_clip{h->pcm_dev + f.tab[(size_t)f.dev[i]].pcm_off, f.lay[i].n_frames, flac_format(f.lay[i]), f.lay[i].channels};
       clips = job.decoded.data();
+    } else if (s.kind == kAdpcmClips) {
+      AdpcmJob& a = job.adpcm;
+      if ((rc = queue_adpcm(h, s.n, a.files.data(), a.lay.data(), a.segs, a.pcm_off.data()))) return rc;
+      job.decoded.assign((size_t)s.n, bp_clip{nullptr, 0, BP_PCM_S16, 1});
+      for (size_t i = 0; i < a.lay.size(); ++i)
+        if (a.lay[i].n_frames > 0) job.decoded[i] = bp_clip{h->ad.pcm + a.pcm_off[i], a.lay[i].n_frames, BP_PCM_S16, a.lay[i].channels};
+      clips = job.decoded.data();
     }
     job.tab.resize((size_t)s.n);
-    rc = queue_clips_maps(h, s.n, clips, s.sample_rate, s.kind == kFlacClips ? BP_MEM_DEVICE : s.mem_kind, job.flac.n_model.data(),
+    rc = queue_clips_maps(h, s.n, clips, s.sample_rate, s.kind != kPcmClips ? BP_MEM_DEVICE : s.mem_kind, job.flac.n_model.data(),
                           job.offs, job.tab, &all);
   }
   if (rc) return rc;
@@ -503,7 +561,7 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   return events_queue(h, job.ev, job.plan, TrackInputs{all.note, d_bits, d_bend, h->clip_rows, h->clip_stats});
 }
 
-int run_clips(bp_handle h, const char* what, const JobSource& src, const JobSink& k) {
+int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   if (!h) return BP_ERR_INVALID_ARG;
   auto invalid = [&](const char* why) { return ::invalid(h, what, why); };
   const int64_t n = src.n;
@@ -528,6 +586,8 @@ int run_clips(bp_handle h, const char* what, const JobSource& src, const JobSink
   } else {
     if (flac) {
       rc = plan_flac_clips(h, what, n, src.flac, src.sample_rate, &job.flac);
+    } else if (src.kind == kAdpcmClips) {  // (the rate is the files' own)
+      rc = plan_adpcm_clips(h, what, n, src.adpcm, &job.adpcm, &src.sample_rate, &job.flac.n_model, &job.flac.offs);
     } else {
       job.flac.n_model.resize((size_t)std::max<int64_t>(n, 0)), job.flac.offs.resize(job.flac.n_model.size() + 1);
       rc = check_clips(h, what, n, src.clips, src.sample_rate, src.mem_kind, true, job.flac.n_model.data(), job.flac.offs.data());
@@ -697,5 +757,13 @@ int bp_infer_flac_clips_events(bp_handle h, int64_t n_clips, const bp_flac_clip*
                    events_sink(params, events, max_events, bends, max_bends, event_offsets, status));
 }
 
-}  // extern "C"
+// ---- a job of IMA ADPCM clips (include/basic_pitch_amd_adpcm.h) -------------------------------------------------------------------
+int bp_infer_adpcm_clips_events(bp_handle h, int64_t n_clips, const bp_adpcm_clip* clips, const bp_note_params* params,
+                                bp_note_event* events, int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets,
+                                int* status) {
+  JobSource src{kAdpcmClips, n_clips, BP_MEM_HOST, 0};
+  src.adpcm = clips;
+  return run_clips(h, "bp_infer_adpcm_clips_events", src, events_sink(params, events, max_events, bends, max_bends, event_offsets, status));
+}
 
+}  // extern "C"

@@ -7,7 +7,8 @@
 // its outputs; the GPU is a shared resource the workers queue for (one lane per handle), everything else runs in parallel.
 //
 // This file is the job alone: what it does on the host without a device lies in wav_file.cpp (RIFF/WAVE, RF64), pcm_file.cpp
-// (AIFF, CAF, AU), note_writers.cpp (.csv / .mid bytes) and file_io.cpp (reading and writing files), declared in file_host.h.
+// (AIFF, CAF, AU), adpcm_file.cpp (IMA ADPCM in WAV and CAF), note_writers.cpp (.csv / .mid bytes) and file_io.cpp (reading and
+// writing files), declared in file_host.h.
 #include <algorithm>
 #include <atomic>
 #include <chrono>
@@ -23,7 +24,9 @@
 #include <sys/stat.h>
 #include <unistd.h>
 
+#include "../../include/basic_pitch_amd_adpcm.h"
 #include "../../include/basic_pitch_amd_flac_clips.h"
+#include "adpcm_host.h"
 #include "file_host.h"
 
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);  // flac_decode.cpp
@@ -111,6 +114,41 @@ Container sniff(const uint8_t* head, size_t size) {
   return Container::Neither;
 }
 
+// What a Wav or Pcm file holds, from its headers: samples the device converts as they are stored (format: their BP_PCM_*), or
+// IMA ADPCM blocks (adpcm: BP_ADPCM_*, `ad` filled; RIFF/WAVE tag 0x11, CAF ima4), which the device expands itself
+// (adpcm_device.hip).  The one walk behind clip_route and the per-file route.  False: g_file_error says why.
+struct Samples {
+  int channels = 0, sample_rate = 0, format = BP_PCM_F32, adpcm = 0;
+  int64_t n_frames = 0;
+  size_t data_pos = 0;
+  bp_adpcm_layout ad{};
+};
+
+bool walk_samples(const ByteSource& src, Container kind, Samples& s) {
+  s = Samples{};
+  if (kind == Container::Wav) {
+    WavInfo w;
+    if (!wav_walk(src, w, s.data_pos)) return false;
+    s.channels = w.channels, s.sample_rate = w.sample_rate, s.n_frames = w.n_frames, s.format = wav_pcm_format(w);
+    if (w.tag != kWavTagIma) return true;
+  } else {
+    bp_pcm_file_layout lay;
+    if (pcm_file_walk(src, lay)) {
+      s.channels = lay.channels, s.sample_rate = lay.sample_rate, s.n_frames = lay.n_frames, s.format = lay.format;
+      s.data_pos = (size_t)lay.data_start;
+      return true;
+    }
+  }
+  // blocks, not samples: the headers once more as adpcm_file.cpp reads them (a file that is no such file keeps its message)
+  const std::string why = g_file_error;
+  const int codec = adpcm_walk(src, s.ad);
+  if (codec == 0) g_file_error = why;
+  if (codec <= 0) return false;
+  s.channels = s.ad.channels, s.sample_rate = s.ad.sample_rate, s.n_frames = s.ad.n_frames, s.format = BP_PCM_S16;
+  s.data_pos = (size_t)s.ad.data_start, s.adpcm = codec;
+  return true;
+}
+
 // FLAC: the file's BYTES go to the device and are decoded there (flac_device.hip) — no core-time per sample here, half
 // the PCIe bytes of the PCM — unless the stream is one the device decoder leaves to the host (flac_decode.cpp
 // bp_internal_flac_device_supported) or params.host_flac asks for the host decoder.  `bytes`: the file, or a prefix of it
@@ -144,8 +182,11 @@ std::atomic<int64_t> g_batched{0};  // files whose outputs came from a batched c
 struct ClipFile {
   int route = 0;  // 0: the per-file route; 1: a batched PCM call; 2: a batched FLAC call; negative: a bp_status
   int channels = 0, sample_rate = 0, format = BP_PCM_F32;
+  int adpcm = 0;  // route 1: BP_ADPCM_* of a file of IMA ADPCM blocks, which takes the batched ADPCM call; else 0
   int64_t n_frames = 0, windows = 0;
   size_t data_pos = 0;  // WAV, AIFF, CAF, AU: where the samples lie in the file
+  // the calls of a part, one per key: the route, for IMA ADPCM with the codec and the channel count (one of each per call)
+  int group() const { return adpcm ? 0x100 | adpcm | (channels << 16) : route; }
 };
 
 // the windows of n_frames frames at sample_rate at the lanes' geometry (no handle: that of the default mode)
@@ -168,22 +209,16 @@ int clip_route(const ByteSource& src, bp_handle h, const bp_transcribe_params& p
   uint8_t magic[12] = {0};
   if (src.size && !src.at(0, src.size < 12 ? src.size : 12, magic)) return c.route = BP_ERR_BAD_AUDIO;
   auto in_domain = [&]() { return c.channels >= 1 && c.channels <= 64 && c.sample_rate >= 1000 && c.sample_rate <= 768000; };
-  switch (sniff(magic, src.size)) {
-    case Container::Wav: {
-      WavInfo w;
-      if (!wav_walk(src, w, c.data_pos)) return c.route = BP_ERR_BAD_AUDIO;
-      c.channels = w.channels, c.sample_rate = w.sample_rate, c.n_frames = w.n_frames, c.format = wav_pcm_format(w);
+  const Container kind = sniff(magic, src.size);
+  switch (kind) {
+    case Container::Wav:
+    case Container::Pcm: {  // samples, or IMA ADPCM blocks: short files of either are batched
+      Samples sm;
+      if (!walk_samples(src, kind, sm)) return c.route = BP_ERR_BAD_AUDIO;
+      c.channels = sm.channels, c.sample_rate = sm.sample_rate, c.n_frames = sm.n_frames, c.format = sm.format;
+      c.data_pos = sm.data_pos, c.adpcm = sm.adpcm;
       if (host_decodes(prm) || !in_domain() || src.size > kClipBatchBytes) return c.route = 0;
       c.windows = clip_windows(h, c.n_frames, c.sample_rate);  // a file without frames: a clip without rows
-      return c.route = c.windows <= BP_FILES_CLIP_MAX_WINDOWS ? 1 : 0;
-    }
-    case Container::Pcm: {  // what the Wav case does, from the other headers
-      bp_pcm_file_layout lay;
-      if (!pcm_file_walk(src, lay)) return c.route = BP_ERR_BAD_AUDIO;
-      c.channels = lay.channels, c.sample_rate = lay.sample_rate, c.n_frames = lay.n_frames, c.format = lay.format;
-      c.data_pos = (size_t)lay.data_start;
-      if (host_decodes(prm) || !in_domain() || src.size > kClipBatchBytes) return c.route = 0;
-      c.windows = clip_windows(h, c.n_frames, c.sample_rate);
       return c.route = c.windows <= BP_FILES_CLIP_MAX_WINDOWS ? 1 : 0;
     }
     case Container::Flac: {
@@ -355,6 +390,7 @@ class Worker {
     const uint8_t* bytes = nullptr;  // the file
     size_t n_bytes = 0;
     bool flac_on_device = false;  // the device decodes `bytes`; else it gets `pcm`
+    bool adpcm_on_device = false;  // IMA ADPCM: the device expands `bytes`
     const void* pcm = nullptr;
     int channels = 0, sample_rate = 0, format = BP_PCM_F32;
     int64_t n_frames = 0;
@@ -384,7 +420,7 @@ class Worker {
     int rc = BP_OK;
     float ms_device = 0.0f;
   };
-  using Groups = std::map<std::pair<int, int>, Group>;  // by (route, sample rate)
+  using Groups = std::map<std::pair<int, int>, Group>;  // by (ClipFile::group(), sample rate)
 
   // the per-file route: one file from its bytes to its outputs
   void one_file(int64_t i);
@@ -397,12 +433,12 @@ class Worker {
   void claim(int64_t i);
   void flush();
   void read_part(Groups& groups);
-  void infer_group(bp_handle h, bool flac, int sample_rate, Group& g);
+  void infer_group(bp_handle h, int key, int sample_rate, Group& g);
   void write_group(const Group& g, float ms_read, float ms_wait, Lap& lap);
 
   Job& job;
   const bp_transcribe_params& prm;
-  Pinned file, decoded, maps;  // the file's bytes; float PCM of a FLAC file; the three posteriorgrams
+  Pinned file, decoded, maps;  // the file's bytes; PCM of a file decoded on the host; the three posteriorgrams
   std::vector<bp_note_event> events;
   std::vector<int32_t> bends;
   std::vector<uint8_t> midi;
@@ -441,27 +477,34 @@ bool Worker::read_audio(const std::string& path, bp_file_report* rep, Audio& a) 
     return false;
   }
   a.bytes = static_cast<const uint8_t*>(file.p);
-  switch (sniff(a.bytes, a.n_bytes)) {
-    case Container::Wav: {
-      WavInfo w;
-      if (!wav_parse(a.bytes, a.n_bytes, w)) {
-        set_report(rep, BP_ERR_BAD_AUDIO, path + ": " + g_file_error);
-        return false;
-      }
-      // the samples go to the device as the file stores them (bp_infer_pcm_raw converts there)
-      a.channels = w.channels, a.sample_rate = w.sample_rate, a.n_frames = w.n_frames, a.pcm = w.pcm, a.format = wav_pcm_format(w);
-      return true;
-    }
+  const Container kind = sniff(a.bytes, a.n_bytes);
+  switch (kind) {
+    case Container::Wav:
     case Container::Pcm: {
       ByteSource src;
       src.mem = a.bytes, src.size = a.n_bytes;
-      bp_pcm_file_layout lay;
-      if (!pcm_file_walk(src, lay)) {
+      Samples sm;
+      if (!walk_samples(src, kind, sm)) {
         set_report(rep, BP_ERR_BAD_AUDIO, path + ": " + g_file_error);
         return false;
       }
-      a.channels = lay.channels, a.sample_rate = lay.sample_rate, a.n_frames = lay.n_frames, a.pcm = a.bytes + lay.data_start;
-      a.format = lay.format;
+      // the samples go to the device as the file stores them (bp_infer_pcm_raw converts there); IMA ADPCM blocks too
+      // (bp_infer_adpcm expands them there), unless the job decodes on the host: then their int16 samples go
+      a.channels = sm.channels, a.sample_rate = sm.sample_rate, a.n_frames = sm.n_frames, a.pcm = a.bytes + sm.data_pos;
+      a.format = sm.format;
+      if (!sm.adpcm) return true;
+      if (!prm.host_decode) {
+        a.adpcm_on_device = true;
+        return true;
+      }
+      if (!decoded.ensure((size_t)(a.n_frames * a.channels) * sizeof(int16_t) + 4)) {
+        set_report(rep, BP_ERR_OUT_OF_MEMORY, path + ": " + g_file_error);
+        return false;
+      }
+      int16_t* pcm = static_cast<int16_t*>(decoded.p);
+      if (sm.adpcm == BP_ADPCM_IMA_WAV) ima_wav_decode(a.bytes + sm.data_pos, (size_t)sm.ad.data_bytes, a.channels, sm.ad.block_bytes, a.n_frames, pcm);
+      else ima4_decode(a.bytes + sm.data_pos, (size_t)sm.ad.data_bytes, a.channels, a.n_frames, pcm);
+      a.pcm = pcm;
       return true;
     }
     case Container::Flac: {
@@ -491,17 +534,19 @@ bool Worker::infer(const std::string& path, bp_file_report* rep, Audio& a, const
     if (T > 0) {
       if (use_cand) {
         int status = 0;
-        rc = a.flac_on_device ? bp_infer_flac_candidates(h, a.bytes, a.n_bytes, &prm.notes, m.note, m.cand_bits, bend_map, &status)
-                              : bp_infer_pcm_raw_candidates(h, a.pcm, a.format, a.n_frames, a.channels, a.sample_rate, &prm.notes,
-                                                            m.note, m.cand_bits, bend_map, &status);
+        rc = a.flac_on_device    ? bp_infer_flac_candidates(h, a.bytes, a.n_bytes, &prm.notes, m.note, m.cand_bits, bend_map, &status)
+             : a.adpcm_on_device ? bp_infer_adpcm_candidates(h, a.bytes, a.n_bytes, &prm.notes, m.note, m.cand_bits, bend_map, &status)
+                                 : bp_infer_pcm_raw_candidates(h, a.pcm, a.format, a.n_frames, a.channels, a.sample_rate, &prm.notes,
+                                                               m.note, m.cand_bits, bend_map, &status);
         if (rc == BP_OK && status != 0) {  // a NaN in the maps: numpy's rules need the maps themselves — they are
           use_cand = false;                // still on the device, the lane is still ours
           rc = bp_track_maps(h, T, m.note, m.onset, m.contour, BP_MEM_HOST);
         }
       } else {
-        rc = a.flac_on_device ? bp_infer_flac(h, a.bytes, a.n_bytes, m.note, m.onset, m.contour, BP_MEM_HOST)
-                              : bp_infer_pcm_raw(h, a.pcm, a.format, a.n_frames, a.channels, a.sample_rate, m.note, m.onset, m.contour,
-                                                 BP_MEM_HOST);
+        rc = a.flac_on_device    ? bp_infer_flac(h, a.bytes, a.n_bytes, m.note, m.onset, m.contour, BP_MEM_HOST)
+             : a.adpcm_on_device ? bp_infer_adpcm(h, a.bytes, a.n_bytes, m.note, m.onset, m.contour, BP_MEM_HOST)
+                                 : bp_infer_pcm_raw(h, a.pcm, a.format, a.n_frames, a.channels, a.sample_rate, m.note, m.onset, m.contour,
+                                                    BP_MEM_HOST);
       }
       if (rc != BP_OK) err = bp_last_error(h);
     }
@@ -603,21 +648,24 @@ void Worker::read_part(Groups& groups) {
     const int route = m.c.route;
     if (!ok || clip_route(src, job.handles[0], prm, m.c) != route) continue;  // the bytes read decide, as the headers did
     m.rows = job.rows_of(m.c.n_frames, m.c.sample_rate);
-    groups[{route, m.c.sample_rate}].members.push_back(k);
+    groups[{m.c.group(), m.c.sample_rate}].members.push_back(k);
   }
 }
 
 // one clips-events call over a group's files, once more if it asks for more room
-void Worker::infer_group(bp_handle h, bool flac, int sample_rate, Group& g) {
+void Worker::infer_group(bp_handle h, int key, int sample_rate, Group& g) {
+  const bool flac = key == 2, adpcm = (key & 0x100) != 0;
   const uint8_t* base = static_cast<const uint8_t*>(batch.p);
   const int64_t n = (int64_t)g.members.size();
   std::vector<bp_clip> pcm_clips;
   std::vector<bp_flac_clip> flac_clips;
+  std::vector<bp_adpcm_clip> adpcm_clips;
   int64_t rows = 0;
   for (size_t k : g.members) {
     const Member& m = part[k];
     rows += m.rows;
     if (flac) flac_clips.push_back(bp_flac_clip{base + m.offset, m.n_bytes});
+    else if (adpcm) adpcm_clips.push_back(bp_adpcm_clip{base + m.offset, m.n_bytes});
     else pcm_clips.push_back(bp_clip{base + m.offset + m.c.data_pos, m.c.n_frames, m.c.format, m.c.channels});
   }
   g.offsets.assign((size_t)n + 1, 0), g.status.assign((size_t)n, 0);
@@ -626,6 +674,8 @@ void Worker::infer_group(bp_handle h, bool flac, int sample_rate, Group& g) {
     g.events.resize((size_t)cap_ev), g.bends.resize((size_t)cap_b);
     g.rc = flac ? bp_infer_flac_clips_events(h, n, flac_clips.data(), sample_rate, &prm.notes, g.events.data(), cap_ev, g.bends.data(),
                                              cap_b, g.offsets.data(), g.status.data())
+           : adpcm ? bp_infer_adpcm_clips_events(h, n, adpcm_clips.data(), &prm.notes, g.events.data(), cap_ev, g.bends.data(), cap_b,
+                                                 g.offsets.data(), g.status.data())
                 : bp_infer_clips_events(h, n, pcm_clips.data(), sample_rate, BP_MEM_HOST, &prm.notes, g.events.data(), cap_ev,
                                         g.bends.data(), cap_b, g.offsets.data(), g.status.data());
     if (g.rc != BP_ERR_INVALID_ARG || !grow_to_needed(bp_last_error(h), cap_ev, cap_b)) break;
@@ -678,7 +728,7 @@ void Worker::flush() {
     Lane lane(job);
     ms_wait = lap() / (float)n_grouped;
     for (auto& kv : groups) {
-      infer_group(lane.handle(), kv.first.first == 2, kv.first.second, kv.second);
+      infer_group(lane.handle(), kv.first.first, kv.first.second, kv.second);
       kv.second.ms_device = lap() / (float)kv.second.members.size();
     }
   }  // the lane goes back before anything is written

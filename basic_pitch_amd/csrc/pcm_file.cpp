@@ -2,7 +2,8 @@
 // names what is read of each).  Like wav_walk, a parser reads the headers from an open file and says what the samples are
 // and where they lie; the samples themselves go to the device as the file stores them (audio_ingest.hip pcm_sample<FMT>).
 // pcm_to_float is that conversion on the host, the checker behind bp_pcm_file_decode.  RF64 / BW64 is wav_walk's.
-// Nothing here calls the device library.  Not read: the little-endian AU variant (`dns.`), Sony Wave64, ADPCM of any kind.
+// Nothing here calls the device library.  Not read: the little-endian AU variant (`dns.`), Sony Wave64, MS ADPCM; IMA ADPCM
+// (WAV tag 0x11, CAF ima4) is adpcm_file.cpp's.
 //   AIFF:   Audio Interchange File Format 1.3 (Apple, 1989); AIFF-C draft 08/26/91; `sowt`, `fl32`, `in24`: Apple TN 2053
 //   CAF:    Apple Core Audio Format Specification 1.0
 //   AU:     the Sun / NeXT audio file header (audio_filehdr)
@@ -60,19 +61,6 @@ int int_format(int bytes, bool little) {
 void take_frames(uint64_t header_frames, uint64_t data_bytes, bp_pcm_file_layout& lay) {
   const uint64_t held = data_bytes / ((uint64_t)width_of(lay.format) * (uint64_t)lay.channels);
   lay.n_frames = (int64_t)(held < header_frames ? held : header_frames);
-}
-
-int ulaw_expand(uint32_t b) {
-  const uint32_t u = ~b & 0xffu;
-  const int t = (int)((((u & 15u) << 3) + 0x84u) << ((u >> 4) & 7u));
-  return (u & 0x80u) ? 0x84 - t : t - 0x84;
-}
-
-int alaw_expand(uint32_t b) {
-  const uint32_t a = (b ^ 0x55u) & 0xffu, s = (a >> 4) & 7u;
-  int t = (int)((a & 15u) << 4);
-  t = s == 0 ? t + 8 : s == 1 ? t + 0x108 : (t + 0x108) << (s - 1);
-  return (a & 0x80u) ? t : -t;
 }
 
 }  // namespace
@@ -257,6 +245,7 @@ bool pcm_file_walk(const ByteSource& src, bp_pcm_file_layout& lay) {
       WavInfo w;
       size_t data_pos = 0;
       if (!wav_walk(src, w, data_pos)) return false;
+      if (w.tag == kWavTagIma) return fail("IMA ADPCM samples are blocks, not PCM of a bp_pcm_format (bp_adpcm_layout_of reads the file)");
       lay = bp_pcm_file_layout{};
       lay.container = BP_CONTAINER_WAV, lay.format = wav_pcm_format(w), lay.channels = w.channels, lay.sample_rate = w.sample_rate;
       lay.bits_per_sample = w.bits, lay.n_frames = w.n_frames, lay.data_start = (int64_t)data_pos;

@@ -1,6 +1,6 @@
 // C ABI of the track family (include/basic_pitch_amd.h): whole signals -> un-overlapped posteriorgrams on the device — from
-// host or device samples, raw PCM (downmix + resampling), or a FLAC file's bytes decoded on the device — and the device-side
-// note candidates of those maps.
+// host or device samples, raw PCM (downmix + resampling), or a FLAC or IMA ADPCM file's bytes decoded on the device — and the
+// device-side note candidates of those maps.
 //
 // Every entry point is a source, the track and a sink on one driver (run_track):
 //   validate everything -> queue the source -> tracks_core -> queue the sink -> wait -> the FLAC decoder's verdict.
@@ -11,6 +11,7 @@
 // needs before it queues work on them, and nothing here frees by hand.
 #include <algorithm>
 
+#include "../../include/basic_pitch_amd_adpcm.h"
 #include "bp_context.h"
 
 using namespace bp;
@@ -333,6 +334,55 @@ int flac_device_verdict(bp_handle h) {
   return BP_ERR_BAD_AUDIO;
 }
 
+// ---- IMA ADPCM decoded on the device (adpcm_device.hip) ------------------------------------------------------------------------
+int check_adpcm(bp_handle h, const void* file, size_t nbytes, bp_adpcm_layout* lay) {
+  if (!file) {
+    h->err = "IMA ADPCM on the device: null file";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (bp_adpcm_layout_of(file, nbytes, lay) != BP_OK) {
+    h->err = std::string("IMA ADPCM on the device: ") + bp_files_last_error();
+    return BP_ERR_BAD_AUDIO;
+  }
+  return BP_OK;
+}
+
+}  // namespace
+
+// What the track calls and the clip jobs share (bp_context.h): the blocks of n files at files[i] + lay[i].data_start to the
+// device, one after the other, and ONE launch that expands them all; file i's samples (BP_PCM_S16, interleaved) lie at
+// h->ad.pcm + pcm_off[i].  All files have lay[0]'s codec.  segs: the caller's, alive until the stream has been waited for.
+int bp::queue_adpcm(bp_handle h, int64_t n, const void* const* files, const bp_adpcm_layout* lay, std::vector<AdpcmSeg>& segs,
+                    int64_t* pcm_off) {
+  hipStream_t s = h->stream;
+  segs.clear();
+  int64_t bytes = 0, samples = 0, chains = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const bp_adpcm_layout& l = lay[i];
+    const int64_t blocks = (l.n_frames + l.block_frames - 1) / l.block_frames;  // (those that hold a frame to write)
+    samples = (samples + 7) / 8 * 8;  // every file's samples from a 16-byte boundary
+    pcm_off[i] = samples;
+    if (blocks > 0) segs.push_back(AdpcmSeg{bytes, blocks * l.block_bytes, samples, l.n_frames, chains, (int32_t)blocks, l.block_bytes, l.block_frames, l.channels});
+    bytes += blocks * l.block_bytes, samples += l.n_frames * l.channels, chains += blocks * l.channels;
+  }
+  if (segs.empty()) return BP_OK;
+  if ((size_t)bytes > h->ad.file.capacity()) BP_HIP(h->ad.file.reserve((size_t)(bytes + bytes / 4 + 4096)));
+  if ((size_t)samples > h->ad.pcm.capacity()) BP_HIP(h->ad.pcm.reserve((size_t)(samples + samples / 4 + 4096)));
+  if (segs.size() > h->ad.segs.capacity()) BP_HIP(h->ad.segs.reserve(segs.size() + segs.size() / 4 + 16));
+  for (int64_t i = 0, k = 0; i < n; ++i) {
+    if (lay[i].n_frames <= 0) continue;
+    const AdpcmSeg& sg = segs[(size_t)k++];
+    BP_HIP(hipMemcpyAsync(h->ad.file + sg.byte_off, static_cast<const uint8_t*>(files[i]) + lay[i].data_start, (size_t)sg.data_bytes,
+                          hipMemcpyHostToDevice, s));
+  }
+  BP_HIP(hipMemcpyAsync(h->ad.segs, segs.data(), segs.size() * sizeof(AdpcmSeg), hipMemcpyHostToDevice, s));
+  launch_adpcm_decode(lay[0].codec, h->ad.file, h->ad.segs, (int)segs.size(), chains, h->ad.pcm, s);
+  BP_HIP(hipGetLastError());
+  return BP_OK;
+}
+
+namespace {
+
 // ---- device-side note candidates (note_device.hip): what note decoding needs of a track's maps
 // m: device maps of T > 0 frames (note / onset are modified when the parameters set a frequency range, like
 // constrain_frequency does).  Outputs: host buffers, complete once the stream has been waited for.
@@ -361,8 +411,9 @@ int queue_candidates(bp_handle h, const Maps& m, int64_t T, const bp_note_params
 // ---- the driver ------------------------------------------------------------------------------------------------------------
 // Where the 22.05 kHz signal comes from.  kSamples: `count` samples; kPcm: `count` frames of PCM (downmix + resampling);
 // kFlac: a FLAC file of `count` bytes in host memory, decoded on the device, then as kPcm; kFlacPcm: the same decode, the PCM
-// left in h->pcm_dev (bp_flac_decode_device); kMaps: no signal but `count` rows of maps already made (data: the note map).
-enum SourceKind { kSamples, kPcm, kFlac, kFlacPcm, kMaps };
+// left in h->pcm_dev (bp_flac_decode_device); kAdpcm / kAdpcmPcm: the same for an IMA ADPCM file, the PCM in h->ad.pcm;
+// kMaps: no signal but `count` rows of maps already made (data: the note map).
+enum SourceKind { kSamples, kPcm, kFlac, kFlacPcm, kAdpcm, kAdpcmPcm, kMaps };
 struct Source {
   SourceKind kind;
   const void* data;
@@ -372,6 +423,8 @@ struct Source {
   const float *onset, *contour;       // kMaps
   int64_t n;                          // set by check_args: the signal's length (kMaps: rows)
   bp_flac_stream_layout lay;          // set by check_args: kFlac / kFlacPcm
+  bp_adpcm_layout ad;                 // set by check_args: kAdpcm / kAdpcmPcm
+  std::vector<AdpcmSeg> ad_segs;      // the decode launch's table (read by an asynchronous copy: alive until the wait)
 };
 
 // Where the results go.  kSignal: the signal to `signal` (host or device memory after mem_kind; NULL: it stays on the
@@ -411,6 +464,11 @@ int check_args(bp_handle h, const char* what, Source& src, const Sink& k, int64_
   } else if (src.kind == kPcm) {
     if ((rc = check_ingest(h, src.data != nullptr, src.format, src.count, src.channels, src.sample_rate, src.mem_kind))) return rc;
     src.n = resampled_length(src.count, src.sample_rate, h->rate);
+  } else if (src.kind == kAdpcm || src.kind == kAdpcmPcm) {
+    if ((rc = check_adpcm(h, src.data, (size_t)src.count, &src.ad))) return rc;
+    const bp_adpcm_layout& l = src.ad;
+    if ((rc = check_ingest(h, true, BP_PCM_S16, l.n_frames, l.channels, l.sample_rate, BP_MEM_DEVICE))) return rc;
+    if (src.kind == kAdpcm) src.n = resampled_length(l.n_frames, l.sample_rate, h->rate);
   } else {
     if ((rc = check_flac(h, src.data, (size_t)src.count, &src.lay))) return rc;
     const bp_flac_stream_layout& l = src.lay;
@@ -428,7 +486,7 @@ int check_args(bp_handle h, const char* what, Source& src, const Sink& k, int64_
 
 // the source, the track, the sink: everything a call queues.  kMaps: a private copy of the given maps goes to track_out (the
 // frequency limits are applied in place).
-int queue_all(bp_handle h, const Source& src, const Sink& k, int64_t T, bool* exported_by_kernel) {
+int queue_all(bp_handle h, Source& src, const Sink& k, int64_t T, bool* exported_by_kernel) {
   const float* d = static_cast<const float*>(src.data);  // the signal on the device (kFlacPcm: none, the PCM in h->pcm_dev)
   Maps m = k.maps;
   int rc = BP_OK;
@@ -441,6 +499,10 @@ int queue_all(bp_handle h, const Source& src, const Sink& k, int64_t T, bool* ex
              src.kind == kFlac) {
     rc = queue_ingest(h, h->pcm_dev, flac_format(src.lay), src.lay.n_frames, src.lay.channels, src.lay.sample_rate,
                       BP_MEM_DEVICE, &d);
+  } else if (src.kind == kAdpcm || src.kind == kAdpcmPcm) {
+    int64_t pcm_off = 0;
+    if (!(rc = queue_adpcm(h, 1, &src.data, &src.ad, src.ad_segs, &pcm_off)) && src.kind == kAdpcm && src.ad.n_frames > 0)
+      rc = queue_ingest(h, h->ad.pcm, BP_PCM_S16, src.ad.n_frames, src.ad.channels, src.ad.sample_rate, BP_MEM_DEVICE, &d);
   } else if (src.kind == kMaps) {
     rc = take_given_maps(h, d, src.onset, src.contour, T, src.mem_kind, &m);
   }
@@ -465,16 +527,18 @@ int queue_all(bp_handle h, const Source& src, const Sink& k, int64_t T, bool* ex
   return BP_OK;
 }
 
-int run_track(bp_handle h, const char* what, Source src, const Sink& k, bp_flac_stream_layout* lay = nullptr) {
+int run_track(bp_handle h, const char* what, Source src, const Sink& k, bp_flac_stream_layout* lay = nullptr,
+              bp_adpcm_layout* ad = nullptr) {
   if (!h) return BP_ERR_INVALID_ARG;
   int64_t T = 0;
   int rc = check_args(h, what, src, k, &T);
   if (rc) return rc;
   const bool flac = src.kind == kFlac || src.kind == kFlacPcm;
   if (lay) *lay = src.lay;
+  if (ad) *ad = src.ad;
   if (k.kind == kCandidates) *k.status = 0;
   // nothing to queue and nothing to wait for (a candidates call waits for the stream whatever the length)
-  if (!flac && src.n == 0 && k.kind != kCandidates) return BP_OK;
+  if (!flac && src.n == 0 && k.kind != kCandidates && !(src.kind == kAdpcmPcm && src.ad.n_frames > 0)) return BP_OK;
   BP_HIP(hipSetDevice(h->device));
   bool exported_by_kernel = false;
   if ((rc = finish(h, queue_all(h, src, k, T, &exported_by_kernel)))) return rc;
@@ -637,6 +701,34 @@ int bp_infer_flac(bp_handle h, const void* file, size_t nbytes, float* note, flo
 int bp_infer_flac_candidates(bp_handle h, const void* file, size_t nbytes, const bp_note_params* params, float* note_out,
                              uint8_t* cand_bits, int8_t* bend_map, int* status) {
   return run_track(h, "bp_infer_flac_candidates", Source{kFlac, file, (int64_t)nbytes},
+                   Sink{kCandidates, {}, nullptr, 0, params, note_out, cand_bits, bend_map, status});
+}
+
+// ---- IMA ADPCM files (include/basic_pitch_amd_adpcm.h) -------------------------------------------------------------------------
+int bp_adpcm_decode_device(bp_handle h, const void* file, size_t nbytes, int16_t* pcm, int64_t max_frames, int64_t* n_frames) {
+  if (!h || !n_frames) return BP_ERR_INVALID_ARG;
+  const char* what = "bp_adpcm_decode_device";
+  // (the layout twice: the room is an argument, and every argument is checked before anything is queued)
+  bp_adpcm_layout lay;
+  if (int rc = check_adpcm(h, file, nbytes, &lay)) return rc;
+  *n_frames = lay.n_frames;
+  if (pcm && max_frames < lay.n_frames) {
+    h->err = std::string(what) + ": the output buffer is too small";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (int rc = run_track(h, what, Source{kAdpcmPcm, file, (int64_t)nbytes}, Sink{kSignal}, nullptr, &lay)) return rc;
+  if (!pcm || lay.n_frames == 0) return BP_OK;
+  BP_HIP(hipMemcpy(pcm, h->ad.pcm, (size_t)(lay.n_frames * lay.channels) * sizeof(int16_t), hipMemcpyDeviceToHost));
+  return BP_OK;
+}
+
+int bp_infer_adpcm(bp_handle h, const void* file, size_t nbytes, float* note, float* onset, float* contour, int mem_kind) {
+  return run_track(h, "bp_infer_adpcm", Source{kAdpcm, file, (int64_t)nbytes}, maps_sink(note, onset, contour, mem_kind));
+}
+
+int bp_infer_adpcm_candidates(bp_handle h, const void* file, size_t nbytes, const bp_note_params* params, float* note_out,
+                              uint8_t* cand_bits, int8_t* bend_map, int* status) {
+  return run_track(h, "bp_infer_adpcm_candidates", Source{kAdpcm, file, (int64_t)nbytes},
                    Sink{kCandidates, {}, nullptr, 0, params, note_out, cand_bits, bend_map, status});
 }
 

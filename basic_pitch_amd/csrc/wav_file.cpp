@@ -1,10 +1,12 @@
-// RIFF / WAVE, on the host alone (basic_pitch_amd/audio.py read_wav: PCM 8 / 16 / 24 / 32 and IEEE float 32 / 64,
-// WAVE_FORMAT_EXTENSIBLE; RF64 / BW64, whose 64-bit data size lies in a ds64 chunk: EBU Tech 3306): the chunk walk, the
+// RIFF / WAVE, on the host alone (basic_pitch_amd/audio.py read_wav: PCM 8 / 16 / 24 / 32, IEEE float 32 / 64, G.711 (tags 7
+// and 6) and IMA ADPCM (tag 0x11, adpcm_host.h); WAVE_FORMAT_EXTENSIBLE; RF64 / BW64, whose 64-bit data size lies in a ds64
+// chunk: EBU Tech 3306): the chunk walk, the
 // sample conversion, bp_wav_info and bp_wav_decode.  Nothing here calls the device library; the file job (file_pipeline.cpp) parses its WAV files with wav_walk / wav_parse and sends the samples as stored.
 #include <cerrno>
 #include <cstring>
 #include <unistd.h>
 
+#include "adpcm_host.h"
 #include "file_host.h"
 
 namespace bp_file {
@@ -34,7 +36,8 @@ bool ByteSource::at(size_t pos, size_t len, uint8_t* out) const {
 }
 
 // the chunk walk of a RIFF/WAVE file: the format and where the samples lie (data_pos; w.pcm is the caller's to set).  Reads
-// the 12-byte head, every chunk's 8-byte head, up to 26 bytes of a fmt chunk and 24 of a ds64 chunk, nothing else.
+// the 12-byte head, every chunk's 8-byte head, up to 26 bytes of a fmt chunk, 24 of a ds64 chunk and 4 of a fact chunk, nothing
+// else.
 bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos) {
   const size_t n = src.size;
   uint8_t head[12] = {0}, body[26];
@@ -60,11 +63,15 @@ bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos) {
     if (std::memcmp(head, "fmt ", 4) == 0 && avail >= 16) {
       if (!src.at(pos + 8, avail < 26 ? avail : 26, body)) return false;
       w.tag = rd16(body), w.channels = rd16(body + 2), w.sample_rate = (int)rd32(body + 4), w.bits = rd16(body + 14);
+      w.block_align = rd16(body + 12);
       if (w.tag == 0xFFFE && avail >= 26) w.tag = rd16(body + 24);  // the real tag sits in the GUID
       have_fmt = true;
     } else if (std::memcmp(head, "data", 4) == 0) {
       data_pos = pos + 8, w.pcm_bytes = avail;
       have_data = true;
+    } else if (std::memcmp(head, "fact", 4) == 0 && avail >= 4) {  // the sample count of a compressed format
+      if (!src.at(pos + 8, 4, body)) return false;
+      if (rd32(body) != 0xffffffffu) w.fact_frames = (int64_t)rd32(body);  // (RF64: the count is ds64's; the blocks decide)
     }
     if (size >= n - (pos + 8)) break;  // the file ends in this chunk
     pos += 8 + (size_t)size + (size & 1);
@@ -76,6 +83,27 @@ bool wav_walk(const ByteSource& src, WavInfo& w, size_t& data_pos) {
   int width = 0;
   if (w.tag == 1 && (w.bits == 8 || w.bits == 16 || w.bits == 24 || w.bits == 32)) width = w.bits / 8;
   if (w.tag == 3 && (w.bits == 32 || w.bits == 64)) width = w.bits / 8;
+  if ((w.tag == 7 || w.tag == 6) && w.bits == 8) width = 1;  // G.711 mu-law, A-law
+  if (w.tag == kWavTagIma) {
+    // blocks of block_align bytes: 4 header bytes a channel, then groups of 4 bytes a channel (adpcm_host.h)
+    if (w.bits != 4) {
+      g_file_error = "unsupported IMA ADPCM sample size " + std::to_string(w.bits) + " (4 bits a sample are read)";
+      return false;
+    }
+    if (w.channels < 1) {
+      g_file_error = "zero channels";
+      return false;
+    }
+    const int payload = w.block_align - 4 * w.channels;
+    if (payload <= 0 || payload % (4 * w.channels) != 0) {
+      g_file_error = "unsupported IMA ADPCM block align " + std::to_string(w.block_align) + " for " + std::to_string(w.channels) +
+                     " channels (4 header bytes and whole groups of 4 bytes a channel are read)";
+      return false;
+    }
+    w.n_frames = (int64_t)(w.pcm_bytes / (size_t)w.block_align) * ((int64_t)payload * 2 / w.channels + 1);  // whole blocks only
+    if (w.fact_frames >= 0 && w.fact_frames < w.n_frames) w.n_frames = w.fact_frames;
+    return true;
+  }
   if (!width) {
     g_file_error = w.tag == 1 ? "unsupported PCM bit depth " + std::to_string(w.bits)
                               : "unsupported WAV format tag " + std::to_string(w.tag);
@@ -114,6 +142,14 @@ void wav_to_float(const WavInfo& w, float* out) {
     }
   } else if (w.tag == 1 && w.bits == 32) {
     for (int64_t i = 0; i < n; ++i) out[i] = (float)((double)(int32_t)rd32(p + 4 * i) / 2147483648.0);
+  } else if (w.tag == 7) {
+    for (int64_t i = 0; i < n; ++i) out[i] = (float)ulaw_expand(p[i]) * (1.0f / 32768.0f);
+  } else if (w.tag == 6) {
+    for (int64_t i = 0; i < n; ++i) out[i] = (float)alaw_expand(p[i]) * (1.0f / 32768.0f);
+  } else if (w.tag == kWavTagIma) {
+    std::vector<int16_t> pcm((size_t)n);
+    ima_wav_decode(p, w.pcm_bytes, w.channels, w.block_align, w.n_frames, pcm.data());
+    for (int64_t i = 0; i < n; ++i) out[i] = (float)pcm[(size_t)i] * (1.0f / 32768.0f);
   } else if (w.bits == 32) {
     std::memcpy(out, p, (size_t)n * 4);
   } else {
@@ -127,6 +163,8 @@ void wav_to_float(const WavInfo& w, float* out) {
 
 int wav_pcm_format(const WavInfo& w) {
   if (w.tag == 1) return w.bits == 8 ? BP_PCM_U8 : w.bits == 16 ? BP_PCM_S16 : w.bits == 24 ? BP_PCM_S24 : BP_PCM_S32;
+  if (w.tag == 7 || w.tag == 6) return w.tag == 7 ? BP_PCM_ULAW : BP_PCM_ALAW;
+  if (w.tag == kWavTagIma) return -1;
   return w.bits == 32 ? BP_PCM_F32 : BP_PCM_F64;
 }
 

@@ -372,6 +372,58 @@ class Model:
         _native.check(self._lib, self._handle, rc, "bp_flac_decode_device")
         return pcm[: n.value], lay["sample_rate"]
 
+    def adpcm_layout(self, data: bytes) -> Dict[str, int]:
+        """The facts of an IMA ADPCM file's bytes from its headers (host, no decoding; include/basic_pitch_amd_adpcm.h):
+        container, codec, channels, sample_rate, block_bytes, block_frames, n_frames, data_start, data_bytes.  ValueError for
+        a file that is no such file or has a fault in its headers."""
+        lay = _native.bp_adpcm_layout()
+        rc = self._lib.bp_adpcm_layout_of(data, len(data), C.byref(lay))
+        if rc != _native.BP_OK:
+            raise ValueError(f"bp_adpcm_layout_of: {self._lib.bp_files_last_error().decode(errors='replace')}")
+        return {k: int(getattr(lay, k)) for k, _ in lay._fields_}
+
+    def adpcm_decode_device(self, data: bytes) -> Tuple[np.ndarray, int]:
+        """An IMA ADPCM file's bytes decoded ON THE DEVICE (csrc/adpcm_device.hip): (int16 samples [n_frames, channels],
+        sample rate), the samples of the host decoder `bp_adpcm_decode`."""
+        lay = self.adpcm_layout(data)
+        pcm = np.empty((lay["n_frames"], lay["channels"]), dtype=np.int16)
+        n = C.c_int64(0)
+        rc = self._lib.bp_adpcm_decode_device(self._handle, data, len(data), pcm.ctypes.data if pcm.size else None, pcm.shape[0], C.byref(n))
+        _native.check(self._lib, self._handle, rc, "bp_adpcm_decode_device")
+        return pcm[: n.value], lay["sample_rate"]
+
+    def predict_adpcm(self, data: bytes) -> Dict[str, np.ndarray]:
+        """The posteriorgrams of an IMA ADPCM file's bytes (RIFF/WAVE format tag 0x11, CAF ima4): the bytes cross PCIe as they
+        are, a quarter of the PCM, one launch expands them on the device, then what predict_pcm_raw does (bp_infer_adpcm)."""
+        lay = self.adpcm_layout(data)
+        out = _empty_maps((self._pcm_frames(lay["n_frames"], lay["sample_rate"]),))
+        self._infer("bp_infer_adpcm", (data, len(data)), out)
+        return out
+
+    def transcribe_adpcm_clips(
+        self,
+        blobs: Sequence[Any],
+        onset_threshold: float = DEFAULT_ONSET_THRESHOLD,
+        frame_threshold: float = DEFAULT_FRAME_THRESHOLD,
+        minimum_note_length: float = DEFAULT_MINIMUM_NOTE_LENGTH_MS,
+        minimum_frequency: Optional[float] = None,
+        maximum_frequency: Optional[float] = None,
+        multiple_pitch_bends: bool = False,
+        melodia_trick: bool = True,
+        midi_tempo: float = DEFAULT_MINIMUM_MIDI_TEMPO,
+        threads: int = 8,
+        decode: str = "device",
+    ) -> "List[Any]":
+        """Many short IMA ADPCM files (`bytes`-like) -> [(midi_data, note_events)] in input order, mirroring
+        `transcribe_flac_clips`.  decode="device": the files of one codec, sample rate and channel count go to the device in
+        ONE call and are expanded there by one launch (`bp_infer_adpcm_clips_events`); decode="host": the host decoder's
+        samples take `transcribe_clips`.  The events of a clip are the same either way."""
+        from . import adpcm_clips as _adpcm_clips
+
+        return _adpcm_clips.transcribe_adpcm_clips(self, blobs, onset_threshold, frame_threshold, minimum_note_length,
+                                                   minimum_frequency, maximum_frequency, multiple_pitch_bends, melodia_trick,
+                                                   midi_tempo, threads, decode)
+
     def predict_flac(self, data: bytes) -> Dict[str, np.ndarray]:
         """The posteriorgrams of a FLAC file's bytes: decode on the device, then what predict_pcm_raw does (bp_infer_flac)."""
         lay = self.flac_layout(data)
@@ -598,7 +650,20 @@ def run_inference(
     # to 22.05 kHz, the 3840-sample lead-in + windowing, CQT + CNN, un-overlapping (inference.py:239-244, 302-315)
     with open(audio_path, "rb") as f:
         head = f.read(12)
-    if head[:4] == b"RIFF" and head[8:12] == b"WAVE" and hasattr(model, "predict_pcm_raw"):
+    adpcm = False
+    if (head[:4] in (b"RIFF", b"RF64", b"BW64", b"caff")) and hasattr(model, "predict_adpcm"):
+        adpcm = _audio.is_adpcm_file(str(audio_path))  # from the format chunk alone
+    if adpcm:
+        # an IMA ADPCM file's BYTES go to the device and are expanded there (csrc/adpcm_device.hip): a quarter of the PCIe bytes
+        # of the PCM and no host core-time per sample; where the library refuses, the numpy reader decodes the file here
+        with open(audio_path, "rb") as f:
+            blob = f.read()
+        try:
+            lay = model.adpcm_layout(blob)
+            unwrapped_output, n_file_frames, file_sr = model.predict_adpcm(blob), lay["n_frames"], lay["sample_rate"]
+        except (ValueError, _native.NativeLibraryError):  # (a fault in the headers: the reader names it with the path)
+            unwrapped_output, n_file_frames, file_sr = host_decoded()
+    elif head[:4] == b"RIFF" and head[8:12] == b"WAVE" and hasattr(model, "predict_pcm_raw"):
         # a WAV file's samples go to the device in the file's own format (no float copy on the host, half the PCIe bytes
         # for 16-bit audio); same posteriorgrams, bit for bit, as decoding them here
         raw, tag, bits, channels, file_sr = _audio.wav_raw(str(audio_path))

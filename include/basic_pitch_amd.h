@@ -542,8 +542,9 @@ int bp_transcribe_files(bp_handle* handles, int n_handles, const char* const* pa
  * device library; the CPU tests pin them to the Python writers and readers).
  * bp_notes_to_midi / bp_notes_to_csv return the number of bytes of the file (written to `out` if it fits `capacity`; call
  * with out = NULL to size the buffer), or a negative bp_status.  `bends` may be NULL (no pitch bends).
- * bp_wav_info / bp_wav_decode: RIFF/WAVE (RF64 / BW64 too) PCM 8 / 16 / 24 / 32 and IEEE float 32 / 64 -> float32 [n_frames, channels] in
- * [-1, 1), the scaling of libsndfile's float read that librosa.load uses (inference.py:239). */
+ * bp_wav_info / bp_wav_decode: RIFF/WAVE (RF64 / BW64 too) PCM 8 / 16 / 24 / 32, IEEE float 32 / 64, G.711 (format tags 7 and
+ * 6, 8 bits) and IMA ADPCM (tag 0x11, 4 bits: basic_pitch_amd_adpcm.h) -> float32 [n_frames, channels] in [-1, 1), the
+ * scaling of libsndfile's float read that librosa.load uses (inference.py:239). */
 int64_t bp_notes_to_midi(const bp_note_event* events, int64_t n_events, const int32_t* bends, int multiple_pitch_bends,
                          double midi_tempo, uint8_t* out, int64_t capacity);
 int64_t bp_notes_to_csv(const bp_note_event* events, int64_t n_events, const int32_t* bends, char* out, int64_t capacity);

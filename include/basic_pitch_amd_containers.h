@@ -20,9 +20,13 @@
  *                   27 A-law; a data size of 0xffffffff means to the end of the file.
  *   RF64 / BW64     a RIFF/WAVE file whose 64-bit sizes lie in its ds64 chunk: BP_CONTAINER_WAV; bp_wav_info and
  *                   bp_wav_decode take it too.
- * A file that ends before its header's count holds the frames that are there.  Not read: the little-endian AU variant
- * (`dns.`), Sony Wave64, ADPCM of any kind and every other compressed AIFF-C type (ima4, MAC3, ...): BP_ERR_BAD_AUDIO,
- * naming what was found.
+ *   RIFF/WAVE       beside integer and float PCM: G.711, format tag 7 (mu-law) or 6 (A-law) with 8 bits, plain, inside
+ *                   WAVE_FORMAT_EXTENSIBLE or in RF64 / BW64: BP_PCM_ULAW / BP_PCM_ALAW, the samples of the AU or AIFF-C
+ *                   file of the same bytes.
+ * A file that ends before its header's count holds the frames that are there.  IMA ADPCM (RIFF/WAVE tag 0x11, CAF `ima4`)
+ * is not samples but blocks: include/basic_pitch_amd_adpcm.h reads it, these two calls answer BP_ERR_BAD_AUDIO.  Not read:
+ * the little-endian AU variant (`dns.`), Sony Wave64, MS ADPCM (tag 2), 3- and 5-bit IMA and every compressed AIFF-C type
+ * (ima4, MAC3, ...): BP_ERR_BAD_AUDIO, naming what was found.
  *
  *   bp_pcm_file_layout_of   the facts of a file from its headers: host code, no handle, thread-safe; `file` = the whole
  *                           file in memory, or a prefix of it that holds the headers (the frame count is then that of
