@@ -727,6 +727,16 @@ def run_inference_windowed(
     }
 
 
+def _window_geometry(model: Any) -> Tuple[int, int, int]:
+    """(window length, hop, lead-in) in samples at the model's own rate: the reference's 43844 / 36164 / 3840 at 22.05 kHz,
+    hop and lead-in scaled by rate / 22050 for a model of another geometry (`Model(ext_cqt_44k=True)`: 87688 / 72328 / 7680
+    at 44.1 kHz).  A model-shaped object without `sample_rate` and `audio_n_samples` has the reference's."""
+    rate, win = getattr(model, "sample_rate", None), getattr(model, "audio_n_samples", None)
+    if rate is None or win is None:
+        return AUDIO_N_SAMPLES, _HOP_SIZE, _OVERLAP_LEN // 2
+    return int(win), _HOP_SIZE * int(rate) // AUDIO_SAMPLE_RATE, (_OVERLAP_LEN // 2) * int(rate) // AUDIO_SAMPLE_RATE
+
+
 def predict_window_range(
     audio_path: Union[pathlib.Path, str],
     model_or_model_path: Union[Model, pathlib.Path, str],
@@ -735,7 +745,8 @@ def predict_window_range(
 ) -> Dict[str, Any]:
     """Piece `piece` of `n_pieces` of ONE long file (the window-range fallback of the file-sharded job).
 
-    A window's samples are determined by its index alone (start = w * 36164 - 3840: inference.py:207,242) and a window's 142
+    A window's samples are determined by its index alone (start = w * 36164 - 3840: inference.py:207,242; w * hop - lead-in of
+    the model's own geometry, `_window_geometry`) and a window's 142
     un-overlapped rows by the window alone (per-window normalisation, signal.py:177-183), so a rank can compute windows
     [w0, w1) = `sharding.split_windows(n_windows, n_pieces)[piece]` without any of its neighbours' data: the file is decoded
     and resampled (on the device, by the same kernel the whole-file call uses), this range's windows are cut on the host
@@ -749,23 +760,24 @@ def predict_window_range(
     pcm, file_sr = _audio.read_audio(str(audio_path))
     y = np.ascontiguousarray(model.resample(pcm, file_sr), dtype=np.float32)
     n_olap = DEFAULT_OVERLAPPING_FRAMES // 2
-    padded = np.concatenate([np.zeros((_OVERLAP_LEN // 2,), dtype=np.float32), y])
-    n_windows = len(range(0, padded.shape[0], _HOP_SIZE))
+    win, hop, lead = _window_geometry(model)
+    padded = np.concatenate([np.zeros((lead,), dtype=np.float32), y])
+    n_windows = len(range(0, padded.shape[0], hop))
     w0, w1 = split_windows(n_windows, n_pieces)[piece]
     rows: Dict[str, List[np.ndarray]] = {k: [] for k, _ in _MAPS}
     batch = int(getattr(model, "max_windows", 256))
     for a in range(w0, w1, batch):
         b = min(w1, a + batch)
-        x = np.zeros((b - a, AUDIO_N_SAMPLES), dtype=np.float32)
+        x = np.zeros((b - a, win), dtype=np.float32)
         for w in range(a, b):
-            seg = padded[w * _HOP_SIZE : w * _HOP_SIZE + AUDIO_N_SAMPLES]
+            seg = padded[w * hop : w * hop + win]
             x[w - a, : len(seg)] = seg
         for k, v in model.predict(x).items():
             if k in rows:
                 v = np.asarray(v)[:, n_olap:-n_olap, :]
                 rows[k].append(v.reshape(v.shape[0] * v.shape[1], v.shape[2]))
     return {"rows": {k: (np.concatenate(rows[k]) if rows[k] else np.zeros((0, w), np.float32)) for k, w in _MAPS},
-            "range": (w0, w1), "n_windows": n_windows, "original_length": int(y.shape[0])}
+            "range": (w0, w1), "n_windows": n_windows, "original_length": int(y.shape[0]), "hop": hop}
 
 
 def _min_note_len_frames(minimum_note_length: float) -> int:
@@ -814,7 +826,7 @@ def assemble_window_ranges(
         at = p["range"][1]
     if not parts or at != parts[0]["n_windows"]:
         raise ValueError("window ranges do not cover the file")
-    n_rows = int(parts[0]["original_length"] / _HOP_SIZE * (AUDIO_WINDOW_LENGTH * ANNOTATIONS_FPS - DEFAULT_OVERLAPPING_FRAMES))
+    n_rows = int(parts[0]["original_length"] / parts[0].get("hop", _HOP_SIZE) * (AUDIO_WINDOW_LENGTH * ANNOTATIONS_FPS - DEFAULT_OVERLAPPING_FRAMES))
     model_output = {k: np.ascontiguousarray(np.concatenate([p["rows"][k] for p in parts])[:n_rows]) for k, _ in _MAPS}
     return (model_output,) + _output_to_notes(
         model_output, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency, maximum_frequency,

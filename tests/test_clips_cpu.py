@@ -158,7 +158,8 @@ def test_bad_clips_are_refused_and_the_message_names_the_clip(lib, model):
         rc = lib.bp_infer_clips_candidates(h, n, table, rate, _native.BP_MEM_HOST, C.addressof(prm), *[o.ctypes.data for o in out])
         assert rc == _native.BP_ERR_INVALID_ARG and where in err() and "bp_infer_clips_candidates" in err(), err()
 
-    for field, value in (("n_frames", -1), ("format", 6), ("format", -1), ("channels", 0), ("channels", 65)):
+    # (formats 0 ... 13 exist, BP_PCM_F32 ... BP_PCM_ALAW: 14 is the first code past them)
+    for field, value in (("n_frames", -1), ("format", _native.BP_PCM_ALAW + 1), ("format", -1), ("channels", 0), ("channels", 65)):
         for at in (0, 1, 2):
             t = clips.clip_table([clips.as_clip(c, i) for i, c in enumerate(good)])
             setattr(t[at], field, value)
