@@ -191,6 +191,16 @@ class bp_note_event(C.Structure):
     ]
 
 
+class bp_sweep_decode(C.Structure):
+    """One decode of a sweep (include/basic_pitch_amd_sweep.h): segment `segment` under parameter set `params`."""
+
+    _fields_ = [
+        ("segment", C.c_int64),
+        ("params", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -317,6 +327,11 @@ EVENTS_SYMBOLS = [
     "bp_events_capacity",
     "bp_infer_clips_events",
     "bp_note_events_from_maps",
+]
+# every symbol include/basic_pitch_amd_sweep.h declares (bound in basic_pitch_amd/sweep.py)
+SWEEP_SYMBOLS = [
+    "bp_note_events_sweep",
+    "bp_infer_clips_events_sweep",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

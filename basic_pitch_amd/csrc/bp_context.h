@@ -92,6 +92,13 @@ struct bp_context {
   Buffer<float> ev_scratch;
   Table ev_seg;  // bp_streams_events: the table of the segments' own parameters (NoteTrackSeg)
   bp::PinnedBuffer<int64_t> ev_home;
+  // a sweep (bp_note_events_sweep, clips_api.hip queue_sweep), all grow-only, scratch of one call and grown by sweeps alone: the
+  // note rows constrained per band [bands][T][88], the working copy of the onset rows [T][88], per dense key the bitmap
+  // [keys][T][12] and the stats records [keys][segments], the decode table (NoteSweepDecode) with the rows and the event
+  // records before each decode behind it
+  Buffer<float> sw_note, sw_onset;
+  Buffer<uint8_t> sw_bits;
+  Table sw_stats, sw_tab;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

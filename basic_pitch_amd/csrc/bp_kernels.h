@@ -201,6 +201,10 @@ void launch_clips_candidates(float* note, float* onset, const float* contour, co
                              int64_t total_rows, int lo, int hi, int infer, double onset_thresh, const void* tab,
                              const double* gauss, void* table, uint8_t* bits, int8_t* bend, hipStream_t s);
 void launch_note_stats_init(void* stats, hipStream_t s);
+// constrain_frequency into copies: the bins outside [lo, hi) of n_rows rows of note -> note_dst and onset -> onset_dst are 0, the
+// others the source's; a null destination is skipped.  The sources are only read (a sweep's maps are shared by its sets).
+void launch_constrain_copy(const float* note, const float* onset, float* note_dst, float* onset_dst, int64_t n_rows, int lo,
+                           int hi, hipStream_t s);
 
 // note_track.hip: the sequential half of note decoding for many clips, one workgroup per clip (bp_infer_clips_events).
 // A clip of at most kNoteTrackLdsRows rows keeps its working copy of the note rows in LDS, a longer one in `scratch`
@@ -230,6 +234,22 @@ hipError_t launch_note_track_segs(const float* note, const uint8_t* bits, const 
                                   const int64_t* ev_first, const void* stats, const NoteTrackSeg* seg, int64_t n_segs,
                                   int64_t max_rows, int form, float* scratch, void* ev_pool, int8_t* bd_pool, void* counts,
                                   int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s);
+// The same over the decode table of a sweep (bp_note_events_sweep, include/basic_pitch_amd_sweep.h): decode j is one
+// workgroup, a segment of the shared maps under one parameter set.  Many decodes read the same rows; what a decode writes is
+// its own: with pool_rows[j] the rows of the decodes before it, its bends go to bd_pool + 88 * pool_rows[j], its working state
+// (a segment of more than kNoteTrackLdsRows rows) to scratch + note_track_scratch_floats(pool_rows[j]), its events to its region
+// ev_first[j] of ev_pool.  pool_rows and ev_first ([n_decodes + 1], device memory) are the two arrays the offsets and pack
+// launches read for the clips of a job; meta, ev_out and bd_out are theirs, over decodes.
+struct NoteSweepDecode {
+  const float* note;    // the note rows its set decodes: the copy constrained to the set's band (all segments' rows)
+  const uint8_t* bits;  // the onset-peak bitmap of its set's dense key (all segments' rows)
+  const void* stats;    // its segment's record in that key's block (null: seg.skip)
+  int64_t first, rows;  // its segment's rows in `note`, `bits` and the bend map
+  NoteTrackSeg seg;     // the tracker's parameters; skip: an onset threshold <= 0, the host's (status 1)
+};
+hipError_t launch_note_track_sweep(const NoteSweepDecode* tab, int64_t n_decodes, int64_t max_rows, const int8_t* bend_map,
+                                   const int64_t* pool_rows, const int64_t* ev_first, float* scratch, void* ev_pool, int8_t* bd_pool,
+                                   void* counts, int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -1,6 +1,7 @@
-// C ABI of the jobs of many clips (include/basic_pitch_amd_clips.h, _events.h, _flac_clips.h): many short clips through the
+// C ABI of the jobs of many clips (include/basic_pitch_amd_clips.h, _events.h, _flac_clips.h, _sweep.h): many short clips through the
 // model in one call — raw PCM, FLAC or IMA ADPCM files' bytes decoded on the device, or maps the caller already holds — and home either
-// the note candidates of every clip or, the tracker run on the device too, the note events alone.
+// the note candidates of every clip or, the tracker run on the device too, the note events alone: under one parameter set, or
+// (a sweep) every segment under many.
 //
 // Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
 //   the sink's fixed arguments -> the source's plan (rows of every clip) -> the outputs against the rows -> statuses and the
@@ -12,9 +13,12 @@
 // bp_streams_events (stream_api.hip) puts it behind its own dense half.
 #include <algorithm>
 #include <cstring>
+#include <map>
+#include <tuple>
 
 #include "../../include/basic_pitch_amd_adpcm.h"
 #include "../../include/basic_pitch_amd_flac_clips.h"
+#include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
 using namespace bp;
@@ -291,14 +295,22 @@ int queue_clips_maps(bp_handle h, int64_t n_clips, const bp_clip* clips, int sam
 
 // ---- note events of many clips (include/basic_pitch_amd_events.h)
 // every argument that is not a clip's, before anything is queued
+// why the tracker refuses a parameter set (null: it takes it), and why a call's room for events and bends is refused
+const char* bad_params(const bp_note_params& prm) {
+  if (prm.melodia_trick && prm.frame_threshold < 0.0)
+    return "a negative frame threshold with the melodia trick never terminates (note_creation.py:452)";
+  return prm.min_note_len < 0 ? "negative min_note_len" : nullptr;
+}
+const char* bad_room(const EventsSink& out) {
+  const bool bad = out.max_events < 0 || out.max_bends < 0 || (out.max_events > 0 && !out.events) || (out.max_bends > 0 && !out.bends);
+  return bad ? "negative max_events / max_bends, or room without a buffer" : nullptr;
+}
+
 int check_events(bp_handle h, const char* what, int64_t n_clips, const bp_note_params* prm, const EventsSink& out) {
   auto invalid = [&](const char* why) { return ::invalid(h, what, why); };
   if (n_clips < 0 || !prm || !out.event_offsets || (n_clips > 0 && !out.status)) return invalid("negative n_clips, null params, event_offsets or status");
-  if (out.max_events < 0 || out.max_bends < 0 || (out.max_events > 0 && !out.events) || (out.max_bends > 0 && !out.bends))
-    return invalid("negative max_events / max_bends, or room without a buffer");
-  if (prm->melodia_trick && prm->frame_threshold < 0.0)
-    return invalid("a negative frame threshold with the melodia trick never terminates (note_creation.py:452)");
-  if (prm->min_note_len < 0) return invalid("negative min_note_len");
+  if (const char* why = bad_room(out)) return invalid(why);
+  if (const char* why = bad_params(*prm)) return invalid(why);
   return BP_OK;
 }
 
@@ -483,8 +495,10 @@ struct JobSource {
 
 // Where the results go.  kCandidatesHome: the note candidates of all rows (host buffers) and out.status, the maps stay in
 // track_out; kEventsHome: the events (out).  params: of the dense half, and of the tracker unless seg_params gives every
-// segment its own (with the tracker's form and the call's name for n: the A/B hook).
-enum JobSinkKind { kCandidatesHome, kEventsHome };
+// segment its own (with the tracker's form and the call's name for n: the A/B hook).  kSweepHome: the events (out) of n_decodes
+// decodes, decode j segment decodes[j].segment under sets[decodes[j].params] (decodes null: the cross product, set-major);
+// params is null, every set has its own dense half.
+enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome };
 struct JobSink {
   JobSinkKind kind;
   const bp_note_params* params;
@@ -495,6 +509,9 @@ struct JobSink {
   const bp_note_params* seg_params;
   int form;
   const char* count_name;
+  int64_t n_sets, n_decodes;
+  const bp_note_params* sets;
+  const bp_sweep_decode* decodes;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -507,6 +524,112 @@ JobSink events_sink(const bp_note_params* params, bp_note_event* events, int64_t
                  nullptr, nullptr, nullptr, nullptr, kNoteTrackFormAuto, "n_clips"};
 }
 
+JobSink sweep_sink(int64_t n_sets, const bp_note_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes, bp_note_event* events,
+                   int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
+  JobSink k = events_sink(nullptr, events, max_events, bends, max_bends, event_offsets, status);
+  k.kind = kSweepHome, k.count_name = "n_decodes";
+  k.n_sets = n_sets, k.n_decodes = n_decodes, k.sets = sets, k.decodes = decodes;
+  return k;
+}
+
+// ---- a sweep: the segments of a job under many parameter sets (include/basic_pitch_amd_sweep.h) -----------------
+// A dense key: what the dense half of note decoding depends on.  Sets of one key share its bitmap and its block of stats
+// records; keys of one band [lo, hi) share the constrained copy of the note rows.
+struct SweepKey {
+  int lo, hi, infer;
+  double onset_thresh;
+  int band;  // its band's slot of h->sw_note; -1: all 88 bins, the maps themselves
+};
+// What the host knows of a sweep before anything is queued, and what its asynchronous copies read.
+struct SweepJob {
+  std::vector<int64_t> segment;     // per decode: its segment, its set (the cross product spelled out)
+  std::vector<int32_t> params;
+  std::vector<NoteTrackSeg> seg;    // per decode: the tracker's parameters
+  std::vector<int64_t> pool_rows;   // [n_decodes + 1] rows of the decodes before each: its regions of the pools
+  std::vector<int> set_key;         // set -> its key; -1: no decode with rows names it, or its onset threshold is <= 0
+  std::vector<SweepKey> keys;       // ordered by band
+  int64_t n_bands = 0;              // constrained copies of the note rows
+  bool bends = false;               // a decode that reaches the tracker wants bends
+  std::vector<uint8_t> block;       // the decode table (NoteSweepDecode) with pool_rows and the event regions behind it
+};
+
+// every argument of a sweep that is not a segment's, before anything is queued
+int check_sweep(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (n_segs < 0 || k.n_sets < 0 || k.n_decodes < 0 || (k.n_sets > 0 && !k.sets) || !k.out.event_offsets || (k.n_decodes > 0 && !k.out.status))
+    return invalid("negative n_segments / n_clips, n_sets or n_decodes, null sets, event_offsets or status");
+  if (const char* why = bad_room(k.out)) return invalid(why);
+  if (k.n_decodes > BP_SWEEP_MAX_DECODES)
+    return invalid(std::to_string(k.n_decodes) + " decodes, more than BP_SWEEP_MAX_DECODES (" + std::to_string(BP_SWEEP_MAX_DECODES) +
+                   "): split the job");
+  for (int64_t p = 0; p < k.n_sets; ++p)
+    if (const char* why = bad_params(k.sets[p])) return invalid("set " + std::to_string(p) + ": " + why);
+  if (!k.decodes) {
+    const bool product = n_segs == 0 || k.n_sets == 0 ? k.n_decodes == 0 : k.n_decodes % n_segs == 0 && k.n_decodes / n_segs == k.n_sets;
+    if (!product) return invalid("decodes is NULL (the cross product) and n_decodes is not n_sets * n_segments");
+    return BP_OK;
+  }
+  for (int64_t j = 0; j < k.n_decodes; ++j) {
+    const bp_sweep_decode& d = k.decodes[j];
+    if (d.reserved != 0) return invalid("decode " + std::to_string(j) + ": reserved must be 0");
+    if (d.params < 0 || d.params >= k.n_sets)
+      return invalid("decode " + std::to_string(j) + ": params " + std::to_string(d.params) + " is not one of the " + std::to_string(k.n_sets) + " sets");
+    if (d.segment < 0 || d.segment >= n_segs)
+      return invalid("decode " + std::to_string(j) + ": segment " + std::to_string(d.segment) + " is not one of the " + std::to_string(n_segs) + " segments");
+  }
+  return BP_OK;
+}
+
+// The decodes against the rows (offs: of the n_segs segments): every decode's tracker parameters and regions, the dense keys of
+// the sets that reach the tracker.  *queued false: no decode needs the device — no rows, or an onset threshold <= 0 (status 1,
+// as events_without_device says it) — and the outputs are complete.
+int plan_sweep(bp_handle h, const char* what, int64_t n_segs, const int64_t* offs, const JobSink& k, SweepJob* w, bool* queued) {
+  const int64_t n = k.n_decodes;
+  w->segment.resize((size_t)n), w->params.resize((size_t)n), w->seg.resize((size_t)n);
+  w->pool_rows.assign((size_t)n + 1, 0);
+  w->set_key.assign((size_t)k.n_sets, -1);
+  std::map<std::tuple<int, int, int, double>, int> keys;  // (a threshold > 0 is no NaN: the order is total)
+  *queued = false;
+  for (int64_t j = 0; j < n; ++j) {
+    const int64_t i = k.decodes ? k.decodes[j].segment : j % n_segs;
+    const int32_t p = k.decodes ? k.decodes[j].params : (int32_t)(j / n_segs);
+    const bp_note_params& prm = k.sets[p];
+    const int64_t rows = offs[i + 1] - offs[i];
+    const bool skip = !(prm.onset_threshold > 0.0);
+    w->segment[(size_t)j] = i, w->params[(size_t)j] = p;
+    w->seg[(size_t)j] = NoteTrackSeg{prm.frame_threshold, prm.energy_tol, prm.min_note_len, prm.melodia_trick != 0,
+                                     prm.include_pitch_bends != 0, skip, 0};
+    w->pool_rows[(size_t)j + 1] = w->pool_rows[(size_t)j] + rows;
+    if (rows == 0 || skip) continue;
+    *queued = true;
+    w->bends = w->bends || prm.include_pitch_bends != 0;
+    if (w->set_key[(size_t)p] >= 0) continue;
+    int lo = 0, hi = 88;
+    bp_internal_freq_limits(&prm, &lo, &hi);
+    w->set_key[(size_t)p] = keys.emplace(std::make_tuple(lo, hi, prm.infer_onsets != 0, prm.onset_threshold), (int)keys.size()).first->second;
+  }
+  if (w->pool_rows[(size_t)n] > BP_SWEEP_MAX_ROWS)
+    return invalid(h, what, "the decodes have " + std::to_string(w->pool_rows[(size_t)n]) + " rows in all, more than BP_SWEEP_MAX_ROWS (" +
+                                std::to_string(BP_SWEEP_MAX_ROWS) + "): split the job");
+  if (!*queued) {
+    for (int64_t j = 0; j < n; ++j) k.out.status[j] = w->pool_rows[(size_t)j + 1] > w->pool_rows[(size_t)j] ? 1 : 0;
+    for (int64_t j = 0; j <= n; ++j) k.out.event_offsets[j] = 0;
+    return BP_OK;
+  }
+  // the keys in the map's order, which keeps a band's keys together; a set's key by that order
+  std::vector<int> order(keys.size());
+  for (const auto& kv : keys) {
+    const auto& [lo, hi, infer, thresh] = kv.first;
+    const bool full = lo <= 0 && hi >= 88;
+    if (!full && (w->keys.empty() || w->keys.back().lo != lo || w->keys.back().hi != hi)) ++w->n_bands;
+    order[(size_t)kv.second] = (int)w->keys.size();
+    w->keys.push_back(SweepKey{lo, hi, infer, thresh, full ? -1 : (int)w->n_bands - 1});
+  }
+  for (int& key : w->set_key)
+    if (key >= 0) key = order[(size_t)key];
+  return BP_OK;
+}
+
 // What a job knows of itself, and every host buffer its asynchronous copies read: the driver holds it until the wait is over.
 struct ClipsJob {
   FlacJob flac;                                // n_model and offs of the clips (kPcmClips too); the rest: kFlacClips
@@ -516,10 +639,78 @@ struct ClipsJob {
   std::vector<ClipDesc> tab;
   std::vector<NoteTrackSeg> seg;
   bool dense_bends = false;                    // kEventsHome: the dense half makes the bend map
+  SweepJob sweep;                              // kSweepHome
   EventsJob ev{};
   EventsPlan plan;
   bool exported_by_kernel = false;
 };
+
+// A sweep behind the maps of its n_segs segments (offs: their rows, T > 0 in all): the dense half once per key — the note rows
+// constrained into the band's copy where the band is new, the onset rows into the one working copy (the launches are serial:
+// it is reused from band to band), then the stats and the bitmap of every segment as the clips calls make them, into the key's
+// own blocks — and the bend map once; the tracker over the decode table; the offsets on their way home.  The maps
+// themselves are only read.  The records are in h->sw_stats, not the clips calls' h->clip_stats, whose state stays as it was.
+int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* offs, ClipsJob& job) {
+  hipStream_t s = h->stream;
+  SweepJob& w = job.sweep;
+  const int64_t T = offs[n_segs], n = job.ev.n, n_keys = (int64_t)w.keys.size();
+  const int64_t plane = T * kFreqN, bits_plane = T * BP_NOTE_CAND_ROW_BYTES, stats_block = n_segs * (int64_t)kStatsBytes;
+  const void* tab = nullptr;
+  const double* gauss = nullptr;
+  if (int rc = note_tables(h, &tab, &gauss)) return rc;
+  uint8_t* unused = nullptr;
+  int8_t* d_bend = nullptr;
+  if (w.bends)
+    if (int rc = reserve_candidates(h, T, &unused, &d_bend)) return rc;
+  if (w.n_bands) {
+    BP_HIP(h->sw_note.reserve((size_t)(w.n_bands * plane)));
+    BP_HIP(h->sw_onset.reserve((size_t)plane));
+  }
+  BP_HIP(h->sw_bits.reserve((size_t)(n_keys * bits_plane)));
+  BP_HIP(h->sw_stats.reserve((size_t)(n_keys * stats_block)));
+  BP_HIP(h->clip_rows.reserve((size_t)n_segs + 1));
+  // The decode table and, behind it, the two arrays the tracker's launches read by decode — the rows and the event records
+  // before each — as ONE block and one copy, queued with the row offsets before the first launch: a copy from pageable memory
+  // waits for the stream's earlier work.
+  const size_t tab_bytes = (size_t)n * sizeof(NoteSweepDecode), pre_bytes = (size_t)(n + 1) * sizeof(int64_t);
+  static_assert(sizeof(NoteSweepDecode) % sizeof(int64_t) == 0, "the arrays behind the table are aligned");
+  w.block.assign(tab_bytes + 2 * pre_bytes, 0);
+  BP_HIP(h->sw_tab.reserve(w.block.size()));
+  NoteSweepDecode* recs = reinterpret_cast<NoteSweepDecode*>(w.block.data());
+  for (int64_t j = 0; j < n; ++j) {
+    NoteSweepDecode& d = recs[j];
+    const int64_t seg = w.segment[(size_t)j];
+    const int key = w.set_key[(size_t)w.params[(size_t)j]];
+    d.first = offs[seg], d.rows = offs[seg + 1] - offs[seg], d.seg = w.seg[(size_t)j];
+    if (d.rows == 0 || d.seg.skip) continue;  // (never reaches the tracker's body: nothing of a key is read)
+    const int band = w.keys[(size_t)key].band;
+    d.note = band >= 0 ? h->sw_note + band * plane : all.note;
+    d.bits = h->sw_bits + key * bits_plane;
+    d.stats = h->sw_stats + key * stats_block + seg * (int64_t)kStatsBytes;
+  }
+  std::memcpy(w.block.data() + tab_bytes, w.pool_rows.data(), pre_bytes);
+  std::memcpy(w.block.data() + tab_bytes + pre_bytes, job.plan.ev_first.data(), pre_bytes);
+  const int64_t* d_rows = reinterpret_cast<const int64_t*>(h->sw_tab + tab_bytes);
+  BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n_segs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+  BP_HIP(hipMemcpyAsync(h->sw_tab, w.block.data(), w.block.size(), hipMemcpyHostToDevice, s));
+  launch_clips_stats_init(h->sw_stats, n_keys * n_segs, s);
+  int made = 0;  // bands whose copies exist; sw_onset holds the last one's
+  for (int64_t i = 0; i < n_keys; ++i) {
+    const SweepKey& key = w.keys[(size_t)i];
+    float *note = all.note, *onset = all.onset;
+    if (key.band >= 0) {
+      note = h->sw_note + key.band * plane, onset = h->sw_onset;
+      if (key.band == made) launch_constrain_copy(all.note, all.onset, note, onset, T, key.lo, key.hi, s), ++made;
+    }
+    launch_clips_candidates(note, onset, all.contour, h->clip_rows, n_segs, T, 0, kFreqN, key.infer, key.onset_thresh, tab, gauss,
+                            h->sw_stats + i * stats_block, h->sw_bits + i * bits_plane, i == 0 ? d_bend : nullptr, s);
+  }
+  BP_HIP(hipGetLastError());
+  BP_HIP(launch_note_track_sweep(h->sw_tab.as<NoteSweepDecode>(), n, job.plan.max_rows, d_bend, d_rows, d_rows + n + 1, h->ev_scratch,
+                                 h->ev_pool, h->bd_pool, h->ev_counts, h->ev_meta, h->ev_out, h->bd_out, s));
+  BP_HIP(hipMemcpyAsync(h->ev_home, h->ev_meta, (size_t)(3 * n + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
 
 // everything a job queues: the source (the maps of all segments to track_out, concatenated by job.offs), the dense half of
 // note decoding for every segment as its own track, the sink
@@ -557,6 +748,7 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   uint8_t* d_bits = nullptr;
   int8_t* d_bend = nullptr;
   if ((rc = events_reserve(h, job.ev, &job.plan))) return rc;
+  if (k.kind == kSweepHome) return queue_sweep(h, all, s.n, job.offs, job);
   if ((rc = queue_clips_dense(h, all, s.n, job.offs, k.params, job.dense_bends, &d_bits, &d_bend))) return rc;
   return events_queue(h, job.ev, job.plan, TrackInputs{all.note, d_bits, d_bend, h->clip_rows, h->clip_stats});
 }
@@ -565,11 +757,11 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   if (!h) return BP_ERR_INVALID_ARG;
   auto invalid = [&](const char* why) { return ::invalid(h, what, why); };
   const int64_t n = src.n;
-  const bool flac = src.kind == kFlacClips, events = k.kind == kEventsHome;
+  const bool flac = src.kind == kFlacClips, sweep = k.kind == kSweepHome, events = k.kind == kEventsHome || sweep;
   int rc = BP_OK;
   // the sink's fixed arguments
   if (events) {
-    if ((rc = check_events(h, what, n, k.params, k.out))) return rc;
+    if ((rc = sweep ? check_sweep(h, what, n, k) : check_events(h, what, n, k.params, k.out))) return rc;
     if (flac && src.sample_rate < 1) return invalid("no sample rate");
   } else if (!k.params || (n > 0 && !k.out.status) || (flac && src.sample_rate < 1)) {
     return invalid(flac ? "null params / status or no sample rate" : "null params / status");
@@ -600,13 +792,22 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   // the statuses the host knows, and the jobs that need no device work
   if (!events)
     for (int64_t i = 0; i < n; ++i) k.out.status[i] = 0;
-  const bool done = events ? events_without_device(n, job.offs, k.params, k.out) : total == 0;  // (no clip has a row)
+  bool done = total == 0;  // (no clip has a row)
+  if (sweep) {
+    bool queued = false;
+    if ((rc = plan_sweep(h, what, n, job.offs, k, &job.sweep, &queued))) return rc;
+    done = !queued;
+  } else if (events) {
+    done = events_without_device(n, job.offs, k.params, k.out);
+  }
   if (flac && (done || !events)) flac_clips_status(h, job.flac, false, k.out.status);
   if (done) return BP_OK;
   BP_HIP(hipSetDevice(h->device));
   if (src.kind != kGivenMaps && src.sample_rate != h->rate)
     if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
-  if (events) {
+  if (sweep) {  // the tracker's job is over the decodes: its "row offsets" are the decodes' regions of the pools
+    job.ev = EventsJob{what, k.count_name, k.n_decodes, job.sweep.pool_rows.data(), nullptr, job.sweep.seg.data(), nullptr, k.form};
+  } else if (events) {
     job.dense_bends = !k.seg_params && k.params->include_pitch_bends != 0;
     for (int64_t i = 0; k.seg_params && i < n; ++i) {
       const bp_note_params& p = k.seg_params[i];
@@ -662,6 +863,22 @@ int bp_note_events_from_maps(bp_handle h, int64_t n_clips, const int64_t* row_of
                              int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
   return run_clips(h, "bp_note_events_from_maps", JobSource{kGivenMaps, n_clips, mem_kind, 0, nullptr, nullptr, row_offsets, note, onset, contour},
                    events_sink(params, events, max_events, bends, max_bends, event_offsets, status));
+}
+
+// ---- a sweep (include/basic_pitch_amd_sweep.h) -------------------------------------------------------------------------------------
+int bp_note_events_sweep(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* note, const float* onset,
+                         const float* contour, int mem_kind, int64_t n_sets, const bp_note_params* sets, int64_t n_decodes,
+                         const bp_sweep_decode* decodes, bp_note_event* events, int64_t max_events, int32_t* bends, int64_t max_bends,
+                         int64_t* event_offsets, int* status) {
+  return run_clips(h, "bp_note_events_sweep", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, note, onset, contour},
+                   sweep_sink(n_sets, sets, n_decodes, decodes, events, max_events, bends, max_bends, event_offsets, status));
+}
+
+int bp_infer_clips_events_sweep(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind, int64_t n_sets,
+                                const bp_note_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes, bp_note_event* events,
+                                int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
+  return run_clips(h, "bp_infer_clips_events_sweep", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   sweep_sink(n_sets, sets, n_decodes, decodes, events, max_events, bends, max_bends, event_offsets, status));
 }
 
 #ifdef BP_AB_KERNELS

@@ -37,6 +37,18 @@ __global__ __launch_bounds__(256) void nd_constrain_kernel(float* __restrict__ n
   if (f < lo || f >= hi) note[i] = onset[i] = 0.0f;
 }
 
+// the same into copies (a sweep's sets share the source rows); a null destination is skipped
+__global__ __launch_bounds__(256) void nd_constrain_copy_kernel(const float* __restrict__ note, const float* __restrict__ onset,
+                                                                float* __restrict__ note_dst, float* __restrict__ onset_dst,
+                                                                int64_t n_cells, int lo, int hi) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n_cells) return;
+  const int f = (int)(i % kNdF);
+  const bool keep = f >= lo && f < hi;
+  if (note_dst) note_dst[i] = keep ? note[i] : 0.0f;
+  if (onset_dst) onset_dst[i] = keep ? onset[i] : 0.0f;
+}
+
 // the initial values of a record: maxima that any row exceeds or equals, no NaN seen
 __device__ __forceinline__ void nd_stats_reset(NdStats* st) {
   st->max_on_ord = f2ord(-__int_as_float(0x7f800000));
@@ -419,6 +431,13 @@ void launch_note_export(const void* note, void* note_dst, int64_t note_bytes, co
                      static_cast<uint32_t*>(bits_dst), bits_dst ? bits_bytes / 4 : 0, static_cast<const uint32_t*>(bend),
                      static_cast<uint32_t*>(bend_dst), bend_dst ? bend_bytes / 4 : 0, static_cast<NdStats*>(stats),
                      static_cast<NdStats*>(stats_dst), n_stats);
+}
+
+void launch_constrain_copy(const float* note, const float* onset, float* note_dst, float* onset_dst, int64_t n_rows, int lo,
+                           int hi, hipStream_t s) {
+  if (n_rows <= 0 || (!note_dst && !onset_dst)) return;
+  hipLaunchKernelGGL(nd_constrain_copy_kernel, dim3((unsigned)((n_rows * kNdF + 255) / 256)), dim3(256), 0, s, note, onset, note_dst,
+                     onset_dst, n_rows * kNdF, lo, hi);
 }
 
 void launch_clips_stats_init(void* table, int64_t n_clips, hipStream_t s) {

@@ -8,8 +8,13 @@
 // frames of a pitch per ballot, the zeroing, the wipes and the argmax go over all 256 threads, amplitudes one event per lane.
 //
 // `energy`, the working copy of the clip's note rows that found notes are zeroed in, lies in LDS where the clip fits
-// (kNoteTrackLdsRows rows; a one-window clip of 142 rows is 50 KB, three workgroups per compute unit) and in a scratch buffer of the
-// handle where it does not.  Both forms run one body (nt_track), in the style of note_device.hip's kRing / linear templates.
+// (kNoteTrackLdsRows rows) and in a scratch buffer of the handle where it does not.  Both forms run one body (nt_track), in the
+// style of note_device.hip's kRing / linear templates.
+//
+// The LDS budget.  A compute unit has 160 KiB and runs floor(163840 / bytes per workgroup) workgroups.  A launch's dynamic LDS
+// is the state of its longest clip plus the pairwise sum's stacks at the depth that length needs (nt_stack_depth), beside 32
+// static bytes: a job of one-window clips (142 rows) takes 51,120 + 512 + 32 bytes, THREE workgroups per compute unit.  (With
+// the stacks static at the depth of the longest clip the library takes, 5,120 bytes, the same job took 56,272 bytes: two.)
 //
 // The order contract.  Onset phase: frames T-2 ... 1, bins 87 ... 0, every set bit of the onset-peak bitmap in exactly that
 // order, each seeing the zeroes of the notes before it.  Melodia phase: the argmax of `energy` over the clip, ties to the
@@ -20,6 +25,9 @@
 // device recursion, no indexed register array: the product library's kernels use no scratch).  Only float32 additions and one
 // IEEE division are involved; `#pragma clang fp contract(off) reassociate(off)` below keeps the compiler from fusing or
 // reordering any of them, whatever flags the library is built with, and HIP's float division is correctly rounded by default.
+#include <algorithm>
+#include <vector>
+
 #include "bp_kernels.h"
 
 #pragma clang fp contract(off)
@@ -30,9 +38,25 @@ namespace bp {
 constexpr int kNtF = 88, kNtMidi = 21;
 // words of working state per row: 88 cells of energy, the row's maximum, the lowest bin that holds it
 constexpr int kNtRowWords = kNtF + 2;
-constexpr int kNtStack = 10;  // depth of the pairwise sum's stack: 7 suffices for kNoteTrackMaxRows (m_d <= n / 2^d + 15)
+constexpr int kNtStack = 10;  // bound of the pairwise sum's stack depth: 7 suffices for kNoteTrackMaxRows (m_d <= n / 2^d + 15)
 static_assert(kNoteTrackLdsRows * kNtRowWords * 4 + 2 * kNtStack * 64 * 4 + 256 <= 160 * 1024, "LDS budget per workgroup");
 static_assert((kNoteTrackMaxRows >> 7) + 15 <= 128, "depth 7 reaches a leaf");
+
+// The deepest the stack of nt_mean gets over any n <= rows values (a note may span any part of a clip): a sum of n > 128 values
+// is one level above the deeper of its two halves.  Not monotonic in n — 255 values split into 120 + 135 and need two levels,
+// 256 into 128 + 128 and need one — so the answer is the running maximum.  At least 1: the stacks are never empty arrays.
+static int nt_stack_depth(int64_t rows) {
+  static const std::vector<uint8_t> upto = [] {
+    std::vector<uint8_t> need(kNoteTrackMaxRows + 1, 0), most(kNoteTrackMaxRows + 1, 1);
+    for (int n = 129; n <= kNoteTrackMaxRows; ++n) {
+      const int n2 = n / 2 - (n / 2) % 8;
+      need[n] = (uint8_t)(1 + std::max(need[n2], need[n - n2]));
+      most[n] = std::max(most[n - 1], need[n]);
+    }
+    return most;
+  }();
+  return upto[(size_t)(rows < 0 ? 0 : (rows < kNoteTrackMaxRows ? rows : kNoteTrackMaxRows))];
+}
 
 struct NtEvent {
   int start, end, pitch;
@@ -152,7 +176,7 @@ struct NtArgs {
   const float* note;        // [rows][88] frequency-constrained note rows of all clips
   const uint32_t* bits;     // [rows][3] onset-peak bitmap
   const int8_t* bend_map;   // [rows][88], or null: no bends wanted
-  const int64_t* offs;      // [n_clips + 1] rows before each clip
+  const int64_t* offs;      // [n_clips + 1] rows before each clip (a sweep: before each decode, which is where it writes)
   const int64_t* ev_first;  // [n_clips + 1] event records before each clip's region of the pool
   const int4* stats;        // per clip the record of note_device.hip (NdStats): .y != 0 is "a NaN in the note or onset rows"
   float* scratch;           // kNtRowWords words per row of all clips: the working state of clips over kNoteTrackLdsRows rows
@@ -164,18 +188,19 @@ struct NtArgs {
 };
 
 // One clip.  energy: the working state of T rows (LDS or scratch), the cells and behind them per row the maximum and the bits of
-// its bin; everything else as in NtArgs.
-__device__ __forceinline__ void nt_track(const NtArgs& a, int64_t c, int T, float* energy) {
-  __shared__ int s_off[kNtStack][64], s_len[kNtStack][64];
+// its bin; stack: 2 x depth x 64 words of LDS for nt_mean, depth >= nt_stack_depth(T); first: the clip's first row of a.note,
+// a.bits and a.bend_map (the clips of a job: a.offs[c]; a decode of a sweep: its segment's, which other decodes share); its
+// regions of the pools and its counts go by c.  Everything else as in NtArgs.
+__device__ __forceinline__ void nt_track(const NtArgs& a, int64_t c, int64_t first, int T, float* energy, int* stack, int depth) {
+  int(*s_off)[64] = reinterpret_cast<int(*)[64]>(stack), (*s_len)[64] = reinterpret_cast<int(*)[64]>(stack + depth * 64);
   __shared__ float s_best_v[4];
   __shared__ int s_best_i[4];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-  const int64_t first = a.offs[c];
   const float* note = a.note + first * kNtF;
   const uint32_t* bits = a.bits + first * 3;
   const int8_t* bend_map = a.bend_map ? a.bend_map + first * kNtF : nullptr;
   NtEvent* ev = a.ev_pool + a.ev_first[c];
-  int8_t* bd = a.bd_pool + first * kNtF;
+  int8_t* bd = a.bd_pool + a.offs[c] * kNtF;
   const int cap_e = (int)(a.ev_first[c + 1] - a.ev_first[c]);
   const int tol = a.energy_tol, mnl = a.min_note_len;
   const double thresh = a.frame_thresh;
@@ -298,10 +323,17 @@ __device__ __forceinline__ void nt_track(const NtArgs& a, int64_t c, int T, floa
   if (tid == 0) a.counts[c] = make_int4(ne, nb, full ? 2 : 0, 0);
 }
 
-// kLds: the clips of at most lds_rows rows, their working state in dynamic LDS (lds_rows * kNtRowWords words); otherwise the
-// longer ones, theirs in the scratch buffer.  A clip of the other kind is the other launch's.
+// where the stacks lie in a launch's dynamic LDS: behind the working state of lds_rows rows (kLds), or alone
 template <bool kLds>
-__global__ __launch_bounds__(256) void nt_track_kernel(NtArgs a, int lds_rows) {
+__device__ __forceinline__ int* nt_stack(float* s_state, int lds_rows) {
+  return reinterpret_cast<int*>(s_state + (kLds ? lds_rows * kNtRowWords : 0));
+}
+
+// kLds: the clips of at most lds_rows rows, their working state in dynamic LDS (lds_rows * kNtRowWords words, the stacks behind
+// it); otherwise the longer ones, theirs in the scratch buffer (dynamic LDS: the stacks alone).  A clip of the other kind is
+// the other launch's.  depth: of the stacks the launch has room for.
+template <bool kLds>
+__global__ __launch_bounds__(256) void nt_track_kernel(NtArgs a, int lds_rows, int depth) {
   extern __shared__ float s_state[];
   const int64_t c = blockIdx.x;
   const int64_t rows = a.offs[c + 1] - a.offs[c];
@@ -313,13 +345,13 @@ __global__ __launch_bounds__(256) void nt_track_kernel(NtArgs a, int lds_rows) {
   }
   const int T = (int)rows;
   float* state = kLds ? s_state : a.scratch + a.offs[c] * kNtRowWords;
-  nt_track(a, c, T, state);
+  nt_track(a, c, a.offs[c], T, state, nt_stack<kLds>(s_state, lds_rows), depth);
 }
 
 // The same two forms for segments that carry their own parameters (bp_streams_events: a segment is a stream's slice): segment
 // c decodes with seg[c], read beside its row offsets; a segment marked `skip` (an onset threshold <= 0) is the host's, status 1.
 template <bool kLds>
-__global__ __launch_bounds__(256) void nt_track_segs_kernel(NtArgs a, const NoteTrackSeg* __restrict__ seg, int lds_rows) {
+__global__ __launch_bounds__(256) void nt_track_segs_kernel(NtArgs a, const NoteTrackSeg* __restrict__ seg, int lds_rows, int depth) {
   extern __shared__ float s_state[];
   const int64_t c = blockIdx.x;
   const int64_t rows = a.offs[c + 1] - a.offs[c];
@@ -334,7 +366,32 @@ __global__ __launch_bounds__(256) void nt_track_segs_kernel(NtArgs a, const Note
   a.energy_tol = p.energy_tol, a.min_note_len = p.min_note_len, a.melodia = p.melodia;
   if (!p.bends) a.bend_map = nullptr;
   float* state = kLds ? s_state : a.scratch + a.offs[c] * kNtRowWords;
-  nt_track(a, c, (int)rows, state);
+  nt_track(a, c, a.offs[c], (int)rows, state, nt_stack<kLds>(s_state, lds_rows), depth);
+}
+
+// The same two forms over the decode table of a sweep (bp_note_events_sweep): workgroup c is decode c, tab[c] says which rows
+// of which note copy, bitmap and stats block it reads and with which parameters.  Decodes share rows, so what a decode WRITES
+// is its own: a.offs holds the rows of the decodes before it — its region of the bend pool and of the scratch state —, and
+// a.ev_first its region of the event pool, as for the clips of a job.  a.bend_map is the one bend map of the shared rows.
+template <bool kLds>
+__global__ __launch_bounds__(256) void nt_track_sweep_kernel(NtArgs a, const NoteSweepDecode* __restrict__ tab, int lds_rows,
+                                                             int depth) {
+  extern __shared__ float s_state[];
+  const int64_t c = blockIdx.x;
+  const NoteSweepDecode d = tab[c];
+  if ((d.rows <= lds_rows) != kLds) return;
+  // (a set with an onset threshold <= 0 has no dense half: its stats pointer is null and never read)
+  const bool host = d.rows > 0 && (d.seg.skip != 0 || static_cast<const int4*>(d.stats)->y != 0);
+  if (d.rows == 0 || host || d.rows > kNoteTrackMaxRows) {
+    if (threadIdx.x == 0) a.counts[c] = make_int4(0, 0, d.rows == 0 ? 0 : (host ? 1 : 2), 0);
+    return;
+  }
+  a.note = d.note, a.bits = reinterpret_cast<const uint32_t*>(d.bits);
+  a.frame_thresh = d.seg.frame_thresh;
+  a.energy_tol = d.seg.energy_tol, a.min_note_len = d.seg.min_note_len, a.melodia = d.seg.melodia;
+  if (!d.seg.bends) a.bend_map = nullptr;
+  float* state = kLds ? s_state : a.scratch + a.offs[c] * kNtRowWords;
+  nt_track(a, c, d.first, (int)d.rows, state, nt_stack<kLds>(s_state, lds_rows), depth);
 }
 
 // ---- the second step: events and bends contiguous in clip order.  meta: [n + 1] events before each clip, [n + 1] bends before
@@ -388,16 +445,19 @@ int64_t note_track_scratch_floats(int64_t total_rows) { return total_rows * kNtR
 
 // The tracker's launches for either kind of segment: the LDS form sized by the longest segment that takes it (a job of
 // one-window clips runs three workgroups per compute unit), the scratch form where a segment is longer (lds_limit 0: for every
-// segment); then the second step.  extra: what a kernel takes between the arguments and lds_rows.
+// segment), each with the stacks its longest segment needs; then the second step.  extra: what a kernel takes between the
+// arguments and lds_rows.
 template <class Kernel, class... Extra>
 static hipError_t nt_launch(Kernel lds, Kernel scratch, const NtArgs& a, int64_t n, int64_t max_rows, int lds_limit, int64_t* meta,
                             void* ev_out, int8_t* bd_out, hipStream_t s, Extra... extra) {
   const int lds_rows = (int)(max_rows < lds_limit ? max_rows : lds_limit);
-  const size_t lds_bytes = (size_t)(lds_rows > 0 ? lds_rows : 1) * kNtRowWords * 4;
+  const int depth = nt_stack_depth(lds_rows), deep = nt_stack_depth(max_rows);
+  const size_t lds_bytes = ((size_t)lds_rows * kNtRowWords + 2 * depth * 64) * 4;
   const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(lds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes);
   if (e != hipSuccess) return e;
-  hipLaunchKernelGGL(lds, dim3((unsigned)n), dim3(256), lds_bytes, s, a, extra..., lds_rows);
-  if (max_rows > lds_limit) hipLaunchKernelGGL(scratch, dim3((unsigned)n), dim3(256), 0, s, a, extra..., lds_rows);
+  hipLaunchKernelGGL(lds, dim3((unsigned)n), dim3(256), lds_bytes, s, a, extra..., lds_rows, depth);
+  if (max_rows > lds_limit)
+    hipLaunchKernelGGL(scratch, dim3((unsigned)n), dim3(256), (size_t)2 * deep * 64 * 4, s, a, extra..., lds_rows, deep);
   hipLaunchKernelGGL(nt_offsets_kernel, dim3(1), dim3(256), 0, s, a.counts, n, meta);
   hipLaunchKernelGGL(nt_pack_kernel, dim3((unsigned)n), dim3(256), 0, s, a.counts, a.offs, a.ev_first, meta, n,
                      reinterpret_cast<const int4*>(a.ev_pool), a.bd_pool, static_cast<int4*>(ev_out), bd_out);
@@ -413,6 +473,16 @@ hipError_t launch_note_track_segs(const float* note, const uint8_t* bits, const 
                  static_cast<NtEvent*>(ev_pool), bd_pool, static_cast<int4*>(counts), 0.0, 0, 0, 0};
   return nt_launch(&nt_track_segs_kernel<true>, &nt_track_segs_kernel<false>, a, n_segs, max_rows,
                    form == kNoteTrackFormScratch ? 0 : kNoteTrackLdsRows, meta, ev_out, bd_out, s, seg);
+}
+
+hipError_t launch_note_track_sweep(const NoteSweepDecode* tab, int64_t n_decodes, int64_t max_rows, const int8_t* bend_map,
+                                   const int64_t* pool_rows, const int64_t* ev_first, float* scratch, void* ev_pool, int8_t* bd_pool,
+                                   void* counts, int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s) {
+  if (n_decodes <= 0) return hipSuccess;
+  const NtArgs a{nullptr, nullptr, bend_map, pool_rows, ev_first, nullptr, scratch, static_cast<NtEvent*>(ev_pool), bd_pool,
+                 static_cast<int4*>(counts), 0.0, 0, 0, 0};
+  return nt_launch(&nt_track_sweep_kernel<true>, &nt_track_sweep_kernel<false>, a, n_decodes, max_rows, kNoteTrackLdsRows, meta,
+                   ev_out, bd_out, s, tab);
 }
 
 hipError_t launch_note_track(const float* note, const uint8_t* bits, const int8_t* bend_map, const int64_t* offs,

@@ -99,14 +99,12 @@ def clip_events(events, bends: np.ndarray, offsets: np.ndarray, i: int, include_
             for e in events[int(offsets[i]) : int(offsets[i + 1])]]
 
 
-def note_events(model: Any, outputs: Sequence[Any], prm: Any) -> List[Tuple[Optional[List["_notes.NoteEvent"]], int]]:
-    """`Model.note_events`: a list of posteriorgram dicts (numpy arrays or CUDA tensors, all of one kind) through one
-    `bp_note_events_from_maps` call -> [(events, status)] per dict; events is None where the status is 1 or 2 (decode those
-    maps with `note_creation.model_output_to_notes`)."""
+def stack_maps(outputs: Sequence[Any], what: str):
+    """Posteriorgram dicts (numpy arrays or CUDA tensors, all of one kind) as the maps calls take them: (row offsets, the
+    three maps of all segments one after the other, {map: pointer, or None without rows}, mem_kind).  The pointers are into
+    the returned maps, which the caller holds until its call has returned."""
     from . import inference as _inf
 
-    if not outputs:
-        return []
     on_dev = _inf._is_torch_cuda(outputs[0]["note"])
     maps = {}
     for k, w in _inf._MAPS:
@@ -114,7 +112,7 @@ def note_events(model: Any, outputs: Sequence[Any], prm: Any) -> List[Tuple[Opti
         for out in outputs:
             a = out[k]
             if _inf._is_torch_cuda(a) != on_dev:
-                raise ValueError("note_events: the maps must all be numpy arrays or all CUDA tensors")
+                raise ValueError(f"{what}: the maps must all be numpy arrays or all CUDA tensors")
             a = a.contiguous().float() if on_dev else np.require(a, np.float32, ["C"])
             if a.ndim != 2 or a.shape[1] != w:
                 raise ValueError(f"{k}: expected (T, {w})")
@@ -127,15 +125,24 @@ def note_events(model: Any, outputs: Sequence[Any], prm: Any) -> List[Tuple[Opti
             maps[k] = np.concatenate(parts) if len(parts) > 1 else parts[0]
     rows = [int(out["note"].shape[0]) for out in outputs]
     if any(int(out[k].shape[0]) != r for out, r in zip(outputs, rows) for k, _ in _inf._MAPS):
-        raise ValueError("note_events: note, onset and contour of a segment must have the same number of rows")
+        raise ValueError(f"{what}: note, onset and contour of a segment must have the same number of rows")
     offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
     if on_dev:
         import torch
 
         torch.cuda.current_stream(maps["note"].device).synchronize()
-    ptr = lambda a: _inf._ptr(a) if int(offs[-1]) else None  # noqa: E731
-    events, bends, ev_offs, status = note_events_from_maps(model, offs, ptr(maps["note"]), ptr(maps["onset"]), ptr(maps["contour"]),
-                                                           _inf._mem_kind(maps["note"]), prm)
+    ptrs = {k: (_inf._ptr(a) if int(offs[-1]) else None) for k, a in maps.items()}
+    return offs, maps, ptrs, _inf._mem_kind(maps["note"])
+
+
+def note_events(model: Any, outputs: Sequence[Any], prm: Any) -> List[Tuple[Optional[List["_notes.NoteEvent"]], int]]:
+    """`Model.note_events`: a list of posteriorgram dicts (numpy arrays or CUDA tensors, all of one kind) through one
+    `bp_note_events_from_maps` call -> [(events, status)] per dict; events is None where the status is 1 or 2 (decode those
+    maps with `note_creation.model_output_to_notes`)."""
+    if not outputs:
+        return []
+    offs, maps, ptr, mem_kind = stack_maps(outputs, "note_events")
+    events, bends, ev_offs, status = note_events_from_maps(model, offs, ptr["note"], ptr["onset"], ptr["contour"], mem_kind, prm)
     with_bends = bool(prm.include_pitch_bends)
     return [(clip_events(events, bends, ev_offs, i, with_bends) if not status[i] else None, int(status[i]))
             for i in range(len(outputs))]

@@ -497,6 +497,27 @@ class Model:
 
         return _events.note_events(self, outputs, prm)
 
+    def sweep_note_events(self, outputs: Sequence[Dict[str, Any]], params: Sequence[Any],
+                          pairs: "Optional[Sequence[Tuple[int, int]]]" = None):
+        """The segments `outputs` (as for `note_events`) decoded under every parameter set of `params` (a list of
+        `note_creation._note_params`) in ONE device call (`bp_note_events_sweep`): the maps go to the device once, the dense
+        half runs once per distinct (frequency band, infer_onsets, onset threshold) among the sets, the tracker is one launch
+        with a workgroup per decode.  Returns result[set][segment] = (events | None, status), each what `note_events` gives
+        for that segment alone with that set; with `pairs`, a list of (segment, set), one such tuple per pair."""
+        from . import sweep as _sweep
+
+        return _sweep.sweep_note_events(self, outputs, params, pairs)
+
+    def transcribe_clips_sweep(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Sequence[Any]
+                               ) -> "List[List[List[Any]]]":
+        """Many short clips (as for `transcribe_clips`) under every parameter set of `params` (a list of
+        `note_creation._note_params`): result[set][clip] = note_events.  The clips of a rate go through the model ONCE
+        (`bp_infer_clips_events_sweep`) whatever the number of sets; the events of a clip under a set are those of
+        `transcribe_clips(..., decode="device")` with that set's parameters."""
+        from . import sweep as _sweep
+
+        return _sweep.transcribe_clips_sweep(self, clips, sample_rates, params)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
