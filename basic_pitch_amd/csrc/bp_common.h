@@ -9,7 +9,7 @@
 namespace bp {
 
 // A/B switches.  The product library reads no behaviour switch from the environment: the env-selected variants of a
-// kernel (BP_CONV1, BP_CONV2, BP_NOTE, BP_ONSET, BP_RIM, BP_RESAMPLE) and the kernels only
+// kernel (BP_CONV1, BP_CONV2, BP_NOTE, BP_ONSET, BP_RIM, BP_RESAMPLE, BP_MARCH_PRIO) and the kernels only
 // they can reach exist in builds with -DBP_AB_KERNELS (basic_pitch_amd/build.py: build_library(ab=True), the library
 // the comparison tests and tools load through BASIC_PITCH_AMD_LIB); in the default build this returns null.
 inline const char* ab_env(const char* name) {

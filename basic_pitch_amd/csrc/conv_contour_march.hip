@@ -55,6 +55,7 @@ constexpr int kCmRowU = 2 * kCmLoU;  // one z row image: 320 units = 5 KB
 #define BP_CM_PF 1
 #endif
 constexpr int kCmPf = BP_CM_PF;      // k-steps of B fragments read ahead of the matrix instructions
+constexpr int kCmPrio = 0;           // march_common.h: no wave changes priority (profiles/march_priority.md)
 static_assert(cm_copy_off(3) + kCmCopyU <= kCmLoU, "copies fit a plane");
 
 struct ContourMarchParams {
@@ -64,7 +65,9 @@ struct ContourMarchParams {
   float* c1;           // [n][172][kC1Row][8]
   int n_tasks;         // n_windows * chunks * kCmStrips
   int chunks;          // frame chunks per window: kCmChunks at full batches, more when few windows must fill the chip
+  int prio;            // march_common.h BP_MARCH_PRIO_*: the rule by which the two waves of a SIMD share the issue priority
 };
+BP_MARCH_PROF_BUF(bp_prof_contour)
 
 template <bool WLO>
 __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(ContourMarchParams p) {
@@ -74,6 +77,7 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
   const int wave = wave_id();
   const int gq = lane >> 4, n = lane & 15;
   uint4* img = lds[wave];
+  BP_MARCH_PROF_ENTRY(bp_prof_contour, wave)
 
   // resident weights
   uint4 ah[3][kCmKS], al[WLO ? 3 : 1][kCmKS];
@@ -98,12 +102,22 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
   // per wave are no imbalance — every SIMD hosts one wave of each kind and the matrix pipe is what they share — while
   // consecutive tasks, the strips of one (window, chunk), read the same zp rows at the same time from the same CU.)
   const int lblock = BP_XCD_LOGICAL_BLOCK();
+  BP_MARCH_PROF_SETUP();
+  // the rows of the wave's tasks (march_common.h: what a percentage rule counts): a task marches z rows T0 - 1 .. T1
+  int share_rows = 0;
+  if (p.prio > 0 && p.prio < 100 && BP_MARCH_PRIO_SECOND_HALF())
+    for (int task = lblock * kCmWaves + wave; task < p.n_tasks; task += total_waves) {
+      const int ci = (task % (p.chunks * kCmStrips)) / kCmStrips;
+      share_rows += ((ci + 1) * kFrames) / p.chunks - (ci * kFrames) / p.chunks + 2;
+    }
+  BP_MARCH_PRIO_STATE(p.prio, share_rows);
 #pragma unroll 1
   for (int task = lblock * kCmWaves + wave; task < p.n_tasks; task += total_waves) {  // wave-uniform; no barriers
     const int b = task / (p.chunks * kCmStrips);
     const int rem = task - b * (p.chunks * kCmStrips);
     const int ci = rem / kCmStrips, strip = rem - ci * kCmStrips;
     const int T0 = (ci * kFrames) / p.chunks, T1 = ((ci + 1) * kFrames) / p.chunks;
+    BP_MARCH_PRIO_PIECE(p.prio, T1 - T0 + 2)
     const int p0 = 10 + 16 * strip;                  // first position (bin pair) of the strip: bins 2 p0 = 20 + 32 strip
     const int wb = 2 * p0 - 4;                       // first zp word of the strip's window (a multiple of 4)
     const uint32_t* zwin = p.zp + (int64_t)b * kZWin + wb;
@@ -205,6 +219,8 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
     // run this row's matrix work, finish the frame it completes
 #define BP_CM_STEP(N0, N1, N2)                                          \
   do {                                                                  \
+    BP_MARCH_PRIO_ROW();                                                \
+    BP_MARCH_PROF_ROW();                                                \
     stage_commit(buf ^ 1, ld0);                                         \
     ld0 = ld1;                                                          \
     ld1 = stage_issue(row_c(zr + 3));                                   \
@@ -224,7 +240,9 @@ __global__ __launch_bounds__(64 * kCmWaves, 2) void contour_conv1_march_kernel(C
       BP_CM_STEP(C, B, A);
     }
 #undef BP_CM_STEP
+    BP_MARCH_PROF_PIECE_END();
   }
+  BP_MARCH_PROF_EXIT();
 }
 
 // folded conv1, interior bins: the wave-private march (default) or the round-2 kernel (BP_CONV1=rounds)
@@ -242,10 +260,11 @@ void launch_contour_conv1_march(const uint32_t* zp, const void* wfrag, const flo
   // one window, 4 chunks leave 28 waves marching 45 rows each while 2020 wave slots idle)
   int chunks = kCmChunks;
   while (chunks < 32 && (int64_t)n_windows * chunks * kCmStrips < (int64_t)2 * n_cu * kCmWaves) chunks *= 2;
-  ContourMarchParams p{static_cast<const uint4*>(wfrag), bias, zp, c1, n_windows * chunks * kCmStrips, chunks};
+  ContourMarchParams p{static_cast<const uint4*>(wfrag), bias, zp, c1, n_windows * chunks * kCmStrips, chunks, 0};
   if (p.n_tasks <= 0) return;
   int grid = (p.n_tasks + kCmWaves - 1) / kCmWaves;
   if (grid > 2 * n_cu) grid = 2 * n_cu;  // two workgroups of four waves per CU (registers), persistent
+  p.prio = march_prio(kCmPrio, grid, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(contour_conv1_march_kernel<true>, dim3(grid), dim3(64 * kCmWaves), 0, stream, p);
   else

@@ -1,10 +1,13 @@
 // What the wave-private marches (note_march16.hip, onset_march16.hip, conv_contour_march.hip, the 32x32x16 forms kept for
 // A/B runs) share beside their arithmetic and their LDS layouts: the fence around a wave's LDS image, the order in which
-// workgroups take their work, the cut of the frames into shares, the launchers' grid.  The block order and the cut are
+// workgroups take their work, the cut of the frames into shares, the launchers' grid, the hand-over of the issue priority
+// between the two waves of a SIMD, the tool builds' stamps.  The block order, the cut and the priority rule are
 // TEXT that a kernel expands in place: as functions (forced inline or not; the cut as `bool next()`, as `done()` +
 // `take()`, as a loop calling the body back) they moved the compiler's block layout and register allocation of the march
 // around them, and a march's device code does not move for a helper's sake (tools/kernel_digest.py).
 #pragma once
+#include <cstring>
+
 #include "bp_common.h"
 
 namespace bp {
@@ -79,6 +82,101 @@ struct MarchShares {
     return true;
   }
 };
+
+// Sharing the issue priority.  With both halves of the grid resident (gridDim.x == 2 n_cu) every SIMD holds one wave of
+// the first half and one of the second, dispatched later.  At equal priority the older wave wins the vector-issue
+// arbitration on every row, runs ahead and retires first; the younger one finishes alone, at the one-wave rate, and the
+// launch waits for it (profiles/march_priority.md).  The rule `prio` (wave-uniform, from the launcher: march_prio) hands
+// the arbitration over ONCE — no flip per row or k-step, which slows both waves:
+//    0         no wave changes priority;
+//    1 .. 99   a second-half wave raises its priority when it has marched that percentage of the rows of its own share,
+//              counted over all its pieces, halo rows included;
+//    -1        the same at half of EACH piece, back to 0 at the piece's end (A/B);
+//    100, 101  the first / the second half runs at priority 1 from its first row (A/B).
+// First-half waves never flip; a wave without rows never reaches _ROW.  The countdown lives in one scalar register.
+// _ROWS (between _SHARES_STATE and the piece loop) counts the rows of the wave's share: `halo` rows per piece beside its
+// frames; _STATE declares the countdown; _PIECE stands at the head of a piece, _ROW at the head of a row.
+#define BP_MARCH_PRIO_SECOND_HALF() ((int)blockIdx.x >= (int)gridDim.x / 2)
+#define BP_MARCH_PRIO_ROWS(prio, kStrips, kCut1, kCut2, kCut3, halo, rows)                                         \
+  int rows = 0;                                                                                                    \
+  if ((prio) > 0 && (prio) < 100 && BP_MARCH_PRIO_SECOND_HALF()) {                                                 \
+    const int64_t F0_first = F0;                                                                                   \
+    for (int pi = 0;; ++pi) {                                                                                      \
+      int ws, T0, T1;                                                                                              \
+      BP_MARCH_SHARES_TAKE(kStrips, kCut1, kCut2, kCut3, break)                                                    \
+      (void)ws;                                                                                                    \
+      rows += T1 - T0 + (halo);                                                                                    \
+    }                                                                                                              \
+    F0 = F0_first;                                                                                                 \
+  }
+#define BP_MARCH_PRIO_STATE(prio, rows)                                                                            \
+  int prio_left = ((prio) > 0 && (prio) < 100 && BP_MARCH_PRIO_SECOND_HALF()) ? 1 + (rows) * (prio) / 100 : 0;     \
+  if ((prio) >= 100 && ((prio) == 101) == BP_MARCH_PRIO_SECOND_HALF()) __builtin_amdgcn_s_setprio(1)
+#define BP_MARCH_PRIO_PIECE(prio, piece_rows)                                                                      \
+  if ((prio) < 0 && BP_MARCH_PRIO_SECOND_HALF()) {                                                                 \
+    __builtin_amdgcn_s_setprio(0);                                                                                 \
+    prio_left = 1 + (piece_rows) / 2;                                                                              \
+  }
+#define BP_MARCH_PRIO_ROW() \
+  if (--prio_left == 0) __builtin_amdgcn_s_setprio(1)
+
+// The rule of a launch: `adopted` (the kernel's measured choice) when both halves of the grid are resident, none otherwise.
+// A/B library only: BP_MARCH_PRIO = off | 1 .. 99 | piece | first | second replaces every kernel's choice.
+inline int march_prio(int adopted, int grid, int n_cu) {
+  static const int forced = [] {
+    const char* e = ab_env("BP_MARCH_PRIO");
+    if (!e) return -2;
+    if (strcmp(e, "off") == 0) return 0;
+    if (strcmp(e, "piece") == 0) return -1;
+    if (strcmp(e, "first") == 0) return 100;
+    if (strcmp(e, "second") == 0) return 101;
+    const int v = atoi(e);
+    return v >= 1 && v <= 99 ? v : -2;
+  }();
+  return grid == 2 * n_cu ? (forced != -2 ? forced : adopted) : 0;
+}
+
+#ifdef BP_MARCH_PROF
+// Tool builds only (tools/experiments/march_prof.py): 100 MHz stamps of EVERY wave of a launch of at most 512 workgroups,
+// written by lane 0 as they are taken into a buffer of their own that no kernel reads: per wave [0] entry, [1] set-up
+// done, [2 .. 5] end of piece 0 .. 3, [6] exit, [7] rows | pieces << 16 | XCC_ID << 20 | HW_ID << 32.  The wave's slot is
+// its PHYSICAL place, 4 blockIdx.x + wave.  _READ defines the C function the tool fetches the last launch's stamps with.
+#define BP_MARCH_PROF_BUF(name)                                                                                    \
+  __device__ unsigned long long name[2048 * 8];                                                                    \
+  extern "C" int name##_read(unsigned long long* dst) {                                                            \
+    if (hipDeviceSynchronize() != hipSuccess) return -1;                                                           \
+    return hipMemcpyFromSymbol(dst, HIP_SYMBOL(name), sizeof(name)) == hipSuccess ? 0 : -1;                        \
+  }
+#define BP_MARCH_PROF_ENTRY(name, wave)                                                                            \
+  unsigned long long* const prof_rec = name + ((int)blockIdx.x * 4 + (wave)) * 8;                                  \
+  const bool prof_on = (threadIdx.x & 63) == 0 && gridDim.x <= 512;                                                \
+  int prof_rows = 0, prof_pieces = 0;                                                                              \
+  if (prof_on) {                                                                                                   \
+    prof_rec[0] = __builtin_amdgcn_s_memrealtime();                                                                \
+    prof_rec[2] = prof_rec[3] = prof_rec[4] = prof_rec[5] = 0;                                                     \
+  }
+#define BP_MARCH_PROF_SETUP()                                                                                      \
+  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");                                                      \
+  if (prof_on) prof_rec[1] = __builtin_amdgcn_s_memrealtime()
+#define BP_MARCH_PROF_ROW() ++prof_rows
+#define BP_MARCH_PROF_PIECE_END()                                                                                  \
+  if (prof_on && prof_pieces < 4) prof_rec[2 + prof_pieces] = __builtin_amdgcn_s_memrealtime();                    \
+  ++prof_pieces
+#define BP_MARCH_PROF_EXIT()                                                                                       \
+  if (prof_on) {                                                                                                   \
+    prof_rec[6] = __builtin_amdgcn_s_memrealtime();                                                                \
+    prof_rec[7] = (unsigned long long)(unsigned)(prof_rows & 0xffff) | (unsigned long long)(prof_pieces & 15) << 16 | \
+                  (unsigned long long)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 15) << 20 |                     \
+                  (unsigned long long)(unsigned)__builtin_amdgcn_s_getreg(4 | (31 << 11)) << 32;                   \
+  }
+#else
+#define BP_MARCH_PROF_BUF(name)
+#define BP_MARCH_PROF_ENTRY(name, wave)
+#define BP_MARCH_PROF_SETUP()
+#define BP_MARCH_PROF_ROW()
+#define BP_MARCH_PROF_PIECE_END()
+#define BP_MARCH_PROF_EXIT()
+#endif
 
 // Grid of a persistent march over n_ws pairs: `occ` workgroups per CU; small batches: waves of at least min_frames frames.
 inline int march_grid(int n_ws, int min_frames, int waves_per_wg, int occ, int n_cu) {

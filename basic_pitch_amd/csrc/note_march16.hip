@@ -32,7 +32,6 @@
 //     march's cut): 8 % halo rows instead of 28 %.
 // Roofline: f16 MFMA issue; 20 16x16x32 per 16 pixels (12 conv1 + 2 residual + 6 projection); HBM 182 KB read (through L2:
 // the three strips of a window overlap by 2 pixels, shares by 6 rows) and 61 KB written per window.
-#include <stdio.h>
 #include <stdlib.h>
 
 #include "bp_kernels.h"
@@ -50,6 +49,7 @@ constexpr int kN16Frags = 18;   // pack_note16
 #define N16_OCC 2
 #endif
 constexpr int kN16Occ = N16_OCC;  // resident workgroups per CU (x 4 waves: waves per SIMD)
+constexpr int kN16Prio = 45;      // march_common.h: a second-half wave takes the issue priority at 45 % of its rows
 static_assert(kN16Strips * 30 >= kFreqN, "strips cover a row");
 static_assert(kN16Row % 16 == 0, "conflict-free ds_read_b128: rows differ by a multiple of 16 units");
 
@@ -59,7 +59,9 @@ struct Note16Params {
   const float* contour;  // [n][172][264]
   float* out;            // [n][172][88]
   int n_ws;              // n_windows * kN16Strips (window, strip) pairs of 172 frames each
+  int prio;              // march_common.h BP_MARCH_PRIO_*: the rule by which the two waves of a SIMD share the issue priority
 };
+BP_MARCH_PROF_BUF(bp_prof_note)
 
 template <int V>
 struct N16Phase {
@@ -75,11 +77,7 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
   const int g = lane >> 4, n = lane & 15;
   uint4* ring = lds[wave];
   uint2* ring2 = reinterpret_cast<uint2*>(ring);
-#ifdef N16_PROF  // tools only: 100 MHz stamps of a few waves (entry, set-up done, per share: prologue done, march done)
-  unsigned long long pt[8];
-  int npt = 0;
-  pt[npt++] = __builtin_amdgcn_s_memrealtime();
-#endif
+  BP_MARCH_PROF_ENTRY(bp_prof_note, wave)
 
   // resident A operands (pack_note16): conv1 [kind H = hi 2^11, h = hi, L = lo 2^11][k-step][block], conv2 [kind][block]
   uint4 a1H[2][2], a1h[2][2], a1L[2][2], a2H[2], a2h[2], a2L[2];
@@ -125,10 +123,7 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
   const int src_l4 = ((n + 15) & 15) * 4;         // ds_bpermute: pixel n - 1 of lane group 0
   const int src_r4 = (32 + ((n + 1) & 15)) * 4;   // pixel n + 1 of lane group 2
 
-#ifdef N16_PROF
-  asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-  pt[npt++] = __builtin_amdgcn_s_memrealtime();
-#endif
+  BP_MARCH_PROF_SETUP();
   // work distribution: onset_march16.hip's (march_common.h: XCD-aware order; equal contiguous shares of the frames of all
   // (window, strip) pairs; at exactly 8 waves per window the three strips of a frame range are marched by neighbouring waves)
   const int total_waves = gridDim.x * kN16Waves;
@@ -138,10 +133,13 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
   // (profiles/r06_note_phases.md: with the onset march's cuts 64 | 65 | 43 the two-share waves ran 75 rows against 67)
   constexpr int kCut1 = 68, kCut2 = 133, kCut3 = 151;
   BP_MARCH_SHARES_STATE(gw, total_waves, p.n_ws, kN16Strips);
+  BP_MARCH_PRIO_ROWS(p.prio, kN16Strips, kCut1, kCut2, kCut3, 6, share_rows)  // a piece marches T0 - 3 .. T1 + 2
+  BP_MARCH_PRIO_STATE(p.prio, share_rows);
 #pragma unroll 1
   for (int pi = 0;; ++pi) {  // wave-uniform; no barriers
     int ws, T0, T1;
     BP_MARCH_SHARES_TAKE(kN16Strips, kCut1, kCut2, kCut3, break)
+    BP_MARCH_PRIO_PIECE(p.prio, T1 - T0 + 6)
     const int b = ws / kN16Strips, strip = ws - b * kN16Strips;
 
     // this lane's two pixels of the strip (tile nt: strip pixel 16 nt + n)
@@ -223,10 +221,6 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
       }
     };
     read_k(0, bh0, bl0);
-#ifdef N16_PROF
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    if (npt < 7) pt[npt++] = __builtin_amdgcn_s_memrealtime();
-#endif
     const float sig_k = -1.44269504088896341f * kLoUnscale;  // sigmoid((y + b) 2^-11) = 1 / (1 + exp2((y + b) sig_k))
     const int st_w0 = w[0], st_w1 = w[1];
 
@@ -237,6 +231,8 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
     auto step = [&](auto PH, int r) {
       constexpr int ph = decltype(PH)::v;
       const bool live = r >= 0 && r < kFrames;  // wave-uniform; a conv1 row outside the window is conv2's zero padding
+      BP_MARCH_PRIO_ROW();
+      BP_MARCH_PROF_ROW();
       f32x4 acc[2][2];
       f16x8 bh1[2], bl1[2];
       auto conv1_kstep = [&](int s, const f16x8 (&bh)[2], const f16x8 (&bl)[2]) {
@@ -388,25 +384,19 @@ __global__ __launch_bounds__(64 * kN16Waves, kN16Occ) void note_march16_kernel(N
       if (++r > r_last) break;
     }
     wave_lds_fence();  // the next piece's prologue overwrites the ring
-#ifdef N16_PROF
-    if (npt < 7) pt[npt++] = __builtin_amdgcn_s_memrealtime();
-#endif
+    BP_MARCH_PROF_PIECE_END();
   }
-#ifdef N16_PROF
-  pt[npt++] = __builtin_amdgcn_s_memrealtime();
-  if (lane == 0 && p.n_ws >= 768 && (gw < 8 || gw == 1003 || gw == 1006 || gw == 2040 || gw == 2047))
-    printf("N16P gw %d block %d t0 %llu setup %llu | %llu %llu %llu %llu | end %llu\n", gw, (int)blockIdx.x, pt[0] % 100000000ull, pt[1] - pt[0],
-           npt > 3 ? pt[2] - pt[0] : 0ull, npt > 3 ? pt[3] - pt[0] : 0ull, npt > 5 ? pt[4] - pt[0] : 0ull, npt > 5 ? pt[5] - pt[0] : 0ull, pt[npt - 1] - pt[0]);
-#endif
+  BP_MARCH_PROF_EXIT();
 }
 
 void launch_note_march16(const float* contour, const void* wfrag, const float* wf32, float* note, int n_windows, int n_cu,
                          bool weights_have_lo, hipStream_t stream) {
   // two resident workgroups per CU, persistent; small batches: fewer waves, at least kMinFrames frames each
-  Note16Params p{static_cast<const uint4*>(wfrag), wf32, contour, note, n_windows * kN16Strips};
+  Note16Params p{static_cast<const uint4*>(wfrag), wf32, contour, note, n_windows * kN16Strips, 0};
   if (p.n_ws <= 0) return;
   constexpr int kMinFrames = 12;
   const int grid = march_grid(p.n_ws, kMinFrames, kN16Waves, kN16Occ, n_cu);
+  p.prio = march_prio(kN16Prio, grid, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(note_march16_kernel<true>, dim3(grid), dim3(64 * kN16Waves), 0, stream, p);
   else

@@ -47,6 +47,7 @@ constexpr int kO16KS = kOnset16KSteps;         // 7 (bp_common.h: the tap table 
 #define BP_ONSET16_PF 1
 #endif
 constexpr int kO16Pf = BP_ONSET16_PF;          // k-steps of image fragments read ahead of the matrix instructions
+constexpr int kO16Prio = 45;                   // march_common.h: a second-half wave takes the issue priority at 45 % of its rows
 static_assert(kO16Strips * 30 >= kFreqN, "strips cover a row");
 static_assert(kO16Lo >= kO16Slots && 2 * kO16Lo <= kO16Row && kO16Row % 16 == 0, "ring geometry");
 
@@ -57,7 +58,9 @@ struct Onset16Params {
   const float* note;    // [n][172][88]
   float* out;           // [n][172][88]
   int n_ws;             // n_windows * kO16Strips (window, strip) pairs of 172 frames each
+  int prio;             // march_common.h BP_MARCH_PRIO_*: the rule by which the two waves of a SIMD share the issue priority
 };
+BP_MARCH_PROF_BUF(bp_prof_onset)
 
 template <bool WLO>
 __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset16Params p) {
@@ -67,6 +70,7 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
   const int wave = wave_id();
   const int g = lane >> 4, n = lane & 15;
   uint4* ring = lds[wave];
+  BP_MARCH_PROF_ENTRY(bp_prof_onset, wave)
 
   // resident A operands and constants
   uint4 a1h[kO16KS][2], a1l[WLO ? kO16KS : 1][2], a2h, a2l;
@@ -115,6 +119,7 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
   const int at04 = 3 * n + onset16_dw(0, g);
   const int at56 = 3 * n + 2;
 
+  BP_MARCH_PROF_SETUP();
   const int total_waves = gridDim.x * kO16Waves;
   // Work = the frames of all (window, strip) pairs, in the XCD-aware order of workgroups; every wave takes an equal share
   // of them as at most two marches (march_common.h: BP_MARCH_SHARES_TAKE.  Round 4: three tasks of an eighth of a window-strip each
@@ -124,10 +129,13 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
   const int gw = BP_XCD_LOGICAL_BLOCK() * kO16Waves + wave;
   constexpr int kCut1 = 64, kCut2 = 129, kCut3 = 150;  // 64 | 65 | 43 = 21 + 22
   BP_MARCH_SHARES_STATE(gw, total_waves, p.n_ws, kO16Strips);
+  BP_MARCH_PRIO_ROWS(p.prio, kO16Strips, kCut1, kCut2, kCut3, 2, share_rows)  // a piece marches T0 - 1 .. T1
+  BP_MARCH_PRIO_STATE(p.prio, share_rows);
 #pragma unroll 1
   for (int pi = 0;; ++pi) {  // wave-uniform; no barriers
     int ws, T0, T1;
     BP_MARCH_SHARES_TAKE(kO16Strips, kCut1, kCut2, kCut3, break)
+    BP_MARCH_PRIO_PIECE(p.prio, T1 - T0 + 2)
     const int b = ws / kO16Strips, strip = ws - b * kO16Strips;
 
     // this lane's two pixels of the strip (tile nt: strip pixel 16 nt + n), and the stack bin of image slot 0
@@ -311,6 +319,8 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
     int slot_m2 = 0;            // ring slot of image row r - 2
 #pragma unroll 1
     for (int r = r_first; r <= T1; ++r) {
+      BP_MARCH_PRIO_ROW();
+      BP_MARCH_PROF_ROW();
       uint32_t st[16];
       int slot_p3 = slot_m2 + 5;  // row r + 3 takes the slot of row r - 3
       slot_p3 = slot_p3 >= kO16Ring ? slot_p3 - kO16Ring : slot_p3;
@@ -338,16 +348,19 @@ __global__ __launch_bounds__(64 * kO16Waves, 2) void onset_march16_kernel(Onset1
       stage_commit(slot_p3, st);
       slot_m2 = slot_m2 + 1 == kO16Ring ? 0 : slot_m2 + 1;
     }
+    BP_MARCH_PROF_PIECE_END();
   }
+  BP_MARCH_PROF_EXIT();
 }
 
 void launch_onset_march16(const uint32_t* zp, const float* note, const void* wfrag, const float* wf32, float* onset,
                           int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
   // two resident workgroups per CU (LDS), persistent; small batches: fewer waves, at least kMinFrames frames each
-  Onset16Params p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows * kO16Strips};
+  Onset16Params p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows * kO16Strips, 0};
   if (p.n_ws <= 0) return;
   constexpr int kMinFrames = 6;
   const int grid = march_grid(p.n_ws, kMinFrames, kO16Waves, 2, n_cu);
+  p.prio = march_prio(kO16Prio, grid, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(onset_march16_kernel<true>, dim3(grid), dim3(64 * kO16Waves), 0, stream, p);
   else
