@@ -201,6 +201,40 @@ class bp_sweep_decode(C.Structure):
     ]
 
 
+class bp_ref_note(C.Structure):
+    """A reference note (include/basic_pitch_amd_score.h): seconds from the start of its segment, a MIDI pitch that may be fractional."""
+
+    _fields_ = [
+        ("start_s", C.c_double),
+        ("end_s", C.c_double),
+        ("pitch_midi", C.c_double),
+    ]
+
+
+class bp_score_params(C.Structure):
+    """The tolerances of note-level scoring (include/basic_pitch_amd_score.h); `bp_score_params_default` fills in mir_eval's."""
+
+    _fields_ = [
+        ("onset_tolerance_s", C.c_double),
+        ("offset_ratio", C.c_double),
+        ("offset_min_tolerance_s", C.c_double),
+        ("pitch_tolerance_cents", C.c_double),
+        ("strict", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class bp_note_score(C.Structure):
+    """The counts of one scored decode (include/basic_pitch_amd_score.h)."""
+
+    _fields_ = [
+        ("n_ref", C.c_int32),
+        ("n_est", C.c_int32),
+        ("matched_onset", C.c_int32),
+        ("matched_offset", C.c_int32),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -332,6 +366,13 @@ EVENTS_SYMBOLS = [
 SWEEP_SYMBOLS = [
     "bp_note_events_sweep",
     "bp_infer_clips_events_sweep",
+]
+# every symbol include/basic_pitch_amd_score.h declares (bound in basic_pitch_amd/score.py)
+SCORE_SYMBOLS = [
+    "bp_score_params_default",
+    "bp_score_note_events",
+    "bp_note_events_sweep_score",
+    "bp_infer_clips_events_sweep_score",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

@@ -99,6 +99,13 @@ struct bp_context {
   Buffer<float> sw_note, sw_onset;
   Buffer<uint8_t> sw_bits;
   Table sw_stats, sw_tab;
+  // a scored sweep (bp_note_events_sweep_score, clips_api.hip queue_sweep), all grow-only, scratch of one call and grown by the
+  // score calls alone: the refs of all segments, per decode which of them are its segment's, the scores [decodes][4] with the
+  // statuses [decodes] behind them, and the page-locked block they come home in
+  Buffer<bp::NoteScoreRef> sc_refs;
+  Buffer<bp::NoteScoreDecode> sc_dec;
+  Buffer<int32_t> sc_out;
+  bp::PinnedBuffer<int32_t> sc_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.
@@ -234,7 +241,8 @@ struct TrackInputs {
 // The handle's buffers grown to the job (nothing queued); the tracker, the pack and the offsets on their way home; and, after
 // the wait, the offsets and status, the events and bends home in one copy each and the frame-to-time arithmetic.
 // *device_error (may be null) is set where events_home fails after queuing; buffers too small is not such a failure.
-int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan);
+// home false: the events stay in the pool (a scored sweep) — no bends, no packed copies, no offsets.
+int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan, bool home = true);
 int events_queue(bp_handle h, const EventsJob& job, const EventsPlan& plan, const TrackInputs& in);
 int events_home(bp_handle h, const EventsJob& job, const EventsSink& out, bool* device_error);
 }  // namespace bp

@@ -250,6 +250,35 @@ struct NoteSweepDecode {
 hipError_t launch_note_track_sweep(const NoteSweepDecode* tab, int64_t n_decodes, int64_t max_rows, const int8_t* bend_map,
                                    const int64_t* pool_rows, const int64_t* ev_first, float* scratch, void* ev_pool, int8_t* bd_pool,
                                    void* counts, int64_t* meta, void* ev_out, int8_t* bd_out, hipStream_t s);
+// meta null: the tracker alone — no offsets, no pack, ev_out and bd_out unused; the events stay in the decodes' regions of
+// ev_pool with their counts and statuses in `counts` (16 bytes per decode: events, bends, status, 0) for launch_note_score.
+
+// note_score.hip: the decodes of a sweep scored against reference notes in place (bp_note_events_sweep_score,
+// include/basic_pitch_amd_score.h), one workgroup per decode behind launch_note_track_sweep(meta = null).  refs: the table of
+// all segments' refs with the offset tolerance each ref sets; dec[j]: the refs of decode j's segment.  prm: the tolerances the
+// predicates compare against.  max_refs / max_depth size the launch's LDS (note_score_lds_bytes): every decode has at most
+// max_refs refs or more than kNoteScoreMaxNotes (status 3), and min(events its region holds, refs + 1) <= max_depth.
+// out: [n_decodes] {n_ref, n_est, matched_onset, matched_offset}, then [n_decodes] status.
+constexpr int kNoteScoreMaxNotes = 16384;  // BP_SCORE_MAX_NOTES
+struct NoteScoreRef {
+  double start_s, end_s, pitch_midi;
+  double offset_tol;  // max(offset_ratio * (end_s - start_s), offset_min_tolerance_s)
+};
+struct NoteScoreDecode {
+  int64_t ref_first;
+  int32_t n_ref;      // at most kNoteScoreMaxNotes + 1 (more: the same status)
+  int32_t bend_room;  // 88 * rows where the decode's set asks for bends, else -1.  No bends are made, but a decode whose
+                      // events span more frames than its bend region would hold is the sweep calls' status 2: the tracker
+                      // stops at the event that passes the room, and the lengths being positive, that is when the sum does
+};
+struct NoteScoreParams {
+  double onset_tol, pitch_tol;
+  int strict;
+};
+size_t note_score_lds_bytes(int max_refs, int max_depth);
+hipError_t launch_note_score(const void* counts, const int64_t* ev_first, const void* ev_pool, const NoteScoreDecode* dec,
+                             const NoteScoreRef* refs, const NoteScoreParams& prm, int64_t n_decodes, int max_refs, int max_depth,
+                             int32_t* out, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

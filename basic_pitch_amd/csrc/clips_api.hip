@@ -18,6 +18,7 @@
 
 #include "../../include/basic_pitch_amd_adpcm.h"
 #include "../../include/basic_pitch_amd_flac_clips.h"
+#include "../../include/basic_pitch_amd_score.h"
 #include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
@@ -25,6 +26,9 @@ using namespace bp;
 
 extern "C" void bp_internal_freq_limits(const bp_note_params* prm, int* lo, int* hi);
 extern "C" double bp_internal_frame_time(int64_t frame);
+extern "C" const char* bp_internal_score_bad_params(const bp_score_params* p);
+extern "C" int64_t bp_internal_score_bad_ref(const bp_ref_note* refs, int64_t n);
+extern "C" double bp_internal_score_offset_tol(const bp_ref_note* r, const bp_score_params* p);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 namespace bp {
@@ -34,7 +38,7 @@ static bool seg_bends(const EventsJob& job, int64_t c) {
   return job.seg ? job.seg[c].bends != 0 : job.prm->include_pitch_bends != 0;
 }
 
-int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan) {
+int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan, bool home) {
   const int64_t n = job.n, T = job.offs[n];
   plan->ev_first.assign((size_t)n + 1, 0);
   plan->max_rows = 0;
@@ -47,14 +51,15 @@ int events_reserve(bp_handle h, const EventsJob& job, EventsPlan* plan) {
   const int64_t pool_events = plan->ev_first[(size_t)n], n_meta = 3 * n + 2;
   const bool scratch = plan->max_rows > kNoteTrackLdsRows || job.form == kNoteTrackFormScratch;
   BP_HIP(h->ev_first.reserve((size_t)n + 1));
-  BP_HIP(h->ev_meta.reserve((size_t)n_meta));
   BP_HIP(h->ev_counts.reserve((size_t)n * 16));
   BP_HIP(h->ev_pool.reserve((size_t)pool_events * 16));
+  if (scratch) BP_HIP(h->ev_scratch.reserve((size_t)note_track_scratch_floats(T)));
+  if (job.seg) BP_HIP(h->ev_seg.reserve((size_t)n * sizeof(NoteTrackSeg)));
+  if (!home) return BP_OK;
+  BP_HIP(h->ev_meta.reserve((size_t)n_meta));
   BP_HIP(h->ev_out.reserve((size_t)pool_events * 16));
   BP_HIP(h->bd_pool.reserve((size_t)T * 88));
   BP_HIP(h->bd_out.reserve((size_t)T * 88));
-  if (scratch) BP_HIP(h->ev_scratch.reserve((size_t)note_track_scratch_floats(T)));
-  if (job.seg) BP_HIP(h->ev_seg.reserve((size_t)n * sizeof(NoteTrackSeg)));
   BP_HIP(h->ev_home.reserve((size_t)n_meta));  // page-locked: the offsets and status come home first
   return BP_OK;
 }
@@ -497,8 +502,9 @@ struct JobSource {
 // track_out; kEventsHome: the events (out).  params: of the dense half, and of the tracker unless seg_params gives every
 // segment its own (with the tracker's form and the call's name for n: the A/B hook).  kSweepHome: the events (out) of n_decodes
 // decodes, decode j segment decodes[j].segment under sets[decodes[j].params] (decodes null: the cross product, set-major);
-// params is null, every set has its own dense half.
-enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome };
+// params is null, every set has its own dense half.  kScoreHome: the same sweep, but what goes home is `scores` and out.status
+// alone — every decode's events scored on the device against the refs of its segment (include/basic_pitch_amd_score.h).
+enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome };
 struct JobSink {
   JobSinkKind kind;
   const bp_note_params* params;
@@ -512,6 +518,10 @@ struct JobSink {
   int64_t n_sets, n_decodes;
   const bp_note_params* sets;
   const bp_sweep_decode* decodes;
+  const int64_t* ref_offsets;  // kScoreHome: [n segments + 1], the refs of each segment
+  const bp_ref_note* refs;
+  const bp_score_params* score_params;
+  bp_note_score* scores;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -529,6 +539,14 @@ JobSink sweep_sink(int64_t n_sets, const bp_note_params* sets, int64_t n_decodes
   JobSink k = events_sink(nullptr, events, max_events, bends, max_bends, event_offsets, status);
   k.kind = kSweepHome, k.count_name = "n_decodes";
   k.n_sets = n_sets, k.n_decodes = n_decodes, k.sets = sets, k.decodes = decodes;
+  return k;
+}
+
+JobSink score_sink(int64_t n_sets, const bp_note_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes, const int64_t* ref_offsets,
+                   const bp_ref_note* refs, const bp_score_params* score_params, bp_note_score* scores, int* status) {
+  JobSink k = sweep_sink(n_sets, sets, n_decodes, decodes, nullptr, 0, nullptr, 0, nullptr, status);
+  k.kind = kScoreHome;
+  k.ref_offsets = ref_offsets, k.refs = refs, k.score_params = score_params, k.scores = scores;
   return k;
 }
 
@@ -551,14 +569,42 @@ struct SweepJob {
   int64_t n_bands = 0;              // constrained copies of the note rows
   bool bends = false;               // a decode that reaches the tracker wants bends
   std::vector<uint8_t> block;       // the decode table (NoteSweepDecode) with pool_rows and the event regions behind it
+  // kScoreHome: the refs as the device reads them, per decode which are its segment's, the room the launch's LDS needs
+  std::vector<NoteScoreRef> refs;
+  std::vector<NoteScoreDecode> ref_of;
+  int max_refs = 0, max_depth = 0;
 };
+
+// what a scored sweep takes beside a sweep's arguments, before anything is queued
+int check_score(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (!k.ref_offsets || (k.n_decodes > 0 && !k.scores)) return invalid("null ref_offsets or scores");
+  if (const char* why = bp_internal_score_bad_params(k.score_params)) return invalid(why);
+  if (k.ref_offsets[0] != 0) return invalid("ref_offsets must start at 0");
+  for (int64_t i = 0; i < n_segs; ++i)
+    if (k.ref_offsets[i + 1] < k.ref_offsets[i])
+      return invalid("segment " + std::to_string(i) + ": ref_offsets decrease (" + std::to_string(k.ref_offsets[i]) + " to " +
+                     std::to_string(k.ref_offsets[i + 1]) + ")");
+  if (k.ref_offsets[n_segs] > 0 && !k.refs) return invalid("null refs");
+  const int64_t bad = bp_internal_score_bad_ref(k.refs, k.ref_offsets[n_segs]);
+  if (bad >= 0) return invalid("ref " + std::to_string(bad) + ": a field is not finite, or end_s < start_s");
+  return BP_OK;
+}
+
+// decode j of a scored sweep without events: {n_ref, 0, 0, 0} (its segment: seg)
+void score_nothing(const JobSink& k, int64_t j, int64_t seg) {
+  const int64_t n_ref = k.ref_offsets[seg + 1] - k.ref_offsets[seg];
+  k.scores[j] = bp_note_score{(int32_t)std::min<int64_t>(n_ref, INT32_MAX), 0, 0, 0};
+}
 
 // every argument of a sweep that is not a segment's, before anything is queued
 int check_sweep(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
   auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
-  if (n_segs < 0 || k.n_sets < 0 || k.n_decodes < 0 || (k.n_sets > 0 && !k.sets) || !k.out.event_offsets || (k.n_decodes > 0 && !k.out.status))
+  const bool score = k.kind == kScoreHome;  // no events go home: no offsets, no room
+  if (n_segs < 0 || k.n_sets < 0 || k.n_decodes < 0 || (k.n_sets > 0 && !k.sets) || (!score && !k.out.event_offsets) ||
+      (k.n_decodes > 0 && !k.out.status))
     return invalid("negative n_segments / n_clips, n_sets or n_decodes, null sets, event_offsets or status");
-  if (const char* why = bad_room(k.out)) return invalid(why);
+  if (const char* why = score ? nullptr : bad_room(k.out)) return invalid(why);
   if (k.n_decodes > BP_SWEEP_MAX_DECODES)
     return invalid(std::to_string(k.n_decodes) + " decodes, more than BP_SWEEP_MAX_DECODES (" + std::to_string(BP_SWEEP_MAX_DECODES) +
                    "): split the job");
@@ -585,6 +631,7 @@ int check_sweep(bp_handle h, const char* what, int64_t n_segs, const JobSink& k)
 // as events_without_device says it) — and the outputs are complete.
 int plan_sweep(bp_handle h, const char* what, int64_t n_segs, const int64_t* offs, const JobSink& k, SweepJob* w, bool* queued) {
   const int64_t n = k.n_decodes;
+  const bool score = k.kind == kScoreHome;
   w->segment.resize((size_t)n), w->params.resize((size_t)n), w->seg.resize((size_t)n);
   w->pool_rows.assign((size_t)n + 1, 0);
   w->set_key.assign((size_t)k.n_sets, -1);
@@ -602,7 +649,7 @@ int plan_sweep(bp_handle h, const char* what, int64_t n_segs, const int64_t* off
     w->pool_rows[(size_t)j + 1] = w->pool_rows[(size_t)j] + rows;
     if (rows == 0 || skip) continue;
     *queued = true;
-    w->bends = w->bends || prm.include_pitch_bends != 0;
+    w->bends = w->bends || (prm.include_pitch_bends != 0 && !score);  // (a scored sweep counts the bends and makes none)
     if (w->set_key[(size_t)p] >= 0) continue;
     int lo = 0, hi = 88;
     bp_internal_freq_limits(&prm, &lo, &hi);
@@ -613,8 +660,24 @@ int plan_sweep(bp_handle h, const char* what, int64_t n_segs, const int64_t* off
                                 std::to_string(BP_SWEEP_MAX_ROWS) + "): split the job");
   if (!*queued) {
     for (int64_t j = 0; j < n; ++j) k.out.status[j] = w->pool_rows[(size_t)j + 1] > w->pool_rows[(size_t)j] ? 1 : 0;
-    for (int64_t j = 0; j <= n; ++j) k.out.event_offsets[j] = 0;
+    for (int64_t j = 0; j <= n && !score; ++j) k.out.event_offsets[j] = 0;
+    for (int64_t j = 0; j < n && score; ++j) score_nothing(k, j, w->segment[(size_t)j]);
     return BP_OK;
+  }
+  if (score) {  // the refs as the device reads them; which are whose
+    const int64_t n_refs = k.ref_offsets[n_segs];
+    w->refs.resize((size_t)n_refs);
+    for (int64_t i = 0; i < n_refs; ++i) {
+      const bp_ref_note& r = k.refs[i];
+      w->refs[(size_t)i] = NoteScoreRef{r.start_s, r.end_s, r.pitch_midi, bp_internal_score_offset_tol(&r, k.score_params)};
+    }
+    w->ref_of.resize((size_t)n);
+    for (int64_t j = 0; j < n; ++j) {
+      const int64_t seg = w->segment[(size_t)j], first = k.ref_offsets[seg];
+      const int64_t rows = w->pool_rows[(size_t)j + 1] - w->pool_rows[(size_t)j];
+      w->ref_of[(size_t)j] = NoteScoreDecode{first, (int32_t)std::min<int64_t>(k.ref_offsets[seg + 1] - first, kNoteScoreMaxNotes + 1),
+                                             w->seg[(size_t)j].bends && rows <= kNoteTrackMaxRows ? (int32_t)(88 * rows) : -1};
+    }
   }
   // the keys in the map's order, which keeps a band's keys together; a set's key by that order
   std::vector<int> order(keys.size());
@@ -639,7 +702,8 @@ struct ClipsJob {
   std::vector<ClipDesc> tab;
   std::vector<NoteTrackSeg> seg;
   bool dense_bends = false;                    // kEventsHome: the dense half makes the bend map
-  SweepJob sweep;                              // kSweepHome
+  SweepJob sweep;                              // kSweepHome, kScoreHome
+  const bp_score_params* score_params = nullptr;  // kScoreHome
   EventsJob ev{};
   EventsPlan plan;
   bool exported_by_kernel = false;
@@ -650,7 +714,9 @@ struct ClipsJob {
 // it is reused from band to band), then the stats and the bitmap of every segment as the clips calls make them, into the key's
 // own blocks — and the bend map once; the tracker over the decode table; the offsets on their way home.  The maps
 // themselves are only read.  The records are in h->sw_stats, not the clips calls' h->clip_stats, whose state stays as it was.
-int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* offs, ClipsJob& job) {
+// score: no bend map, the tracker without its offsets and pack launches, then the scoring launch over the events where they
+// lie (note_score.hip) and the scores with the statuses on their way home.
+int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* offs, ClipsJob& job, bool score) {
   hipStream_t s = h->stream;
   SweepJob& w = job.sweep;
   const int64_t T = offs[n_segs], n = job.ev.n, n_keys = (int64_t)w.keys.size();
@@ -693,6 +759,24 @@ int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* off
   const int64_t* d_rows = reinterpret_cast<const int64_t*>(h->sw_tab + tab_bytes);
   BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n_segs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
   BP_HIP(hipMemcpyAsync(h->sw_tab, w.block.data(), w.block.size(), hipMemcpyHostToDevice, s));
+  if (score) {
+    // The LDS of the scoring launch: the most refs a decode it scores can have, the deepest its path can get — min(events,
+    // refs + 1), the events bounded by what the decode's region of the pool holds.  Its tables go with the tracker's.
+    for (int64_t j = 0; j < n; ++j) {
+      const int n_ref = w.ref_of[(size_t)j].n_ref;
+      if (n_ref > kNoteScoreMaxNotes) continue;  // status 3: never searched
+      const int64_t room = job.plan.ev_first[(size_t)j + 1] - job.plan.ev_first[(size_t)j];
+      w.max_refs = std::max(w.max_refs, n_ref);
+      w.max_depth = std::max(w.max_depth, (int)std::min<int64_t>({room, (int64_t)n_ref + 1, (int64_t)kNoteScoreMaxNotes}));
+    }
+    BP_HIP(h->sc_refs.reserve(w.refs.size()));
+    BP_HIP(h->sc_dec.reserve((size_t)n));
+    BP_HIP(h->sc_out.reserve((size_t)(5 * n)));
+    BP_HIP(h->sc_home.reserve((size_t)(5 * n)));
+    if (!w.refs.empty())
+      BP_HIP(hipMemcpyAsync(h->sc_refs, w.refs.data(), w.refs.size() * sizeof(NoteScoreRef), hipMemcpyHostToDevice, s));
+    BP_HIP(hipMemcpyAsync(h->sc_dec, w.ref_of.data(), (size_t)n * sizeof(NoteScoreDecode), hipMemcpyHostToDevice, s));
+  }
   launch_clips_stats_init(h->sw_stats, n_keys * n_segs, s);
   int made = 0;  // bands whose copies exist; sw_onset holds the last one's
   for (int64_t i = 0; i < n_keys; ++i) {
@@ -706,6 +790,16 @@ int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* off
                             h->sw_stats + i * stats_block, h->sw_bits + i * bits_plane, i == 0 ? d_bend : nullptr, s);
   }
   BP_HIP(hipGetLastError());
+  if (score) {  // the events stay where the tracker leaves them: one more launch, and 20 bytes per decode go home
+    BP_HIP(launch_note_track_sweep(h->sw_tab.as<NoteSweepDecode>(), n, job.plan.max_rows, nullptr, d_rows, d_rows + n + 1, h->ev_scratch,
+                                   h->ev_pool, nullptr, h->ev_counts, nullptr, nullptr, nullptr, s));
+    const bp_score_params& p = *job.score_params;
+    BP_HIP(launch_note_score(h->ev_counts, d_rows + n + 1, h->ev_pool, h->sc_dec, h->sc_refs,
+                             NoteScoreParams{p.onset_tolerance_s, p.pitch_tolerance_cents, p.strict != 0}, n, w.max_refs, w.max_depth,
+                             h->sc_out, s));
+    BP_HIP(hipMemcpyAsync(h->sc_home, h->sc_out, (size_t)(5 * n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    return BP_OK;
+  }
   BP_HIP(launch_note_track_sweep(h->sw_tab.as<NoteSweepDecode>(), n, job.plan.max_rows, d_bend, d_rows, d_rows + n + 1, h->ev_scratch,
                                  h->ev_pool, h->bd_pool, h->ev_counts, h->ev_meta, h->ev_out, h->bd_out, s));
   BP_HIP(hipMemcpyAsync(h->ev_home, h->ev_meta, (size_t)(3 * n + 2) * sizeof(int64_t), hipMemcpyDeviceToHost, s));
@@ -747,8 +841,9 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
     return queue_clips_candidates(h, all, s.n, job.offs, k.params, k.note_out, k.cand_bits, k.bend_map, &job.exported_by_kernel);
   uint8_t* d_bits = nullptr;
   int8_t* d_bend = nullptr;
-  if ((rc = events_reserve(h, job.ev, &job.plan))) return rc;
-  if (k.kind == kSweepHome) return queue_sweep(h, all, s.n, job.offs, job);
+  const bool score = k.kind == kScoreHome;
+  if ((rc = events_reserve(h, job.ev, &job.plan, !score))) return rc;
+  if (k.kind == kSweepHome || score) return queue_sweep(h, all, s.n, job.offs, job, score);
   if ((rc = queue_clips_dense(h, all, s.n, job.offs, k.params, job.dense_bends, &d_bits, &d_bend))) return rc;
   return events_queue(h, job.ev, job.plan, TrackInputs{all.note, d_bits, d_bend, h->clip_rows, h->clip_stats});
 }
@@ -757,17 +852,20 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   if (!h) return BP_ERR_INVALID_ARG;
   auto invalid = [&](const char* why) { return ::invalid(h, what, why); };
   const int64_t n = src.n;
-  const bool flac = src.kind == kFlacClips, sweep = k.kind == kSweepHome, events = k.kind == kEventsHome || sweep;
+  const bool flac = src.kind == kFlacClips, score = k.kind == kScoreHome, sweep = k.kind == kSweepHome || score;
+  const bool events = k.kind == kEventsHome || sweep;
   int rc = BP_OK;
   // the sink's fixed arguments
   if (events) {
     if ((rc = sweep ? check_sweep(h, what, n, k) : check_events(h, what, n, k.params, k.out))) return rc;
+    if (score && (rc = check_score(h, what, n, k))) return rc;
     if (flac && src.sample_rate < 1) return invalid("no sample rate");
   } else if (!k.params || (n > 0 && !k.out.status) || (flac && src.sample_rate < 1)) {
     return invalid(flac ? "null params / status or no sample rate" : "null params / status");
   }
   // the source's plan (every argument of every segment, its rows), the outputs against the rows
   ClipsJob job;
+  job.score_params = k.score_params;
   if (src.kind == kGivenMaps) {
     bool ordered = n >= 0 && src.row_offsets && src.row_offsets[0] == 0;
     for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
@@ -823,6 +921,10 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
     if (job.exported_by_kernel) h->clip_stats_ready = n;  // only now: the export kernel, which re-initialises the records, has run
     for (int64_t i = 0; i < n; ++i)
       k.out.status[i] = job.offs[i + 1] > job.offs[i] && (h->clip_stats_host[4 * i + 1] || !(k.params->onset_threshold > 0.0)) ? 1 : 0;
+  } else if (score) {  // the stream has drained: the scores and the statuses are in the page-locked block
+    if (rc) return rc;
+    std::memcpy(k.scores, h->sc_home, (size_t)k.n_decodes * sizeof(bp_note_score));
+    for (int64_t j = 0; j < k.n_decodes; ++j) k.out.status[j] = h->sc_home[4 * k.n_decodes + j];
   } else if (rc || (rc = events_home(h, job.ev, k.out, nullptr))) {
     // (buffers too small: status and event_offsets are complete but for the decoder's verdicts)
     if (flac) flac_clips_status(h, job.flac, false, k.out.status);
@@ -879,6 +981,23 @@ int bp_infer_clips_events_sweep(bp_handle h, int64_t n_clips, const bp_clip* cli
                                 int64_t max_events, int32_t* bends, int64_t max_bends, int64_t* event_offsets, int* status) {
   return run_clips(h, "bp_infer_clips_events_sweep", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
                    sweep_sink(n_sets, sets, n_decodes, decodes, events, max_events, bends, max_bends, event_offsets, status));
+}
+
+// ---- a scored sweep (include/basic_pitch_amd_score.h) -----------------------------------------------------------------------------
+int bp_note_events_sweep_score(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* note, const float* onset,
+                               const float* contour, int mem_kind, int64_t n_sets, const bp_note_params* sets, int64_t n_decodes,
+                               const bp_sweep_decode* decodes, const int64_t* ref_offsets, const bp_ref_note* refs,
+                               const bp_score_params* score_params, bp_note_score* scores, int* status) {
+  return run_clips(h, "bp_note_events_sweep_score", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, note, onset, contour},
+                   score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, status));
+}
+
+int bp_infer_clips_events_sweep_score(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                                      int64_t n_sets, const bp_note_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                                      const int64_t* ref_offsets, const bp_ref_note* refs, const bp_score_params* score_params,
+                                      bp_note_score* scores, int* status) {
+  return run_clips(h, "bp_infer_clips_events_sweep_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, status));
 }
 
 #ifdef BP_AB_KERNELS

@@ -445,7 +445,7 @@ int64_t note_track_scratch_floats(int64_t total_rows) { return total_rows * kNtR
 
 // The tracker's launches for either kind of segment: the LDS form sized by the longest segment that takes it (a job of
 // one-window clips runs three workgroups per compute unit), the scratch form where a segment is longer (lds_limit 0: for every
-// segment), each with the stacks its longest segment needs; then the second step.  extra: what a kernel takes between the
+// segment), each with the stacks its longest segment needs; then the second step (meta null: none).  extra: what a kernel takes between the
 // arguments and lds_rows.
 template <class Kernel, class... Extra>
 static hipError_t nt_launch(Kernel lds, Kernel scratch, const NtArgs& a, int64_t n, int64_t max_rows, int lds_limit, int64_t* meta,
@@ -458,6 +458,7 @@ static hipError_t nt_launch(Kernel lds, Kernel scratch, const NtArgs& a, int64_t
   hipLaunchKernelGGL(lds, dim3((unsigned)n), dim3(256), lds_bytes, s, a, extra..., lds_rows, depth);
   if (max_rows > lds_limit)
     hipLaunchKernelGGL(scratch, dim3((unsigned)n), dim3(256), (size_t)2 * deep * 64 * 4, s, a, extra..., lds_rows, deep);
+  if (!meta) return hipGetLastError();  // the events stay in the pool (launch_note_track_sweep for launch_note_score)
   hipLaunchKernelGGL(nt_offsets_kernel, dim3(1), dim3(256), 0, s, a.counts, n, meta);
   hipLaunchKernelGGL(nt_pack_kernel, dim3((unsigned)n), dim3(256), 0, s, a.counts, a.offs, a.ev_first, meta, n,
                      reinterpret_cast<const int4*>(a.ev_pool), a.bd_pool, static_cast<int4*>(ev_out), bd_out);

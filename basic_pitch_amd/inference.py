@@ -518,6 +518,27 @@ class Model:
 
         return _sweep.transcribe_clips_sweep(self, clips, sample_rates, params)
 
+    def sweep_note_scores(self, outputs: Sequence[Dict[str, Any]], params: Sequence[Any], refs: Sequence[Any],
+                          pairs: "Optional[Sequence[Tuple[int, int]]]" = None, **tolerances: Any):
+        """The segments `outputs` decoded under every set of `params` as by `sweep_note_events`, and every decode scored on
+        the device against `refs` — per segment a sequence of (start_s, end_s, pitch_midi) or an (n, 3) array — in ONE call
+        (`bp_note_events_sweep_score`): no event comes home, only the counts.  Returns a structured array with the fields
+        n_ref, n_est, matched_onset, matched_offset, status, shaped (sets, segments), or (len(pairs),) with `pairs`;
+        `score.precision_recall_f1` and `score.best_set` read it.  `tolerances`: the fields of `bp_score_params`
+        (mir_eval's defaults).  A decode the device leaves (status != 0) is scored on the host; its status stays."""
+        from . import score as _score
+
+        return _score.sweep_note_scores(self, outputs, params, refs, pairs, **tolerances)
+
+    def transcribe_clips_sweep_scores(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Sequence[Any],
+                                      refs: Sequence[Any], pairs: "Optional[Sequence[Tuple[int, int]]]" = None, **tolerances: Any):
+        """The same behind the model, for many short clips (as for `transcribe_clips_sweep`): the clips of a rate go through
+        the model once (`bp_infer_clips_events_sweep_score`), and what comes home is the structured array of
+        `sweep_note_scores`, a segment being a clip."""
+        from . import score as _score
+
+        return _score.transcribe_clips_sweep_scores(self, clips, sample_rates, params, refs, pairs, **tolerances)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
