@@ -90,6 +90,18 @@ class bp_stage_buffers(C.Structure):
     ]
 
 
+class bp_launch_plan_out(C.Structure):
+    """What the launchers decide for one chunk (include/basic_pitch_amd.h: bp_launch_plan); every field an int32."""
+
+    _fields_ = [(name, C.c_int32) for name in (
+        "pyramid_one_launch", "pyramid_decimate_grid", "pyramid_decimate_grid_cap", "filterbank_fused", "filterbank_grid",
+        "conv1_chunks", "conv1_grid", "conv1_prio", "rim_march", "rim_items", "rim_per_side", "rim_items_max", "rim_items_min",
+        "rim_ring", "conv2_slots", "conv2_launches", "conv2_windows", "conv2_first_windows", "conv2_first_groups",
+        "conv2_first_slabs", "conv2_first_slab_rows", "conv2_first_grid", "conv2_last_windows", "conv2_last_groups",
+        "conv2_last_slabs", "conv2_last_slab_rows", "conv2_last_grid", "note_grid", "note_grid_cap", "note_prio", "note_aligned",
+        "note_share_spans_pairs", "onset_grid", "onset_grid_cap", "onset_prio", "onset_aligned", "onset_share_spans_pairs")]
+
+
 class bp_note_params(C.Structure):
     _fields_ = [
         ("onset_threshold", C.c_double),
@@ -293,6 +305,7 @@ EXPORTED_SYMBOLS = [
     "bp_get_info",
     "bp_get_stage_ms",
     "bp_run_stage",
+    "bp_launch_plan",
     "bp_pyramid_layout",
     "bp_version",
     "bp_device_count",
@@ -495,6 +508,8 @@ def load_library(path: Optional[str] = None) -> C.CDLL:
     lib.bp_get_stage_ms.restype = C.c_int
     lib.bp_run_stage.argtypes = [vp, C.c_int, C.POINTER(bp_stage_buffers), i64]
     lib.bp_run_stage.restype = C.c_int
+    lib.bp_launch_plan.argtypes = [i64, C.c_int, C.c_uint, C.POINTER(bp_launch_plan_out)]
+    lib.bp_launch_plan.restype = C.c_int
     lib.bp_pyramid_layout.argtypes = [C.c_int, C.POINTER(i64), C.POINTER(i64)]
     lib.bp_pyramid_layout.restype = C.c_int
     lib.bp_device_count.argtypes = []

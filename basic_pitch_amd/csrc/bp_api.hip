@@ -10,6 +10,8 @@
 #include <ctime>
 
 #include "bp_context.h"
+#include "cqt_planes.h"
+#include "launch_plan.h"
 #include "weight_pack.h"
 
 namespace bp {
@@ -607,6 +609,58 @@ int bp_run_stage(bp_handle h, int stage, const bp_stage_buffers* bf, int64_t n_w
   }
   BP_HIP(hipGetLastError());
   BP_HIP(hipStreamSynchronize(s));
+  return BP_OK;
+}
+
+// What the launchers of the default path decide for a chunk of n_windows windows on a device of n_cu compute units, from
+// the functions they call themselves (launch_plan.h).  No handle, no device.
+int bp_launch_plan(int64_t n_windows, int n_cu, unsigned flags, bp_launch_plan_out* out) {
+  if (!out || n_windows <= 0 || n_windows > BP_MAX_WINDOWS_PER_CHUNK || n_cu <= 0 || n_cu > 4096) return BP_ERR_INVALID_ARG;
+  if (flags & BP_FLAG_F32_MFMA) return BP_ERR_UNSUPPORTED;  // the exact-f32 path has launchers of its own
+  const int n = (int)n_windows;
+  const bool ext = (flags & BP_FLAG_EXT_CQT_44K) != 0;
+  const PlGeo g = make_pl_geo(ext);
+  std::memset(out, 0, sizeof *out);
+  // pyramid
+  out->pyramid_one_launch = pyramid_one_launch(n, n_cu, ext);
+  out->pyramid_decimate_grid = out->pyramid_one_launch ? 0 : pyramid_decimate_grid((g.len[1] + kPlTileOut - 1) / kPlTileOut, n, n_cu);
+  out->pyramid_decimate_grid_cap = pl_resident_waves(n_cu) / kPlDecimateWaves;
+  // filterbank of run_chunk (zp given)
+  out->filterbank_fused = filterbank_fused(true, n, n_cu);
+  out->filterbank_grid = filterbank_grid(out->filterbank_fused != 0, n, n * g.n_levels * kPlTilesPerLevel, n_cu);
+  // contour conv1: interior march, rim (the extended mode's rim is the GEMM, a workgroup per item: no decision)
+  out->conv1_chunks = contour_march_chunks(n, n_cu);
+  out->conv1_grid = contour_march_grid(n * out->conv1_chunks * kCmStrips, n_cu);
+  out->conv1_prio = march_prio(kCmPrio, out->conv1_grid, n_cu);
+  out->rim_march = !ext;
+  if (!ext) {
+    out->rim_items = n * kRmTiles;
+    out->rim_per_side = rim_march_per_side(out->rim_items, n_cu);
+    out->rim_items_max = rim_march_items_of(0, out->rim_items, out->rim_per_side);
+    out->rim_items_min = rim_march_items_of(out->rim_per_side - 1, out->rim_items, out->rim_per_side);
+    out->rim_ring = kRmRing;
+  }
+  // contour conv2
+  out->conv2_slots = (int32_t)conv2_proj_slots(n_cu);
+  for (int w0 = 0; w0 < n; w0 += kP2PerLaunch) {
+    const Conv2ProjLaunch l = conv2_proj_launch(n, w0, n_cu);
+    int32_t* dst = w0 == 0 ? &out->conv2_first_windows : &out->conv2_last_windows;
+    dst[0] = l.n, dst[1] = l.n_groups, dst[2] = l.n_slabs, dst[3] = l.slab_rows, dst[4] = l.grid;
+    if (w0 == 0) std::memcpy(&out->conv2_last_windows, dst, 5 * sizeof(int32_t));
+    out->conv2_launches += 1;
+    out->conv2_windows += l.n;
+  }
+  // note and onset marches
+  out->note_grid = march_grid(n * kN16Strips, kN16MinFrames, kN16Waves, kN16Occ, n_cu);
+  out->note_grid_cap = kN16Occ * n_cu;
+  out->note_prio = march_prio(kN16Prio, out->note_grid, n_cu);
+  out->note_aligned = march_aligned(out->note_grid * kN16Waves, n * kN16Strips, kN16Strips);
+  out->note_share_spans_pairs = march_share_spans_pairs(out->note_grid * kN16Waves, n * kN16Strips, kN16Strips);
+  out->onset_grid = march_grid(n * kO16Strips, kO16MinFrames, kO16Waves, kO16Occ, n_cu);
+  out->onset_grid_cap = kO16Occ * n_cu;
+  out->onset_prio = march_prio(kO16Prio, out->onset_grid, n_cu);
+  out->onset_aligned = march_aligned(out->onset_grid * kO16Waves, n * kO16Strips, kO16Strips);
+  out->onset_share_spans_pairs = march_share_spans_pairs(out->onset_grid * kO16Waves, n * kO16Strips, kO16Strips);
   return BP_OK;
 }
 

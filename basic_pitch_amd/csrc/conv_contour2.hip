@@ -8,6 +8,7 @@
 #include <stdlib.h>
 
 #include "bp_kernels.h"
+#include "launch_plan.h"
 
 namespace bp {
 
@@ -30,10 +31,7 @@ namespace bp {
 //     outside the window contribute P = 0.
 // Roofline: HBM (1.48 MB in + 7 % strip overlap + 9 % slab halo, 182 KB out per window); matrix 4 instructions per 64 pixels.
 
-constexpr int kP2Group = 16;                         // windows per flat index group
-constexpr int kP2Cols = kP2Group * kC1Row;           // 4288 flat columns per group
-constexpr int kP2Strip = 64, kP2Stride = 60;         // columns a wave reads / stores per row
-constexpr int kP2Strips = (kP2Cols + kP2Stride - 1) / kP2Stride;  // 72
+// kP2Group = 16, kP2Cols, kP2Strip = 64, kP2Stride = 60, kP2Strips = 72, kP2Occ: launch_plan.h
 static_assert(kC1Pad == 2, "the pad columns of c1 are the zero padding of the 5-tap rows");
 
 struct Conv2ProjParams {
@@ -45,11 +43,6 @@ struct Conv2ProjParams {
   int slab_rows;        // frames per slab
   int n_slabs;          // slabs per window
 };
-
-#ifndef P2_OCC
-#define P2_OCC 4
-#endif
-constexpr int kP2Occ = P2_OCC;  // resident waves per SIMD the launch is cut for (and the register budget allows)
 
 // The instruction is v_mfma_f32_32x32x16_f16 with the three split-precision products packed along K: a lane's B operand is
 // [hi(c1[pixel][4 h .. 4 h + 3]) | lo 2^11 of the same four channels] — the 8 halves its own split leaves —, A1 = [w_hi 2^11 |
@@ -233,26 +226,15 @@ __global__ __launch_bounds__(256, kP2Occ) void contour_conv2_proj_kernel(Conv2Pr
 
 void launch_contour_conv2_proj(const float* c1, const void* wfrag, float bias, float* contour, int n_windows, int n_cu,
                                bool weights_have_lo, hipStream_t stream) {
-  // sub-batches of 256 windows, each cut into as many frame slabs as keep one launch within the resident waves
-  const int64_t slots = (int64_t)n_cu * 4 * kP2Occ;
-  const int per_launch = 256;
-  for (int w0 = 0; w0 < n_windows; w0 += per_launch) {
-    const int n = n_windows - w0 < per_launch ? n_windows - w0 : per_launch;
-    const int n_groups = (n + kP2Group - 1) / kP2Group;
-    int n_slabs = (int)(slots / ((int64_t)n_groups * kP2Strips));
-    n_slabs = n_slabs < 1 ? 1 : (n_slabs > 16 ? 16 : n_slabs);
-#ifdef P2_SLABS  // tools only
-    n_slabs = P2_SLABS;
-#endif
-    const int slab_rows = (kFrames + n_slabs - 1) / n_slabs;
-    n_slabs = (kFrames + slab_rows - 1) / slab_rows;
-    Conv2ProjParams p{c1 + (int64_t)w0 * kC1Win, static_cast<const uint4*>(wfrag), bias, contour + (int64_t)w0 * kPlaneC, n,
-                      slab_rows, n_slabs};
-    const int64_t waves = (int64_t)n_groups * n_slabs * kP2Strips;
+  // sub-batches of 256 windows, each cut into as many frame slabs as keep one launch within the resident waves (launch_plan.h)
+  for (int w0 = 0; w0 < n_windows; w0 += kP2PerLaunch) {
+    const Conv2ProjLaunch l = conv2_proj_launch(n_windows, w0, n_cu);
+    Conv2ProjParams p{c1 + (int64_t)w0 * kC1Win, static_cast<const uint4*>(wfrag), bias, contour + (int64_t)w0 * kPlaneC, l.n,
+                      l.slab_rows, l.n_slabs};
     if (weights_have_lo)
-      hipLaunchKernelGGL(contour_conv2_proj_kernel<true>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, p);
+      hipLaunchKernelGGL(contour_conv2_proj_kernel<true>, dim3((unsigned)l.grid), dim3(256), 0, stream, p);
     else
-      hipLaunchKernelGGL(contour_conv2_proj_kernel<false>, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, stream, p);
+      hipLaunchKernelGGL(contour_conv2_proj_kernel<false>, dim3((unsigned)l.grid), dim3(256), 0, stream, p);
   }
 }
 

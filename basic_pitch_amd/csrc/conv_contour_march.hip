@@ -31,18 +31,11 @@
 #include <string.h>
 
 #include "bp_kernels.h"
-#include "march_common.h"
+#include "launch_plan.h"
 
 namespace bp {
 
-constexpr int kCmWaves = 4;          // independent waves per workgroup
-constexpr int kCmStrips = 7;         // 32-bin strips: bins 20 .. 243
-#ifndef BP_CM_CHUNKS
-#define BP_CM_CHUNKS 4
-#endif
-constexpr int kCmChunks = BP_CM_CHUNKS;  // frame chunks per window (4: 0.211 ms at B = 256; 8: 0.225 — twice the warm-up rows; 1: 0.227 —
-                                         // 7 of a CU's 8 wave slots busy; same-box sweep at the end of round 4: 2 / 3 / 4 / 5 / 6
-                                         // chunks = 0.225 / 0.227 / 0.201 / 0.210 / 0.215 ms)
+// kCmWaves, kCmStrips, kCmChunks, kCmPrio: launch_plan.h (the launcher's decisions read them)
 constexpr int kCmKS = 6;             // k-steps of 32 taps per frame tap: 192 >= 176 + 1 + 1
 constexpr int kCmCopyU = 30;         // 16-byte units per row copy: one unit of front slack (the staging lanes whose words lie
                                      // in front of a shifted copy write there instead of branching), 28 used, one behind
@@ -55,7 +48,6 @@ constexpr int kCmRowU = 2 * kCmLoU;  // one z row image: 320 units = 5 KB
 #define BP_CM_PF 1
 #endif
 constexpr int kCmPf = BP_CM_PF;      // k-steps of B fragments read ahead of the matrix instructions
-constexpr int kCmPrio = 0;           // march_common.h: no wave changes priority (profiles/march_priority.md)
 static_assert(cm_copy_off(3) + kCmCopyU <= kCmLoU, "copies fit a plane");
 
 struct ContourMarchParams {
@@ -256,14 +248,10 @@ bool contour_conv1_use_march() {
 
 void launch_contour_conv1_march(const uint32_t* zp, const void* wfrag, const float* bias, float* c1, int n_windows, int n_cu,
                                 bool weights_have_lo, hipStream_t stream) {
-  // small batches: more, shorter chunks until there is a task per resident wave (a task is a serial march of rows: at
-  // one window, 4 chunks leave 28 waves marching 45 rows each while 2020 wave slots idle)
-  int chunks = kCmChunks;
-  while (chunks < 32 && (int64_t)n_windows * chunks * kCmStrips < (int64_t)2 * n_cu * kCmWaves) chunks *= 2;
+  const int chunks = contour_march_chunks(n_windows, n_cu);  // small batches: more, shorter chunks (launch_plan.h)
   ContourMarchParams p{static_cast<const uint4*>(wfrag), bias, zp, c1, n_windows * chunks * kCmStrips, chunks, 0};
   if (p.n_tasks <= 0) return;
-  int grid = (p.n_tasks + kCmWaves - 1) / kCmWaves;
-  if (grid > 2 * n_cu) grid = 2 * n_cu;  // two workgroups of four waves per CU (registers), persistent
+  const int grid = contour_march_grid(p.n_tasks, n_cu);  // two workgroups of four waves per CU, persistent
   p.prio = march_prio(kCmPrio, grid, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(contour_conv1_march_kernel<true>, dim3(grid), dim3(64 * kCmWaves), 0, stream, p);

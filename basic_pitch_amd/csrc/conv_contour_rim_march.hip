@@ -26,6 +26,7 @@
 #include <stdio.h>
 
 #include "bp_kernels.h"
+#include "launch_plan.h"
 
 namespace bp {
 
@@ -35,8 +36,7 @@ constexpr int kRmBins = 144;                        // z bins per frame a side r
 constexpr int kRmUnits = kRmBins / 8;               // 16-byte units per plane and row: 18 (also the LDS row pitch)
 constexpr int kRmK = 3 * kRmBins;                   // 432
 constexpr int kRmSteps = (kRmK + 31) / 32;          // 14
-constexpr int kRmTileFrames = 16;
-constexpr int kRmTiles = (kFrames + kRmTileFrames - 1) / kRmTileFrames;  // 11
+// kRmTileFrames = 16, kRmTiles = 11, kRmDepth, kRmRing: launch_plan.h
 constexpr int kRmRows = kRmTileFrames + 2;          // z rows of a tile
 constexpr int kRmPlaneU = kRmRows * kRmUnits;       // units per plane: 324
 constexpr int kRmBufU = 2 * kRmPlaneU;              // hi plane, lo plane
@@ -64,11 +64,6 @@ __device__ __forceinline__ void rm_dma16(const void* gsrc, uint4* lds_wave_base)
 #ifndef BP_RM_PF
 #define BP_RM_PF 2
 #endif
-#ifndef BP_RM_DEPTH
-#define BP_RM_DEPTH 4
-#endif
-constexpr int kRmDepth = BP_RM_DEPTH;        // items whose zp words are in flight (LDS-DMA)
-constexpr int kRmRing = kRmDepth + 1;        // raw buffers
 static_assert(kRmDepth >= 2, "the counted s_waitcnt vmcnt(1 + 3 (kRmDepth - 2)) of the item loop assumes at least two items in flight");
 constexpr int kRmRawU = 2 * kRmPlaneU + 2;   // 648 pieces of 16 bytes + 2 dummies (every wave issues two DMA instructions)
 static_assert(2 * kRmPlaneU == kRmBlocks * 64 + 8, "piece q = 64 wave + lane, and one more piece for waves 0..7");
@@ -248,10 +243,8 @@ void launch_contour_conv1_rim_march(const uint32_t* zp, const void* afrag, const
                                     bool weights_have_lo, hipStream_t stream) {
   RimMarchParams p{zp, static_cast<const uint4*>(afrag), bias, c1, n_windows * kRmTiles};
   if (p.n_items <= 0) return;
-  // one workgroup of ten waves per CU (168 VGPRs: three waves per SIMD), half of them per side; few windows: a workgroup
-  // per item and side
-  int per_side = n_cu / 2 > 0 ? n_cu / 2 : 1;
-  if (per_side > p.n_items) per_side = p.n_items;
+  // one workgroup of ten waves per CU, half of them per side; few windows: a workgroup per item and side (launch_plan.h)
+  const int per_side = rim_march_per_side(p.n_items, n_cu);
   const dim3 grid(2 * per_side), block(kRmThreads);
   if (weights_have_lo)
     hipLaunchKernelGGL(contour_conv1_rim_march_kernel<true>, grid, block, 0, stream, p);

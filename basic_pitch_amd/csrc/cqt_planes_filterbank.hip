@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "cqt_planes.h"
+#include "launch_plan.h"
 
 namespace bp {
 
@@ -461,19 +462,11 @@ bool launch_filterbank_planes(const uint16_t* pl, const float* audio, int64_t au
   float2* mm = reinterpret_cast<float2*>(scratch);
   const unsigned per_window = (unsigned)(g.n_levels * kPlTilesPerLevel);
   const unsigned magic = (unsigned)((0x100000000ull + per_window - 1) / per_window);
-  // one window per workgroup pays from half a window per CU on.  (A file job's 110-window tracks on three lanes, round 5:
-  // with the fused form from 32 windows on, 1,258 files/s against 1,460 — a third of the CUs for 60 us is worse than all
-  // of them for 29 + 15 us even when other lanes' kernels could fill the rest.)
-  const bool fused = zp != nullptr && 2 * n_windows >= n_cu;
+  // one window per workgroup pays from half a window per CU on (launch_plan.h)
+  const bool fused = filterbank_fused(zp != nullptr, n_windows, n_cu);
   // (768 threads with 7 / 5 k-steps of A fragments ahead, 158 VGPRs: 0.070 - 0.074 / 0.069 ms against 0.069 - 0.070, round 5)
-  constexpr int kThreads = 1024, kApf = 3;
-  int grid;
-  if (fused) {
-    grid = n_windows < n_cu ? n_windows : n_cu;
-  } else {
-    grid = (tasks + kThreads / 64 - 1) / (kThreads / 64);
-    if (grid > n_cu) grid = n_cu;
-  }
+  constexpr int kThreads = kPlFbThreads, kApf = 3;
+  const int grid = filterbank_grid(fused, n_windows, tasks, n_cu);
 #define BP_PL_FB_LAUNCH(F, E)                                                                                           \
   hipLaunchKernelGGL((cqt_filterbank_planes_kernel<kThreads, kApf, F, E>), dim3(grid), dim3(kThreads), 0, stream, pl,   \
                      audio, audio_stride, bf, bk, lp, mm, zp, n_windows, kc, g, magic)

@@ -6,6 +6,7 @@
 #include <cstring>
 
 #include "cqt_planes.h"
+#include "launch_plan.h"
 
 namespace bp {
 
@@ -755,8 +756,6 @@ __global__ __launch_bounds__(kPwThreads) void pl_pyramid_window_kernel(const flo
 
 // ================================================================================================
 // host side
-static int pl_resident_waves(int n_cu) { return n_cu * 16; }
-
 void launch_planes_split(const float* src, int64_t src_stride, int level, uint16_t* pl, int n_windows, bool ext,
                          hipStream_t stream) {
   const PlGeo g = make_pl_geo(ext);
@@ -784,19 +783,15 @@ void launch_pyramid_planes(const float* audio, int64_t audio_stride, uint16_t* p
                            bool ext, hipStream_t stream) {
   const PlGeo g = make_pl_geo(ext);
   const uint4* tf = static_cast<const uint4*>(tfrag);
-  // with at least half a window per CU the whole pyramid is ONE launch, a workgroup per window (the 22.05 kHz kernel from
-  // a third: a 3-minute track is 110 windows, and the four wide launches it took below half the CUs cost 55 us where
-  // 110 workgroups of the per-window kernel take 40)
-  const bool one_launch = ext ? n_windows >= n_cu / 2 : 3 * n_windows >= n_cu;
+  // with at least half a window per CU (the 22.05 kHz kernel: a third) the whole pyramid is ONE launch (launch_plan.h)
+  const bool one_launch = pyramid_one_launch(n_windows, n_cu, ext);
   if (one_launch && !ext) {
     hipLaunchKernelGGL(pl_pyramid_window_kernel, dim3(n_windows), dim3(kPwThreads), 0, stream, audio, audio_stride, pl, g, tf);
     return;
   }
   if (!one_launch) {
     const int tiles = (g.len[1] + kPlTileOut - 1) / kPlTileOut;
-    const int items = tiles * n_windows;
-    int grid = (items + 3) / 4;
-    if (grid > pl_resident_waves(n_cu) / 4) grid = pl_resident_waves(n_cu) / 4;
+    const int grid = pyramid_decimate_grid(tiles, n_windows, n_cu);
     hipLaunchKernelGGL(pl_decimate_kernel<true>, dim3(grid), dim3(256), 0, stream, audio, audio_stride, pl, g.stride, g.off[0],
                        g.len[0], g.off[1], g.len[1], tiles, tf, n_windows, g.hop0);
   }
@@ -806,9 +801,7 @@ void launch_pyramid_planes(const float* audio, int64_t audio_stride, uint16_t* p
     for (; first_tail < g.n_levels && g.len[first_tail] > 16 * kPlTileOut; ++first_tail) {
       const int k = first_tail;
       const int tiles = (g.len[k] + kPlTileOut - 1) / kPlTileOut;
-      const int items = tiles * n_windows;
-      int grid = (items + 3) / 4;
-      if (grid > pl_resident_waves(n_cu) / 4) grid = pl_resident_waves(n_cu) / 4;
+      const int grid = pyramid_decimate_grid(tiles, n_windows, n_cu);
       hipLaunchKernelGGL(pl_decimate_kernel<false>, dim3(grid), dim3(256), 0, stream, (const float*)nullptr, (int64_t)0, pl,
                          g.stride, g.off[k - 1], g.len[k - 1], g.off[k], g.len[k], tiles, tf, n_windows, 0);
     }

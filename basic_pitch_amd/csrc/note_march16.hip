@@ -35,21 +35,15 @@
 #include <stdlib.h>
 
 #include "bp_kernels.h"
-#include "march_common.h"
+#include "launch_plan.h"
 
 namespace bp {
 
-constexpr int kN16Waves = 4;    // independent waves per workgroup
-constexpr int kN16Strips = 3;   // 32-pixel strips of a row, 30 inner pixels each
+// kN16Waves = 4, kN16Strips = 3, kN16Occ, kN16Prio, kN16MinFrames: launch_plan.h
 constexpr int kN16Ring = 8;     // image rows a wave keeps: r - 3 .. r + 3 in use, r + 4 being written
 constexpr int kN16Row = 64;     // ring row stride in 16-byte units: hi plane (32 pixels), lo plane at kN16Lo
 constexpr int kN16Lo = 32;
 constexpr int kN16Frags = 18;   // pack_note16
-#ifndef N16_OCC
-#define N16_OCC 2
-#endif
-constexpr int kN16Occ = N16_OCC;  // resident workgroups per CU (x 4 waves: waves per SIMD)
-constexpr int kN16Prio = 45;      // march_common.h: a second-half wave takes the issue priority at 45 % of its rows
 static_assert(kN16Strips * 30 >= kFreqN, "strips cover a row");
 static_assert(kN16Row % 16 == 0, "conflict-free ds_read_b128: rows differ by a multiple of 16 units");
 
@@ -394,8 +388,7 @@ void launch_note_march16(const float* contour, const void* wfrag, const float* w
   // two resident workgroups per CU, persistent; small batches: fewer waves, at least kMinFrames frames each
   Note16Params p{static_cast<const uint4*>(wfrag), wf32, contour, note, n_windows * kN16Strips, 0};
   if (p.n_ws <= 0) return;
-  constexpr int kMinFrames = 12;
-  const int grid = march_grid(p.n_ws, kMinFrames, kN16Waves, kN16Occ, n_cu);
+  const int grid = march_grid(p.n_ws, kN16MinFrames, kN16Waves, kN16Occ, n_cu);
   p.prio = march_prio(kN16Prio, grid, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(note_march16_kernel<true>, dim3(grid), dim3(64 * kN16Waves), 0, stream, p);

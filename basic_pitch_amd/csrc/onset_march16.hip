@@ -32,12 +32,11 @@
 #include <stdlib.h>
 
 #include "bp_kernels.h"
-#include "march_common.h"
+#include "launch_plan.h"
 
 namespace bp {
 
-constexpr int kO16Waves = 4;  // independent waves per workgroup
-constexpr int kO16Strips = 3;                  // 32-pixel strips of a row, 30 inner pixels each
+// kO16Waves = 4, kO16Strips = 3, kO16Occ, kO16Prio, kO16MinFrames: launch_plan.h
 constexpr int kO16Ring = 6;                    // image rows a wave keeps: r - 2 .. r + 2 in use, r + 3 being written
 constexpr int kO16Slots = 98;                  // stack bins a strip's 32 pixels read: 3 * 31 + 5
 constexpr int kO16Row = 208;                   // ring row stride in 16-byte slots: hi plane, lo plane at kO16Lo; 13 x 16
@@ -47,7 +46,6 @@ constexpr int kO16KS = kOnset16KSteps;         // 7 (bp_common.h: the tap table 
 #define BP_ONSET16_PF 1
 #endif
 constexpr int kO16Pf = BP_ONSET16_PF;          // k-steps of image fragments read ahead of the matrix instructions
-constexpr int kO16Prio = 45;                   // march_common.h: a second-half wave takes the issue priority at 45 % of its rows
 static_assert(kO16Strips * 30 >= kFreqN, "strips cover a row");
 static_assert(kO16Lo >= kO16Slots && 2 * kO16Lo <= kO16Row && kO16Row % 16 == 0, "ring geometry");
 
@@ -358,8 +356,7 @@ void launch_onset_march16(const uint32_t* zp, const float* note, const void* wfr
   // two resident workgroups per CU (LDS), persistent; small batches: fewer waves, at least kMinFrames frames each
   Onset16Params p{static_cast<const uint4*>(wfrag), wf32, zp, note, onset, n_windows * kO16Strips, 0};
   if (p.n_ws <= 0) return;
-  constexpr int kMinFrames = 6;
-  const int grid = march_grid(p.n_ws, kMinFrames, kO16Waves, 2, n_cu);
+  const int grid = march_grid(p.n_ws, kO16MinFrames, kO16Waves, kO16Occ, n_cu);
   p.prio = march_prio(kO16Prio, grid, n_cu);
   if (weights_have_lo)
     hipLaunchKernelGGL(onset_march16_kernel<true>, dim3(grid), dim3(64 * kO16Waves), 0, stream, p);

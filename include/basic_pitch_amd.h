@@ -388,6 +388,53 @@ typedef struct bp_stage_buffers {
 } bp_stage_buffers;
 int bp_run_stage(bp_handle h, int stage, const bp_stage_buffers* buf, int64_t n_windows);
 
+/*
+ * Test hook: what the launchers of the default (split-precision) path decide for one chunk of n_windows windows on a
+ * device of n_cu compute units — which kernel form, which grid, how many chunks, slabs and items per workgroup — filled
+ * from the functions the launchers themselves call (csrc/launch_plan.h).  No handle, no GPU.  flags: BP_FLAG_BF16_WEIGHTS
+ * and BP_FLAG_EXT_CQT_44K select the mode (BP_FLAG_F32_MFMA: BP_ERR_UNSUPPORTED); 1 <= n_windows <= 16384.
+ */
+typedef struct bp_launch_plan_out {
+  int32_t pyramid_one_launch;        /* 1: one per-window launch; 0: wide decimators + the per-window tail */
+  int32_t pyramid_decimate_grid;     /* workgroups of the first wide decimator launch (0 with one launch) */
+  int32_t pyramid_decimate_grid_cap; /* the resident workgroups that grid is capped at */
+  int32_t filterbank_fused;          /* 1: whole windows per workgroup, normalise / BatchNorm / split fused */
+  int32_t filterbank_grid;           /* fused: workgroup g owns windows g, g + grid, ... */
+  int32_t conv1_chunks;              /* frame chunks per window of the contour conv1 march */
+  int32_t conv1_grid;
+  int32_t conv1_prio;                /* the march's priority rule (0: off) */
+  int32_t rim_march;                 /* 1: the register-resident rim march; 0: the rim GEMM (extended mode), rim_* are 0 */
+  int32_t rim_items;                 /* (window, 16-frame tile) items per side */
+  int32_t rim_per_side;              /* persistent workgroups per side */
+  int32_t rim_items_max;             /* items of the first workgroup of a side */
+  int32_t rim_items_min;             /* items of the last */
+  int32_t rim_ring;                  /* LDS-DMA buffers of a workgroup: items in flight + 1 */
+  int32_t conv2_slots;               /* resident waves a conv2 launch is cut for */
+  int32_t conv2_launches;            /* launches of at most 256 windows */
+  int32_t conv2_windows;             /* windows they cover together */
+  int32_t conv2_first_windows;       /* the first launch: windows, groups of 16, frame slabs, frames per slab, workgroups */
+  int32_t conv2_first_groups;
+  int32_t conv2_first_slabs;
+  int32_t conv2_first_slab_rows;
+  int32_t conv2_first_grid;
+  int32_t conv2_last_windows;        /* the last launch (the first again when there is one) */
+  int32_t conv2_last_groups;
+  int32_t conv2_last_slabs;
+  int32_t conv2_last_slab_rows;
+  int32_t conv2_last_grid;
+  int32_t note_grid;                 /* note march: workgroups of four waves */
+  int32_t note_grid_cap;             /* the resident workgroups it saturates at */
+  int32_t note_prio;                 /* priority rule: percentage of a second-half wave's rows, 0: off */
+  int32_t note_aligned;              /* 1: exactly eight waves per window, the aligned cut */
+  int32_t note_share_spans_pairs;    /* 1: a wave's share is longer than one (window, strip) pair */
+  int32_t onset_grid;                /* onset march: the same */
+  int32_t onset_grid_cap;
+  int32_t onset_prio;
+  int32_t onset_aligned;
+  int32_t onset_share_spans_pairs;
+} bp_launch_plan_out;
+int bp_launch_plan(int64_t n_windows, int n_cu, unsigned flags, bp_launch_plan_out* out);
+
 /* Offsets (in floats) of pyramid levels 1..8 inside one window's pyr row, and their lengths. */
 int bp_pyramid_layout(int level /*1..8*/, int64_t* offset, int64_t* length);
 
