@@ -247,6 +247,18 @@ class bp_note_score(C.Structure):
     ]
 
 
+class bp_frame_score(C.Structure):
+    """The frame-level counts of one scored decode (include/basic_pitch_amd_frame_score.h)."""
+
+    _fields_ = [
+        ("n_frames", C.c_int64),
+        ("ref_frames", C.c_int64),
+        ("est_frames", C.c_int64),
+        ("true_pos", C.c_int64),
+        ("e_sub", C.c_int64),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -386,6 +398,12 @@ SCORE_SYMBOLS = [
     "bp_score_note_events",
     "bp_note_events_sweep_score",
     "bp_infer_clips_events_sweep_score",
+]
+# every symbol include/basic_pitch_amd_frame_score.h declares (bound in basic_pitch_amd/frame_score.py)
+FRAME_SCORE_SYMBOLS = [
+    "bp_score_note_frames",
+    "bp_note_events_sweep_frame_score",
+    "bp_infer_clips_events_sweep_frame_score",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

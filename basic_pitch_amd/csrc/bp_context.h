@@ -106,6 +106,12 @@ struct bp_context {
   Buffer<bp::NoteScoreDecode> sc_dec;
   Buffer<int32_t> sc_out;
   bp::PinnedBuffer<int32_t> sc_home;
+  // the frame level of a scored sweep (bp_note_events_sweep_frame_score, clips_api.hip queue_sweep), all grow-only, scratch of
+  // one call and grown by the frame-score calls alone: per segment its refs in pitch order as frames and note bins, the counts
+  // [decodes][5] with the statuses [decodes] (32-bit) behind them, and the page-locked block they come home in
+  Buffer<bp::NoteFrameRef> fs_refs;
+  Buffer<int64_t> fs_out;
+  bp::PinnedBuffer<int64_t> fs_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

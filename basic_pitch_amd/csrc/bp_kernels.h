@@ -279,6 +279,22 @@ size_t note_score_lds_bytes(int max_refs, int max_depth);
 hipError_t launch_note_score(const void* counts, const int64_t* ev_first, const void* ev_pool, const NoteScoreDecode* dec,
                              const NoteScoreRef* refs, const NoteScoreParams& prm, int64_t n_decodes, int max_refs, int max_depth,
                              int32_t* out, hipStream_t s);
+// The same decodes scored frame by frame (note_frames.hip; bp_note_events_sweep_frame_score,
+// include/basic_pitch_amd_frame_score.h), one workgroup per decode, beside or in place of launch_note_score.  rows: [n_decodes
+// + 1] the rows of the decodes before each (the tracker's row offsets).  dec: launch_note_score's table, read for the refs of
+// the decode's segment and the status; refs: per segment its refs IN ASCENDING PITCH, each as the frames it sounds on and the
+// note bins it hits (made on the host by the checker's functions, note_frames_host.cpp).  max_rows: the longest decode, which
+// sizes the launch's LDS (note_frames_lds_bytes).  out: [n_decodes] {n_frames, ref_frames, est_frames, true_pos, e_sub},
+// then, as 32-bit words, [n_decodes] status — the status launch_note_score leaves.
+constexpr int kNoteFramesChunk = 2048;  // frames a workgroup rolls into LDS at a time
+struct NoteFrameRef {
+  int32_t f0, f1;  // sounds on frames f0 ... f1 - 1 of its segment
+  int32_t lo, hi;  // hits the note bins lo ... hi (lo > hi: none)
+};
+size_t note_frames_lds_bytes(int64_t max_rows);
+hipError_t launch_note_frames(const void* counts, const int64_t* rows, const int64_t* ev_first, const void* ev_pool,
+                              const NoteScoreDecode* dec, const NoteFrameRef* refs, int64_t n_decodes, int64_t max_rows, int64_t* out,
+                              hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -19,6 +19,7 @@
 #include "../../include/basic_pitch_amd_adpcm.h"
 #include "../../include/basic_pitch_amd_flac_clips.h"
 #include "../../include/basic_pitch_amd_score.h"
+#include "../../include/basic_pitch_amd_frame_score.h"
 #include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
@@ -29,6 +30,8 @@ extern "C" double bp_internal_frame_time(int64_t frame);
 extern "C" const char* bp_internal_score_bad_params(const bp_score_params* p);
 extern "C" int64_t bp_internal_score_bad_ref(const bp_ref_note* refs, int64_t n);
 extern "C" double bp_internal_score_offset_tol(const bp_ref_note* r, const bp_score_params* p);
+extern "C" void bp_internal_frame_interval(double start_s, double end_s, int64_t n_frames, int64_t* f0, int64_t* f1);
+extern "C" void bp_internal_frame_pitch_range(const bp_ref_note* r, const bp_score_params* p, int32_t* lo, int32_t* hi);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 namespace bp {
@@ -504,6 +507,7 @@ struct JobSource {
 // decodes, decode j segment decodes[j].segment under sets[decodes[j].params] (decodes null: the cross product, set-major);
 // params is null, every set has its own dense half.  kScoreHome: the same sweep, but what goes home is `scores` and out.status
 // alone — every decode's events scored on the device against the refs of its segment (include/basic_pitch_amd_score.h).
+// with_frames: the calls of include/basic_pitch_amd_frame_score.h — `frames` goes home too, and `scores` may be null.
 enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome };
 struct JobSink {
   JobSinkKind kind;
@@ -522,6 +526,8 @@ struct JobSink {
   const bp_ref_note* refs;
   const bp_score_params* score_params;
   bp_note_score* scores;
+  bool with_frames;
+  bp_frame_score* frames;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -550,6 +556,14 @@ JobSink score_sink(int64_t n_sets, const bp_note_params* sets, int64_t n_decodes
   return k;
 }
 
+JobSink frame_score_sink(int64_t n_sets, const bp_note_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                         const int64_t* ref_offsets, const bp_ref_note* refs, const bp_score_params* score_params, bp_note_score* scores,
+                         bp_frame_score* frames, int* status) {
+  JobSink k = score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, status);
+  k.with_frames = true, k.frames = frames;
+  return k;
+}
+
 // ---- a sweep: the segments of a job under many parameter sets (include/basic_pitch_amd_sweep.h) -----------------
 // A dense key: what the dense half of note decoding depends on.  Sets of one key share its bitmap and its block of stats
 // records; keys of one band [lo, hi) share the constrained copy of the note rows.
@@ -573,12 +587,17 @@ struct SweepJob {
   std::vector<NoteScoreRef> refs;
   std::vector<NoteScoreDecode> ref_of;
   int max_refs = 0, max_depth = 0;
+  std::vector<NoteFrameRef> frame_refs;  // with_frames: per segment its refs in ascending pitch, as note_frames.hip reads them
 };
 
 // what a scored sweep takes beside a sweep's arguments, before anything is queued
 int check_score(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
   auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
-  if (!k.ref_offsets || (k.n_decodes > 0 && !k.scores)) return invalid("null ref_offsets or scores");
+  if (k.with_frames) {
+    if (!k.ref_offsets || (k.n_decodes > 0 && !k.frames)) return invalid("null ref_offsets or frames");
+  } else if (!k.ref_offsets || (k.n_decodes > 0 && !k.scores)) {
+    return invalid("null ref_offsets or scores");
+  }
   if (const char* why = bp_internal_score_bad_params(k.score_params)) return invalid(why);
   if (k.ref_offsets[0] != 0) return invalid("ref_offsets must start at 0");
   for (int64_t i = 0; i < n_segs; ++i)
@@ -591,10 +610,11 @@ int check_score(bp_handle h, const char* what, int64_t n_segs, const JobSink& k)
   return BP_OK;
 }
 
-// decode j of a scored sweep without events: {n_ref, 0, 0, 0} (its segment: seg)
-void score_nothing(const JobSink& k, int64_t j, int64_t seg) {
+// decode j of a scored sweep without events: {n_ref, 0, 0, 0} and {rows, 0, 0, 0, 0} (its segment: seg)
+void score_nothing(const JobSink& k, int64_t j, int64_t seg, int64_t rows) {
   const int64_t n_ref = k.ref_offsets[seg + 1] - k.ref_offsets[seg];
-  k.scores[j] = bp_note_score{(int32_t)std::min<int64_t>(n_ref, INT32_MAX), 0, 0, 0};
+  if (k.scores) k.scores[j] = bp_note_score{(int32_t)std::min<int64_t>(n_ref, INT32_MAX), 0, 0, 0};
+  if (k.frames) k.frames[j] = bp_frame_score{rows, 0, 0, 0, 0};
 }
 
 // every argument of a sweep that is not a segment's, before anything is queued
@@ -661,13 +681,14 @@ int plan_sweep(bp_handle h, const char* what, int64_t n_segs, const int64_t* off
   if (!*queued) {
     for (int64_t j = 0; j < n; ++j) k.out.status[j] = w->pool_rows[(size_t)j + 1] > w->pool_rows[(size_t)j] ? 1 : 0;
     for (int64_t j = 0; j <= n && !score; ++j) k.out.event_offsets[j] = 0;
-    for (int64_t j = 0; j < n && score; ++j) score_nothing(k, j, w->segment[(size_t)j]);
+    for (int64_t j = 0; j < n && score; ++j)
+      score_nothing(k, j, w->segment[(size_t)j], w->pool_rows[(size_t)j + 1] - w->pool_rows[(size_t)j]);
     return BP_OK;
   }
   if (score) {  // the refs as the device reads them; which are whose
     const int64_t n_refs = k.ref_offsets[n_segs];
-    w->refs.resize((size_t)n_refs);
-    for (int64_t i = 0; i < n_refs; ++i) {
+    w->refs.resize(k.scores ? (size_t)n_refs : 0);
+    for (int64_t i = 0; i < n_refs && k.scores; ++i) {
       const bp_ref_note& r = k.refs[i];
       w->refs[(size_t)i] = NoteScoreRef{r.start_s, r.end_s, r.pitch_midi, bp_internal_score_offset_tol(&r, k.score_params)};
     }
@@ -677,6 +698,24 @@ int plan_sweep(bp_handle h, const char* what, int64_t n_segs, const int64_t* off
       const int64_t rows = w->pool_rows[(size_t)j + 1] - w->pool_rows[(size_t)j];
       w->ref_of[(size_t)j] = NoteScoreDecode{first, (int32_t)std::min<int64_t>(k.ref_offsets[seg + 1] - first, kNoteScoreMaxNotes + 1),
                                              w->seg[(size_t)j].bends && rows <= kNoteTrackMaxRows ? (int32_t)(88 * rows) : -1};
+    }
+  }
+  if (score && k.with_frames) {  // what depends on a ref and its segment alone, by the checker's own functions; a segment's in pitch order
+    w->frame_refs.resize((size_t)k.ref_offsets[n_segs]);
+    std::vector<int64_t> order;
+    for (int64_t i = 0; i < n_segs; ++i) {
+      const int64_t first = k.ref_offsets[i], rows = offs[i + 1] - offs[i];
+      order.resize((size_t)(k.ref_offsets[i + 1] - first));
+      for (size_t r = 0; r < order.size(); ++r) order[r] = first + (int64_t)r;
+      std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return k.refs[a].pitch_midi < k.refs[b].pitch_midi; });
+      for (size_t r = 0; r < order.size(); ++r) {
+        const bp_ref_note& ref = k.refs[order[r]];
+        int64_t f0 = 0, f1 = 0;
+        NoteFrameRef& out = w->frame_refs[(size_t)first + r];
+        bp_internal_frame_interval(ref.start_s, ref.end_s, rows, &f0, &f1);
+        out.f0 = (int32_t)f0, out.f1 = (int32_t)f1;  // (rows <= BP_SWEEP_MAX_ROWS)
+        bp_internal_frame_pitch_range(&ref, k.score_params, &out.lo, &out.hi);
+      }
     }
   }
   // the keys in the map's order, which keeps a band's keys together; a set's key by that order
@@ -704,6 +743,7 @@ struct ClipsJob {
   bool dense_bends = false;                    // kEventsHome: the dense half makes the bend map
   SweepJob sweep;                              // kSweepHome, kScoreHome
   const bp_score_params* score_params = nullptr;  // kScoreHome
+  bool want_scores = true, want_frames = false;   // kScoreHome: the note-matching launch, the frame launch
   EventsJob ev{};
   EventsPlan plan;
   bool exported_by_kernel = false;
@@ -759,7 +799,7 @@ int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* off
   const int64_t* d_rows = reinterpret_cast<const int64_t*>(h->sw_tab + tab_bytes);
   BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n_segs + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
   BP_HIP(hipMemcpyAsync(h->sw_tab, w.block.data(), w.block.size(), hipMemcpyHostToDevice, s));
-  if (score) {
+  if (score && job.want_scores) {
     // The LDS of the scoring launch: the most refs a decode it scores can have, the deepest its path can get — min(events,
     // refs + 1), the events bounded by what the decode's region of the pool holds.  Its tables go with the tracker's.
     for (int64_t j = 0; j < n; ++j) {
@@ -770,12 +810,21 @@ int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* off
       w.max_depth = std::max(w.max_depth, (int)std::min<int64_t>({room, (int64_t)n_ref + 1, (int64_t)kNoteScoreMaxNotes}));
     }
     BP_HIP(h->sc_refs.reserve(w.refs.size()));
-    BP_HIP(h->sc_dec.reserve((size_t)n));
     BP_HIP(h->sc_out.reserve((size_t)(5 * n)));
     BP_HIP(h->sc_home.reserve((size_t)(5 * n)));
     if (!w.refs.empty())
       BP_HIP(hipMemcpyAsync(h->sc_refs, w.refs.data(), w.refs.size() * sizeof(NoteScoreRef), hipMemcpyHostToDevice, s));
+  }
+  if (score) {  // which refs are whose: both scoring launches read it
+    BP_HIP(h->sc_dec.reserve((size_t)n));
     BP_HIP(hipMemcpyAsync(h->sc_dec, w.ref_of.data(), (size_t)n * sizeof(NoteScoreDecode), hipMemcpyHostToDevice, s));
+  }
+  if (score && job.want_frames) {  // the frame launch's table, its counts [decodes][5] with the statuses (32-bit) behind them
+    BP_HIP(h->fs_refs.reserve(w.frame_refs.size()));
+    BP_HIP(h->fs_out.reserve((size_t)(5 * n + (n + 1) / 2)));
+    BP_HIP(h->fs_home.reserve((size_t)(5 * n + (n + 1) / 2)));
+    if (!w.frame_refs.empty())
+      BP_HIP(hipMemcpyAsync(h->fs_refs, w.frame_refs.data(), w.frame_refs.size() * sizeof(NoteFrameRef), hipMemcpyHostToDevice, s));
   }
   launch_clips_stats_init(h->sw_stats, n_keys * n_segs, s);
   int made = 0;  // bands whose copies exist; sw_onset holds the last one's
@@ -794,10 +843,17 @@ int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* off
     BP_HIP(launch_note_track_sweep(h->sw_tab.as<NoteSweepDecode>(), n, job.plan.max_rows, nullptr, d_rows, d_rows + n + 1, h->ev_scratch,
                                    h->ev_pool, nullptr, h->ev_counts, nullptr, nullptr, nullptr, s));
     const bp_score_params& p = *job.score_params;
-    BP_HIP(launch_note_score(h->ev_counts, d_rows + n + 1, h->ev_pool, h->sc_dec, h->sc_refs,
-                             NoteScoreParams{p.onset_tolerance_s, p.pitch_tolerance_cents, p.strict != 0}, n, w.max_refs, w.max_depth,
-                             h->sc_out, s));
-    BP_HIP(hipMemcpyAsync(h->sc_home, h->sc_out, (size_t)(5 * n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    if (job.want_scores) {
+      BP_HIP(launch_note_score(h->ev_counts, d_rows + n + 1, h->ev_pool, h->sc_dec, h->sc_refs,
+                               NoteScoreParams{p.onset_tolerance_s, p.pitch_tolerance_cents, p.strict != 0}, n, w.max_refs, w.max_depth,
+                               h->sc_out, s));
+      BP_HIP(hipMemcpyAsync(h->sc_home, h->sc_out, (size_t)(5 * n) * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+    }
+    if (job.want_frames) {  // 40 bytes more per decode; the statuses too where the note-matching launch was skipped
+      BP_HIP(launch_note_frames(h->ev_counts, d_rows, d_rows + n + 1, h->ev_pool, h->sc_dec, h->fs_refs, n, job.plan.max_rows, h->fs_out, s));
+      const size_t bytes = (size_t)(5 * n) * sizeof(int64_t) + (job.want_scores ? 0 : (size_t)n * sizeof(int32_t));
+      BP_HIP(hipMemcpyAsync(h->fs_home, h->fs_out, bytes, hipMemcpyDeviceToHost, s));
+    }
     return BP_OK;
   }
   BP_HIP(launch_note_track_sweep(h->sw_tab.as<NoteSweepDecode>(), n, job.plan.max_rows, d_bend, d_rows, d_rows + n + 1, h->ev_scratch,
@@ -866,6 +922,7 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   // the source's plan (every argument of every segment, its rows), the outputs against the rows
   ClipsJob job;
   job.score_params = k.score_params;
+  job.want_scores = !k.with_frames || k.scores != nullptr, job.want_frames = k.with_frames;
   if (src.kind == kGivenMaps) {
     bool ordered = n >= 0 && src.row_offsets && src.row_offsets[0] == 0;
     for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
@@ -923,8 +980,10 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
       k.out.status[i] = job.offs[i + 1] > job.offs[i] && (h->clip_stats_host[4 * i + 1] || !(k.params->onset_threshold > 0.0)) ? 1 : 0;
   } else if (score) {  // the stream has drained: the scores and the statuses are in the page-locked block
     if (rc) return rc;
-    std::memcpy(k.scores, h->sc_home, (size_t)k.n_decodes * sizeof(bp_note_score));
-    for (int64_t j = 0; j < k.n_decodes; ++j) k.out.status[j] = h->sc_home[4 * k.n_decodes + j];
+    if (job.want_scores) std::memcpy(k.scores, h->sc_home, (size_t)k.n_decodes * sizeof(bp_note_score));
+    if (job.want_frames) std::memcpy(k.frames, h->fs_home, (size_t)k.n_decodes * sizeof(bp_frame_score));
+    const int32_t* st = job.want_scores ? h->sc_home + 4 * k.n_decodes : reinterpret_cast<const int32_t*>(h->fs_home + 5 * k.n_decodes);
+    for (int64_t j = 0; j < k.n_decodes; ++j) k.out.status[j] = st[j];
   } else if (rc || (rc = events_home(h, job.ev, k.out, nullptr))) {
     // (buffers too small: status and event_offsets are complete but for the decoder's verdicts)
     if (flac) flac_clips_status(h, job.flac, false, k.out.status);
@@ -998,6 +1057,25 @@ int bp_infer_clips_events_sweep_score(bp_handle h, int64_t n_clips, const bp_cli
                                       bp_note_score* scores, int* status) {
   return run_clips(h, "bp_infer_clips_events_sweep_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
                    score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, status));
+}
+
+// ---- a sweep scored at the note and the frame level (include/basic_pitch_amd_frame_score.h) ----------------------------------------
+int bp_note_events_sweep_frame_score(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* note,
+                                     const float* onset, const float* contour, int mem_kind, int64_t n_sets,
+                                     const bp_note_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                                     const int64_t* ref_offsets, const bp_ref_note* refs, const bp_score_params* score_params,
+                                     bp_note_score* scores, bp_frame_score* frames, int* status) {
+  return run_clips(h, "bp_note_events_sweep_frame_score", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, note, onset, contour},
+                   frame_score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, frames, status));
+}
+
+int bp_infer_clips_events_sweep_frame_score(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                                            int64_t n_sets, const bp_note_params* sets, int64_t n_decodes,
+                                            const bp_sweep_decode* decodes, const int64_t* ref_offsets, const bp_ref_note* refs,
+                                            const bp_score_params* score_params, bp_note_score* scores, bp_frame_score* frames,
+                                            int* status) {
+  return run_clips(h, "bp_infer_clips_events_sweep_frame_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   frame_score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, frames, status));
 }
 
 #ifdef BP_AB_KERNELS

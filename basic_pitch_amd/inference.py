@@ -539,6 +539,29 @@ class Model:
 
         return _score.transcribe_clips_sweep_scores(self, clips, sample_rates, params, refs, pairs, **tolerances)
 
+    def sweep_frame_scores(self, outputs: Sequence[Dict[str, Any]], params: Sequence[Any], refs: Sequence[Any],
+                           pairs: "Optional[Sequence[Tuple[int, int]]]" = None, notes: bool = True, **tolerances: Any):
+        """`sweep_note_scores` with the frame level beside it, in ONE call (`bp_note_events_sweep_frame_score`): every decode is
+        also scored frame by frame on the device (the restatement of mir_eval.multipitch in
+        include/basic_pitch_amd_frame_score.h).  Returns (note counts, frame counts): the array of `sweep_note_scores` and one of
+        the same shape with the fields n_frames, ref_frames, est_frames, true_pos, e_sub, status, which
+        `frame_score.frame_metrics` and `frame_score.best_set_by_accuracy` read.  notes False: the note matching is skipped
+        and the frame counts alone are returned.  A decode the device leaves (status != 0) is scored on the host; its status
+        stays."""
+        from . import frame_score as _frames
+
+        return _frames.sweep_frame_scores(self, outputs, params, refs, pairs, notes, **tolerances)
+
+    def transcribe_clips_sweep_frame_scores(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Sequence[Any],
+                                            refs: Sequence[Any], pairs: "Optional[Sequence[Tuple[int, int]]]" = None,
+                                            notes: bool = True, **tolerances: Any):
+        """The same behind the model, for many short clips (as for `transcribe_clips_sweep_scores`): the clips of a rate go
+        through the model once (`bp_infer_clips_events_sweep_frame_score`); returns as `sweep_frame_scores`, a segment being
+        a clip."""
+        from . import frame_score as _frames
+
+        return _frames.transcribe_clips_sweep_frame_scores(self, clips, sample_rates, params, refs, pairs, notes, **tolerances)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
