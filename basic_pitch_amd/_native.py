@@ -259,6 +259,27 @@ class bp_frame_score(C.Structure):
     ]
 
 
+class bp_mp_params(C.Structure):
+    """One parameter set of multi-pitch picking (include/basic_pitch_amd_multipitch.h); `bp_mp_params_default` fills it in."""
+
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("min_bin", C.c_int32),
+        ("max_bin", C.c_int32),
+        ("reserved", C.c_int32),
+    ]
+
+
+class bp_f0_point(C.Structure):
+    """One f0 peak of a contour row (include/basic_pitch_amd_multipitch.h)."""
+
+    _fields_ = [
+        ("frame", C.c_int32),
+        ("salience", C.c_float),
+        ("pitch_midi", C.c_double),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -404,6 +425,16 @@ FRAME_SCORE_SYMBOLS = [
     "bp_score_note_frames",
     "bp_note_events_sweep_frame_score",
     "bp_infer_clips_events_sweep_frame_score",
+]
+# every symbol include/basic_pitch_amd_multipitch.h declares (bound in basic_pitch_amd/multipitch.py)
+MULTIPITCH_SYMBOLS = [
+    "bp_mp_params_default",
+    "bp_multipitch_rows",
+    "bp_score_f0_frames",
+    "bp_multipitch_from_maps",
+    "bp_infer_clips_multipitch",
+    "bp_multipitch_sweep_frame_score",
+    "bp_infer_clips_multipitch_sweep_frame_score",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

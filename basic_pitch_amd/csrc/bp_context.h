@@ -112,6 +112,20 @@ struct bp_context {
   Buffer<bp::NoteFrameRef> fs_refs;
   Buffer<int64_t> fs_out;
   bp::PinnedBuffer<int64_t> fs_home;
+  // multi-pitch estimates (bp_multipitch_from_maps and its kin, clips_api.hip), all grow-only, scratch of one call and grown
+  // by those calls alone: the device copy of a contour map given in host memory, per row its peak count and segment, the
+  // points before each row, per segment the not-finite flag, the point offsets with the statuses behind them, the points; of a
+  // scored sweep the sets, the decode table, the refs in pitch order and the counts [decodes][5] with the statuses (32-bit)
+  // behind them; and the page-locked block offsets or counts come home in
+  Buffer<float> mp_contour;
+  Buffer<int2> mp_rows;
+  Buffer<int64_t> mp_first, mp_meta, mp_out;
+  Buffer<int32_t> mp_bad;
+  Table mp_points;
+  Buffer<bp::MpParams> mp_sets;
+  Buffer<bp::MpDecode> mp_dec;
+  Buffer<bp::MpRef> mp_refs;
+  bp::PinnedBuffer<int64_t> mp_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

@@ -295,6 +295,42 @@ size_t note_frames_lds_bytes(int64_t max_rows);
 hipError_t launch_note_frames(const void* counts, const int64_t* rows, const int64_t* ev_first, const void* ev_pool,
                               const NoteScoreDecode* dec, const NoteFrameRef* refs, int64_t n_decodes, int64_t max_rows, int64_t* out,
                               hipStream_t s);
+// multipitch.hip: the f0 peaks of contour rows (include/basic_pitch_amd_multipitch.h).  T rows in n_segs
+// segments, segment i at rows [offs[i], offs[i + 1]) (offs on the device).
+// count: row_info[r] = {the peaks of row r, its segment}, seg_bad[i] != 0 where a cell of segment i is not finite (zeroed by
+// the caller).  scan: row_first[r] = the points before row r with the rows of flagged segments empty, row_first[T] the total;
+// meta = point_offsets [n_segs + 1], then as 32-bit words the statuses [n_segs].  write: the points (16-byte bp_f0_point
+// records) of every row at row_first[r]; the caller has made sure that row_first[T] of them fit.
+constexpr int kMpBins = 264, kMpScanTile = 1024;  // BP_MP_BINS, BP_MP_SCAN_TILE_ROWS
+struct MpParams {  // bp_mp_params
+  float threshold;
+  int32_t min_bin, max_bin, reserved;
+};
+hipError_t launch_mp_count(const float* contour, const int64_t* offs, int64_t n_segs, int64_t T, MpParams p, int2* row_info,
+                           int32_t* seg_bad, hipStream_t s);
+hipError_t launch_mp_scan(const int2* row_info, const int32_t* seg_bad, const int64_t* offs, int64_t n_segs, int64_t T,
+                          int64_t* row_first, int64_t* meta, hipStream_t s);
+hipError_t launch_mp_write(const float* contour, int64_t T, MpParams p, const int2* row_info, const int32_t* seg_bad,
+                           const int64_t* offs, const int64_t* row_first, void* points, hipStream_t s);
+// The decodes of a multi-pitch sweep scored frame by frame, one workgroup per decode: decode j is rows [first, first + rows)
+// of contour under sets[set] against refs[ref_first ... ref_first + n_ref), its segment's IN ASCENDING PITCH with the frames
+// they sound on.  out: [n_decodes] {n_frames, ref_frames, est_frames, true_pos, e_sub}, then as 32-bit words [n_decodes]
+// status (1: a cell is not finite; 3: n_ref > kNoteScoreMaxNotes).
+struct MpRef {
+  int32_t f0, f1;  // sounds on frames f0 ... f1 - 1 of its segment
+  double pitch;
+};
+struct MpDecode {
+  int64_t first, rows, ref_first;
+  int32_t n_ref, set;  // n_ref at most kNoteScoreMaxNotes + 1 (more: the same status)
+};
+struct MpScoreParams {
+  double pitch_tolerance_cents;
+  bool strict;
+};
+constexpr int64_t kMpSweepLongRows = 2048;  // a job whose longest decode has more rows gets workgroups of 16 waves, not 4
+hipError_t launch_mp_sweep_frames(const float* contour, const MpParams* sets, const MpDecode* dec, const MpRef* refs,
+                                  MpScoreParams sp, int64_t n_decodes, int64_t max_rows, int64_t* out, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -1,7 +1,8 @@
 // C ABI of the jobs of many clips (include/basic_pitch_amd_clips.h, _events.h, _flac_clips.h, _sweep.h): many short clips through the
 // model in one call — raw PCM, FLAC or IMA ADPCM files' bytes decoded on the device, or maps the caller already holds — and home either
 // the note candidates of every clip or, the tracker run on the device too, the note events alone: under one parameter set, or
-// (a sweep) every segment under many.
+// (a sweep) every segment under many; or, of the contour rows alone, the f0 peaks of every segment and the frame-level counts of
+// threshold sweeps over them (include/basic_pitch_amd_multipitch.h).
 //
 // Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
 //   the sink's fixed arguments -> the source's plan (rows of every clip) -> the outputs against the rows -> statuses and the
@@ -20,6 +21,7 @@
 #include "../../include/basic_pitch_amd_flac_clips.h"
 #include "../../include/basic_pitch_amd_score.h"
 #include "../../include/basic_pitch_amd_frame_score.h"
+#include "../../include/basic_pitch_amd_multipitch.h"
 #include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
@@ -32,6 +34,7 @@ extern "C" int64_t bp_internal_score_bad_ref(const bp_ref_note* refs, int64_t n)
 extern "C" double bp_internal_score_offset_tol(const bp_ref_note* r, const bp_score_params* p);
 extern "C" void bp_internal_frame_interval(double start_s, double end_s, int64_t n_frames, int64_t* f0, int64_t* f1);
 extern "C" void bp_internal_frame_pitch_range(const bp_ref_note* r, const bp_score_params* p, int32_t* lo, int32_t* hi);
+extern "C" const char* bp_internal_mp_bad_params(const bp_mp_params* p);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 namespace bp {
@@ -508,7 +511,7 @@ struct JobSource {
 // params is null, every set has its own dense half.  kScoreHome: the same sweep, but what goes home is `scores` and out.status
 // alone — every decode's events scored on the device against the refs of its segment (include/basic_pitch_amd_score.h).
 // with_frames: the calls of include/basic_pitch_amd_frame_score.h — `frames` goes home too, and `scores` may be null.
-enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome };
+enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome };
 struct JobSink {
   JobSinkKind kind;
   const bp_note_params* params;
@@ -528,6 +531,13 @@ struct JobSink {
   bp_note_score* scores;
   bool with_frames;
   bp_frame_score* frames;
+  // kMultiPitchHome: the points (include/basic_pitch_amd_multipitch.h) of the n segments under mp_params[0], out.status per
+  // segment.  kMultiPitchScoreHome: n_decodes decodes of the segments under mp_params[0 ... n_sets), scored against the refs:
+  // `frames` and out.status alone go home.
+  const bp_mp_params* mp_params;
+  bp_f0_point* points;
+  int64_t max_points;
+  int64_t* point_offsets;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -561,6 +571,23 @@ JobSink frame_score_sink(int64_t n_sets, const bp_note_params* sets, int64_t n_d
                          bp_frame_score* frames, int* status) {
   JobSink k = score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, status);
   k.with_frames = true, k.frames = frames;
+  return k;
+}
+
+JobSink multipitch_sink(const bp_mp_params* p, bp_f0_point* points, int64_t max_points, int64_t* point_offsets, int* status) {
+  JobSink k{};
+  k.kind = kMultiPitchHome, k.out.status = status;
+  k.mp_params = p, k.points = points, k.max_points = max_points, k.point_offsets = point_offsets;
+  return k;
+}
+
+JobSink multipitch_score_sink(int64_t n_sets, const bp_mp_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                              const int64_t* ref_offsets, const bp_ref_note* refs, const bp_score_params* score_params,
+                              bp_frame_score* frames, int* status) {
+  JobSink k{};
+  k.kind = kMultiPitchScoreHome, k.out.status = status;
+  k.mp_params = sets, k.n_sets = n_sets, k.n_decodes = n_decodes, k.decodes = decodes;
+  k.ref_offsets = ref_offsets, k.refs = refs, k.score_params = score_params, k.with_frames = true, k.frames = frames;
   return k;
 }
 
@@ -617,6 +644,25 @@ void score_nothing(const JobSink& k, int64_t j, int64_t seg, int64_t rows) {
   if (k.frames) k.frames[j] = bp_frame_score{rows, 0, 0, 0, 0};
 }
 
+// the decode table of a sweep against its segments and sets; decodes null: the cross product
+int check_decode_table(bp_handle h, const char* what, int64_t n_segs, int64_t n_sets, int64_t n_decodes, const bp_sweep_decode* decodes) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (!decodes) {
+    const bool product = n_segs == 0 || n_sets == 0 ? n_decodes == 0 : n_decodes % n_segs == 0 && n_decodes / n_segs == n_sets;
+    if (!product) return invalid("decodes is NULL (the cross product) and n_decodes is not n_sets * n_segments");
+    return BP_OK;
+  }
+  for (int64_t j = 0; j < n_decodes; ++j) {
+    const bp_sweep_decode& d = decodes[j];
+    if (d.reserved != 0) return invalid("decode " + std::to_string(j) + ": reserved must be 0");
+    if (d.params < 0 || d.params >= n_sets)
+      return invalid("decode " + std::to_string(j) + ": params " + std::to_string(d.params) + " is not one of the " + std::to_string(n_sets) + " sets");
+    if (d.segment < 0 || d.segment >= n_segs)
+      return invalid("decode " + std::to_string(j) + ": segment " + std::to_string(d.segment) + " is not one of the " + std::to_string(n_segs) + " segments");
+  }
+  return BP_OK;
+}
+
 // every argument of a sweep that is not a segment's, before anything is queued
 int check_sweep(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
   auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
@@ -630,20 +676,7 @@ int check_sweep(bp_handle h, const char* what, int64_t n_segs, const JobSink& k)
                    "): split the job");
   for (int64_t p = 0; p < k.n_sets; ++p)
     if (const char* why = bad_params(k.sets[p])) return invalid("set " + std::to_string(p) + ": " + why);
-  if (!k.decodes) {
-    const bool product = n_segs == 0 || k.n_sets == 0 ? k.n_decodes == 0 : k.n_decodes % n_segs == 0 && k.n_decodes / n_segs == k.n_sets;
-    if (!product) return invalid("decodes is NULL (the cross product) and n_decodes is not n_sets * n_segments");
-    return BP_OK;
-  }
-  for (int64_t j = 0; j < k.n_decodes; ++j) {
-    const bp_sweep_decode& d = k.decodes[j];
-    if (d.reserved != 0) return invalid("decode " + std::to_string(j) + ": reserved must be 0");
-    if (d.params < 0 || d.params >= k.n_sets)
-      return invalid("decode " + std::to_string(j) + ": params " + std::to_string(d.params) + " is not one of the " + std::to_string(k.n_sets) + " sets");
-    if (d.segment < 0 || d.segment >= n_segs)
-      return invalid("decode " + std::to_string(j) + ": segment " + std::to_string(d.segment) + " is not one of the " + std::to_string(n_segs) + " segments");
-  }
-  return BP_OK;
+  return check_decode_table(h, what, n_segs, k.n_sets, k.n_decodes, k.decodes);
 }
 
 // The decodes against the rows (offs: of the n_segs segments): every decode's tracker parameters and regions, the dense keys of
@@ -747,6 +780,11 @@ struct ClipsJob {
   EventsJob ev{};
   EventsPlan plan;
   bool exported_by_kernel = false;
+  // kMultiPitchHome, kMultiPitchScoreHome: where the contour rows lie on the device (the write pass runs after the first
+  // wait); the decode table and the refs in pitch order as multipitch.hip reads them
+  const float* mp_contour = nullptr;
+  std::vector<MpDecode> mp_dec;
+  std::vector<MpRef> mp_refs;
 };
 
 // A sweep behind the maps of its n_segs segments (offs: their rows, T > 0 in all): the dense half once per key — the note rows
@@ -862,12 +900,169 @@ int queue_sweep(bp_handle h, const Maps& all, int64_t n_segs, const int64_t* off
   return BP_OK;
 }
 
+// ---- multi-pitch estimates: the f0 peaks of the contour rows (include/basic_pitch_amd_multipitch.h) ---------------
+MpParams mp_device_params(const bp_mp_params& p) { return MpParams{p.threshold, p.min_bin, p.max_bin, 0}; }
+
+// the sink's fixed arguments, before anything is queued
+int check_multipitch(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (k.kind == kMultiPitchHome) {
+    if (n_segs < 0 || !k.point_offsets || (n_segs > 0 && !k.out.status))
+      return invalid("negative n_segments / n_clips, null point_offsets or status");
+    if (k.max_points < 0 || (k.max_points > 0 && !k.points)) return invalid("negative max_points, or room without a buffer");
+    if (const char* why = bp_internal_mp_bad_params(k.mp_params)) return invalid(std::string("params: ") + why);
+    return BP_OK;
+  }
+  if (n_segs < 0 || k.n_sets < 0 || k.n_decodes < 0 || (k.n_sets > 0 && !k.mp_params) || (k.n_decodes > 0 && !k.out.status))
+    return invalid("negative n_segments / n_clips, n_sets or n_decodes, null sets or status");
+  if (k.n_decodes > BP_SWEEP_MAX_DECODES)
+    return invalid(std::to_string(k.n_decodes) + " decodes, more than BP_SWEEP_MAX_DECODES (" + std::to_string(BP_SWEEP_MAX_DECODES) +
+                   "): split the job");
+  for (int64_t p = 0; p < k.n_sets; ++p)
+    if (const char* why = bp_internal_mp_bad_params(k.mp_params + p)) return invalid("set " + std::to_string(p) + ": " + why);
+  if (int rc = check_decode_table(h, what, n_segs, k.n_sets, k.n_decodes, k.decodes)) return rc;
+  return check_score(h, what, n_segs, k);
+}
+
+// The outputs against the rows (offs: of the n segments).  *queued false: nothing needs the device and the outputs are
+// complete.  A scored sweep: the decode table, and per segment its refs in ascending pitch with the frames they sound on, by the
+// checker's own function.
+int plan_multipitch(bp_handle h, const char* what, int64_t n, const int64_t* offs, const JobSink& k, ClipsJob& job, bool* queued) {
+  const auto too_many = [&](int64_t rows) {
+    return invalid(h, what, std::to_string(rows) + " rows in all, more than BP_SWEEP_MAX_ROWS (" + std::to_string(BP_SWEEP_MAX_ROWS) +
+                                "): split the job");
+  };
+  if (k.kind == kMultiPitchHome) {
+    if (offs[n] > BP_SWEEP_MAX_ROWS) return too_many(offs[n]);
+    *queued = offs[n] > 0;
+    for (int64_t i = 0; i <= n && !*queued; ++i) k.point_offsets[i] = 0;
+    for (int64_t i = 0; i < n && !*queued; ++i) k.out.status[i] = 0;
+    return BP_OK;
+  }
+  job.mp_dec.resize((size_t)k.n_decodes);
+  int64_t rows_in_all = 0;
+  for (int64_t j = 0; j < k.n_decodes; ++j) {
+    const int64_t i = k.decodes ? k.decodes[j].segment : j % n;
+    const int32_t p = k.decodes ? k.decodes[j].params : (int32_t)(j / n);
+    const int64_t first = k.ref_offsets[i];
+    job.mp_dec[(size_t)j] = MpDecode{offs[i], offs[i + 1] - offs[i], first,
+                                     (int32_t)std::min<int64_t>(k.ref_offsets[i + 1] - first, kNoteScoreMaxNotes + 1), p};
+    rows_in_all += offs[i + 1] - offs[i];
+  }
+  if (rows_in_all > BP_SWEEP_MAX_ROWS) return too_many(rows_in_all);
+  *queued = rows_in_all > 0;
+  if (!*queued) {  // (every decode is of a segment without rows)
+    for (int64_t j = 0; j < k.n_decodes; ++j) {
+      k.frames[j] = bp_frame_score{0, 0, 0, 0, 0};
+      k.out.status[j] = job.mp_dec[(size_t)j].n_ref > kNoteScoreMaxNotes ? 3 : 0;
+    }
+    return BP_OK;
+  }
+  job.mp_refs.resize((size_t)k.ref_offsets[n]);
+  std::vector<int64_t> order;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t first = k.ref_offsets[i], rows = offs[i + 1] - offs[i];
+    order.resize((size_t)(k.ref_offsets[i + 1] - first));
+    for (size_t r = 0; r < order.size(); ++r) order[r] = first + (int64_t)r;
+    std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return k.refs[a].pitch_midi < k.refs[b].pitch_midi; });
+    for (size_t r = 0; r < order.size(); ++r) {
+      const bp_ref_note& ref = k.refs[order[r]];
+      int64_t f0 = 0, f1 = 0;
+      bp_internal_frame_interval(ref.start_s, ref.end_s, rows, &f0, &f1);
+      job.mp_refs[(size_t)first + r] = MpRef{(int32_t)f0, (int32_t)f1, ref.pitch_midi};  // (rows <= BP_SWEEP_MAX_ROWS)
+    }
+  }
+  return BP_OK;
+}
+
+// Behind the contour rows of the n segments (on the device, T > 0 in all).  The points: the count pass, the scan, and the
+// offsets and statuses on their way home — the write pass waits for the host's look at the total (multipitch_home).  A scored
+// sweep: its tables, its one launch, the counts with the statuses on their way home.
+int queue_multipitch(bp_handle h, const float* contour, int64_t n, const int64_t* offs, const JobSink& k, ClipsJob& job) {
+  hipStream_t s = h->stream;
+  const int64_t T = offs[n];
+  job.mp_contour = contour;
+  if (k.kind == kMultiPitchHome) {
+    const size_t n_meta = (size_t)(n + 1 + (n + 1) / 2);
+    BP_HIP(h->clip_rows.reserve((size_t)n + 1));
+    BP_HIP(h->mp_rows.reserve((size_t)T));
+    BP_HIP(h->mp_first.reserve((size_t)T + 1));
+    BP_HIP(h->mp_bad.reserve((size_t)n));
+    BP_HIP(h->mp_meta.reserve(n_meta));
+    BP_HIP(h->mp_home.reserve(n_meta));
+    BP_HIP(hipMemcpyAsync(h->clip_rows, offs, (size_t)(n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, s));
+    BP_HIP(hipMemsetAsync(h->mp_bad, 0, (size_t)n * sizeof(int32_t), s));
+    BP_HIP(launch_mp_count(contour, h->clip_rows, n, T, mp_device_params(*k.mp_params), h->mp_rows, h->mp_bad, s));
+    BP_HIP(launch_mp_scan(h->mp_rows, h->mp_bad, h->clip_rows, n, T, h->mp_first, h->mp_meta, s));
+    BP_HIP(hipMemcpyAsync(h->mp_home, h->mp_meta, n_meta * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+    return BP_OK;
+  }
+  const int64_t nd = k.n_decodes;
+  const size_t n_out = (size_t)(5 * nd + (nd + 1) / 2);
+  int64_t max_rows = 0;
+  for (const MpDecode& d : job.mp_dec) max_rows = std::max(max_rows, d.rows);
+  static_assert(sizeof(MpParams) == sizeof(bp_mp_params), "the sets go to the device as they are");
+  BP_HIP(h->mp_sets.reserve((size_t)k.n_sets));
+  BP_HIP(h->mp_dec.reserve((size_t)nd));
+  BP_HIP(h->mp_refs.reserve(job.mp_refs.size()));
+  BP_HIP(h->mp_out.reserve(n_out));
+  BP_HIP(h->mp_home.reserve(n_out));
+  BP_HIP(hipMemcpyAsync(h->mp_sets, k.mp_params, (size_t)k.n_sets * sizeof(MpParams), hipMemcpyHostToDevice, s));
+  BP_HIP(hipMemcpyAsync(h->mp_dec, job.mp_dec.data(), (size_t)nd * sizeof(MpDecode), hipMemcpyHostToDevice, s));
+  if (!job.mp_refs.empty())
+    BP_HIP(hipMemcpyAsync(h->mp_refs, job.mp_refs.data(), job.mp_refs.size() * sizeof(MpRef), hipMemcpyHostToDevice, s));
+  BP_HIP(launch_mp_sweep_frames(contour, h->mp_sets, h->mp_dec, h->mp_refs,
+                                MpScoreParams{k.score_params->pitch_tolerance_cents, k.score_params->strict != 0}, nd, max_rows, h->mp_out, s));
+  BP_HIP(hipMemcpyAsync(h->mp_home, h->mp_out, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+// The stream has drained.  The points: the offsets and statuses are in the page-locked block; when the total fits the
+// caller's room, the write pass and the points home, and the wait for them.  A scored sweep: the counts and statuses.
+int multipitch_home(bp_handle h, const char* what, int64_t n, const int64_t* offs, const JobSink& k, const ClipsJob& job) {
+  if (k.kind == kMultiPitchScoreHome) {
+    std::memcpy(k.frames, h->mp_home, (size_t)k.n_decodes * sizeof(bp_frame_score));
+    const int32_t* st = reinterpret_cast<const int32_t*>(h->mp_home + 5 * k.n_decodes);
+    for (int64_t j = 0; j < k.n_decodes; ++j) k.out.status[j] = st[j];
+    return BP_OK;
+  }
+  const int64_t* meta = h->mp_home;
+  const int32_t* st = reinterpret_cast<const int32_t*>(meta + n + 1);
+  const int64_t total = meta[n];
+  for (int64_t i = 0; i <= n; ++i) k.point_offsets[i] = meta[i];
+  for (int64_t i = 0; i < n; ++i) k.out.status[i] = st[i];
+  if (total > k.max_points) {
+    h->err = std::string(what) + ": output buffer too small: " + std::to_string(total) +
+             " points are needed (point_offsets[n] holds them; nothing has been written to points)";
+    return BP_ERR_INVALID_ARG;
+  }
+  if (total == 0) return BP_OK;
+  auto write = [&]() -> int {
+    BP_HIP(h->mp_points.reserve((size_t)total * sizeof(bp_f0_point)));
+    BP_HIP(launch_mp_write(job.mp_contour, offs[n], mp_device_params(*k.mp_params), h->mp_rows, h->mp_bad, h->clip_rows, h->mp_first,
+                           h->mp_points, h->stream));
+    BP_HIP(hipMemcpyAsync(k.points, h->mp_points, (size_t)total * sizeof(bp_f0_point), hipMemcpyDeviceToHost, h->stream));
+    return BP_OK;
+  };
+  return finish(h, write());
+}
+
 // everything a job queues: the source (the maps of all segments to track_out, concatenated by job.offs), the dense half of
 // note decoding for every segment as its own track, the sink
 int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) {
   Maps all{};
   int rc = BP_OK;
-  if (s.kind == kGivenMaps) {
+  const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
+  if (s.kind == kGivenMaps && multipitch) {
+    // the contour rows alone, read where they lie: a map in host memory gets a device copy, one in device memory is not copied
+    all.contour = const_cast<float*>(s.contour);
+    if (s.mem_kind == BP_MEM_HOST) {
+      const size_t cells = (size_t)job.offs[s.n] * kFreqC;
+      BP_HIP(h->mp_contour.reserve(cells));
+      BP_HIP(hipMemcpyAsync(h->mp_contour, s.contour, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      all.contour = h->mp_contour;
+    }
+  } else if (s.kind == kGivenMaps) {
     rc = take_given_maps(h, s.note, s.onset, s.contour, job.offs[s.n], s.mem_kind, &all);
   } else {
     const bp_clip* clips = s.clips;
@@ -893,6 +1088,7 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
                           job.offs, job.tab, &all);
   }
   if (rc) return rc;
+  if (multipitch) return queue_multipitch(h, all.contour, s.n, job.offs, k, job);
   if (k.kind == kCandidatesHome)
     return queue_clips_candidates(h, all, s.n, job.offs, k.params, k.note_out, k.cand_bits, k.bend_map, &job.exported_by_kernel);
   uint8_t* d_bits = nullptr;
@@ -910,9 +1106,12 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   const int64_t n = src.n;
   const bool flac = src.kind == kFlacClips, score = k.kind == kScoreHome, sweep = k.kind == kSweepHome || score;
   const bool events = k.kind == kEventsHome || sweep;
+  const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
   int rc = BP_OK;
   // the sink's fixed arguments
-  if (events) {
+  if (multipitch) {
+    if ((rc = check_multipitch(h, what, n, k))) return rc;
+  } else if (events) {
     if ((rc = sweep ? check_sweep(h, what, n, k) : check_events(h, what, n, k.params, k.out))) return rc;
     if (score && (rc = check_score(h, what, n, k))) return rc;
     if (flac && src.sample_rate < 1) return invalid("no sample rate");
@@ -928,7 +1127,7 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
     for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
     if (!ordered || (src.mem_kind != BP_MEM_HOST && src.mem_kind != BP_MEM_DEVICE))
       return invalid("row_offsets must start at 0 and never decrease; mem_kind must be BP_MEM_HOST or BP_MEM_DEVICE");
-    if (src.row_offsets[n] > 0 && (!src.note || !src.onset || !src.contour)) return invalid("null input pointer");
+    if (src.row_offsets[n] > 0 && (!src.contour || (!multipitch && (!src.note || !src.onset)))) return invalid("null input pointer");
     job.offs = src.row_offsets;
   } else {
     if (flac) {
@@ -943,6 +1142,15 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
     job.offs = job.flac.offs.data();
   }
   const int64_t total = job.offs[n];
+  if (multipitch) {  // the points or the counts of the contour rows: no note decoding, and a wait before the points are written
+    bool queued = false;
+    if ((rc = plan_multipitch(h, what, n, job.offs, k, job, &queued)) || !queued) return rc;
+    BP_HIP(hipSetDevice(h->device));
+    if (src.kind != kGivenMaps && src.sample_rate != h->rate)
+      if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
+    if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
+    return multipitch_home(h, what, n, job.offs, k, job);
+  }
   if (!events && total > 0 && (!k.note_out || !k.cand_bits)) return invalid("null output pointer");
   // the statuses the host knows, and the jobs that need no device work
   if (!events)
@@ -1076,6 +1284,36 @@ int bp_infer_clips_events_sweep_frame_score(bp_handle h, int64_t n_clips, const 
                                             int* status) {
   return run_clips(h, "bp_infer_clips_events_sweep_frame_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
                    frame_score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, frames, status));
+}
+
+// ---- multi-pitch estimates (include/basic_pitch_amd_multipitch.h) -------------------------------------------------------------------
+int bp_multipitch_from_maps(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* contour, int mem_kind,
+                            const bp_mp_params* p, bp_f0_point* points, int64_t max_points, int64_t* point_offsets, int* status) {
+  return run_clips(h, "bp_multipitch_from_maps", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, nullptr, nullptr, contour},
+                   multipitch_sink(p, points, max_points, point_offsets, status));
+}
+
+int bp_infer_clips_multipitch(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                              const bp_mp_params* p, bp_f0_point* points, int64_t max_points, int64_t* point_offsets, int* status) {
+  return run_clips(h, "bp_infer_clips_multipitch", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   multipitch_sink(p, points, max_points, point_offsets, status));
+}
+
+int bp_multipitch_sweep_frame_score(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* contour, int mem_kind,
+                                    int64_t n_sets, const bp_mp_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                                    const int64_t* ref_offsets, const bp_ref_note* refs, const bp_score_params* score_params,
+                                    bp_frame_score* frames, int* status) {
+  return run_clips(h, "bp_multipitch_sweep_frame_score",
+                   JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, nullptr, nullptr, contour},
+                   multipitch_score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, frames, status));
+}
+
+int bp_infer_clips_multipitch_sweep_frame_score(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                                                int64_t n_sets, const bp_mp_params* sets, int64_t n_decodes,
+                                                const bp_sweep_decode* decodes, const int64_t* ref_offsets, const bp_ref_note* refs,
+                                                const bp_score_params* score_params, bp_frame_score* frames, int* status) {
+  return run_clips(h, "bp_infer_clips_multipitch_sweep_frame_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   multipitch_score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, frames, status));
 }
 
 #ifdef BP_AB_KERNELS

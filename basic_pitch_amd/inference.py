@@ -562,6 +562,43 @@ class Model:
 
         return _frames.transcribe_clips_sweep_frame_scores(self, clips, sample_rates, params, refs, pairs, notes, **tolerances)
 
+    # -- multi-pitch estimates (basic_pitch_amd/multipitch.py) -------------------------------------
+    def multipitch(self, outputs: Sequence[Any], params: Any = None) -> "List[Any]":
+        """The multi-pitch estimate of every segment of `outputs` (the dicts `predict` / `run_inference` return, numpy arrays
+        or CUDA tensors of one kind; their "contour" maps alone are read) in ONE call (`bp_multipitch_from_maps`): the f0 peaks
+        of every contour row — at or above the threshold and above both neighbours, refined by a parabola —, picked and
+        compacted on the device.  `params`: the fields of `bp_mp_params` (threshold 0.3, min_bin 1, max_bin 262 by default).
+        Returns one `multipitch.MultiPitch` per segment: frames, times_s, pitch_midi, salience, freqs_hz, status."""
+        from . import multipitch as _mp
+
+        return _mp.multipitch(self, outputs, params)
+
+    def transcribe_clips_multipitch(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None) -> "List[Any]":
+        """The same behind the model, for many short clips (grouped by sample rate as `transcribe_clips` groups them): the
+        clips of a rate go through the model once (`bp_infer_clips_multipitch`), and the points alone come home."""
+        from . import multipitch as _mp
+
+        return _mp.transcribe_clips_multipitch(self, clips, sample_rates, params)
+
+    def sweep_multipitch_frame_scores(self, outputs: Sequence[Any], sets: Sequence[Any], refs: Sequence[Any],
+                                      pairs: "Optional[Sequence[Tuple[int, int]]]" = None, **tolerances: Any):
+        """Every segment of `outputs` under every set of `sets` (thresholds and bands: the fields of `bp_mp_params`), each
+        decode scored frame by frame against `refs[segment]` ((start_s, end_s, pitch_midi) rows) on the device
+        (`bp_multipitch_sweep_frame_score`): the structured array of `sweep_frame_scores`' frame level, shaped (sets,
+        segments), or one record per pair of `pairs`.  A decode left for too many refs (status 3) is finished on the host; one
+        with a NaN or an infinity in its rows (status 1) has no points and is reported as it is."""
+        from . import multipitch as _mp
+
+        return _mp.sweep_multipitch_frame_scores(self, outputs, sets, refs, pairs, **tolerances)
+
+    def transcribe_clips_sweep_multipitch_frame_scores(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]],
+                                                       sets: Sequence[Any], refs: Sequence[Any],
+                                                       pairs: "Optional[Sequence[Tuple[int, int]]]" = None, **tolerances: Any):
+        """The same behind the model (`bp_infer_clips_multipitch_sweep_frame_score`), a segment being a clip."""
+        from . import multipitch as _mp
+
+        return _mp.transcribe_clips_sweep_multipitch_frame_scores(self, clips, sample_rates, sets, refs, pairs, **tolerances)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
