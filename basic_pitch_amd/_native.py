@@ -280,6 +280,43 @@ class bp_f0_point(C.Structure):
     ]
 
 
+class bp_melody_params(C.Structure):
+    """One parameter set of the melody decode (include/basic_pitch_amd_melody.h); `bp_melody_params_default` fills it in."""
+
+    _fields_ = [
+        ("threshold", C.c_float),
+        ("jump_penalty", C.c_float),
+        ("voicing_penalty", C.c_float),
+        ("max_jump", C.c_int32),
+        ("min_bin", C.c_int32),
+        ("max_bin", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
+class bp_melody_point(C.Structure):
+    """The melody record of one contour row (include/basic_pitch_amd_melody.h); bin -1: unvoiced."""
+
+    _fields_ = [
+        ("bin", C.c_int32),
+        ("salience", C.c_float),
+        ("pitch_midi", C.c_double),
+    ]
+
+
+class bp_melody_score(C.Structure):
+    """The counts the melody measures are formed from (include/basic_pitch_amd_melody.h)."""
+
+    _fields_ = [
+        ("n_frames", C.c_int64),
+        ("ref_voiced", C.c_int64),
+        ("est_voiced", C.c_int64),
+        ("both_voiced", C.c_int64),
+        ("pitch_ok", C.c_int64),
+        ("chroma_ok", C.c_int64),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -435,6 +472,16 @@ MULTIPITCH_SYMBOLS = [
     "bp_infer_clips_multipitch",
     "bp_multipitch_sweep_frame_score",
     "bp_infer_clips_multipitch_sweep_frame_score",
+]
+# every symbol include/basic_pitch_amd_melody.h declares (bound in basic_pitch_amd/melody.py)
+MELODY_SYMBOLS = [
+    "bp_melody_params_default",
+    "bp_melody_rows",
+    "bp_score_melody_frames",
+    "bp_melody_from_maps",
+    "bp_infer_clips_melody",
+    "bp_melody_sweep_score",
+    "bp_infer_clips_melody_sweep_score",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

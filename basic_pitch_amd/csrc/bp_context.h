@@ -126,6 +126,18 @@ struct bp_context {
   Buffer<bp::MpDecode> mp_dec;
   Buffer<bp::MpRef> mp_refs;
   bp::PinnedBuffer<int64_t> mp_home;
+  // the melody (bp_melody_from_maps and its kin, clips_api.hip), all grow-only, scratch of one call and grown by those calls
+  // alone: the device copy of a contour map given in host memory, the sets, the decode table, the predecessors (one byte per
+  // state per row of every decode, bp::kMelodyPredStride bytes a row: the one large pool, 2.3 GB at BP_SWEEP_MAX_ROWS), the
+  // records, a scored sweep's reference track, the counts [decodes][6] with the statuses (32-bit) behind them, and the
+  // page-locked block they come home in
+  Buffer<float> mel_contour;
+  Buffer<bp::MelodyParams> mel_sets;
+  Buffer<bp::MelodyDecode> mel_dec;
+  Table mel_pred, mel_points;
+  Buffer<double> mel_ref;
+  Buffer<int64_t> mel_out;
+  bp::PinnedBuffer<int64_t> mel_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

@@ -331,6 +331,27 @@ struct MpScoreParams {
 constexpr int64_t kMpSweepLongRows = 2048;  // a job whose longest decode has more rows gets workgroups of 16 waves, not 4
 hipError_t launch_mp_sweep_frames(const float* contour, const MpParams* sets, const MpDecode* dec, const MpRef* refs,
                                   MpScoreParams sp, int64_t n_decodes, int64_t max_rows, int64_t* out, hipStream_t s);
+// melody.hip: one f0 track per decode by a Viterbi recurrence over its rows (include/basic_pitch_amd_melody.h),
+// a workgroup per decode.  Decode j is rows [first, first + rows) of contour under sets[set]; its predecessors go to rows
+// [pred_first, pred_first + rows) of pred (kMelodyPredStride bytes a row, regions of distinct decodes disjoint).  points given:
+// record r of decode j at points[first + r] (16-byte bp_melody_point records).  points null: the records are scored against
+// ref_pitch[first + r] instead and scores[j] = {n_frames, ref_voiced, est_voiced, both_voiced, pitch_ok, chroma_ok}.  status[j]:
+// 0, or 1 where a cell of the rows is NaN or above 65536 in magnitude (unvoiced records, or {n_frames, 0, 0, 0, 0, 0}).
+// max_jump: the largest max_jump of the sets the decodes name; a launch whose sets all stay within kMelodyNarrowJump reads
+// windows of that width, any other the full kMelodyMaxJump on either side.
+constexpr int kMelodyMaxJump = 16, kMelodyReadAhead = 8, kMelodyTileRows = 128, kMelodyPredStride = 272;  // BP_MELODY_*
+constexpr int kMelodyNarrowJump = 4;
+struct MelodyParams {  // bp_melody_params
+  float threshold, jump_penalty, voicing_penalty;
+  int32_t max_jump, min_bin, max_bin, reserved[2];
+};
+struct MelodyDecode {
+  int64_t first, rows, pred_first;
+  int32_t set, reserved;
+};
+hipError_t launch_melody(const float* contour, const MelodyParams* sets, const MelodyDecode* dec, int64_t n_decodes, int max_jump,
+                         uint8_t* pred, void* points, const double* ref_pitch, MpScoreParams sp, int64_t* scores, int32_t* status,
+                         hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -2,7 +2,8 @@
 // model in one call — raw PCM, FLAC or IMA ADPCM files' bytes decoded on the device, or maps the caller already holds — and home either
 // the note candidates of every clip or, the tracker run on the device too, the note events alone: under one parameter set, or
 // (a sweep) every segment under many; or, of the contour rows alone, the f0 peaks of every segment and the frame-level counts of
-// threshold sweeps over them (include/basic_pitch_amd_multipitch.h).
+// threshold sweeps over them (include/basic_pitch_amd_multipitch.h); or the melody of every segment, one f0 track by a Viterbi
+// recurrence, and the melody measures of parameter sweeps over it (include/basic_pitch_amd_melody.h).
 //
 // Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
 //   the sink's fixed arguments -> the source's plan (rows of every clip) -> the outputs against the rows -> statuses and the
@@ -22,6 +23,7 @@
 #include "../../include/basic_pitch_amd_score.h"
 #include "../../include/basic_pitch_amd_frame_score.h"
 #include "../../include/basic_pitch_amd_multipitch.h"
+#include "../../include/basic_pitch_amd_melody.h"
 #include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
@@ -35,6 +37,8 @@ extern "C" double bp_internal_score_offset_tol(const bp_ref_note* r, const bp_sc
 extern "C" void bp_internal_frame_interval(double start_s, double end_s, int64_t n_frames, int64_t* f0, int64_t* f1);
 extern "C" void bp_internal_frame_pitch_range(const bp_ref_note* r, const bp_score_params* p, int32_t* lo, int32_t* hi);
 extern "C" const char* bp_internal_mp_bad_params(const bp_mp_params* p);
+extern "C" const char* bp_internal_melody_bad_params(const bp_melody_params* p);  // melody_host.cpp
+extern "C" int64_t bp_internal_melody_bad_ref(const double* ref_pitch, int64_t n);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 namespace bp {
@@ -511,7 +515,7 @@ struct JobSource {
 // params is null, every set has its own dense half.  kScoreHome: the same sweep, but what goes home is `scores` and out.status
 // alone — every decode's events scored on the device against the refs of its segment (include/basic_pitch_amd_score.h).
 // with_frames: the calls of include/basic_pitch_amd_frame_score.h — `frames` goes home too, and `scores` may be null.
-enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome };
+enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome, kMelodyHome, kMelodyScoreHome };
 struct JobSink {
   JobSinkKind kind;
   const bp_note_params* params;
@@ -538,6 +542,13 @@ struct JobSink {
   bp_f0_point* points;
   int64_t max_points;
   int64_t* point_offsets;
+  // kMelodyHome: the records (include/basic_pitch_amd_melody.h) of the n segments under mel_params[0], a record per row, room
+  // for max_points of them, out.status per segment.  kMelodyScoreHome: n_decodes decodes of the segments under mel_params[0 ...
+  // n_sets), scored against ref_pitch (parallel to the rows of the segments): mel_scores and out.status alone go home.
+  const bp_melody_params* mel_params;
+  bp_melody_point* mel_points;
+  const double* ref_pitch;
+  bp_melody_score* mel_scores;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -588,6 +599,22 @@ JobSink multipitch_score_sink(int64_t n_sets, const bp_mp_params* sets, int64_t 
   k.kind = kMultiPitchScoreHome, k.out.status = status;
   k.mp_params = sets, k.n_sets = n_sets, k.n_decodes = n_decodes, k.decodes = decodes;
   k.ref_offsets = ref_offsets, k.refs = refs, k.score_params = score_params, k.with_frames = true, k.frames = frames;
+  return k;
+}
+
+JobSink melody_sink(const bp_melody_params* p, bp_melody_point* points, int64_t max_points, int* status) {
+  JobSink k{};
+  k.kind = kMelodyHome, k.out.status = status;
+  k.mel_params = p, k.mel_points = points, k.max_points = max_points;
+  return k;
+}
+
+JobSink melody_score_sink(int64_t n_sets, const bp_melody_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                          const double* ref_pitch, const bp_score_params* score_params, bp_melody_score* scores, int* status) {
+  JobSink k{};
+  k.kind = kMelodyScoreHome, k.out.status = status;
+  k.mel_params = sets, k.n_sets = n_sets, k.n_decodes = n_decodes, k.decodes = decodes;
+  k.ref_pitch = ref_pitch, k.score_params = score_params, k.mel_scores = scores;
   return k;
 }
 
@@ -785,6 +812,7 @@ struct ClipsJob {
   const float* mp_contour = nullptr;
   std::vector<MpDecode> mp_dec;
   std::vector<MpRef> mp_refs;
+  std::vector<MelodyDecode> mel_dec;  // kMelodyHome: a decode per segment; kMelodyScoreHome: the decode table
 };
 
 // A sweep behind the maps of its n_segs segments (offs: their rows, T > 0 in all): the dense half once per key — the note rows
@@ -1047,20 +1075,128 @@ int multipitch_home(bp_handle h, const char* what, int64_t n, const int64_t* off
   return finish(h, write());
 }
 
+// ---- the melody: one f0 track per segment by a Viterbi recurrence (include/basic_pitch_amd_melody.h) ---------------
+// the sink's fixed arguments, before anything is queued
+int check_melody(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (k.kind == kMelodyHome) {
+    if (n_segs < 0 || (n_segs > 0 && !k.out.status)) return invalid("negative n_segments / n_clips, or null status");
+    if (k.max_points < 0 || (k.max_points > 0 && !k.mel_points)) return invalid("negative max_points, or room without a buffer");
+    if (const char* why = bp_internal_melody_bad_params(k.mel_params)) return invalid(std::string("params: ") + why);
+    return BP_OK;
+  }
+  if (n_segs < 0 || k.n_sets < 0 || k.n_decodes < 0 || (k.n_sets > 0 && !k.mel_params) || (k.n_decodes > 0 && (!k.out.status || !k.mel_scores)))
+    return invalid("negative n_segments / n_clips, n_sets or n_decodes, null sets, scores or status");
+  if (k.n_decodes > BP_SWEEP_MAX_DECODES)
+    return invalid(std::to_string(k.n_decodes) + " decodes, more than BP_SWEEP_MAX_DECODES (" + std::to_string(BP_SWEEP_MAX_DECODES) +
+                   "): split the job");
+  for (int64_t p = 0; p < k.n_sets; ++p)
+    if (const char* why = bp_internal_melody_bad_params(k.mel_params + p)) return invalid("set " + std::to_string(p) + ": " + why);
+  if (int rc = check_decode_table(h, what, n_segs, k.n_sets, k.n_decodes, k.decodes)) return rc;
+  if (const char* why = bp_internal_score_bad_params(k.score_params)) return invalid(why);
+  return BP_OK;
+}
+
+// The outputs against the rows (offs: of the n segments): the room, the reference track, the bound, the decode table with
+// every decode's region of the predecessor pool.  *queued false: nothing needs the device and the outputs are complete.
+int plan_melody(bp_handle h, const char* what, int64_t n, const int64_t* offs, const JobSink& k, ClipsJob& job, bool* queued) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  const auto too_many = [&](int64_t rows) {
+    return invalid(std::to_string(rows) + " rows in all, more than BP_SWEEP_MAX_ROWS (" + std::to_string(BP_SWEEP_MAX_ROWS) + "): split the job");
+  };
+  if (k.kind == kMelodyHome) {
+    if (offs[n] > BP_SWEEP_MAX_ROWS) return too_many(offs[n]);
+    if (k.max_points < offs[n])
+      return invalid("room for " + std::to_string(k.max_points) + " records, but the segments have " + std::to_string(offs[n]) +
+                     " rows and a row is a record (nothing has been written)");
+    *queued = offs[n] > 0;
+    for (int64_t i = 0; i < n; ++i) k.out.status[i] = 0;
+    for (int64_t i = 0; i < n && *queued; ++i)
+      if (offs[i + 1] > offs[i]) job.mel_dec.push_back(MelodyDecode{offs[i], offs[i + 1] - offs[i], offs[i], 0, (int32_t)i});
+    return BP_OK;
+  }
+  if (offs[n] > 0 && !k.ref_pitch) return invalid("null ref_pitch");
+  const int64_t bad = bp_internal_melody_bad_ref(k.ref_pitch, offs[n]);
+  if (bad >= 0) return invalid("ref_pitch " + std::to_string(bad) + ": negative or not finite");
+  job.mel_dec.resize((size_t)k.n_decodes);
+  int64_t rows_in_all = 0;
+  for (int64_t j = 0; j < k.n_decodes; ++j) {
+    const int64_t i = k.decodes ? k.decodes[j].segment : j % n;
+    const int32_t p = k.decodes ? k.decodes[j].params : (int32_t)(j / n);
+    job.mel_dec[(size_t)j] = MelodyDecode{offs[i], offs[i + 1] - offs[i], rows_in_all, p, 0};
+    rows_in_all += offs[i + 1] - offs[i];
+    if (rows_in_all > BP_SWEEP_MAX_ROWS) return too_many(rows_in_all);
+  }
+  *queued = rows_in_all > 0;
+  for (int64_t j = 0; j < k.n_decodes && !*queued; ++j) k.mel_scores[j] = bp_melody_score{0, 0, 0, 0, 0, 0}, k.out.status[j] = 0;
+  return BP_OK;
+}
+
+// Behind the contour rows of the n segments (on the device, T > 0 in all): the tables, the one launch, and the records or
+// the counts with the statuses on their way home.  kMelodyHome: the `reserved` word of a decode is its segment (the kernel
+// does not read it), and the statuses come home per decode.
+int queue_melody(bp_handle h, const float* contour, int64_t n, const int64_t* offs, const JobSink& k, ClipsJob& job) {
+  hipStream_t s = h->stream;
+  const bool scored = k.kind == kMelodyScoreHome;
+  const int64_t nd = (int64_t)job.mel_dec.size(), n_sets = scored ? k.n_sets : 1;
+  int64_t pred_rows = 0;
+  int max_jump = 0;  // of the sets a decode names
+  for (const MelodyDecode& d : job.mel_dec) pred_rows += d.rows, max_jump = std::max(max_jump, (int)k.mel_params[d.set].max_jump);
+  static_assert(sizeof(MelodyParams) == sizeof(bp_melody_params), "the sets go to the device as they are");
+  const size_t n_out = (size_t)((scored ? 6 * nd : 0) + (nd + 1) / 2);
+  BP_HIP(h->mel_sets.reserve((size_t)n_sets));
+  BP_HIP(h->mel_dec.reserve((size_t)nd));
+  BP_HIP(h->mel_pred.reserve((size_t)pred_rows * kMelodyPredStride));
+  BP_HIP(h->mel_out.reserve(n_out));
+  BP_HIP(h->mel_home.reserve(n_out));
+  BP_HIP(hipMemcpyAsync(h->mel_sets, k.mel_params, (size_t)n_sets * sizeof(MelodyParams), hipMemcpyHostToDevice, s));
+  BP_HIP(hipMemcpyAsync(h->mel_dec, job.mel_dec.data(), (size_t)nd * sizeof(MelodyDecode), hipMemcpyHostToDevice, s));
+  int64_t* out = h->mel_out;
+  if (scored) {
+    BP_HIP(h->mel_ref.reserve((size_t)offs[n]));
+    BP_HIP(hipMemcpyAsync(h->mel_ref, k.ref_pitch, (size_t)offs[n] * sizeof(double), hipMemcpyHostToDevice, s));
+    BP_HIP(launch_melody(contour, h->mel_sets, h->mel_dec, nd, max_jump, h->mel_pred, nullptr, h->mel_ref,
+                         MpScoreParams{k.score_params->pitch_tolerance_cents, k.score_params->strict != 0}, out,
+                         reinterpret_cast<int32_t*>(out + 6 * nd), s));
+  } else {
+    BP_HIP(h->mel_points.reserve((size_t)offs[n] * sizeof(bp_melody_point)));
+    BP_HIP(launch_melody(contour, h->mel_sets, h->mel_dec, nd, max_jump, h->mel_pred, h->mel_points, nullptr, MpScoreParams{0.0, false}, nullptr,
+                         reinterpret_cast<int32_t*>(out), s));
+    BP_HIP(hipMemcpyAsync(k.mel_points, h->mel_points, (size_t)offs[n] * sizeof(bp_melody_point), hipMemcpyDeviceToHost, s));
+  }
+  BP_HIP(hipMemcpyAsync(h->mel_home, out, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+// the stream has drained: the statuses, and a scored sweep's counts, are in the page-locked block
+void melody_home(bp_handle h, const JobSink& k, const ClipsJob& job) {
+  const int64_t nd = (int64_t)job.mel_dec.size();
+  if (k.kind == kMelodyScoreHome) {
+    std::memcpy(k.mel_scores, h->mel_home, (size_t)nd * sizeof(bp_melody_score));
+    const int32_t* st = reinterpret_cast<const int32_t*>(h->mel_home + 6 * nd);
+    for (int64_t j = 0; j < nd; ++j) k.out.status[j] = st[j];
+    return;
+  }
+  const int32_t* st = reinterpret_cast<const int32_t*>(static_cast<int64_t*>(h->mel_home));
+  for (int64_t j = 0; j < nd; ++j) k.out.status[job.mel_dec[(size_t)j].reserved] = st[j];
+}
+
 // everything a job queues: the source (the maps of all segments to track_out, concatenated by job.offs), the dense half of
 // note decoding for every segment as its own track, the sink
 int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) {
   Maps all{};
   int rc = BP_OK;
   const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
-  if (s.kind == kGivenMaps && multipitch) {
+  const bool melody = k.kind == kMelodyHome || k.kind == kMelodyScoreHome;
+  if (s.kind == kGivenMaps && (multipitch || melody)) {
     // the contour rows alone, read where they lie: a map in host memory gets a device copy, one in device memory is not copied
     all.contour = const_cast<float*>(s.contour);
     if (s.mem_kind == BP_MEM_HOST) {
+      auto& copy = melody ? h->mel_contour : h->mp_contour;
       const size_t cells = (size_t)job.offs[s.n] * kFreqC;
-      BP_HIP(h->mp_contour.reserve(cells));
-      BP_HIP(hipMemcpyAsync(h->mp_contour, s.contour, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
-      all.contour = h->mp_contour;
+      BP_HIP(copy.reserve(cells));
+      BP_HIP(hipMemcpyAsync(copy, s.contour, cells * sizeof(float), hipMemcpyHostToDevice, h->stream));
+      all.contour = copy;
     }
   } else if (s.kind == kGivenMaps) {
     rc = take_given_maps(h, s.note, s.onset, s.contour, job.offs[s.n], s.mem_kind, &all);
@@ -1089,6 +1225,7 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   }
   if (rc) return rc;
   if (multipitch) return queue_multipitch(h, all.contour, s.n, job.offs, k, job);
+  if (melody) return queue_melody(h, all.contour, s.n, job.offs, k, job);
   if (k.kind == kCandidatesHome)
     return queue_clips_candidates(h, all, s.n, job.offs, k.params, k.note_out, k.cand_bits, k.bend_map, &job.exported_by_kernel);
   uint8_t* d_bits = nullptr;
@@ -1107,10 +1244,13 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   const bool flac = src.kind == kFlacClips, score = k.kind == kScoreHome, sweep = k.kind == kSweepHome || score;
   const bool events = k.kind == kEventsHome || sweep;
   const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
+  const bool melody = k.kind == kMelodyHome || k.kind == kMelodyScoreHome;
   int rc = BP_OK;
   // the sink's fixed arguments
   if (multipitch) {
     if ((rc = check_multipitch(h, what, n, k))) return rc;
+  } else if (melody) {
+    if ((rc = check_melody(h, what, n, k))) return rc;
   } else if (events) {
     if ((rc = sweep ? check_sweep(h, what, n, k) : check_events(h, what, n, k.params, k.out))) return rc;
     if (score && (rc = check_score(h, what, n, k))) return rc;
@@ -1127,7 +1267,7 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
     for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
     if (!ordered || (src.mem_kind != BP_MEM_HOST && src.mem_kind != BP_MEM_DEVICE))
       return invalid("row_offsets must start at 0 and never decrease; mem_kind must be BP_MEM_HOST or BP_MEM_DEVICE");
-    if (src.row_offsets[n] > 0 && (!src.contour || (!multipitch && (!src.note || !src.onset)))) return invalid("null input pointer");
+    if (src.row_offsets[n] > 0 && (!src.contour || (!multipitch && !melody && (!src.note || !src.onset)))) return invalid("null input pointer");
     job.offs = src.row_offsets;
   } else {
     if (flac) {
@@ -1150,6 +1290,16 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
       if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
     if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
     return multipitch_home(h, what, n, job.offs, k, job);
+  }
+  if (melody) {  // the records or the counts of the contour rows: no note decoding, one launch
+    bool queued = false;
+    if ((rc = plan_melody(h, what, n, job.offs, k, job, &queued)) || !queued) return rc;
+    BP_HIP(hipSetDevice(h->device));
+    if (src.kind != kGivenMaps && src.sample_rate != h->rate)
+      if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
+    if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
+    melody_home(h, k, job);
+    return BP_OK;
   }
   if (!events && total > 0 && (!k.note_out || !k.cand_bits)) return invalid("null output pointer");
   // the statuses the host knows, and the jobs that need no device work
@@ -1314,6 +1464,34 @@ int bp_infer_clips_multipitch_sweep_frame_score(bp_handle h, int64_t n_clips, co
                                                 const bp_score_params* score_params, bp_frame_score* frames, int* status) {
   return run_clips(h, "bp_infer_clips_multipitch_sweep_frame_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
                    multipitch_score_sink(n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, frames, status));
+}
+
+// ---- the melody (include/basic_pitch_amd_melody.h) -------------------------------------------------------------------------------
+int bp_melody_from_maps(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* contour, int mem_kind,
+                        const bp_melody_params* p, bp_melody_point* points, int64_t max_points, int* status) {
+  return run_clips(h, "bp_melody_from_maps", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, nullptr, nullptr, contour},
+                   melody_sink(p, points, max_points, status));
+}
+
+int bp_infer_clips_melody(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                          const bp_melody_params* p, bp_melody_point* points, int64_t max_points, int* status) {
+  return run_clips(h, "bp_infer_clips_melody", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   melody_sink(p, points, max_points, status));
+}
+
+int bp_melody_sweep_score(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* contour, int mem_kind,
+                          int64_t n_sets, const bp_melody_params* sets, int64_t n_decodes, const bp_sweep_decode* decodes,
+                          const double* ref_pitch, const bp_score_params* score_params, bp_melody_score* scores, int* status) {
+  return run_clips(h, "bp_melody_sweep_score", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, nullptr, nullptr, contour},
+                   melody_score_sink(n_sets, sets, n_decodes, decodes, ref_pitch, score_params, scores, status));
+}
+
+int bp_infer_clips_melody_sweep_score(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                                      int64_t n_sets, const bp_melody_params* sets, int64_t n_decodes,
+                                      const bp_sweep_decode* decodes, const double* ref_pitch,
+                                      const bp_score_params* score_params, bp_melody_score* scores, int* status) {
+  return run_clips(h, "bp_infer_clips_melody_sweep_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   melody_score_sink(n_sets, sets, n_decodes, decodes, ref_pitch, score_params, scores, status));
 }
 
 #ifdef BP_AB_KERNELS

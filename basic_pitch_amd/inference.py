@@ -599,6 +599,44 @@ class Model:
 
         return _mp.transcribe_clips_sweep_multipitch_frame_scores(self, clips, sample_rates, sets, refs, pairs, **tolerances)
 
+    # -- the melody (basic_pitch_amd/melody.py) ----------------------------------------------------
+    def melody(self, outputs: Sequence[Any], params: Any = None) -> "List[Any]":
+        """The melody of every segment of `outputs` (the dicts `predict` / `run_inference` return, numpy arrays or CUDA
+        tensors of one kind; their "contour" maps alone are read) in ONE call (`bp_melody_from_maps`): one f0 track with
+        voiced / unvoiced decisions per segment, the best path of a Viterbi recurrence over its frames, decoded on the device
+        with a workgroup per segment.  `params`: the fields of `bp_melody_params` (threshold 0.3, jump_penalty 0.05,
+        voicing_penalty 0.5, max_jump 4, bins 0 ... 263 by default).  Returns one `melody.Melody` per segment: bins, times_s,
+        pitch_midi, salience, freqs_hz, voiced, status."""
+        from . import melody as _mel
+
+        return _mel.melody(self, outputs, params)
+
+    def transcribe_clips_melody(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None) -> "List[Any]":
+        """The same behind the model, for many short clips (grouped by sample rate as `transcribe_clips` groups them): the
+        clips of a rate go through the model once (`bp_infer_clips_melody`), and a 16-byte record per row comes home."""
+        from . import melody as _mel
+
+        return _mel.transcribe_clips_melody(self, clips, sample_rates, params)
+
+    def sweep_melody_scores(self, outputs: Sequence[Any], sets: Sequence[Any], ref_tracks: Sequence[Any],
+                            pairs: "Optional[Sequence[Tuple[int, int]]]" = None, **tolerances: Any):
+        """Every segment of `outputs` under every set of `sets` (the fields of `bp_melody_params`), each decode scored on the
+        device against `ref_tracks[segment]` (a MIDI pitch per row, 0.0 unvoiced: `melody.ref_track` makes one from an
+        annotation) by the melody measures' counts (`bp_melody_sweep_score`): a structured array of `melody.MELODY_COUNTS`
+        shaped (sets, segments), or one record per pair of `pairs`; `melody.measures` forms the ratios.  A decode with a NaN
+        or a magnitude above 65536 in its rows (status 1) is all unvoiced and reported as it is."""
+        from . import melody as _mel
+
+        return _mel.sweep_melody_scores(self, outputs, sets, ref_tracks, pairs, **tolerances)
+
+    def transcribe_clips_sweep_melody_scores(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], sets: Sequence[Any],
+                                             ref_tracks: Sequence[Any], pairs: "Optional[Sequence[Tuple[int, int]]]" = None,
+                                             **tolerances: Any):
+        """The same behind the model (`bp_infer_clips_melody_sweep_score`), a segment being a clip."""
+        from . import melody as _mel
+
+        return _mel.transcribe_clips_sweep_melody_scores(self, clips, sample_rates, sets, ref_tracks, pairs, **tolerances)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
