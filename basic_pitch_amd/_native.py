@@ -317,6 +317,27 @@ class bp_melody_score(C.Structure):
     ]
 
 
+class bp_align_state(C.Structure):
+    """One state of a score (include/basic_pitch_amd_align.h): bit p of `active` is pitch 21 + p, `begins` a subset of it."""
+
+    _fields_ = [
+        ("active", C.c_uint64 * 2),
+        ("begins", C.c_uint64 * 2),
+        ("earliest", C.c_int32),
+        ("latest", C.c_int32),
+    ]
+
+
+class bp_align_params(C.Structure):
+    """The parameters of forced alignment (include/basic_pitch_amd_align.h); `bp_align_params_default` fills them in."""
+
+    _fields_ = [
+        ("threshold_q", C.c_int32),
+        ("onset_weight", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -482,6 +503,13 @@ MELODY_SYMBOLS = [
     "bp_infer_clips_melody",
     "bp_melody_sweep_score",
     "bp_infer_clips_melody_sweep_score",
+]
+# every symbol include/basic_pitch_amd_align.h declares (bound in basic_pitch_amd/align.py)
+ALIGN_SYMBOLS = [
+    "bp_align_params_default",
+    "bp_align_rows",
+    "bp_align_from_maps",
+    "bp_infer_clips_align",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

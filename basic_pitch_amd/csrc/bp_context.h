@@ -138,6 +138,20 @@ struct bp_context {
   Buffer<double> mel_ref;
   Buffer<int64_t> mel_out;
   bp::PinnedBuffer<int64_t> mel_home;
+  // forced alignment (bp_align_from_maps, bp_infer_clips_align, clips_api.hip), all grow-only, scratch of one call and grown by
+  // those calls alone: the device copies of note and onset maps given in host memory (or not 16-byte aligned), the states, the
+  // segment table, the gains (8 bytes a cell: the one large pool, 2 GiB at BP_ALIGN_MAX_CELLS), the predecessor bits (a bit a
+  // cell in whole 64-bit words a row), the NaN flags, the first frames, the totals [segments] with the statuses (32-bit) behind
+  // them, and the page-locked block those come home in
+  Buffer<float> al_note, al_onset;
+  Buffer<bp::AlignState> al_states;
+  Buffer<bp::AlignSeg> al_segs;
+  Table al_gains;
+  Buffer<uint64_t> al_pred;
+  Buffer<uint32_t> al_nan;
+  Buffer<int32_t> al_first;
+  Buffer<int64_t> al_out;
+  bp::PinnedBuffer<int64_t> al_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

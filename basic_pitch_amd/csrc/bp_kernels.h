@@ -352,6 +352,27 @@ struct MelodyDecode {
 hipError_t launch_melody(const float* contour, const MelodyParams* sets, const MelodyDecode* dec, int64_t n_decodes, int max_jump,
                          uint8_t* pred, void* points, const double* ref_pitch, MpScoreParams sp, int64_t* scores, int32_t* status,
                          hipStream_t s);
+// align.hip: forced alignment (include/basic_pitch_amd_align.h).  Segment c of segs is rows [row_first, row_first
+// + rows) of note / onset against states [state_first, state_first + n_states) of states, rows > 0 and 1 <= n_states <=
+// kAlignMaxStates; its gains go to cells [cell_first, cell_first + rows * n_states) of gains (8 bytes a cell), its predecessor
+// bits to words [pred_first, pred_first + rows * ceil(n_states / 64)) of pred, and the tiles of 32 rows x 32 states of its
+// emissions are tiles [tile_first, tile_first + ceil(rows / 32) * ceil(n_states / 32)) of the n_tiles of the launch (the
+// regions of distinct segments disjoint, tile_first ascending).  first_frame[state_first + j], total[c], status[c]: the
+// header's, -1 / 0 with a status of 1 (a NaN; nan_flags [n_segs] is scratch) or 2 (infeasible).  max_states: the largest
+// n_states, which chooses the workgroup of the recurrence.  note and onset must be 16-byte aligned.
+constexpr int kAlignLanes = 1024, kAlignSmallLanes = 256, kAlignMaxStates = 4096, kAlignReadAhead = 8, kAlignReadAheadWide = 4;  // BP_ALIGN_*
+constexpr int kAlignTileRows = 128, kAlignEmitRows = 32;
+struct AlignState {  // bp_align_state
+  uint64_t active[2], begins[2];
+  int32_t earliest, latest;
+};
+struct AlignSeg {
+  int64_t row_first, rows, state_first, cell_first, pred_first, tile_first;
+  int32_t n_states, segment;  // segment: the caller's index (the kernels do not read it)
+};
+hipError_t launch_align(const float* note, const float* onset, const AlignState* states, const AlignSeg* segs, int64_t n_segs,
+                        int64_t n_tiles, int max_states, int threshold_q, int onset_weight, void* gains, uint64_t* pred,
+                        uint32_t* nan_flags, int32_t* first_frame, int64_t* total, int32_t* status, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

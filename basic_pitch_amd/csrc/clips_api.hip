@@ -3,7 +3,8 @@
 // the note candidates of every clip or, the tracker run on the device too, the note events alone: under one parameter set, or
 // (a sweep) every segment under many; or, of the contour rows alone, the f0 peaks of every segment and the frame-level counts of
 // threshold sweeps over them (include/basic_pitch_amd_multipitch.h); or the melody of every segment, one f0 track by a Viterbi
-// recurrence, and the melody measures of parameter sweeps over it (include/basic_pitch_amd_melody.h).
+// recurrence, and the melody measures of parameter sweeps over it (include/basic_pitch_amd_melody.h); or, of the note and onset
+// rows, the alignment of every segment's reference score by a monotone recurrence (include/basic_pitch_amd_align.h).
 //
 // Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
 //   the sink's fixed arguments -> the source's plan (rows of every clip) -> the outputs against the rows -> statuses and the
@@ -24,6 +25,7 @@
 #include "../../include/basic_pitch_amd_frame_score.h"
 #include "../../include/basic_pitch_amd_multipitch.h"
 #include "../../include/basic_pitch_amd_melody.h"
+#include "../../include/basic_pitch_amd_align.h"
 #include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
@@ -39,6 +41,8 @@ extern "C" void bp_internal_frame_pitch_range(const bp_ref_note* r, const bp_sco
 extern "C" const char* bp_internal_mp_bad_params(const bp_mp_params* p);
 extern "C" const char* bp_internal_melody_bad_params(const bp_melody_params* p);  // melody_host.cpp
 extern "C" int64_t bp_internal_melody_bad_ref(const double* ref_pitch, int64_t n);
+extern "C" const char* bp_internal_align_bad_params(const bp_align_params* p);  // align_host.cpp
+extern "C" const char* bp_internal_align_bad_states(const bp_align_state* states, int64_t n, int64_t* index);
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 namespace bp {
@@ -515,7 +519,7 @@ struct JobSource {
 // params is null, every set has its own dense half.  kScoreHome: the same sweep, but what goes home is `scores` and out.status
 // alone — every decode's events scored on the device against the refs of its segment (include/basic_pitch_amd_score.h).
 // with_frames: the calls of include/basic_pitch_amd_frame_score.h — `frames` goes home too, and `scores` may be null.
-enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome, kMelodyHome, kMelodyScoreHome };
+enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome, kMelodyHome, kMelodyScoreHome, kAlignHome };
 struct JobSink {
   JobSinkKind kind;
   const bp_note_params* params;
@@ -549,6 +553,15 @@ struct JobSink {
   bp_melody_point* mel_points;
   const double* ref_pitch;
   bp_melody_score* mel_scores;
+  // kAlignHome: the alignment (include/basic_pitch_amd_align.h) of the n segments, segment i against al_states[state_offsets[i]
+  // ... state_offsets[i + 1]) under al_params: first_frame parallel to the states (room for max_states), al_total and out.status
+  // per segment.
+  const bp_align_params* al_params;
+  const int64_t* state_offsets;
+  const bp_align_state* al_states;
+  int32_t* first_frame;
+  int64_t max_states;
+  int64_t* al_total;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -615,6 +628,15 @@ JobSink melody_score_sink(int64_t n_sets, const bp_melody_params* sets, int64_t 
   k.kind = kMelodyScoreHome, k.out.status = status;
   k.mel_params = sets, k.n_sets = n_sets, k.n_decodes = n_decodes, k.decodes = decodes;
   k.ref_pitch = ref_pitch, k.score_params = score_params, k.mel_scores = scores;
+  return k;
+}
+
+JobSink align_sink(const int64_t* state_offsets, const bp_align_state* states, const bp_align_params* p, int32_t* first_frame,
+                   int64_t max_states, int64_t* total, int* status) {
+  JobSink k{};
+  k.kind = kAlignHome, k.out.status = status;
+  k.al_params = p, k.state_offsets = state_offsets, k.al_states = states, k.first_frame = first_frame, k.max_states = max_states;
+  k.al_total = total;
   return k;
 }
 
@@ -813,6 +835,9 @@ struct ClipsJob {
   std::vector<MpDecode> mp_dec;
   std::vector<MpRef> mp_refs;
   std::vector<MelodyDecode> mel_dec;  // kMelodyHome: a decode per segment; kMelodyScoreHome: the decode table
+  std::vector<AlignSeg> al_segs;      // kAlignHome: the segments with rows and states, and what they take of the pools
+  int64_t al_cells = 0, al_words = 0, al_tiles = 0;
+  int al_max_states = 0;
 };
 
 // A sweep behind the maps of its n_segs segments (offs: their rows, T > 0 in all): the dense half once per key — the note rows
@@ -1181,6 +1206,98 @@ void melody_home(bp_handle h, const JobSink& k, const ClipsJob& job) {
   for (int64_t j = 0; j < nd; ++j) k.out.status[job.mel_dec[(size_t)j].reserved] = st[j];
 }
 
+// ---- forced alignment: the states of a score against the note and onset rows (include/basic_pitch_amd_align.h) ---
+// the sink's fixed arguments, before anything is queued
+int check_align(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (n_segs < 0 || (n_segs > 0 && (!k.out.status || !k.al_total))) return invalid("negative n_segments / n_clips, or null total or status");
+  if (const char* why = bp_internal_align_bad_params(k.al_params)) return invalid(std::string("params: ") + why);
+  if (n_segs == 0) return BP_OK;
+  bool ordered = k.state_offsets && k.state_offsets[0] == 0;
+  for (int64_t i = 0; ordered && i < n_segs; ++i) ordered = k.state_offsets[i + 1] >= k.state_offsets[i];
+  if (!ordered) return invalid("state_offsets must start at 0 and never decrease");
+  const int64_t n_states = k.state_offsets[n_segs];
+  if (n_states > 0 && !k.al_states) return invalid("null states");
+  if (k.max_states < 0 || (k.max_states > 0 && !k.first_frame)) return invalid("negative max_states, or room without a buffer");
+  if (k.max_states < n_states)
+    return invalid("room for " + std::to_string(k.max_states) + " first frames, but the segments have " + std::to_string(n_states) +
+                   " states (nothing has been written)");
+  for (int64_t i = 0; i < n_segs; ++i)
+    if (k.state_offsets[i + 1] - k.state_offsets[i] > BP_ALIGN_MAX_STATES)
+      return invalid("segment " + std::to_string(i) + ": " + std::to_string(k.state_offsets[i + 1] - k.state_offsets[i]) +
+                     " states, more than BP_ALIGN_MAX_STATES (" + std::to_string(BP_ALIGN_MAX_STATES) + ")");
+  int64_t bad = -1;
+  if (const char* why = bp_internal_align_bad_states(k.al_states, n_states, &bad)) return invalid("state " + std::to_string(bad) + ": " + why);
+  return BP_OK;
+}
+
+// The outputs against the rows (offs: of the n segments): the bounds, the results of the segments that need no device, and
+// for the others their regions of the pools.  *queued false: nothing needs the device and the outputs are complete.
+int plan_align(bp_handle h, const char* what, int64_t n, const int64_t* offs, const JobSink& k, ClipsJob& job, bool* queued) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (offs[n] > BP_SWEEP_MAX_ROWS)
+    return invalid(std::to_string(offs[n]) + " rows in all, more than BP_SWEEP_MAX_ROWS (" + std::to_string(BP_SWEEP_MAX_ROWS) + "): split the job");
+  int64_t cells = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t rows = offs[i + 1] - offs[i], S = k.state_offsets[i + 1] - k.state_offsets[i];
+    if (rows > 0 && S == 0) return invalid("segment " + std::to_string(i) + ": rows but no state (a path needs a state)");
+    cells += rows * S;  // (at most 2^23 x 2^12 a segment: no overflow before the test)
+    if (cells > BP_ALIGN_MAX_CELLS)
+      return invalid(std::to_string(cells) + " cells (rows x states) up to segment " + std::to_string(i) + ", more than BP_ALIGN_MAX_CELLS (" +
+                     std::to_string(BP_ALIGN_MAX_CELLS) + "): split the job");
+  }
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t rows = offs[i + 1] - offs[i], S = k.state_offsets[i + 1] - k.state_offsets[i];
+    k.al_total[i] = 0, k.out.status[i] = rows == 0 && S > 0 ? 2 : 0;  // (states without a row: infeasible)
+    for (int64_t j = 0; j < S; ++j) k.first_frame[k.state_offsets[i] + j] = -1;
+    if (rows == 0 || S == 0) continue;
+    job.al_segs.push_back(AlignSeg{offs[i], rows, k.state_offsets[i], job.al_cells, job.al_words, job.al_tiles, (int32_t)S, (int32_t)i});
+    job.al_cells += rows * S, job.al_words += rows * ((S + 63) / 64);
+    job.al_tiles += ((rows + kAlignEmitRows - 1) / kAlignEmitRows) * ((S + kAlignEmitRows - 1) / kAlignEmitRows);
+    job.al_max_states = std::max(job.al_max_states, (int)S);
+  }
+  *queued = !job.al_segs.empty();
+  return BP_OK;
+}
+
+// Behind the note and onset rows of the n segments (on the device, 16-byte aligned): the tables, the launches, and the first
+// frames, totals and statuses on their way home.
+int queue_align(bp_handle h, const float* note, const float* onset, int64_t n, const JobSink& k, ClipsJob& job) {
+  hipStream_t s = h->stream;
+  const int64_t nd = (int64_t)job.al_segs.size(), n_states = k.state_offsets[n];
+  static_assert(sizeof(AlignState) == sizeof(bp_align_state) && sizeof(bp_align_state) == 40, "the states go to the device as they are");
+  const size_t n_out = (size_t)(nd + (nd + 1) / 2);
+  BP_HIP(h->al_states.reserve((size_t)n_states));
+  BP_HIP(h->al_segs.reserve((size_t)nd));
+  BP_HIP(h->al_gains.reserve((size_t)job.al_cells * 8));
+  BP_HIP(h->al_pred.reserve((size_t)job.al_words));
+  BP_HIP(h->al_nan.reserve((size_t)nd));
+  BP_HIP(h->al_first.reserve((size_t)n_states));
+  BP_HIP(h->al_out.reserve(n_out));
+  BP_HIP(h->al_home.reserve(n_out));
+  BP_HIP(hipMemcpyAsync(h->al_states, k.al_states, (size_t)n_states * sizeof(AlignState), hipMemcpyHostToDevice, s));
+  BP_HIP(hipMemcpyAsync(h->al_segs, job.al_segs.data(), (size_t)nd * sizeof(AlignSeg), hipMemcpyHostToDevice, s));
+  // (the first frames of the segments that are not queued are -1 already, on the host and here)
+  BP_HIP(hipMemsetAsync(h->al_first, 0xff, (size_t)n_states * sizeof(int32_t), s));
+  int64_t* out = h->al_out;
+  BP_HIP(launch_align(note, onset, h->al_states, h->al_segs, nd, job.al_tiles, job.al_max_states, k.al_params->threshold_q,
+                      k.al_params->onset_weight, static_cast<uint8_t*>(h->al_gains), h->al_pred, h->al_nan, h->al_first, out,
+                      reinterpret_cast<int32_t*>(out + nd), s));
+  BP_HIP(hipMemcpyAsync(k.first_frame, h->al_first, (size_t)n_states * sizeof(int32_t), hipMemcpyDeviceToHost, s));
+  BP_HIP(hipMemcpyAsync(h->al_home, out, n_out * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+// the stream has drained: the totals and the statuses are in the page-locked block
+void align_home(bp_handle h, const JobSink& k, const ClipsJob& job) {
+  const int64_t nd = (int64_t)job.al_segs.size();
+  const int32_t* st = reinterpret_cast<const int32_t*>(h->al_home + nd);
+  for (int64_t c = 0; c < nd; ++c) {
+    const int32_t i = job.al_segs[(size_t)c].segment;
+    k.al_total[i] = h->al_home[c], k.out.status[i] = st[c];
+  }
+}
+
 // everything a job queues: the source (the maps of all segments to track_out, concatenated by job.offs), the dense half of
 // note decoding for every segment as its own track, the sink
 int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) {
@@ -1188,7 +1305,19 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   int rc = BP_OK;
   const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
   const bool melody = k.kind == kMelodyHome || k.kind == kMelodyScoreHome;
-  if (s.kind == kGivenMaps && (multipitch || melody)) {
+  if (s.kind == kGivenMaps && k.kind == kAlignHome) {
+    // the note and onset rows alone, read where they lie unless they are in host memory or not 16-byte aligned
+    const size_t cells = (size_t)job.offs[s.n] * kFreqN;
+    const auto where = [&](const float* given, DeviceBuffer<float>& copy, float** at) -> int {
+      *at = const_cast<float*>(given);
+      if (s.mem_kind == BP_MEM_DEVICE && reinterpret_cast<uintptr_t>(given) % 16 == 0) return BP_OK;
+      BP_HIP(copy.reserve(cells));
+      BP_HIP(hipMemcpyAsync(copy, given, cells * sizeof(float), s.mem_kind == BP_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice, h->stream));
+      *at = copy;
+      return BP_OK;
+    };
+    if ((rc = where(s.note, h->al_note, &all.note)) || (rc = where(s.onset, h->al_onset, &all.onset))) return rc;
+  } else if (s.kind == kGivenMaps && (multipitch || melody)) {
     // the contour rows alone, read where they lie: a map in host memory gets a device copy, one in device memory is not copied
     all.contour = const_cast<float*>(s.contour);
     if (s.mem_kind == BP_MEM_HOST) {
@@ -1226,6 +1355,7 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   if (rc) return rc;
   if (multipitch) return queue_multipitch(h, all.contour, s.n, job.offs, k, job);
   if (melody) return queue_melody(h, all.contour, s.n, job.offs, k, job);
+  if (k.kind == kAlignHome) return queue_align(h, all.note, all.onset, s.n, k, job);
   if (k.kind == kCandidatesHome)
     return queue_clips_candidates(h, all, s.n, job.offs, k.params, k.note_out, k.cand_bits, k.bend_map, &job.exported_by_kernel);
   uint8_t* d_bits = nullptr;
@@ -1245,9 +1375,12 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   const bool events = k.kind == kEventsHome || sweep;
   const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
   const bool melody = k.kind == kMelodyHome || k.kind == kMelodyScoreHome;
+  const bool align = k.kind == kAlignHome;
   int rc = BP_OK;
   // the sink's fixed arguments
-  if (multipitch) {
+  if (align) {
+    if ((rc = check_align(h, what, n, k))) return rc;
+  } else if (multipitch) {
     if ((rc = check_multipitch(h, what, n, k))) return rc;
   } else if (melody) {
     if ((rc = check_melody(h, what, n, k))) return rc;
@@ -1267,7 +1400,7 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
     for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
     if (!ordered || (src.mem_kind != BP_MEM_HOST && src.mem_kind != BP_MEM_DEVICE))
       return invalid("row_offsets must start at 0 and never decrease; mem_kind must be BP_MEM_HOST or BP_MEM_DEVICE");
-    if (src.row_offsets[n] > 0 && (!src.contour || (!multipitch && !melody && (!src.note || !src.onset)))) return invalid("null input pointer");
+    if (src.row_offsets[n] > 0 && ((!align && !src.contour) || (!multipitch && !melody && (!src.note || !src.onset)))) return invalid("null input pointer");
     job.offs = src.row_offsets;
   } else {
     if (flac) {
@@ -1299,6 +1432,16 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
       if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
     if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
     melody_home(h, k, job);
+    return BP_OK;
+  }
+  if (align) {  // the first frames of every segment's states: no note decoding, the emissions and one workgroup per segment
+    bool queued = false;
+    if ((rc = plan_align(h, what, n, job.offs, k, job, &queued)) || !queued) return rc;
+    BP_HIP(hipSetDevice(h->device));
+    if (src.kind != kGivenMaps && src.sample_rate != h->rate)
+      if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
+    if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
+    align_home(h, k, job);
     return BP_OK;
   }
   if (!events && total > 0 && (!k.note_out || !k.cand_bits)) return invalid("null output pointer");
@@ -1492,6 +1635,21 @@ int bp_infer_clips_melody_sweep_score(bp_handle h, int64_t n_clips, const bp_cli
                                       const bp_score_params* score_params, bp_melody_score* scores, int* status) {
   return run_clips(h, "bp_infer_clips_melody_sweep_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
                    melody_score_sink(n_sets, sets, n_decodes, decodes, ref_pitch, score_params, scores, status));
+}
+
+// ---- forced alignment (include/basic_pitch_amd_align.h) --------------------------------------------------------------------------
+int bp_align_from_maps(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* note, const float* onset,
+                       int mem_kind, const int64_t* state_offsets, const bp_align_state* states, const bp_align_params* p,
+                       int32_t* first_frame, int64_t max_states, int64_t* total, int* status) {
+  return run_clips(h, "bp_align_from_maps", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, note, onset, nullptr},
+                   align_sink(state_offsets, states, p, first_frame, max_states, total, status));
+}
+
+int bp_infer_clips_align(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind,
+                         const int64_t* state_offsets, const bp_align_state* states, const bp_align_params* p, int32_t* first_frame,
+                         int64_t max_states, int64_t* total, int* status) {
+  return run_clips(h, "bp_infer_clips_align", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   align_sink(state_offsets, states, p, first_frame, max_states, total, status));
 }
 
 #ifdef BP_AB_KERNELS

@@ -637,6 +637,26 @@ class Model:
 
         return _mel.transcribe_clips_sweep_melody_scores(self, clips, sample_rates, sets, ref_tracks, pairs, **tolerances)
 
+    # -- forced alignment (basic_pitch_amd/align.py) -----------------------------------------------
+    def align(self, outputs: Sequence[Any], ref_notes: Sequence[Any], **params: Any) -> "List[Any]":
+        """Reference notes that are not on the audio's time base aligned to every segment of `outputs` (the dicts `predict` /
+        `run_inference` return, numpy arrays or CUDA tensors of one kind; their "note" and "onset" maps are read) in ONE call
+        (`bp_align_from_maps`): `ref_notes[i]` rows of (start_s, end_s, pitch_midi) become states in order
+        (`align.states_from_notes`; `lead`, `tail`, `max_shift_s` go there), a monotone dynamic programme on the device finds
+        every state's first frame (`threshold_q` 307, `onset_weight` 2 by default), and the notes come back on the audio's
+        frames.  Returns one `align.Alignment` per segment: notes, first_frame, total, status."""
+        from . import align as _al
+
+        return _al.align(self, outputs, ref_notes, **params)
+
+    def transcribe_clips_align(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], ref_notes: Sequence[Any],
+                               **params: Any) -> "List[Any]":
+        """The same behind the model, for many short clips (grouped by sample rate as `transcribe_clips` groups them): the
+        clips of a rate go through the model once (`bp_infer_clips_align`), and 4 bytes per state come home."""
+        from . import align as _al
+
+        return _al.transcribe_clips_align(self, clips, sample_rates, ref_notes, **params)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
