@@ -338,6 +338,35 @@ class bp_align_params(C.Structure):
     ]
 
 
+class bp_beat_params(C.Structure):
+    """The parameters of tempo and beats (include/basic_pitch_amd_beat.h), the prior table among them;
+    `bp_beat_params_default` fills them in."""
+
+    _fields_ = [
+        ("threshold_q", C.c_int32),
+        ("min_pitch", C.c_int32),
+        ("max_pitch", C.c_int32),
+        ("lag_min", C.c_int32),
+        ("lag_max", C.c_int32),
+        ("tightness", C.c_int32),
+        ("reserved", C.c_int32 * 2),
+        ("prior", C.c_int32 * 257),
+        ("reserved_tail", C.c_int32),
+    ]
+
+
+class bp_beat_summary(C.Structure):
+    """Tempo and beats of one segment (include/basic_pitch_amd_beat.h): status 1 a NaN, 2 no pulse."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("period", C.c_int32),
+        ("n_beats", C.c_int64),
+        ("score", C.c_int64),
+        ("period_refined", C.c_double),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -510,6 +539,15 @@ ALIGN_SYMBOLS = [
     "bp_align_rows",
     "bp_align_from_maps",
     "bp_infer_clips_align",
+]
+# every symbol include/basic_pitch_amd_beat.h declares (bound in basic_pitch_amd/beat.py)
+BEAT_SYMBOLS = [
+    "bp_beat_params_default",
+    "bp_beat_prior",
+    "bp_beats_capacity",
+    "bp_beat_rows",
+    "bp_beats_from_maps",
+    "bp_infer_clips_beats",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

@@ -152,6 +152,20 @@ struct bp_context {
   Buffer<int32_t> al_first;
   Buffer<int64_t> al_out;
   bp::PinnedBuffer<int64_t> al_home;
+  // tempo and beats (bp_beats_from_maps, bp_infer_clips_beats, clips_api.hip), all grow-only, scratch of one call and grown by
+  // those calls alone: the device copy of an onset map given in host memory (or not 16-byte aligned), the parameters with their
+  // prior table, the segment table, the strength of every row, per segment bp::kBeatAccStride sums (sum o, sum o^2, the NaN
+  // flag, the autocorrelation per lag, the path kernel's clock readings), the predecessors (one uint16 a row: 16 MiB at
+  // BP_SWEEP_MAX_ROWS), the summaries [segments] with the beat pool (32-bit) behind them, and the page-locked block those come
+  // home in
+  Buffer<float> bt_onset;
+  Buffer<bp::BeatParams> bt_params;
+  Buffer<bp::BeatSeg> bt_segs;
+  Buffer<int32_t> bt_strength;
+  Buffer<int64_t> bt_acc;
+  Buffer<uint16_t> bt_pred;
+  Buffer<int64_t> bt_out;
+  bp::PinnedBuffer<int64_t> bt_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

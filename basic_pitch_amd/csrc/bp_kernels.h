@@ -373,6 +373,32 @@ struct AlignSeg {
 hipError_t launch_align(const float* note, const float* onset, const AlignState* states, const AlignSeg* segs, int64_t n_segs,
                         int64_t n_tiles, int max_states, int threshold_q, int onset_weight, void* gains, uint64_t* pred,
                         uint32_t* nan_flags, int32_t* first_frame, int64_t* total, int32_t* status, hipStream_t s);
+// beat.hip: tempo and beats (include/basic_pitch_amd_beat.h).  Segment c of segs is rows [row_first, row_first +
+// rows) of onset, rows > 0; it is blocks [blk_first, blk_first + ceil(rows / kBeatStrengthRows)) of the n_blocks of the strength
+// launch and tiles [tile_first, tile_first + ceil(rows / kBeatTempoRows) * lag_tiles) of the n_tiles of the tempo launch
+// (lag_tiles: ceil(admissible lags / kBeatTempoLags), 0 where rows <= lag_min; both firsts ascending, the regions of distinct
+// segments disjoint).  strength [all rows] is o[t], parallel to the rows of onset; acc is kBeatAccStride int64 a segment: sum o,
+// sum o^2, the NaN flag, A[0 ... 256], and four clock readings of the path kernel (100 MHz: start, period picked, recurrence
+// done, backtrace done) for tools/bench_beat.py; pred one uint16 a row, parallel to the rows of onset.  summaries[c]: the
+// header's record.  The beats of segment c go to beats[beat_first ...) IN DESCENDING ORDER, summaries[c].n_beats of them (at most
+// bp_beats_capacity of the segment: the caller's region).  onset must be 16-byte aligned.
+constexpr int kBeatMaxLag = 256, kBeatRing = 1024, kBeatTempoRows = 256, kBeatTempoLags = 64, kBeatPathWaves = 16;  // BP_BEAT_*
+constexpr int kBeatStrengthRows = 32, kBeatAccStride = 264, kBeatAccLags = 3, kBeatAccClocks = 260;
+struct BeatParams {  // bp_beat_params
+  int32_t threshold_q, min_pitch, max_pitch, lag_min, lag_max, tightness, reserved[2], prior[kBeatMaxLag + 1], reserved_tail;
+};
+struct BeatSummary {  // bp_beat_summary
+  int32_t status, period;
+  int64_t n_beats, score;
+  double period_refined;
+};
+struct BeatSeg {
+  int64_t row_first, rows, blk_first, tile_first, beat_first, beat_cap;  // beat_cap: the room at beat_first; nothing is stored beyond it
+  int32_t lag_tiles, segment;  // segment: the caller's index (the kernels do not read it)
+};
+hipError_t launch_beats(const float* onset, const BeatParams* params, const BeatSeg* segs, int64_t n_segs, int64_t n_blocks,
+                        int64_t n_tiles, int32_t* strength, int64_t* acc, uint16_t* pred, int32_t* beats, BeatSummary* summaries,
+                        hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

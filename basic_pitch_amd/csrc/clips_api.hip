@@ -4,7 +4,8 @@
 // (a sweep) every segment under many; or, of the contour rows alone, the f0 peaks of every segment and the frame-level counts of
 // threshold sweeps over them (include/basic_pitch_amd_multipitch.h); or the melody of every segment, one f0 track by a Viterbi
 // recurrence, and the melody measures of parameter sweeps over it (include/basic_pitch_amd_melody.h); or, of the note and onset
-// rows, the alignment of every segment's reference score by a monotone recurrence (include/basic_pitch_amd_align.h).
+// rows, the alignment of every segment's reference score by a monotone recurrence (include/basic_pitch_amd_align.h); or, of the
+// onset rows alone, the tempo and the beats of every segment (include/basic_pitch_amd_beat.h).
 //
 // Every entry point is a source and a sink on one driver (run_clips), the job family's run_track (track_api.hip):
 //   the sink's fixed arguments -> the source's plan (rows of every clip) -> the outputs against the rows -> statuses and the
@@ -26,6 +27,7 @@
 #include "../../include/basic_pitch_amd_multipitch.h"
 #include "../../include/basic_pitch_amd_melody.h"
 #include "../../include/basic_pitch_amd_align.h"
+#include "../../include/basic_pitch_amd_beat.h"
 #include "../../include/basic_pitch_amd_sweep.h"
 #include "bp_context.h"
 
@@ -43,6 +45,7 @@ extern "C" const char* bp_internal_melody_bad_params(const bp_melody_params* p);
 extern "C" int64_t bp_internal_melody_bad_ref(const double* ref_pitch, int64_t n);
 extern "C" const char* bp_internal_align_bad_params(const bp_align_params* p);  // align_host.cpp
 extern "C" const char* bp_internal_align_bad_states(const bp_align_state* states, int64_t n, int64_t* index);
+extern "C" const char* bp_internal_beat_bad_params(const bp_beat_params* p);  // beat_host.cpp
 extern "C" int bp_internal_flac_device_supported(const bp_flac_stream_layout* lay, size_t nbytes);
 
 namespace bp {
@@ -519,7 +522,7 @@ struct JobSource {
 // params is null, every set has its own dense half.  kScoreHome: the same sweep, but what goes home is `scores` and out.status
 // alone — every decode's events scored on the device against the refs of its segment (include/basic_pitch_amd_score.h).
 // with_frames: the calls of include/basic_pitch_amd_frame_score.h — `frames` goes home too, and `scores` may be null.
-enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome, kMelodyHome, kMelodyScoreHome, kAlignHome };
+enum JobSinkKind { kCandidatesHome, kEventsHome, kSweepHome, kScoreHome, kMultiPitchHome, kMultiPitchScoreHome, kMelodyHome, kMelodyScoreHome, kAlignHome, kBeatHome };
 struct JobSink {
   JobSinkKind kind;
   const bp_note_params* params;
@@ -562,6 +565,13 @@ struct JobSink {
   int32_t* first_frame;
   int64_t max_states;
   int64_t* al_total;
+  // kBeatHome: tempo and beats (include/basic_pitch_amd_beat.h) of the n segments under bt_params: a summary per segment, the
+  // beats as one compact array (room for max_beats) with bt_offsets [n + 1].
+  const bp_beat_params* bt_params;
+  bp_beat_summary* bt_summaries;
+  int32_t* bt_beats;
+  int64_t max_beats;
+  int64_t* bt_offsets;
 };
 
 JobSink candidates_sink(const bp_note_params* params, float* note_out, uint8_t* cand_bits, int8_t* bend_map, int* status) {
@@ -637,6 +647,13 @@ JobSink align_sink(const int64_t* state_offsets, const bp_align_state* states, c
   k.kind = kAlignHome, k.out.status = status;
   k.al_params = p, k.state_offsets = state_offsets, k.al_states = states, k.first_frame = first_frame, k.max_states = max_states;
   k.al_total = total;
+  return k;
+}
+
+JobSink beat_sink(const bp_beat_params* p, bp_beat_summary* summaries, int32_t* beats, int64_t max_beats, int64_t* beat_offsets) {
+  JobSink k{};
+  k.kind = kBeatHome;
+  k.bt_params = p, k.bt_summaries = summaries, k.bt_beats = beats, k.max_beats = max_beats, k.bt_offsets = beat_offsets;
   return k;
 }
 
@@ -838,6 +855,8 @@ struct ClipsJob {
   std::vector<AlignSeg> al_segs;      // kAlignHome: the segments with rows and states, and what they take of the pools
   int64_t al_cells = 0, al_words = 0, al_tiles = 0;
   int al_max_states = 0;
+  std::vector<BeatSeg> bt_segs;       // kBeatHome: the segments with rows, and what they take of the launches and of the beat pool
+  int64_t bt_blocks = 0, bt_tiles = 0, bt_cap = 0;
 };
 
 // A sweep behind the maps of its n_segs segments (offs: their rows, T > 0 in all): the dense half once per key — the note rows
@@ -1298,6 +1317,95 @@ void align_home(bp_handle h, const JobSink& k, const ClipsJob& job) {
   }
 }
 
+// ---- tempo and beats: the onset rows alone (include/basic_pitch_amd_beat.h) -----------------------------------------
+// the sink's fixed arguments, before anything is queued
+int check_beat(bp_handle h, const char* what, int64_t n_segs, const JobSink& k) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (n_segs < 0 || (n_segs > 0 && (!k.bt_summaries || !k.bt_offsets))) return invalid("negative n_segments / n_clips, or null summaries or beat_offsets");
+  if (const char* why = bp_internal_beat_bad_params(k.bt_params)) return invalid(std::string("params: ") + why);
+  if (k.max_beats < 0 || (k.max_beats > 0 && !k.bt_beats)) return invalid("negative max_beats, or room without a buffer");
+  return BP_OK;
+}
+
+// The outputs against the rows (offs: of the n segments): the bounds, the room, the results of the segments without rows, and
+// for the others their blocks, tiles and regions of the beat pool.  *queued false: nothing needs the device and the outputs
+// are complete.
+int plan_beat(bp_handle h, const char* what, int64_t n, const int64_t* offs, const JobSink& k, ClipsJob& job, bool* queued) {
+  auto invalid = [&](const std::string& why) { return ::invalid(h, what, why); };
+  if (offs[n] > BP_SWEEP_MAX_ROWS)
+    return invalid(std::to_string(offs[n]) + " rows in all, more than BP_SWEEP_MAX_ROWS (" + std::to_string(BP_SWEEP_MAX_ROWS) + "): split the job");
+  const bp_beat_params& p = *k.bt_params;
+  int64_t cap = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t rows = offs[i + 1] - offs[i];
+    if (rows > BP_BEAT_MAX_ROWS)
+      return invalid("segment " + std::to_string(i) + ": " + std::to_string(rows) + " rows, more than BP_BEAT_MAX_ROWS (" +
+                     std::to_string(BP_BEAT_MAX_ROWS) + ")");
+    cap += bp_beats_capacity(rows, p.lag_min);
+  }
+  if (k.max_beats < cap)
+    return invalid("room for " + std::to_string(k.max_beats) + " beats, but the segments can have " + std::to_string(cap) +
+                   " (the sum of bp_beats_capacity; nothing has been written)");
+  for (int64_t i = 0; i < n; ++i) {
+    const int64_t rows = offs[i + 1] - offs[i];
+    k.bt_summaries[i] = bp_beat_summary{rows == 0 ? 2 : 0, 0, 0, 0, 0.0};  // (no row: no pulse)
+    if (rows == 0) continue;
+    const int64_t last_lag = std::min<int64_t>(p.lag_max, rows - 1), room = bp_beats_capacity(rows, p.lag_min);
+    const int32_t lag_tiles = last_lag < p.lag_min ? 0 : (int32_t)((last_lag - p.lag_min + kBeatTempoLags) / kBeatTempoLags);
+    job.bt_segs.push_back(BeatSeg{offs[i], rows, job.bt_blocks, job.bt_tiles, job.bt_cap, room, lag_tiles, (int32_t)i});
+    job.bt_blocks += (rows + kBeatStrengthRows - 1) / kBeatStrengthRows;
+    job.bt_tiles += (rows + kBeatTempoRows - 1) / kBeatTempoRows * lag_tiles;
+    job.bt_cap += room;
+  }
+  *queued = !job.bt_segs.empty();
+  for (int64_t i = 0; i <= n && !*queued && k.bt_offsets; ++i) k.bt_offsets[i] = 0;  // (null: a call of zero segments may pass none)
+  return BP_OK;
+}
+
+// Behind the onset rows of the n segments (on the device, 16-byte aligned): the tables, the three launches, and the summaries
+// and the beat pool on their way home (one page-locked block: the summaries, then the pool).
+int queue_beat(bp_handle h, const float* onset, int64_t n, const JobSink& k, ClipsJob& job) {
+  hipStream_t s = h->stream;
+  const int64_t nd = (int64_t)job.bt_segs.size(), rows = job.offs[n];
+  static_assert(sizeof(BeatParams) == sizeof(bp_beat_params) && sizeof(bp_beat_params) == 1064, "the parameters go to the device as they are");
+  static_assert(sizeof(BeatSummary) == sizeof(bp_beat_summary) && sizeof(bp_beat_summary) == 32, "the summaries come home as they are");
+  const size_t n_home = (size_t)(4 * nd + (job.bt_cap + 1) / 2);  // in int64: 32 bytes a summary, 4 a beat
+  BP_HIP(h->bt_params.reserve(1));
+  BP_HIP(h->bt_segs.reserve((size_t)nd));
+  BP_HIP(h->bt_strength.reserve((size_t)rows));
+  BP_HIP(h->bt_acc.reserve((size_t)nd * kBeatAccStride));
+  BP_HIP(h->bt_pred.reserve((size_t)rows));
+  BP_HIP(h->bt_out.reserve(n_home));
+  BP_HIP(h->bt_home.reserve(n_home));
+  BP_HIP(hipMemcpyAsync(h->bt_params, k.bt_params, sizeof(BeatParams), hipMemcpyHostToDevice, s));
+  BP_HIP(hipMemcpyAsync(h->bt_segs, job.bt_segs.data(), (size_t)nd * sizeof(BeatSeg), hipMemcpyHostToDevice, s));
+  int64_t* out = h->bt_out;
+  BP_HIP(launch_beats(onset, h->bt_params, h->bt_segs, nd, job.bt_blocks, job.bt_tiles, h->bt_strength, h->bt_acc, h->bt_pred,
+                      reinterpret_cast<int32_t*>(out + 4 * nd), reinterpret_cast<BeatSummary*>(out), s));
+  BP_HIP(hipMemcpyAsync(h->bt_home, out, n_home * sizeof(int64_t), hipMemcpyDeviceToHost, s));
+  return BP_OK;
+}
+
+// the stream has drained: the summaries and the pool are in the page-locked block; the beats leave it compact and ascending
+// (a segment's lie in its region of the pool last beat first)
+void beat_home(bp_handle h, int64_t n, const JobSink& k, const ClipsJob& job) {
+  const int64_t nd = (int64_t)job.bt_segs.size();
+  const int64_t* home = h->bt_home;
+  const int32_t* pool = reinterpret_cast<const int32_t*>(home + 4 * nd);
+  for (int64_t c = 0; c < nd; ++c) std::memcpy(&k.bt_summaries[job.bt_segs[(size_t)c].segment], home + 4 * c, sizeof(bp_beat_summary));
+  int64_t at = 0, c = 0;
+  for (int64_t i = 0; i < n; ++i) {
+    k.bt_offsets[i] = at;
+    if (c < nd && job.bt_segs[(size_t)c].segment == i) {
+      const BeatSeg& seg = job.bt_segs[(size_t)c++];
+      const int64_t nb = std::min(k.bt_summaries[i].n_beats, seg.beat_cap);  // (n_beats is within the room by the header's bound)
+      for (int64_t j = 0; j < nb; ++j) k.bt_beats[at + j] = pool[seg.beat_first + nb - 1 - j];
+      at += nb;
+    }
+  }
+  k.bt_offsets[n] = at;
+}
+
 // everything a job queues: the source (the maps of all segments to track_out, concatenated by job.offs), the dense half of
 // note decoding for every segment as its own track, the sink
 int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) {
@@ -1305,8 +1413,9 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   int rc = BP_OK;
   const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
   const bool melody = k.kind == kMelodyHome || k.kind == kMelodyScoreHome;
-  if (s.kind == kGivenMaps && k.kind == kAlignHome) {
-    // the note and onset rows alone, read where they lie unless they are in host memory or not 16-byte aligned
+  if (s.kind == kGivenMaps && (k.kind == kAlignHome || k.kind == kBeatHome)) {
+    // the note and onset rows alone (the beats: the onset rows), read where they lie unless they are in host memory or not
+    // 16-byte aligned
     const size_t cells = (size_t)job.offs[s.n] * kFreqN;
     const auto where = [&](const float* given, DeviceBuffer<float>& copy, float** at) -> int {
       *at = const_cast<float*>(given);
@@ -1316,7 +1425,11 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
       *at = copy;
       return BP_OK;
     };
-    if ((rc = where(s.note, h->al_note, &all.note)) || (rc = where(s.onset, h->al_onset, &all.onset))) return rc;
+    if (k.kind == kBeatHome) {
+      if ((rc = where(s.onset, h->bt_onset, &all.onset))) return rc;
+    } else if ((rc = where(s.note, h->al_note, &all.note)) || (rc = where(s.onset, h->al_onset, &all.onset))) {
+      return rc;
+    }
   } else if (s.kind == kGivenMaps && (multipitch || melody)) {
     // the contour rows alone, read where they lie: a map in host memory gets a device copy, one in device memory is not copied
     all.contour = const_cast<float*>(s.contour);
@@ -1356,6 +1469,7 @@ int queue_job(bp_handle h, const JobSource& s, const JobSink& k, ClipsJob& job) 
   if (multipitch) return queue_multipitch(h, all.contour, s.n, job.offs, k, job);
   if (melody) return queue_melody(h, all.contour, s.n, job.offs, k, job);
   if (k.kind == kAlignHome) return queue_align(h, all.note, all.onset, s.n, k, job);
+  if (k.kind == kBeatHome) return queue_beat(h, all.onset, s.n, k, job);
   if (k.kind == kCandidatesHome)
     return queue_clips_candidates(h, all, s.n, job.offs, k.params, k.note_out, k.cand_bits, k.bend_map, &job.exported_by_kernel);
   uint8_t* d_bits = nullptr;
@@ -1375,10 +1489,12 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
   const bool events = k.kind == kEventsHome || sweep;
   const bool multipitch = k.kind == kMultiPitchHome || k.kind == kMultiPitchScoreHome;
   const bool melody = k.kind == kMelodyHome || k.kind == kMelodyScoreHome;
-  const bool align = k.kind == kAlignHome;
+  const bool align = k.kind == kAlignHome, beat = k.kind == kBeatHome;
   int rc = BP_OK;
   // the sink's fixed arguments
-  if (align) {
+  if (beat) {
+    if ((rc = check_beat(h, what, n, k))) return rc;
+  } else if (align) {
     if ((rc = check_align(h, what, n, k))) return rc;
   } else if (multipitch) {
     if ((rc = check_multipitch(h, what, n, k))) return rc;
@@ -1400,7 +1516,8 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
     for (int64_t i = 0; ordered && i < n; ++i) ordered = src.row_offsets[i + 1] >= src.row_offsets[i];
     if (!ordered || (src.mem_kind != BP_MEM_HOST && src.mem_kind != BP_MEM_DEVICE))
       return invalid("row_offsets must start at 0 and never decrease; mem_kind must be BP_MEM_HOST or BP_MEM_DEVICE");
-    if (src.row_offsets[n] > 0 && ((!align && !src.contour) || (!multipitch && !melody && (!src.note || !src.onset)))) return invalid("null input pointer");
+    if (src.row_offsets[n] > 0 && (beat ? !src.onset : (!align && !src.contour) || (!multipitch && !melody && (!src.note || !src.onset))))
+      return invalid("null input pointer");
     job.offs = src.row_offsets;
   } else {
     if (flac) {
@@ -1442,6 +1559,16 @@ int run_clips(bp_handle h, const char* what, JobSource src, const JobSink& k) {
       if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
     if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
     align_home(h, k, job);
+    return BP_OK;
+  }
+  if (beat) {  // the summaries and the beats of the onset rows: no note decoding, three launches
+    bool queued = false;
+    if ((rc = plan_beat(h, what, n, job.offs, k, job, &queued)) || !queued) return rc;
+    BP_HIP(hipSetDevice(h->device));
+    if (src.kind != kGivenMaps && src.sample_rate != h->rate)
+      if ((rc = clips_filter(h, what, src.sample_rate))) return rc;
+    if ((rc = finish(h, queue_job(h, src, k, job)))) return rc;
+    beat_home(h, n, k, job);
     return BP_OK;
   }
   if (!events && total > 0 && (!k.note_out || !k.cand_bits)) return invalid("null output pointer");
@@ -1635,6 +1762,28 @@ int bp_infer_clips_melody_sweep_score(bp_handle h, int64_t n_clips, const bp_cli
                                       const bp_score_params* score_params, bp_melody_score* scores, int* status) {
   return run_clips(h, "bp_infer_clips_melody_sweep_score", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
                    melody_score_sink(n_sets, sets, n_decodes, decodes, ref_pitch, score_params, scores, status));
+}
+
+// ---- tempo and beats (include/basic_pitch_amd_beat.h) ----------------------------------------------------------------------------
+int bp_beats_from_maps(bp_handle h, int64_t n_segments, const int64_t* row_offsets, const float* onset, int mem_kind,
+                       const bp_beat_params* p, bp_beat_summary* summaries, int32_t* beats, int64_t max_beats, int64_t* beat_offsets) {
+  return run_clips(h, "bp_beats_from_maps", JobSource{kGivenMaps, n_segments, mem_kind, 0, nullptr, nullptr, row_offsets, nullptr, onset, nullptr},
+                   beat_sink(p, summaries, beats, max_beats, beat_offsets));
+}
+
+int bp_infer_clips_beats(bp_handle h, int64_t n_clips, const bp_clip* clips, int sample_rate, int pcm_mem_kind, const bp_beat_params* p,
+                         bp_beat_summary* summaries, int32_t* beats, int64_t max_beats, int64_t* beat_offsets) {
+  return run_clips(h, "bp_infer_clips_beats", JobSource{kPcmClips, n_clips, pcm_mem_kind, sample_rate, clips},
+                   beat_sink(p, summaries, beats, max_beats, beat_offsets));
+}
+
+// the clock readings of the path kernel for segment c of the handle's last beat call with rows (100 MHz ticks: start, period
+// picked, recurrence done, backtrace done): tools/bench_beat.py
+int bp_internal_beat_clocks(bp_handle h, int64_t c, int64_t* clocks) {
+  if (!h || !clocks || c < 0 || (size_t)(c + 1) * kBeatAccStride > h->bt_acc.capacity()) return BP_ERR_INVALID_ARG;
+  BP_HIP(hipSetDevice(h->device));
+  BP_HIP(hipMemcpy(clocks, h->bt_acc + c * kBeatAccStride + kBeatAccClocks, 4 * sizeof(int64_t), hipMemcpyDeviceToHost));
+  return BP_OK;
 }
 
 // ---- forced alignment (include/basic_pitch_amd_align.h) --------------------------------------------------------------------------

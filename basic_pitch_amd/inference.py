@@ -657,6 +657,25 @@ class Model:
 
         return _al.transcribe_clips_align(self, clips, sample_rates, ref_notes, **params)
 
+    # -- tempo and beats (basic_pitch_amd/beat.py) -------------------------------------------------
+    def beats(self, outputs: Sequence[Any], params: Any = None) -> "List[Any]":
+        """Tempo and beats of every segment of `outputs` (the dicts `predict` / `run_inference` return, numpy arrays or CUDA
+        tensors of one kind; their "onset" maps alone are read) in ONE call (`bp_beats_from_maps`): one period per segment by
+        autocorrelation under a tempo prior, then the beat frames by a dynamic programme, in exact integers on the device.
+        `params`: the fields of `bp_beat_params` (threshold_q 307, lags 21 ... 172, tightness 4 by default; `start_bpm` /
+        `sd_octaves` make the prior).  Returns one `beat.Beats` per segment: frames, times_s, period_frames, bpm, status; the
+        bpm goes into the `midi_tempo` arguments as it is."""
+        from . import beat as _bt
+
+        return _bt.beats(self, outputs, params)
+
+    def transcribe_clips_beats(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None) -> "List[Any]":
+        """The same behind the model, a segment being a clip ([n_frames, channels] arrays, each with its sample rate): the
+        clips of a rate go through the model once (`bp_infer_clips_beats`), and 32 bytes per clip and 4 per beat come home."""
+        from . import beat as _bt
+
+        return _bt.transcribe_clips_beats(self, clips, sample_rates, params)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
