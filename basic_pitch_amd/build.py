@@ -36,6 +36,11 @@ SOURCES = [
     "bp_api.hip",
     "track_api.hip",
     "clips_api.hip",
+    "clips_sweep.hip",
+    "clips_multipitch.hip",
+    "clips_melody.hip",
+    "clips_align.hip",
+    "clips_beat.hip",
     "stream_api.hip",
     "weight_pack.hip",
     "cqt_pyramid.hip",
@@ -89,7 +94,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "weight_pack.h", "march_common.h", "launch_plan.h", "cqt_planes.h", "flac_kernels.h", "file_host.h", "adpcm_host.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER, SWEEP_HEADER, SCORE_HEADER, FRAME_SCORE_HEADER, MULTIPITCH_HEADER, MELODY_HEADER, ALIGN_HEADER, BEAT_HEADER, STREAM_EVENTS_HEADER, FLAC_CLIPS_HEADER, CONTAINERS_HEADER, ADPCM_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "clips_job.h", "weight_pack.h", "march_common.h", "launch_plan.h", "cqt_planes.h", "flac_kernels.h", "file_host.h", "adpcm_host.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER, SWEEP_HEADER, SCORE_HEADER, FRAME_SCORE_HEADER, MULTIPITCH_HEADER, MELODY_HEADER, ALIGN_HEADER, BEAT_HEADER, STREAM_EVENTS_HEADER, FLAC_CLIPS_HEADER, CONTAINERS_HEADER, ADPCM_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

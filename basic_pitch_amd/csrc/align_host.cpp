@@ -1,5 +1,5 @@
 // Forced alignment on the host (include/basic_pitch_amd_align.h): bp_align_rows, the checker the device kernels (align.hip)
-// are held to, and the validation of parameters and states that the device entry points (clips_api.hip) use instead of a
+// are held to, and the validation of parameters and states that the device entry points (clips_align.hip) use instead of a
 // copy.  Device-free: links with plain g++.
 //
 // The recurrence is the header's in int64, with "unreachable" a flag beside the number, not a sentinel inside it.

@@ -1,6 +1,6 @@
 // Tempo and beats on the host (include/basic_pitch_amd_beat.h): bp_beat_rows, the checker the device kernels (beat.hip) are
 // held to, the prior table and the room for beats, and the validation of the parameters that the device entry points
-// (clips_api.hip) use instead of a copy.  Device-free: links with plain g++.
+// (clips_beat.hip) use instead of a copy.  Device-free: links with plain g++.
 //
 // Everything is the header's integers; the one float64 expression, the refined period, is written operation by operation.
 #include <cmath>

@@ -1,4 +1,5 @@
-// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip, clips_api.hip, stream_api.hip and
+// Private to csrc: the handle (struct bp_context) and what bp_api.hip, track_api.hip, the clip jobs (clips_api.hip and the sinks'
+// clips_*.hip, which share clips_job.h beside this header), stream_api.hip and
 // weight_pack.hip share of it — the HIP error macro, the chunk / wait helpers (defined in bp_api.hip), the maps, filter,
 // argument and candidates helpers of the track calls, the clip jobs and the streaming sessions (defined in track_api.hip), and
 // the tracker's host half (defined in clips_api.hip).  The handle's memory is owned by the buffers of device_buffer.h:
@@ -92,27 +93,27 @@ struct bp_context {
   Buffer<float> ev_scratch;
   Table ev_seg;  // bp_streams_events: the table of the segments' own parameters (NoteTrackSeg)
   bp::PinnedBuffer<int64_t> ev_home;
-  // a sweep (bp_note_events_sweep, clips_api.hip queue_sweep), all grow-only, scratch of one call and grown by sweeps alone: the
+  // a sweep (bp_note_events_sweep, clips_sweep.hip SweepSink::queue), all grow-only, scratch of one call and grown by sweeps alone: the
   // note rows constrained per band [bands][T][88], the working copy of the onset rows [T][88], per dense key the bitmap
   // [keys][T][12] and the stats records [keys][segments], the decode table (NoteSweepDecode) with the rows and the event
   // records before each decode behind it
   Buffer<float> sw_note, sw_onset;
   Buffer<uint8_t> sw_bits;
   Table sw_stats, sw_tab;
-  // a scored sweep (bp_note_events_sweep_score, clips_api.hip queue_sweep), all grow-only, scratch of one call and grown by the
+  // a scored sweep (bp_note_events_sweep_score, clips_sweep.hip SweepSink::queue), all grow-only, scratch of one call and grown by the
   // score calls alone: the refs of all segments, per decode which of them are its segment's, the scores [decodes][4] with the
   // statuses [decodes] behind them, and the page-locked block they come home in
   Buffer<bp::NoteScoreRef> sc_refs;
   Buffer<bp::NoteScoreDecode> sc_dec;
   Buffer<int32_t> sc_out;
   bp::PinnedBuffer<int32_t> sc_home;
-  // the frame level of a scored sweep (bp_note_events_sweep_frame_score, clips_api.hip queue_sweep), all grow-only, scratch of
+  // the frame level of a scored sweep (bp_note_events_sweep_frame_score, clips_sweep.hip SweepSink::queue), all grow-only, scratch of
   // one call and grown by the frame-score calls alone: per segment its refs in pitch order as frames and note bins, the counts
   // [decodes][5] with the statuses [decodes] (32-bit) behind them, and the page-locked block they come home in
   Buffer<bp::NoteFrameRef> fs_refs;
   Buffer<int64_t> fs_out;
   bp::PinnedBuffer<int64_t> fs_home;
-  // multi-pitch estimates (bp_multipitch_from_maps and its kin, clips_api.hip), all grow-only, scratch of one call and grown
+  // multi-pitch estimates (bp_multipitch_from_maps and its kin, clips_multipitch.hip), all grow-only, scratch of one call and grown
   // by those calls alone: the device copy of a contour map given in host memory, per row its peak count and segment, the
   // points before each row, per segment the not-finite flag, the point offsets with the statuses behind them, the points; of a
   // scored sweep the sets, the decode table, the refs in pitch order and the counts [decodes][5] with the statuses (32-bit)
@@ -126,7 +127,7 @@ struct bp_context {
   Buffer<bp::MpDecode> mp_dec;
   Buffer<bp::MpRef> mp_refs;
   bp::PinnedBuffer<int64_t> mp_home;
-  // the melody (bp_melody_from_maps and its kin, clips_api.hip), all grow-only, scratch of one call and grown by those calls
+  // the melody (bp_melody_from_maps and its kin, clips_melody.hip), all grow-only, scratch of one call and grown by those calls
   // alone: the device copy of a contour map given in host memory, the sets, the decode table, the predecessors (one byte per
   // state per row of every decode, bp::kMelodyPredStride bytes a row: the one large pool, 2.3 GB at BP_SWEEP_MAX_ROWS), the
   // records, a scored sweep's reference track, the counts [decodes][6] with the statuses (32-bit) behind them, and the
@@ -138,7 +139,7 @@ struct bp_context {
   Buffer<double> mel_ref;
   Buffer<int64_t> mel_out;
   bp::PinnedBuffer<int64_t> mel_home;
-  // forced alignment (bp_align_from_maps, bp_infer_clips_align, clips_api.hip), all grow-only, scratch of one call and grown by
+  // forced alignment (bp_align_from_maps, bp_infer_clips_align, clips_align.hip), all grow-only, scratch of one call and grown by
   // those calls alone: the device copies of note and onset maps given in host memory (or not 16-byte aligned), the states, the
   // segment table, the gains (8 bytes a cell: the one large pool, 2 GiB at BP_ALIGN_MAX_CELLS), the predecessor bits (a bit a
   // cell in whole 64-bit words a row), the NaN flags, the first frames, the totals [segments] with the statuses (32-bit) behind
@@ -152,7 +153,7 @@ struct bp_context {
   Buffer<int32_t> al_first;
   Buffer<int64_t> al_out;
   bp::PinnedBuffer<int64_t> al_home;
-  // tempo and beats (bp_beats_from_maps, bp_infer_clips_beats, clips_api.hip), all grow-only, scratch of one call and grown by
+  // tempo and beats (bp_beats_from_maps, bp_infer_clips_beats, clips_beat.hip), all grow-only, scratch of one call and grown by
   // those calls alone: the device copy of an onset map given in host memory (or not 16-byte aligned), the parameters with their
   // prior table, the segment table, the strength of every row, per segment bp::kBeatAccStride sums (sum o, sum o^2, the NaN
   // flag, the autocorrelation per lag, the path kernel's clock readings), the predecessors (one uint16 a row: 16 MiB at
@@ -242,7 +243,7 @@ int copy_maps(bp_handle h, const Maps& dst, const Maps& src, int64_t T, hipMemcp
 // Gaussian on the device, the page-locked copy of the stats record
 int note_tables(bp_handle h, const void** tab, const double** gauss);
 constexpr size_t kTabBytes = 88 * 16, kGaussBytes = 51 * 8, kStatsBytes = 16;  // of nd_tables; a stats record
-// track_api.hip, for the jobs of many clips (clips_api.hip).  The geometry of a handle: the length of a signal resampled to
+// track_api.hip, for the jobs of many clips (clips_api.hip and the sinks' files).  The geometry of a handle: the length of a signal resampled to
 // `rate`, the rows of the maps of n samples at the handle's rate
 int64_t resampled_length(int64_t n_frames, int sample_rate, int rate);
 int64_t h_frames(bp_handle h, int64_t n);
@@ -264,7 +265,7 @@ int send_candidates(bp_handle h, const float* d_note, int64_t T, const uint8_t* 
                     uint8_t* cand_out, int8_t* bend_out, void* d_stats, int* stats_host, void* stats_host_dev, int64_t n_stats,
                     bool* exported_by_kernel);
 
-// ---- the tracker (note_track.hip) behind any dense half, its host half in clips_api.hip: the clips calls there,
+// ---- the tracker (note_track.hip) behind any dense half, its host half in clips_api.hip: the clips calls there and in clips_sweep.hip,
 // bp_streams_events (stream_api.hip).
 // Where a call's results go:
 struct EventsSink {

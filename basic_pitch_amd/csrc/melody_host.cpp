@@ -1,6 +1,6 @@
 // The melody of a contour map on the host (include/basic_pitch_amd_melody.h): bp_melody_rows, the checker the device kernel
 // (melody.hip) is held to, bp_score_melody_frames, the checker of the scored sweep, and the validation of parameter sets and
-// reference tracks that the device entry points (clips_api.hip) use instead of a copy.  Device-free: links with plain g++
+// reference tracks that the device entry points (clips_melody.hip) use instead of a copy.  Device-free: links with plain g++
 // beside note_frames_host.cpp and note_score_host.cpp, whose validation of the tolerances it uses.
 //
 // The recurrence and the refinement are the header's, as written: float32 operations one at a time, the parabola in float64,

@@ -1,7 +1,7 @@
 // Frame-level scoring on the host (include/basic_pitch_amd_frame_score.h): bp_score_note_frames, the checker the device kernel
 // (note_frames.hip) is held to and the route for the decodes a device call leaves, and the two functions of a ref and its
 // segment alone that both share — the frames a note sounds on and the estimated pitches a ref hits — which the device reads
-// from a table the host makes with them (clips_api.hip), so that the kernel compares integers alone.
+// from a table the host makes with them (clips_sweep.hip), so that the kernel compares integers alone.
 //
 // The predicates are the header's, in float64 and as written.  The frame time is strictly increasing, so the frames a note
 // sounds on are one interval, found from a guess by steps with the very comparison of the definition.  Between two frames

@@ -44,7 +44,7 @@ int64_t bp_internal_score_bad_ref(const bp_ref_note* refs, int64_t n) {
   return -1;
 }
 
-// the offset tolerance a ref sets, the one expression of it: the checker below and the table the device reads (clips_api.hip)
+// the offset tolerance a ref sets, the one expression of it: the checker below and the table the device reads (clips_sweep.hip)
 double bp_internal_score_offset_tol(const bp_ref_note* r, const bp_score_params* p) {
   return std::fmax(p->offset_ratio * (r->end_s - r->start_s), p->offset_min_tolerance_s);
 }
