@@ -367,6 +367,36 @@ class bp_beat_summary(C.Structure):
     ]
 
 
+class bp_chord_params(C.Structure):
+    """The parameters of chords and key (include/basic_pitch_amd_chord.h), the state table and the key profiles among them;
+    `bp_chord_params_default` fills them in."""
+
+    _fields_ = [
+        ("threshold_q", C.c_int32),
+        ("min_pitch", C.c_int32),
+        ("max_pitch", C.c_int32),
+        ("n_states", C.c_int32),
+        ("switch_penalty", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+        ("bias", C.c_int32 * 64),
+        ("weights", (C.c_int32 * 12) * 64),
+        ("key_profile", (C.c_int32 * 12) * 2),
+    ]
+
+
+class bp_chord_summary(C.Structure):
+    """Chords and key of one segment (include/basic_pitch_amd_chord.h): status 1 a NaN, 2 nothing sounds."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("key", C.c_int32),
+        ("n_units", C.c_int32),
+        ("n_changes", C.c_int32),
+        ("score", C.c_int64),
+        ("key_score", C.c_int64),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -548,6 +578,15 @@ BEAT_SYMBOLS = [
     "bp_beat_rows",
     "bp_beats_from_maps",
     "bp_infer_clips_beats",
+]
+# every symbol include/basic_pitch_amd_chord.h declares (bound in basic_pitch_amd/chord.py)
+CHORD_SYMBOLS = [
+    "bp_chord_params_default",
+    "bp_chord_templates",
+    "bp_chord_key_profiles",
+    "bp_chord_rows",
+    "bp_chords_from_maps",
+    "bp_infer_clips_chords",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

@@ -274,4 +274,28 @@ __device__ __forceinline__ void lds_barrier() {
 
 __device__ __forceinline__ int wave_id() { return __builtin_amdgcn_readfirstlane(threadIdx.x >> 6); }
 
+// The maximum of a wave's 64-bit keys in every lane: row scans by 1, 2, 4, 8 within the rows of 16 lanes (a lane without a
+// source is offered 0 and keeps its own), lane 15 of a row to the row above, lane 31 to the upper half, and lane 63 holds it.
+// The 64 bits go as two words: the maximum of the high words first, then the maximum of the low words of the lanes that hold
+// it (the others offer 0) — two scans of one 32-bit maximum a step instead of one of a 64-bit compare and two selects.
+template <int kCtrl, int kRows>
+__device__ __forceinline__ uint32_t dpp_max32(uint32_t v) {
+  const uint32_t other = (uint32_t)__builtin_amdgcn_update_dpp(0, (int)v, kCtrl, kRows, 0xf, false);  // (0: the maximum's identity, so the move folds into v_max_u32_dpp)
+  return other > v ? other : v;
+}
+__device__ __forceinline__ uint32_t wave_max32(uint32_t v) {
+  v = dpp_max32<0x111, 0xf>(v);  // row_shr:1
+  v = dpp_max32<0x112, 0xf>(v);  // row_shr:2
+  v = dpp_max32<0x114, 0xf>(v);  // row_shr:4
+  v = dpp_max32<0x118, 0xf>(v);  // row_shr:8
+  v = dpp_max32<0x142, 0xa>(v);  // row_bcast:15 into rows 1, 3
+  v = dpp_max32<0x143, 0xc>(v);  // row_bcast:31 into rows 2, 3
+  return (uint32_t)__builtin_amdgcn_readlane((int)v, 63);
+}
+__device__ __forceinline__ unsigned long long wave_max64(unsigned long long v) {
+  const uint32_t hi = (uint32_t)(v >> 32), top = wave_max32(hi);
+  const uint32_t low = wave_max32(hi == top ? (uint32_t)v : 0u);
+  return ((unsigned long long)top << 32) | low;
+}
+
 }  // namespace bp

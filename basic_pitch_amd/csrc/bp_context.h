@@ -167,6 +167,23 @@ struct bp_context {
   Buffer<uint16_t> bt_pred;
   Buffer<int64_t> bt_out;
   bp::PinnedBuffer<int64_t> bt_home;
+  // chords and key (bp_chords_from_maps, bp_infer_clips_chords, clips_chord.hip), all grow-only, scratch of one call and grown
+  // by those calls alone: the device copy of a note map given in host memory (or not 16-byte aligned), the parameters with
+  // their tables, the segment table, the boundaries of all segments, the chroma (32 bytes a row), the pooled sums (64 bytes
+  // a unit of a segment with boundaries), per segment bp::kChordAccStride sums, the records (16 bytes a unit: 128 MiB at
+  // BP_SWEEP_MAX_ROWS), a label a unit, the summaries [segments] with the labels (a byte a row) behind them, and the
+  // page-locked block those come home in
+  Buffer<float> ch_note;
+  Buffer<bp::ChordParams> ch_params;
+  Buffer<bp::ChordSeg> ch_segs;
+  Buffer<int32_t> ch_bounds;
+  Buffer<uint16_t> ch_chroma;
+  Buffer<uint32_t> ch_pool;
+  Buffer<int64_t> ch_acc;
+  Buffer<uint4> ch_records;
+  Buffer<uint8_t> ch_unit_labels;
+  Buffer<int64_t> ch_out;
+  bp::PinnedBuffer<int64_t> ch_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

@@ -399,6 +399,34 @@ struct BeatSeg {
 hipError_t launch_beats(const float* onset, const BeatParams* params, const BeatSeg* segs, int64_t n_segs, int64_t n_blocks,
                         int64_t n_tiles, int32_t* strength, int64_t* acc, uint16_t* pred, int32_t* beats, BeatSummary* summaries,
                         hipStream_t s);
+// chord.hip: chords and key (include/basic_pitch_amd_chord.h).  Segment c of segs is rows [row_first, row_first +
+// rows) of note, rows > 0, the segments' rows one run from 0 to n_rows; it is blocks [blk_first, blk_first + ceil(rows /
+// kChordChromaRows)) of the n_blocks of the chroma launch and units [unit_first, unit_first + n_units) of records and
+// unit_labels.  pooled 0: unit u is row u.  pooled 1: the units lie between bounds[bound_first ... bound_first + n_units - 1)
+// (strictly ascending inside 0 < B < rows) and are units [pool_first, pool_first + n_units) of the n_pool_units of the pool
+// launch (pool_first ascending).  chroma is one row of 16 uint16 a row of note (classes 0 ... 11, then zeros), pool one row
+// of 16 uint32 a pooled unit (the classes' sums, the unit's length, zeros); acc is kChordAccStride int64 a segment: sum c, sum
+// c^2, the NaN flag, Ctot[12], and at kChordAccClocks four clock readings of the path kernel (100 MHz: start, key picked,
+// recurrence done, backtrace done) for tools/bench_chord.py; records 16 bytes a unit (the predecessor mask and the best
+// state); unit_labels a byte a unit; labels a byte a row of note; summaries[c]: the header's record.  note must be 16-byte
+// aligned.
+constexpr int kChordMaxStates = 64, kChordClasses = 12, kChordChromaRows = 32, kChordTraceTile = 512, kChordPathWaves = 4;  // BP_CHORD_*
+constexpr int kChordChunk = 64, kChordAccStride = 24, kChordAccClasses = 3, kChordAccClocks = 16;
+struct ChordParams {  // bp_chord_params
+  int32_t threshold_q, min_pitch, max_pitch, n_states, switch_penalty, reserved[3], bias[kChordMaxStates];
+  int32_t weights[kChordMaxStates][kChordClasses], key_profile[2][kChordClasses];
+};
+struct ChordSummary {  // bp_chord_summary
+  int32_t status, key, n_units, n_changes;
+  int64_t score, key_score;
+};
+struct ChordSeg {
+  int64_t row_first, rows, blk_first, unit_first, n_units, pool_first, bound_first;
+  int32_t pooled, segment;  // segment: the caller's index (the kernels do not read it)
+};
+hipError_t launch_chords(const float* note, const ChordParams* params, const ChordSeg* segs, int64_t n_segs, int64_t n_blocks,
+                         int64_t n_rows, int64_t n_pool_units, const int32_t* bounds, uint16_t* chroma, uint32_t* pool, int64_t* acc,
+                         void* records, uint8_t* unit_labels, uint8_t* labels, ChordSummary* summaries, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -676,6 +676,28 @@ class Model:
 
         return _bt.transcribe_clips_beats(self, clips, sample_rates, params)
 
+    # -- chords and key (basic_pitch_amd/chord.py) -------------------------------------------------
+    def chords(self, outputs: Sequence[Any], params: Any = None, beats: Any = None) -> "List[Any]":
+        """Chords and key of every segment of `outputs` (the dicts `predict` / `run_inference` return, numpy arrays or CUDA
+        tensors of one kind; their "note" maps alone are read) in ONE call (`bp_chords_from_maps`): a chroma per row, a Viterbi
+        path over a table of chord templates with a switching penalty, a key by profile correlation, in exact integers on the
+        device.  `params`: the fields of `bp_chord_params` (threshold_q 307, switch_penalty 128 by default) and `vocabulary`
+        ("majmin", "triads", "sevenths").  `beats`: the list `Model.beats` returns (or one array of frames per segment): the
+        units are the stretches between beats instead of frames.  Returns one `chord.Chords` per segment: labels, runs,
+        times_s, key, status."""
+        from . import chord as _ch
+
+        return _ch.chords(self, outputs, params, beats)
+
+    def transcribe_clips_chords(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None,
+                                bounds: Any = None) -> "List[Any]":
+        """The same behind the model, a segment being a clip ([n_frames, channels] arrays, each with its sample rate): the
+        clips of a rate go through the model once (`bp_infer_clips_chords`), and 32 bytes per clip and a byte per row come
+        home.  `bounds`: per clip the boundary frames (or a `beat.Beats`), or None for frame units."""
+        from . import chord as _ch
+
+        return _ch.transcribe_clips_chords(self, clips, sample_rates, params, bounds)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:
