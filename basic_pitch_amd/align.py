@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _native
 from . import clips as _clips
-from .multipitch import _rates
+from . import jobs as _jobs
 from .note_creation import frames_to_time_at
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -193,9 +193,8 @@ def _split_params(params: dict) -> Tuple[dict, dict]:
 
 def _scores(ref_notes: Sequence[Any], rows: Sequence[int], how: dict):
     built = [states_from_notes(r, int(t), **how) for r, t in zip(ref_notes, rows)]
-    offs = np.concatenate([[0], np.cumsum([len(b[0]) for b in built])]).astype(np.int64)
     flat = np.ascontiguousarray(np.concatenate([b[0] for b in built]) if built else np.zeros(0, ALIGN_STATE), ALIGN_STATE)
-    return built, offs, flat
+    return built, _jobs.offsets_of([len(b[0]) for b in built]), flat
 
 
 def _align_call(model: Any, what: str, fixed: tuple, state_offsets: np.ndarray, states: np.ndarray, params: Any):
@@ -216,45 +215,16 @@ def align_from_maps(model: Any, row_offsets: Sequence[int], note: Any, onset: An
                     states: np.ndarray, params: Any = None):
     """One `bp_align_from_maps` call: `note` / `onset` pointers (or None without rows) to the rows of all segments in host or
     device memory.  Returns (first_frame of all states, total per segment, status per segment)."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    s_offs = np.ascontiguousarray(state_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), note, onset, int(mem_kind))
-    return _align_call(model, "bp_align_from_maps", fixed, s_offs, np.ascontiguousarray(states, ALIGN_STATE), params)
+    fixed, offs = _jobs.maps_source(model, row_offsets, (note, onset), mem_kind)
+    return _align_call(model, "bp_align_from_maps", fixed, np.ascontiguousarray(state_offsets, np.int64),
+                       np.ascontiguousarray(states, ALIGN_STATE), params)
 
 
 def infer_clips_align(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, state_offsets: Sequence[int], states: np.ndarray,
                       params: Any = None):
     """One `bp_infer_clips_align` call for [n_frames, channels] arrays at one rate: (first_frame, total, status)."""
-    tab = _clips.clip_table(arrays)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _align_call(model, "bp_infer_clips_align", fixed, np.ascontiguousarray(state_offsets, np.int64),
+    return _align_call(model, "bp_infer_clips_align", _jobs.clips_source(model, arrays, sample_rate), np.ascontiguousarray(state_offsets, np.int64),
                        np.ascontiguousarray(states, ALIGN_STATE), params)
-
-
-def _stack(outputs: Sequence[Any], key: str, what: str):
-    """The `key` maps of posteriorgram dicts (numpy arrays or CUDA tensors, all of one kind) one after the other: (rows per
-    segment, the stacked map — kept alive by the caller —, its pointer or None without rows, mem_kind)."""
-    from . import inference as _inf
-
-    maps = [out[key] for out in outputs]
-    on_dev = _inf._is_torch_cuda(maps[0])
-    parts = []
-    for a in maps:
-        if _inf._is_torch_cuda(a) != on_dev:
-            raise ValueError(f"{what}: the maps must all be numpy arrays or all CUDA tensors")
-        a = a.contiguous().float() if on_dev else np.require(a, np.float32, ["C"])
-        if a.ndim != 2 or a.shape[1] != PITCHES:
-            raise ValueError(f"{key}: expected (T, {PITCHES})")
-        parts.append(a)
-    if on_dev:
-        import torch
-
-        stacked = torch.cat(parts) if len(parts) > 1 else parts[0]
-        torch.cuda.current_stream(stacked.device).synchronize()
-    else:
-        stacked = np.concatenate(parts) if len(parts) > 1 else parts[0]
-    rows = [int(a.shape[0]) for a in parts]
-    return rows, stacked, (_inf._ptr(stacked) if sum(rows) else None), _inf._mem_kind(stacked)
 
 
 def _results(ref_notes, built, offs, rows, ff, total, status) -> List[Alignment]:
@@ -274,13 +244,11 @@ def align(model: Any, outputs: Sequence[Any], ref_notes: Sequence[Any], **params
     if not outputs:
         return []
     prm, how = _split_params(params)
-    rows, note, n_ptr, mem_kind = _stack(outputs, "note", "align")
-    rows_o, onset, o_ptr, mem_kind_o = _stack(outputs, "onset", "align")
-    if rows_o != rows or mem_kind_o != mem_kind:
-        raise ValueError("align: the note and onset maps of a segment must have one length and lie in one kind of memory")
+    row_offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("note", "onset"), "align", mismatch="align: the note and onset maps of a "
+                                                "segment must have one length and lie in one kind of memory")
+    rows = np.diff(row_offs).tolist()
     built, offs, flat = _scores(ref_notes, rows, how)
-    row_offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-    ff, total, status = align_from_maps(model, row_offs, n_ptr, o_ptr, mem_kind, offs, flat, prm)
+    ff, total, status = align_from_maps(model, row_offs, ptr["note"], ptr["onset"], mem_kind, offs, flat, prm)
     return _results(ref_notes, built, offs, rows, ff, total, status)
 
 
@@ -291,15 +259,13 @@ def transcribe_clips_align(model: Any, clips: Sequence[Any], sample_rates: Union
     if len(arrays) != len(ref_notes):
         raise ValueError(f"transcribe_clips_align: {len(arrays)} clips but {len(ref_notes)} lists of reference notes")
     prm, how = _split_params(params)
-    rates = _rates(arrays, sample_rates)
-    results: List[Optional[Alignment]] = [None] * len(arrays)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
+
+    def run(ids, rate):
         mine = [arrays[i] for i in ids]
         rows = np.diff(_clips.clips_row_offsets(model, mine, rate))
         refs = [ref_notes[i] for i in ids]
         built, offs, flat = _scores(refs, rows, how)
         ff, total, status = infer_clips_align(model, mine, rate, offs, flat, prm)
-        for i, res in zip(ids, _results(refs, built, offs, rows, ff, total, status)):
-            results[i] = res
-    return results  # type: ignore[return-value]
+        return _results(refs, built, offs, rows, ff, total, status)
+
+    return _jobs.per_rate(_jobs.rates_of(arrays, sample_rates), run)

@@ -14,13 +14,13 @@ from __future__ import annotations
 
 import ctypes as C
 from dataclasses import dataclass
-from typing import Any, List, Optional, Sequence, Tuple, Union
+from typing import Any, List, Sequence, Tuple, Union
 
 import numpy as np
 
 from . import _native
 from . import clips as _clips
-from .multipitch import _rates
+from . import jobs as _jobs
 from .note_creation import frames_to_time_at
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -175,17 +175,14 @@ def _beat_call(model: Any, what: str, fixed: tuple, rows: Sequence[int], params:
 def beats_from_maps(model: Any, row_offsets: Sequence[int], onset: Any, mem_kind: int, params: Any = None):
     """One `bp_beats_from_maps` call: `onset` a pointer (or None without rows) to the onset rows of all segments in host or
     device memory.  Returns (`BEAT_SUMMARY` records per segment, the beats of all segments, beat_offsets)."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), onset, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (onset,), mem_kind)
     return _beat_call(model, "bp_beats_from_maps", fixed, np.diff(offs), params)
 
 
 def infer_clips_beats(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, params: Any = None):
     """One `bp_infer_clips_beats` call for [n_frames, channels] arrays at one rate: (summaries, beats, beat_offsets)."""
-    tab = _clips.clip_table(arrays)
     rows = np.diff(_clips.clips_row_offsets(model, arrays, sample_rate)) if len(arrays) else []
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _beat_call(model, "bp_infer_clips_beats", fixed, rows, params)
+    return _beat_call(model, "bp_infer_clips_beats", _jobs.clips_source(model, arrays, sample_rate), rows, params)
 
 
 def _results(summaries: np.ndarray, beats: np.ndarray, offsets: np.ndarray) -> List[Beats]:
@@ -194,22 +191,14 @@ def _results(summaries: np.ndarray, beats: np.ndarray, offsets: np.ndarray) -> L
 
 def beats(model: Any, outputs: Sequence[Any], params: Any = None) -> List[Beats]:
     """`Model.beats`."""
-    from .align import _stack
-
     if not outputs:
         return []
-    rows, onset, ptr, mem_kind = _stack(outputs, "onset", "beats")
-    offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-    return _results(*beats_from_maps(model, offs, ptr, mem_kind, params))
+    offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("onset",), "beats")
+    return _results(*beats_from_maps(model, offs, ptr["onset"], mem_kind, params))
 
 
 def transcribe_clips_beats(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None) -> List[Beats]:
     """`Model.transcribe_clips_beats`: the clips of each rate in one `bp_infer_clips_beats` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    rates = _rates(arrays, sample_rates)
-    results: List[Optional[Beats]] = [None] * len(arrays)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
-        for i, res in zip(ids, _results(*infer_clips_beats(model, [arrays[i] for i in ids], rate, params))):
-            results[i] = res
-    return results  # type: ignore[return-value]
+    return _jobs.per_rate(_jobs.rates_of(arrays, sample_rates),
+                          lambda ids, rate: _results(*infer_clips_beats(model, [arrays[i] for i in ids], rate, params)))

@@ -21,7 +21,7 @@ import numpy as np
 
 from . import _native
 from . import clips as _clips
-from .multipitch import _rates
+from . import jobs as _jobs
 from .note_creation import frames_to_time_at
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -200,9 +200,8 @@ def _bound_arrays(bounds: Optional[Sequence[Any]], n: int):
     if len(bounds) != n:
         raise ValueError(f"bounds: expected one list of boundaries per segment ({n}), got {len(bounds)}")
     parts = [_boundaries(b) for b in bounds]
-    offs = np.concatenate([[0], np.cumsum([len(b) for b in parts])]).astype(np.int64)
     flat = np.concatenate(parts + [np.zeros(0, np.int32)]).astype(np.int32)
-    return offs, (flat if len(flat) else np.zeros(1, np.int32))
+    return _jobs.offsets_of([len(b) for b in parts]), (flat if len(flat) else np.zeros(1, np.int32))
 
 
 def _chord_call(model: Any, what: str, fixed: tuple, rows: Sequence[int], params: Any, bounds: Optional[Sequence[Any]]):
@@ -225,17 +224,15 @@ def chords_from_maps(model: Any, row_offsets: Sequence[int], note: Any, mem_kind
     """One `bp_chords_from_maps` call: `note` a pointer (or None without rows) to the note rows of all segments in host or
     device memory, `bounds` per segment its boundary frames (None: frame units everywhere).  Returns (`CHORD_SUMMARY` records
     per segment, the labels of all rows)."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), note, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (note,), mem_kind)
     return _chord_call(model, "bp_chords_from_maps", fixed, np.diff(offs), params, bounds)
 
 
 def infer_clips_chords(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, params: Any = None,
                        bounds: Optional[Sequence[Any]] = None):
     """One `bp_infer_clips_chords` call for [n_frames, channels] arrays at one rate: (summaries, labels, row_offsets)."""
-    tab = _clips.clip_table(arrays)
     offs = _clips.clips_row_offsets(model, arrays, sample_rate) if len(arrays) else np.zeros(1, np.int64)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
+    fixed = _jobs.clips_source(model, arrays, sample_rate)
     return _chord_call(model, "bp_infer_clips_chords", fixed, np.diff(offs), params, bounds) + (np.asarray(offs, np.int64),)
 
 
@@ -245,28 +242,24 @@ def _results(summaries: np.ndarray, labels: np.ndarray, offs: np.ndarray, names:
 
 def chords(model: Any, outputs: Sequence[Any], params: Any = None, beats: Optional[Sequence[Any]] = None) -> List[Chords]:
     """`Model.chords`."""
-    from .align import _stack
-
     if not outputs:
         return []
     p = chord_params(params)
-    rows, note, ptr, mem_kind = _stack(outputs, "note", "chords")
-    offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-    return _results(*chords_from_maps(model, offs, ptr, mem_kind, p, beats), offs, _names(p))
+    offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("note",), "chords")
+    return _results(*chords_from_maps(model, offs, ptr["note"], mem_kind, p, beats), offs, _names(p))
 
 
 def transcribe_clips_chords(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None,
                             bounds: Optional[Sequence[Any]] = None) -> List[Chords]:
     """`Model.transcribe_clips_chords`: the clips of each rate in one `bp_infer_clips_chords` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    rates = _rates(arrays, sample_rates)
+    rates = _jobs.rates_of(arrays, sample_rates)
     if bounds is not None and len(bounds) != len(arrays):
         raise ValueError(f"bounds: expected one list of boundaries per clip ({len(arrays)}), got {len(bounds)}")
     p = chord_params(params)
-    results: List[Optional[Chords]] = [None] * len(arrays)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
+
+    def run(ids, rate):
         got = infer_clips_chords(model, [arrays[i] for i in ids], rate, p, None if bounds is None else [bounds[i] for i in ids])
-        for i, res in zip(ids, _results(*got, _names(p))):
-            results[i] = res
-    return results  # type: ignore[return-value]
+        return _results(*got, _names(p))
+
+    return _jobs.per_rate(rates, run)

@@ -15,6 +15,7 @@ from typing import Any, List, Optional, Sequence, Tuple, Union
 import numpy as np
 
 from . import _native
+from . import jobs as _jobs
 from . import note_creation as _notes
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -111,9 +112,8 @@ def _call(lib, handle, what: str, fn, fixed: tuple, offs: np.ndarray, prm: Any
 def infer_clips_candidates(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, prm: Any):
     """One `bp_infer_clips_candidates` call for [n_frames, channels] arrays at one rate: as `_call` returns."""
     lib = bind(model._lib)
-    fixed = (model._handle, len(arrays), clip_table(arrays), int(sample_rate), _native.BP_MEM_HOST)
-    return _call(lib, model._handle, "bp_infer_clips_candidates", lib.bp_infer_clips_candidates, fixed,
-                 clips_row_offsets(model, arrays, sample_rate), prm)
+    return _call(lib, model._handle, "bp_infer_clips_candidates", lib.bp_infer_clips_candidates,
+                 _jobs.clips_source(model, arrays, sample_rate), clips_row_offsets(model, arrays, sample_rate), prm)
 
 
 def transcribe_groups(groups, candidates, events, fallback, results: List[Any], prm: Any, decode: str, multiple_pitch_bends: bool,
@@ -157,15 +157,11 @@ def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, 
     device too (`bp_infer_clips_events`, basic_pitch_amd/events.py) and only events and bends come home."""
     if decode not in ("host", "device"):
         raise ValueError(f"decode must be 'host' or 'device', got {decode!r}")
+    from . import events as _events
     from . import inference as _inf
 
     arrays = [as_clip(c, i) for i, c in enumerate(clips)]
-    if isinstance(sample_rates, (int, np.integer)):
-        rates = [int(sample_rates)] * len(arrays)
-    else:
-        rates = [int(r) for r in sample_rates]
-        if len(rates) != len(arrays):
-            raise ValueError(f"{len(arrays)} clips but {len(rates)} sample rates")
+    rates = _jobs.rates_of(arrays, sample_rates)
     prm = _notes._note_params(onset_threshold, frame_threshold, _inf._min_note_len_frames(minimum_note_length), True,
                               maximum_frequency, minimum_frequency, melodia_trick, _notes.ENERGY_TOLERANCE, True)
     results: List[Any] = [None] * len(arrays)
@@ -176,10 +172,7 @@ def transcribe_clips(model: Any, clips: Sequence[Any], sample_rates: Union[int, 
         results[i] = _inf._output_to_notes(out, onset_threshold, frame_threshold, minimum_note_length, minimum_frequency,
                                            maximum_frequency, multiple_pitch_bends, melodia_trick, midi_tempo)
 
-    from . import events as _events
-
-    groups = [(rate, [i for i, r in enumerate(rates) if r == rate]) for rate in dict.fromkeys(rates)]  # by first appearance
-    transcribe_groups(groups, lambda ids, rate: infer_clips_candidates(model, [arrays[i] for i in ids], rate, prm),
+    transcribe_groups(_jobs.rate_groups(rates), lambda ids, rate: infer_clips_candidates(model, [arrays[i] for i in ids], rate, prm),
                       lambda ids, rate: _events.infer_clips_events(model, [arrays[i] for i in ids], rate, prm),
                       host_decoded, results, prm, decode, multiple_pitch_bends, midi_tempo, threads)
     return results

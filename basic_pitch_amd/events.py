@@ -16,6 +16,7 @@ import numpy as np
 
 from . import _native
 from . import clips as _clips
+from . import jobs as _jobs
 from . import note_creation as _notes
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -103,36 +104,7 @@ def stack_maps(outputs: Sequence[Any], what: str):
     """Posteriorgram dicts (numpy arrays or CUDA tensors, all of one kind) as the maps calls take them: (row offsets, the
     three maps of all segments one after the other, {map: pointer, or None without rows}, mem_kind).  The pointers are into
     the returned maps, which the caller holds until its call has returned."""
-    from . import inference as _inf
-
-    on_dev = _inf._is_torch_cuda(outputs[0]["note"])
-    maps = {}
-    for k, w in _inf._MAPS:
-        parts = []
-        for out in outputs:
-            a = out[k]
-            if _inf._is_torch_cuda(a) != on_dev:
-                raise ValueError(f"{what}: the maps must all be numpy arrays or all CUDA tensors")
-            a = a.contiguous().float() if on_dev else np.require(a, np.float32, ["C"])
-            if a.ndim != 2 or a.shape[1] != w:
-                raise ValueError(f"{k}: expected (T, {w})")
-            parts.append(a)
-        if on_dev:
-            import torch
-
-            maps[k] = torch.cat(parts) if len(parts) > 1 else parts[0]
-        else:
-            maps[k] = np.concatenate(parts) if len(parts) > 1 else parts[0]
-    rows = [int(out["note"].shape[0]) for out in outputs]
-    if any(int(out[k].shape[0]) != r for out, r in zip(outputs, rows) for k, _ in _inf._MAPS):
-        raise ValueError(f"{what}: note, onset and contour of a segment must have the same number of rows")
-    offs = np.concatenate([[0], np.cumsum(rows)]).astype(np.int64)
-    if on_dev:
-        import torch
-
-        torch.cuda.current_stream(maps["note"].device).synchronize()
-    ptrs = {k: (_inf._ptr(a) if int(offs[-1]) else None) for k, a in maps.items()}
-    return offs, maps, ptrs, _inf._mem_kind(maps["note"])
+    return _jobs.stack(outputs, ("note", "onset", "contour"), what)
 
 
 def note_events(model: Any, outputs: Sequence[Any], prm: Any) -> List[Tuple[Optional[List["_notes.NoteEvent"]], int]]:

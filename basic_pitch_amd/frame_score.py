@@ -20,6 +20,7 @@ import numpy as np
 from . import _native
 from . import clips as _clips
 from . import events as _events
+from . import jobs as _jobs
 from . import score as _score
 from . import sweep as _sweep
 
@@ -98,26 +99,14 @@ def _call(model: Any, what: str, fixed: tuple, params: Sequence[Any], pairs: Opt
     ref_offs, flat = _score.refs_table(refs)
     prm = _score.score_params(**tolerances)
     sets = _sweep.sets_array(params)
-    n = len(pairs) if pairs is not None else len(params) * n_segments
-    tab = _sweep.decode_table(pairs) if pairs is not None else None
+    block, n = _jobs.decodes_block(sets, len(params), pairs, n_segments)
     scores = np.zeros((max(1, n), 4), np.int32)
     frames = np.zeros((max(1, n), 5), np.int64)
     status = np.zeros(max(1, n), np.int32)
-    rc = getattr(lib, what)(*fixed, len(params), C.addressof(sets), n, C.addressof(tab) if tab is not None else None,
-                            ref_offs.ctypes.data_as(_pi64), flat.ctypes.data if len(flat) else None, C.addressof(prm),
-                            scores.ctypes.data if notes else None, frames.ctypes.data, status.ctypes.data)
+    rc = getattr(lib, what)(*fixed, *block, ref_offs.ctypes.data_as(_pi64), flat.ctypes.data if len(flat) else None,
+                            C.addressof(prm), scores.ctypes.data if notes else None, frames.ctypes.data, status.ctypes.data)
     _native.check(lib, model._handle, rc, what)
-    out = np.zeros(n, FRAME_COUNTS)
-    for i, name in enumerate(_FIELDS):
-        out[name] = frames[:n, i]
-    out["status"] = status[:n]
-    note = None
-    if notes:
-        note = np.zeros(n, _score.COUNTS)
-        for i, name in enumerate(("n_ref", "n_est", "matched_onset", "matched_offset")):
-            note[name] = scores[:n, i]
-        note["status"] = status[:n]
-    return note, out
+    return (_jobs.records(_score.COUNTS, scores, status, n) if notes else None), _jobs.records(FRAME_COUNTS, frames, status, n)
 
 
 def note_events_sweep_frame_score(model: Any, row_offsets: Sequence[int], note: Any, onset: Any, contour: Any, mem_kind: int,
@@ -126,8 +115,7 @@ def note_events_sweep_frame_score(model: Any, row_offsets: Sequence[int], note: 
     """One `bp_note_events_sweep_frame_score` call (the maps as for `sweep.note_events_sweep`): (`score.COUNTS`,
     `FRAME_COUNTS`) per decode as the device left them — a decode with a non-zero status has {n_ref, 0, 0, 0} and {n_frames, 0,
     0, 0, 0}.  notes False: `scores` is NULL, the note-matching launch is skipped and the first of the pair is None."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), note, onset, contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (note, onset, contour), mem_kind)
     return _call(model, "bp_note_events_sweep_frame_score", fixed, params, pairs, len(offs) - 1, refs, notes, tolerances)
 
 
@@ -136,9 +124,8 @@ def infer_clips_events_sweep_frame_score(model: Any, arrays: Sequence[np.ndarray
                                          **tolerances: Any) -> Tuple[Optional[np.ndarray], np.ndarray]:
     """One `bp_infer_clips_events_sweep_frame_score` call for [n_frames, channels] arrays at one rate; returns as
     `note_events_sweep_frame_score`, a decode's segment being a clip."""
-    tab = _clips.clip_table(arrays)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _call(model, "bp_infer_clips_events_sweep_frame_score", fixed, params, pairs, len(arrays), refs, notes, tolerances)
+    return _call(model, "bp_infer_clips_events_sweep_frame_score", _jobs.clips_source(model, arrays, sample_rate), params, pairs,
+                 len(arrays), refs, notes, tolerances)
 
 
 def _on_the_host(events: Any, refs: Any, n_frames: int, status: int, notes: bool, tolerances: dict):
@@ -162,7 +149,7 @@ def sweep_frame_scores(model: Any, outputs: Sequence[Any], params: Sequence[Any]
                        pairs: Optional[Sequence[Pair]] = None, notes: bool = True, **tolerances: Any):
     """`Model.sweep_frame_scores`."""
     n_seg, n_sets = len(outputs), len(params)
-    todo = _score._pairs_checked(pairs, n_seg, n_sets, refs, "sweep_frame_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "sweep_frame_scores", refs)
     note, frame = np.zeros(len(todo), _score.COUNTS), np.zeros(len(todo), FRAME_COUNTS)
     if todo:
         offs, maps, ptr, mem_kind = _events.stack_maps(outputs, "sweep_frame_scores")
@@ -184,30 +171,22 @@ def transcribe_clips_sweep_frame_scores(model: Any, clips: Sequence[Any], sample
                                         notes: bool = True, **tolerances: Any):
     """`Model.transcribe_clips_sweep_frame_scores`: the clips of each rate in one `bp_infer_clips_events_sweep_frame_score` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    if isinstance(sample_rates, (int, np.integer)):
-        rates = [int(sample_rates)] * len(arrays)
-    else:
-        rates = [int(r) for r in sample_rates]
-        if len(rates) != len(arrays):
-            raise ValueError(f"{len(arrays)} clips but {len(rates)} sample rates")
+    rates = _jobs.rates_of(arrays, sample_rates)
     n_seg, n_sets = len(arrays), len(params)
-    todo = _score._pairs_checked(pairs, n_seg, n_sets, refs, "transcribe_clips_sweep_frame_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "transcribe_clips_sweep_frame_scores", refs)
     note, frame = np.zeros(len(todo), _score.COUNTS), np.zeros(len(todo), FRAME_COUNTS)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
-        local = {i: k for k, i in enumerate(ids)}
-        mine = [j for j, (s, _) in enumerate(todo) if s in local]
-        if not mine:
-            continue
-        got = infer_clips_events_sweep_frame_score(model, [arrays[i] for i in ids], rate, params, [refs[i] for i in ids],
-                                                   [(local[todo[j][0]], todo[j][1]) for j in mine], notes, **tolerances)
-        for k, j in enumerate(mine):
-            n_rec, f_rec = got[0][k] if notes else None, got[1][k]
-            if f_rec["status"]:
-                s, p = todo[j]
-                n_rec, f_rec = _on_the_host(_sweep._host_events(model, arrays[s], rate, params[p]), refs[s], int(f_rec["n_frames"]),
-                                            int(f_rec["status"]), notes, tolerances)
-            frame[j] = f_rec
-            if notes:
-                note[j] = n_rec
+
+    def run(ids, rate, local_pairs):
+        return infer_clips_events_sweep_frame_score(model, [arrays[i] for i in ids], rate, params, [refs[i] for i in ids],
+                                                    local_pairs, notes, **tolerances)
+
+    for j, k, rate, got in _jobs.per_rate_swept(todo, rates, run):
+        n_rec, f_rec = got[0][k] if notes else None, got[1][k]
+        if f_rec["status"]:
+            s, p = todo[j]
+            n_rec, f_rec = _on_the_host(_sweep._host_events(model, arrays[s], rate, params[p]), refs[s], int(f_rec["n_frames"]),
+                                        int(f_rec["status"]), notes, tolerances)
+        frame[j] = f_rec
+        if notes:
+            note[j] = n_rec
     return _result(note, frame, notes, (n_sets, n_seg) if pairs is None else None)

@@ -19,9 +19,9 @@ import numpy as np
 
 from . import _native
 from . import clips as _clips
+from . import jobs as _jobs
 from . import score as _score
-from . import sweep as _sweep
-from .multipitch import BINS, _rates, _stack_contours, midi_to_hz
+from .multipitch import BINS, midi_to_hz
 from .note_creation import frames_to_time_at
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -199,21 +199,14 @@ def _points_call(model: Any, what: str, fixed: tuple, row_offsets: np.ndarray, p
 def melody_from_maps(model: Any, row_offsets: Sequence[int], contour: Any, mem_kind: int, params: Any = None) -> Tuple[np.ndarray, np.ndarray]:
     """One `bp_melody_from_maps` call: `contour` a pointer (or None without rows) to the rows of all segments in host or device
     memory.  Returns (`MELODY_POINT` record per row of all segments, status per segment)."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (contour,), mem_kind)
     return _points_call(model, "bp_melody_from_maps", fixed, offs, params)
-
-
-def _clip_rows(model: Any, arrays: Sequence[np.ndarray], sample_rate: int) -> np.ndarray:
-    return _clips.clips_row_offsets(model, arrays, sample_rate)
 
 
 def infer_clips_melody(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, params: Any = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One `bp_infer_clips_melody` call for [n_frames, channels] arrays at one rate: (records, status, row_offsets)."""
-    tab = _clips.clip_table(arrays)
-    offs = _clip_rows(model, arrays, sample_rate)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    points, status = _points_call(model, "bp_infer_clips_melody", fixed, offs, params)
+    offs = _clips.clips_row_offsets(model, arrays, sample_rate)
+    points, status = _points_call(model, "bp_infer_clips_melody", _jobs.clips_source(model, arrays, sample_rate), offs, params)
     return points, status, offs
 
 
@@ -225,22 +218,20 @@ def melody(model: Any, outputs: Sequence[Any], params: Any = None) -> List[Melod
     """`Model.melody`."""
     if not outputs:
         return []
-    offs, stacked, ptr, mem_kind = _stack_contours(outputs, "melody")
-    points, status = melody_from_maps(model, offs, ptr, mem_kind, params)
+    offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("contour",), "melody", bare=True)
+    points, status = melody_from_maps(model, offs, ptr["contour"], mem_kind, params)
     return _split(points, offs, status)
 
 
 def transcribe_clips_melody(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Any = None) -> List[Melody]:
     """`Model.transcribe_clips_melody`: the clips of each rate in one `bp_infer_clips_melody` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    rates = _rates(arrays, sample_rates)
-    results: List[Optional[Melody]] = [None] * len(arrays)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
+
+    def run(ids, rate):
         points, status, offs = infer_clips_melody(model, [arrays[i] for i in ids], rate, params)
-        for i, est in zip(ids, _split(points, offs, status)):
-            results[i] = est
-    return results  # type: ignore[return-value]
+        return _split(points, offs, status)
+
+    return _jobs.per_rate(_jobs.rates_of(arrays, sample_rates), run)
 
 
 def _flat_refs(ref_tracks: Sequence[Any], row_offsets: np.ndarray, what: str) -> np.ndarray:
@@ -257,35 +248,28 @@ def _score_call(model: Any, what: str, fixed: tuple, sets: Sequence[Any], pairs:
     lib = bind(model._lib)
     prm = _score.score_params(**tolerances)
     arr = sets_array(sets)
-    n = len(pairs) if pairs is not None else len(sets) * n_segments
-    tab = _sweep.decode_table(pairs) if pairs is not None else None
+    block, n = _jobs.decodes_block(arr, len(sets), pairs, n_segments)
     scores = np.zeros((max(1, n), 6), np.int64)
     status = np.zeros(max(1, n), np.int32)
-    rc = getattr(lib, what)(*fixed, len(sets), C.addressof(arr), n, C.addressof(tab) if tab is not None else None,
-                            ref_pitch.ctypes.data if len(ref_pitch) else None, C.addressof(prm), scores.ctypes.data, status.ctypes.data)
+    rc = getattr(lib, what)(*fixed, *block, ref_pitch.ctypes.data if len(ref_pitch) else None, C.addressof(prm), scores.ctypes.data,
+                            status.ctypes.data)
     _native.check(lib, model._handle, rc, what)
-    out = np.zeros(n, MELODY_COUNTS)
-    for i, name in enumerate(_FIELDS):
-        out[name] = scores[:n, i]
-    out["status"] = status[:n]
-    return out
+    return _jobs.records(MELODY_COUNTS, scores, status, n)
 
 
 def melody_sweep_score(model: Any, row_offsets: Sequence[int], contour: Any, mem_kind: int, sets: Sequence[Any], ref_pitch: Any,
                        pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """One `bp_melody_sweep_score` call: `MELODY_COUNTS` per decode; `ref_pitch` one float64 per row of the segments."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (contour,), mem_kind)
     return _score_call(model, "bp_melody_sweep_score", fixed, sets, pairs, len(offs) - 1, np.ascontiguousarray(ref_pitch, np.float64), tolerances)
 
 
 def infer_clips_melody_sweep_score(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, sets: Sequence[Any], ref_tracks: Sequence[Any],
                                    pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """One `bp_infer_clips_melody_sweep_score` call for [n_frames, channels] arrays at one rate."""
-    tab = _clips.clip_table(arrays)
-    ref = _flat_refs(ref_tracks, _clip_rows(model, arrays, sample_rate), "infer_clips_melody_sweep_score")
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _score_call(model, "bp_infer_clips_melody_sweep_score", fixed, sets, pairs, len(arrays), ref, tolerances)
+    ref = _flat_refs(ref_tracks, _clips.clips_row_offsets(model, arrays, sample_rate), "infer_clips_melody_sweep_score")
+    return _score_call(model, "bp_infer_clips_melody_sweep_score", _jobs.clips_source(model, arrays, sample_rate), sets, pairs,
+                       len(arrays), ref, tolerances)
 
 
 def _result(counts: np.ndarray, shape: Optional[Tuple[int, int]]) -> np.ndarray:
@@ -296,11 +280,11 @@ def sweep_melody_scores(model: Any, outputs: Sequence[Any], sets: Sequence[Any],
                         pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """`Model.sweep_melody_scores`."""
     n_seg, n_sets = len(outputs), len(sets)
-    todo = _score._pairs_checked(pairs, n_seg, n_sets, ref_tracks, "sweep_melody_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "sweep_melody_scores", ref_tracks)
     counts = np.zeros(len(todo), MELODY_COUNTS)
     if todo:
-        offs, stacked, ptr, mem_kind = _stack_contours(outputs, "sweep_melody_scores")
-        counts = melody_sweep_score(model, offs, ptr, mem_kind, sets, _flat_refs(ref_tracks, offs, "sweep_melody_scores"), pairs, **tolerances)
+        offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("contour",), "sweep_melody_scores", bare=True)
+        counts = melody_sweep_score(model, offs, ptr["contour"], mem_kind, sets, _flat_refs(ref_tracks, offs, "sweep_melody_scores"), pairs, **tolerances)
     return _result(counts, (n_sets, n_seg) if pairs is None else None)
 
 
@@ -308,18 +292,15 @@ def transcribe_clips_sweep_melody_scores(model: Any, clips: Sequence[Any], sampl
                                          ref_tracks: Sequence[Any], pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """`Model.transcribe_clips_sweep_melody_scores`: the clips of each rate in one `bp_infer_clips_melody_sweep_score` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    rates = _rates(arrays, sample_rates)
+    rates = _jobs.rates_of(arrays, sample_rates)
     n_seg, n_sets = len(arrays), len(sets)
-    todo = _score._pairs_checked(pairs, n_seg, n_sets, ref_tracks, "transcribe_clips_sweep_melody_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "transcribe_clips_sweep_melody_scores", ref_tracks)
     counts = np.zeros(len(todo), MELODY_COUNTS)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
-        local = {i: k for k, i in enumerate(ids)}
-        mine = [j for j, (s, _) in enumerate(todo) if s in local]
-        if not mine:
-            continue
-        got = infer_clips_melody_sweep_score(model, [arrays[i] for i in ids], rate, sets, [ref_tracks[i] for i in ids],
-                                             [(local[todo[j][0]], todo[j][1]) for j in mine], **tolerances)
-        for k, j in enumerate(mine):
-            counts[j] = got[k]
+
+    def run(ids, rate, local_pairs):
+        return infer_clips_melody_sweep_score(model, [arrays[i] for i in ids], rate, sets, [ref_tracks[i] for i in ids],
+                                              local_pairs, **tolerances)
+
+    for j, k, _, got in _jobs.per_rate_swept(todo, rates, run):
+        counts[j] = got[k]
     return _result(counts, (n_sets, n_seg) if pairs is None else None)

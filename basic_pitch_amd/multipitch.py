@@ -19,8 +19,8 @@ import numpy as np
 from . import _native
 from . import clips as _clips
 from . import frame_score as _frames
+from . import jobs as _jobs
 from . import score as _score
-from . import sweep as _sweep
 from .note_creation import frames_to_time_at
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
@@ -139,32 +139,6 @@ def score_f0_frames(points: np.ndarray, refs: Any, n_frames: int, **tolerances: 
     return np.array(tuple(getattr(out, name) for name in _frames._FIELDS) + (0,), _frames.FRAME_COUNTS)
 
 
-def _stack_contours(outputs: Sequence[Any], what: str):
-    """The contour maps of posteriorgram dicts (numpy arrays or CUDA tensors, all of one kind; a bare (T, 264) map is taken
-    too) one after the other: (row offsets, the stacked map, its pointer or None without rows, mem_kind)."""
-    from . import inference as _inf
-
-    maps = [out["contour"] if isinstance(out, dict) else out for out in outputs]
-    on_dev = _inf._is_torch_cuda(maps[0])
-    parts = []
-    for a in maps:
-        if _inf._is_torch_cuda(a) != on_dev:
-            raise ValueError(f"{what}: the maps must all be numpy arrays or all CUDA tensors")
-        a = a.contiguous().float() if on_dev else np.require(a, np.float32, ["C"])
-        if a.ndim != 2 or a.shape[1] != BINS:
-            raise ValueError(f"contour: expected (T, {BINS})")
-        parts.append(a)
-    if on_dev:
-        import torch
-
-        stacked = torch.cat(parts) if len(parts) > 1 else parts[0]
-        torch.cuda.current_stream(stacked.device).synchronize()
-    else:
-        stacked = np.concatenate(parts) if len(parts) > 1 else parts[0]
-    offs = np.concatenate([[0], np.cumsum([int(a.shape[0]) for a in parts])]).astype(np.int64)
-    return offs, stacked, (_inf._ptr(stacked) if int(offs[-1]) else None), _inf._mem_kind(stacked)
-
-
 def _points_call(model: Any, what: str, fixed: tuple, n_segments: int, params: Any, room: Optional[int]):
     """`what(*fixed, p, points, max_points, point_offsets, status)` -> (points, point_offsets, status).  room None: asked for
     with a first call without room (the capacity protocol: the refusal leaves the total in point_offsets[n])."""
@@ -193,17 +167,15 @@ def multipitch_from_maps(model: Any, row_offsets: Sequence[int], contour: Any, m
                          max_points: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One `bp_multipitch_from_maps` call: `contour` a pointer (or None without rows) to the rows of all segments in host or
     device memory.  Returns (`F0_POINT` records of all segments, point_offsets, status per segment)."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (contour,), mem_kind)
     return _points_call(model, "bp_multipitch_from_maps", fixed, len(offs) - 1, params, max_points)
 
 
 def infer_clips_multipitch(model: Any, arrays: Sequence[np.ndarray], sample_rate: int, params: Any = None,
                            max_points: Optional[int] = None) -> Tuple[np.ndarray, np.ndarray, np.ndarray]:
     """One `bp_infer_clips_multipitch` call for [n_frames, channels] arrays at one rate; returns as `multipitch_from_maps`."""
-    tab = _clips.clip_table(arrays)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _points_call(model, "bp_infer_clips_multipitch", fixed, len(arrays), params, max_points)
+    return _points_call(model, "bp_infer_clips_multipitch", _jobs.clips_source(model, arrays, sample_rate), len(arrays), params,
+                        max_points)
 
 
 def _split(points: np.ndarray, offsets: np.ndarray, status: np.ndarray) -> List[MultiPitch]:
@@ -214,30 +186,16 @@ def multipitch(model: Any, outputs: Sequence[Any], params: Any = None) -> List[M
     """`Model.multipitch`."""
     if not outputs:
         return []
-    offs, stacked, ptr, mem_kind = _stack_contours(outputs, "multipitch")
-    return _split(*multipitch_from_maps(model, offs, ptr, mem_kind, params))
-
-
-def _rates(arrays: Sequence[Any], sample_rates: Union[int, Sequence[int]]) -> List[int]:
-    if isinstance(sample_rates, (int, np.integer)):
-        return [int(sample_rates)] * len(arrays)
-    rates = [int(r) for r in sample_rates]
-    if len(rates) != len(arrays):
-        raise ValueError(f"{len(arrays)} clips but {len(rates)} sample rates")
-    return rates
+    offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("contour",), "multipitch", bare=True)
+    return _split(*multipitch_from_maps(model, offs, ptr["contour"], mem_kind, params))
 
 
 def transcribe_clips_multipitch(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]],
                                 params: Any = None) -> List[MultiPitch]:
     """`Model.transcribe_clips_multipitch`: the clips of each rate in one `bp_infer_clips_multipitch` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    rates = _rates(arrays, sample_rates)
-    results: List[Optional[MultiPitch]] = [None] * len(arrays)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
-        for i, est in zip(ids, _split(*infer_clips_multipitch(model, [arrays[i] for i in ids], rate, params))):
-            results[i] = est
-    return results  # type: ignore[return-value]
+    return _jobs.per_rate(_jobs.rates_of(arrays, sample_rates),
+                          lambda ids, rate: _split(*infer_clips_multipitch(model, [arrays[i] for i in ids], rate, params)))
 
 
 def _score_call(model: Any, what: str, fixed: tuple, sets: Sequence[Any], pairs: Optional[Sequence[Pair]], n_segments: int,
@@ -248,27 +206,20 @@ def _score_call(model: Any, what: str, fixed: tuple, sets: Sequence[Any], pairs:
     ref_offs, flat = _score.refs_table(refs)
     prm = _score.score_params(**tolerances)
     arr = sets_array(sets)
-    n = len(pairs) if pairs is not None else len(sets) * n_segments
-    tab = _sweep.decode_table(pairs) if pairs is not None else None
+    block, n = _jobs.decodes_block(arr, len(sets), pairs, n_segments)
     frames = np.zeros((max(1, n), 5), np.int64)
     status = np.zeros(max(1, n), np.int32)
-    rc = getattr(lib, what)(*fixed, len(sets), C.addressof(arr), n, C.addressof(tab) if tab is not None else None,
-                            ref_offs.ctypes.data_as(_pi64), flat.ctypes.data if len(flat) else None, C.addressof(prm),
-                            frames.ctypes.data, status.ctypes.data)
+    rc = getattr(lib, what)(*fixed, *block, ref_offs.ctypes.data_as(_pi64), flat.ctypes.data if len(flat) else None,
+                            C.addressof(prm), frames.ctypes.data, status.ctypes.data)
     _native.check(lib, model._handle, rc, what)
-    out = np.zeros(n, _frames.FRAME_COUNTS)
-    for i, name in enumerate(_frames._FIELDS):
-        out[name] = frames[:n, i]
-    out["status"] = status[:n]
-    return out
+    return _jobs.records(_frames.FRAME_COUNTS, frames, status, n)
 
 
 def multipitch_sweep_frame_score(model: Any, row_offsets: Sequence[int], contour: Any, mem_kind: int, sets: Sequence[Any],
                                  refs: Sequence[Any], pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """One `bp_multipitch_sweep_frame_score` call: `frame_score.FRAME_COUNTS` per decode as the device left them — a decode
     with a non-zero status has {n_frames, 0, 0, 0, 0}."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (contour,), mem_kind)
     return _score_call(model, "bp_multipitch_sweep_frame_score", fixed, sets, pairs, len(offs) - 1, refs, tolerances)
 
 
@@ -276,9 +227,8 @@ def infer_clips_multipitch_sweep_frame_score(model: Any, arrays: Sequence[np.nda
                                              refs: Sequence[Any], pairs: Optional[Sequence[Pair]] = None,
                                              **tolerances: Any) -> np.ndarray:
     """One `bp_infer_clips_multipitch_sweep_frame_score` call for [n_frames, channels] arrays at one rate."""
-    tab = _clips.clip_table(arrays)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _score_call(model, "bp_infer_clips_multipitch_sweep_frame_score", fixed, sets, pairs, len(arrays), refs, tolerances)
+    return _score_call(model, "bp_infer_clips_multipitch_sweep_frame_score", _jobs.clips_source(model, arrays, sample_rate), sets,
+                       pairs, len(arrays), refs, tolerances)
 
 
 def _on_the_host(contour: np.ndarray, params: Any, refs: Any, status: int, tolerances: dict) -> np.ndarray:
@@ -297,14 +247,14 @@ def sweep_multipitch_frame_scores(model: Any, outputs: Sequence[Any], sets: Sequ
                                   pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """`Model.sweep_multipitch_frame_scores`."""
     n_seg, n_sets = len(outputs), len(sets)
-    todo = _score._pairs_checked(pairs, n_seg, n_sets, refs, "sweep_multipitch_frame_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "sweep_multipitch_frame_scores", refs)
     frame = np.zeros(len(todo), _frames.FRAME_COUNTS)
     if todo:
-        offs, stacked, ptr, mem_kind = _stack_contours(outputs, "sweep_multipitch_frame_scores")
-        frame = multipitch_sweep_frame_score(model, offs, ptr, mem_kind, sets, refs, pairs, **tolerances)
+        offs, maps, ptr, mem_kind = _jobs.stack(outputs, ("contour",), "sweep_multipitch_frame_scores", bare=True)
+        frame = multipitch_sweep_frame_score(model, offs, ptr["contour"], mem_kind, sets, refs, pairs, **tolerances)
         for j in np.flatnonzero(frame["status"] == 3):  # too many refs for the device: finished here.  1 stays as it is
             s, p = todo[j]
-            rows = stacked[int(offs[s]) : int(offs[s + 1])]
+            rows = maps["contour"][int(offs[s]) : int(offs[s + 1])]
             rows = rows if isinstance(rows, np.ndarray) else rows.cpu().numpy()
             frame[j] = _on_the_host(rows, sets[p], refs[s], 3, tolerances)
     return _result(frame, (n_sets, n_seg) if pairs is None else None)
@@ -316,23 +266,20 @@ def transcribe_clips_sweep_multipitch_frame_scores(model: Any, clips: Sequence[A
     """`Model.transcribe_clips_sweep_multipitch_frame_scores`: the clips of each rate in one
     `bp_infer_clips_multipitch_sweep_frame_score` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    rates = _rates(arrays, sample_rates)
+    rates = _jobs.rates_of(arrays, sample_rates)
     n_seg, n_sets = len(arrays), len(sets)
-    todo = _score._pairs_checked(pairs, n_seg, n_sets, refs, "transcribe_clips_sweep_multipitch_frame_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "transcribe_clips_sweep_multipitch_frame_scores", refs)
     frame = np.zeros(len(todo), _frames.FRAME_COUNTS)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
-        local = {i: k for k, i in enumerate(ids)}
-        mine = [j for j, (s, _) in enumerate(todo) if s in local]
-        if not mine:
-            continue
-        got = infer_clips_multipitch_sweep_frame_score(model, [arrays[i] for i in ids], rate, sets, [refs[i] for i in ids],
-                                                       [(local[todo[j][0]], todo[j][1]) for j in mine], **tolerances)
-        for k, j in enumerate(mine):
-            rec = got[k]
-            if rec["status"] == 3:  # the clip's contour rows through the model once more, then both checkers
-                s, p = todo[j]
-                rows = model.predict_pcm(arrays[s], rate)["contour"]
-                rec = _on_the_host(rows, sets[p], refs[s], 3, tolerances)
-            frame[j] = rec
+
+    def run(ids, rate, local_pairs):
+        return infer_clips_multipitch_sweep_frame_score(model, [arrays[i] for i in ids], rate, sets, [refs[i] for i in ids],
+                                                        local_pairs, **tolerances)
+
+    for j, k, rate, got in _jobs.per_rate_swept(todo, rates, run):
+        rec = got[k]
+        if rec["status"] == 3:  # the clip's contour rows through the model once more, then both checkers
+            s, p = todo[j]
+            rows = model.predict_pcm(arrays[s], rate)["contour"]
+            rec = _on_the_host(rows, sets[p], refs[s], 3, tolerances)
+        frame[j] = rec
     return _result(frame, (n_sets, n_seg) if pairs is None else None)

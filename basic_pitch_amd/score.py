@@ -17,6 +17,7 @@ import numpy as np
 from . import _native
 from . import clips as _clips
 from . import events as _events
+from . import jobs as _jobs
 from . import note_creation as _notes
 from . import sweep as _sweep
 
@@ -62,9 +63,8 @@ def refs_table(refs: Sequence[Any]) -> Tuple[np.ndarray, np.ndarray]:
     """Per segment a sequence of (start_s, end_s, pitch_midi) or an (n, 3) array -> (ref_offsets, the `bp_ref_note` records
     of all segments as one (N, 3) float64 array)."""
     parts = [np.asarray(r, np.float64).reshape(-1, 3) for r in refs]
-    offs = np.concatenate([[0], np.cumsum([len(p) for p in parts])]).astype(np.int64)
     flat = np.ascontiguousarray(np.concatenate(parts) if parts else np.zeros((0, 3)), np.float64)
-    return offs, flat
+    return _jobs.offsets_of([len(p) for p in parts]), flat
 
 
 def events_array(events: Any):
@@ -123,19 +123,13 @@ def _call(model: Any, what: str, fixed: tuple, params: Sequence[Any], pairs: Opt
     """`what(*fixed, n_sets, sets, n_decodes, decodes, ref_offsets, refs, score_params, scores, status)` -> `COUNTS` per decode."""
     lib = bind(model._lib)
     sets = _sweep.sets_array(params)
-    n = len(pairs) if pairs is not None else len(params) * n_segments
-    tab = _sweep.decode_table(pairs) if pairs is not None else None
+    block, n = _jobs.decodes_block(sets, len(params), pairs, n_segments)
     scores = np.zeros((max(1, n), 4), np.int32)
     status = np.zeros(max(1, n), np.int32)
-    rc = getattr(lib, what)(*fixed, len(params), C.addressof(sets), n, C.addressof(tab) if tab is not None else None,
-                            ref_offs.ctypes.data_as(_pi64), flat.ctypes.data if len(flat) else None, C.addressof(prm),
-                            scores.ctypes.data, status.ctypes.data)
+    rc = getattr(lib, what)(*fixed, *block, ref_offs.ctypes.data_as(_pi64), flat.ctypes.data if len(flat) else None,
+                            C.addressof(prm), scores.ctypes.data, status.ctypes.data)
     _native.check(lib, model._handle, rc, what)
-    out = np.zeros(n, COUNTS)
-    for i, name in enumerate(("n_ref", "n_est", "matched_onset", "matched_offset")):
-        out[name] = scores[:n, i]
-    out["status"] = status[:n]
-    return out
+    return _jobs.records(COUNTS, scores, status, n)
 
 
 def note_events_sweep_score(model: Any, row_offsets: Sequence[int], note: Any, onset: Any, contour: Any, mem_kind: int,
@@ -143,9 +137,8 @@ def note_events_sweep_score(model: Any, row_offsets: Sequence[int], note: Any, o
                             **tolerances: Any) -> np.ndarray:
     """One `bp_note_events_sweep_score` call (the maps as for `sweep.note_events_sweep`): `COUNTS` per decode, as the device
     left them — a decode with a non-zero status has {n_ref, 0, 0, 0}."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
     ref_offs, flat = refs_table(refs)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), note, onset, contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (note, onset, contour), mem_kind)
     return _call(model, "bp_note_events_sweep_score", fixed, params, pairs, len(offs) - 1, ref_offs, flat, score_params(**tolerances))
 
 
@@ -153,38 +146,24 @@ def infer_clips_events_sweep_score(model: Any, arrays: Sequence[np.ndarray], sam
                                    refs: Sequence[Any], pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """One `bp_infer_clips_events_sweep_score` call for [n_frames, channels] arrays at one rate; returns as
     `note_events_sweep_score`, a decode's segment being a clip."""
-    tab = _clips.clip_table(arrays)
     ref_offs, flat = refs_table(refs)
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _call(model, "bp_infer_clips_events_sweep_score", fixed, params, pairs, len(arrays), ref_offs, flat,
-                 score_params(**tolerances))
+    return _call(model, "bp_infer_clips_events_sweep_score", _jobs.clips_source(model, arrays, sample_rate), params, pairs,
+                 len(arrays), ref_offs, flat, score_params(**tolerances))
 
 
 def _host_events_from_maps(out: Any, prm: Any) -> List["_notes.NoteEvent"]:
     """A segment's maps under one set by the host decoder (`bp_notes_decode`), on copies."""
     from . import inference as _inf
 
-    maps = [np.array(out[k].cpu().numpy() if _inf._is_torch_cuda(out[k]) else out[k], np.float32, order="C") for k, _ in _inf._MAPS]
-    T = int(maps[0].shape[0])
-    decoded = _notes._grow_and_call(_native.load_library().bp_notes_decode, tuple(m.ctypes.data for m in maps) + (T, C.byref(prm)),
-                                    T, "bp_notes_decode")
-    return _notes._note_events(*decoded, bool(prm.include_pitch_bends))
-
-
-def _pairs_checked(pairs: Optional[Sequence[Pair]], n_seg: int, n_sets: int, refs: Sequence[Any], what: str) -> List[Pair]:
-    if len(refs) != n_seg:
-        raise ValueError(f"{what}: {n_seg} segments but refs for {len(refs)}")
-    todo = list(pairs) if pairs is not None else _sweep.cross_product(n_sets, n_seg)
-    if any(not (0 <= s < n_seg and 0 <= p < n_sets) for s, p in todo):
-        raise ValueError(f"{what}: a pair names a segment outside 0..{n_seg - 1} or a set outside 0..{n_sets - 1}")
-    return todo
+    return _jobs.host_decode([np.array(out[k].cpu().numpy() if _inf._is_torch_cuda(out[k]) else out[k], np.float32, order="C")
+                              for k, _ in _inf._MAPS], prm)
 
 
 def sweep_note_scores(model: Any, outputs: Sequence[Any], params: Sequence[Any], refs: Sequence[Any],
                       pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """`Model.sweep_note_scores`."""
     n_seg, n_sets = len(outputs), len(params)
-    todo = _pairs_checked(pairs, n_seg, n_sets, refs, "sweep_note_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "sweep_note_scores", refs)
     counts = np.zeros(len(todo), COUNTS)
     if todo:
         offs, maps, ptr, mem_kind = _events.stack_maps(outputs, "sweep_note_scores")
@@ -202,29 +181,21 @@ def transcribe_clips_sweep_scores(model: Any, clips: Sequence[Any], sample_rates
                                   refs: Sequence[Any], pairs: Optional[Sequence[Pair]] = None, **tolerances: Any) -> np.ndarray:
     """`Model.transcribe_clips_sweep_scores`: the clips of each rate in one `bp_infer_clips_events_sweep_score` call."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    if isinstance(sample_rates, (int, np.integer)):
-        rates = [int(sample_rates)] * len(arrays)
-    else:
-        rates = [int(r) for r in sample_rates]
-        if len(rates) != len(arrays):
-            raise ValueError(f"{len(arrays)} clips but {len(rates)} sample rates")
+    rates = _jobs.rates_of(arrays, sample_rates)
     n_seg, n_sets = len(arrays), len(params)
-    todo = _pairs_checked(pairs, n_seg, n_sets, refs, "transcribe_clips_sweep_scores")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "transcribe_clips_sweep_scores", refs)
     counts = np.zeros(len(todo), COUNTS)
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
-        local = {i: k for k, i in enumerate(ids)}
-        mine = [j for j, (s, _) in enumerate(todo) if s in local]
-        if not mine:
-            continue
-        group = [arrays[i] for i in ids]
-        got = infer_clips_events_sweep_score(model, group, rate, params, [refs[i] for i in ids],
-                                             [(local[todo[j][0]], todo[j][1]) for j in mine], **tolerances)
-        for j, rec in zip(mine, got):
-            if rec["status"]:
-                s, p = todo[j]
-                host = score_note_events(_sweep._host_events(model, arrays[s], rate, params[p]), refs[s], **tolerances)
-                host["status"] = rec["status"]
-                rec = host
-            counts[j] = rec
+
+    def run(ids, rate, local_pairs):
+        return infer_clips_events_sweep_score(model, [arrays[i] for i in ids], rate, params, [refs[i] for i in ids], local_pairs,
+                                              **tolerances)
+
+    for j, k, rate, got in _jobs.per_rate_swept(todo, rates, run):
+        rec = got[k]
+        if rec["status"]:
+            s, p = todo[j]
+            host = score_note_events(_sweep._host_events(model, arrays[s], rate, params[p]), refs[s], **tolerances)
+            host["status"] = rec["status"]
+            rec = host
+        counts[j] = rec
     return counts if pairs is not None else counts.reshape(n_sets, n_seg)

@@ -19,7 +19,9 @@ import numpy as np
 from . import _native
 from . import clips as _clips
 from . import events as _events
+from . import jobs as _jobs
 from . import note_creation as _notes
+from .jobs import cross_product, decode_table  # noqa: F401  (the decodes of a sweep, shared with the score calls)
 
 _vp, _i64, _int = C.c_void_p, C.c_int64, C.c_int
 _pi64 = C.POINTER(C.c_int64)
@@ -40,19 +42,6 @@ Pair = Tuple[int, int]  # (segment, set)
 def bind(lib: C.CDLL) -> C.CDLL:
     """Declare the prototypes of include/basic_pitch_amd_sweep.h on a loaded library."""
     return _native.bind(lib, PROTOTYPES)
-
-
-def cross_product(n_sets: int, n_segments: int) -> List[Pair]:
-    """The decodes a call without a table runs, in its order: set-major, decode p * n_segments + i is (segment i, set p)."""
-    return [(i, p) for p in range(n_sets) for i in range(n_segments)]
-
-
-def decode_table(pairs: Sequence[Pair]):
-    """The `bp_sweep_decode` array of (segment, set) pairs."""
-    tab = (_native.bp_sweep_decode * max(1, len(pairs)))()
-    for j, (seg, p) in enumerate(pairs):
-        tab[j] = _native.bp_sweep_decode(int(seg), int(p), 0)
-    return tab
 
 
 def sets_array(params: Sequence[Any]):
@@ -99,11 +88,9 @@ def _call(model: Any, what: str, fixed: tuple, params: Sequence[Any], pairs: Opt
     bends, event_offsets, status per decode)."""
     lib = bind(model._lib)
     sets = sets_array(params)
-    n_decodes = len(pairs) if pairs is not None else len(params) * len(rows)
-    tab = decode_table(pairs) if pairs is not None else None
+    block, n_decodes = _jobs.decodes_block(sets, len(params), pairs, len(rows))
     total = sum(rows[s] for s, _ in pairs) if pairs is not None else len(params) * sum(rows)
-    fixed = fixed + (len(params), C.addressof(sets), n_decodes, C.addressof(tab) if tab is not None else None)
-    return _events._call(lib, model._handle, what, getattr(lib, what), fixed, n_decodes, int(total), room)
+    return _events._call(lib, model._handle, what, getattr(lib, what), fixed + block, n_decodes, int(total), room)
 
 
 def note_events_sweep(model: Any, row_offsets: Sequence[int], note: Any, onset: Any, contour: Any, mem_kind: int,
@@ -111,8 +98,7 @@ def note_events_sweep(model: Any, row_offsets: Sequence[int], note: Any, onset: 
     """One `bp_note_events_sweep` call: note / onset / contour are pointers (ints) to the maps of all segments, segment i at
     rows row_offsets[i]:row_offsets[i + 1]; `pairs` None is the cross product (`cross_product`).  Returns (events, bends,
     event_offsets, status per decode), decode j's events at event_offsets[j]:event_offsets[j + 1]."""
-    offs = np.ascontiguousarray(row_offsets, np.int64)
-    fixed = (model._handle, len(offs) - 1, offs.ctypes.data_as(_pi64), note, onset, contour, int(mem_kind))
+    fixed, offs = _jobs.maps_source(model, row_offsets, (note, onset, contour), mem_kind)
     return _call(model, "bp_note_events_sweep", fixed, params, pairs, np.diff(offs).tolist(), room)
 
 
@@ -120,10 +106,8 @@ def infer_clips_events_sweep(model: Any, arrays: Sequence[np.ndarray], sample_ra
                              pairs: Optional[Sequence[Pair]] = None, room: Optional[Tuple[int, int]] = None):
     """One `bp_infer_clips_events_sweep` call for [n_frames, channels] arrays at one rate; returns as `note_events_sweep`,
     a decode's segment being a clip."""
-    tab = _clips.clip_table(arrays)
     rows = np.diff(_clips.clips_row_offsets(model, arrays, sample_rate)).tolist()
-    fixed = (model._handle, len(arrays), tab, int(sample_rate), _native.BP_MEM_HOST)
-    return _call(model, "bp_infer_clips_events_sweep", fixed, params, pairs, rows, room)
+    return _call(model, "bp_infer_clips_events_sweep", _jobs.clips_source(model, arrays, sample_rate), params, pairs, rows, room)
 
 
 def sweep_note_events(model: Any, outputs: Sequence[Dict[str, Any]], params: Sequence[Any],
@@ -132,9 +116,7 @@ def sweep_note_events(model: Any, outputs: Sequence[Dict[str, Any]], params: Seq
     through one `bp_note_events_sweep` call.  Without `pairs`: result[set][segment] = (events | None, status); with `pairs`,
     a list of (segment, set): one such tuple per pair.  events is None where the status is 1 or 2."""
     n_seg, n_sets = len(outputs), len(params)
-    todo = list(pairs) if pairs is not None else cross_product(n_sets, n_seg)
-    if any(not (0 <= s < n_seg and 0 <= p < n_sets) for s, p in todo):
-        raise ValueError(f"sweep_note_events: a pair names a segment outside 0..{n_seg - 1} or a set outside 0..{n_sets - 1}")
+    todo = _jobs.pairs_checked(pairs, n_seg, n_sets, "sweep_note_events")
     flat: List[Tuple[Optional[List[Any]], int]] = []
     if todo:
         offs, maps, ptr, mem_kind = _events.stack_maps(outputs, "sweep_note_events")
@@ -150,11 +132,8 @@ def sweep_note_events(model: Any, outputs: Sequence[Dict[str, Any]], params: Seq
 def _host_events(model: Any, a: np.ndarray, rate: int, prm: Any) -> List["_notes.NoteEvent"]:
     """A clip under one set by the route that takes every input: the model, then the host decoder on its maps."""
     out = model.predict_pcm_raw(a, _clips.FORMATS[a.dtype], a.shape[0], a.shape[1], rate)
-    maps = [np.require(out[k], np.float32, ["C", "W"] if k != "contour" else ["C"]) for k in ("note", "onset", "contour")]
-    T = int(maps[0].shape[0])
-    decoded = _notes._grow_and_call(_native.load_library().bp_notes_decode, tuple(m.ctypes.data for m in maps) + (T, C.byref(prm)),
-                                    T, "bp_notes_decode")
-    return _notes._note_events(*decoded, bool(prm.include_pitch_bends))
+    return _jobs.host_decode([np.require(out[k], np.float32, ["C", "W"] if k != "contour" else ["C"])
+                              for k in ("note", "onset", "contour")], prm)
 
 
 def transcribe_clips_sweep(model: Any, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], params: Sequence[Any]
@@ -164,17 +143,11 @@ def transcribe_clips_sweep(model: Any, clips: Sequence[Any], sample_rates: Union
     finished for that clip and set alone by the model and the host decoder, as `transcribe_clips(decode="device")` finishes
     such clips: the result is always complete."""
     arrays = [_clips.as_clip(c, i) for i, c in enumerate(clips)]
-    if isinstance(sample_rates, (int, np.integer)):
-        rates = [int(sample_rates)] * len(arrays)
-    else:
-        rates = [int(r) for r in sample_rates]
-        if len(rates) != len(arrays):
-            raise ValueError(f"{len(arrays)} clips but {len(rates)} sample rates")
+    rates = _jobs.rates_of(arrays, sample_rates)
     results: List[List[Any]] = [[None] * len(arrays) for _ in params]
     if not params:
         return results
-    for rate in dict.fromkeys(rates):  # by first appearance
-        ids = [i for i, r in enumerate(rates) if r == rate]
+    for rate, ids in _jobs.rate_groups(rates):
         group = [arrays[i] for i in ids]
         events, bends, ev_offs, status = infer_clips_events_sweep(model, group, rate, params)
         for j, (k, p) in enumerate(cross_product(len(params), len(ids))):
