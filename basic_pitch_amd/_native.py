@@ -99,7 +99,9 @@ class bp_launch_plan_out(C.Structure):
         "rim_ring", "conv2_slots", "conv2_launches", "conv2_windows", "conv2_first_windows", "conv2_first_groups",
         "conv2_first_slabs", "conv2_first_slab_rows", "conv2_first_grid", "conv2_last_windows", "conv2_last_groups",
         "conv2_last_slabs", "conv2_last_slab_rows", "conv2_last_grid", "note_grid", "note_grid_cap", "note_prio", "note_aligned",
-        "note_share_spans_pairs", "onset_grid", "onset_grid_cap", "onset_prio", "onset_aligned", "onset_share_spans_pairs")]
+        "note_share_spans_pairs", "onset_grid", "onset_grid_cap", "onset_prio", "onset_aligned", "onset_share_spans_pairs",
+        "conv2_fused", "fused_cols", "fused_seam_rows", "fused_term_rows", "fused_window_floats", "finish_slabs",
+        "finish_slab_rows", "finish_grid")]
 
 
 class bp_note_params(C.Structure):

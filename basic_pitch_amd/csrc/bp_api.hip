@@ -135,6 +135,18 @@ static void launch_rim(bp_handle h, const uint32_t* zp, float* c1, int n, bool w
     launch_contour_conv1_rim_march(zp, h->d_d1_wrimm, h->d_d1_bias.as<float>(), c1, n, h->n_cu, wlo, s);
 }
 
+// conv2 inside the interior march (the default of the 309-bin path): the march leaves partial sums of conv2 instead of c1,
+// in the exact-f32 path's c1 plane (idle here; launch_plan.h kCfWin), and contour_conv2_finish_kernel takes the place of the
+// projection kernel.  The extended mode keeps the unfused pair; A/B library only: BP_CONV2=unfused (and valu, and
+// BP_CONV1=rounds, whose kernels need c1) select it for the default mode.
+static bool contour_fused(bp_handle h) {
+  static const bool unfused = [] {
+    const char* e = ab_env("BP_CONV2");
+    return e && (std::strcmp(e, "unfused") == 0 || std::strcmp(e, "valu") == 0);
+  }();
+  return !h->ext && !unfused && contour_conv1_use_march();
+}
+
 // The interior of contour conv1: the vertical march.  A/B library only: the round-2 folded kernel on BP_CONV1=rounds.
 static void launch_conv1_interior(bp_handle h, const uint32_t* zp, float* c1, int n, bool wlo, hipStream_t s) {
 #ifdef BP_AB_KERNELS
@@ -143,7 +155,18 @@ static void launch_conv1_interior(bp_handle h, const uint32_t* zp, float* c1, in
     return;
   }
 #endif
-  launch_contour_conv1_march(zp, h->d_d1_wmarch, h->d_d1_bias.as<float>(), c1, n, h->n_cu, wlo, s);
+  if (contour_fused(h))
+    launch_contour_conv1_march(zp, h->d_d1_wmarch, h->d_d1_bias.as<float>(), h->c1, h->d_d2_w.as<float>(), n, h->n_cu, wlo, s);
+  else
+    launch_contour_conv1_march(zp, h->d_d1_wmarch, h->d_d1_bias.as<float>(), c1, nullptr, n, h->n_cu, wlo, s);
+}
+
+// contour conv2 of a handle: the finisher behind the fused march, or launch_conv2 on c1
+static void launch_conv2_of(bp_handle h, float* contour, int n, bool wlo, hipStream_t s) {
+  if (contour_fused(h))
+    launch_contour_conv2_finish(h->c1s, h->c1, h->d_d2_wproj, h->b_contour2, contour, n, h->n_cu, wlo, s);
+  else
+    launch_conv2(h->c1s, h->d_d2_w.as<float>(), h->d_d2_wproj, h->b_contour2, contour, n, h->n_cu, wlo, s);
 }
 
 // Offset of pyramid level k >= 1 in a window's fp32 pyramid row (the extended mode's level 1 is the 22.05 kHz signal itself).
@@ -237,7 +260,7 @@ int run_chunk(bp_handle h, const float* audio_dev, int n, float* note_dev, float
     launch_conv1_interior(h, zp, h->c1s, n, wlo, s);
     BP_DOM_END(BP_STAGE_CONTOUR_CONV1);
     BP_MARK(BP_STAGE_CONTOUR_CONV1);
-    launch_conv2(h->c1s, h->d_d2_w.as<float>(), h->d_d2_wproj, h->b_contour2, contour_dev, n, h->n_cu, wlo, s);
+    launch_conv2_of(h, contour_dev, n, wlo, s);
     BP_MARK(BP_STAGE_CONTOUR_CONV2);
     launch_note(contour_dev, h->d_note_wfrag, h->d_note_w16, h->d_note_wf32.as<float>(), note_dev, n, h->n_cu, wlo, s);
     BP_MARK(BP_STAGE_NOTE);
@@ -587,7 +610,7 @@ int bp_run_stage(bp_handle h, int stage, const bp_stage_buffers* bf, int64_t n_w
         } else {
           launch_rim(h, bf->zp, h->c1s, n, wlo, s);
           launch_conv1_interior(h, bf->zp, h->c1s, n, wlo, s);
-          launch_conv2(h->c1s, h->d_d2_w.as<float>(), h->d_d2_wproj, h->b_contour2, bf->contour, n, h->n_cu, wlo, s);
+          launch_conv2_of(h, bf->contour, n, wlo, s);
         }
       }
       break;
@@ -649,6 +672,14 @@ int bp_launch_plan(int64_t n_windows, int n_cu, unsigned flags, bp_launch_plan_o
     if (w0 == 0) std::memcpy(&out->conv2_last_windows, dst, 5 * sizeof(int32_t));
     out->conv2_launches += 1;
     out->conv2_windows += l.n;
+  }
+  // conv2 in the march's epilogue (the 309-bin path's default) and its finisher
+  out->conv2_fused = !ext;
+  if (!ext) {
+    const Conv2FinishLaunch l = conv2_finish_launch(n, n_cu);
+    out->fused_cols = kCfCols, out->fused_seam_rows = kCfPrefRows, out->fused_term_rows = kCfTermRows;
+    out->fused_window_floats = kCfWin;
+    out->finish_slabs = l.n_slabs, out->finish_slab_rows = l.slab_rows, out->finish_grid = l.grid;
   }
   // note and onset marches
   out->note_grid = march_grid(n * kN16Strips, kN16MinFrames, kN16Waves, kN16Occ, n_cu);

@@ -68,8 +68,9 @@ void launch_zpack_partials(const float* lp, const float* scratch, int n_partials
 
 // contour conv1: conv_contour_march.hip (interior), conv_contour_rim_march.hip and conv_contour_rim.hip (rim)
 bool contour_conv1_use_march();
-void launch_contour_conv1_march(const uint32_t* zp, const void* wfrag, const float* bias, float* c1, int n_windows, int n_cu,
-                                bool weights_have_lo, hipStream_t stream);
+// (w2 = conv2's taps [5][5][8]: conv2 in the march's epilogue, c1 = the partial sums of launch_plan.h; nullptr: relu(conv1))
+void launch_contour_conv1_march(const uint32_t* zp, const void* wfrag, const float* bias, float* c1, const float* w2,
+                                int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
 void launch_contour_conv1_rim(const uint32_t* zp, const void* afrag, const float* bias, float* c1, int n_windows, int n_cu,
                               bool weights_have_lo, bool ext, hipStream_t stream);
 void launch_contour_conv1_rim_march(const uint32_t* zp, const void* afrag, const float* bias, float* c1, int n_windows, int n_cu,
@@ -77,6 +78,9 @@ void launch_contour_conv1_rim_march(const uint32_t* zp, const void* afrag, const
 // conv_contour2.hip
 void launch_contour_conv2_proj(const float* c1, const void* wfrag, float bias, float* contour, int n_windows, int n_cu,
                                bool weights_have_lo, hipStream_t stream);
+// behind the fused march: partial sums + the rim's c1 (c1s) -> contour
+void launch_contour_conv2_finish(const float* c1s, float* part, const void* wfrag, float bias, float* contour,
+                                 int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream);
 // note_march16.hip, onset_march16.hip
 void launch_note_march16(const float* contour, const void* wfrag, const float* wf32, float* note, int n_windows, int n_cu,
                          bool weights_have_lo, hipStream_t stream);

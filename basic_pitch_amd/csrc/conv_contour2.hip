@@ -2,7 +2,10 @@
 // nn.py:105-119), c1 -> contour.  conv1 leaves relu(conv1) channel-last in HBM (conv_contour_march.hip + conv_contour_rim.hip);
 // the layer is HBM-paced: 1.48 MB read, 181,632 B written per window, 18.2 MFLOP.
 //
-// Round 6: `contour_conv2_proj_kernel` (the default) puts the channel contraction on the matrix cores; the round-2 vector
+// The default of the 309-bin path no longer has this layer as a pass over c1: the interior march projects its own c1 rows on
+// the taps (conv_contour_march.hip, FUSE) and `contour_conv2_seam_kernel` + `contour_conv2_finish_kernel` below add what it
+// leaves, with the rim's share.  The extended 44.1 kHz mode and the A/B library (BP_CONV2=unfused) keep the kernels that read c1:
+// Round 6: `contour_conv2_proj_kernel` (their default) puts the channel contraction on the matrix cores; the round-2 vector
 // kernel `contour_conv2_kernel` (200 FMAs per output behind scalar tap loads: 58 % of its wave cycles in s_waitcnt, neither at
 // the HBM rate nor at the vector rate) stays in the A/B library behind BP_CONV2=valu.
 #include <stdlib.h>
@@ -236,6 +239,250 @@ void launch_contour_conv2_proj(const float* c1, const void* wfrag, float bias, f
     else
       hipLaunchKernelGGL(contour_conv2_proj_kernel<false>, dim3((unsigned)l.grid), dim3(256), 0, stream, p);
   }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// conv2 behind the FUSED march (conv_contour_march.hip, FUSE): the march has projected its own c1 rows on the taps and left
+// partial sums (launch_plan.h: 36 columns per (window, strip, output row), prefixes and single terms where a chunk of frames
+// was cut); c1 itself exists only for the rim (bins 0 .. 19, 244 .. 263: conv_contour_rim_march.hip into c1s).  Per output
+//   bins 24 .. 239:             the strip's sum + the neighbour strip's halo column where the bin is one of a strip's outer two
+//   bins 0 .. 23, 240 .. 263:   the same (bins 18 .. 23, 240 .. 245) + the rim pixels' taps, projected here as the kernel
+//                               above projects them: one 32-column tile per side, the same chains down the frames
+// then bias and sigmoid.  A work item is (window, slab of frames) and belongs to one wave: lanes 0 .. 53 own four interior
+// bins each (16-byte loads and stores), the upper half's lanes the 24 + 24 rim-side bins; three rows of loads in flight.
+// The seam rows' sums are made in between by contour_conv2_seam_kernel — per class prefix + term + term, dt ascending, then
+// the classes as the march adds them (cf_seam_col), written where the march writes a finished row — so that an output is the
+// same sequence of additions whatever the number of chunks, and the finisher knows no seams.
+// Roofline: HBM; per window and row 1,008 B of partial sums + 1,280 B of rim c1 read, 1,056 B written.
+struct Conv2FinishParams {
+  const float* c1s;     // [n][172][kC1Row][8]: the rim columns are read
+  const float* part;    // [n][kCfWin]
+  const uint4* wfrag;   // pack_conv2_proj
+  float bias;
+  float* out;           // [n][172][264]
+  int n_windows;
+  int slab_rows;
+  int n_slabs;
+};
+
+// One class of seam row R: the prefix of the chunk in front of the cut, then the terms dt = 4 - R .. 4 of the chunk behind it —
+// every load in front of the first addition.  `on` = 0: the column has no such part (the loads are made, of element 0).
+template <int R>
+__device__ __forceinline__ float cf_seam_class(const float* rec, int cls, int el, bool on) {
+  const float* q = rec + 32 * cls + (on ? el : 0);
+  float tv[R + 2];
+  tv[0] = q[R * kCfClassRow];
+#pragma unroll
+  for (int i = 0; i <= R; ++i) tv[1 + i] = q[(kCfPrefRows + cf_term_index(R, 4 - R + i)) * kCfClassRow];
+  float v = tv[0];
+#pragma unroll
+  for (int i = 0; i <= R; ++i) v += tv[1 + i];
+  return on ? v : 0.0f;
+}
+// Column col of seam row R as the march adds a finished row's classes: (class 2 of the position in front + class 1) + class 0
+// of the position behind; the columns in front of the strip (32, 33) are class 0 of position 0 alone, those behind it (34,
+// 35) class 2 of position 15.  No branch on the column: the three classes' loads are in flight together.
+template <int R>
+__device__ __forceinline__ float cf_seam_col(const float* rec, int col) {
+  const bool own = col < 32;
+  const float left = cf_seam_class<R>(rec, 2, own ? col - 2 : col - 4, own ? col >= 2 : col >= 34);
+  const float mid = cf_seam_class<R>(rec, 1, col, own);
+  const float right = cf_seam_class<R>(rec, 0, own ? col + 2 : col - 32, own ? col < 30 : col < 34);
+  return (left + mid) + right;
+}
+
+// a workgroup per (window, seam, seam row): threads (strip, column), 252 of 256; 12 of a window's 172 rows at 4 chunks
+__global__ __launch_bounds__(256) void contour_conv2_seam_kernel(float* part, int n_windows, int chunks) {
+  const int i = (int)blockIdx.x;  // < n_windows * (chunks - 1) * 4
+  const int r = i % kCfPrefRows, ci = 1 + (i / kCfPrefRows) % (chunks - 1), b = i / (kCfPrefRows * (chunks - 1));
+  const int strip = threadIdx.x / kCfCols, col = threadIdx.x - strip * kCfCols;
+  if (b >= n_windows || strip >= kCmStrips) return;
+  float* pw = part + (int64_t)b * kCfWin;
+  const float* rec = pw + cf_seam_offset(ci, strip);
+  const int t = cf_chunk_t0(ci, chunks) - 2 + r;  // 3 <= t <= 167: a chunk has at least five frames
+  float v;
+  switch (r) {  // workgroup-uniform
+    case 0: v = cf_seam_col<0>(rec, col); break;
+    case 1: v = cf_seam_col<1>(rec, col); break;
+    case 2: v = cf_seam_col<2>(rec, col); break;
+    default: v = cf_seam_col<3>(rec, col); break;
+  }
+  pw[(strip * kFrames + t) * kCfCols + col] = v;
+}
+
+template <bool WLO>
+__global__ __launch_bounds__(256, kCfOcc) void contour_conv2_finish_kernel(Conv2FinishParams p) {
+  const int lane = threadIdx.x & 63;
+  const int n = lane & 31, h = lane >> 5;
+  // whole windows per XCD, as above
+  const int lblock = (gridDim.x % 8 == 0) ? ((int)blockIdx.x % 8) * ((int)gridDim.x / 8) + (int)blockIdx.x / 8 : (int)blockIdx.x;
+  const int64_t wg = (int64_t)lblock * 4 + wave_id();  // wave-uniform work item; whole waves only, no barrier
+  if (wg >= (int64_t)p.n_windows * p.n_slabs) return;
+  const int b = (int)(wg / p.n_slabs), slab = (int)(wg - (int64_t)b * p.n_slabs);
+  const int ta = slab * p.slab_rows;
+  const int tb = ta + p.slab_rows < kFrames ? ta + p.slab_rows : kFrames;
+
+  const f16x8 a1 = __builtin_bit_cast(f16x8, p.wfrag[lane]);
+  const f16x8 a2 = __builtin_bit_cast(f16x8, WLO ? p.wfrag[64 + lane] : uint4{0u, 0u, 0u, 0u});
+  const float* c1w = p.c1s + (int64_t)b * kC1Win;
+  const float* partw = p.part + (int64_t)b * kCfWin;
+  float* outw = p.out + (int64_t)b * kPlaneC;
+
+  // the rim tiles: padded columns 0 .. 31 (bins -2 .. 29) and 236 .. 267 (bins 234 .. 265); only the rim's own pixels are
+  // read, every other column of the tile is zero here whatever c1s holds
+  const int src_off[2] = {n * 8 + 4 * h, (236 + n) * 8 + 4 * h};
+  const bool ld_ok[2] = {n >= 2 && n <= 21, n >= 10 && n <= 29};
+  // the upper half's lanes store bins 0 .. 23 (tile 0) and 240 .. 263 (tile 1); the march's share of bins 18 .. 23 / 240 .. 245:
+  // strip 0's columns in front (32, 33) and own columns 0 .. 3, strip 6's own columns 28 .. 31 and the columns behind (34, 35)
+  const int obin[2] = {n - 2, 234 + n};
+  const bool st_ok[2] = {h == 1 && n >= 2 && n <= 25, h == 1 && n >= 6 && n <= 29};
+  const int rcol[2] = {obin[0] >= 20 ? obin[0] - 20 : (obin[0] >= 18 ? obin[0] + 14 : -1),
+                       obin[1] <= 243 ? obin[1] - 212 : (obin[1] <= 245 ? obin[1] - 210 : -1)};
+  const bool r_ok[2] = {st_ok[0] && rcol[0] >= 0, st_ok[1] && rcol[1] >= 0};
+  // lanes 0 .. 53: bins 24 + 4 lane .. + 3 of one strip; the strip's first four columns take the columns behind the strip
+  // in front, its last four the columns in front of the strip behind
+  const bool i_ok = lane < 54;
+  const int ibin = 24 + 4 * (i_ok ? lane : 0);
+  const int istrip = (ibin - 20) >> 5, icol = (ibin - 20) & 31;
+  const int hal = !i_ok ? 0 : (icol == 0 ? 1 : (icol == 28 ? 2 : 0));
+  const int hstrip = hal == 1 ? istrip - 1 : istrip + 1;  // hal == 2: istrip <= 5 (the last lane's columns are 24 .. 27 of strip 6)
+  const float* imain = partw + (int64_t)istrip * kFrames * kCfCols + icol;
+  const float* ihalo = partw + (int64_t)(hal ? hstrip : istrip) * kFrames * kCfCols + 32;
+
+  const int xhalf4 = (lane ^ 32) * 4;
+  int sh4[4];  // ds_bpermute addresses of the frequency taps df = 0, 1, 3, 4: lane n + df - 2 of half 1
+#pragma unroll
+  for (int k = 0; k < 4; ++k) sh4[k] = (32 + ((n + (k < 2 ? k - 2 : k - 1)) & 31)) * 4;
+  const float bias_s = p.bias * kLoScale;
+  const float sig_k = -1.44269504088896341f * kLoUnscale;
+  const float hmask = h ? 1.0f : 0.0f;
+
+  float X0[2][5], X1[2][5], IN[2][5];
+#pragma unroll
+  for (int tl = 0; tl < 2; ++tl)
+#pragma unroll
+    for (int df = 0; df < 5; ++df) X0[tl][df] = X1[tl][df] = IN[tl][df] = 0.0f;
+
+  constexpr int kRowFloats = kC1Row * 8;
+  auto load = [&](int rho, int tl) {  // rows outside the window are never used: a row of it
+    const int rc = rho < 0 ? 0 : (rho > kFrames - 1 ? kFrames - 1 : rho);
+    float4 v = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (ld_ok[tl]) v = *reinterpret_cast<const float4*>(c1w + (int64_t)rc * kRowFloats + src_off[tl]);
+    return v;
+  };
+  struct PartRow {
+    float4 m, hq;
+    float r0, r1;
+  };
+  auto loadp = [&](int t) {  // the partial sums of output row t
+    const int tc = t < 0 ? 0 : (t > kFrames - 1 ? kFrames - 1 : t);
+    PartRow q = {{0.0f, 0.0f, 0.0f, 0.0f}, {0.0f, 0.0f, 0.0f, 0.0f}, 0.0f, 0.0f};
+    if (i_ok) q.m = *reinterpret_cast<const float4*>(imain + tc * kCfCols);
+    if (hal) q.hq = *reinterpret_cast<const float4*>(ihalo + tc * kCfCols);
+    if (r_ok[0]) q.r0 = partw[tc * kCfCols + rcol[0]];  // strip 0
+    if (r_ok[1]) q.r1 = partw[((kCmStrips - 1) * kFrames + tc) * kCfCols + rcol[1]];
+    return q;
+  };
+  const int r_first = ta - 2, r_last = tb + 1;
+  // three rows in flight ahead of the one in work, in three register sets whose roles rotate with the row (as above);
+  // set k holds c1 row rho + 3 and the partial sums of output row rho + 1 when row rho is in work
+  float4 buf[3][2];
+  PartRow pbuf[3];
+#pragma unroll
+  for (int k = 0; k < 3; ++k) {
+#pragma unroll
+    for (int tl = 0; tl < 2; ++tl) buf[k][tl] = load(r_first + k, tl);
+    pbuf[k] = loadp(r_first + k - 2);
+  }
+
+  auto step = [&](auto PH, int rho) {
+    constexpr int ph = decltype(PH)::v;
+    const int t = rho - 2;                // the output row half 1 completes now
+    const bool emit = t >= ta && t < tb;  // wave-uniform
+    float V[2][5];
+    if (rho >= 0 && rho < kFrames) {  // wave-uniform
+      f16x8 bq[2];
+#pragma unroll
+      for (int tl = 0; tl < 2; ++tl) {
+        uint32_t h01, l01, h23, l23;
+        split_f16x2(f32x2{buf[ph][tl].x, buf[ph][tl].y}, h01, l01);
+        split_f16x2(f32x2{buf[ph][tl].z, buf[ph][tl].w}, h23, l23);
+        bq[tl] = __builtin_bit_cast(f16x8, uint4{h01, h23, l01, l23});
+        buf[ph][tl] = load(rho + 3, tl);  // this set's next row
+      }
+#pragma unroll
+      for (int tl = 0; tl < 2; ++tl) {
+        const f32x16 zero16 = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+        f32x16 P = __builtin_amdgcn_mfma_f32_32x32x16_f16(a1, bq[tl], zero16, 0, 0, 0);
+        if (WLO) P = __builtin_amdgcn_mfma_f32_32x32x16_f16(a2, bq[tl], P, 0, 0, 0);
+#pragma unroll
+        for (int df = 0; df < 5; ++df) {
+          const float x2 = X1[tl][df] + P[10 + df];
+          const float x1 = X0[tl][df] + P[5 + df];
+          X0[tl][df] = __builtin_fmaf(IN[tl][df], hmask, P[df]);
+          X1[tl][df] = x1;
+          V[tl][df] = x1;  // half 1: all five frame taps of output row rho - 2
+          IN[tl][df] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(xhalf4, __builtin_bit_cast(int, x2)));
+        }
+      }
+    } else {  // a row outside the window is "same" padding: P = 0
+#pragma unroll
+      for (int tl = 0; tl < 2; ++tl) {
+        buf[ph][tl] = load(rho + 3, tl);
+#pragma unroll
+        for (int df = 0; df < 5; ++df) {
+          const float x2 = X1[tl][df];
+          V[tl][df] = X1[tl][df] = X0[tl][df];
+          X0[tl][df] = IN[tl][df] * hmask;
+          IN[tl][df] = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(xhalf4, __builtin_bit_cast(int, x2)));
+        }
+      }
+    }
+    PartRow q = pbuf[ph];
+    pbuf[ph] = loadp(rho + 1);  // this set's next row
+    if (emit) {
+      // the rim's share of the tile's bins: out[n] = sum_df V[df][n + df - 2] (a tile's two outer lanes on either side take
+      // wrapped neighbours: they are not stored)
+      float y[2] = {V[0][2], V[1][2]};
+#pragma unroll
+      for (int k = 0; k < 4; ++k) {
+        const int df = k < 2 ? k : k + 1;
+        y[0] += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(sh4[k], __builtin_bit_cast(int, V[0][df])));
+        y[1] += __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(sh4[k], __builtin_bit_cast(int, V[1][df])));
+      }
+      if (hal == 1) q.m.x += q.hq.z, q.m.y += q.hq.w;
+      if (hal == 2) q.m.z += q.hq.x, q.m.w += q.hq.y;
+      float* orow = outw + (int64_t)t * kFreqC;  // wave-uniform base
+      auto sig = [&](float v) { return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f((v + bias_s) * sig_k)); };
+      if (i_ok) *reinterpret_cast<float4*>(orow + ibin) = float4{sig(q.m.x), sig(q.m.y), sig(q.m.z), sig(q.m.w)};
+      if (st_ok[0]) orow[obin[0]] = sig(q.r0 + y[0]);
+      if (st_ok[1]) orow[obin[1]] = sig(q.r1 + y[1]);
+    }
+  };
+  int rho = r_first;
+#pragma unroll 1
+  for (;;) {
+    step(P2Phase<0>{}, rho);
+    if (++rho > r_last) break;
+    step(P2Phase<1>{}, rho);
+    if (++rho > r_last) break;
+    step(P2Phase<2>{}, rho);
+    if (++rho > r_last) break;
+  }
+}
+
+void launch_contour_conv2_finish(const float* c1s, float* part, const void* wfrag, float bias, float* contour,
+                                 int n_windows, int n_cu, bool weights_have_lo, hipStream_t stream) {
+  if (n_windows <= 0) return;
+  const int chunks = contour_march_chunks(n_windows, n_cu);  // the march's cut of this batch
+  hipLaunchKernelGGL(contour_conv2_seam_kernel, dim3((unsigned)(n_windows * (chunks - 1) * kCfPrefRows)), dim3(256), 0, stream,
+                     part, n_windows, chunks);
+  const Conv2FinishLaunch l = conv2_finish_launch(n_windows, n_cu);
+  Conv2FinishParams p{c1s, part, static_cast<const uint4*>(wfrag), bias, contour, n_windows, l.slab_rows, l.n_slabs};
+  if (weights_have_lo)
+    hipLaunchKernelGGL(contour_conv2_finish_kernel<true>, dim3((unsigned)l.grid), dim3(256), 0, stream, p);
+  else
+    hipLaunchKernelGGL(contour_conv2_finish_kernel<false>, dim3((unsigned)l.grid), dim3(256), 0, stream, p);
 }
 
 #ifdef BP_AB_KERNELS  // the round-2 vector kernel (BP_CONV2=valu)

@@ -4,8 +4,9 @@
 // handle-free test hook of include/basic_pitch_amd.h) fills its struct from the same functions, so that
 // tests/test_launch_plan_cpu.py can enumerate every regime of every batch size without a device and
 // tests/test_gpu_launch_regimes.py can run the sizes on either side of every change.  march_grid and march_prio
-// (march_common.h) are the note and the onset march's part of it.  Host code only: nothing here reaches a kernel's text
-// except as the constants the kernels read before (tools/kernel_digest.py).
+// (march_common.h) are the note and the onset march's part of it.  Host code only — nothing here reaches a kernel's text
+// except as the constants the kernels read before (tools/kernel_digest.py) — but for the layout of the fused contour
+// march's partial sums (kCf*, cf_*), which its writer, its readers and the plan share as __host__ __device__ functions.
 #pragma once
 #include "march_common.h"
 
@@ -69,6 +70,71 @@ inline int contour_march_grid(int n_tasks, int n_cu) {
   int grid = (n_tasks + kCmWaves - 1) / kCmWaves;
   if (grid > 2 * n_cu) grid = 2 * n_cu;
   return grid;
+}
+
+// ---- conv_contour_march.hip with conv2 in its epilogue, conv_contour2.hip contour_conv2_finish_kernel: what the fused
+// march hands on instead of c1 (these functions are the kernels' text too: __host__ __device__).
+// A position's c1 pixel pair is projected on (frame tap dt) x (output bin offset ob = -2 .. 3 relative to bin 2 p); the
+// three offsets that meet in output bin 2 q + e — ob = e + 2 from position q - 1, e from q, e - 2 from q + 1 — are the
+// classes 2, 1, 0.  A class sums its five frame taps in the order dt = 0 .. 4; an output column is then
+// (class 2 of q - 1 + class 1 of q) + class 0 of q + 1.  Per (window, strip) and output row the march stores kCfCols columns:
+// 32 of its own bins, then the two bins in front of the strip (class 0 of its first position) and the two behind it
+// (class 2 of its last).  Where a chunk of frames begins at T0 > 0, the output rows T0 - 2 .. T0 + 1 have terms on both sides
+// of the cut: the chunk in front stores what it has summed (kCfPrefRows prefixes), the chunk behind stores its terms one by
+// one (kCfTermRows, cf_term_index), per class, and the finisher adds prefix + term + term in the same order — whatever the
+// number of chunks, every output is the same sequence of additions.
+constexpr int kCfCols = 36;
+constexpr int kCfClassRow = 3 * 32;   // a seam row: [class][position n][e]
+constexpr int kCfPrefRows = 4;        // output rows T0 - 2 .. T0 + 1
+constexpr int kCfTermRows = 10;       // 1 + 2 + 3 + 4 terms of those rows
+constexpr int kCfSeam = (kCfPrefRows + kCfTermRows) * kCfClassRow;            // floats per (seam, strip)
+constexpr int kCfMain = kCmStrips * kFrames * kCfCols;                        // floats per window: [strip][row][col]
+constexpr int kCfWin = kCfMain + (kCmMaxChunks - 1) * kCmStrips * kCfSeam;    // + [seam][strip] records
+static_assert(kCfWin <= 8 * kPlaneC, "the partial sums of a window fit the exact-f32 path's c1 plane, which the default path leaves idle");
+__host__ __device__ constexpr int cf_chunk_t0(int ci, int chunks) { return (ci * kFrames) / chunks; }
+// the chunk that holds frame x
+__host__ __device__ constexpr int cf_chunk_of(int x, int chunks) { return ((x + 1) * chunks - 1) / kFrames; }
+// output row t lies on a seam (rows T0 - 2 .. T0 + 1 of a chunk ci >= 1): the chunk, and the row's index r = t - (T0 - 2)
+__host__ __device__ inline bool cf_seam_of_row(int t, int chunks, int& ci, int& r) {
+  const int x = t + 2 < kFrames - 1 ? t + 2 : kFrames - 1;
+  ci = cf_chunk_of(x, chunks);
+  const int T0 = cf_chunk_t0(ci, chunks);
+  r = t - (T0 - 2);
+  return ci >= 1 && T0 >= t - 1;
+}
+// seam row r holds the terms dt = 4 - r .. 4 of the chunk behind the cut
+__host__ __device__ constexpr int cf_term_index(int r, int dt) { return r * (r + 1) / 2 + dt - (4 - r); }
+__host__ __device__ constexpr int64_t cf_seam_offset(int ci, int strip) {
+  return (int64_t)kCfMain + (int64_t)((ci - 1) * kCmStrips + strip) * kCfSeam;
+}
+// The projection's row 16 block + 4 gq + r is C register r of lane group gq = e + 2 s; slot = 4 block + r:
+//   s = 0: slots 0 .. 4 = class 0 (ob = e - 2), dt = slot;  slots 5 .. 7 = class 1 (ob = e), dt = slot - 5
+//   s = 1: slots 0 .. 4 = class 2 (ob = e + 2), dt = slot;  slots 5, 6 = class 1, dt = slot - 2;  slot 7 unused
+__host__ __device__ inline bool cf_slot(int gq, int slot, int& dt, int& ob) {
+  const int e = gq & 1, s = gq >> 1;
+  if (slot < 5) {
+    dt = slot, ob = s ? e + 2 : e - 2;
+    return true;
+  }
+  dt = s ? slot - 2 : slot - 5, ob = e;
+  return !(s && slot == 7);
+}
+// The finisher: a wave per (window, slab of frames), within the resident waves.  Two waves per SIMD (184 VGPRs: three rows
+// of c1 AND of partial sums in flight per wave; at three waves per SIMD with the partial sums one row ahead the launch took
+// 53.7 us in the trace against 44 - 45)
+constexpr int kCfOcc = 2;
+constexpr int kCfMaxSlabs = 16;
+struct Conv2FinishLaunch {
+  int n_slabs, slab_rows, grid;
+};
+inline Conv2FinishLaunch conv2_finish_launch(int n_windows, int n_cu) {
+  Conv2FinishLaunch l;
+  int n_slabs = (int)(((int64_t)n_cu * 4 * kCfOcc) / n_windows);
+  n_slabs = n_slabs < 1 ? 1 : (n_slabs > kCfMaxSlabs ? kCfMaxSlabs : n_slabs);
+  l.slab_rows = (kFrames + n_slabs - 1) / n_slabs;
+  l.n_slabs = (kFrames + l.slab_rows - 1) / l.slab_rows;
+  l.grid = (int)(((int64_t)n_windows * l.n_slabs + 3) / 4);
+  return l;
 }
 
 // ---- conv_contour_rim_march.hip

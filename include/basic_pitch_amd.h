@@ -432,6 +432,15 @@ typedef struct bp_launch_plan_out {
   int32_t onset_prio;
   int32_t onset_aligned;
   int32_t onset_share_spans_pairs;
+  int32_t conv2_fused;               /* 1: conv2 in the conv1 march's epilogue + the finisher (the 309-bin path); conv2_* above
+                                        describe the projection kernel, which the extended mode launches */
+  int32_t fused_cols;                /* partial-sum columns per (window, strip, output row): 32 own + 2 in front + 2 behind */
+  int32_t fused_seam_rows;           /* output rows T0 - 2 .. of a chunk cut at T0 that have terms on both sides */
+  int32_t fused_term_rows;           /* single terms the chunk behind a cut stores for them */
+  int32_t fused_window_floats;       /* partial sums + seam records of a window */
+  int32_t finish_slabs;              /* finisher: frame slabs per window, frames per slab, workgroups of four waves */
+  int32_t finish_slab_rows;
+  int32_t finish_grid;
 } bp_launch_plan_out;
 int bp_launch_plan(int64_t n_windows, int n_cu, unsigned flags, bp_launch_plan_out* out);
 
