@@ -399,6 +399,42 @@ class bp_chord_summary(C.Structure):
     ]
 
 
+class bp_sync_params(C.Structure):
+    """The parameters of the synchronisation of two segments (include/basic_pitch_amd_sync.h); `bp_sync_params_default` fills
+    them in."""
+
+    _fields_ = [
+        ("threshold_q", C.c_int32),
+        ("min_pitch", C.c_int32),
+        ("max_pitch", C.c_int32),
+        ("hop", C.c_int32),
+        ("band", C.c_int32),
+        ("reserved", C.c_int32 * 3),
+    ]
+
+
+class bp_sync_pair(C.Structure):
+    """One pair of segment indices of a synchronisation job (include/basic_pitch_amd_sync.h)."""
+
+    _fields_ = [
+        ("a", C.c_int32),
+        ("b", C.c_int32),
+    ]
+
+
+class bp_sync_summary(C.Structure):
+    """The synchronisation of one pair (include/basic_pitch_amd_sync.h): status 1 a NaN, 2 a segment without rows."""
+
+    _fields_ = [
+        ("status", C.c_int32),
+        ("units_a", C.c_int32),
+        ("units_b", C.c_int32),
+        ("n_path", C.c_int32),
+        ("path_first", C.c_int64),
+        ("total", C.c_int64),
+    ]
+
+
 class bp_stream_update(C.Structure):
     """One stream of `bp_streams_candidates` (include/basic_pitch_amd_update.h): `stream` and `held_rows` in, the rest out."""
 
@@ -589,6 +625,13 @@ CHORD_SYMBOLS = [
     "bp_chord_rows",
     "bp_chords_from_maps",
     "bp_infer_clips_chords",
+]
+# every symbol include/basic_pitch_amd_sync.h declares (bound in basic_pitch_amd/sync.py)
+SYNC_SYMBOLS = [
+    "bp_sync_params_default",
+    "bp_sync_rows",
+    "bp_sync_from_maps",
+    "bp_infer_clips_sync",
 ]
 # every symbol include/basic_pitch_amd_flac_clips.h declares (bound in basic_pitch_amd/flac_clips.py)
 FLAC_CLIPS_SYMBOLS = [

@@ -28,6 +28,7 @@ MELODY_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_melody.h
 ALIGN_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_align.h")
 BEAT_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_beat.h")
 CHORD_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_chord.h")
+SYNC_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_sync.h")
 FLAC_CLIPS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_flac_clips.h")
 CONTAINERS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_containers.h")
 STREAM_EVENTS_HEADER = os.path.join(PKG_DIR, "..", "include", "basic_pitch_amd_stream_events.h")
@@ -43,6 +44,7 @@ SOURCES = [
     "clips_align.hip",
     "clips_beat.hip",
     "clips_chord.hip",
+    "clips_sync.hip",
     "stream_api.hip",
     "weight_pack.hip",
     "cqt_pyramid.hip",
@@ -68,6 +70,7 @@ SOURCES = [
     "align.hip",
     "beat.hip",
     "chord.hip",
+    "sync.hip",
     "audio_ingest.hip",
     "flac_device.hip",
     "flac_clips.hip",
@@ -80,6 +83,7 @@ SOURCES = [
     "align_host.cpp",
     "beat_host.cpp",
     "chord_host.cpp",
+    "sync_host.cpp",
     "flac_decode.cpp",
     "wav_file.cpp",
     "pcm_file.cpp",
@@ -98,7 +102,7 @@ AB_SOURCES = [
 ]
 AB_LIB_PATH = os.path.join(LIB_DIR, "libbasicpitch_amd_ab.so")
 # every header a source includes: editing one rebuilds all objects
-HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "clips_job.h", "weight_pack.h", "march_common.h", "launch_plan.h", "cqt_planes.h", "flac_kernels.h", "file_host.h", "adpcm_host.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER, SWEEP_HEADER, SCORE_HEADER, FRAME_SCORE_HEADER, MULTIPITCH_HEADER, MELODY_HEADER, ALIGN_HEADER, BEAT_HEADER, CHORD_HEADER, STREAM_EVENTS_HEADER, FLAC_CLIPS_HEADER, CONTAINERS_HEADER, ADPCM_HEADER]
+HEADERS = [os.path.join(CSRC, h) for h in ("bp_common.h", "device_buffer.h", "bp_kernels.h", "bp_context.h", "clips_job.h", "weight_pack.h", "march_common.h", "launch_plan.h", "cqt_planes.h", "flac_kernels.h", "file_host.h", "adpcm_host.h")] + [HEADER, LIVE_HEADER, ROLLING_HEADER, CLIPS_HEADER, UPDATE_HEADER, EVENTS_HEADER, SWEEP_HEADER, SCORE_HEADER, FRAME_SCORE_HEADER, MULTIPITCH_HEADER, MELODY_HEADER, ALIGN_HEADER, BEAT_HEADER, CHORD_HEADER, SYNC_HEADER, STREAM_EVENTS_HEADER, FLAC_CLIPS_HEADER, CONTAINERS_HEADER, ADPCM_HEADER]
 
 
 def _sources(ab: bool = False) -> List[str]:

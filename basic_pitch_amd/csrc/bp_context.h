@@ -184,6 +184,20 @@ struct bp_context {
   Buffer<uint8_t> ch_unit_labels;
   Buffer<int64_t> ch_out;
   bp::PinnedBuffer<int64_t> ch_home;
+  // two recordings against each other (bp_sync_from_maps, bp_infer_clips_sync, clips_sync.hip), all grow-only, scratch of one
+  // call and grown by those calls alone: the device copy of a note map given in host memory, the tables of the segments that
+  // a pair names and of the pairs, a NaN flag a segment, the features (16 bytes a unit), the predecessors in the skewed order
+  // of the recurrence (at most bp::kSyncMaxPredBytes), the walked path (4 bytes an entry), the summaries [pairs] with the
+  // path (8 bytes an entry) behind them, and the page-locked block those come home in
+  Buffer<float> sy_note;
+  Buffer<bp::SyncSeg> sy_segs;
+  Buffer<bp::SyncPair> sy_pairs;
+  Buffer<uint32_t> sy_nan;
+  Buffer<uint4> sy_feat;
+  Buffer<uint8_t> sy_pred;
+  Buffer<uint32_t> sy_walk;
+  Buffer<int64_t> sy_out;
+  bp::PinnedBuffer<int64_t> sy_home;
   // streaming sessions (stream_api.hip).  Scratch of one step (grow-only; nothing of a stream survives a call in them):
   // the PCM of the step's chunks, their mono form, the rows on their way to host buffers, the step's window segments.  The
   // streams' own state is theirs.  The filters are kept per input rate: streams of one rate share a table.

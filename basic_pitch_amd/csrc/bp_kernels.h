@@ -431,6 +431,50 @@ struct ChordSeg {
 hipError_t launch_chords(const float* note, const ChordParams* params, const ChordSeg* segs, int64_t n_segs, int64_t n_blocks,
                          int64_t n_rows, int64_t n_pool_units, const int32_t* bounds, uint16_t* chroma, uint32_t* pool, int64_t* acc,
                          void* records, uint8_t* unit_labels, uint8_t* labels, ChordSummary* summaries, hipStream_t s);
+// sync.hip: two recordings against each other (include/basic_pitch_amd_sync.h).  Segment c of segs is rows
+// [row_first, row_first + rows) of note, rows > 0, and units [unit_first, unit_first + n_units) of the n_units of feat, 16
+// bytes a unit (unit_first ascending).  Pair p of pairs is segments a and b of segs, pred_bytes bytes of pred from pred_first
+// (16-byte aligned) and n_a + n_b - 1 entries of walk and of path from path_first; summaries[p]: the header's record.  max_n,
+// max_m: the most units of an a and of a b; they choose the launch variant (sync_plan), which the host needs for the pairs'
+// pred_bytes.  note is read by 4-byte loads: it needs no alignment beyond a float's.
+constexpr int kSyncMaxUnits = 8192, kSyncMaxHop = 64, kSyncTraceTile = 64;  // BP_SYNC_*
+constexpr int kSyncSmallLanes = 256, kSyncLanes = 1024, kSyncSmallRows = 2048;
+constexpr int64_t kSyncMaxPredBytes = 1ll << 28;  // BP_SYNC_MAX_PRED_BYTES
+struct SyncParams {  // bp_sync_params
+  int32_t threshold_q, min_pitch, max_pitch, hop, band, reserved[3];
+};
+struct SyncSummary {  // bp_sync_summary
+  int32_t status, units_a, units_b, n_path;
+  int64_t path_first, total;
+};
+struct SyncSeg {
+  int64_t row_first, rows, unit_first, n_units;
+};
+struct SyncPair {
+  int32_t a, b;
+  int64_t pred_first, path_first;
+};
+// the variant for a job whose longest b has max_m units: lanes of the workgroup, columns a lane, bytes of predecessors a lane
+// and step
+struct SyncPlan {
+  int lanes, cols, pred_bytes;
+};
+inline SyncPlan sync_plan(int max_m) {
+  if (max_m <= kSyncSmallLanes) return SyncPlan{kSyncSmallLanes, 1, 1};
+  if (max_m <= 2 * kSyncSmallLanes) return SyncPlan{kSyncSmallLanes, 2, 1};
+  if (max_m <= 4 * kSyncSmallLanes) return SyncPlan{kSyncSmallLanes, 4, 1};
+  if (max_m <= 8 * kSyncSmallLanes) return SyncPlan{kSyncSmallLanes, 8, 2};
+  if (max_m <= 4 * kSyncLanes) return SyncPlan{kSyncLanes, 4, 1};
+  return SyncPlan{kSyncLanes, 8, 2};
+}
+// the bytes of predecessors of a pair of n x m units under a plan: (n + lanes in use - 1) steps of lanes in use
+inline int64_t sync_pred_bytes(const SyncPlan& plan, int64_t n, int64_t m) {
+  const int64_t used = (m + plan.cols - 1) / plan.cols;
+  return ((n + used - 1) * used * plan.pred_bytes + 15) / 16 * 16;
+}
+hipError_t launch_sync(const float* note, const SyncParams& params, const SyncSeg* segs, int64_t n_segs, int64_t n_units,
+                       const SyncPair* pairs, int64_t n_pairs, int max_n, int max_m, uint32_t* nan_flags, void* feat, uint8_t* pred,
+                       uint32_t* walk, int32_t* path, SyncSummary* summaries, hipStream_t s);
 // frames [t0, t1) of linear device maps join a stats record (launch_note_candidates' second step on its own)
 void launch_note_fold(const float* note, const float* onset, int64_t t0, int64_t t1, int infer, void* stats, hipStream_t s);
 // The rows a stream retains (stream_api.hip): `ring` is [cap] note, [cap] onset, [cap] contour with absolute row r at slot

@@ -698,6 +698,33 @@ class Model:
 
         return _ch.transcribe_clips_chords(self, clips, sample_rates, params, bounds)
 
+    # -- two recordings against each other (basic_pitch_amd/sync.py) -------------------------------
+    def sync(self, outputs_a: Sequence[Any], outputs_b: Sequence[Any], **params: Any) -> "List[Any]":
+        """The i-th of `outputs_a` synchronised with the i-th of `outputs_b` (the dicts `predict` / `run_inference` return,
+        numpy arrays or CUDA tensors of one kind; their "note" maps alone are read) in ONE call (`bp_sync_from_maps`): a chroma
+        per row pooled over units of `hop` frames, one feature byte a class, and the best monotone path over the units of both
+        by a dynamic time warp in exact integers on the device.  `params`: the fields of `bp_sync_params` (threshold_q 307,
+        hop 4, band 0 by default).  Returns one `sync.Sync` per pair: status, total, path, and `map_times` / `transfer_notes`
+        to move times and notes from one recording's time base to the other's."""
+        from . import sync as _sy
+
+        return _sy.sync(self, outputs_a, outputs_b, **params)
+
+    def sync_pairs(self, outputs: Sequence[Any], pairs: Sequence[Any], **params: Any) -> "List[Any]":
+        """The same for a table of (a, b) indices into `outputs`: one against many, or a segment against itself."""
+        from . import sync as _sy
+
+        return _sy.sync_pairs(self, outputs, pairs, **params)
+
+    def transcribe_clips_sync(self, clips: Sequence[Any], sample_rates: Union[int, Sequence[int]], pairs: Sequence[Any],
+                              **params: Any) -> "List[Any]":
+        """The same behind the model, a segment being a clip ([n_frames, channels] arrays, each with its sample rate): the
+        clips of a rate go through the model once (`bp_infer_clips_sync`), and 32 bytes per pair and 8 per path entry come
+        home.  A pair whose clips differ in sample rate is a ValueError: use `sync` on `predict_pcm` outputs."""
+        from . import sync as _sy
+
+        return _sy.transcribe_clips_sync(self, clips, sample_rates, pairs, **params)
+
     # -- streaming (basic_pitch_amd/streaming.py) --------------------------------------------------
     def open_stream(self, sample_rate: int, channels: int = 1, fmt: int = _native.BP_PCM_F32):
         """A streaming session on this model for interleaved PCM of `fmt` (a BP_PCM_* code) at `sample_rate`:

@@ -1,7 +1,7 @@
 """What the analyses over many segments or clips share on the host side: stacking the maps of a job, the leading arguments
 of the two standard sources (maps the caller holds, PCM clips behind the model), the sample rates of a job and the loops over
 its rate groups, the decodes of a sweep, and the record arrays the score calls bring home.  `events`, `sweep`, `score`,
-`frame_score`, `multipitch`, `melody`, `align`, `beat` and `chord` call into it; a new analysis starts from it and adds its
+`frame_score`, `multipitch`, `melody`, `align`, `beat`, `chord` and `sync` call into it; a new analysis starts from it and adds its
 parameters, its result class and its one native-call wrapper.
 """
 from __future__ import annotations
