@@ -216,39 +216,51 @@ def forward(
 
 
 # ---- windowing / stitching (inference.py) ---------------------------------------------------------
-def window_track(samples: np.ndarray) -> Tuple[np.ndarray, int]:
-    """inference.py:222-244 + 194-219: prepend 3840 zeros, hop 36164, zero-pad the tail."""
+def window_track(
+    samples: np.ndarray, win: int = AUDIO_N_SAMPLES, hop: int = HOP_SIZE, lead: int = OVERLAP_LEN // 2
+) -> Tuple[np.ndarray, int]:
+    """inference.py:222-244 + 194-219: prepend 3840 zeros, hop 36164, zero-pad the tail.
+    win / hop / lead: another handle's geometry (the extended mode: 87688 / 72328 / 7680)."""
     samples = np.asarray(samples, dtype=np.float32)
     original_length = samples.shape[0]
-    padded = np.concatenate([np.zeros(OVERLAP_LEN // 2, dtype=np.float32), samples])
+    padded = np.concatenate([np.zeros(lead, dtype=np.float32), samples])
     wins = []
-    for i in range(0, padded.shape[0], HOP_SIZE):
-        w = padded[i : i + AUDIO_N_SAMPLES]
-        if len(w) < AUDIO_N_SAMPLES:
-            w = np.pad(w, [[0, AUDIO_N_SAMPLES - len(w)]])
+    for i in range(0, padded.shape[0], hop):
+        w = padded[i : i + win]
+        if len(w) < win:
+            w = np.pad(w, [[0, win - len(w)]])
         wins.append(w)
     return np.stack(wins), original_length
 
 
-def unwrap_output(output: np.ndarray, audio_original_length: int) -> np.ndarray:
-    """inference.py:247-279."""
+def unwrap_output(
+    output: np.ndarray, audio_original_length: int, win: int = AUDIO_N_SAMPLES, hop: int = HOP_SIZE, lead: int = OVERLAP_LEN // 2
+) -> np.ndarray:
+    """inference.py:247-279.  win / hop / lead: another handle's geometry.  A window stays 172 frames of which 15 on each
+    side are dropped, so the lead-in must be the 15 / 172 of it that the reference's is: win = hop + 2 * lead and
+    lead : win = 3840 : 43844."""
+    assert win == hop + 2 * lead and lead * AUDIO_N_SAMPLES == win * (OVERLAP_LEN // 2), (win, hop, lead)
     n_olap = N_OVERLAPPING_FRAMES // 2
     output = output[:, n_olap:-n_olap, :]
     flat = output.reshape(output.shape[0] * output.shape[1], output.shape[2])
-    n_expected_windows = audio_original_length / HOP_SIZE
+    n_expected_windows = audio_original_length / hop
     n_frames_per_window = (2 * 86) - N_OVERLAPPING_FRAMES
     return flat[: int(n_expected_windows * n_frames_per_window), :]
 
 
-def run_track(samples: np.ndarray, W=None, dtype=np.float64, batch: int = 8) -> Dict[str, np.ndarray]:
-    """inference.py:282-330 run_inference() on already-decoded 22.05 kHz mono samples."""
-    wins, n = window_track(samples)
+def run_track(
+    samples: np.ndarray, W=None, dtype=np.float64, batch: int = 8, win: int = AUDIO_N_SAMPLES, hop: int = HOP_SIZE,
+    lead: int = OVERLAP_LEN // 2,
+) -> Dict[str, np.ndarray]:
+    """inference.py:282-330 run_inference() on already-decoded 22.05 kHz mono samples; with the extended geometry
+    (win = 87688, hop = 72328, lead = 7680) on 44.1 kHz samples through the extended CQT."""
+    wins, n = window_track(samples, win, hop, lead)
     outs = {"note": [], "onset": [], "contour": []}
     for i in range(0, len(wins), batch):
-        r = forward(wins[i : i + batch], W, dtype)
+        r = forward(wins[i : i + batch], W, dtype, ext=win == EXT_AUDIO_N_SAMPLES)
         for k in outs:
             outs[k].append(r[k])
-    return {k: unwrap_output(np.concatenate(v), n) for k, v in outs.items()}
+    return {k: unwrap_output(np.concatenate(v), n, win, hop, lead) for k, v in outs.items()}
 
 
 # ---- the C restatement (oracle/bp_oracle.c), used as a cross-check and as bench.py's CPU baseline -----------

@@ -189,7 +189,9 @@ def run_stream(s, data, sizes, after_push=None):
 
 # ---- Part A 1: Model.resample to 44.1 kHz against the float64 restatement of the filter design ----------------------------
 RESAMPLE_CASES = ((88200, 1, 40001), (176400, 1, 30000), (22050, 2, 30000), (11025, 2, 5000), (48000, 2, 48001), (96000, 1, 20000),
-                  (8000, 1, 999), (16000, 3, 4000), (32000, 1, 1), (44101, 1, 600))
+                  (8000, 1, 999), (16000, 3, 4000), (32000, 1, 1), (44101, 1, 600),
+                  # 8 : 1 (the tiled kernel, taps in memory) and 16 : 1 (the one-thread-per-output kernel)
+                  (352800, 1, 40000), (705600, 1, 40000))
 
 
 def _noise_and_sine(sr, ch, n, seed=3):
@@ -250,10 +252,9 @@ def test_the_extended_path_from_48_khz_against_the_oracle(ext, nat, weights):
     assert L == int(np.ceil(n * 44100 / 48000))
     n_win = -(-(L + lead) // hop)
     assert n_win == 3
-    pad = np.concatenate([np.zeros(lead, np.float32), y, np.zeros(n_win * hop + win, np.float32)])
-    wins = np.stack([pad[w * hop : w * hop + win] for w in range(n_win)])
-    T = int(L / hop * 142)
-    unwrap = lambda r: {k: np.asarray(r[k])[:, 15:157].reshape(n_win * 142, -1)[:T] for k in MAPS}  # noqa: E731
+    wins, _ = O.window_track(y, win=win, hop=hop, lead=lead)
+    assert wins.shape == (n_win, win)
+    unwrap = lambda r: {k: O.unwrap_output(np.asarray(r[k]), L, win=win, hop=hop, lead=lead) for k in MAPS}  # noqa: E731
     r64 = unwrap(O.forward(wins, weights, np.float64, ext=True))
     r32 = unwrap(O.forward(wins, weights, np.float32, ext=True))
     for k in MAPS:

@@ -340,13 +340,13 @@ def test_extended_cqt_44k_mode(weights):
     n = 72328 * 3 + 1234
     y = rng.uniform(-0.5, 0.5, n).astype(np.float32)
     tr = m.predict_track(y)
-    n_win = -(-(n + 7680) // 72328)
-    pad = np.concatenate([np.zeros(7680, np.float32), y, np.zeros(n_win * 72328 + 87688, np.float32)])
-    wins = np.stack([pad[w * 72328 : w * 72328 + 87688] for w in range(n_win)])
+    ext_geometry = dict(win=87688, hop=72328, lead=7680)
+    wins, _ = O.window_track(y, **ext_geometry)
+    assert wins.shape == (-(-(n + 7680) // 72328), 87688)
     pw = m.predict(wins)
-    T = int(n / 72328 * 142)
     for k in tr:
-        ref = pw[k][:, 15:157].reshape(n_win * 142, -1)[:T]
+        ref = O.unwrap_output(pw[k], n, **ext_geometry)
+        assert ref.shape[0] == int(n / 72328 * 142)
         assert tr[k].shape == ref.shape and np.array_equal(tr[k], ref), k
     # 48 kHz stereo PCM is resampled to the handle's 44.1 kHz on the device
     pcm = rng.uniform(-0.5, 0.5, (48000, 2)).astype(np.float32)
@@ -751,7 +751,10 @@ def test_device_audio_ingest(weights):
     m = Model(max_windows=8)
     rng = np.random.default_rng(3)
     for sr, ch, n in ((44100, 2, 150001), (48000, 1, 9600), (16000, 3, 4000), (8000, 1, 999), (22050, 2, 50000),
-                      (32000, 1, 1), (11025, 2, 30000), (88200, 1, 40000), (10004, 1, 600)):
+                      (32000, 1, 1), (11025, 2, 30000), (88200, 1, 40000), (10004, 1, 600),
+                      # 8 : 1: 1,541 taps, more than the tiled kernel keeps in LDS; 16 : 1: a block of 256 outputs reaches more
+                      # inputs than its tile holds, the product library launches the one-thread-per-output kernel
+                      (176400, 1, 40000), (352800, 1, 40000)):
         pcm = rng.uniform(-1, 1, (n, ch)).astype(np.float32)
         t = np.arange(n) / sr
         pcm[:, 0] += 0.5 * np.sin(2 * np.pi * 440.0 * t).astype(np.float32)
@@ -877,9 +880,10 @@ def _ab_env(**switches):
 
 def test_resample_kernels_agree_bit_for_bit(tmp_path):
     """The resampler's three kernels — one thread per output, the LDS-tiled one, the 2 : 1 register-window one — add the
-    same products in the same order: identical float32 signals, at the signal's edges too (a 2 : 1 length that is not a
-    multiple of the block's 1024 outputs, a signal shorter than the filter).  One process per kernel: the product library
-    (automatic choice) and the A/B library with BP_RESAMPLE=plain / tiled."""
+    same products in the same order: identical float32 signals, at the signal's edges too (2 : 1 lengths that are not a
+    multiple of the block's 256 x 16 = 4096 outputs and one that is, a signal shorter than the filter), and at 8 : 1 and
+    16 : 1, where the automatic choice is the tiled kernel with its taps in memory and the one-thread-per-output kernel.
+    One process per kernel: the product library (automatic choice) and the A/B library with BP_RESAMPLE=plain / tiled."""
     import subprocess
     import sys
 

@@ -109,7 +109,8 @@ def test_host_resampler_equals_soxr_restatement():
     assert np.abs(H[f <= fp * 11025] - 1.0).max() <= 2e-6
     assert 20 * np.log10(H[f >= 11025].max()) <= -120.0
     rng = np.random.default_rng(0)
-    for sr, n in ((44100, 30001), (48000, 2000), (16000, 1500), (8000, 999), (32000, 1), (11025, 700), (96000, 4000)):
+    for sr, n in ((44100, 30001), (48000, 2000), (16000, 1500), (8000, 999), (32000, 1), (11025, 700), (96000, 4000),
+                  (176400, 8000), (352800, 16000)):  # 8 : 1 and 16 : 1 (1,541 and 3,077 taps)
         x = rng.uniform(-1, 1, n).astype(np.float32)
         a, b = audio.resample(x, sr), S.resample(x, sr)
         assert a.shape == b.shape == (int(np.ceil(n * 22050 / sr)),), sr
